@@ -17,6 +17,8 @@ Order of a run: build the workload -> device pre-warm (`--prewarm-s`, default 1.
 `prewarm_steps`; 0 switches it off) -> W warm-up steps -> barrier + synchronize -> EXACTLY K timed steps -> barrier + synchronize.
 The pre-warm exists because a GPU that was idle a moment ago runs its first milliseconds below its sustained state: `--steps 20
 --warmup 5` straight after start-up read 347 M env-steps/s on a build that sustains 385 M (same command with the pre-warm: 383-385 M).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs); the pre-warm then runs on a twin of
+the workload, so that two builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -71,6 +73,10 @@ def parse():
                     "learner-group shapes on the same box and report them as compact sub-records under \"also\" (auto: only for the default headline workload -- "
                     "train mode, 65 536 envs, one GPU)")
     ap.add_argument("--also-which", default=None, help="comma-separated subset of the sub-record names (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most "
+                         "64 MB in all (an array larger than its share: a fixed, seeded sample of its rows).  The pre-warm then runs on a twin of "
+                         "the workload, so that the dumped step depends on the arguments alone")
     return ap.parse_args()
 
 
@@ -440,6 +446,52 @@ def cpu_baseline(n_envs, mode, updates, scale=1.0):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def workload_outputs(wl, torch):
+    """What a caller of the timed path holds after its last step: the env batch's next state and row index, the step's rewards where the
+    path returns them, and the learners' networks with their last losses (train: one learner; group: one row per learner).  Device arrays
+    stay torch tensors here, so that a large one is sampled before it is copied."""
+    env = wl.env
+    out = {"state": env.state, "idx": env.idx.astype("float64")}
+    if isinstance(getattr(wl, "rew32", None), torch.Tensor):
+        out["reward"] = wl.rew32
+    if getattr(wl, "agent", None) is not None and wl.name == "train":
+        for k in ("actor", "critic", "actor_t", "critic_t", "losses"):
+            out[k] = getattr(wl.agent, k)
+    if wl.name == "group":
+        g = wl.group.flux_()                     # the Flux-order blocks are current again (the tiled form keeps layer 2 in its tiles)
+        for k in ("actor", "critic", "actor_t", "critic_t", "losses"):
+            off, n = g.layout[k]
+            out[k] = g.slab[:, off:off + n]
+    return out
+
+
+def dump_outputs(wl, torch, path):
+    """DIR/<name>.npy for every array of workload_outputs(); an array larger than DUMP_BYTES / (number of arrays) keeps a fixed, seeded
+    sample of its rows (sorted, the same for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = workload_outputs(wl, torch)
+    share = DUMP_BYTES // len(arrays)
+    torch.cuda.synchronize()
+    for name, a in arrays.items():
+        dt = np.float64 if a.dtype in (np.float64, torch.float64) else np.float32
+        itemsize = np.dtype(dt).itemsize
+        size = a.numel() if isinstance(a, torch.Tensor) else a.size
+        if a.ndim > 1 and size // a.shape[0] * itemsize > share:        # one row alone is over the share: sample its elements
+            a = a.reshape(-1)
+        rows = a.shape[0]
+        per_row = size // rows * itemsize
+        if size * itemsize > share:
+            sel = np.sort(np.random.default_rng(0).choice(rows, share // per_row, replace=False))
+            a = a[torch.from_numpy(sel).to(a.device)] if isinstance(a, torch.Tensor) else a[sel]
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=dt))
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` with no rendezvous in the environment: this process becomes the launcher.  It has made NO
     GPU call (torch is not even imported here) and starts N fresh children of this same script, one rank per GPU, with
@@ -523,24 +575,27 @@ def main():
         if train_mod is None and mode == "train":
             raise SystemExit("train mode requested but the DDPG path is not built")
         mode = "train" if train_mod is not None else "env"
-    if mode == "group":
-        wl = importlib.import_module(PKG + ".group").GroupWorkload(S, torch, args.envs, args.learners, seed=1231 + 1000 * rank, mixed=args.mixed, form=args.group_form, window=args.group_window)
-    elif mode == "policy":
-        wl = PolicyWorkload(S, torch, args.envs, seed=123 + rank)
-    elif mode == "train":
-        wl = train_mod.TrainWorkload(S, torch, args.envs, seed=1231 + rank, updates=args.updates, dist=dist, overlap=args.overlap or False, loop=args.loop, mixed=args.mixed, scaled_replay=args.scaled_replay,
-                                     hidden=tuple(int(x) for x in args.hidden.lower().split("x")))
-    else:
-        wl = EnvWorkload(S, torch, args.envs, seed=123 + rank)
+    def make_workload(dist):
+        if mode == "group":
+            return importlib.import_module(PKG + ".group").GroupWorkload(S, torch, args.envs, args.learners, seed=1231 + 1000 * rank, mixed=args.mixed, form=args.group_form, window=args.group_window)
+        if mode == "policy":
+            return PolicyWorkload(S, torch, args.envs, seed=123 + rank)
+        if mode == "train":
+            return train_mod.TrainWorkload(S, torch, args.envs, seed=1231 + rank, updates=args.updates, dist=dist, overlap=args.overlap or False, loop=args.loop, mixed=args.mixed, scaled_replay=args.scaled_replay,
+                                           hidden=tuple(int(x) for x in args.hidden.lower().split("x")))
+        return EnvWorkload(S, torch, args.envs, seed=123 + rank)
 
-    def run_steps(k):
+    wl = make_workload(dist)
+
+    def run_steps(k, w=None):
         # the train workload enqueues k vector steps with ONE foreign call (shems_train_steps: the hour loop of episode! in native code);
         # the other workloads are one call per launch
-        many = getattr(wl, "steps", None)
+        w = wl if w is None else w
+        many = getattr(w, "steps", None)
         if many is not None:
             return many(k)
         for _ in range(k):
-            wl.step()
+            w.step()
 
     def barrier():
         torch.cuda.synchronize()
@@ -552,11 +607,14 @@ def main():
     # Device pre-warm (untimed, reported as prewarm_steps): a GPU that has been idle runs its first milliseconds well below the
     # sustained state (clock ramp, cold instruction / TLB / L2 state): 20 steps right after start-up measured 353 M env-steps/s where
     # the same build sustains 388 M.  The contract's W warm-up steps and K timed steps follow unchanged.  Ranks agree on the count.
+    # With --dump-outputs the pre-warm runs on a twin of the workload (same arguments, no gradient exchange), freed after the timed steps:
+    # a pre-warm of a wall-clock time takes a varying number of steps, and the dumped step must depend on the arguments alone.
     prewarm_steps = 0
     if args.prewarm_s > 0:
+        pw = make_workload(None) if args.dump_outputs else wl
         tp = time.perf_counter()
         while True:
-            run_steps(50)
+            run_steps(50, pw)
             prewarm_steps += 50
             torch.cuda.synchronize()
             more = time.perf_counter() - tp < args.prewarm_s
@@ -574,6 +632,20 @@ def main():
     dt = time.perf_counter() - t0
     wl.finish()
     t_gpu_section_end = time.perf_counter()
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(wl, torch, args.dump_outputs)
+        if args.prewarm_s > 0:
+            # the twin is freed only now: tearing it down between the pre-warm and the warm-up leaves the GPU idle long enough to lose
+            # the sustained clock the pre-warm exists for (measured: 11 % on ms_per_step at --steps 20 --warmup 5)
+            pw.finish()
+            if hasattr(pw, "close"):
+                pw.close()
+            pw.env.close()
+            pw = None
+            import gc
+            gc.collect()
+            torch.cuda.empty_cache()
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

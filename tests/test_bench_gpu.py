@@ -86,6 +86,44 @@ def test_bench_group_window_one():
     assert d["replay_window_envs_per_step"] == 1 and d["envs_per_learner"] == 32 and d["updates_per_sec"] > 1600
 
 
+def _dumped(path):
+    import numpy as np
+    files = sorted(path.glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    out = {f.stem: np.load(f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    return out
+
+
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float .npy files, 64 MB at most, the same bytes from two runs of the same
+    arguments (the pre-warm, a wall-clock time, runs on a twin of the workload); a larger output keeps a seeded sample of its rows."""
+    cmd = [sys.executable, "bench.py", "--steps", "16", "--warmup", "4", "--envs", "8192", "--no-cpu-baseline", "--prewarm-s", "0.2"]
+    runs = []
+    for k in range(2):
+        d = _run(cmd + ["--dump-outputs", str(tmp_path / f"train{k}")])
+        assert d["steps"] == 16 and d["ms_per_step"] > 0 and d["prewarm_steps"] >= 50
+        runs.append(_dumped(tmp_path / f"train{k}"))
+    a, b = runs
+    assert sorted(a) == ["actor", "actor_t", "critic", "critic_t", "idx", "losses", "reward", "state"]
+    assert a["state"].shape == (8192, 9) and a["reward"].shape == (8192,) and a["actor"].shape == (129002,)
+    for name in a:
+        assert a[name].tobytes() == b[name].tobytes(), name
+    # 400 learners x 32 households (the thesis-exact shape): 4 x 400 networks are over the budget, so rows (learners) are sampled
+    cmd = [sys.executable, "bench.py", "--mode", "group", "--learners", "400", "--envs", "12800", "--mixed", "--group-window", "1", "--steps", "4",
+           "--warmup", "1", "--no-cpu-baseline", "--prewarm-s", "0.1"]
+    runs = []
+    for k in range(2):
+        d = _run(cmd + ["--dump-outputs", str(tmp_path / f"group{k}")])
+        assert d["steps"] == 4 and d["learners"] == 400
+        runs.append(_dumped(tmp_path / f"group{k}"))
+    a, b = runs
+    assert sorted(a) == ["actor", "actor_t", "critic", "critic_t", "idx", "losses", "state"]
+    assert a["state"].shape == (12800, 9) and a["losses"].shape == (400, 2) and 0 < a["actor"].shape[0] < 400 and a["actor"].shape[1] == 129002
+    for name in a:
+        assert a[name].tobytes() == b[name].tobytes(), name
+
+
 def test_group_mode_shards_as_plain_replicas_over_ranks():
     """Learner groups shard over GPUs as plain replicas: every rank advances its own learners on its own env shard, no collective on the
     data path; `value` / `updates_per_sec` are whole-job aggregates.  Rehearsal form: two rank processes on device 0, gloo for the
