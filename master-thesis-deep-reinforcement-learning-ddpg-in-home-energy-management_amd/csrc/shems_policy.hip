@@ -1710,45 +1710,82 @@ static int launch_actg(const ActArgs &a, hipStream_t st)
 // k_act (SHEMS_ACT_FORM4 = 1: free-running waves, 0: shared W2 stream): 128-env tiles from 32 768 envs, 64-env tiles from 16 384, 32 below.
 static int act_form() { static const int f = []() { const char *e = getenv("SHEMS_ACT_FORM"); return e ? atoi(e) : -1; }(); return f; }
 static int act_form4() { static const int f = []() { const char *e = getenv("SHEMS_ACT_FORM4"); return e ? atoi(e) : 2; }(); return f; }
-// envs per workgroup tile (= per entry of block_reward) of the form that runs m envs
+// Every form a launch can run, and its profiler name.
+enum ActForm { kAct2, kAct440, kAct442, kAct240, kAct242, kAct140, kAct142, kAct143, kActg1422, kActg1423, kActg1813 };
+static const char *act_form_name(ActForm f)
+{
+    static const char *const names[] = {"shems::k_act2", "shems::k_act<4, 4, 0>", "shems::k_act<4, 4, 2>", "shems::k_act<2, 4, 0>",
+                                        "shems::k_act<2, 4, 2>", "shems::k_act<1, 4, 0>", "shems::k_act<1, 4, 2>", "shems::k_act<1, 4, 3>",
+                                        "shems::k_actg<1, 4, 2, 2>", "shems::k_actg<1, 4, 2, 3>", "shems::k_actg<1, 8, 1, 3>"};
+    return names[f];
+}
+static int act_form_tile_envs(ActForm f)
+{
+    switch (f) {
+    case kAct2: return 64;
+    case kAct440: case kAct442: return 128;
+    case kAct240: case kAct242: return 64;
+    default: return 32;
+    }
+}
+
+// THE decision: which form runs a launch of cnt envs.  tm_max: the learner group's tile limit (0: none); gcount: learners in the launch
+// (0 or 1: a single learner); w2t: a tiled learner group; want_sum: per-tile reward sums asked for.  dispatch_act launches what this
+// returns and the name functions report it, so the two cannot drift apart.
+static ActForm pick_act_form(int64_t cnt, int tm_max, int gcount, bool w2t, bool want_sum)
+{
+    const int form = act_form(), form4 = act_form4();
+    if (w2t) {                                                // tiled learner group: the free-running forms read W2 from the tiled regions
+        const int tmt = pick_tm(cnt, tm_max);
+        return tmt == 4 ? kAct442 : tmt == 2 ? kAct242 : kAct142;
+    }
+    if (form4 == 2 && form < 0 && cnt > 8192 && gcount <= 1) return kAct2;
+    if (form4 == 2 && form == 12 && (tm_max == 0 || tm_max >= 2)) return kAct2;    // A/B: the two-per-CU form (64-env tiles) at any size
+    const int tm = pick_tm(cnt, tm_max);
+    if (tm == 4) return form4 == 0 ? kAct440 : kAct442;
+    if (tm == 2) return form == 0 || form4 == 0 ? kAct240 : kAct242;
+    if (form == 0) return kAct140;
+    if (form == 2) return kAct142;
+    if (form == 3) return kAct143;
+    // 4 096 < envs <= 8 192 (round 4): the split form with a ring of TWO chunks -- 76.5 KB per workgroup, so the two halves of a tile's work
+    // are two independent workgroups resident on one CU (8 waves, two per SIMD, as the 8-wave form) without that form's coupling (its early
+    // waves wait at the barrier for the late ones): 23.1 against 23.8 us at 8 192 envs.  At <= 4 096 envs (one workgroup per CU) the
+    // shallower ring costs more than it wins (17.7 against 16.2 us): ring of three there.  Per-tile reward sums need ONE workgroup per tile.
+    // (a learner group whose env block admits only 32-env tiles can be large: beyond the split forms' exchange scratch the
+    // one-workgroup-per-tile form runs)
+    const bool split_fits = (cnt + 31) / 32 <= kSplitMaxTiles;
+    if ((form == 10 || (form < 0 && cnt > 128 * 32)) && !want_sum && split_fits) return kActg1422;
+    if (form == 8 || !split_fits || (form != 9 && (cnt > 128 * 32 || want_sum))) return kActg1813;
+    return kActg1423;
+}
+
+// envs per workgroup tile (= per entry of block_reward) of the form that runs m envs with per-tile reward sums
 // (learner groups keep k_act's 128-env tiles: with 32 weight sets in flight two co-resident workgroups of different learners cost more
 // in L2 than they win -- 151.9 against 145.7 us at 32 x 2 048 envs)
-static int act_tile_envs(int64_t m, bool grouped = false)
-{
-    if (act_form4() == 2 && ((act_form() < 0 && m > 8192 && !grouped) || act_form() == 12)) return 64;
-    return 32 * pick_tm(m);
-}
+static int act_tile_envs(int64_t m) { return act_form_tile_envs(pick_act_form(m, 0, 0, false, true)); }
 
 static int dispatch_act(const ActArgs &a, hipStream_t st)
 {
-    const int form = act_form(), form4 = act_form4();
 #ifdef SHEMS_STAMP_ACT
     const bool want_sum = false;                              // stamp builds: block_reward is the stamp buffer
 #else
     const bool want_sum = a.block_reward != nullptr;          // per-tile reward sums: a form whose one workgroup finishes the whole tile
 #endif
-    const int64_t cnt = a.m - a.m0;                           // envs of this launch (a range launch: every form writes the same bytes)
-    if (a.w2t) {                                              // tiled learner group: the free-running forms read W2 from the tiled regions
-        const int tmt = pick_tm(cnt, a.tm_max);
-        return tmt == 4 ? launch_act<4, 4, 2>(a, st) : tmt == 2 ? launch_act<2, 4, 2>(a, st) : launch_act<1, 4, 2>(a, st);
+    // envs of this launch a.m - a.m0 (a range launch: every form writes the same bytes)
+    switch (pick_act_form(a.m - a.m0, a.tm_max, a.gcount, a.w2t != nullptr, want_sum)) {
+    case kAct2: return launch_act2(a, st);
+    case kAct440: return launch_act<4, 4>(a, st);
+    case kAct442: return launch_act<4, 4, 2>(a, st);
+    case kAct240: return launch_act<2, 4>(a, st);
+    case kAct242: return launch_act<2, 4, 2>(a, st);
+    case kAct140: return launch_act<1, 4>(a, st);
+    case kAct142: return launch_act<1, 4, 2>(a, st);
+    case kAct143: return launch_act<1, 4, 3>(a, st);
+    case kActg1422: return launch_actg<1, 4, 2, 2>(a, st);
+    case kActg1423: return launch_actg<1, 4, 2, 3>(a, st);
+    case kActg1813: return launch_actg<1, 8, 1, 3>(a, st);
     }
-    if (form4 == 2 && form < 0 && cnt > 8192 && a.gcount <= 1) return launch_act2(a, st);
-    if (form4 == 2 && form == 12 && (a.tm_max == 0 || a.tm_max >= 2)) return launch_act2(a, st);      // A/B: the two-per-CU form (64-env tiles) at any size
-    const int tm = pick_tm(cnt, a.tm_max);
-    if (tm == 4) return form4 == 0 ? launch_act<4, 4>(a, st) : launch_act<4, 4, 2>(a, st);
-    if (tm == 2) return form == 0 || form4 == 0 ? launch_act<2, 4>(a, st) : launch_act<2, 4, 2>(a, st);
-    if (form == 0) return launch_act<1, 4>(a, st);
-    if (form == 2) return launch_act<1, 4, 2>(a, st);
-    if (form == 3) return launch_act<1, 4, 3>(a, st);
-    // 4 096 < envs <= 8 192 (round 4): the split form with a ring of TWO chunks -- 76.5 KB per workgroup, so the two halves of a tile's work
-    // are two independent workgroups resident on one CU (8 waves, two per SIMD, as the 8-wave form) without that form's coupling (its early
-    // waves wait at the barrier for the late ones): 23.1 against 23.8 us at 8 192 envs.  At <= 4 096 envs (one workgroup per CU) the
-    // shallower ring costs more than it wins (17.7 against 16.2 us): ring of three there.  Per-tile reward sums need ONE workgroup per tile.
-    if ((form == 10 || (form < 0 && cnt > 128 * 32)) && !want_sum && (cnt + 31) / 32 <= kSplitMaxTiles) return launch_actg<1, 4, 2, 2>(a, st);
-    // (a learner group whose env block admits only 32-env tiles can be large: beyond the split forms' exchange scratch the one-workgroup-per-tile form runs)
-    const bool split_fits = (cnt + 31) / 32 <= kSplitMaxTiles;
-    if (form == 8 || !split_fits || (form != 9 && (cnt > 128 * 32 || want_sum))) return launch_actg<1, 8, 1, 3>(a, st);
-    return launch_actg<1, 4, 2, 3>(a, st);
+    return set_error(SHEMS_ERR_ARG, "dispatch_act: no form");
 }
 
 // Wide networks (shems_wide.hip): the layers ran as matrix products and left partial sums of the output layer; this is the rest of the
@@ -1791,46 +1828,24 @@ int shems_act_step_grid(int64_t n_envs, int64_t *out_blocks)
     return SHEMS_OK;
 }
 
-/* Which kernel shems_act_step_dev / shems_act_step_group_dev dispatches for n_envs envs (grouped != 0: a learner group), as the
- * profiler prints it: the same decisions as dispatch_act, environment overrides included. */
+/* Which kernel shems_act_step_dev / shems_act_step_group_dev dispatches for n_envs envs without per-tile reward sums (grouped: 0 a
+ * single learner, 1 a learner group in Flux order without a tile limit, 2 one on the tiled working layout), as the profiler prints it:
+ * pick_act_form, the dispatcher's own decision, environment overrides included. */
 int shems_act_step_kernel(int64_t n_envs, int grouped, char *out, int32_t cap)
 {
     if (n_envs <= 0 || !out || cap < 2) return set_error(SHEMS_ERR_ARG, "shems_act_step_kernel: bad arguments");
-    const int form = act_form(), form4 = act_form4();
-    const char *name;
-    if (grouped == 2) {                                       // a learner group on the tiled working layout
-        const int tmt = pick_tm(n_envs);
-        name = tmt == 4 ? "shems::k_act<4, 4, 2>" : tmt == 2 ? "shems::k_act<2, 4, 2>" : "shems::k_act<1, 4, 2>";
-    } else if (form4 == 2 && ((form < 0 && n_envs > 8192 && !grouped) || form == 12)) name = "shems::k_act2";
-    else {
-        const int tm = pick_tm(n_envs);
-        if (tm == 4) name = form4 == 0 ? "shems::k_act<4, 4, 0>" : "shems::k_act<4, 4, 2>";
-        else if (tm == 2) name = form == 0 || form4 == 0 ? "shems::k_act<2, 4, 0>" : "shems::k_act<2, 4, 2>";
-        else if (form == 0) name = "shems::k_act<1, 4, 0>";
-        else if (form == 2) name = "shems::k_act<1, 4, 2>";
-        else if (form == 3) name = "shems::k_act<1, 4, 3>";
-        else if ((form == 10 || (form < 0 && n_envs > 128 * 32)) && (n_envs + 31) / 32 <= kSplitMaxTiles) name = "shems::k_actg<1, 4, 2, 2>";
-        else if (form == 8 || (n_envs + 31) / 32 > kSplitMaxTiles || (form != 9 && n_envs > 128 * 32)) name = "shems::k_actg<1, 8, 1, 3>";
-        else name = "shems::k_actg<1, 4, 2, 3>";
-    }
-    snprintf(out, (size_t)cap, "%s", name);
+    snprintf(out, (size_t)cap, "%s", act_form_name(pick_act_form(n_envs, 0, grouped ? 2 : 1, grouped == 2, false)));
     return SHEMS_OK;
 }
 
-/* The same for a learner group: the tile never straddles two learners, so envs_per_learner limits it. */
+/* The same for a learner group of n_envs / envs_per_learner learners: the tile never straddles two learners, so envs_per_learner
+ * limits it (act_step_group's tm_max). */
 int shems_act_step_group_kernel(int64_t n_envs, int64_t envs_per_learner, int tiled, char *out, int32_t cap)
 {
-    if (n_envs <= 0 || envs_per_learner < 32 || envs_per_learner % 32 != 0 || !out || cap < 2)
+    if (n_envs <= 0 || envs_per_learner < 32 || envs_per_learner % 32 != 0 || n_envs % envs_per_learner != 0 || !out || cap < 2)
         return set_error(SHEMS_ERR_ARG, "shems_act_step_group_kernel: bad arguments");
-    const int form = act_form(), form4 = act_form4(), tmax = group_tm_max(envs_per_learner);
-    const int tm = pick_tm(n_envs, tmax);
-    const char *name;
-    if (tiled) name = tm == 4 ? "shems::k_act<4, 4, 2>" : tm == 2 ? "shems::k_act<2, 4, 2>" : "shems::k_act<1, 4, 2>";
-    else if (form4 == 2 && form == 12 && tmax >= 2) name = "shems::k_act2";
-    else if (tm == 4) name = form4 == 0 ? "shems::k_act<4, 4, 0>" : "shems::k_act<4, 4, 2>";
-    else if (tm == 2) name = form == 0 || form4 == 0 ? "shems::k_act<2, 4, 0>" : "shems::k_act<2, 4, 2>";
-    else return shems_act_step_kernel(n_envs, 1, out, cap);          // 32-env tiles: the ungrouped decision tree below tm = 2
-    snprintf(out, (size_t)cap, "%s", name);
+    const int64_t count = n_envs / envs_per_learner;
+    snprintf(out, (size_t)cap, "%s", act_form_name(pick_act_form(n_envs, group_tm_max(envs_per_learner), (int)count, tiled != 0, false)));
     return SHEMS_OK;
 }
 

@@ -257,3 +257,18 @@ def test_julia_learner_module_matches_the_header(built_lib):
                    "function episode!(g::LearnerGroup", "function flux!(g::LearnerGroup", "function min_max_buffer(g::LearnerGroup",
                    "function populate_memory(g::LearnerGroup"):
         assert needed in src, needed
+
+
+def test_act_kernel_names_follow_the_dispatchers_decision(built_lib):
+    """The names bench.py credits FLOPs to come from the decision function dispatch_act launches from: no device needed to ask."""
+    D = importlib.import_module(U.PKG_NAME + ".ddpg")
+    G = importlib.import_module(U.PKG_NAME + ".group")
+    assert D.act_kernel_name(65536) == "shems::k_act2" and D.act_kernel_name(4096) == "shems::k_actg<1, 4, 2, 3>"
+    assert D.act_kernel_name(8192) == "shems::k_actg<1, 4, 2, 2>" and D.act_kernel_name(65536, grouped=True) == "shems::k_act<4, 4, 2>"
+    for (L, E, tiled), want in (((300, 96, False), "k_actg<1, 8, 1, 3>"), ((1024, 32, False), "k_actg<1, 8, 1, 3>"),
+                                ((300, 96, True), "k_act<1, 4, 2>"), ((520, 64, False), "k_act<2, 4, 2>"),
+                                ((12, 32, False), "k_actg<1, 4, 2, 3>"), ((1, 16384, False), "k_act2"),
+                                ((40, 128, False), "k_actg<1, 4, 2, 2>"), ((520, 64, True), "k_act<2, 4, 2>")):
+        assert G.group_act_kernel_name(L * E, E, tiled) == "shems::" + want, (L, E, tiled)
+    with pytest.raises(Exception):
+        G.group_act_kernel_name(100 * 32 + 32 * 3 // 2, 32, False)          # not a whole number of learners

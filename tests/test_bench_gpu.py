@@ -141,6 +141,13 @@ def test_bench_kernel_name_follows_the_dispatcher():
     D = importlib.import_module(U.PKG_NAME + ".ddpg")
     assert D.act_kernel_name(65536) == "shems::k_act2" and D.act_kernel_name(4096) == "shems::k_actg<1, 4, 2, 3>"
     assert D.act_kernel_name(8192) == "shems::k_actg<1, 4, 2, 2>" and D.act_kernel_name(65536, grouped=True) == "shems::k_act<4, 4, 2>"
+    G = importlib.import_module(U.PKG_NAME + ".group")
+    # learner groups: the name comes from the dispatcher's own decision (env blocks that allow only 32-env tiles beyond the split forms'
+    # 512 tiles, one learner above 8 192 envs)
+    for (L, E, tiled), want in (((300, 96, False), "k_actg<1, 8, 1, 3>"), ((1024, 32, False), "k_actg<1, 8, 1, 3>"),
+                                ((300, 96, True), "k_act<1, 4, 2>"), ((520, 64, False), "k_act<2, 4, 2>"),
+                                ((12, 32, False), "k_actg<1, 4, 2, 3>"), ((1, 16384, False), "k_act2")):
+        assert G.group_act_kernel_name(L * E, E, tiled) == "shems::" + want, (L, E, tiled)
 
 
 def test_bench_scaled_replay_mode():

@@ -179,3 +179,39 @@ def bits32(a):
 
 def bits64(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+# ------------------------------------------------------ per-env configs --
+SWEEP = ((0.01, 2.0), (0.04, 2.0), (0.1, 2.0), (0.01, 1.0), (0.04, 1.0), (0.1, 1.0))     # env.mixed_profile_setup's default
+
+
+def mixed_batches(n, co=None, maxsteps=72):
+    """BASELINE config 5 on the device and in the C oracle: the tables of env.mixed_profile_setup (real series of 4 319 / 4 320 rows
+    where the reference holds one), one config per (charger profile, sweep point), config co[i] for env i (default i mod 60).
+    Returns (ShemsBatch, oracle_c.Batch, tables, configs, co, table_of_env)."""
+    S = pkg()
+    tabs, cfgs, co0 = S.mixed_profile_setup(n)
+    co = co0 if co is None else np.ascontiguousarray(co, dtype=np.uint16)
+    assert co.shape == (n,) and int(co.max()) < len(cfgs)
+    profs = [oracle_c.profile(c, w, pot) for c in CHARGER_IDS for (w, pot) in SWEEP]
+    tab_of = np.repeat(np.arange(len(CHARGER_IDS)), len(SWEEP))[co]
+    env = S.ShemsBatch(n, maxsteps, tabs, cfgs, co)
+    ref = oracle_c.Batch(n, maxsteps, tabs, profs, tab_of, co)
+    return env, ref, tabs, cfgs, co, tab_of
+
+
+def learner_grid_cfgs(count, envs_per_learner):
+    """The thesis grid of a learner group on the mixed_profile_setup configs: every env of learner l on charger profile l mod 10, the
+    weight point l mod 6 (one learner: env i on config i mod 60)."""
+    n = count * envs_per_learner
+    if count == 1:
+        return (np.arange(n) % (len(CHARGER_IDS) * len(SWEEP))).astype(np.uint16)
+    l = np.arange(n) // envs_per_learner
+    return (len(SWEEP) * (l % len(CHARGER_IDS)) + l % len(SWEEP)).astype(np.uint16)
+
+
+def obs_of_rows(tab, idx, soc_b):
+    """The observation of envs sitting on 1-based rows `idx` of `tab` (the layout reset! leaves: soc_b, soc_ev, h, d_e, g_e, p_buy,
+    h_cos, h_sin, season)."""
+    rows = tab[np.asarray(idx) - 1]
+    return np.concatenate([np.asarray(soc_b, np.float32)[:, None], rows[:, [1, 0]], rows[:, 2:]], 1).astype(np.float32)
