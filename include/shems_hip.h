@@ -487,6 +487,35 @@ int shems_ddpg_group_critic_apply(const shems_ddpg *d0, const shems_group *g, do
 int shems_ddpg_group_actor_grad(const shems_ddpg *d0, const shems_group *g, void *stream);
 int shems_ddpg_group_actor_apply(const shems_ddpg *d0, const shems_group *g, double eta, double bp1, double bp2,
                                  void *stream);
+/* ------------------------------------------- per-learner hyper-parameters of a learner group -- */
+/* The thesis's experiment is a hyper-parameter grid (input09_08_on_01-09_eval.jl:62-106: BATCH, noise_act, (L1, L2), (eta_act,
+ * eta_crit)).  With one record per learner -- a DEVICE array of g->count records, learner l's is d_hp[l] -- one group runs many grid
+ * points at once.  The entry points below are those of the throughput form and of the fused group step with the record's scalars in
+ * place of the shared ones: shems_ddpg.gamma / tau / batch of d0 and shems_act_params.noise_mu / noise_sigma of p0 are IGNORED.  The
+ * ADAM beta powers stay shared (the learners advance in lockstep).  A record holding d0's / p0's values gives the bits of the shared
+ * entry points.  Hidden sizes below (250, 500) need no field: such a learner's networks are zero-padded (ddpg.pad_net) and stay so. */
+typedef struct shems_group_hparams {
+    double  eta_act, eta_crit;     /* ADAM(eta), DDPG.jl:105-108: the Float64 value of the Float32 literal (as Agent.eta_*)      */
+    float   gamma, tau;            /* DDPG.jl:133, 99-103                                                                        */
+    float   noise_mu, noise_sigma; /* GNoise of act(), DDPG.jl:151-160                                                           */
+    int32_t batch;                 /* BATCH_SIZE, 1..128 (the device clamps it to that range whatever the record holds)          */
+    int32_t reserved;              /* 0                                                                                          */
+} shems_group_hparams;             /* 40 bytes */
+/* Host-side validation of count records in HOST memory: batch in 1..128, eta finite and > 0, 0 < tau <= 1, 0 <= gamma <= 1,
+ * noise_sigma >= 0, every value finite.  SHEMS_ERR_ARG names the first bad learner and field. */
+int shems_group_hparams_check(const shems_group_hparams *host_hp, int32_t count);
+/* shems_act_step_group_dev (t == NULL) / shems_act_step_group_tiled_dev (t != NULL) with learner l's envs drawing their action noise
+ * as d_hp[l].noise_mu + d_hp[l].noise_sigma * z (z keyed by the global env index, as there).  Gaussian noise only: p0->noise_kind
+ * must be SHEMS_NOISE_GAUSS. */
+int shems_act_step_group_hp_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
+                                const shems_group_hparams *d_hp, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                                const shems_ring_window *window, void *stream);
+/* shems_ddpg_group_update_tp (t == NULL) / shems_ddpg_group_update_tiled (t != NULL) with learner l's batch (the first batch_l draws of
+ * the same minibatch stream, masks, divisors, losses), gamma, tau and eta (k1 = eta_l / (1 - bp1) formed on the device, correctly
+ * rounded) from d_hp[l]. */
+int shems_ddpg_group_update_hp(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *t,
+                               const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double bp1_crit,
+                               double bp2_crit, double bp1_act, double bp2_act, int32_t flags, void *stream);
 /* min_max_buffer for every learner of the group (learner l: Philox key seed + l). */
 int shems_minmax_group_dev(const shems_replay *ring0, const shems_group *g, int64_t ring_len, int64_t count,
                            uint64_t seed, float *d_s_min0, float *d_s_max0, void *stream);

@@ -34,6 +34,8 @@
 // evaluation with the same bound as the latency form (tests/test_group_gpu.py).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <type_traits>
 
@@ -107,6 +109,19 @@ __device__ __forceinline__ float half_sum32(float x)      // sum over the 32 lan
 }
 __device__ __forceinline__ float wave_sum64(float x) { x = half_sum32(x); return x + __shfl_xor(x, 32, 64); }
 
+// ---- per-learner hyper-parameters (shems_group_hparams; the *_hp kernels below) ---------------------------------------------------
+// A record is read whole by the workgroups of its learner (uniform: scalar loads).  batch is clamped to 1..BP whatever the record holds,
+// so that no kernel indexes outside its tiles even if a record was overwritten after the host check.
+__device__ __forceinline__ int hp_batch(const shems_group_hparams &h) { return min(max((int)h.batch, 1), BP); }
+// learner l's ADAM scalars and soft-update rate in the shared context: k1 = eta_l / (1 - bp1), the correctly rounded Float64 quotient
+// the host forms for the shared entry points (a true division, not a reciprocal: the bits must be the host's)
+__device__ __forceinline__ void hp_adam(AdamCtx &c, const shems_group_hparams &h, bool critic)
+{
+    c.eta = critic ? h.eta_crit : h.eta_act;
+    c.k1 = c.eta / (1.0 - c.bp1);
+    c.tau = h.tau;
+}
+
 __device__ __forceinline__ void adam_at(const AdamCtx &c, int i, float g, bool store_grad)
 {
     float m = c.mt[i], v = c.vt[i], p = c.p[i], t = c.target[i];
@@ -139,7 +154,8 @@ __device__ __forceinline__ void gshift(shems_replay &r, int64_t off)
 
 // grid (5, learners): workgroup 0 samples / gathers / normalises and freezes the output layers, workgroups 1..4 pack one network's
 // frozen layer-1 image each (one launch of 2 000 short workgroups instead of 400 long ones: 49 -> ~10 us at 400 learners)
-__device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, const int l)
+template <bool HP>
+__device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, const int l, const shems_group_hparams *hp)
 {
     const int tid = threadIdx.x;
     const int64_t off = (int64_t)l * A.gstride;
@@ -165,6 +181,7 @@ __device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, con
         }
         return;
     }
+    if constexpr (HP) d.batch = hp_batch(hp[l]);              // the first batch_l draws of the same stream are live
     const uint64_t seed = A.seed + (uint64_t)l;               // learner l: Philox key seed + l (as the latency form)
     if (tid < BP) {
         const int m = tid;
@@ -304,8 +321,8 @@ template <bool QG, int NTL_> struct FwdShape {
     static constexpr int LDS = (W1K * W1C + NW * 4 + 2 * 32 * S) * 4;
 };
 
-template <bool QG, int NTL_, bool TL>
-__device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bx, const int by, float *smem)
+template <bool QG, int NTL_, bool TL, bool HP>
+__device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp)
 {
     typedef FwdShape<QG, NTL_> SH;
     constexpr int S = SH::S, NTL = SH::NTL, NW = SH::NW;
@@ -382,7 +399,8 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bx, const i
         for (int r = 0; r < 16; ++r) acc[tt][r] = 0.0f;
     float da0 = 0.0f, da1 = 0.0f;
     unsigned mbits = 0u;                         // QG: bit 16 tt + r = (h2 > 0) of this lane's element (tt, r)
-    const float d3q = m < A.batch ? -1.0f / (float)A.batch : 0.0f;          // d(-mean q)/dq
+    const int batch = HP ? hp_batch(hp[by]) : A.batch;
+    const float d3q = m < batch ? -1.0f / (float)batch : 0.0f;              // d(-mean q)/dq
     // One pass over the n-tile's eight weight chunks; chunk it + 1 is requested before chunk it is consumed and lands in the other half
     // of the ring.  BWD = false: layer 2 forward; BWD = true (QG only): the input gradient through this n-tile.
     auto pass = [&](auto bwd, int it0, bool wrap) {
@@ -591,8 +609,8 @@ constexpr unsigned kNarrowBelow = 48;
 constexpr int d1_ring(int KT) { return 2 * 32 * KT * D1_S > 4 * KT * 8 * 64 ? 2 * 32 * KT * D1_S : 4 * KT * 8 * 64; }      // floats: the ring, later the four waves' gW1 partials
 constexpr int d1_lds(int KT) { return (d1_ring(KT) + 1024 + 2 * BP + 8 + W1K * BP + W1K * 32 * KT) * 4; }
 
-template <int IN, int KT, bool TL>
-__device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const int by, float *smem)
+template <int IN, int KT, bool TL, bool HP>
+__device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp)
 {
     typedef NetOf<IN> N;
     constexpr int OUT = N::OUT;
@@ -609,6 +627,11 @@ __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const in
     shems_ddpg d = A.d;
     AdamCtx c = A.c;
     gshift(d, off); gshift(c, off);
+    if constexpr (HP) {                          // the heads read gamma / batch from d
+        const shems_group_hparams h = hp[by];
+        d.gamma = h.gamma; d.batch = hp_batch(h);
+        hp_adam(c, h, N::critic);
+    }
     float *ws = d.ws;
     const float *__restrict__ P = c.p;
     const float *__restrict__ W2 = P + off_w2(IN);
@@ -805,8 +828,8 @@ constexpr int GW_WGS = 4 * NT;     // k-tiles x n-tiles of 64 per learner
 constexpr int GW_LDS = (64 * GW_S + 2 * BP + 64 * 2 + 64 * 3 + W1K * BP) * 4;
 static_assert(64 * GW_TS <= 64 * GW_S, "the row-major copy of a tile fits the D2 panel it replaces");
 
-template <int IN, bool TL>
-__device__ __forceinline__ void gw2_body(const NetArgs &A, const int bx, const int by, float *smem)
+template <int IN, bool TL, bool HP>
+__device__ __forceinline__ void gw2_body(const NetArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp)
 {
     typedef NetOf<IN> N;
     constexpr int OUT = N::OUT;
@@ -822,6 +845,7 @@ __device__ __forceinline__ void gw2_body(const NetArgs &A, const int bx, const i
     shems_ddpg d = A.d;
     AdamCtx c = A.c;
     gshift(d, off); gshift(c, off);
+    if constexpr (HP) hp_adam(c, hp[by], N::critic);
     float *ws = d.ws;
     const float *__restrict__ H2 = N::H2(ws);
     const bool store_grad = A.store_grad != 0;
@@ -963,34 +987,60 @@ __device__ __forceinline__ void gw2_body(const NetArgs &A, const int bx, const i
 }
 
 // ---- one launch per phase (the plain form: every learner of the group in the same phase) ---------------------------------------
-__global__ __launch_bounds__(256) void k_tp_prep(PrepArgs A) { prep_body(A, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(256) void k_tp_prep(PrepArgs A) { prep_body<false>(A, blockIdx.x, blockIdx.y, nullptr); }
 template <bool QG, int NTL, bool TL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTL == 4 ? 3 : 4, 4))) void k_tp_fwd(FwdArgs A)      // (the wide form's LDS allows three workgroups per CU)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    fwd_body<QG, NTL, TL>(A, blockIdx.x, blockIdx.y, smem);
+    fwd_body<QG, NTL, TL, false>(A, blockIdx.x, blockIdx.y, smem, nullptr);
 }
 // (Round 6 also built the forward launches as PERSISTENT workgroups -- 768 / 1 024 of them drawing their (n-tile, learner) items from a counter, which
 // tools/micro/fwd_anatomy.hip rates 0.86 against 0.82 of the peak for loops without prologues -- verified against the float64 oracle, measured slower
 // with the real prologues and epilogues (P1 373.5 against 355.3 us, P2 143.0 / 133.6, P5 278.9 / 273.8; 204.4 against 207.6 k updates/s), removed:
 // profiles/r06_fwd_persistent_ab.txt.)
-template <int IN, int KT, bool TL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1(NetArgs A)
+// A learner's k-tile workgroups (T = 8 / KT of them) read the same 256 KB of relu(layer 2): they are placed on ONE XCD (workgroup id
+// mod 8 picks the XCD and its L2), consecutive in its dispatch order -- learner = 8 (q / T) + xcd, k-tile = q mod T with q = id / 8.
+template <int IN, int KT, bool TL, bool HP>
+__device__ __forceinline__ void d1_entry(const NetArgs &A, float *smem, const shems_group_hparams *hp)
 {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    // A learner's k-tile workgroups (T = 8 / KT of them) read the same 256 KB of relu(layer 2): they are placed on ONE XCD (workgroup id
-    // mod 8 picks the XCD and its L2), consecutive in its dispatch order -- learner = 8 (q / T) + xcd, k-tile = q mod T with q = id / 8.
     constexpr unsigned T = 8 / KT;
     const unsigned id = blockIdx.x, xcd = id & 7u, q = id >> 3;
     const unsigned learner = 8u * (q / T) + xcd;
     if (learner >= (unsigned)A.learners) return;
-    d1_body<IN, KT, TL>(A, (int)(q % T), (int)learner, smem);
+    d1_body<IN, KT, TL, HP>(A, (int)(q % T), (int)learner, smem, hp);
+}
+template <int IN, int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1(NetArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<IN, KT, TL, false>(A, smem, nullptr);
 }
 template <int IN, bool TL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_gw2(NetArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    gw2_body<IN, TL>(A, blockIdx.x, blockIdx.y, smem);
+    gw2_body<IN, TL, false>(A, blockIdx.x, blockIdx.y, smem, nullptr);
+}
+
+// ---- the same launches with per-learner hyper-parameters (shems_ddpg_group_update_hp): own names, the bodies above with HP = true ----
+__global__ __launch_bounds__(256) void k_tp_prep_hp(PrepArgs A, const shems_group_hparams *hp) { prep_body<true>(A, blockIdx.x, blockIdx.y, hp); }
+template <bool QG, int NTL, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTL == 4 ? 3 : 4, 4))) void k_tp_fwd_hp(FwdArgs A, const shems_group_hparams *hp)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    fwd_body<QG, NTL, TL, true>(A, blockIdx.x, blockIdx.y, smem, hp);
+}
+template <int IN, int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1_hp(NetArgs A, const shems_group_hparams *hp)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<IN, KT, TL, true>(A, smem, hp);
+}
+template <int IN, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_gw2_hp(NetArgs A, const shems_group_hparams *hp)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    gw2_body<IN, TL, true>(A, blockIdx.x, blockIdx.y, smem, hp);
 }
 
 // (Round 5 also built two ways of running the HBM-bound phases (P4, P7) under the MFMA-bound ones (P1, P2, P5) of OTHER learners: cohorts
@@ -1048,10 +1098,11 @@ static int check_group_tp(const shems_group *g, const char *fn)
 }
 
 // t == null: every array in Flux order (round 5's form); else the layer-2 state of both networks lives in the tiled regions.
-template <bool TL>
+// HP: learner l's batch / gamma / tau / eta from hp[l] (device), the *_hp kernels; d->batch / gamma / tau and eta_* are not used.
+template <bool TL, bool HP>
 static int group_update_tp(const char *fn, const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, int64_t ring_len,
                            uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act,
-                           int32_t flags, void *stream)
+                           int32_t flags, void *stream, const shems_group_hparams *hp = nullptr)
 {
     if (int rc = check_group_tp(g, fn)) return rc;
     if (!d || !d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
@@ -1059,7 +1110,8 @@ static int group_update_tp(const char *fn, const shems_ddpg *d, const shems_repl
         return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
     if ((flags & SHEMS_TP_STORE_GRAD) && (!d->grad_actor || !d->grad_critic)) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
     if (flags & ~SHEMS_TP_STORE_GRAD) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
-    if (d->batch < 1 || d->batch > BP) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
+    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
+    if (HP && (!hp || ((uintptr_t)hp & 7) != 0)) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
     for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
         if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
     if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
@@ -1098,18 +1150,32 @@ static int group_update_tp(const char *fn, const shems_ddpg *d, const shems_repl
                          ws + TP_DAP, CIN, 1};
     U.nc = NetArgs{*d, tc, adam_ctx(true), gs, 1, sg, (int)L};
     U.na = NetArgs{*d, ta, adam_ctx(false), gs, 2, sg, (int)L};
-    hipLaunchKernelGGL(k_tp_prep, dim3(5, L), dim3(256), 0, st, U.pa);
     typedef FwdShape<false, 4> SW;           // (typedefs: the launch macro splits its arguments at the commas of a template argument list)
     typedef FwdShape<false, 2> SN;
     typedef FwdShape<true, 2> SQ;
+    const bool narrow = L < kNarrowBelow;
+    const unsigned g8 = 8 * ((L + 7) / 8);
+    if constexpr (HP) {                      // the same eight launches, each reading its learner's record
+        hipLaunchKernelGGL(k_tp_prep_hp, dim3(5, L), dim3(256), 0, st, U.pa, hp);
+        if (narrow) hipLaunchKernelGGL((k_tp_fwd_hp<false, 2, TL>), dim3(3 * SN::TILES, L), dim3(256), SN::LDS, st, U.f1, hp);
+        else hipLaunchKernelGGL((k_tp_fwd_hp<false, 4, TL>), dim3(3 * SW::TILES, L), dim3(256), SW::LDS, st, U.f1, hp);
+        hipLaunchKernelGGL((k_tp_fwd_hp<false, 2, TL>), dim3(SN::TILES, L), dim3(256), SN::LDS, st, U.f2, hp);
+        if (narrow) hipLaunchKernelGGL((k_tp_d1_hp<CIN, 1, TL>), dim3(8 * g8), dim3(256), d1_lds(1), st, U.nc, hp);
+        else hipLaunchKernelGGL((k_tp_d1_hp<CIN, 2, TL>), dim3(4 * g8), dim3(256), d1_lds(2) + SHEMS_D1_PAD, st, U.nc, hp);
+        hipLaunchKernelGGL((k_tp_gw2_hp<CIN, TL>), dim3(GW_WGS, L), dim3(256), GW_LDS, st, U.nc, hp);
+        hipLaunchKernelGGL((k_tp_fwd_hp<true, 2, TL>), dim3(SQ::TILES, L), dim3(256), SQ::LDS, st, U.f5, hp);
+        if (narrow) hipLaunchKernelGGL((k_tp_d1_hp<SIN, 1, TL>), dim3(8 * g8), dim3(256), d1_lds(1), st, U.na, hp);
+        else hipLaunchKernelGGL((k_tp_d1_hp<SIN, 2, TL>), dim3(4 * g8), dim3(256), d1_lds(2) + SHEMS_D1_PAD, st, U.na, hp);
+        hipLaunchKernelGGL((k_tp_gw2_hp<SIN, TL>), dim3(GW_WGS, L), dim3(256), GW_LDS, st, U.na, hp);
+        return hip_ok(hipGetLastError(), "grouped update (throughput form, per-learner hyper-parameters) launches");
+    }
+    hipLaunchKernelGGL(k_tp_prep, dim3(5, L), dim3(256), 0, st, U.pa);
     // Few learners: the shapes with twice the workgroups (P1 on 64-wide n-tiles, P3 / P6 on 32-wide k-tiles).  Below kNarrowBelow learners
     // the wide shapes leave CUs without work (P3 at 32 learners: 128 workgroups); measured per grouped update, wide / narrow: 32 learners
     // 247 / 226 us, 48 learners 322 / 320, 64 learners 362 / 372, 128 learners 669 / 695 (profiles/NOTES.md, round-5 log).
-    const bool narrow = L < kNarrowBelow;
     if (narrow) hipLaunchKernelGGL((k_tp_fwd<false, 2, TL>), dim3(3 * SN::TILES, L), dim3(256), SN::LDS, st, U.f1);
     else hipLaunchKernelGGL((k_tp_fwd<false, 4, TL>), dim3(3 * SW::TILES, L), dim3(256), SW::LDS, st, U.f1);
     hipLaunchKernelGGL((k_tp_fwd<false, 2, TL>), dim3(SN::TILES, L), dim3(256), SN::LDS, st, U.f2);
-    const unsigned g8 = 8 * ((L + 7) / 8);
     if (narrow) hipLaunchKernelGGL((k_tp_d1<CIN, 1, TL>), dim3(8 * g8), dim3(256), d1_lds(1), st, U.nc);
     else hipLaunchKernelGGL((k_tp_d1<CIN, 2, TL>), dim3(4 * g8), dim3(256), d1_lds(2) + SHEMS_D1_PAD, st, U.nc);
     hipLaunchKernelGGL((k_tp_gw2<CIN, TL>), dim3(GW_WGS, L), dim3(256), GW_LDS, st, U.nc);
@@ -1124,7 +1190,7 @@ extern "C" int shems_ddpg_group_update_tp(const shems_ddpg *d, const shems_repla
                                           uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
                                           double bp2_act, int32_t flags, void *stream)
 {
-    return group_update_tp<false>("shems_ddpg_group_update_tp", d, ring, g, nullptr, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
+    return group_update_tp<false, false>("shems_ddpg_group_update_tp", d, ring, g, nullptr, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
                                   flags, stream);
 }
 
@@ -1132,8 +1198,41 @@ extern "C" int shems_ddpg_group_update_tiled(const shems_ddpg *d, const shems_re
                                              uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
                                              double bp2_act, int32_t flags, void *stream)
 {
-    return group_update_tp<true>("shems_ddpg_group_update_tiled", d, ring, g, t, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
+    return group_update_tp<true, false>("shems_ddpg_group_update_tiled", d, ring, g, t, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
                                  flags, stream);
+}
+
+extern "C" int shems_ddpg_group_update_hp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
+                                          const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double bp1_crit,
+                                          double bp2_crit, double bp1_act, double bp2_act, int32_t flags, void *stream)
+{
+    // (eta_* = 0: the kernels form k1 from the records; the host context's k1 is never read by them)
+    if (t) return group_update_tp<true, true>("shems_ddpg_group_update_hp", d, ring, g, t, ring_len, seed, tick, 0.0, bp1_crit, bp2_crit, 0.0, bp1_act,
+                                              bp2_act, flags, stream, d_hp);
+    return group_update_tp<false, true>("shems_ddpg_group_update_hp", d, ring, g, nullptr, ring_len, seed, tick, 0.0, bp1_crit, bp2_crit, 0.0, bp1_act,
+                                        bp2_act, flags, stream, d_hp);
+}
+
+static_assert(sizeof(shems_group_hparams) == 40 && offsetof(shems_group_hparams, gamma) == 16 && offsetof(shems_group_hparams, noise_mu) == 24 &&
+              offsetof(shems_group_hparams, batch) == 32, "shems_group_hparams: 40 bytes, the layout of include/shems_hip.h and group.HParams");
+
+extern "C" int shems_group_hparams_check(const shems_group_hparams *hp, int32_t count)
+{
+    const char *fn = "shems_group_hparams_check";
+    if (!hp || count < 1) return set_error(SHEMS_ERR_ARG, "%s: need count >= 1 records", fn);
+    for (int32_t l = 0; l < count; ++l) {
+        const shems_group_hparams &h = hp[l];
+        if (h.batch < 1 || h.batch > BP) return set_error(SHEMS_ERR_ARG, "%s: learner %d: batch %d outside 1..128", fn, l, h.batch);
+        if (!(std::isfinite(h.eta_act) && h.eta_act > 0.0)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: eta_act %g must be finite and > 0", fn, l, h.eta_act);
+        if (!(std::isfinite(h.eta_crit) && h.eta_crit > 0.0)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: eta_crit %g must be finite and > 0", fn, l, h.eta_crit);
+        if (!(h.tau > 0.0f && h.tau <= 1.0f)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: tau %g outside (0, 1]", fn, l, (double)h.tau);
+        if (!(h.gamma >= 0.0f && h.gamma <= 1.0f)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: gamma %g outside [0, 1]", fn, l, (double)h.gamma);
+        if (!std::isfinite(h.noise_mu)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: noise_mu %g is not finite", fn, l, (double)h.noise_mu);
+        if (!(std::isfinite(h.noise_sigma) && h.noise_sigma >= 0.0f))
+            return set_error(SHEMS_ERR_ARG, "%s: learner %d: noise_sigma %g must be finite and >= 0", fn, l, (double)h.noise_sigma);
+        if (h.reserved != 0) return set_error(SHEMS_ERR_ARG, "%s: learner %d: reserved must be 0", fn, l);
+    }
+    return SHEMS_OK;
 }
 
 static int w2_layout(const char *fn, bool to_tiled, const shems_ddpg *d, const shems_group *g, const shems_group_w2t *t, void *stream)

@@ -276,8 +276,10 @@ __device__ __forceinline__ TailPre tailpre_load(const float *lds)
 // remember (DDPG.jl:148-184, 199-229).  Returns the env's reward (0 when nothing was stepped).
 // obs_lds: the env's 9 raw observations in LDS (the caller staged them), or null = read them from the view.
 // pre_lds: the env's TailPre block in LDS (the caller fetched it ahead), or null = draw / read in place.
+// HP (shems_act_step_group_hp_dev): the Gaussian noise of learner l's envs is hp[l].noise_mu + hp[l].noise_sigma * z.
+template <bool HP = false>
 __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, float p0, float p1, int64_t learner, int64_t goff,
-                                               const float *obs_lds, const float *pre_lds = nullptr)
+                                               const float *obs_lds, const float *pre_lds = nullptr, const shems_group_hparams *hp = nullptr)
 {
     double reward = 0.0;
     {
@@ -305,7 +307,13 @@ __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, floa
                     p1 += X.y;
                     nmean = 0.5f * (X.x + X.y);
                 } else {                                               // DDPG.jl:57-61, 159-160: Normal(mu, sigma_act)
-                    const float n0 = A.p.noise_mu + A.p.noise_sigma * z.x, n1 = A.p.noise_mu + A.p.noise_sigma * z.y;
+                    float n0, n1;
+                    if constexpr (HP) {
+                        const float mu = hp[learner].noise_mu, sg = hp[learner].noise_sigma;
+                        n0 = mu + sg * z.x; n1 = mu + sg * z.y;
+                    } else {
+                        n0 = A.p.noise_mu + A.p.noise_sigma * z.x; n1 = A.p.noise_mu + A.p.noise_sigma * z.y;
+                    }
                     p0 += n0;
                     p1 += n1;
                     nmean = 0.5f * (n0 + n1);
@@ -394,8 +402,10 @@ constexpr int free_keep(int c)
     return n;
 }
 
-template <int TM, int NW, int RD>
-__global__ __launch_bounds__(64 * NW, NW / 4) void k_act(ActArgs A)
+// (every form a learner group can run is a body with a bool HP: the kernels of the shared entry points instantiate it with false, the
+// *_hp kernels -- own names, shems_act_step_group_hp_dev -- with true)
+template <int TM, int NW, int RD, bool HP>
+__device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_hparams *hp)
 {
     static_assert(RD == 0 || (NW == 4 && RD >= 2 && RD <= 4), "free-running form: 4 waves, ring of 2..4 chunks");
     constexpr int NT_ = 64 * NW;            // threads per workgroup
@@ -940,7 +950,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_act(ActArgs A)
             for (int j = 0; j < 2; ++j)
                 hs[hf][j] = ((RED_OF(4 * hf)[tid * 2 + j] + RED_OF(4 * hf + 1)[tid * 2 + j]) + RED_OF(4 * hf + 2)[tid * 2 + j]) + RED_OF(4 * hf + 3)[tid * 2 + j];
         const float p0 = tl[kH2P + kH2P * kOut + 0] + (hs[0][0] + hs[1][0]), p1 = tl[kH2P + kH2P * kOut + 1] + (hs[0][1] + hs[1][1]);   // b3 + (H0 + H1)
-        reward = act_env_tail(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, PRE ? xP + tid * kPreDw : PRE2 ? w1 + tid * kPreDw : nullptr);
+        reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, PRE ? xP + tid * kPreDw : PRE2 ? w1 + tid * kPreDw : nullptr, hp);
     }
     PSTAMP(12);
 #ifndef SHEMS_STAMP_ACT
@@ -952,6 +962,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_act(ActArgs A)
     }
 #endif
 }
+template <int TM, int NW, int RD>
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_act(ActArgs A) { k_act_body<TM, NW, RD, false>(A, nullptr); }
+template <int TM, int NW, int RD>
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_act_hp(ActArgs A, const shems_group_hparams *hp) { k_act_body<TM, NW, RD, true>(A, hp); }
 
 // =====================================================================================================================
 // Column-group forms for small batches: k_actg<TM, NW, NS, RD>.
@@ -1003,8 +1017,8 @@ __device__ __forceinline__ void g_piece(const char *sbase, uint32_t voff, uint32
     }
 }
 
-template <int TM, int NW, int NS, int RD>
-__global__ __launch_bounds__(64 * NW) void k_actg(ActArgs A, ActSplit X)
+template <int TM, int NW, int NS, int RD, bool HP>
+__device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X, const shems_group_hparams *hp)
 {
     static_assert(NW * NS == 8 && (NW == 4 || NW == 8), "8 column groups per env tile: 8 waves, or two workgroups of 4");
 #ifdef SHEMS_STAMP_ACT
@@ -1304,7 +1318,7 @@ __global__ __launch_bounds__(64 * NW) void k_actg(ActArgs A, ActSplit X)
     }
     GSTAMP(9, blockIdx.x == 0);
     GSTAMP(11, tile == 0 && fin);
-    if (fin) reward = act_env_tail(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, xP + tid * kPreDw);
+    if (fin) reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, xP + tid * kPreDw, hp);
     GSTAMP(12, tile == 0 && fin);
 #ifndef SHEMS_STAMP_ACT
     if (NS == 1 && A.block_reward) {
@@ -1315,6 +1329,10 @@ __global__ __launch_bounds__(64 * NW) void k_actg(ActArgs A, ActSplit X)
     }
 #endif
 }
+template <int TM, int NW, int NS, int RD>
+__global__ __launch_bounds__(64 * NW) void k_actg(ActArgs A, ActSplit X) { k_actg_body<TM, NW, NS, RD, false>(A, X, nullptr); }
+template <int TM, int NW, int NS, int RD>
+__global__ __launch_bounds__(64 * NW) void k_actg_hp(ActArgs A, ActSplit X, const shems_group_hparams *hp) { k_actg_body<TM, NW, NS, RD, true>(A, X, hp); }
 
 // =====================================================================================================================
 // k_act2: the fused step for large batches with TWO workgroups resident per CU.
@@ -1343,7 +1361,8 @@ __device__ __forceinline__ void k2_piece(const char *sbase, uint32_t voff, uint3
     if (q == 0) glds16_asm<-1024>(sbase, voff, lds_base); else glds16_asm<0>(sbase, voff, lds_base);
 }
 
-__global__ __launch_bounds__(256, 2) void k_act2(ActArgs A)
+template <bool HP>
+__device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_hparams *hp)
 {
     constexpr int TM = 2, BM = 64, NA = 4, NT_ = 256, HR = 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1604,7 +1623,7 @@ __global__ __launch_bounds__(256, 2) void k_act2(ActArgs A)
                 hs[hf][j] = ((r0[tid * 2 + j] + r0[BM * kOut + tid * 2 + j]) + r1[tid * 2 + j]) + r1[BM * kOut + tid * 2 + j];
             }
         const float p0 = tl[kH2P + kH2P * kOut + 0] + (hs[0][0] + hs[1][0]), p1 = tl[kH2P + kH2P * kOut + 1] + (hs[0][1] + hs[1][1]);
-        reward = act_env_tail(A, i, p0, p1, learner, goff, nullptr, xP + tid * kPreDw);
+        reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, nullptr, xP + tid * kPreDw, hp);
     }
 #ifndef SHEMS_STAMP_ACT
     if (A.block_reward) {
@@ -1615,14 +1634,23 @@ __global__ __launch_bounds__(256, 2) void k_act2(ActArgs A)
     }
 #endif
 }
+__global__ __launch_bounds__(256, 2) void k_act2(ActArgs A) { k_act2_body<false>(A, nullptr); }
+__global__ __launch_bounds__(256, 2) void k_act2_hp(ActArgs A, const shems_group_hparams *hp) { k_act2_body<true>(A, hp); }
 
-static int launch_act2(const ActArgs &a, hipStream_t st)
+// hp != null (shems_act_step_group_hp_dev): the *_hp kernel of the same form
+static int launch_act2(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
 {
     constexpr size_t lds = act2_lds_bytes();
     static_assert(lds <= 80 * 1024, "k_act2: two workgroups must fit a CU's 160 KB");
-    static std::atomic<uint64_t> optin{0};
+    static std::atomic<uint64_t> optin{0}, optin_hp{0};
+    const dim3 grid((unsigned)((a.m - a.m0 + 63) / 64));
+    if (hp) {
+        if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_act2_hp), (int)lds, "hipFuncSetAttribute(k_act2_hp)")) return rc;
+        hipLaunchKernelGGL(k_act2_hp, grid, dim3(256), lds, st, a, hp);
+        return hip_ok(hipGetLastError(), "k_act2_hp launch");
+    }
     if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_act2), (int)lds, "hipFuncSetAttribute(k_act2)")) return rc;
-    hipLaunchKernelGGL(k_act2, dim3((unsigned)((a.m - a.m0 + 63) / 64)), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(k_act2, grid, dim3(256), lds, st, a);
     return hip_ok(hipGetLastError(), "k_act2 launch");
 }
 
@@ -1636,14 +1664,19 @@ static int pick_tm(int64_t m, int tm_max = 0)
 static int group_tm_max(int64_t envs_per_learner) { return envs_per_learner % 128 == 0 ? 4 : envs_per_learner % 64 == 0 ? 2 : 1; }
 
 template <int TM, int NW, int RD = 0>
-static int launch_act(const ActArgs &a, hipStream_t st)
+static int launch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
 {
     constexpr int BM = 32 * TM;
     const size_t lds = act_lds_bytes<TM, NW, RD>();
     static_assert(act_lds_bytes<TM, NW, RD>() <= 160 * 1024, "k_act: LDS image exceeds 160 KB");
-    static std::atomic<uint64_t> optin{0};                   // per device: see lds_optin
-    if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_act<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act)")) return rc;
+    static std::atomic<uint64_t> optin{0}, optin_hp{0};      // per device: see lds_optin
     const unsigned grid = (unsigned)((a.m - a.m0 + BM - 1) / BM);
+    if (hp) {
+        if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_act_hp<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act_hp)")) return rc;
+        hipLaunchKernelGGL((k_act_hp<TM, NW, RD>), dim3(grid), dim3(64 * NW), lds, st, a, hp);
+        return hip_ok(hipGetLastError(), "k_act_hp launch");
+    }
+    if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_act<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act)")) return rc;
     hipLaunchKernelGGL((k_act<TM, NW, RD>), dim3(grid), dim3(64 * NW), lds, st, a);
     return hip_ok(hipGetLastError(), "k_act launch");
 }
@@ -1680,13 +1713,15 @@ static int split_scratch(hipStream_t st, ActSplit *out)
 }
 
 template <int TM, int NW, int NS, int RD>
-static int launch_actg(const ActArgs &a, hipStream_t st)
+static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
 {
     constexpr int BM = 32 * TM;
     constexpr size_t lds = actg_lds_bytes<TM, NW, RD>();
     static_assert(lds <= 160 * 1024, "k_actg: LDS image exceeds 160 KB");
-    static std::atomic<uint64_t> optin{0};                   // per device: see lds_optin
-    if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_actg<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg)")) return rc;
+    static std::atomic<uint64_t> optin{0}, optin_hp{0};      // per device: see lds_optin
+    if (hp) {
+        if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_actg_hp<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg_hp)")) return rc;
+    } else if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_actg<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg)")) return rc;
     const int64_t tiles = (a.m - a.m0 + BM - 1) / BM;
     ActSplit x = {nullptr};
     if constexpr (NS == 2) {
@@ -1694,8 +1729,12 @@ static int launch_actg(const ActArgs &a, hipStream_t st)
         if (split_scratch(st, &x) != SHEMS_OK) {
             // no exchange slab for this (device, stream) -- the 33rd distinct stream of a long-lived process, or hipMalloc failed: the
             // one-workgroup-per-tile form needs none and writes the same bytes
-            return launch_actg<1, 8, 1, RD>(a, st);
+            return launch_actg<1, 8, 1, RD>(a, st, hp);
         }
+    }
+    if (hp) {
+        hipLaunchKernelGGL((k_actg_hp<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x, hp);
+        return hip_ok(hipGetLastError(), "k_actg_hp launch");
     }
     hipLaunchKernelGGL((k_actg<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x);
     return hip_ok(hipGetLastError(), "k_actg launch");
@@ -1764,7 +1803,7 @@ static ActForm pick_act_form(int64_t cnt, int tm_max, int gcount, bool w2t, bool
 // in L2 than they win -- 151.9 against 145.7 us at 32 x 2 048 envs)
 static int act_tile_envs(int64_t m) { return act_form_tile_envs(pick_act_form(m, 0, 0, false, true)); }
 
-static int dispatch_act(const ActArgs &a, hipStream_t st)
+static int dispatch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
 {
 #ifdef SHEMS_STAMP_ACT
     const bool want_sum = false;                              // stamp builds: block_reward is the stamp buffer
@@ -1773,17 +1812,17 @@ static int dispatch_act(const ActArgs &a, hipStream_t st)
 #endif
     // envs of this launch a.m - a.m0 (a range launch: every form writes the same bytes)
     switch (pick_act_form(a.m - a.m0, a.tm_max, a.gcount, a.w2t != nullptr, want_sum)) {
-    case kAct2: return launch_act2(a, st);
-    case kAct440: return launch_act<4, 4>(a, st);
-    case kAct442: return launch_act<4, 4, 2>(a, st);
-    case kAct240: return launch_act<2, 4>(a, st);
-    case kAct242: return launch_act<2, 4, 2>(a, st);
-    case kAct140: return launch_act<1, 4>(a, st);
-    case kAct142: return launch_act<1, 4, 2>(a, st);
-    case kAct143: return launch_act<1, 4, 3>(a, st);
-    case kActg1422: return launch_actg<1, 4, 2, 2>(a, st);
-    case kActg1423: return launch_actg<1, 4, 2, 3>(a, st);
-    case kActg1813: return launch_actg<1, 8, 1, 3>(a, st);
+    case kAct2: return launch_act2(a, st, hp);
+    case kAct440: return launch_act<4, 4>(a, st, hp);
+    case kAct442: return launch_act<4, 4, 2>(a, st, hp);
+    case kAct240: return launch_act<2, 4>(a, st, hp);
+    case kAct242: return launch_act<2, 4, 2>(a, st, hp);
+    case kAct140: return launch_act<1, 4>(a, st, hp);
+    case kAct142: return launch_act<1, 4, 2>(a, st, hp);
+    case kAct143: return launch_act<1, 4, 3>(a, st, hp);
+    case kActg1422: return launch_actg<1, 4, 2, 2>(a, st, hp);
+    case kActg1423: return launch_actg<1, 4, 2, 3>(a, st, hp);
+    case kActg1813: return launch_actg<1, 8, 1, 3>(a, st, hp);
     }
     return set_error(SHEMS_ERR_ARG, "dispatch_act: no form");
 }
@@ -1954,7 +1993,8 @@ int shems_wide_act_step_dev(const shems_view *v, const shems_act_params *p, int3
 }
 
 static int act_step_group(const char *fn, const shems_view *v, const shems_act_params *p0, const shems_group *g, const float *w2t, float *d_a,
-                          double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream)
+                          double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream,
+                          const shems_group_hparams *hp = nullptr)
 {
     if (int rc = check_act(p0, fn)) return rc;
     if (int rc = check_view(v, fn)) return rc;
@@ -1981,7 +2021,7 @@ static int act_step_group(const char *fn, const shems_view *v, const shems_act_p
                              (long long)window->offset, (long long)g->envs_per_learner);
         a.ring = *ring0; a.win = *window; a.use_ring = 1;
     }
-    return dispatch_act(a, (hipStream_t)stream);
+    return dispatch_act(a, (hipStream_t)stream, hp);
 }
 
 int shems_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, float *d_a,
@@ -1996,6 +2036,19 @@ int shems_act_step_group_tiled_dev(const shems_view *v, const shems_act_params *
     if (!t || !t->actor || ((uintptr_t)t->actor & 15) != 0)
         return set_error(SHEMS_ERR_ARG, "shems_act_step_group_tiled_dev: shems_group_w2t.actor must be a 16-byte aligned device pointer");
     return act_step_group("shems_act_step_group_tiled_dev", v, p0, g, t->actor, d_a, d_returns_acc, ring0, window, stream);
+}
+
+int shems_act_step_group_hp_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
+                                const shems_group_hparams *d_hp, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                                const shems_ring_window *window, void *stream)
+{
+    const char *fn = "shems_act_step_group_hp_dev";
+    if (!d_hp || ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (p0 && p0->noise_kind != SHEMS_NOISE_GAUSS)
+        return set_error(SHEMS_ERR_ARG, "%s: per-learner noise is Gaussian only (noise_kind %d)", fn, p0->noise_kind);
+    if (t && (!t->actor || ((uintptr_t)t->actor & 15) != 0))
+        return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t.actor must be a 16-byte aligned device pointer", fn);
+    return act_step_group(fn, v, p0, g, t ? t->actor : nullptr, d_a, d_returns_acc, ring0, window, stream, d_hp);
 }
 
 }  // extern "C"

@@ -17,7 +17,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .ddpg import (ACTION, BATCH_SIZE, MEM_SIZE, N_ACTOR, N_CRITIC, NOISE_SIGMA, STATE, Agent, RingWindow, _declare, act_kernel_name)
+from .ddpg import (ACTION, BATCH_SIZE, ETA_ACT, ETA_CRIT, GAMMA, L1, L2, MEM_SIZE, N_ACTOR, N_CRITIC, NOISE_SIGMA, STATE, TAU, Agent, RingWindow,
+                   _declare, act_kernel_name)
 from .replay import ReplayRing
 
 
@@ -27,6 +28,93 @@ class Group(C.Structure):              # shems_group
 
 class GroupW2T(C.Structure):           # shems_group_w2t
     _fields_ = [("actor", C.c_void_p), ("critic", C.c_void_p)]
+
+
+class HParams(C.Structure):            # shems_group_hparams: one learner's record of a group with per-learner hyper-parameters
+    _fields_ = [("eta_act", C.c_double), ("eta_crit", C.c_double), ("gamma", C.c_float), ("tau", C.c_float),
+                ("noise_mu", C.c_float), ("noise_sigma", C.c_float), ("batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(HParams) == 40
+
+# keys of a per-learner mapping (LearnerGroup(hparams=...)); a missing key takes today's default
+HPARAM_KEYS = ("eta_act", "eta_crit", "gamma", "tau", "sigma", "mu", "batch", "hidden", "noise_type", "mem_size")
+MAX_GROUP_BATCH = 128                  # one update pass holds 128 minibatch columns (the group kernels have no sub-batch path)
+
+
+def hparam_defaults(sigma=NOISE_SIGMA):
+    """Today's values: what every learner of a group without hparams trains with."""
+    return dict(eta_act=ETA_ACT, eta_crit=ETA_CRIT, gamma=GAMMA, tau=TAU, sigma=sigma, mu=0.0, batch=BATCH_SIZE, hidden=(L1, L2))
+
+
+def _hparams_records(count, hparams, sigma, capacity):
+    """Per-learner mappings -> (full dicts, ctypes array of HParams).  Everything the group kernels cannot hold is refused here, naming the
+    learner; the records themselves go through shems_group_hparams_check.  Host only: no device work."""
+    hparams = list(hparams)
+    if len(hparams) != count:
+        raise ValueError(f"hparams holds {len(hparams)} records for a group of {count} learners")
+    full = []
+    for l, h in enumerate(hparams):
+        if not hasattr(h, "keys"):
+            raise ValueError(f"hparams[{l}]: a mapping is needed, got {type(h).__name__}")
+        unknown = sorted(set(h.keys()) - set(HPARAM_KEYS))
+        if unknown:
+            raise ValueError(f"hparams[{l}]: unknown keys {unknown} (known: {', '.join(HPARAM_KEYS)})")
+        r = hparam_defaults(sigma)
+        r.update({k: v for k, v in h.items() if k not in ("noise_type", "mem_size")})
+        if h.get("noise_type", "gn") != "gn":
+            raise ValueError(f"hparams[{l}]: noise_type {h['noise_type']!r}: a learner group draws Gaussian action noise only (\"gn\")")
+        if "mem_size" in h and int(h["mem_size"]) != capacity:
+            raise ValueError(f"hparams[{l}]: mem_size {h['mem_size']} differs from the group's ring capacity {capacity}: "
+                             "every learner's ring has the same capacity")
+        if int(r["batch"]) > MAX_GROUP_BATCH:
+            raise ValueError(f"hparams[{l}]: batch {r['batch']} > {MAX_GROUP_BATCH}: the group kernels hold one 128-column update pass")
+        hid = tuple(int(x) for x in r["hidden"])
+        if len(hid) != 2 or hid[0] < 1 or hid[1] < 1 or hid[0] > L1 or hid[1] > L2:
+            raise ValueError(f"hparams[{l}]: hidden {tuple(r['hidden'])} does not fit ({L1}, {L2}): wider networks run on the single-learner "
+                             "wide path, not in a group")
+        r["hidden"] = hid
+        r["batch"] = int(r["batch"])
+        for k in ("eta_act", "eta_crit"):         # ADAM(eta) with a Float32 literal: its Float64 value (Agent.eta_*)
+            r[k] = float(np.float32(r[k]))
+        for k in ("gamma", "tau", "sigma", "mu"):
+            r[k] = float(np.float32(r[k]))
+        full.append(r)
+    arr = (HParams * count)(*[HParams(r["eta_act"], r["eta_crit"], r["gamma"], r["tau"], r["mu"], r["sigma"], r["batch"], 0) for r in full])
+    L = _declare_group()
+    if L.shems_group_hparams_check(arr, count) != _capi.OK:
+        raise ValueError(L.shems_last_error().decode("utf-8", "replace"))
+    return full, arr
+
+
+def tuned_grid(job_ids, seeds=1, chargers=1):
+    """Per-learner records of a slice of the tuned template's hyper-parameter grid (input09_08_on_01-09_eval.jl:62-106), decoded by
+    main.set_hyperparameters from each JOB_ID's last two digits.  Returns (records, points, skipped): `records` holds
+    len(points) x seeds x chargers mappings for LearnerGroup(hparams=...), learner (p * seeds + s) * chargers + c running point points[p];
+    `skipped` lists (job_id, reason) for the points a group cannot run (BATCH_SIZE 150, (L1, L2) = (300, 600))."""
+    from .main import RunConfig, set_hyperparameters
+    records, points, skipped = [], [], []
+    for jid in job_ids:
+        jid = str(jid)
+        cfg = set_hyperparameters(RunConfig(job_id=jid.zfill(2), task_id="0", gpu_id=0, template="tuned"))
+        why = []
+        if cfg.BATCH_SIZE > MAX_GROUP_BATCH:
+            why.append(f"BATCH_SIZE {cfg.BATCH_SIZE} > {MAX_GROUP_BATCH}")
+        if cfg.L1 > L1 or cfg.L2 > L2:
+            why.append(f"(L1, L2) = ({cfg.L1}, {cfg.L2}) wider than ({L1}, {L2})")
+        if cfg.noise_type != "gn":
+            why.append(f"noise_type {cfg.noise_type!r}")
+        if why:
+            skipped.append((jid, "; ".join(why)))
+            continue
+        rec = dict(eta_act=float(np.float32(cfg.eta_act)), eta_crit=float(np.float32(cfg.eta_crit)), gamma=float(np.float32(cfg.gamma)),
+                   tau=float(np.float32(cfg.tau)), sigma=float(cfg.noise_act), mu=0.0, batch=int(cfg.BATCH_SIZE), hidden=(cfg.L1, cfg.L2))
+        points.append(jid)
+        records += [dict(rec) for _ in range(int(seeds) * int(chargers))]
+    return records, points, skipped
+
+
+TUNED_RUNNABLE = tuple(f"{c:02d}" for c in range(81) if c // 27 != 2 and (c // 3) % 3 != 0)   # the 36 points tuned_grid keeps
 
 
 W2T_FLOATS = 32 * 4 * 64 * 64          # SHEMS_W2T_FLOATS: [4 k-tiles][8 n-tiles][m | v | p | target][64][64] per network
@@ -57,6 +145,11 @@ def _declare_group():
     L.shems_ddpg_group_actor_grad.argtypes = [PD, PG, vp]
     L.shems_ddpg_group_actor_apply.argtypes = [PD, PG, C.c_double, C.c_double, C.c_double, vp]
     L.shems_minmax_group_dev.argtypes = [PR, PG, i64, i64, C.c_uint64, vp, vp, vp]
+    L.shems_group_hparams_check.argtypes = [C.POINTER(HParams), C.c_int32]
+    L.shems_act_step_group_hp_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, PT, vp, vp, vp, PR, C.POINTER(RingWindow), vp]
+    L.shems_ddpg_group_update_hp.argtypes = [PD, PR, PG, PT, vp, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, C.c_int32, vp]
+    for fn in ("shems_group_hparams_check", "shems_act_step_group_hp_dev", "shems_ddpg_group_update_hp"):
+        getattr(L, fn).restype = C.c_int
     for fn in ("shems_act_step_group_dev", "shems_ddpg_group_critic_grad", "shems_ddpg_group_critic_apply",
                "shems_ddpg_group_actor_grad", "shems_ddpg_group_actor_apply", "shems_minmax_group_dev"):
         getattr(L, fn).restype = C.c_int
@@ -85,19 +178,34 @@ class LearnerGroup:
     # bit-identical to Agent.replay).  Default: throughput from TP_MIN_LEARNERS learners up.
     TP_MIN_LEARNERS = 16
 
-    def __init__(self, count, envs_per_learner, seed=1231, rng_seed=None, capacity=MEM_SIZE, sigma=NOISE_SIGMA, device=None, form=None, tiled=None):
+    def __init__(self, count, envs_per_learner, seed=1231, rng_seed=None, capacity=MEM_SIZE, sigma=NOISE_SIGMA, device=None, form=None, tiled=None,
+                 hparams=None):
         """tiled (throughput form only; default on, SHEMS_GROUP_TILED=0 switches it off): the layer-2 state of both networks (W2, its
         ADAM moments, the target's W2) is kept in the TILED working layout (shems_group_w2t, include/shems_hip.h) while the group trains:
         one contiguous 64 KB piece per 64 x 64 tile for the update's W2-gradient / ADAM launches (4.78 against 3.85 TB/s), read from
         there by the forward / D1 launches and by the fused act/step launch.  The Flux-order blocks -- what `learners[l].actor` etc. ARE --
         keep everything else and are the API's view of W2: `flux_()` brings their W2 ranges up to date (call it before reading a learner's
         tensors, evaluating a learner through its Agent, or saving), `Agent.set_params` on a learner of the group is noticed by itself,
-        any other write into those tensors must be followed by `flux_changed()`."""
+        any other write into those tensors must be followed by `flux_changed()`.
+
+        hparams: None (every learner trains with today's values through the shared entry points), or `count` mappings, learner l's with
+        the keys of HPARAM_KEYS (eta_act, eta_crit, gamma, tau, sigma, mu, batch, hidden; a missing key takes today's default): the group
+        then runs the throughput form whatever its size, through the per-learner entry points (shems_ddpg_group_update_hp,
+        shems_act_step_group_hp_dev), and learners[l] carries learner l's values.  The records are checked and uploaded once, here.
+        Refused, naming the learner: batch > 128, hidden wider than (250, 500), noise_type other than "gn", a per-learner mem_size."""
         import os
         import torch
         self.torch = torch
         self.L = _declare_group()
         self.count, self.envs_per_learner, self.capacity = int(count), int(envs_per_learner), int(capacity)
+        self.hparams, self._hp_host, self._hp_dev = None, None, None
+        if hparams is not None:                    # every argument error before any device work
+            if form == "latency":
+                raise ValueError("per-learner hyper-parameters run on the throughput form: form='latency' cannot take hparams")
+            if self.count < 1:
+                raise ValueError("a learner group needs count >= 1")
+            self.hparams, self._hp_host = _hparams_records(self.count, hparams, sigma, self.capacity)
+            form = "throughput"
         self.form = form if form is not None else ("throughput" if self.count >= self.TP_MIN_LEARNERS else "latency")
         if self.form not in ("throughput", "latency"):
             raise ValueError("form must be 'throughput' or 'latency'")
@@ -130,14 +238,27 @@ class LearnerGroup:
             v = lambda name: self.slab[l, layout[name][0]:layout[name][0] + layout[name][1]]
             tens = {k: v(k) for k in ("actor", "critic", "actor_t", "critic_t", "m_actor", "v_actor", "m_critic", "v_critic",
                                       "grad_actor", "grad_critic", "s_min", "s_max", "ws", "losses")}
-            self.learners.append(Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=sigma, device=self.device, tensors=tens))
+            if self.hparams is None:
+                self.learners.append(Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=sigma, device=self.device, tensors=tens))
+            else:                                  # smaller networks come zero-padded (ddpg.pad_net) and stay so under training
+                h = self.hparams[l]
+                ag = Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=h["sigma"], mu=h["mu"], device=self.device, tensors=tens,
+                           hidden=h["hidden"])
+                ag.gamma, ag.tau, ag.batch, ag.eta_act, ag.eta_crit = h["gamma"], h["tau"], h["batch"], h["eta_act"], h["eta_crit"]
+                self.learners.append(ag)
             if self.tiled:
                 self.learners[-1]._before_param_write = self._before_flux_write
             done = v("ring_done").view(torch.uint8)[:self.capacity]
             self.rings.append(ReplayRing(self.capacity, tensors=(v("ring_s").view(self.capacity, STATE), v("ring_a").view(self.capacity, ACTION),
                                                                  v("ring_r"), v("ring_s2").view(self.capacity, STATE), done)))
+        if self._hp_host is not None:              # the records, once, in a small device buffer the group owns
+            raw = np.frombuffer(bytes(self._hp_host), dtype=np.uint8).copy()
+            self._hp_dev = torch.from_numpy(raw).to(self.device)
         self.updates = 0
         self.tick = 0
+
+    def _hp_ptr(self):
+        return C.c_void_p(self._hp_dev.data_ptr())
 
     # ------------------------------------------------------------------
     def struct(self):
@@ -220,7 +341,12 @@ class LearnerGroup:
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
         r0 = self.rings[0].struct()
         w = RingWindow(*window) if window is not None else None
-        if self._use_tiled():
+        if self._hp_dev is not None:               # learner l's noise mu / sigma from its record
+            t = self.w2t_struct() if self._use_tiled() else None
+            _capi.check(self.L.shems_act_step_group_hp_dev(C.byref(v), C.byref(p), C.byref(g), C.byref(t) if t is not None else None, self._hp_ptr(),
+                                                           ptr(a_out), ptr(returns_acc), C.byref(r0) if w is not None else None,
+                                                           C.byref(w) if w is not None else None, self._stream()))
+        elif self._use_tiled():
             t = self.w2t_struct()
             _capi.check(self.L.shems_act_step_group_tiled_dev(C.byref(v), C.byref(p), C.byref(g), C.byref(t), ptr(a_out), ptr(returns_acc),
                                                               C.byref(r0) if w is not None else None, C.byref(w) if w is not None else None,
@@ -240,7 +366,15 @@ class LearnerGroup:
         d = a0._ddpg_args()
         st = self._stream()
         tick = self.updates if tick is None else tick
-        if self._use_tiled():
+        if self._hp_dev is not None:               # learner l's batch / gamma / tau / eta from its record
+            tl = self._use_tiled()
+            t = self.w2t_struct() if tl else None
+            _capi.check(self.L.shems_ddpg_group_update_hp(C.byref(d), C.byref(r0), C.byref(g), C.byref(t) if tl else None, self._hp_ptr(),
+                                                          len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.bp_critic[0], a0.bp_critic[1],
+                                                          a0.bp_actor[0], a0.bp_actor[1], 1 if self.store_grad else 0, st))
+            if tl:
+                self._flux_valid = False
+        elif self._use_tiled():
             t = self.w2t_struct()
             _capi.check(self.L.shems_ddpg_group_update_tiled(C.byref(d), C.byref(r0), C.byref(g), C.byref(t), len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF,
                                                              a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1],
