@@ -516,6 +516,31 @@ int shems_act_step_group_hp_dev(const shems_view *v, const shems_act_params *p0,
 int shems_ddpg_group_update_hp(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *t,
                                const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double bp1_crit,
                                double bp2_crit, double bp1_act, double bp2_act, int32_t flags, void *stream);
+/* ------------------------------------------- the wide group form: learner groups on the layer-by-layer path -- */
+/* A learner group whose networks have one padded hidden size (l1, l2) up to 4096 (the tuned grid's (300, 600); smaller learners are
+ * zero-padded into it and stay so) and whose learners' batches reach 256.  One update pass holds P = max(128, max_batch rounded up to
+ * 32) minibatch rows; learner l's rows batch_l .. P-1 are zero and masked.  Every launch runs all learners (grid z / x = learner),
+ * so the launch count does not depend on the group's size.  The shems_ddpg blocks of d0, learner l's at + l * g->stride_bytes,
+ * are carved for (l1, l2) by shems_wide_params, ws for P by shems_wide_group_workspace_floats. */
+/* shems_group_hparams_check with batch in 1..max_batch, max_batch <= 256. */
+int shems_group_hparams_check_wide(const shems_group_hparams *host_hp, int32_t count, int32_t max_batch);
+/* Floats of one learner's ws for pass width P (= shems_wide_workspace_floats for max_batch <= 128). */
+int shems_wide_group_workspace_floats(int32_t l1, int32_t l2, int32_t max_batch, int64_t *out);
+/* replay() (DDPG.jl:121-145) for every learner: the launches of shems_wide_critic_grad_ex, _critic_apply, _actor_grad and
+ * _actor_apply_pub, each once for the whole group.  Learner l samples the first batch_l draws of the stream (seed + l, tick) (as
+ * shems_ddpg_sample_indices).  d_hp: learner l's batch (clamped to 1..max_batch on the device), gamma, tau and eta (k1 formed on the
+ * device); NULL: d0's batch, gamma and tau and eta_crit / eta_act for every learner.  The ADAM beta powers are shared.  At P = 128
+ * and without records, learner l's results are bit-identical to the single-learner wide entry points on its blocks with seed + l. */
+int shems_wide_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
+                            const shems_group_hparams *d_hp, int32_t max_batch, int64_t ring_len, uint64_t seed, uint32_t tick,
+                            double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, void *stream);
+/* The fused vector step (shems_wide_act_step_dev) for a group, four launches for all learners: env i is driven by learner
+ * i / envs_per_learner; Gaussian noise only, keyed by the global env index, with d_hp[l].noise_mu / noise_sigma (NULL: p0's).  The
+ * ring window applies inside each learner's env block, as in shems_act_step_group_dev.  d_ws: 16-byte aligned,
+ * shems_wide_act_workspace_floats(l1, l2, n_envs) floats. */
+int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
+                                  const shems_group_hparams *d_hp, float *d_ws, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                                  const shems_ring_window *window, void *stream);
 /* min_max_buffer for every learner of the group (learner l: Philox key seed + l). */
 int shems_minmax_group_dev(const shems_replay *ring0, const shems_group *g, int64_t ring_len, int64_t count,
                            uint64_t seed, float *d_s_min0, float *d_s_max0, void *stream);

@@ -1039,6 +1039,18 @@ __global__ __launch_bounds__(256) void k_adam_soft(AdamCtx c, int64_t gstride)
     const int i0 = 4 * ((int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x);
     if (i0 < c.n) adam_vec4(c, i0);
 }
+// A learner group with per-learner records (shems_wide_group_update): learner l = grid z takes eta and tau from hp[l] and forms
+// k1 = eta_l / (1 - bp1) here, a true Float64 division (the host's quotient for the same eta, bit for bit).
+__global__ __launch_bounds__(256) void k_adam_soft_hp(AdamCtx c, int64_t gstride, const shems_group_hparams *hp, int critic)
+{
+    const int64_t l = blockIdx.z;
+    gshift(c, l * gstride);
+    c.eta = critic ? hp[l].eta_crit : hp[l].eta_act;
+    c.k1 = c.eta / (1.0 - c.bp1);
+    c.tau = hp[l].tau;
+    const int i0 = 4 * ((int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x);
+    if (i0 < c.n) adam_vec4(c, i0);
+}
 // (two elements per thread -- twice the workgroups, 252 of the 256 CUs covered -- was measured inside the noise of the 7-launch form in
 // round 4, 40.1-43.6 against 40.2-41.4 us, and removed)
 
@@ -1724,6 +1736,20 @@ int adam_soft_sweep(float *p, const float *g, float *m, float *v, float *target,
         if (((uintptr_t)q & 15) != 0) return set_error(SHEMS_ERR_ARG, "adam_soft_sweep: buffers must be 16-byte aligned");
     const AdamCtx c{p, g, m, v, target, publish, n, 0, eta, bp1, bp2, gscale, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), tau};
     hipLaunchKernelGGL(k_adam_soft, dim3((n + 1023) / 1024, 1, 1), dim3(256), 0, st, c, (int64_t)0);
+    return hip_ok(hipGetLastError(), "k_adam_soft launch");
+}
+int adam_soft_sweep_group(float *p, const float *g, float *m, float *v, float *target, int n, double eta, double bp1, double bp2, float tau,
+                          int count, int64_t gstride_bytes, const shems_group_hparams *hp, bool critic, hipStream_t st)
+{
+    if (int rc = check_adam(bp1, bp2, "adam_soft_sweep_group")) return rc;
+    if (!p || !g || !m || !v || !target || n < 1 || count < 1 || count > 65535 || (gstride_bytes & 15) != 0)
+        return set_error(SHEMS_ERR_ARG, "adam_soft_sweep_group: bad buffers");
+    for (const void *q : {(const void *)p, (const void *)g, (const void *)m, (const void *)v, (const void *)target})
+        if (((uintptr_t)q & 15) != 0) return set_error(SHEMS_ERR_ARG, "adam_soft_sweep_group: buffers must be 16-byte aligned");
+    const AdamCtx c{p, g, m, v, target, nullptr, n, 0, eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), tau};
+    const dim3 grid((n + 1023) / 1024, 1, (unsigned)count);
+    if (hp) hipLaunchKernelGGL(k_adam_soft_hp, grid, dim3(256), 0, st, c, gstride_bytes, hp, critic ? 1 : 0);
+    else hipLaunchKernelGGL(k_adam_soft, grid, dim3(256), 0, st, c, gstride_bytes);
     return hip_ok(hipGetLastError(), "k_adam_soft launch");
 }
 }  // namespace shems

@@ -1216,13 +1216,12 @@ extern "C" int shems_ddpg_group_update_hp(const shems_ddpg *d, const shems_repla
 static_assert(sizeof(shems_group_hparams) == 40 && offsetof(shems_group_hparams, gamma) == 16 && offsetof(shems_group_hparams, noise_mu) == 24 &&
               offsetof(shems_group_hparams, batch) == 32, "shems_group_hparams: 40 bytes, the layout of include/shems_hip.h and group.HParams");
 
-extern "C" int shems_group_hparams_check(const shems_group_hparams *hp, int32_t count)
+static int hparams_check(const char *fn, const shems_group_hparams *hp, int32_t count, int max_batch)
 {
-    const char *fn = "shems_group_hparams_check";
     if (!hp || count < 1) return set_error(SHEMS_ERR_ARG, "%s: need count >= 1 records", fn);
     for (int32_t l = 0; l < count; ++l) {
         const shems_group_hparams &h = hp[l];
-        if (h.batch < 1 || h.batch > BP) return set_error(SHEMS_ERR_ARG, "%s: learner %d: batch %d outside 1..128", fn, l, h.batch);
+        if (h.batch < 1 || h.batch > max_batch) return set_error(SHEMS_ERR_ARG, "%s: learner %d: batch %d outside 1..%d", fn, l, h.batch, max_batch);
         if (!(std::isfinite(h.eta_act) && h.eta_act > 0.0)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: eta_act %g must be finite and > 0", fn, l, h.eta_act);
         if (!(std::isfinite(h.eta_crit) && h.eta_crit > 0.0)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: eta_crit %g must be finite and > 0", fn, l, h.eta_crit);
         if (!(h.tau > 0.0f && h.tau <= 1.0f)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: tau %g outside (0, 1]", fn, l, (double)h.tau);
@@ -1233,6 +1232,17 @@ extern "C" int shems_group_hparams_check(const shems_group_hparams *hp, int32_t 
         if (h.reserved != 0) return set_error(SHEMS_ERR_ARG, "%s: learner %d: reserved must be 0", fn, l);
     }
     return SHEMS_OK;
+}
+extern "C" int shems_group_hparams_check(const shems_group_hparams *hp, int32_t count)
+{
+    return hparams_check("shems_group_hparams_check", hp, count, BP);
+}
+/* the wide group form (shems_wide_group_update): batch in 1..max_batch, max_batch <= 256 */
+extern "C" int shems_group_hparams_check_wide(const shems_group_hparams *hp, int32_t count, int32_t max_batch)
+{
+    if (max_batch < 1 || max_batch > 256)
+        return set_error(SHEMS_ERR_ARG, "shems_group_hparams_check_wide: max_batch must be in 1..256 (got %d)", max_batch);
+    return hparams_check("shems_group_hparams_check_wide", hp, count, max_batch);
 }
 
 static int w2_layout(const char *fn, bool to_tiled, const shems_ddpg *d, const shems_group *g, const shems_group_w2t *t, void *stream)

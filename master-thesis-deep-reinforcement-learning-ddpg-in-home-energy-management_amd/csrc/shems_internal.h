@@ -29,12 +29,20 @@ int check_view(const shems_view *v, const char *fn);    // every entry point tha
 // on any parameter count: the wide-network path (shems_wide.hip) applies its gradients with it.
 int adam_soft_sweep(float *p, const float *g, float *m, float *v, float *target, float *publish, int n, double eta, double bp1, double bp2,
                     double gscale, float tau, hipStream_t st);
+// The same sweep for `count` learners of a group (learner l: every block + l * gstride_bytes) in one launch, grad_scale 1, no publish
+// copy.  hp: learner l's eta and tau from hp[l] (k1 formed on the device); null: eta / tau for every learner.
+int adam_soft_sweep_group(float *p, const float *g, float *m, float *v, float *target, int n, double eta, double bp1, double bp2, float tau,
+                          int count, int64_t gstride_bytes, const shems_group_hparams *hp, bool critic, hipStream_t st);
 // shems_wide.hip: forward pass of an actor (9 -> l1 -> l2 -> 2) of any hidden sizes for m observations, up to the output layer's partial
 // sums: d_part [*n_partials][m][2] (b3 not included; the caller adds b3 and the partials in index order).  d_ws holds
 // wide_act_ws_floats(l1, l2, m) floats of scratch (normalised observations, layer 1, then -- at wide_act_part_offset -- the partials).
 int wide_actor_pre(const float *actor, const float *s_min, const float *s_max, int l1, int l2, const float *d_obs, int64_t m, float *d_ws,
                    float *d_part, int *n_partials, hipStream_t st);
 int64_t wide_act_ws_floats(int l1, int l2, int64_t m);
+// The same for a learner group (shems_wide_act_step_group_dev): env i = l * epl + r runs learner l's actor and normalisation (learner 0's
+// + l * stride floats); d_part holds learner l's partials at [l][*n_partials][epl][2].  The workspace is wide_act_ws_floats(l1, l2, count * epl).
+int wide_actor_pre_group(const float *actor0, const float *s_min0, const float *s_max0, int64_t stride, int count, int64_t epl, int l1, int l2,
+                         const float *d_obs, float *d_ws, float *d_part, int *n_partials, hipStream_t st);
 int64_t wide_act_part_offset(int l1, int64_t m);
 
 // ---- data-parallel replicas: the direct gradient exchange (csrc/shems_dp.hip owns the memory, csrc/shems_ddpg.hip the kernel) ---------

@@ -1842,6 +1842,25 @@ __global__ __launch_bounds__(256) void k_act_tail(ActArgs A, const float *__rest
     act_env_tail(A, i, b3[0] + p0, b3[1] + p1, 0, 0, nullptr);
 }
 
+// A learner group's tail (shems_wide_act_step_group_dev): env i is learner i / genvs's, whose b3, ring and (HP) noise record it uses;
+// its partials are at [learner][p][genvs][2].
+template <bool HP>
+__global__ __launch_bounds__(256) void k_act_tail_g(ActArgs A, const float *__restrict__ part, int n_part, const float *__restrict__ b3_0,
+                                                    const shems_group_hparams *hp)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.m) return;
+    const int64_t learner = i / A.genvs, r = i - learner * A.genvs, goff = learner * A.gstride;
+    const float *b3 = gsh(b3_0, goff);
+    const float2 *pp = reinterpret_cast<const float2 *>(part) + learner * n_part * A.genvs + r;
+    float p0 = 0.0f, p1 = 0.0f;
+    for (int p = 0; p < n_part; ++p) {
+        const float2 v = pp[(int64_t)p * A.genvs];
+        p0 += v.x; p1 += v.y;
+    }
+    act_env_tail<HP>(A, i, b3[0] + p0, b3[1] + p1, learner, goff, nullptr, nullptr, hp);
+}
+
 static int wide_act(const ActArgs &a, int l1, int l2, float *d_ws, hipStream_t st)
 {
     if (!d_ws || ((uintptr_t)d_ws & 15) != 0) return set_error(SHEMS_ERR_ARG, "shems_wide_act: 16-byte aligned workspace required");
@@ -1992,9 +2011,9 @@ int shems_wide_act_step_dev(const shems_view *v, const shems_act_params *p, int3
     return wide_act(a, l1, l2, d_ws, (hipStream_t)stream);
 }
 
-static int act_step_group(const char *fn, const shems_view *v, const shems_act_params *p0, const shems_group *g, const float *w2t, float *d_a,
-                          double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream,
-                          const shems_group_hparams *hp = nullptr)
+// The checks of a grouped fused step and its ActArgs (every group form)
+static int group_act_args(const char *fn, const shems_view *v, const shems_act_params *p0, const shems_group *g, float *d_a,
+                          double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, ActArgs &a)
 {
     if (int rc = check_act(p0, fn)) return rc;
     if (int rc = check_view(v, fn)) return rc;
@@ -2003,13 +2022,11 @@ static int act_step_group(const char *fn, const shems_view *v, const shems_act_p
     if (g->envs_per_learner < 32 || g->envs_per_learner % 32 != 0 || g->envs_per_learner * g->count != v->n_envs)
         return set_error(SHEMS_ERR_ARG, "%s: envs_per_learner must be a multiple of 32 and count * envs_per_learner == n_envs "
                          "(got %lld x %d for %lld envs)", fn, (long long)g->envs_per_learner, g->count, (long long)v->n_envs);
-    ActArgs a;
     std::memset(&a, 0, sizeof a);
     a.v = *v; a.p = *p0; a.obs = v->obs; a.m = v->n_envs; a.a_out = d_a;
     a.returns_acc = d_returns_acc;
     a.do_step = 1;
     a.gcount = g->count; a.gstride = g->count > 1 ? g->stride_bytes : 0; a.genvs = g->envs_per_learner;
-    a.w2t = w2t;
     a.tm_max = group_tm_max(g->envs_per_learner);
     if (ring0 && window && window->count > 0) {
         if (ring0->capacity <= 0 || !ring0->s || !ring0->a || !ring0->r || !ring0->s2 || !ring0->done)
@@ -2021,6 +2038,15 @@ static int act_step_group(const char *fn, const shems_view *v, const shems_act_p
                              (long long)window->offset, (long long)g->envs_per_learner);
         a.ring = *ring0; a.win = *window; a.use_ring = 1;
     }
+    return SHEMS_OK;
+}
+static int act_step_group(const char *fn, const shems_view *v, const shems_act_params *p0, const shems_group *g, const float *w2t, float *d_a,
+                          double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream,
+                          const shems_group_hparams *hp = nullptr)
+{
+    ActArgs a;
+    if (int rc = group_act_args(fn, v, p0, g, d_a, d_returns_acc, ring0, window, a)) return rc;
+    a.w2t = w2t;
     return dispatch_act(a, (hipStream_t)stream, hp);
 }
 
@@ -2049,6 +2075,29 @@ int shems_act_step_group_hp_dev(const shems_view *v, const shems_act_params *p0,
     if (t && (!t->actor || ((uintptr_t)t->actor & 15) != 0))
         return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t.actor must be a 16-byte aligned device pointer", fn);
     return act_step_group(fn, v, p0, g, t ? t->actor : nullptr, d_a, d_returns_acc, ring0, window, stream, d_hp);
+}
+
+int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
+                                  const shems_group_hparams *d_hp, float *d_ws, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                                  const shems_ring_window *window, void *stream)
+{
+    const char *fn = "shems_wide_act_step_group_dev";
+    ActArgs a;
+    if (int rc = group_act_args(fn, v, p0, g, d_a, d_returns_acc, ring0, window, a)) return rc;
+    if (p0->noise_kind != SHEMS_NOISE_GAUSS) return set_error(SHEMS_ERR_ARG, "%s: a group draws Gaussian noise only (noise_kind %d)", fn, p0->noise_kind);
+    if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (g->count > 65535) return set_error(SHEMS_ERR_ARG, "%s: at most 65535 learners", fn);
+    if (!d_ws || ((uintptr_t)d_ws & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: 16-byte aligned workspace required", fn);
+    hipStream_t st = (hipStream_t)stream;
+    float *part = d_ws + wide_act_part_offset(l1, a.m);
+    int n_part = 0;
+    if (int rc = wide_actor_pre_group(p0->actor, p0->s_min, p0->s_max, a.gstride / 4, g->count, g->envs_per_learner, l1, l2, a.obs, d_ws, part,
+                                      &n_part, st)) return rc;
+    const float *b3 = p0->actor + ((int64_t)kIn * l1 + l1 + (int64_t)l1 * l2 + l2 + (int64_t)l2 * kOut);
+    const dim3 grid((unsigned)((a.m + 255) / 256));
+    if (d_hp) hipLaunchKernelGGL(k_act_tail_g<true>, grid, dim3(256), 0, st, a, part, n_part, b3, d_hp);
+    else hipLaunchKernelGGL(k_act_tail_g<false>, grid, dim3(256), 0, st, a, part, n_part, b3, d_hp);
+    return hip_ok(hipGetLastError(), "k_act_tail_g launch");
 }
 
 }  // extern "C"

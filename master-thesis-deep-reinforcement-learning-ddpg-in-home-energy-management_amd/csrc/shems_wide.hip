@@ -27,6 +27,7 @@
 
 #include "philox.h"
 #include "shems_internal.h"
+#include "shems_adam.h"
 
 namespace shems {
 
@@ -53,68 +54,26 @@ struct GemmArgs {
     int head_n;
 };
 
+// Learner groups (shems_wide_group_*): per operand, the float distance between learner l's copy and learner l - 1's.  A learner's
+// networks, workspace and ring lie in its slab (one stride for all of them); the fused step's activations lie in a learner's env rows.
+struct GStride { int64_t a, b, c, bias, gate, hw, ho; };
+__device__ __forceinline__ GemmArgs gemm_at(GemmArgs G, const GStride &s, int64_t l)
+{
+    auto sh = [&](auto *p, int64_t d) { return p ? p + l * d : p; };
+    G.A = sh(G.A, s.a); G.B = sh(G.B, s.b); G.C = sh(G.C, s.c); G.bias = sh(G.bias, s.bias); G.gate = sh(G.gate, s.gate);
+    G.head_w = sh(G.head_w, s.hw); G.head_out = sh(G.head_out, s.ho);
+    return G;
+}
+
 __global__ __launch_bounds__(256) void k_wgemm(GemmArgs G)
 {
-    __shared__ float As[2][GK][GLD], Bs[2][GK][GLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int wi = wave >> 1, wj = wave & 1;
-    const int64_t m0 = (int64_t)blockIdx.x * GT, n0 = (int64_t)blockIdx.y * GT;
-    const bool a_kfast = G.sak == 1, b_jfast = G.sbj == 1;
-    // element e = tid + 256 r of a 64 x GK operand tile: (row, k) with the memory-contiguous index fastest across threads
-    int ai[GR], ak[GR], bj[GR], bk[GR];
-#pragma unroll
-    for (int r = 0; r < GR; ++r) {
-        const int e = tid + 256 * r;
-        ai[r] = a_kfast ? e >> GKB : e & 63;  ak[r] = a_kfast ? e & (GK - 1) : e >> 6;
-        bj[r] = b_jfast ? e & 63 : e >> GKB;  bk[r] = b_jfast ? e >> 6 : e & (GK - 1);
-    }
-    // the global loads of stage s + 1 are in flight while stage s is multiplied; double-buffered LDS, one barrier per stage.  (With
-    // thousands of workgroups the latency is hidden by occupancy: a deeper register ring and unpredicated clamped loads, which pay off
-    // in the small-M kernel below, measured slower here -- 480-490 against 443 us for the vector step of 65 536 envs.)
-    float ra[GR], rb[GR];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int r = 0; r < GR; ++r) {
-            const int64_t i = m0 + ai[r], j = n0 + bj[r];
-            const int ka = k0 + ak[r], kb = k0 + bk[r];
-            ra[r] = (i < G.M && ka < G.K) ? G.A[i * G.sai + ka * G.sak] : 0.0f;
-            rb[r] = (j < G.N && kb < G.K) ? G.B[kb * G.sbk + j * G.sbj] : 0.0f;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int r = 0; r < GR; ++r) { As[buf][ak[r]][ai[r]] = ra[r]; Bs[buf][bk[r]][bj[r]] = rb[r]; }
-    };
-    wf32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    const int nst = (G.K + GK - 1) / GK;
-    for (int s = 0; s < nst; ++s) {
-        const int buf = s & 1;
-        if (s + 1 < nst) fetch((s + 1) * GK);
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[buf][kk + lh][wi * 32 + li], Bs[buf][kk + lh][wj * 32 + li], acc, 0, 0, 0);
-        if (s + 1 < nst) stash(buf ^ 1);
-        __syncthreads();
-    }
-    const int64_t j = n0 + wj * 32 + li;
-    if (j < G.N) {
-        const float bj_ = G.bias ? G.bias[j] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t i = m0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (i < G.M) {
-                float v = acc[r] + bj_;
-                if (G.relu) v = fmaxf(v, 0.0f);
-                if (G.gate) v = G.gate[i * G.ldg + j] > 0.0f ? v : 0.0f;
-                G.C[i * G.ldc + j] = v;
-            }
-        }
-    }
+#include "wgemm_body.h"
+}
+// grid z = learner
+__global__ __launch_bounds__(256) void k_wgemm_g(GemmArgs G0, GStride S)
+{
+    const GemmArgs G = gemm_at(G0, S, blockIdx.z);
+#include "wgemm_body.h"
 }
 
 // The vector step's layer 2 (M = tens of thousands of envs, N = l2, K = l1: 98 % of its FLOPs): 128 x 128 tile, each wave a 64 x 64
@@ -130,129 +89,14 @@ typedef float wf32x4 __attribute__((ext_vector_type(4)));
 template <bool HEAD, bool V4>
 __global__ __launch_bounds__(256) void k_wgemm128(GemmArgs G)
 {
-    __shared__ __attribute__((aligned(16))) float As[2][GK][BLD], Bs[2][GK][BLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int wi = wave >> 1, wj = wave & 1;
-    const int64_t m0 = (int64_t)blockIdx.x * BT, n0 = (int64_t)blockIdx.y * BT;
-    const bool a_kfast = G.sak == 1, b_jfast = G.sbj == 1;
-    int ai[BR], ak[BR], bj[BR], bk[BR];
-#pragma unroll
-    for (int r = 0; r < BR; ++r) {
-        const int e = tid + 256 * r;
-        ai[r] = a_kfast ? e >> GKB : e & (BT - 1);  ak[r] = a_kfast ? e & (GK - 1) : e >> 7;
-        bj[r] = b_jfast ? e & (BT - 1) : e >> GKB;  bk[r] = b_jfast ? e >> 7 : e & (GK - 1);
-    }
-    float ra[BR], rb[BR];
-    wf32x4 va[2], vb[2];
-    auto fetch = [&](int k0) {
-        if constexpr (V4) {
-            // quad f = tid + 256 r: A row f >> 2, k = 4 (f & 3) ..; B row k = f >> 5, j = 4 (f & 31) ..
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const int f = tid + 256 * r;
-                const int64_t i = m0 + (f >> 2), j = n0 + 4 * (f & 31);
-                const int ka = k0 + 4 * (f & 3), kb = k0 + (f >> 5);
-                const wf32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-                va[r] = (i < G.M && ka < G.K) ? *reinterpret_cast<const wf32x4 *>(G.A + i * G.sai + ka) : z;
-                vb[r] = (j < G.N && kb < G.K) ? *reinterpret_cast<const wf32x4 *>(G.B + kb * G.sbk + j) : z;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < BR; ++r) {
-                const int64_t i = m0 + ai[r], j = n0 + bj[r];
-                const int ka = k0 + ak[r], kb = k0 + bk[r];
-                ra[r] = (i < G.M && ka < G.K) ? G.A[i * G.sai + ka * G.sak] : 0.0f;
-                rb[r] = (j < G.N && kb < G.K) ? G.B[kb * G.sbk + j * G.sbj] : 0.0f;
-            }
-        }
-    };
-    auto stash = [&](int buf) {
-        if constexpr (V4) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const int f = tid + 256 * r;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) As[buf][4 * (f & 3) + c][f >> 2] = va[r][c];
-                *reinterpret_cast<wf32x4 *>(&Bs[buf][f >> 5][4 * (f & 31)]) = vb[r];
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < BR; ++r) { As[buf][ak[r]][ai[r]] = ra[r]; Bs[buf][bk[r]][bj[r]] = rb[r]; }
-        }
-    };
-    wf32x16 acc[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.0f;
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    const int nst = (G.K + GK - 1) / GK;
-    for (int s = 0; s < nst; ++s) {
-        const int buf = s & 1;
-        if (s + 1 < nst) fetch((s + 1) * GK);
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2) {
-            const float a0 = As[buf][kk + lh][wi * 64 + li], a1 = As[buf][kk + lh][wi * 64 + 32 + li];
-            const float b0 = Bs[buf][kk + lh][wj * 64 + li], b1 = Bs[buf][kk + lh][wj * 64 + 32 + li];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if (s + 1 < nst) stash(buf ^ 1);
-        __syncthreads();
-    }
-    if constexpr (!HEAD) {
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            const int64_t j = n0 + wj * 64 + y * 32 + li;
-            if (j >= G.N) continue;
-            const float bj_ = G.bias ? G.bias[j] : 0.0f;
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int64_t i = m0 + wi * 64 + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (i < G.M) {
-                        float v = acc[x][y][r] + bj_;
-                        if (G.relu) v = fmaxf(v, 0.0f);
-                        if (G.gate) v = G.gate[i * G.ldg + j] > 0.0f ? v : 0.0f;
-                        G.C[i * G.ldc + j] = v;
-                    }
-                }
-        }
-    } else {
-        // this lane's two columns: bias and the head's weights (zero beyond N, so padded columns add nothing)
-        float bb[2], w3[2][2];
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            const int64_t j = n0 + wj * 64 + y * 32 + li;
-            const bool in = j < G.N;
-            const int64_t jc = in ? j : 0;
-            bb[y] = in && G.bias ? G.bias[jc] : 0.0f;
-#pragma unroll
-            for (int o = 0; o < 2; ++o) w3[y][o] = in && o < G.head_n ? G.head_w[jc * G.head_n + o] : 0.0f;
-        }
-        float *out = G.head_out + ((int64_t)blockIdx.y * 2 + wj) * G.M * G.head_n;
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v0 = fmaxf(acc[x][0][r] + bb[0], 0.0f), v1 = fmaxf(acc[x][1][r] + bb[1], 0.0f);
-                float s0 = v0 * w3[0][0] + v1 * w3[1][0], s1 = v0 * w3[0][1] + v1 * w3[1][1];
-#pragma unroll
-                for (int off = 16; off > 0; off >>= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }     // over the half's 32 lanes
-                const int64_t i = m0 + wi * 64 + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (li == 0 && i < G.M) {
-                    out[i * G.head_n] = s0;
-                    if (G.head_n > 1) out[i * G.head_n + 1] = s1;
-                }
-            }
-    }
+#include "wgemm128_body.h"
+}
+// grid z = learner
+template <bool HEAD, bool V4>
+__global__ __launch_bounds__(256) void k_wgemm128_g(GemmArgs G0, GStride S)
+{
+    const GemmArgs G = gemm_at(G0, S, blockIdx.z);
+#include "wgemm128_body.h"
 }
 
 // The minibatch-sized products (M <= a few hundred rows): few tiles and a long K.  One wave's chain of 32x32x2 MFMAs costs 32 cycles
@@ -266,81 +110,16 @@ struct GemmBatch { GemmArgs g[GMAX]; };
 __global__ __launch_bounds__(256) void k_wgemm_sk(GemmBatch B)
 {
     const GemmArgs &G = B.g[blockIdx.z];
-    if ((int64_t)blockIdx.x * 32 >= G.M || (int64_t)blockIdx.y * 32 >= G.N) return;      // (the grid is the largest problem's)
-    __shared__ float As[2][SK][SLD], Bs[2][SK][SLD];
-    __shared__ float red[4][16 * 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int64_t m0 = (int64_t)blockIdx.x * 32, n0 = (int64_t)blockIdx.y * 32;
-    const bool a_kfast = G.sak == 1, b_jfast = G.sbj == 1;
-    int ai[SR], ak[SR], bj[SR], bk[SR];
-#pragma unroll
-    for (int r = 0; r < SR; ++r) {
-        const int e = tid + 256 * r;
-        ai[r] = a_kfast ? e >> SKB : e & 31;  ak[r] = a_kfast ? e & (SK - 1) : e >> 5;
-        bj[r] = b_jfast ? e & 31 : e >> SKB;  bk[r] = b_jfast ? e >> 5 : e & (SK - 1);
-    }
-    // global loads run GP stages ahead in a ring of register slots; every load is unconditional, from a clamped (always valid) address,
-    // and the zero of an out-of-range element is selected when the slot is stashed (a load under a lane predicate is sunk into a branch
-    // behind s_waitcnt vmcnt(0), which serialises the ring).  One barrier per stage: stash(s) -> barrier -> MFMAs(s); buffer s & 1 was
-    // last read in stage s - 2, which every thread left before anyone passed barrier s - 1.
-    constexpr int GP = 2;
-    float ra[GP][SR], rb[GP][SR];
-    unsigned oka[GP], okb[GP];
-    auto fetch = [&](int k0, float (&xa)[SR], float (&xb)[SR], unsigned &ma, unsigned &mb) {
-        ma = mb = 0u;
-#pragma unroll
-        for (int r = 0; r < SR; ++r) {
-            const int64_t i = m0 + ai[r], j = n0 + bj[r];
-            const int ka = k0 + ak[r], kb = k0 + bk[r];
-            ma |= (i < G.M && ka < G.K) ? 1u << r : 0u;
-            mb |= (j < G.N && kb < G.K) ? 1u << r : 0u;
-            xa[r] = G.A[min(i, (int64_t)G.M - 1) * G.sai + min(ka, G.K - 1) * G.sak];
-            xb[r] = G.B[min(kb, G.K - 1) * G.sbk + min(j, (int64_t)G.N - 1) * G.sbj];
-        }
-    };
-    auto stash = [&](int buf, const float (&xa)[SR], const float (&xb)[SR], unsigned ma, unsigned mb) {
-#pragma unroll
-        for (int r = 0; r < SR; ++r) {
-            As[buf][ak[r]][ai[r]] = (ma >> r & 1u) ? xa[r] : 0.0f;
-            Bs[buf][bk[r]][bj[r]] = (mb >> r & 1u) ? xb[r] : 0.0f;
-        }
-    };
-    wf32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    const int nst = (G.K + SK - 1) / SK;
-#pragma unroll
-    for (int u = 0; u < GP; ++u) fetch(u * SK, ra[u], rb[u], oka[u], okb[u]);
-    for (int s0 = 0; s0 < nst; s0 += GP) {
-#pragma unroll
-        for (int u = 0; u < GP; ++u) {
-            const int s = s0 + u;
-            if (s < nst) {
-                const int buf = s & 1;
-                stash(buf, ra[u], rb[u], oka[u], okb[u]);
-                __syncthreads();
-                if (s + GP < nst) fetch((s + GP) * SK, ra[u], rb[u], oka[u], okb[u]);
-#pragma unroll
-                for (int kk = 0; kk < SK / 4; kk += 2)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[buf][wave * (SK / 4) + kk + lh][li], Bs[buf][wave * (SK / 4) + kk + lh][li], acc, 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][r * 64 + lane] = acc[r];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int e = tid + 256 * q, r = e >> 6, l2 = e & 63;
-        const int64_t i = m0 + (r & 3) + 8 * (r >> 2) + 4 * (l2 >> 5), j = n0 + (l2 & 31);
-        if (i < G.M && j < G.N) {
-            float v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-            if (G.bias) v += G.bias[j];
-            if (G.relu) v = fmaxf(v, 0.0f);
-            if (G.gate) v = G.gate[i * G.ldg + j] > 0.0f ? v : 0.0f;
-            G.C[i * G.ldc + j] = v;
-        }
-    }
+#include "wgemm_sk_body.h"
+}
+// A learner group's products: grid z = learner * n + product, learner l's operands at the learner-0 pointers + l * its stride.  Each
+// output element is summed in the same order as k_wgemm_sk's.
+struct GemmBatchG { GemmArgs g[GMAX]; GStride s[GMAX]; int n; };
+__global__ __launch_bounds__(256) void k_wgemm_sk_g(GemmBatchG B)
+{
+    const int q = (int)(blockIdx.z % (unsigned)B.n);
+    const GemmArgs G = gemm_at(B.g[q], B.s[q], blockIdx.z / (unsigned)B.n);
+#include "wgemm_sk_body.h"
 }
 
 static GemmArgs prod(const float *A, int64_t sai, int64_t sak, const float *B, int64_t sbk, int64_t sbj, float *C, int64_t ldc,
@@ -348,8 +127,11 @@ static GemmArgs prod(const float *A, int64_t sai, int64_t sak, const float *B, i
 {
     return GemmArgs{A, B, C, (int)M, N, K, sai, sak, sbk, sbj, ldc, bias, gate, ldg, relu};
 }
-// independent minibatch-sized products (one of M, N, K is the minibatch) in one launch
-static int gemm_multi(hipStream_t st, std::initializer_list<GemmArgs> list)
+// A learner group's replay(): `count` learners whose every buffer (networks, workspace, ring) is learner 0's + l * `stride` floats.
+// null: one learner, the single-learner launches.
+struct WGrp { int count; int64_t stride; };
+// independent minibatch-sized products (one of M, N, K is the minibatch) in one launch; a group: the same products of every learner
+static int gemm_multi(hipStream_t st, std::initializer_list<GemmArgs> list, const WGrp *grp = nullptr)
 {
     GemmBatch b;
     std::memset(&b, 0, sizeof b);
@@ -360,14 +142,24 @@ static int gemm_multi(hipStream_t st, std::initializer_list<GemmArgs> list)
         gx = std::max(gx, (unsigned)((g.M + 31) / 32));
         gy = std::max(gy, (unsigned)((g.N + 31) / 32));
     }
+    if (grp) {
+        GemmBatchG bg;
+        std::memset(&bg, 0, sizeof bg);
+        const int64_t s = grp->stride;
+        for (unsigned q = 0; q < n; ++q) { bg.g[q] = b.g[q]; bg.s[q] = GStride{s, s, s, s, s, 0, 0}; }
+        bg.n = (int)n;
+        hipLaunchKernelGGL(k_wgemm_sk_g, dim3(gx, gy, n * (unsigned)grp->count), dim3(256), 0, st, bg);
+        return hip_ok(hipGetLastError(), "k_wgemm_sk_g launch");
+    }
     hipLaunchKernelGGL(k_wgemm_sk, dim3(gx, gy, n), dim3(256), 0, st, b);
     return hip_ok(hipGetLastError(), "k_wgemm_sk launch");
 }
 static int gemm(hipStream_t st, const float *A, int64_t sai, int64_t sak, const float *B, int64_t sbk, int64_t sbj, float *C, int64_t ldc,
-                int64_t M, int N, int K, const float *bias = nullptr, int relu = 0, const float *gate = nullptr, int64_t ldg = 0)
+                int64_t M, int N, int K, const float *bias = nullptr, int relu = 0, const float *gate = nullptr, int64_t ldg = 0,
+                const WGrp *grp = nullptr)
 {
     GemmArgs g{A, B, C, (int)M, N, K, sai, sak, sbk, sbj, ldc, bias, gate, ldg, relu};
-    if (M <= 512) return gemm_multi(st, {g});
+    if (M <= 512 || grp) return gemm_multi(st, {g}, grp);
     hipLaunchKernelGGL(k_wgemm, dim3((unsigned)((M + GT - 1) / GT), (unsigned)((N + GT - 1) / GT)), dim3(256), 0, st, g);
     return hip_ok(hipGetLastError(), "k_wgemm launch");
 }
@@ -384,20 +176,21 @@ static WNet wnet(const float *P, int in, int l1, int l2, int out)
 }
 static int64_t wnet_size(int in, int l1, int l2, int out) { return (int64_t)in * l1 + l1 + (int64_t)l1 * l2 + l2 + (int64_t)l2 * out + out; }
 
-// The three layer products of a forward pass over WBP rows, as values: independent passes are launched layer by layer together.
+// The three layer products of a forward pass over `rows` (the pass width: WBP, or a group's P) rows, as values: independent passes are
+// launched layer by layer together.
 struct Fwd { GemmArgs l1, l2, l3; };
-static Fwd fwd_of(const WNet &n, const float *X, float *H1, float *H2, float *P)
+static Fwd fwd_of(const WNet &n, const float *X, float *H1, float *H2, float *P, int rows = WBP)
 {
-    return Fwd{prod(X, n.in, 1, n.W1, n.l1, 1, H1, n.l1, WBP, n.l1, n.in, n.b1, 1), prod(H1, n.l1, 1, n.W2, n.l2, 1, H2, n.l2, WBP, n.l2, n.l1, n.b2, 1),
-               prod(H2, n.l2, 1, n.W3, n.out, 1, P, n.out, WBP, n.out, n.l2, n.b3, 0)};
+    return Fwd{prod(X, n.in, 1, n.W1, n.l1, 1, H1, n.l1, rows, n.l1, n.in, n.b1, 1), prod(H1, n.l1, 1, n.W2, n.l2, 1, H2, n.l2, rows, n.l2, n.l1, n.b2, 1),
+               prod(H2, n.l2, 1, n.W3, n.out, 1, P, n.out, rows, n.out, n.l2, n.b3, 0)};
 }
 
 // X [m][in] -> H1 [m][l1], H2 [m][l2] (post-relu), P [m][out] (pre-activation of the last layer, b3 included)
-static int net_forward(hipStream_t st, const WNet &n, const float *X, int64_t m, float *H1, float *H2, float *P)
+static int net_forward(hipStream_t st, const WNet &n, const float *X, int64_t m, float *H1, float *H2, float *P, const WGrp *grp = nullptr)
 {
-    if (int rc = gemm(st, X, n.in, 1, n.W1, n.l1, 1, H1, n.l1, m, n.l1, n.in, n.b1, 1)) return rc;
-    if (int rc = gemm(st, H1, n.l1, 1, n.W2, n.l2, 1, H2, n.l2, m, n.l2, n.l1, n.b2, 1)) return rc;
-    return gemm(st, H2, n.l2, 1, n.W3, n.out, 1, P, n.out, m, n.out, n.l2, n.b3, 0);
+    if (int rc = gemm(st, X, n.in, 1, n.W1, n.l1, 1, H1, n.l1, m, n.l1, n.in, n.b1, 1, nullptr, 0, grp)) return rc;
+    if (int rc = gemm(st, H1, n.l1, 1, n.W2, n.l2, 1, H2, n.l2, m, n.l2, n.l1, n.b2, 1, nullptr, 0, grp)) return rc;
+    return gemm(st, H2, n.l2, 1, n.W3, n.out, 1, P, n.out, m, n.out, n.l2, n.b3, 0, nullptr, 0, grp);
 }
 
 // obs [m][9] -> (obs - s_min) / ((s_max - s_min) + 1f-8)  (normalize, MPS:55-57)
@@ -411,7 +204,7 @@ __global__ __launch_bounds__(256) void k_wnorm(const float *__restrict__ obs, co
     }
 }
 
-// ---- update workspace (floats; sample-major, WBP rows) ----------------------------------------------------------------------
+// ---- update workspace (floats; sample-major, WBP rows -- a group's pass width P rows) ----------------------------------------
 struct WWs {
     float *XS, *XS2, *XC, *XC2, *XQ;          // [WBP][9] normalize(s), normalize(s'); [WBP][11] [s; a], [s'; actor_target(s')], [s; actor(s)]
     float *R, *DONE, *Y, *Q, *Q2, *DQ, *DQA;  // [WBP]
@@ -421,24 +214,28 @@ struct WWs {
     float *ONES;                              // [WBP] ones: a bias gradient sum_m dY[m][n] is the product ones' dY, one more tile in a launch that runs anyway
     int64_t total;
 };
-static WWs wws(float *base, int l1, int l2)
+// (host and device: a group's kernels carve learner l's workspace themselves)
+__host__ __device__ static inline WWs wws(float *base, int l1, int l2, int P = WBP)
 {
     WWs w;
     int64_t o = 0;
     auto take = [&](int64_t n) { float *p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
-    w.XS = take(WBP * WSIN); w.XS2 = take(WBP * WSIN); w.XC = take(WBP * WCIN); w.XC2 = take(WBP * WCIN); w.XQ = take(WBP * WCIN);
-    w.R = take(WBP); w.DONE = take(WBP); w.Y = take(WBP); w.Q = take(WBP); w.Q2 = take(WBP); w.DQ = take(WBP); w.DQA = take(WBP);
-    w.IDX = reinterpret_cast<int32_t *>(take(WBP));
-    w.PA = take(WBP * WAIN); w.PT = take(WBP * WAIN); w.API = take(WBP * WAIN); w.DA = take(WBP * WCIN); w.D3 = take(WBP * WAIN);
-    w.T1 = take((int64_t)WBP * l1); w.T2 = take((int64_t)WBP * l2);
-    w.H1c = take((int64_t)WBP * l1); w.H2c = take((int64_t)WBP * l2);
-    w.H1a = take((int64_t)WBP * l1); w.H2a = take((int64_t)WBP * l2);
-    w.H1q = take((int64_t)WBP * l1); w.H2q = take((int64_t)WBP * l2);
-    w.G1 = take((int64_t)WBP * l1); w.G2 = take((int64_t)WBP * l2);
-    w.ONES = take(WBP);
+    w.XS = take(P * WSIN); w.XS2 = take(P * WSIN); w.XC = take(P * WCIN); w.XC2 = take(P * WCIN); w.XQ = take(P * WCIN);
+    w.R = take(P); w.DONE = take(P); w.Y = take(P); w.Q = take(P); w.Q2 = take(P); w.DQ = take(P); w.DQA = take(P);
+    w.IDX = reinterpret_cast<int32_t *>(take(P));
+    w.PA = take(P * WAIN); w.PT = take(P * WAIN); w.API = take(P * WAIN); w.DA = take(P * WCIN); w.D3 = take(P * WAIN);
+    w.T1 = take((int64_t)P * l1); w.T2 = take((int64_t)P * l2);
+    w.H1c = take((int64_t)P * l1); w.H2c = take((int64_t)P * l2);
+    w.H1a = take((int64_t)P * l1); w.H2a = take((int64_t)P * l2);
+    w.H1q = take((int64_t)P * l1); w.H2q = take((int64_t)P * l2);
+    w.G1 = take((int64_t)P * l1); w.G2 = take((int64_t)P * l2);
+    w.ONES = take(P);
     w.total = o;
     return w;
 }
+// A group's pass width: P = max(128, max_batch rounded up to 32)
+static int pass_width(int max_batch) { return std::max(WBP, (max_batch + 31) / 32 * 32); }
+constexpr int WPMAX = 256;               // the widest pass a group runs (batch <= 256)
 
 struct WPrep {
     shems_replay ring;
@@ -450,9 +247,8 @@ struct WPrep {
     WWs w;
 };
 // getData (MPS:31-42) + normalize: thread m = minibatch row m.  The sampler is shems_ddpg.hip's prep_load.
-__global__ __launch_bounds__(WBP) void k_wprep(WPrep A)
+__device__ __forceinline__ void wprep_row(const WPrep &A, int m)
 {
-    const int m = threadIdx.x;
     const bool live = m < A.batch;
     const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)A.seed, (uint32_t)(A.seed >> 32));
     const uint32_t wd = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
@@ -475,13 +271,35 @@ __global__ __launch_bounds__(WBP) void k_wprep(WPrep A)
     w.IDX[m] = live ? (int32_t)j : -1;
     w.ONES[m] = 1.0f;
 }
+__global__ __launch_bounds__(WBP) void k_wprep(WPrep A) { wprep_row(A, threadIdx.x); }
 
+// ---- a learner group (shems_wide_group_update): workgroup = learner, thread m = row m of the pass width P ----------------------------
+struct WGroupArgs {
+    shems_ddpg d0;                       // learner 0's blocks (learner l: + l * stride floats)
+    shems_replay ring0;
+    int64_t stride;                      // floats
+    int64_t ring_len;
+    uint64_t seed;
+    uint32_t tick;
+    int l1, l2, P, max_batch;
+    const shems_group_hparams *hp;       // null: d0's batch / gamma
+};
+__device__ __forceinline__ int wg_batch(const WGroupArgs &A, int l) { return min(max(A.hp ? (int)A.hp[l].batch : A.d0.batch, 1), A.max_batch); }
+__device__ __forceinline__ WWs wg_ws(const WGroupArgs &A, int l) { return wws(A.d0.ws + l * A.stride, A.l1, A.l2, A.P); }
+__global__ __launch_bounds__(WPMAX) void k_wprep_g(WGroupArgs A)
+{
+    const int l = blockIdx.x;
+    const int64_t off = (int64_t)l * A.stride * 4;
+    shems_replay r = A.ring0;
+    r.s = gsh(r.s, off); r.a = gsh(r.a, off); r.r = gsh(r.r, off); r.s2 = gsh(r.s2, off); r.done = gsh(r.done, off);
+    const WPrep p{r, A.ring_len, 0, 0, A.seed + (uint64_t)l, A.tick, wg_batch(A, l), A.d0.s_min + l * A.stride, A.d0.s_max + l * A.stride, wg_ws(A, l)};
+    wprep_row(p, threadIdx.x);
+}
 // a = tanh(P) for the live rows -> a_out [WBP][2] (may be null) and the action columns of a [WBP][11] critic input; workgroup 0: the
 // target actor's head into [s'; a'], workgroup 1: the actor's into a_pi and [s; a_pi]
-__global__ __launch_bounds__(WBP) void k_wtanh_cat(const float *__restrict__ P0, float *__restrict__ a0_out, float *__restrict__ cat0,
-                                                   const float *__restrict__ P1, float *__restrict__ a1_out, float *__restrict__ cat1, int batch)
+__device__ __forceinline__ void wtanh_cat_row(const float *__restrict__ P0, float *__restrict__ a0_out, float *__restrict__ cat0,
+                                              const float *__restrict__ P1, float *__restrict__ a1_out, float *__restrict__ cat1, int batch, int m)
 {
-    const int m = threadIdx.x;
     const float *P = blockIdx.x == 0 ? P0 : P1;
     float *a_out = blockIdx.x == 0 ? a0_out : a1_out, *cat = blockIdx.x == 0 ? cat0 : cat1;
     const float a0 = m < batch ? tanhf(P[2 * m]) : 0.0f, a1 = m < batch ? tanhf(P[2 * m + 1]) : 0.0f;
@@ -489,11 +307,23 @@ __global__ __launch_bounds__(WBP) void k_wtanh_cat(const float *__restrict__ P0,
     cat[m * WCIN + 9] = a0;
     cat[m * WCIN + 10] = a1;
 }
+__global__ __launch_bounds__(WBP) void k_wtanh_cat(const float *__restrict__ P0, float *__restrict__ a0_out, float *__restrict__ cat0,
+                                                   const float *__restrict__ P1, float *__restrict__ a1_out, float *__restrict__ cat1, int batch)
+{
+    wtanh_cat_row(P0, a0_out, cat0, P1, a1_out, cat1, batch, threadIdx.x);
+}
+// grid (2, learners)
+__global__ __launch_bounds__(WPMAX) void k_wtanh_cat_g(WGroupArgs A)
+{
+    const int l = blockIdx.y;
+    const WWs w = wg_ws(A, l);
+    wtanh_cat_row(w.PT, nullptr, w.XC2, w.PA, w.API, w.XQ, wg_batch(A, l), threadIdx.x);
+}
 
 // critic loss head (DDPG.jl:131-135): y = r + gamma (1 - done) q', dq = 2 (q - y) / B, loss = mean((q - y)^2)
-__global__ __launch_bounds__(WBP) void k_wloss(WWs w, float gamma, int batch, float *loss)
+// rows: the pass width; red: [rows] of LDS
+__device__ __forceinline__ void wloss_body(const WWs &w, float gamma, int batch, float *loss, int rows, float *red)
 {
-    __shared__ float red[WBP];
     const int m = threadIdx.x;
     const float y = w.R[m] + gamma * (1.0f - w.DONE[m]) * w.Q2[m];
     const float diff = m < batch ? w.Q[m] - y : 0.0f;
@@ -503,15 +333,25 @@ __global__ __launch_bounds__(WBP) void k_wloss(WWs w, float gamma, int batch, fl
     __syncthreads();
     if (m == 0) {
         float s = 0.0f;
-        for (int i = 0; i < WBP; ++i) s += red[i];
+        for (int i = 0; i < rows; ++i) s += red[i];
         loss[0] = s / (float)batch;
     }
 }
-
-// actor loss head (DDPG.jl:137-140): loss = -mean(q); error at the actor's pre-tanh output = d loss / d a_pi * (1 - a_pi^2)
-__global__ __launch_bounds__(WBP) void k_wactor_head(WWs w, int batch, float *loss)
+__global__ __launch_bounds__(WBP) void k_wloss(WWs w, float gamma, int batch, float *loss)
 {
     __shared__ float red[WBP];
+    wloss_body(w, gamma, batch, loss, WBP, red);
+}
+__global__ __launch_bounds__(WPMAX) void k_wloss_g(WGroupArgs A)
+{
+    __shared__ float red[WPMAX];
+    const int l = blockIdx.x;
+    wloss_body(wg_ws(A, l), A.hp ? A.hp[l].gamma : A.d0.gamma, wg_batch(A, l), A.d0.losses + l * A.stride, A.P, red);
+}
+
+// actor loss head (DDPG.jl:137-140): loss = -mean(q); error at the actor's pre-tanh output = d loss / d a_pi * (1 - a_pi^2)
+__device__ __forceinline__ void wactor_head_body(const WWs &w, int batch, float *loss, int rows, float *red)
+{
     const int m = threadIdx.x;
     const bool live = m < batch;
 #pragma unroll
@@ -523,33 +363,46 @@ __global__ __launch_bounds__(WBP) void k_wactor_head(WWs w, int batch, float *lo
     __syncthreads();
     if (m == 0) {
         float s = 0.0f;
-        for (int i = 0; i < WBP; ++i) s += red[i];
+        for (int i = 0; i < rows; ++i) s += red[i];
         loss[1] = -s / (float)batch;
     }
+}
+__global__ __launch_bounds__(WBP) void k_wactor_head(WWs w, int batch, float *loss)
+{
+    __shared__ float red[WBP];
+    wactor_head_body(w, batch, loss, WBP, red);
+}
+__global__ __launch_bounds__(WPMAX) void k_wactor_head_g(WGroupArgs A)
+{
+    __shared__ float red[WPMAX];
+    const int l = blockIdx.x;
+    wactor_head_body(wg_ws(A, l), wg_batch(A, l), A.d0.losses + l * A.stride, A.P, red);
 }
 
 // Zygote's pullback of Chain(Dense, Dense, Dense) for the error d3 [WBP][out] at the last layer's pre-activation: parameter
 // gradients into `grad` (flat Flux layout; null = input gradient only); dX [WBP][in] = d loss / d input if asked for.  X, H1, H2: what
 // the forward pass kept.  Three launches: {gW3, gb3, G2}, {gW2, gb2, G1}, {gW1, gb1, dX} -- within one, nothing depends on anything.
+// rows: the pass width (WBP; a group's P); grp: a learner group (every product of every learner in the same three launches).
 static int net_backward(hipStream_t st, const WNet &n, const float *X, const float *H1, const float *H2, const float *d3, float *grad,
-                        float *G1, float *G2, float *dX, const float *ones)
+                        float *G1, float *G2, float *dX, const float *ones, int rows = WBP, const WGrp *grp = nullptr)
 {
-    const GemmArgs g2 = prod(d3, n.out, 1, n.W3, 1, n.out, G2, n.l2, WBP, n.l2, n.out, nullptr, 0, H2, n.l2);       // (d3 W3') .* relu'
-    const GemmArgs g1 = prod(G2, n.l2, 1, n.W2, 1, n.l2, G1, n.l1, WBP, n.l1, n.l2, nullptr, 0, H1, n.l1);          // (G2 W2') .* relu'
+    const int R = rows;
+    const GemmArgs g2 = prod(d3, n.out, 1, n.W3, 1, n.out, G2, n.l2, R, n.l2, n.out, nullptr, 0, H2, n.l2);       // (d3 W3') .* relu'
+    const GemmArgs g1 = prod(G2, n.l2, 1, n.W2, 1, n.l2, G1, n.l1, R, n.l1, n.l2, nullptr, 0, H1, n.l1);          // (G2 W2') .* relu'
     if (!grad) {
-        if (int rc = gemm_multi(st, {g2})) return rc;
-        if (int rc = gemm_multi(st, {g1})) return rc;
-        return dX ? gemm_multi(st, {prod(G1, n.l1, 1, n.W1, 1, n.l1, dX, n.in, WBP, n.in, n.l1)}) : SHEMS_OK;      // G1 W1'
+        if (int rc = gemm_multi(st, {g2}, grp)) return rc;
+        if (int rc = gemm_multi(st, {g1}, grp)) return rc;
+        return dX ? gemm_multi(st, {prod(G1, n.l1, 1, n.W1, 1, n.l1, dX, n.in, R, n.in, n.l1)}, grp) : SHEMS_OK;      // G1 W1'
     }
     float *gW1 = grad, *gb1 = gW1 + (int64_t)n.in * n.l1, *gW2 = gb1 + n.l1, *gb2 = gW2 + (int64_t)n.l1 * n.l2, *gW3 = gb2 + n.l2,
           *gb3 = gW3 + (int64_t)n.l2 * n.out;
-    auto colsum = [&](const float *D, int cols, float *out) { return prod(ones, WBP, 1, D, cols, 1, out, cols, 1, cols, WBP); };   // ones' D
-    if (int rc = gemm_multi(st, {prod(H2, 1, n.l2, d3, n.out, 1, gW3, n.out, n.l2, n.out, WBP), colsum(d3, n.out, gb3), g2})) return rc;       // gW3 = H2' d3
-    if (int rc = gemm_multi(st, {prod(H1, 1, n.l1, G2, n.l2, 1, gW2, n.l2, n.l1, n.l2, WBP), colsum(G2, n.l2, gb2), g1})) return rc;           // gW2 = H1' G2
+    auto colsum = [&](const float *D, int cols, float *out) { return prod(ones, R, 1, D, cols, 1, out, cols, 1, cols, R); };   // ones' D
+    if (int rc = gemm_multi(st, {prod(H2, 1, n.l2, d3, n.out, 1, gW3, n.out, n.l2, n.out, R), colsum(d3, n.out, gb3), g2}, grp)) return rc;       // gW3 = H2' d3
+    if (int rc = gemm_multi(st, {prod(H1, 1, n.l1, G2, n.l2, 1, gW2, n.l2, n.l1, n.l2, R), colsum(G2, n.l2, gb2), g1}, grp)) return rc;           // gW2 = H1' G2
     if (dX)
-        return gemm_multi(st, {prod(X, 1, n.in, G1, n.l1, 1, gW1, n.l1, n.in, n.l1, WBP), colsum(G1, n.l1, gb1),                             // gW1 = X' G1
-                               prod(G1, n.l1, 1, n.W1, 1, n.l1, dX, n.in, WBP, n.in, n.l1)});
-    return gemm_multi(st, {prod(X, 1, n.in, G1, n.l1, 1, gW1, n.l1, n.in, n.l1, WBP), colsum(G1, n.l1, gb1)});
+        return gemm_multi(st, {prod(X, 1, n.in, G1, n.l1, 1, gW1, n.l1, n.in, n.l1, R), colsum(G1, n.l1, gb1),                             // gW1 = X' G1
+                               prod(G1, n.l1, 1, n.W1, 1, n.l1, dX, n.in, R, n.in, n.l1)}, grp);
+    return gemm_multi(st, {prod(X, 1, n.in, G1, n.l1, 1, gW1, n.l1, n.in, n.l1, R), colsum(G1, n.l1, gb1)}, grp);
 }
 
 static int check_shape(int l1, int l2, const char *fn)
@@ -588,6 +441,44 @@ int wide_actor_pre(const float *actor, const float *s_min, const float *s_max, i
     else hipLaunchKernelGGL((k_wgemm128<true, false>), dim3((unsigned)((m + BT - 1) / BT), ty), dim3(256), 0, st, g);
     return hip_ok(hipGetLastError(), "k_wgemm128 launch");
 }
+// A learner group's fused step (shems_wide_act_step_group_dev): env i = l * epl + r is learner l's; its actor and normalisation are
+// learner 0's + l * stride floats.  Three launches for every learner: normalise, layer 1 (grid z = learner), layer 2 with the head
+// (grid z = learner).  d_part holds learner l's partials at [l][p][epl][2].
+__global__ __launch_bounds__(256) void k_wnorm_g(const float *__restrict__ obs, const float *__restrict__ lo0, const float *__restrict__ hi0,
+                                                 float *__restrict__ out, int64_t count, int64_t per_learner, int64_t stride)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < count) {
+        const int k = (int)(e % WSIN);
+        const int64_t off = (e / per_learner) * stride;
+        const float lo = lo0[off + k], hi = hi0[off + k];
+        out[e] = (obs[e] - lo) / ((hi - lo) + 1e-8f);
+    }
+}
+int wide_actor_pre_group(const float *actor0, const float *s_min0, const float *s_max0, int64_t stride, int count, int64_t epl, int l1, int l2,
+                         const float *d_obs, float *d_ws, float *d_part, int *n_partials, hipStream_t st)
+{
+    if (int rc = check_shape(l1, l2, "shems_wide_act_step_group_dev")) return rc;
+    const int64_t m = epl * count, cnt = m * WSIN;
+    float *xn = d_ws, *H1 = xn + (m * WSIN + 3) / 4 * 4;
+    const WNet n = wnet(actor0, WSIN, l1, l2, WAIN);
+    hipLaunchKernelGGL(k_wnorm_g, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, d_obs, s_min0, s_max0, xn, cnt, epl * WSIN, stride);
+    const GemmArgs g1 = prod(xn, n.in, 1, n.W1, n.l1, 1, H1, n.l1, epl, n.l1, n.in, n.b1, 1);
+    hipLaunchKernelGGL(k_wgemm_g, dim3((unsigned)((epl + GT - 1) / GT), (unsigned)((l1 + GT - 1) / GT), (unsigned)count), dim3(256), 0, st, g1,
+                       GStride{epl * WSIN, stride, epl * l1, stride, 0, 0, 0});
+    if (int rc = hip_ok(hipGetLastError(), "k_wgemm_g launch")) return rc;
+    GemmArgs g = prod(H1, n.l1, 1, n.W2, n.l2, 1, nullptr, 0, epl, n.l2, n.l1, n.b2, 1);
+    g.head_w = n.W3; g.head_out = d_part; g.head_n = WAIN;
+    const unsigned ty = (unsigned)((l2 + BT - 1) / BT);
+    *n_partials = 2 * (int)ty;
+    const GStride s2{epl * l1, stride, 0, stride, 0, stride, 2 * (int64_t)ty * epl * WAIN};
+    const dim3 grid((unsigned)((epl + BT - 1) / BT), ty, (unsigned)count);
+    // learner l's H1 / W2 keep learner 0's 16-byte alignment: epl is a multiple of 32, the stride of 16 bytes
+    const bool v4 = (l1 % 4) == 0 && (l2 % 4) == 0 && ((uintptr_t)H1 & 15) == 0 && ((uintptr_t)n.W2 & 15) == 0 && (stride % 4) == 0;
+    if (v4) hipLaunchKernelGGL((k_wgemm128_g<true, true>), grid, dim3(256), 0, st, g, s2);
+    else hipLaunchKernelGGL((k_wgemm128_g<true, false>), grid, dim3(256), 0, st, g, s2);
+    return hip_ok(hipGetLastError(), "k_wgemm128_g launch");
+}
 // floats of d_ws: normalised observations, layer 1, and the partial sums of the output layer
 int64_t wide_act_part_offset(int l1, int64_t m) { return (m * WSIN + 3) / 4 * 4 + (m * (int64_t)l1 + 3) / 4 * 4; }      // 16-byte aligned
 int64_t wide_act_ws_floats(int l1, int l2, int64_t m) { return wide_act_part_offset(l1, m) + 2 * ((l2 + BT - 1) / BT) * m * WAIN; }
@@ -619,6 +510,16 @@ int shems_wide_act_workspace_floats(int32_t l1, int32_t l2, int64_t m, int64_t *
     if (int rc = check_shape(l1, l2, "shems_wide_act_workspace_floats")) return rc;
     if (!out || m <= 0) return set_error(SHEMS_ERR_ARG, "shems_wide_act_workspace_floats: bad arguments");
     *out = wide_act_ws_floats(l1, l2, m);
+    return SHEMS_OK;
+}
+
+int shems_wide_group_workspace_floats(int32_t l1, int32_t l2, int32_t max_batch, int64_t *out)
+{
+    if (int rc = check_shape(l1, l2, "shems_wide_group_workspace_floats")) return rc;
+    if (!out) return set_error(SHEMS_ERR_ARG, "shems_wide_group_workspace_floats: NULL");
+    if (max_batch < 1 || max_batch > WPMAX)
+        return set_error(SHEMS_ERR_ARG, "shems_wide_group_workspace_floats: max_batch must be in 1..%d (got %d)", WPMAX, max_batch);
+    *out = wws(nullptr, l1, l2, pass_width(max_batch)).total;
     return SHEMS_OK;
 }
 
@@ -677,6 +578,59 @@ int shems_wide_actor_apply_pub(const shems_ddpg *d, int32_t l1, int32_t l2, doub
     if (int rc = check_wide(d, l1, l2, "shems_wide_actor_apply_pub")) return rc;
     return adam_soft_sweep(d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, d_publish, (int)wnet_size(WSIN, l1, l2, WAIN), eta, bp1,
                            bp2, grad_scale, d->tau, (hipStream_t)stream);
+}
+
+/* replay() for every learner of a group on the wide path: the launches of shems_wide_critic_grad_ex, _critic_apply, _actor_grad and
+   _actor_apply_pub, each once for all learners (grid z / x = learner). */
+int shems_wide_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
+                            const shems_group_hparams *d_hp, int32_t max_batch, int64_t ring_len, uint64_t seed, uint32_t tick,
+                            double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, void *stream)
+{
+    const char *fn = "shems_wide_group_update";
+    if (int rc = check_shape(l1, l2, fn)) return rc;
+    if (!d0 || !d0->actor || !d0->critic || !d0->actor_t || !d0->critic_t || !d0->m_actor || !d0->v_actor || !d0->m_critic ||
+        !d0->v_critic || !d0->grad_actor || !d0->grad_critic || !d0->s_min || !d0->s_max || !d0->ws || !d0->losses)
+        return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
+    if (!g || g->count < 1 || g->count > 65535 / GMAX || g->stride_bytes < 0 || (g->stride_bytes & 15) != 0 || (g->count > 1 && g->stride_bytes == 0))
+        return set_error(SHEMS_ERR_ARG, "%s: shems_group needs 1 <= count <= %d and a 16-byte-multiple stride", fn, 65535 / GMAX);
+    if (max_batch < 1 || max_batch > WPMAX) return set_error(SHEMS_ERR_ARG, "%s: max_batch must be in 1..%d (got %d)", fn, WPMAX, max_batch);
+    if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (!d_hp && (d0->batch < 1 || d0->batch > max_batch))
+        return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..max_batch = %d (got %d)", fn, max_batch, d0->batch);
+    if (!ring0 || !ring0->s || !ring0->a || !ring0->r || !ring0->s2 || !ring0->done || ring_len < 1 || ring_len > ring0->capacity)
+        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    for (const void *q : {(const void *)d0->actor, (const void *)d0->critic, (const void *)d0->actor_t, (const void *)d0->critic_t,
+                          (const void *)d0->m_actor, (const void *)d0->v_actor, (const void *)d0->m_critic, (const void *)d0->v_critic,
+                          (const void *)d0->grad_actor, (const void *)d0->grad_critic})
+        if (((uintptr_t)q & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter, moment and gradient blocks must be 16-byte aligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    const int L = g->count, P = pass_width(max_batch);
+    const int64_t stride = g->count > 1 ? g->stride_bytes / 4 : 0;
+    const WGrp grp{L, stride};
+    const WGroupArgs A{*d0, *ring0, stride, ring_len, seed, tick, l1, l2, P, max_batch, d_hp};
+    const WWs w = wws(d0->ws, l1, l2, P);                     // learner 0's carve; learner l's is the same + l * stride
+    // critic gradient (shems_wide_critic_grad_ex)
+    hipLaunchKernelGGL(k_wprep_g, dim3((unsigned)L), dim3((unsigned)P), 0, st, A);
+    const WNet c = wnet(d0->critic, WCIN, l1, l2, 1), a = wnet(d0->actor, WSIN, l1, l2, WAIN);
+    const Fwd ft = fwd_of(wnet(d0->actor_t, WSIN, l1, l2, WAIN), w.XS2, w.T1, w.T2, w.PT, P), fc = fwd_of(c, w.XC, w.H1c, w.H2c, w.Q, P),
+              fa = fwd_of(a, w.XS, w.H1a, w.H2a, w.PA, P);
+    if (int rc = gemm_multi(st, {ft.l1, fc.l1, fa.l1}, &grp)) return rc;
+    if (int rc = gemm_multi(st, {ft.l2, fc.l2, fa.l2}, &grp)) return rc;
+    if (int rc = gemm_multi(st, {ft.l3, fc.l3, fa.l3}, &grp)) return rc;
+    hipLaunchKernelGGL(k_wtanh_cat_g, dim3(2, (unsigned)L), dim3((unsigned)P), 0, st, A);
+    if (int rc = net_forward(st, wnet(d0->critic_t, WCIN, l1, l2, 1), w.XC2, P, w.T1, w.T2, w.Q2, &grp)) return rc;
+    hipLaunchKernelGGL(k_wloss_g, dim3((unsigned)L), dim3((unsigned)P), 0, st, A);
+    if (int rc = net_backward(st, c, w.XC, w.H1c, w.H2c, w.DQ, d0->grad_critic, w.G1, w.G2, nullptr, w.ONES, P, &grp)) return rc;
+    // ADAM + soft update of every critic (shems_wide_critic_apply)
+    if (int rc = adam_soft_sweep_group(d0->critic, d0->grad_critic, d0->m_critic, d0->v_critic, d0->critic_t, (int)wnet_size(WCIN, l1, l2, 1), eta_crit,
+                                       bp1_crit, bp2_crit, d0->tau, L, stride * 4, d_hp, true, st)) return rc;
+    // actor gradient through the updated critic (shems_wide_actor_grad)
+    if (int rc = net_forward(st, c, w.XQ, P, w.H1q, w.H2q, w.Q, &grp)) return rc;
+    if (int rc = net_backward(st, c, w.XQ, w.H1q, w.H2q, w.DQA, nullptr, w.G1, w.G2, w.DA, w.ONES, P, &grp)) return rc;
+    hipLaunchKernelGGL(k_wactor_head_g, dim3((unsigned)L), dim3((unsigned)P), 0, st, A);
+    if (int rc = net_backward(st, a, w.XS, w.H1a, w.H2a, w.D3, d0->grad_actor, w.G1, w.G2, nullptr, w.ONES, P, &grp)) return rc;
+    return adam_soft_sweep_group(d0->actor, d0->grad_actor, d0->m_actor, d0->v_actor, d0->actor_t, (int)wnet_size(WSIN, l1, l2, WAIN), eta_act,
+                                 bp1_act, bp2_act, d0->tau, L, stride * 4, d_hp, false, st);
 }
 
 /* the s rows of the minibatch the last shems_wide_critic_grad_ex sampled (adapt_param_noise!, DDPG.jl:74-87) */

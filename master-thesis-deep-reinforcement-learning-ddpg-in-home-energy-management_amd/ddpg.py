@@ -215,18 +215,36 @@ def pad_net(flat, in_dim, out_dim, hidden):
     if not (1 <= h1 <= L1 and 1 <= h2 <= L2):
         raise NotImplementedError(f"hidden sizes {hidden} do not fit the ({L1}, {L2}) layout: a wider network is not padded, it keeps its own "
                                   "layout (is_wide / Agent(hidden=...) -> shems_wide_*)")
-    W1, b1, W2, b2, W3, b3 = _blocks(np.asarray(flat, f32), in_dim, out_dim, hidden)
-    P1, q1, P2, q2, P3 = (np.zeros(sh, f32) for sh in ((in_dim, L1), (L1,), (L1, L2), (L2,), (L2, out_dim)))
-    P1[:, :h1], q1[:h1], P2[:h1, :h2], q2[:h2], P3[:h2] = W1, b1, W2, b2, W3
-    return np.concatenate([P1.ravel(), q1, P2.ravel(), q2, P3.ravel(), b3.astype(f32)])
+    return pad_net_to(flat, in_dim, out_dim, hidden, (L1, L2))
 
 
 def unpad_net(flat, in_dim, out_dim, hidden):
     """The inverse of pad_net (what a checkpoint of the smaller network holds)."""
-    h1, h2 = hidden
-    if (h1, h2) == (L1, L2):
+    return unpad_net_from(flat, in_dim, out_dim, hidden, (L1, L2))
+
+
+def pad_net_to(flat, in_dim, out_dim, hidden, to):
+    """pad_net into any larger hidden size `to` (the layout of a wide learner group, e.g. (300, 600)): the same zero padding, which
+    stays exact under training for the same reason."""
+    (h1, h2), (t1, t2) = (int(hidden[0]), int(hidden[1])), (int(to[0]), int(to[1]))
+    if not (1 <= h1 <= t1 and 1 <= h2 <= t2):
+        raise ValueError(f"hidden sizes {tuple(hidden)} do not fit the ({t1}, {t2}) layout")
+    if (h1, h2) == (t1, t2):
         return np.asarray(flat, f32).copy()
-    W1, b1, W2, b2, W3, b3 = _blocks(np.asarray(flat, f32), in_dim, out_dim, (L1, L2))
+    W1, b1, W2, b2, W3, b3 = _blocks(np.asarray(flat, f32), in_dim, out_dim, (h1, h2))
+    P1, q1, P2, q2, P3 = (np.zeros(sh, f32) for sh in ((in_dim, t1), (t1,), (t1, t2), (t2,), (t2, out_dim)))
+    P1[:, :h1], q1[:h1], P2[:h1, :h2], q2[:h2], P3[:h2] = W1, b1, W2, b2, W3
+    return np.concatenate([P1.ravel(), q1, P2.ravel(), q2, P3.ravel(), b3.astype(f32)])
+
+
+def unpad_net_from(flat, in_dim, out_dim, hidden, frm):
+    """The inverse of pad_net_to: the (hidden) network held in the `frm` layout."""
+    (h1, h2), (t1, t2) = (int(hidden[0]), int(hidden[1])), (int(frm[0]), int(frm[1]))
+    if not (1 <= h1 <= t1 and 1 <= h2 <= t2):
+        raise ValueError(f"hidden sizes {tuple(hidden)} do not fit the ({t1}, {t2}) layout")
+    if (h1, h2) == (t1, t2):
+        return np.asarray(flat, f32).copy()
+    W1, b1, W2, b2, W3, b3 = _blocks(np.asarray(flat, f32), in_dim, out_dim, (t1, t2))
     return np.concatenate([W1[:, :h1].ravel(), b1[:h1], W2[:h1, :h2].ravel(), b2[:h2], W3[:h2].ravel(), b3])
 
 
@@ -254,11 +272,13 @@ class Agent:
     """The DDPG learner state on one GPU (one replica under data parallelism)."""
 
     def __init__(self, seed=1231, device=None, sigma=NOISE_SIGMA, mu=0.0, rng_seed=None, noise_type="gn", theta=0.15,
-                 dt=1e-2, eps=0.5, tensors=None, hidden=(L1, L2), wide=None):
+                 dt=1e-2, eps=0.5, tensors=None, hidden=(L1, L2), wide=None, layout=None):
         """tensors: dict of float32 device views (actor, critic, actor_t, critic_t, m_actor, v_actor, m_critic, v_critic,
         grad_actor, grad_critic, s_min, s_max, ws, losses) in memory the caller owns -- a learner group's slab -- instead
         of buffers allocated here.  wide: None = by size (is_wide); True = the layer-by-layer path whatever the size (tests hold the two
-        implementations against each other at (250, 500))."""
+        implementations against each other at (250, 500)).  layout (wide path only): the hidden size the networks are zero-padded into
+        and the wide kernels run at (a wide learner group's width, group.LearnerGroup(form="wide")); None = `hidden`.  export_* and
+        set_params speak `hidden`."""
         import torch
         self.torch = torch
         self.L = _declare()
@@ -278,12 +298,15 @@ class Agent:
         if self.hidden != (L1, L2) and not self.wide and noise_type == "pn":
             raise NotImplementedError("parameter noise adds one scalar to EVERY parameter (DDPG.jl:89-96): it would un-zero the padding of a smaller network")
         nws = C.c_int64(0)
+        if layout is not None and not self.wide:
+            raise ValueError("layout= belongs to the wide path")
+        self.whidden = self.hidden if layout is None else (int(layout[0]), int(layout[1]))   # the wide kernels' (padded) hidden size
         if self.wide:
-            if tensors is not None:
-                raise NotImplementedError("learner groups run the (250, 500) kernels: no slabs of wide networks")
-            a = init_params(self.seed, STATE, ACTION, 0, self.hidden)
-            c = init_params(self.seed, STATE + ACTION, 1, 1, self.hidden)
-            _capi.check(self.L.shems_wide_workspace_floats(*self.hidden, C.byref(nws)))
+            a = pad_net_to(init_params(self.seed, STATE, ACTION, 0, self.hidden), STATE, ACTION, self.hidden, self.whidden)
+            c = pad_net_to(init_params(self.seed, STATE + ACTION, 1, 1, self.hidden), STATE + ACTION, 1, self.hidden, self.whidden)
+            _capi.check(self.L.shems_wide_workspace_floats(*self.whidden, C.byref(nws)))
+            if tensors is not None:                # a wide learner group's slab carves ws for its pass width
+                nws = C.c_int64(tensors["ws"].numel())
         else:
             a = pad_net(init_params(self.seed, STATE, ACTION, 0, self.hidden), STATE, ACTION, self.hidden)
             c = pad_net(init_params(self.seed, STATE + ACTION, 1, 1, self.hidden), STATE + ACTION, 1, self.hidden)
@@ -364,13 +387,13 @@ class Agent:
         """The actor (or `tensor`, e.g. the target) as the flat Flux-layout vector of ITS network size (what a checkpoint holds)."""
         src = self.actor if tensor is None else tensor
         if self.wide:
-            return src.detach().cpu().numpy().copy()
+            return unpad_net_from(src.detach().cpu().numpy(), STATE, ACTION, self.hidden, self.whidden)
         return unpad_net(src.detach().cpu().numpy(), STATE, ACTION, self.hidden)
 
     def export_critic(self, tensor=None):
         src = self.critic if tensor is None else tensor
         if self.wide:
-            return src.detach().cpu().numpy().copy()
+            return unpad_net_from(src.detach().cpu().numpy(), STATE + ACTION, 1, self.hidden, self.whidden)
         return unpad_net(src.detach().cpu().numpy(), STATE + ACTION, 1, self.hidden)
 
     def set_params(self, actor=None, critic=None, sync_targets=True):
@@ -385,10 +408,11 @@ class Agent:
             if vec is not None and np.asarray(vec).size not in (n_lay, n_own):
                 raise ValueError(f"set_params: {name} has {np.asarray(vec).size} parameters; a {self.hidden} network holds {n_own}"
                                  + ("" if n_lay == n_own else f" ({n_lay} in the kernels' padded layout)"))
+        pad = (lambda v, i, o: pad_net_to(v, i, o, self.hidden, self.whidden)) if self.wide else (lambda v, i, o: pad_net(v, i, o, self.hidden))
         if actor is not None and np.asarray(actor).size != self.n_actor:
-            actor = pad_net(actor, STATE, ACTION, self.hidden)
+            actor = pad(actor, STATE, ACTION)
         if critic is not None and np.asarray(critic).size != self.n_critic:
-            critic = pad_net(critic, STATE + ACTION, 1, self.hidden)
+            critic = pad(critic, STATE + ACTION, 1)
         if actor is not None:
             self.actor.copy_(t.as_tensor(np.asarray(actor, f32)))
             if sync_targets:
@@ -432,7 +456,7 @@ class Agent:
         st = self._stream()
         if self.wide:
             slots = np.empty(self.batch, np.int32)
-            _capi.check(self.L.shems_wide_batch_slots(C.byref(d), *self.hidden, slots.ctypes.data_as(C.c_void_p), st))
+            _capi.check(self.L.shems_wide_batch_slots(C.byref(d), *self.whidden, slots.ctypes.data_as(C.c_void_p), st))
             obs = ring.s[t.as_tensor(slots.astype(np.int64), device=self.device)].contiguous()
         else:
             obs = t.empty((self.batch, STATE), dtype=t.float32, device=self.device)
@@ -472,7 +496,7 @@ class Agent:
             train, actor = self._explore(train, tick)
         p = self._act_params(train, tick, actor)
         if self.wide:
-            _capi.check(self.L.shems_wide_actor_forward_dev(C.byref(p), *self.hidden, C.c_void_p(ptr), m, C.c_void_p(out.data_ptr()),
+            _capi.check(self.L.shems_wide_actor_forward_dev(C.byref(p), *self.whidden, C.c_void_p(ptr), m, C.c_void_p(out.data_ptr()),
                                                             C.c_void_p(self._wide_act_ws(m).data_ptr()), self._stream()))
             return out
         _capi.check(self.L.shems_actor_forward_dev(C.byref(p), C.c_void_p(ptr), m,
@@ -483,7 +507,7 @@ class Agent:
         """Scratch of the wide path's forward for m observations (normalised observations, both hidden layers, pre-activation outputs):
         m x (9 + l1 + l2 + 2) floats in HBM, kept between calls."""
         need = C.c_int64(0)
-        _capi.check(self.L.shems_wide_act_workspace_floats(*self.hidden, int(m), C.byref(need)))
+        _capi.check(self.L.shems_wide_act_workspace_floats(*self.whidden, int(m), C.byref(need)))
         if self._act_ws is None or self._act_ws.numel() < need.value:
             self._act_ws = self.torch.empty(need.value, dtype=self.torch.float32, device=self.device)
         return self._act_ws
@@ -503,7 +527,7 @@ class Agent:
         if self.wide:
             if block_reward is not None:
                 raise NotImplementedError("per-workgroup reward sums are a by-product of the fused (250, 500) kernel")
-            _capi.check(self.L.shems_wide_act_step_dev(C.byref(v), C.byref(p), *self.hidden, C.c_void_p(self._wide_act_ws(env.n).data_ptr()),
+            _capi.check(self.L.shems_wide_act_step_dev(C.byref(v), C.byref(p), *self.whidden, C.c_void_p(self._wide_act_ws(env.n).data_ptr()),
                                                        ptr(a_out), ptr(rewards), ptr(rewards_f32), ptr(returns_acc),
                                                        C.byref(rs) if rs is not None else None,
                                                        C.byref(window) if window is not None else None, self._stream()))
@@ -541,24 +565,24 @@ class Agent:
     # the four split-form calls of replay(), on the tuned kernels or -- a network wider than (250, 500) -- layer by layer (shems_wide_*)
     def _critic_grad_ex(self, d, rs, ring_len, tick, ex_pos, ex_cnt, st):
         if self.wide:
-            return _capi.check(self.L.shems_wide_critic_grad_ex(C.byref(d), *self.hidden, C.byref(rs), ring_len, self.rng_seed,
+            return _capi.check(self.L.shems_wide_critic_grad_ex(C.byref(d), *self.whidden, C.byref(rs), ring_len, self.rng_seed,
                                                                 int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt, st))
         _capi.check(self.L.shems_ddpg_critic_grad_ex(C.byref(d), C.byref(rs), ring_len, self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt, st))
 
     def _critic_apply(self, d, gs, st):
         if self.wide:
-            return _capi.check(self.L.shems_wide_critic_apply(C.byref(d), *self.hidden, self.eta_crit, self.bp_critic[0], self.bp_critic[1], gs, st))
+            return _capi.check(self.L.shems_wide_critic_apply(C.byref(d), *self.whidden, self.eta_crit, self.bp_critic[0], self.bp_critic[1], gs, st))
         _capi.check(self.L.shems_ddpg_critic_apply(C.byref(d), self.eta_crit, self.bp_critic[0], self.bp_critic[1], gs, st))
 
     def _actor_grad(self, d, st):
         if self.wide:
-            return _capi.check(self.L.shems_wide_actor_grad(C.byref(d), *self.hidden, st))
+            return _capi.check(self.L.shems_wide_actor_grad(C.byref(d), *self.whidden, st))
         _capi.check(self.L.shems_ddpg_actor_grad(C.byref(d), st))
 
     def _actor_apply_pub(self, d, gs, publish, st):
         pub = C.c_void_p(publish.data_ptr()) if publish is not None else None
         if self.wide:
-            return _capi.check(self.L.shems_wide_actor_apply_pub(C.byref(d), *self.hidden, self.eta_act, self.bp_actor[0], self.bp_actor[1], gs, pub, st))
+            return _capi.check(self.L.shems_wide_actor_apply_pub(C.byref(d), *self.whidden, self.eta_act, self.bp_actor[0], self.bp_actor[1], gs, pub, st))
         _capi.check(self.L.shems_ddpg_actor_apply_pub(C.byref(d), self.eta_act, self.bp_actor[0], self.bp_actor[1], gs, pub, st))
 
     def _replay_wide(self, ring, tick, ex_pos, ex_cnt, publish):

@@ -40,6 +40,8 @@ assert C.sizeof(HParams) == 40
 # keys of a per-learner mapping (LearnerGroup(hparams=...)); a missing key takes today's default
 HPARAM_KEYS = ("eta_act", "eta_crit", "gamma", "tau", "sigma", "mu", "batch", "hidden", "noise_type", "mem_size")
 MAX_GROUP_BATCH = 128                  # one update pass holds 128 minibatch columns (the group kernels have no sub-batch path)
+MAX_WIDE_BATCH = 256                   # the wide form (form="wide"): one pass of P = max(128, round_up_32(max batch)) columns
+WIDE_HIDDEN = (300, 600)               # the wide form's default padded hidden size: the tuned grid's widest point
 
 
 def hparam_defaults(sigma=NOISE_SIGMA):
@@ -47,9 +49,10 @@ def hparam_defaults(sigma=NOISE_SIGMA):
     return dict(eta_act=ETA_ACT, eta_crit=ETA_CRIT, gamma=GAMMA, tau=TAU, sigma=sigma, mu=0.0, batch=BATCH_SIZE, hidden=(L1, L2))
 
 
-def _hparams_records(count, hparams, sigma, capacity):
+def _hparams_records(count, hparams, sigma, capacity, width=None):
     """Per-learner mappings -> (full dicts, ctypes array of HParams).  Everything the group kernels cannot hold is refused here, naming the
-    learner; the records themselves go through shems_group_hparams_check.  Host only: no device work."""
+    learner; the records themselves go through shems_group_hparams_check.  Host only: no device work.
+    width: the wide form's padded hidden size -- batch up to 256 and hidden up to `width` (shems_group_hparams_check_wide)."""
     hparams = list(hparams)
     if len(hparams) != count:
         raise ValueError(f"hparams holds {len(hparams)} records for a group of {count} learners")
@@ -67,12 +70,17 @@ def _hparams_records(count, hparams, sigma, capacity):
         if "mem_size" in h and int(h["mem_size"]) != capacity:
             raise ValueError(f"hparams[{l}]: mem_size {h['mem_size']} differs from the group's ring capacity {capacity}: "
                              "every learner's ring has the same capacity")
-        if int(r["batch"]) > MAX_GROUP_BATCH:
+        if width is None and int(r["batch"]) > MAX_GROUP_BATCH:
             raise ValueError(f"hparams[{l}]: batch {r['batch']} > {MAX_GROUP_BATCH}: the group kernels hold one 128-column update pass")
+        if width is not None and int(r["batch"]) > MAX_WIDE_BATCH:
+            raise ValueError(f"hparams[{l}]: batch {r['batch']} > {MAX_WIDE_BATCH}: the wide group form holds one update pass of at most "
+                             f"{MAX_WIDE_BATCH} columns")
         hid = tuple(int(x) for x in r["hidden"])
-        if len(hid) != 2 or hid[0] < 1 or hid[1] < 1 or hid[0] > L1 or hid[1] > L2:
-            raise ValueError(f"hparams[{l}]: hidden {tuple(r['hidden'])} does not fit ({L1}, {L2}): wider networks run on the single-learner "
-                             "wide path, not in a group")
+        W1, W2 = (L1, L2) if width is None else width
+        if len(hid) != 2 or hid[0] < 1 or hid[1] < 1 or hid[0] > W1 or hid[1] > W2:
+            raise ValueError(f"hparams[{l}]: hidden {tuple(r['hidden'])} does not fit ({W1}, {W2}): " +
+                             ("wider networks run on the single-learner wide path, not in a group" if width is None else
+                              "wider than the wide group's hidden size"))
         r["hidden"] = hid
         r["batch"] = int(r["batch"])
         for k in ("eta_act", "eta_crit"):         # ADAM(eta) with a Float32 literal: its Float64 value (Agent.eta_*)
@@ -82,25 +90,43 @@ def _hparams_records(count, hparams, sigma, capacity):
         full.append(r)
     arr = (HParams * count)(*[HParams(r["eta_act"], r["eta_crit"], r["gamma"], r["tau"], r["mu"], r["sigma"], r["batch"], 0) for r in full])
     L = _declare_group()
-    if L.shems_group_hparams_check(arr, count) != _capi.OK:
+    rc = (L.shems_group_hparams_check(arr, count) if width is None else
+          L.shems_group_hparams_check_wide(arr, count, max(r["batch"] for r in full)))
+    if rc != _capi.OK:
         raise ValueError(L.shems_last_error().decode("utf-8", "replace"))
     return full, arr
 
 
-def tuned_grid(job_ids, seeds=1, chargers=1):
+def _wide_width(hparams, hidden):
+    """A wide group's padded hidden size: `hidden`, else the elementwise maximum of the records' (a record without one: (250, 500)), else
+    WIDE_HIDDEN."""
+    if hidden is not None:
+        h = (int(hidden[0]), int(hidden[1]))
+    elif hparams is not None and len(hparams):
+        hs = [tuple(int(x) for x in (h.get("hidden", (L1, L2)) if hasattr(h, "get") else (L1, L2))) for h in hparams]
+        h = (max(x[0] for x in hs), max(x[1] for x in hs))
+    else:
+        h = WIDE_HIDDEN
+    if not (1 <= h[0] <= 4096 and 1 <= h[1] <= 4096):
+        raise ValueError(f"hidden {h}: the wide path holds hidden sizes 1..4096")
+    return h
+
+
+def tuned_grid(job_ids, seeds=1, chargers=1, wide=False):
     """Per-learner records of a slice of the tuned template's hyper-parameter grid (input09_08_on_01-09_eval.jl:62-106), decoded by
     main.set_hyperparameters from each JOB_ID's last two digits.  Returns (records, points, skipped): `records` holds
     len(points) x seeds x chargers mappings for LearnerGroup(hparams=...), learner (p * seeds + s) * chargers + c running point points[p];
-    `skipped` lists (job_id, reason) for the points a group cannot run (BATCH_SIZE 150, (L1, L2) = (300, 600))."""
+    `skipped` lists (job_id, reason) for the points a group cannot run (BATCH_SIZE 150, (L1, L2) = (300, 600)).
+    wide: records for a LearnerGroup(form="wide"), which holds every batch and hidden size of the grid: nothing is skipped for them."""
     from .main import RunConfig, set_hyperparameters
     records, points, skipped = [], [], []
     for jid in job_ids:
         jid = str(jid)
         cfg = set_hyperparameters(RunConfig(job_id=jid.zfill(2), task_id="0", gpu_id=0, template="tuned"))
         why = []
-        if cfg.BATCH_SIZE > MAX_GROUP_BATCH:
-            why.append(f"BATCH_SIZE {cfg.BATCH_SIZE} > {MAX_GROUP_BATCH}")
-        if cfg.L1 > L1 or cfg.L2 > L2:
+        if cfg.BATCH_SIZE > (MAX_WIDE_BATCH if wide else MAX_GROUP_BATCH):
+            why.append(f"BATCH_SIZE {cfg.BATCH_SIZE} > {MAX_WIDE_BATCH if wide else MAX_GROUP_BATCH}")
+        if not wide and (cfg.L1 > L1 or cfg.L2 > L2):
             why.append(f"(L1, L2) = ({cfg.L1}, {cfg.L2}) wider than ({L1}, {L2})")
         if cfg.noise_type != "gn":
             why.append(f"noise_type {cfg.noise_type!r}")
@@ -115,6 +141,7 @@ def tuned_grid(job_ids, seeds=1, chargers=1):
 
 
 TUNED_RUNNABLE = tuple(f"{c:02d}" for c in range(81) if c // 27 != 2 and (c // 3) % 3 != 0)   # the 36 points tuned_grid keeps
+TUNED_ALL = tuple(f"{c:02d}" for c in range(81))                                             # every point: tuned_grid(..., wide=True)
 
 
 W2T_FLOATS = 32 * 4 * 64 * 64          # SHEMS_W2T_FLOATS: [4 k-tiles][8 n-tiles][m | v | p | target][64][64] per network
@@ -148,7 +175,13 @@ def _declare_group():
     L.shems_group_hparams_check.argtypes = [C.POINTER(HParams), C.c_int32]
     L.shems_act_step_group_hp_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, PT, vp, vp, vp, PR, C.POINTER(RingWindow), vp]
     L.shems_ddpg_group_update_hp.argtypes = [PD, PR, PG, PT, vp, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, C.c_int32, vp]
-    for fn in ("shems_group_hparams_check", "shems_act_step_group_hp_dev", "shems_ddpg_group_update_hp"):
+    i32 = C.c_int32
+    L.shems_group_hparams_check_wide.argtypes = [C.POINTER(HParams), i32, i32]
+    L.shems_wide_group_workspace_floats.argtypes = [i32, i32, i32, C.POINTER(i64)]
+    L.shems_wide_group_update.argtypes = [PD, PR, PG, i32, i32, vp, i32, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, dbl, dbl, vp]
+    L.shems_wide_act_step_group_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, i32, i32, vp, vp, vp, vp, PR, C.POINTER(RingWindow), vp]
+    for fn in ("shems_group_hparams_check", "shems_act_step_group_hp_dev", "shems_ddpg_group_update_hp", "shems_group_hparams_check_wide",
+               "shems_wide_group_workspace_floats", "shems_wide_group_update", "shems_wide_act_step_group_dev"):
         getattr(L, fn).restype = C.c_int
     for fn in ("shems_act_step_group_dev", "shems_ddpg_group_critic_grad", "shems_ddpg_group_critic_apply",
                "shems_ddpg_group_actor_grad", "shems_ddpg_group_actor_apply", "shems_minmax_group_dev"):
@@ -175,11 +208,12 @@ class LearnerGroup:
 
     # replay() of a group: "throughput" = csrc/shems_gupd.hip (eight launches shaped for hundreds of learners: small tiles, four workgroups
     # resident per CU, plain back-propagation), "latency" = the single-learner kernels with grid z = learner (five launches, per learner
-    # bit-identical to Agent.replay).  Default: throughput from TP_MIN_LEARNERS learners up.
+    # bit-identical to Agent.replay), "wide" = the layer-by-layer path of csrc/shems_wide.hip with a learner dimension (24 launches; networks
+    # up to 4096 wide, batches up to 256).  Default: throughput from TP_MIN_LEARNERS learners up.
     TP_MIN_LEARNERS = 16
 
     def __init__(self, count, envs_per_learner, seed=1231, rng_seed=None, capacity=MEM_SIZE, sigma=NOISE_SIGMA, device=None, form=None, tiled=None,
-                 hparams=None):
+                 hparams=None, hidden=None):
         """tiled (throughput form only; default on, SHEMS_GROUP_TILED=0 switches it off): the layer-2 state of both networks (W2, its
         ADAM moments, the target's W2) is kept in the TILED working layout (shems_group_w2t, include/shems_hip.h) while the group trains:
         one contiguous 64 KB piece per 64 x 64 tile for the update's W2-gradient / ADAM launches (4.78 against 3.85 TB/s), read from
@@ -192,14 +226,32 @@ class LearnerGroup:
         the keys of HPARAM_KEYS (eta_act, eta_crit, gamma, tau, sigma, mu, batch, hidden; a missing key takes today's default): the group
         then runs the throughput form whatever its size, through the per-learner entry points (shems_ddpg_group_update_hp,
         shems_act_step_group_hp_dev), and learners[l] carries learner l's values.  The records are checked and uploaded once, here.
-        Refused, naming the learner: batch > 128, hidden wider than (250, 500), noise_type other than "gn", a per-learner mem_size."""
+        Refused, naming the learner: batch > 128, hidden wider than (250, 500), noise_type other than "gn", a per-learner mem_size.
+
+        form="wide": the learners run on the layer-by-layer path (csrc/shems_wide.hip), batched over learners -- every launch runs the
+        whole group.  All networks are zero-padded into one hidden size, `hidden` (default: the elementwise maximum of the records'
+        hidden, or (300, 600) without records; up to 4096); a record may then hold batch up to 256 and any hidden size up to `hidden`.
+        learners[l] is learner l's wide Agent at its own size (export_* / set_params).  Without hparams every learner trains with
+        learners[0]'s batch (<= 128), gamma, tau and eta.  No tiled layout."""
         import os
         import torch
         self.torch = torch
         self.L = _declare_group()
         self.count, self.envs_per_learner, self.capacity = int(count), int(envs_per_learner), int(capacity)
         self.hparams, self._hp_host, self._hp_dev = None, None, None
-        if hparams is not None:                    # every argument error before any device work
+        self.hidden = None                         # form "wide": the padded hidden size of every learner's networks
+        if form == "wide":                         # every argument error before any device work
+            if tiled:
+                raise ValueError("form='wide' has no tiled working layout: tiled=True is refused")
+            tiled = False
+            self.hidden = _wide_width(hparams, hidden)
+            if hparams is not None:
+                if self.count < 1:
+                    raise ValueError("a learner group needs count >= 1")
+                self.hparams, self._hp_host = _hparams_records(self.count, hparams, sigma, self.capacity, width=self.hidden)
+        elif hidden is not None:
+            raise ValueError("hidden= belongs to form='wide'")
+        elif hparams is not None:
             if form == "latency":
                 raise ValueError("per-learner hyper-parameters run on the throughput form: form='latency' cannot take hparams")
             if self.count < 1:
@@ -207,8 +259,8 @@ class LearnerGroup:
             self.hparams, self._hp_host = _hparams_records(self.count, hparams, sigma, self.capacity)
             form = "throughput"
         self.form = form if form is not None else ("throughput" if self.count >= self.TP_MIN_LEARNERS else "latency")
-        if self.form not in ("throughput", "latency"):
-            raise ValueError("form must be 'throughput' or 'latency'")
+        if self.form not in ("throughput", "latency", "wide"):
+            raise ValueError("form must be 'throughput', 'latency' or 'wide'")
         self.store_grad = False                    # throughput form: also leave the gradients in grad_actor / grad_critic (tests)
         self.tiled = (self.form == "throughput" and os.environ.get("SHEMS_GROUP_TILED", "1") != "0") if tiled is None else bool(tiled)
         if self.tiled and self.form != "throughput":
@@ -220,13 +272,22 @@ class LearnerGroup:
         self.seed = int(seed)
         self.rng_seed = self.seed if rng_seed is None else int(rng_seed)
         nws = C.c_int64(0)
-        _capi.check(self.L.shems_ddpg_workspace_floats(C.byref(nws)))
+        n_actor, n_critic = N_ACTOR, N_CRITIC
+        if self.form == "wide":                    # the slab carved at the group's width, ws for its pass width
+            self.max_batch = max(r["batch"] for r in self.hparams) if self.hparams is not None else MAX_GROUP_BATCH
+            na, nc = C.c_int64(0), C.c_int64(0)
+            _capi.check(self.L.shems_wide_params(*self.hidden, C.byref(na), C.byref(nc)))
+            n_actor, n_critic = na.value, nc.value
+            _capi.check(self.L.shems_wide_group_workspace_floats(*self.hidden, self.max_batch, C.byref(nws)))
+        else:
+            _capi.check(self.L.shems_ddpg_workspace_floats(C.byref(nws)))
+        self._act_ws = None                        # form "wide": scratch of the fused step (shems_wide_act_workspace_floats)
         # one slab per learner; every block starts on a 16-byte boundary (float offsets are multiples of 4)
         layout, off = {}, 0
-        for name, n in (("actor", N_ACTOR), ("critic", N_CRITIC), ("actor_t", N_ACTOR), ("critic_t", N_CRITIC),
-                        ("m_actor", N_ACTOR), ("v_actor", N_ACTOR), ("m_critic", N_CRITIC), ("v_critic", N_CRITIC),
+        for name, n in (("actor", n_actor), ("critic", n_critic), ("actor_t", n_actor), ("critic_t", n_critic),
+                        ("m_actor", n_actor), ("v_actor", n_actor), ("m_critic", n_critic), ("v_critic", n_critic),
                         ("w2t_actor", W2T_FLOATS if self.tiled else 0), ("w2t_critic", W2T_FLOATS if self.tiled else 0),
-                        ("grad_actor", N_ACTOR), ("grad_critic", N_CRITIC), ("s_min", STATE), ("s_max", STATE), ("losses", 2),
+                        ("grad_actor", n_actor), ("grad_critic", n_critic), ("s_min", STATE), ("s_max", STATE), ("losses", 2),
                         ("ws", nws.value), ("ring_s", self.capacity * STATE), ("ring_a", self.capacity * ACTION),
                         ("ring_r", self.capacity), ("ring_s2", self.capacity * STATE), ("ring_done", (self.capacity + 3) // 4)):
             layout[name] = (off, int(n))
@@ -238,12 +299,14 @@ class LearnerGroup:
             v = lambda name: self.slab[l, layout[name][0]:layout[name][0] + layout[name][1]]
             tens = {k: v(k) for k in ("actor", "critic", "actor_t", "critic_t", "m_actor", "v_actor", "m_critic", "v_critic",
                                       "grad_actor", "grad_critic", "s_min", "s_max", "ws", "losses")}
+            wkw = dict(wide=True, layout=self.hidden) if self.form == "wide" else {}
             if self.hparams is None:
-                self.learners.append(Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=sigma, device=self.device, tensors=tens))
-            else:                                  # smaller networks come zero-padded (ddpg.pad_net) and stay so under training
+                self.learners.append(Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=sigma, device=self.device, tensors=tens,
+                                           **(dict(wkw, hidden=self.hidden) if wkw else {})))
+            else:                                  # smaller networks come zero-padded (ddpg.pad_net / pad_net_to) and stay so under training
                 h = self.hparams[l]
                 ag = Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=h["sigma"], mu=h["mu"], device=self.device, tensors=tens,
-                           hidden=h["hidden"])
+                           hidden=h["hidden"], **wkw)
                 ag.gamma, ag.tau, ag.batch, ag.eta_act, ag.eta_crit = h["gamma"], h["tau"], h["batch"], h["eta_act"], h["eta_crit"]
                 self.learners.append(ag)
             if self.tiled:
@@ -341,7 +404,16 @@ class LearnerGroup:
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
         r0 = self.rings[0].struct()
         w = RingWindow(*window) if window is not None else None
-        if self._hp_dev is not None:               # learner l's noise mu / sigma from its record
+        if self.form == "wide":                    # four launches for the whole group (noise mu / sigma from the records, if any)
+            if self._act_ws is None:
+                need = C.c_int64(0)
+                _capi.check(self.L.shems_wide_act_workspace_floats(*self.hidden, self.n_envs, C.byref(need)))
+                self._act_ws = self.torch.empty(need.value, dtype=self.torch.float32, device=self.device)
+            _capi.check(self.L.shems_wide_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), *self.hidden,
+                                                             self._hp_ptr() if self._hp_dev is not None else None, C.c_void_p(self._act_ws.data_ptr()),
+                                                             ptr(a_out), ptr(returns_acc), C.byref(r0) if w is not None else None,
+                                                             C.byref(w) if w is not None else None, self._stream()))
+        elif self._hp_dev is not None:             # learner l's noise mu / sigma from its record
             t = self.w2t_struct() if self._use_tiled() else None
             _capi.check(self.L.shems_act_step_group_hp_dev(C.byref(v), C.byref(p), C.byref(g), C.byref(t) if t is not None else None, self._hp_ptr(),
                                                            ptr(a_out), ptr(returns_acc), C.byref(r0) if w is not None else None,
@@ -366,7 +438,12 @@ class LearnerGroup:
         d = a0._ddpg_args()
         st = self._stream()
         tick = self.updates if tick is None else tick
-        if self._hp_dev is not None:               # learner l's batch / gamma / tau / eta from its record
+        if self.form == "wide":                    # 24 launches for the whole group (csrc/shems_wide.hip)
+            _capi.check(self.L.shems_wide_group_update(C.byref(d), C.byref(r0), C.byref(g), *self.hidden,
+                                                       self._hp_ptr() if self._hp_dev is not None else None, self.max_batch,
+                                                       len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.eta_crit, a0.bp_critic[0],
+                                                       a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1], st))
+        elif self._hp_dev is not None:             # learner l's batch / gamma / tau / eta from its record
             tl = self._use_tiled()
             t = self.w2t_struct() if tl else None
             _capi.check(self.L.shems_ddpg_group_update_hp(C.byref(d), C.byref(r0), C.byref(g), C.byref(t) if tl else None, self._hp_ptr(),
