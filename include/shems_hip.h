@@ -544,6 +544,17 @@ int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p
 /* min_max_buffer for every learner of the group (learner l: Philox key seed + l). */
 int shems_minmax_group_dev(const shems_replay *ring0, const shems_group *g, int64_t ring_len, int64_t count,
                            uint64_t seed, float *d_s_min0, float *d_s_max0, void *stream);
+/* The evaluation sweep of run_episodes (DDPG.jl:273-290) for every learner of a group, one launch.  g->envs_per_learner is the eval
+ * block E_eval (a multiple of 32); learner l's eval returns are d_returns[l * E_eval + j], j < runs <= E_eval (the rest is padding,
+ * never read).  Per learner: d_score[l] = (sum over j = 0 .. runs-1 in ascending order, float64) / runs; if d_score[l] > d_best_score[l]
+ * (strict; the caller starts from -100000, DDPG.jl:246) then d_best_score[l] = score, d_best_run[l] = episode, d_improved[l] = 1 and
+ * snapshot row l (d_best0 + l * best_stride_bytes: actor | pad to 16 B | s_min[9] | pad | s_max[9] | pad, the row of
+ * harness.inference_many) receives the actor in Flux order and the normalisation; else d_improved[l] = 0 and nothing else is written.
+ * W2 is read from the actor's p tiles when t != NULL (a group training on the tiled layout), else from d0->actor.  Nothing of the
+ * training state is written.  (l1, l2) != (0, 0): the wide form, actors of shems_wide_params(l1, l2) floats; t must be NULL. */
+int shems_group_eval_best_dev(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, int32_t l1, int32_t l2,
+                              const double *d_returns, int32_t runs, int32_t episode, double *d_score, double *d_best_score,
+                              int32_t *d_best_run, uint8_t *d_improved, float *d_best0, int64_t best_stride_bytes, void *stream);
 
 /* Parameter noise, noise_type "pn" (struct ParamNoise input.jl:210-215; add_perturb! DDPG.jl:89-96;
  * adapt_param_noise! DDPG.jl:74-87).  The reference adds ONE scalar draw N(mu, sigma_current) to every parameter

@@ -1078,6 +1078,65 @@ __global__ __launch_bounds__(256) void k_tp_w2_layout(LayoutArgs A)
     }
 }
 
+// ================================================================================================================================
+// The evaluation sweep's bookkeeping (run_episodes, DDPG.jl:273-290) for every learner: one workgroup per learner.  score_l = the mean of
+// the learner's first `runs` eval returns, summed in ascending order in float64 (a host loop reproduces it bit for bit); strictly better
+// than best_score[l] -> best_score / best_run / improved and a Flux-order copy of the actor, s_min and s_max into snapshot row l.  W2
+// comes from the actor's p tiles when the group trains on the tiled layout (the Flux-order W2 is stale then), everything else from the
+// Flux-order block.  Nothing of the training state is written.
+// ================================================================================================================================
+struct EvalBestArgs {
+    const float *actor, *s_min, *s_max, *w2t;          // learner 0's; w2t: the tiled actor region or null
+    int64_t gstride;                                   // bytes between learners' slabs
+    int64_t n_actor;                                   // floats of one actor (129 002, or shems_wide_params at the wide size)
+    const double *returns; int64_t e_eval; int32_t runs, episode;
+    double *score, *best_score; int32_t *best_run; uint8_t *improved;
+    float *best; int64_t best_stride;                  // snapshot row l at best + l * best_stride bytes
+};
+__global__ __launch_bounds__(256) void k_group_eval_best(EvalBestArgs A)
+{
+    __shared__ int s_imp;
+    const int64_t l = blockIdx.x, off = l * A.gstride;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        const double *r = A.returns + l * A.e_eval;
+        double s = 0.0;
+        for (int j = 0; j < A.runs; ++j) s += r[j];    // ascending j: the documented order
+        const double score = s / (double)A.runs;
+        A.score[l] = score;
+        const bool imp = score > A.best_score[l];      // strict (DDPG.jl:282): an equal score keeps the old snapshot
+        if (imp) { A.best_score[l] = score; A.best_run[l] = A.episode; }
+        A.improved[l] = imp ? 1 : 0;
+        s_imp = imp;
+    }
+    __syncthreads();
+    if (!s_imp) return;
+    const float *src = gsh(A.actor, off);
+    float *dst = reinterpret_cast<float *>(reinterpret_cast<char *>(A.best) + l * A.best_stride);
+    const float *tiles = A.w2t ? gsh(A.w2t, off) + TL_P * TL_TILE : nullptr;
+    const int64_t w2 = off_w2(SIN), w2_end = w2 + (int64_t)H1N * H2N;
+    const int64_t n4 = A.n_actor >> 2;
+    // float4 pieces: W2 starts on a multiple of 4 and its rows are 500 wide, so a piece lies inside W2 or outside it, and inside it four
+    // adjacent columns of one row of one 64 x 64 tile
+    for (int64_t q = tid; q < n4; q += 256) {
+        const int64_t e = 4 * q;
+        f32x4 v;
+        if (tiles && e >= w2 && e < w2_end) {
+            const int k = (int)((e - w2) / H2N), n = (int)((e - w2) % H2N);
+            v = *reinterpret_cast<const f32x4 *>(tiles + tl_tile(k >> 6, n >> 6) + (k & 63) * 64 + (n & 63));
+        } else {
+            v = *reinterpret_cast<const f32x4 *>(src + e);
+        }
+        *reinterpret_cast<f32x4 *>(dst + e) = v;
+    }
+    for (int64_t e = 4 * n4 + tid; e < A.n_actor; e += 256) dst[e] = src[e];     // the tail (b3) is never W2
+    const int64_t o_min = (A.n_actor + 3) & ~(int64_t)3;
+    if (tid < SHEMS_NSTATE) {
+        dst[o_min + tid] = gsh(A.s_min, off)[tid];
+        dst[o_min + 16 + tid] = gsh(A.s_max, off)[tid];
+    }
+}
+
 }  // namespace tp
 }  // namespace shems
 
@@ -1267,4 +1326,44 @@ extern "C" int shems_group_w2_to_tiled(const shems_ddpg *d0, const shems_group *
 extern "C" int shems_group_w2_to_flux(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, void *stream)
 {
     return w2_layout("shems_group_w2_to_flux", false, d0, g, t, stream);
+}
+
+// The evaluation sweep's score / compare / snapshot for a whole group (k_group_eval_best above); every argument is checked before any
+// device call.
+extern "C" int shems_group_eval_best_dev(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, int32_t l1, int32_t l2,
+                                         const double *d_returns, int32_t runs, int32_t episode, double *d_score, double *d_best_score,
+                                         int32_t *d_best_run, uint8_t *d_improved, float *d_best0, int64_t best_stride_bytes, void *stream)
+{
+    const char *fn = "shems_group_eval_best_dev";
+    if (!g || g->count < 1 || g->stride_bytes < 0 || (g->stride_bytes & 15) != 0 || (g->count > 1 && g->stride_bytes == 0))
+        return set_error(SHEMS_ERR_ARG, "%s: shems_group needs count >= 1 and a 16-byte-multiple stride", fn);
+    const int64_t e_eval = g->envs_per_learner;
+    if (e_eval < 32 || e_eval % 32 != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: envs_per_learner (the eval block) must be a positive multiple of 32 (got %lld)", fn, (long long)e_eval);
+    if (runs < 1 || runs > e_eval)
+        return set_error(SHEMS_ERR_ARG, "%s: runs must be in 1..envs_per_learner = %lld (got %d)", fn, (long long)e_eval, runs);
+    if (!d0 || !d0->actor || !d0->s_min || !d0->s_max) return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg needs actor, s_min and s_max", fn);
+    const bool wide = l1 != 0 || l2 != 0;
+    int64_t n_actor = SHEMS_ACTOR_PARAMS;
+    if (wide) {
+        int64_t nc = 0;
+        if (t) return set_error(SHEMS_ERR_ARG, "%s: the wide form (l1, l2) = (%d, %d) has no tiled layout: t must be NULL", fn, l1, l2);
+        if (shems_wide_params(l1, l2, &n_actor, &nc) != SHEMS_OK)
+            return set_error(SHEMS_ERR_ARG, "%s: hidden sizes (%d, %d) outside 1..4096", fn, l1, l2);
+    }
+    if (t && (!t->actor || ((uintptr_t)t->actor & 15) != 0))
+        return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t.actor must be a 16-byte aligned device pointer", fn);
+    if (((uintptr_t)d0->actor & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: the actor block must be 16-byte aligned", fn);
+    if (!d_returns || !d_score || !d_best_score || !d_best_run || !d_improved || !d_best0)
+        return set_error(SHEMS_ERR_ARG, "%s: returns, score, best_score, best_run, improved and the snapshot slab are required", fn);
+    if ((((uintptr_t)d_returns | (uintptr_t)d_score | (uintptr_t)d_best_score) & 7) != 0 || ((uintptr_t)d_best_run & 3) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: returns / score / best_score must be 8-byte and best_run 4-byte aligned", fn);
+    const int64_t row = 4 * (((n_actor + 3) & ~(int64_t)3) + 32);     // actor | pad | s_min[9] | pad | s_max[9] | pad
+    if (((uintptr_t)d_best0 & 15) != 0 || (best_stride_bytes & 15) != 0 || best_stride_bytes < row)
+        return set_error(SHEMS_ERR_ARG, "%s: the snapshot slab must be 16-byte aligned with a 16-byte-multiple stride of at least %lld bytes "
+                         "(got %lld)", fn, (long long)row, (long long)best_stride_bytes);
+    EvalBestArgs A{d0->actor, d0->s_min, d0->s_max, t ? t->actor : nullptr, g->count > 1 ? g->stride_bytes : 0, n_actor, d_returns, e_eval, runs,
+                   episode, d_score, d_best_score, d_best_run, d_improved, d_best0, best_stride_bytes};
+    hipLaunchKernelGGL(k_group_eval_best, dim3((unsigned)g->count), dim3(256), 0, (hipStream_t)stream, A);
+    return hip_ok(hipGetLastError(), "k_group_eval_best launch");
 }

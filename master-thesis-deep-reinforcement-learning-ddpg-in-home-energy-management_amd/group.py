@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .ddpg import (ACTION, BATCH_SIZE, ETA_ACT, ETA_CRIT, GAMMA, L1, L2, MEM_SIZE, N_ACTOR, N_CRITIC, NOISE_SIGMA, STATE, TAU, Agent, RingWindow,
-                   _declare, act_kernel_name)
+from .ddpg import (ACTION, BATCH_SIZE, EP_LENGTH_TRAIN, ETA_ACT, ETA_CRIT, GAMMA, L1, L2, MEM_SIZE, N_ACTOR, N_CRITIC, NOISE_SIGMA, SEED_INI,
+                   STATE, TAU, Agent, RingWindow, _declare, act_kernel_name, unpad_net, unpad_net_from)
 from .replay import ReplayRing
 
 
@@ -183,6 +183,8 @@ def _declare_group():
     for fn in ("shems_group_hparams_check", "shems_act_step_group_hp_dev", "shems_ddpg_group_update_hp", "shems_group_hparams_check_wide",
                "shems_wide_group_workspace_floats", "shems_wide_group_update", "shems_wide_act_step_group_dev"):
         getattr(L, fn).restype = C.c_int
+    L.shems_group_eval_best_dev.argtypes = [PD, PG, PT, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]
+    L.shems_group_eval_best_dev.restype = C.c_int
     for fn in ("shems_act_step_group_dev", "shems_ddpg_group_critic_grad", "shems_ddpg_group_critic_apply",
                "shems_ddpg_group_actor_grad", "shems_ddpg_group_actor_apply", "shems_minmax_group_dev"):
         getattr(L, fn).restype = C.c_int
@@ -392,22 +394,29 @@ class LearnerGroup:
                                                   C.c_void_p(a0.s_max.data_ptr()), self._stream()))
         return self
 
-    def act_step(self, env, train=True, tick=None, a_out=None, returns_acc=None, window=None):
+    def act_step(self, env, train=True, tick=None, a_out=None, returns_acc=None, window=None, noise_acc=None, envs_per_learner=None):
         """One fused vector step for all learners: env i acts with learner i // E's actor; with `window` = (pos, count, offset)
-        each learner stores `count` transitions of its own env block into its own ring."""
-        if env.n != self.n_envs:
+        each learner stores `count` transitions of its own env block into its own ring.  noise_acc: float32 [n] device tensor, env i's
+        act() noise mean is added to noise_acc[i] (DDPG.jl:224).  envs_per_learner: the env block of this step when it is not the
+        group's training block (the evaluation sweep's E_eval; no window then)."""
+        epl = self.envs_per_learner if envs_per_learner is None else int(envs_per_learner)
+        if env.n != self.count * epl:
             raise ValueError("the env batch must hold count * envs_per_learner envs")
+        if noise_acc is not None and (noise_acc.dtype != self.torch.float32 or noise_acc.numel() != env.n or not noise_acc.is_contiguous()
+                                      or noise_acc.device != self.device):
+            raise ValueError("noise_acc must be a contiguous float32 tensor of one value per env on the group's device")
         env.use_torch_stream()
         v, g = env.view(), self.struct()
+        g.envs_per_learner = epl
         a0 = self.learners[0]
-        p = a0._act_params(train, self.tick if tick is None else tick)
+        p = a0._act_params(train, self.tick if tick is None else tick, noise_acc=noise_acc)
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
         r0 = self.rings[0].struct()
         w = RingWindow(*window) if window is not None else None
         if self.form == "wide":                    # four launches for the whole group (noise mu / sigma from the records, if any)
-            if self._act_ws is None:
-                need = C.c_int64(0)
-                _capi.check(self.L.shems_wide_act_workspace_floats(*self.hidden, self.n_envs, C.byref(need)))
+            need = C.c_int64(0)
+            _capi.check(self.L.shems_wide_act_workspace_floats(*self.hidden, env.n, C.byref(need)))
+            if self._act_ws is None or self._act_ws.numel() < need.value:      # (an eval batch may be wider than the training batch)
                 self._act_ws = self.torch.empty(need.value, dtype=self.torch.float32, device=self.device)
             _capi.check(self.L.shems_wide_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), *self.hidden,
                                                              self._hp_ptr() if self._hp_dev is not None else None, C.c_void_p(self._act_ws.data_ptr()),
@@ -490,9 +499,10 @@ class LearnerGroup:
             raise ValueError("window_count must be in 1 .. envs_per_learner")
         return wc, (0 if wc == 1 else (self.tick * wc) % E)
 
-    def episode_(self, env, train=True, num_steps=None, rng_ep=0, episode=0, window_count=None):
+    def episode_(self, env, train=True, num_steps=None, rng_ep=0, episode=0, window_count=None, noise_acc=None):
         """episode! for all learners at once (cf. Agent.episode_).  Returns the per-env episode returns [count * E].
-        window_count: see ring_window (1 = one remembered transition per update, the thesis protocol's update-to-data ratio)."""
+        window_count: see ring_window (1 = one remembered transition per update, the thesis protocol's update-to-data ratio).
+        noise_acc: float32 [count * E] device tensor that accumulates every env's act() noise mean (Agent.last_noise)."""
         t = self.torch
         num_steps = env.maxsteps if num_steps is None else int(num_steps)
         env.reset_(rng_ep, episode=episode) if rng_ep != -1 else env.reset_(-1)
@@ -500,11 +510,189 @@ class LearnerGroup:
         for step in range(num_steps):
             tick = (int(episode) * 4096 + step) & 0xFFFFFFFF
             win = (self.rings[0].pos, *self.ring_window(num_steps, window_count)) if train else None
-            self.act_step(env, train=train, tick=tick, returns_acc=returns, window=win)
+            self.act_step(env, train=train, tick=tick, returns_acc=returns, window=win, noise_acc=noise_acc)
             if train:
                 self.replay()
             self.tick += 1
         return returns
+
+    # ---- run_episodes (DDPG.jl:244-298) for every learner ----------------------------------------------------------------------------
+    def run_episodes(self, env_train, env_eval, num_ep, test_every=100, test_runs=100, seed=None, window_count=None, on_eval=None,
+                     on_best=None):
+        """Agent.run_episodes for every learner at once: `num_ep` training episodes (episode_ with rng_ep = seed, episode = i), and when
+        i % test_every == 1 an evaluation sweep on env_eval (eval_batch: count blocks of E_eval envs, learner l's block on its charger):
+        every block reset with the Agent's fixed key (SEED_INI, episode 0, env indices from 0 inside the block), 72 fused group steps
+        without noise, then ONE launch (shems_group_eval_best_dev) scores every learner on its first test_runs envs and snapshots the
+        actors that beat their best score.  A sweep leaves the training state alone (networks, moments, tiles, rings, tick, updates).
+        Per episode the learners' mean return and mean act() noise stay on the device (no host synchronisation); a sweep copies its
+        scores to the host once, for on_eval(l, i, total_reward_l, score_l) (every learner) and on_best(l, i, best_actor_l,
+        total_reward_l [i], score_mean_l [sweeps so far]) (the learners that improved; best_actor_l at the learner's own hidden size).
+        On return flux_() has run, so learners[l].export_actor() is the last actor.  Returns a GroupRun."""
+        E_eval = run_episodes_check(self.count, self.n_envs, getattr(env_train, "n", None), getattr(env_eval, "n", None), num_ep, test_every,
+                                    test_runs)
+        t = self.torch
+        L, E, num_ep, test_every, test_runs = self.count, self.envs_per_learner, int(num_ep), int(test_every), int(test_runs)
+        seed = self.seed if seed is None else int(seed)
+        dev = self.device
+        res = GroupRun(self, num_ep, test_every)
+        noise_acc = t.zeros(self.n_envs, dtype=t.float32, device=dev)
+        ev = t.cuda.Event
+        t_start, t_end, sweeps = ev(enable_timing=True), ev(enable_timing=True), []
+        t_start.record()
+        for i in range(1, num_ep + 1):
+            noise_acc.zero_()
+            ret = self.episode_(env_train, train=True, rng_ep=seed, episode=i, window_count=window_count, noise_acc=noise_acc)
+            res._total[:, i - 1] = ret.view(L, E).mean(1).to(t.float32)
+            res._noise[:, i - 1] = noise_acc.view(L, E).mean(1)
+            if i % test_every != 1:
+                continue
+            k = -(-i // test_every) - 1
+            e0, e1 = ev(enable_timing=True), ev(enable_timing=True)
+            e0.record()
+            returns = self._eval_returns(env_eval, E_eval)
+            d, g = self.learners[0]._ddpg_args(), self.struct()
+            g.envs_per_learner = E_eval
+            tl = self.tiled and not self._flux_valid           # the current W2 lives in the tiles only
+            w2t = self.w2t_struct() if tl else None
+            l1, l2 = self.hidden if self.form == "wide" else (0, 0)
+            ptr = lambda x: C.c_void_p(x.data_ptr())
+            _capi.check(self.L.shems_group_eval_best_dev(C.byref(d), C.byref(g), C.byref(w2t) if tl else None, l1, l2, ptr(returns), test_runs, i,
+                                                         ptr(res._score), ptr(res._best_score), ptr(res._best_run), ptr(res._improved),
+                                                         ptr(res.best), res.best_stride, self._stream()))
+            res._score_mean[:, k] = res._score
+            e1.record()
+            sweeps.append((e0, e1))
+            if on_eval is None and on_best is None:
+                continue
+            host = t.stack([res._score, res._improved.to(t.float64), res._total[:, i - 1].to(t.float64)]).cpu().numpy()    # the sweep's one copy
+            score, imp, tot = host[0], host[1] > 0, host[2].astype(np.float32)
+            if on_best is not None and imp.any():
+                won = np.flatnonzero(imp)
+                rows = res.best[t.as_tensor(won, device=dev), :res.n_actor].cpu().numpy()
+                tr, sm = res._total[:, :i].cpu().numpy(), res._score_mean[:, :k + 1].cpu().numpy()
+                for r, l in enumerate(won):
+                    on_best(int(l), i, res._unpad(int(l), rows[r]), tr[l], sm[l])
+            if on_eval is not None:
+                for l in range(L):
+                    on_eval(l, i, float(tot[l]), float(score[l]))
+        t_end.record()
+        t_end.synchronize()
+        res.wall_ms = t_start.elapsed_time(t_end)
+        res.sweep_ms = sum(a.elapsed_time(b) for a, b in sweeps)
+        res.sweeps = len(sweeps)
+        self.flux_()
+        return res
+
+
+    def _eval_returns(self, env_eval, E_eval):
+        """The 72 hours of one evaluation sweep: every learner's block reset with Agent.run_episodes' fixed key (SEED_INI, episode 0, env
+        indices from 0 inside the block: the same starts every sweep, DDPG.jl:273-277), then the fused group steps without noise.
+        Returns the per-env float64 returns [count * E_eval]."""
+        from .env import EnvSlice
+        t = self.torch
+        for l in range(self.count):
+            EnvSlice(env_eval, l * E_eval, E_eval).reset_(SEED_INI, episode=0)
+        returns = t.zeros(env_eval.n, dtype=t.float64, device=self.device)
+        for step in range(EP_LENGTH_TRAIN):
+            self.act_step(env_eval, train=False, tick=step, returns_acc=returns, envs_per_learner=E_eval)
+        return returns
+
+    def eval_scores(self, env_eval, test_runs=100):
+        """One evaluation sweep of the CURRENT actors (no snapshot, no best tracking): every learner's score, the mean of its first
+        test_runs eval returns summed in ascending order (float64 [count]), as run_episodes scores them."""
+        E_eval = run_episodes_check(self.count, self.n_envs, self.n_envs, getattr(env_eval, "n", None), 1, 1, test_runs)
+        r = self._eval_returns(env_eval, E_eval).view(self.count, E_eval)[:, :int(test_runs)].cpu().numpy()
+        return np.cumsum(r, axis=1)[:, -1] / int(test_runs)
+
+
+def run_episodes_check(count, n_envs, n_train, n_eval, num_ep, test_every, test_runs):
+    """LearnerGroup.run_episodes' argument checks (host only, before any device work).  Returns E_eval, the eval block of one learner."""
+    if n_train != n_envs:
+        raise ValueError(f"env_train holds {n_train} envs; the group trains count x envs_per_learner = {n_envs}")
+    if int(num_ep) < 1 or int(test_every) < 1:
+        raise ValueError(f"num_ep ({num_ep}) and test_every ({test_every}) must be >= 1")
+    if n_eval is None or n_eval < count or n_eval % count:
+        raise ValueError(f"env_eval holds {n_eval} envs: it must hold count = {count} equal blocks (eval_batch builds it)")
+    E_eval = n_eval // count
+    if E_eval % 32:
+        raise ValueError(f"env_eval's block of {E_eval} envs per learner is not a multiple of 32 (eval_batch rounds test_runs up)")
+    if not 1 <= int(test_runs) <= E_eval:
+        raise ValueError(f"test_runs {test_runs} must be in 1 .. {E_eval}, env_eval's block per learner")
+    return E_eval
+
+
+class GroupRun:
+    """What LearnerGroup.run_episodes returns: per learner the curves, the best run and the device snapshot slab `best`
+    ([count][row] float32, row l = actor (the group's padded layout) | pad | s_min[9] | pad | s_max[9] | pad, harness.inference_many's row)."""
+
+    def __init__(self, grp, num_ep, test_every):
+        t = grp.torch
+        L, dev = grp.count, grp.device
+        self.count, self.hidden_of = L, [ag.hidden for ag in grp.learners]
+        self.layout_hidden = grp.hidden if grp.form == "wide" else (L1, L2)
+        self.n_actor = grp.layout["actor"][1]
+        self.row = _pad4(self.n_actor) + 32
+        self.best_stride = self.row * 4
+        self.best = t.zeros((L, self.row), dtype=t.float32, device=dev)
+        self._total = t.zeros((L, num_ep), dtype=t.float32, device=dev)
+        self._noise = t.zeros((L, num_ep), dtype=t.float32, device=dev)
+        self._score_mean = t.zeros((L, -(-num_ep // test_every)), dtype=t.float64, device=dev)
+        self._score = t.zeros(L, dtype=t.float64, device=dev)
+        self._best_score = t.full((L,), -100000.0, dtype=t.float64, device=dev)      # best_score = -100000 (DDPG.jl:246)
+        self._best_run = t.zeros(L, dtype=t.int32, device=dev)
+        self._improved = t.zeros(L, dtype=t.uint8, device=dev)
+        self.wall_ms = self.sweep_ms = 0.0
+        self.sweeps = 0
+
+    total_reward = property(lambda self: self._total.cpu().numpy())          # [L][num_ep] float32
+    noise_mean = property(lambda self: self._noise.cpu().numpy())            # [L][num_ep] float32
+    score_mean = property(lambda self: self._score_mean.cpu().numpy())       # [L][ceil(num_ep / test_every)] float64
+    best_run = property(lambda self: self._best_run.cpu().numpy())           # [L] int32, 0: no sweep beat -100000
+    best_score = property(lambda self: self._best_score.cpu().numpy())
+
+    def _unpad(self, l, flat):
+        h = self.hidden_of[l]
+        return unpad_net_from(flat, STATE, ACTION, h, self.layout_hidden) if self.layout_hidden != (L1, L2) else unpad_net(flat, STATE, ACTION, h)
+
+    def best_actor(self, l):
+        """Learner l's best actor at its own hidden size (what the reference's saveBSON(...; path="temp") holds)."""
+        return self._unpad(l, self.best[l, :self.n_actor].cpu().numpy())
+
+    def best_norm(self, l):
+        """(s_min, s_max) stored with learner l's best actor."""
+        o = _pad4(self.n_actor)
+        r = self.best[l].cpu().numpy()
+        return r[o:o + STATE].copy(), r[o + 16:o + 16 + STATE].copy()
+
+
+def eval_batch(tables, table_of_learner, count, test_runs=100, maxsteps=1439, charger_ids=None, device=None):
+    """The grouped eval ShemsBatch of LearnerGroup.run_episodes: count x E_eval envs, E_eval = test_runs rounded up to 32; learner l's
+    block runs on tables[table_of_learner[l]] with its config (make_config(charger_ids[k], ...); default charger 98) through cfg_of_env.
+    maxsteps: the eval data set's episode length (main.EP_LENGTH; 1439 = ("all", "eval"))."""
+    from .env import ShemsBatch, make_config
+    tabs = list(tables)
+    count, test_runs = int(count), int(test_runs)
+    if count < 1 or test_runs < 1:
+        raise ValueError(f"count ({count}) and test_runs ({test_runs}) must be >= 1")
+    if not tabs:
+        raise ValueError("eval_batch needs at least one table")
+    tol = np.asarray(table_of_learner, dtype=np.int64).reshape(-1)
+    if tol.size != count:
+        raise ValueError(f"table_of_learner holds {tol.size} entries for {count} learners")
+    if tol.size and (tol.min() < 0 or tol.max() >= len(tabs)):
+        raise ValueError(f"table_of_learner names table {int(tol.max() if tol.max() >= len(tabs) else tol.min())}; there are {len(tabs)}")
+    ids = [98] * len(tabs) if charger_ids is None else [int(c) for c in charger_ids]
+    if len(ids) != len(tabs):
+        raise ValueError(f"charger_ids holds {len(ids)} entries for {len(tabs)} tables")
+    if int(maxsteps) < EP_LENGTH_TRAIN:
+        raise ValueError(f"maxsteps {maxsteps} < {EP_LENGTH_TRAIN}: a sweep runs {EP_LENGTH_TRAIN} steps")
+    E_eval = -(-test_runs // 32) * 32
+    row0 = np.cumsum([0] + [np.asarray(t).shape[0] for t in tabs])
+    cfgs = [make_config(c, row0[k], np.asarray(tabs[k]).shape[0]) for k, c in enumerate(ids)]
+    co = np.repeat(tol, E_eval).astype(np.uint16)
+    import torch
+    dev = torch.cuda.current_device() if device is None else int(device)
+    return ShemsBatch(count * E_eval, int(maxsteps), tabs, cfgs, co, device=dev).use_torch_stream()
 
 
 class GroupWorkload:
