@@ -19,6 +19,11 @@ The pre-warm exists because a GPU that was idle a moment ago runs its first mill
 --warmup 5` straight after start-up read 347 M env-steps/s on a build that sustains 385 M (same command with the pre-warm: 383-385 M).
 `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs); the pre-warm then runs on a twin of
 the workload, so that two builds given the same arguments can be compared output for output.
+
+A plain run ends there and prints its line (`roofline` and `cpu_baseline` null).  `--full` adds everything else the benchmark measures,
+after the timed steps and outside them: the roofline pass (the dominant kernel timed with HIP events inside its loop, the learner's update,
+the gradient exchange's figures under `data_parallel` with several ranks), the CPU baseline (unless `--no-cpu-baseline`) and, for the
+default headline workload, the `also` sub-records of the other configurations.
 """
 from __future__ import annotations
 
@@ -68,19 +73,24 @@ def parse():
     ap.add_argument("--group-window", type=int, default=None, help="group mode: transitions each learner remembers per vector step.  Default: the rotating window of "
                     "min(envs per learner, MEM_SIZE / 72) households; 1 = the reference's ratio, ONE remembered transition per replay() (DDPG.jl:229-233), household 0 of "
                     "the learner's block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--also", default="auto", choices=["auto", "on", "off"], help="after the headline run, time the other configurations BASELINE.json names and the "
-                    "learner-group shapes on the same box and report them as compact sub-records under \"also\" (auto: only for the default headline workload -- "
-                    "train mode, 65 536 envs, one GPU)")
-    ap.add_argument("--also-which", default=None, help="comma-separated subset of the sub-record names (tests)")
+    ap.add_argument("--full", action="store_true", help="after the headline run, everything else the benchmark measures: the roofline pass, the CPU "
+                    "baseline and the \"also\" sub-records (off: the line carries the headline and what the timed run itself reports)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--also", default="auto", choices=["auto", "on", "off"], help="with --full: after the headline run, time the other configurations BASELINE.json "
+                    "names and the learner-group shapes on the same GPU and report them as compact sub-records under \"also\" (auto: only for the default "
+                    "headline workload -- train mode, 65 536 envs, one GPU)")
+    ap.add_argument("--also-which", default=None, help="with --full: comma-separated subset of the sub-record names (tests)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most "
                          "64 MB in all (an array larger than its share: a fixed, seeded sample of its rows).  The pre-warm then runs on a twin of "
                          "the workload, so that the dumped step depends on the arguments alone")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.also == "on" or args.also_which is not None):
+        ap.error("--also on / --also-which: the sub-records belong to --full")
+    return args
 
 
-# The other workloads this repo quotes numbers for, timed by the default run so that every claimed figure stands under the driver's clock
+# The other workloads this repo quotes numbers for, timed by a --full run so that every claimed figure stands under the benchmark's own clock
 # (a sixth record added for the thesis-exact ratio): BASELINE configs[1] (4 096 envs), the configs[3] shard (8 192 envs per GPU), configs[4] on one GPU (65 536
 # envs x 10 charger profiles x discomfort-weight sweep), and the learner groups of SURVEY 8(f) rank 4 at the thesis protocol's width
 # (40 seeds x 10 chargers, RL-SHEMS_bs_scheduler_1179_08_on_01-98.sh:67-87) and at 32 learners x 2 048 households.
@@ -665,25 +675,26 @@ def main():
         census = {"backend": dist.get_backend(), "rccl_ranks": dist.get_world_size(), "ranks": gathered,
                   "distinct_devices": len({(g["host"], g["uuid"], g["pci_bus_id"], g["device_index"]) for g in gathered})}
 
+    # From here to the JSON line, only --full measures anything: a plain run has measured its K timed steps and prints them.
     roof = None
     cpu = None
     all_ranks_pass = dist is not None and mode == "train"      # the data-parallel pass issues collectives: every rank runs it
     t_pass0 = time.perf_counter()
-    if rank == 0 or all_ranks_pass:
+    if args.full and (rank == 0 or all_ranks_pass):
         k = wl.kernel_pass(max(200, min(args.steps, 500)))
     t_pass = time.perf_counter() - t_pass0
     t_cpu = 0.0
     also, t_also = None, 0.0
     headline_default = (mode == "train" and world == 1 and args.envs == 65536 and args.updates == 1 and not args.mixed and not args.scaled_replay
                         and not args.overlap and args.hidden.lower() == "250x500")
-    if args.also == "on" or (args.also == "auto" and headline_default):
+    if args.full and (args.also == "on" or (args.also == "auto" and headline_default)):
         if world != 1:
             raise SystemExit("--also on: the sub-records are one-GPU workloads")
         # the headline workload's buffers are kept (its learner checksum is read below); the sub-records fit beside them (< 8 GB)
         t_also0 = time.perf_counter()
         also = run_also(S, torch, which=None if args.also_which is None else set(args.also_which.split(",")), log=lambda m: print(m, file=sys.stderr, flush=True))
         t_also = time.perf_counter() - t_also0
-    if rank == 0:
+    if rank == 0 and args.full:
         achieved = k["algorithmic"] / (k["avg_us"] * 1e-6) / (1e9 if k["unit"] == "GB/s" else 1e12)
         traffic, traffic_src = None, None
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")       # rocprofv3 --pmc passes, see profiles/README.md
@@ -773,6 +784,7 @@ def main():
             "roofline_pass_s": t_pass,
             "cpu_baseline_s": t_cpu,
             "also_s": t_also,
+            "full": bool(args.full),
         }
         if also is not None:
             out["also"] = also

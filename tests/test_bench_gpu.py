@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -23,7 +24,7 @@ def _run(cmd, env=None, timeout=420):
 
 
 def test_bench_json_contract_small():
-    d = _run([sys.executable, "bench.py", "--steps", "16", "--warmup", "4", "--envs", "8192", "--no-cpu-baseline", "--prewarm-s", "0.2"])
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "16", "--warmup", "4", "--envs", "8192", "--no-cpu-baseline", "--prewarm-s", "0.2"])
     assert d["prewarm_steps"] >= 50 and d["steps"] == 16 and d["warmup"] == 4          # the pre-warm is extra, untimed and reported
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -52,9 +53,9 @@ def test_bench_json_contract_small():
 
 
 def test_bench_also_records():
-    """The default run's "also" object (here switched on for a small headline and two of its six entries): compact sub-records of the other
+    """The --full run's "also" object (here switched on for a small headline and two of its six entries): compact sub-records of the other
     configurations and of the learner groups, each with value, ms_per_step, steps, updates_per_sec and roofline{kernel, kernel_avg_us, frac}."""
-    d = _run([sys.executable, "bench.py", "--steps", "16", "--warmup", "4", "--envs", "8192", "--no-cpu-baseline", "--prewarm-s", "0.2",
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "16", "--warmup", "4", "--envs", "8192", "--no-cpu-baseline", "--prewarm-s", "0.2",
               "--also", "on", "--also-which", "config2_4096_envs,group_32x2048"])
     assert d["config"]["envs_per_gpu"] == 8192 and d["value"] > 1e6                      # the headline is untouched
     also = d["also"]
@@ -70,9 +71,24 @@ def test_bench_also_records():
     assert c2["roofline"]["kernel"] == "shems::k_actg<1, 4, 2, 3>" and abs(c2["updates_per_sec"] - c2["steps"] / (c2["ms_per_step"] * 1e-3 * c2["steps"])) < 1e-3 * c2["updates_per_sec"]
     assert g["update_form"] == "throughput" and abs(g["updates_per_sec"] - 32 * 1e3 / g["ms_per_step"]) < 1e-3 * g["updates_per_sec"]
     assert g["roofline"]["kernel"].startswith("grouped replay(), throughput form") and g["roofline"]["other_kernel"]["kernel"].startswith("shems::k_act")
-    # without the switch a non-default headline carries no sub-records
-    d0 = _run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--envs", "4096", "--no-cpu-baseline", "--prewarm-s", "0.1"])
+    # without the switch a non-default headline carries no sub-records, not even under --full
+    d0 = _run([sys.executable, "bench.py", "--full", "--steps", "8", "--warmup", "2", "--envs", "4096", "--no-cpu-baseline", "--prewarm-s", "0.1"])
     assert "also" not in d0 and d0["also_s"] == 0.0
+
+
+def test_bench_plain_run_measures_the_steps_alone():
+    """Without --full the contract's command on the default headline workload sets up, pre-warms, warms up, times its steps and prints the
+    line: no roofline pass, no CPU baseline, no "also" sub-records, and at most 30 s of the process's life outside the W + K steps."""
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)])
+    wall = time.perf_counter() - t0
+    assert d["metric"] == "env-steps/sec" and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["config"]["mode"] == "train" and d["config"]["envs_per_gpu"] == 65536 and d["steps"] == steps and d["warmup"] == warmup
+    assert abs(d["value"] - 65536 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"] and d["prewarm_steps"] > 0
+    assert d["full"] is False and d["roofline"] is None and d["cpu_baseline"] is None and "also" not in d
+    assert d["roofline_pass_s"] < 0.01 and d["cpu_baseline_s"] == 0.0 and d["also_s"] == 0.0
+    assert wall - (steps + warmup) * d["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 def test_bench_group_window_one():
@@ -167,7 +183,7 @@ def test_bench_mixed_profiles():
 
 def test_bench_group_mode_with_charger_grid():
     """--mode group: independent learners, learner l on charger profile l mod 10."""
-    d = _run([sys.executable, "bench.py", "--mode", "group", "--learners", "16", "--envs", "8192", "--mixed", "--steps", "12", "--warmup", "2",
+    d = _run([sys.executable, "bench.py", "--full", "--mode", "group", "--learners", "16", "--envs", "8192", "--mixed", "--steps", "12", "--warmup", "2",
               "--no-cpu-baseline"])
     assert d["config"]["mode"] == "group" and d["learners"] == 16 and d["envs_per_learner"] == 512
     assert d["updates_per_sec"] > 16 * 100 and d["value"] > 1e6
@@ -189,7 +205,7 @@ def test_bench_group_mode_with_charger_grid():
 
 def test_two_rank_data_parallel_rehearsal():
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-              "--master-port", "29541", "bench.py", "--gpus", "2", "--steps", "24", "--warmup", "4", "--envs", "4096"],
+              "--master-port", "29541", "bench.py", "--full", "--gpus", "2", "--steps", "24", "--warmup", "4", "--envs", "4096"],
              env={"SHEMS_BENCH_ONE_DEVICE": "1", "SHEMS_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["cpu_baseline"] is None and d["value"] > 0
     _check_data_parallel_fields(d, 2)
@@ -226,7 +242,7 @@ def test_bench_starts_its_own_ranks_without_torchrun():
         assert k not in os.environ or True
     e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     e.update(env)
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "24", "--warmup", "4", "--envs", "8192"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "24", "--warmup", "4", "--envs", "8192"],
                          cwd=U.ROOT, env=e, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -310,7 +326,7 @@ def test_driver_command_rehearsal_at_the_widest_world_one_box_allows():
     admits at most six processes on the card at once (this pytest process is one of them), so the rehearsal inside the suite is N = 4
     rank processes on device 0 over gloo; the N = 6 run of the same command outside pytest is profiles/r05_dp_world6_rehearsal.json.
     Every data-parallel field, one census entry per rank, replicas identical."""
-    d = _run([sys.executable, "bench.py", "--gpus", "4", "--envs", "8192", "--steps", "20", "--warmup", "5", "--prewarm-s", "0"],
+    d = _run([sys.executable, "bench.py", "--full", "--gpus", "4", "--envs", "8192", "--steps", "20", "--warmup", "5", "--prewarm-s", "0"],
              env={"SHEMS_BENCH_ONE_DEVICE": "1", "SHEMS_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 4 and d["config"]["envs_per_gpu"] == 8192 and len(d["rank_census"]) == 4
     assert abs(d["value"] - 4 * 8192 * 20 / (d["ms_per_step"] * 1e-3 * 20)) < 1e-3 * d["value"]      # whole-job aggregate

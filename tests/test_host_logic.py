@@ -46,6 +46,15 @@ def test_bench_rejects_mismatched_world_size():
     assert out.returncode != 0 and "WORLD_SIZE=3" in out.stderr
 
 
+def test_bench_sub_records_need_full():
+    """The "also" sub-records are part of --full: asking for them on a plain run is an argument error, raised before any GPU call."""
+    e = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    for extra in (["--also", "on"], ["--also-which", "config2_4096_envs"]):
+        out = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "0", *extra], cwd=U.ROOT, env=e,
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 2 and "--full" in out.stderr and not out.stdout.strip(), extra
+
+
 def test_cpu_baseline_times_the_port_not_python():
     """bench.py's cpu_baseline leg: both figures (all cores / one thread) with the thread counts stated, and no per-env foreign
     call in a timed loop (the batch accessors of oracle_c are single C calls)."""

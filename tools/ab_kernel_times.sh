@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
   O=$R/gpurun_out/abk_$(basename $lib .so)
   rm -rf $O; mkdir -p $O
-  SHEMS_HIP_LIB=$R/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --mode group --learners ${LEARNERS:-400} --envs ${ENVS:-51200} --mixed --no-cpu-baseline --steps 72 --warmup 8 --prewarm-s 0.5 > $O/kt.log 2>&1
+  SHEMS_HIP_LIB=$R/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --full --mode group --learners ${LEARNERS:-400} --envs ${ENVS:-51200} --mixed --no-cpu-baseline --steps 72 --warmup 8 --prewarm-s 0.5 > $O/kt.log 2>&1
   f=$(find $O/kt -name "*kernel_stats.csv" | head -1)
   echo "== $lib"
   python3 - "$f" <<PY

@@ -2,7 +2,7 @@
 of bench.py into profiles/<round>_pmc_mfma.csv: per kernel the MFMA-busy fraction and the effective clock.
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d <out> -- python3 <repo>/bench.py --steps 144 --warmup 8 --prewarm-s 0.2 --no-cpu-baseline [--envs N]
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d <out> -- python3 <repo>/bench.py --full --steps 144 --warmup 8 --prewarm-s 0.2 --no-cpu-baseline [--envs N]
     python tools/pmc_mfma.py <out> [<out2> ...] --out profiles/r03_pmc_mfma.csv
 
 Reading the counters (MI355X_MICROARCH.md, rocprofv3 PMC slots / DVFS give-back):
