@@ -197,6 +197,20 @@ def _blocks(flat, in_dim, out_dim, hidden):
     return [np.asarray(flat[o[i]:o[i + 1]]).reshape(sh) for i, sh in enumerate(shapes)]
 
 
+MAX_SUB_BATCHES = 8                             # sub-batch i of update `tick` samples with sampler tick `tick * 8 + i`
+
+
+def sub_batch_sizes(batch, width=128):
+    """The near-equal sizes a minibatch wider than one update pass (`width` columns) is run as (257 -> 86 + 86 + 85).  At most
+    MAX_SUB_BATCHES of them: a ninth would sample with tick `tick * 8 + 8`, the next update's first draw."""
+    batch = int(batch)
+    if not 1 <= batch <= MAX_SUB_BATCHES * width:
+        raise ValueError(f"BATCH_SIZE must be in 1..{MAX_SUB_BATCHES * width} (got {batch}): sub-batch i of an update samples with tick "
+                         f"`tick * {MAX_SUB_BATCHES} + i`, so more than {MAX_SUB_BATCHES} sub-batches would reuse the next update's draws")
+    k = -(-batch // width)
+    return [batch // k + (1 if i < batch % k else 0) for i in range(k)]
+
+
 def is_wide(hidden):
     """Hidden sizes the (250, 500) tile maps cannot hold (the reference grids' (300, 600)): such a network keeps its own flat layout
     and runs through the shems_wide_* entry points (csrc/shems_wide.hip), layer by layer."""
@@ -553,8 +567,7 @@ class Agent:
     def sub_batches(self):
         """BATCH_SIZE > 128: the near-equal sub-batch sizes replay() runs (150 -> 75 + 75, 200 -> 100 + 100), each with its own
         workspace and gradient buffers (allocated on first use)."""
-        k = -(-self.batch // self.MAX_PASS_BATCH)
-        sizes = [self.batch // k + (1 if i < self.batch % k else 0) for i in range(k)]
+        sizes = sub_batch_sizes(self.batch, self.MAX_PASS_BATCH)
         cur = getattr(self, "_subs", None)
         if cur is None or [x["batch"] for x in cur] != sizes:
             t = self.torch
@@ -595,7 +608,7 @@ class Agent:
         vp = lambda x: C.c_void_p(x.data_ptr())
         for i, sb in enumerate(subs):
             d = self._ddpg_args(sb)
-            self._critic_grad_ex(d, rs, len(ring), int(tick) * 8 + i, ex_pos, ex_cnt, st)
+            self._critic_grad_ex(d, rs, len(ring), int(tick) * MAX_SUB_BATCHES + i, ex_pos, ex_cnt, st)
             w = sb["batch"] / self.batch
             _capi.check(self.L.shems_ddpg_combine_dev(vp(self.grad_critic), vp(sb["gc"]), self.n_critic, 0.0 if i == 0 else 1.0, w, st))
             _capi.check(self.L.shems_ddpg_combine_dev(vp(self.losses), vp(sb["losses"]), 1, 0.0 if i == 0 else 1.0, w, st))

@@ -120,6 +120,45 @@ def _blocks(g, g64, in_dim, out_dim, what):
     return errs
 
 
+def _learner_tick_matches_float64(grp, l, ag, h, tick):
+    """Learner l of `grp` after its update at `tick`: every gradient block against float64 (_blocks), the losses, ADAM + soft update
+    and the moments element-wise from its own gradient; then `h` (the learner's host copy) is advanced to the kernel's state.  Returns
+    the block errors."""
+    errs = {}
+    idx = DO.sample_indices(grp.rng_seed + l, tick, h["batch"], len(grp.rings[l]))
+    Lr = DO.Learner(h["pa"], h["pc"], h["s_min"], h["s_max"])
+    s, a, r, s2, done = (h[k][idx] for k in ("s", "a", "r", "s2", "done"))
+    s2n = DO.normalize(s2, h["s_min"], h["s_max"])
+    q2 = DO.critic_forward(h["pct"], s2n, DO.actor_forward(h["pat"], s2n))
+    y = (r + h["gamma"] * (f32(1) - done.astype(f32)) * q2).astype(f32)
+    gc64, lc64 = Lr.critic_grad(s, a, y, dtype=np.float64)
+    gc = ag.grad_critic.cpu().numpy()
+    errs["critic"] = _blocks(gc, gc64, 11, 1, f"critic gradient of learner {l}, tick {tick}")
+    losses = ag.losses.cpu().numpy()
+    assert abs(losses[0] - lc64) < 1e-4 * max(1.0, abs(lc64)), (l, tick)
+    pc1 = h["opt_c"].step(h["pc"], gc)
+    crit = ag.critic.cpu().numpy()
+    np.testing.assert_allclose(crit, pc1, rtol=0, atol=1e-7)
+    np.testing.assert_allclose(ag.critic_t.cpu().numpy(), DO.soft_update(h["pct"], crit, h["tau"]), rtol=0, atol=1e-7)
+    np.testing.assert_allclose(ag.m_critic.cpu().numpy(), h["opt_c"].m, rtol=1e-6, atol=1e-12)
+    np.testing.assert_allclose(ag.v_critic.cpu().numpy(), h["opt_c"].v, rtol=1e-6, atol=1e-15)
+    Lr.critic = crit
+    ga64, la64 = Lr.actor_grad(s, dtype=np.float64)
+    ga = ag.grad_actor.cpu().numpy()
+    errs["actor"] = _blocks(ga, ga64, 9, 2, f"actor gradient of learner {l}, tick {tick}")
+    assert abs(losses[1] - la64) < 1e-4 * max(1.0, abs(la64)), (l, tick)
+    pa1 = h["opt_a"].step(h["pa"], ga)
+    act = ag.actor.cpu().numpy()
+    np.testing.assert_allclose(act, pa1, rtol=0, atol=1e-7)
+    np.testing.assert_allclose(ag.actor_t.cpu().numpy(), DO.soft_update(h["pat"], act, h["tau"]), rtol=0, atol=1e-7)
+    np.testing.assert_allclose(ag.m_actor.cpu().numpy(), h["opt_a"].m, rtol=1e-6, atol=1e-12)
+    np.testing.assert_allclose(ag.v_actor.cpu().numpy(), h["opt_a"].v, rtol=1e-6, atol=1e-15)
+    h["pa"], h["pc"], h["pat"], h["pct"] = act, crit, ag.actor_t.cpu().numpy(), ag.critic_t.cpu().numpy()
+    h["opt_c"].m, h["opt_c"].v = ag.m_critic.cpu().numpy().astype(h["opt_c"].m.dtype), ag.v_critic.cpu().numpy().astype(h["opt_c"].v.dtype)
+    h["opt_a"].m, h["opt_a"].v = ag.m_actor.cpu().numpy().astype(h["opt_a"].m.dtype), ag.v_actor.cpu().numpy().astype(h["opt_a"].v.dtype)
+    return errs
+
+
 def test_mixed_records_match_float64_per_learner_and_block(wide_oracle):
     torch, S, D, G = _mods()
     recs = _mixed_records()
@@ -141,38 +180,7 @@ def test_mixed_records_match_float64_per_learner_and_block(wide_oracle):
         grp.replay(tick=tick)
         torch.cuda.synchronize()
         for l, ag in enumerate(grp.learners):
-            h = host[l]
-            idx = DO.sample_indices(grp.rng_seed + l, tick, h["batch"], len(grp.rings[l]))
-            Lr = DO.Learner(h["pa"], h["pc"], h["s_min"], h["s_max"])
-            s, a, r, s2, done = (h[k][idx] for k in ("s", "a", "r", "s2", "done"))
-            s2n = DO.normalize(s2, h["s_min"], h["s_max"])
-            q2 = DO.critic_forward(h["pct"], s2n, DO.actor_forward(h["pat"], s2n))
-            y = (r + h["gamma"] * (f32(1) - done.astype(f32)) * q2).astype(f32)
-            gc64, lc64 = Lr.critic_grad(s, a, y, dtype=np.float64)
-            gc = ag.grad_critic.cpu().numpy()
-            _blocks(gc, gc64, 11, 1, f"critic gradient of learner {l}, tick {tick}")
-            losses = ag.losses.cpu().numpy()
-            assert abs(losses[0] - lc64) < 1e-4 * max(1.0, abs(lc64)), (l, tick)
-            pc1 = h["opt_c"].step(h["pc"], gc)
-            crit = ag.critic.cpu().numpy()
-            np.testing.assert_allclose(crit, pc1, rtol=0, atol=1e-7)
-            np.testing.assert_allclose(ag.critic_t.cpu().numpy(), DO.soft_update(h["pct"], crit, h["tau"]), rtol=0, atol=1e-7)
-            np.testing.assert_allclose(ag.m_critic.cpu().numpy(), h["opt_c"].m, rtol=1e-6, atol=1e-12)
-            np.testing.assert_allclose(ag.v_critic.cpu().numpy(), h["opt_c"].v, rtol=1e-6, atol=1e-15)
-            Lr.critic = crit
-            ga64, la64 = Lr.actor_grad(s, dtype=np.float64)
-            ga = ag.grad_actor.cpu().numpy()
-            _blocks(ga, ga64, 9, 2, f"actor gradient of learner {l}, tick {tick}")
-            assert abs(losses[1] - la64) < 1e-4 * max(1.0, abs(la64)), (l, tick)
-            pa1 = h["opt_a"].step(h["pa"], ga)
-            act = ag.actor.cpu().numpy()
-            np.testing.assert_allclose(act, pa1, rtol=0, atol=1e-7)
-            np.testing.assert_allclose(ag.actor_t.cpu().numpy(), DO.soft_update(h["pat"], act, h["tau"]), rtol=0, atol=1e-7)
-            np.testing.assert_allclose(ag.m_actor.cpu().numpy(), h["opt_a"].m, rtol=1e-6, atol=1e-12)
-            np.testing.assert_allclose(ag.v_actor.cpu().numpy(), h["opt_a"].v, rtol=1e-6, atol=1e-15)
-            h["pa"], h["pc"], h["pat"], h["pct"] = act, crit, ag.actor_t.cpu().numpy(), ag.critic_t.cpu().numpy()
-            h["opt_c"].m, h["opt_c"].v = ag.m_critic.cpu().numpy().astype(h["opt_c"].m.dtype), ag.v_critic.cpu().numpy().astype(h["opt_c"].v.dtype)
-            h["opt_a"].m, h["opt_a"].v = ag.m_actor.cpu().numpy().astype(h["opt_a"].m.dtype), ag.v_actor.cpu().numpy().astype(h["opt_a"].v.dtype)
+            _learner_tick_matches_float64(grp, l, ag, host[l], tick)
     assert bool(torch.isfinite(grp.slab[:, :grp.layout["ws"][0]]).all())     # (ws holds int32 slot indices)
 
 
