@@ -12,33 +12,37 @@
 //           latency-bound phases (stage 0, layer 1, layer 3, env tail) run under the other's MFMAs -- the default for large batches;
 //   k_actg  <= 8 192 envs: 32-env tiles, one wave per 64-column group; 8 waves per tile, or two workgroups per tile (<= 4 096 envs)
 //           joined by one 8-byte exchange per env;
-//   k_act   the round-1/2 kernel described next: learner groups, and the forms the all-forms test and A/B runs select by knob.
-// (In the description below "tile (a, b) holds the columns n = 128w + 4i + a" is round 2's layout; round 3 interleaves within
-// 64-column groups, see act_col.)
+//   k_act   learner groups (Flux-order and tiled W2), and the forms SHEMS_ACT_FORM = 2 / 3 force for the all-forms test and A/B runs.
 //
-// k_act -- decomposition (gfx950, wave64, 4 waves per workgroup, one workgroup per CU):
+// k_act<TM, NW = 4, RD> -- the free-running form (gfx950, wave64, 4 waves per workgroup = one per SIMD, one workgroup per CU):
 //   * a workgroup owns BM = 32*TM envs.  Everything is kept FEATURE-major ("[k][m]", env index
 //     contiguous) so that layer outputs come out of the MFMA in exactly the layout the next layer
 //     consumes: D'[n][m] = sum_k W[k][n] * H[k][m] with the weights as the MFMA A operand
 //     (A[i = n][k] = W[k][n0+i]: Flux's column-major out x in matrix IS [k][n]) and the activations as
 //     the B operand (B[k][j = m]).  v_mfma_f32_32x32x2_f32: lane l holds A[l&31][l>>5], B[l>>5][l&31].
 //   * layer 2 (97.5 % of the FLOPs): wave w accumulates the 128(n) x BM(m) slab n in [128w, 128w+128)
-//     = 4 x TM tiles of 32x32 (16*4*TM accumulator registers) over K = 250 = 125 MFMA k-steps.  Tile (a, b) holds the
-//     columns n = 128w + 4i + a and the envs m = TM*j + b (i, j = a lane's MFMA row / column index), so what a lane needs
-//     per k-step is contiguous in LDS: one ds_read_b128 of weights, one of activations, fetched one k-step ahead.
-//     Both operands are streamed through LDS, double-buffered: W2 in chunks of 16 k-rows by LDS-DMA
-//     (global_load_lds_dwordx4: wave w moves the 8 consecutive 1-KiB pieces 8w..8w+7 during the first half of the previous
-//     chunk, one 64-bit address and one M0 value per chunk, the piece chosen by the instruction's immediate offset), and the
-//     layer-1 activations relu(W1 x + b1) in 32-row groups that are RECOMPUTED ON THE MATRIX PIPE as well (K = 9 inputs +
-//     a bias row = 10 = 5 MFMA k-steps per 32x32 tile, +1.9 % MFMA work; an inline-asm chain so that its
-//     accumulator stays in VGPRs) -- cheaper than holding the 250 x BM activation tile (125 KB at BM = 128) in LDS, and it
-//     keeps the VALU out of the main loop (the first version computed them with FMAs: profiles/r01_train_v1_*).  N is padded
-//     500 -> 512 (zero bias / W3 rows), the last chunk runs only its 5 real k-steps.
+//     = 4 x TM tiles of 32x32 (16*4*TM accumulator registers) over K = 250 = 125 MFMA k-steps.  Tile (a, b) holds the canonical
+//     columns act_col(128w, a, i) and the envs m = TM*j + b (i, j = a lane's MFMA row / column index), so what a lane needs per
+//     k-step is contiguous in LDS: one ds_read2_b64 of weights, one vector read of activations, requested two k-steps ahead.
+//   * W2: a wave only ever multiplies ITS 128 columns, so it streams only those -- chunks of 16 k-rows x 512 B, 8 LDS-DMA pieces
+//     (global_load_lds_dwordx4) of two row segments each -- through a PRIVATE ring of RD chunks, and waits for nobody but itself:
+//     LDS-DMA completes in issue order, so a counted s_waitcnt vmcnt before the first operand read of the next chunk leaves the
+//     pieces of younger chunks in flight.  No workgroup barrier in the loop.  RD = 2, or 3 where the LDS allows (TM = 1).
+//     N is padded 500 -> 512 (zero bias / W3 rows), the last chunk runs only its 5 real k-steps.
+//   * layer 1: relu(W1 x + b1) is RESIDENT in LDS, laid down on the matrix pipe before the loop (K = 9 inputs + a bias row = 10
+//     = 5 MFMA k-steps per 32x32 tile; inline-asm chains so that the accumulator stays in VGPRs, the VALU stays out of it).
+//     TM <= 2: all 256 (padded) rows.  TM = 4: 256 rows x 128 envs would be 128 KB, so one half at a time -- rows 128..255 are laid
+//     over rows 0..127 between chunk 7 and chunk 8, the only two workgroup barriers of the layer.
+//   * env-tail inputs ahead of time (TailPre): what the tail reads from global memory -- idx, step, config index, the next table
+//     row -- is fetched, and its noise drawn, under stage 0 / layer 1 (TM <= 2: own LDS blocks) or under the mid-layer phase
+//     (TM = 4: over the then dead layer-1 operand image), so the tail does not start with a chain of three dependent global reads.
 //   * epilogue: bias + relu on the accumulators, layer 3 (500 -> 2) as per-lane partial dot products
-//     reduced across lane halves (DPP) and the 4 waves (LDS), + b3, tanh, noise, clamp.
+//     reduced across lane halves and the 4 waves (LDS, over the dead ring), + b3, tanh, noise, clamp.
 //   * one thread per env then runs scale_action + step! (shems_core.h, exact reference arithmetic)
 //     and pushes the transition into the HBM replay ring.
-// LDS: 2 x 32 KB (W2 chunks) + 2 x 32*BM*4 (layer-1 groups) + x (10*BM*4) + layer-1 image 10 KB + b2/W3/b3 6 KB.
+// LDS (act_lds_bytes): 4 rings x RD x 8 KB + relu(layer 1) HR x BM x 4 (HR = 256 rows, 128 at TM = 4) + x 10 x BM x 4 + layer-1 image
+// 10 KB + b2/W3/b3 6 KB + raw obs BM x 36 + TailPre BM x 64 (TM <= 2) = 157 264 / 156 496 / 119 248 B at <4,4,2> / <2,4,2> / <1,4,2>,
+// 152 016 B at <1,4,3>: one workgroup per CU (160 KB).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -76,18 +80,13 @@ template <> __device__ __forceinline__ FVec<4>::type act_load_a<4>(const float *
     const f32x2 x = *reinterpret_cast<const f32x2 *>(p + 2 * li), y = *reinterpret_cast<const f32x2 *>(p + 64 + 2 * li);
     return FVec<4>::type{x[0], x[1], y[0], y[1]};
 }
-template <> __device__ __forceinline__ FVec<2>::type act_load_a<2>(const float *p, int li)
-{
-    return *reinterpret_cast<const f32x2 *>(p + 2 * li);
-}
 constexpr int kKC = 16;                         // k-rows per staged W2 chunk (8 MFMA k-steps)
 constexpr int kChunks = 16;                     // K = 250 padded to 256: the padded rows of layer 1 are exactly 0
-constexpr int kWcFloats = 8192 + 16;             // 32 whole 1-KiB LDS-DMA pieces (16 rows = 8000 floats, + 192 of the next row) + read pad
 constexpr int kW1K = 10, kW1C = 256;            // layer-1 operand image: rows 0..8 W1[j][k], row 9 b1[k] (K = 9 inputs + bias = 5 MFMA k-steps)
 constexpr int kOffB1 = kIn * kH1, kOffW2 = kOffB1 + kH1, kOffB2 = kOffW2 + kH1 * kH2, kOffW3 = kOffB2 + kH2,
               kOffB3 = kOffW3 + kH2 * kOut;
 static_assert(kOffB3 + kOut == SHEMS_ACTOR_PARAMS, "actor layout");
-static_assert(kW1K == 10 && kIn == 9, "L1_GROUP's MFMA chain is written out for 5 k-steps: 9 inputs + the bias row");
+static_assert(kW1K == 10 && kIn == 9, "L1_TILE's MFMA chain is written out for 5 k-steps: 9 inputs + the bias row");
 constexpr int kH2P = 512;                       // n padded to 16 MFMA tiles; pad rows carry zero bias / W3
 constexpr int kTailFloats = kH2P + kH2P * kOut + kOut;   // LDS image: b2[512], W3[512][2], b3[2]
 
@@ -112,7 +111,7 @@ struct ActArgs {
     int64_t gstride;
     int64_t genvs;
     // learner groups on the tiled working layout (shems_group_w2t): learner 0's actor region; W2 is read from its p arrays instead of
-    // from the Flux-order block (the free-running forms of k_act only).  null: Flux order.
+    // from the Flux-order block (k_act only).  null: Flux order.
     const float *w2t;
     int tm_max;                // learner groups: largest env tile (in units of 32 envs) that divides envs_per_learner -- a tile never straddles two learners; 0 = no limit
 };
@@ -126,50 +125,19 @@ __device__ __forceinline__ T *gsh(T *p, int64_t off)
     return p ? reinterpret_cast<T *>(reinterpret_cast<B *>(p) + off) : p;
 }
 
-// RD = 0: the workgroup streams W2 as whole 16-row chunks through a shared double buffer and layer 1 is produced 32 rows at a time
-// inside the loop.  RD >= 2 ("free-running waves", small tiles): each wave streams only ITS 128 columns of W2 through a private ring
-// of RD chunks (16 rows x 512 B) and all of relu(layer 1) is laid down before the loop, so the loop has no workgroup barrier.
+// k_act ("free-running waves"): each wave streams only ITS 128 columns of W2 through a private ring of RD >= 2 chunks (16 rows x 512 B)
+// and relu(layer 1) is laid down before the loop, so the loop has no workgroup barrier.
 constexpr int kFreeChunkFloats = kKC * 128;      // one wave's chunk: 16 rows x 128 columns
-constexpr int kPreDw = 16;                       // TailPre block per env (free-running form)
-// Rows of relu(layer 1) resident in LDS: the shared-stream form keeps two 32-row groups; the free-running form all 256 rows for
-// TM <= 2 and, for TM = 4 (128 envs per workgroup: 256 rows would be 128 KB), one half at a time -- the second half is laid down
-// between chunk 7 and chunk 8, the only two workgroup barriers of the layer.
-constexpr int act_h_rows(int tm, int rd) { return rd == 0 ? 64 : tm == 4 ? 128 : 256; }
-constexpr bool act_tail_pre(int tm, int rd) { return rd != 0 && tm <= 2; }    // TailPre blocks: the small tiles only (LDS)
-template <int TM, int NW, int RD = 0>
+constexpr int kPreDw = 16;                       // TailPre block per env
+// Rows of relu(layer 1) resident in LDS: all 256 rows for TM <= 2 and, for TM = 4 (128 envs per workgroup: 256 rows would be 128 KB),
+// one half at a time -- the second half is laid down between chunk 7 and chunk 8, the only two workgroup barriers of the layer.
+constexpr int act_h_rows(int tm) { return tm == 4 ? 128 : 256; }
+constexpr bool act_tail_pre(int tm) { return tm <= 2; }    // TailPre blocks: the small tiles only (LDS)
+template <int TM, int NW, int RD>
 constexpr size_t act_lds_bytes()
 {
-    return sizeof(float) * ((RD ? NW * RD * kFreeChunkFloats + 16 : 2 * kWcFloats) + act_h_rows(TM, RD) * 32 * TM + kW1K * 32 * TM + kW1K * kW1C +
-                            (kTailFloats + 2) + 32 * TM * kIn + (act_tail_pre(TM, RD) ? 32 * TM * kPreDw : 0));
-}
-
-__device__ __forceinline__ void glds16(const void *g, void *lds)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-
-// Piece q (0..7) of a wave's 8-KiB LDS-DMA stream.  The instruction's immediate offset is added to the global address AND to
-// the LDS address (M0 base + offset + lane * 16), so both bases point at piece 4 and the piece is chosen by (q - 4) KiB alone:
-// one 64-bit address and one M0 value per chunk.  The builtin wants an integer constant expression, hence the switch.
-template <int Q>
-__device__ __forceinline__ void glds16_imm(const char *base, char *lds)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)base,
-                                     (__attribute__((address_space(3))) void *)lds, 16, (Q - 4) * 1024, 0);
-}
-__device__ __forceinline__ void glds16_piece(const char *base, char *lds, int q)
-{
-    switch (q) {
-    case 0: glds16_imm<0>(base, lds); break;
-    case 1: glds16_imm<1>(base, lds); break;
-    case 2: glds16_imm<2>(base, lds); break;
-    case 3: glds16_imm<3>(base, lds); break;
-    case 4: glds16_imm<4>(base, lds); break;
-    case 5: glds16_imm<5>(base, lds); break;
-    case 6: glds16_imm<6>(base, lds); break;
-    default: glds16_imm<7>(base, lds); break;
-    }
+    return sizeof(float) * ((NW * RD * kFreeChunkFloats + 16) + act_h_rows(TM) * 32 * TM + kW1K * 32 * TM + kW1K * kW1C +
+                            (kTailFloats + 2) + 32 * TM * kIn + (act_tail_pre(TM) ? 32 * TM * kPreDw : 0));
 }
 
 // LDS-DMA as an asm statement (k_actg).  Given the builtin, the compiler books a global_load_lds as a FLAT access that may touch LDS
@@ -189,7 +157,7 @@ __device__ __forceinline__ void glds16_asm(const char *sbase, uint32_t voff, uin
                  :: "v"(voff), "s"(sbase), "s"(lds_base), "i"(IMM) : "memory");
 }
 
-// Piece q (0..7) of a wave's 8-KiB stream (k_act's free-running forms), immediate (q - 4) KiB on both addresses.
+// Piece q (0..7) of a wave's 8-KiB stream (k_act), immediate (q - 4) KiB on both addresses.
 __device__ __forceinline__ void glds16_asm_piece8(const char *sbase, uint32_t voff, uint32_t lds_base, int q)
 {
     switch (q) {
@@ -371,28 +339,9 @@ __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, floa
     return reward;
 }
 
-// Scheduling pipeline of one chunk (one basic block): [DS reads of k-step 0], then per k-step
-// [2*TM MFMAs] [DS reads of the NEXT k-step] [2*TM MFMAs] [one LDS-DMA piece]: the operand fetch sits in the middle of an
-// MFMA group, half a group (~500 cycles) ahead of its first use.  ds_read2_b32 fetches two operands, so a k-step is
-// 2 + ceil(TM/2) DS instructions.
-constexpr int kDmaKs = 4;   // 4 waves: the 8 LDS-DMA pieces a wave issues per chunk go out in k-steps 0..3 (two each), so the
-                            // last one has half a chunk (~4000 cycles) to land before the barrier that publishes it
-template <int TM, int NA, bool DMA, int NKS>
-__device__ __forceinline__ void sched_chunk()
-{
-    constexpr int DS = 2;                       // one vector read per operand
-    __builtin_amdgcn_sched_group_barrier(0x100, DS, 0);
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        __builtin_amdgcn_sched_group_barrier(0x008, NA * TM / 2, 0);
-        if (ks + 1 < NKS) __builtin_amdgcn_sched_group_barrier(0x100, DS, 0);
-        if (DMA && NA == 4 && ks < kDmaKs) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, NA * TM - NA * TM / 2, 0);
-        if (DMA && ((NA == 4 && ks < kDmaKs) || (NA != 4 && (ks & 1) == 0))) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-    }
-}
-
-// Free-running form: after chunk c the wave needs its chunk c + 1; the LDS-DMA pieces of chunks c + 2 .. c + RD - 1 (8 each, 5 for
+constexpr int kDmaKs = 4;   // the 8 LDS-DMA pieces a wave issues per chunk go out in k-steps 0..3 (two each); the wave waits for
+                            // them before k-step 6 of the chunk RD - 2 chunks later (ring of 2: the same chunk, two k-steps on)
+// After chunk c the wave needs its chunk c + 1; the LDS-DMA pieces of chunks c + 2 .. c + RD - 1 (8 each, 5 for
 // the short chunk 15) are younger and may stay in flight.
 template <int RD>
 constexpr int free_keep(int c)
@@ -407,26 +356,25 @@ constexpr int free_keep(int c)
 template <int TM, int NW, int RD, bool HP>
 __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_hparams *hp)
 {
-    static_assert(RD == 0 || (NW == 4 && RD >= 2 && RD <= 4), "free-running form: 4 waves, ring of 2..4 chunks");
+    static_assert(NW == 4 && RD >= 2 && RD <= 4, "free-running form: 4 waves, ring of 2..4 chunks");
     constexpr int NT_ = 64 * NW;            // threads per workgroup
-    constexpr int NA = 16 / NW;             // 32-wide n-tiles per wave (4 waves: 4, 8 waves: 2)
+    constexpr int NA = 16 / NW;             // 32-wide n-tiles per wave: 4
     PSTAMP(0);
     constexpr int BM = 32 * TM;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *Wc = reinterpret_cast<float *>(smem);             // RD = 0: [2][kWcFloats] W2 chunks (16 rows x 500); else [NW][RD][16][128]
-    constexpr int HR = act_h_rows(TM, RD);                   // rows of relu(layer 1) resident at a time
-    constexpr bool PRE = act_tail_pre(TM, RD);               // env-tail inputs fetched in stage 0
-    constexpr bool PRE2 = RD != 0 && TM == 4;                // 128-env tiles: indices in stage 0, rows + noise while the second half of h1
+    float *Wc = reinterpret_cast<float *>(smem);             // [NW][RD][16][128] W2: a ring of RD chunks per wave
+    constexpr int HR = act_h_rows(TM);                       // rows of relu(layer 1) resident at a time
+    constexpr bool PRE = act_tail_pre(TM);                   // env-tail inputs fetched in stage 0
+    constexpr bool PRE2 = TM == 4;                           // 128-env tiles: indices in stage 0, rows + noise while the second half of h1
                                                              // is laid down, TailPre blocks over the then dead layer-1 operand image
-    float *Hc = Wc + (RD ? NW * RD * kFreeChunkFloats + 16 : 2 * kWcFloats);   // [HR][BM] relu(layer 1)
+    float *Hc = Wc + NW * RD * kFreeChunkFloats + 16;        // [HR][BM] relu(layer 1)
     float *xT = Hc + HR * BM;                                // [10][BM]  normalised obs (rows 0..8), row 9 = 1 (bias)
     float *w1 = xT + kW1K * BM;                              // [10][256] layer-1 operand image
     float *tl = w1 + kW1K * kW1C;                            // b2 [512], W3 [512][2], b3 [2]
     // Layer-3 group sums [8 column groups][BM][2]: kept over the W2 stream, which is dead by then -- a wave's groups at the start of
-    // ITS OWN ring (free-running form: nobody else touches it) / of its slice of the shared double buffer (dead for everybody after the
-    // last chunk's barrier).  red_of(g) = where the owner of group g put it.
-    constexpr int kRedStride = RD ? RD * kFreeChunkFloats : (16 / NW / 2) * BM * kOut;
-    static_assert((16 / NW / 2) * BM * kOut <= (RD ? RD * kFreeChunkFloats : 2 * kWcFloats / NW), "group sums fit the dead W2 buffer");
+    // ITS OWN ring (nobody else touches it).  RED_OF(g) = where the owner of group g put it.
+    constexpr int kRedStride = RD * kFreeChunkFloats;
+    static_assert((NA / 2) * BM * kOut <= RD * kFreeChunkFloats, "group sums fit the wave's dead W2 ring");
 #define RED_OF(g) (Wc + ((g) / (NA / 2)) * kRedStride + ((g) % (NA / 2)) * (BM * kOut))
     float *xR = tl + (kTailFloats + 2);                        // [BM][9]   the raw observations stage 0 loaded: step! starts from these, not from a
                                                              //           second (stride-36-byte) read of global memory at the end of the kernel
@@ -446,24 +394,10 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
     const float *__restrict__ P = gsh(A.p.actor, goff);
     const float *__restrict__ s_min = gsh(A.p.s_min, goff), *__restrict__ s_max = gsh(A.p.s_max, goff);
 
-    // ---- stage 0: x = normalize(s) -> xT[k][m]; layer-1 image, b2/W3/b3 -> LDS; W2 chunk 0 -> LDS --------------
-    // W2 chunk staging, global -> LDS directly (global_load_lds_dwordx4: no staging registers).  A chunk is 16 rows =
-    // 32000 contiguous bytes = 31 full 1-KiB wave pieces + one of 256 B (16 lanes); wave w issues pieces w, w+4, ...
-    // The LDS image is the linear copy (destination = M0 base + lane*16).  The last chunk holds only rows 240..249
-    // (20000 B): its rows 10..15 receive clamped-source filler that is never read (the last chunk runs 5 k-steps).
+    // ---- stage 0: x = normalize(s) -> xT[k][m]; layer-1 image, b2/W3/b3 -> LDS (the ring's first RD - 1 chunks follow the first barrier) ----
+    // W2 chunk staging, global -> LDS directly (global_load_lds_dwordx4: no staging registers; destination = M0 base + lane*16).
     const char *W2g = reinterpret_cast<const char *>(P + kOffW2);
-    constexpr int kChunkBytes = kKC * kH2 * 4;
-    constexpr int kTotalBytes = kH1 * kH2 * 4;
-#define W2_PIECE(chunk, buf, pc)                                                                  \
-    do {                                                                                          \
-        const int off_ = (pc) * 1024 + lane * 16;                                                 \
-        if (off_ < kChunkBytes && (chunk) * kChunkBytes + off_ < kTotalBytes)                     \
-            glds16(W2g + (chunk) * kChunkBytes + off_,                                            \
-                   reinterpret_cast<char *>(Wc + (buf) * kWcFloats) + (pc) * 1024);               \
-    } while (0)
-#define W2_ISSUE(chunk, buf)                                                                      \
-    do { _Pragma("unroll") for (int pc_ = wave; pc_ < 32; pc_ += NW) W2_PIECE(chunk, buf, pc_); } while (0)
-    // Free-running form: wave w moves rows [16 c, +16) x columns [128 w, +128) of W2 -- piece q = rows 2q, 2q + 1 (lanes 0..31 /
+    // Wave w moves rows [16 c, +16) x columns [128 w, +128) of W2 -- piece q = rows 2q, 2q + 1 (lanes 0..31 /
     // 32..63), 512 B each -- into its own ring.  Columns 500..511 of wave 3 run into the next row (the last row: into b2); those
     // accumulator columns meet zero W3 rows.  Rows >= 250 (pieces 5..7 of chunk 15) are never read and never fetched.
     float *Wf = Wc + wave * (RD * kFreeChunkFloats);
@@ -488,18 +422,15 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
 #define FREE_CHUNK_OFF(chunk) (tiled ? (size_t)((chunk) >> 2) * (8 * kTlTile) + (size_t)((chunk) & 3) * (kKC * 256) : (size_t)(chunk) * (kKC * kH2 * 4))
 #define FREE_PIECE(chunk, q)                                                                      \
     glds16_asm_piece8(wsbase + FREE_CHUNK_OFF(chunk), wvoff[q],                                   \
-                      wf_lds + ((chunk) % (RD ? RD : 1)) * (kFreeChunkFloats * 4), (q))
+                      wf_lds + ((chunk) % RD) * (kFreeChunkFloats * 4), (q))
 #define STAGE0_DMA()                                                                              \
     do {                                                                                          \
-        if constexpr (RD == 0) W2_ISSUE(0, 0);                                                    \
-        else {                                                                                    \
-            _Pragma("unroll") for (int ch_ = 0; ch_ < RD - 1; ++ch_)                              \
-                _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) FREE_PIECE(ch_, q_);             \
-        }                                                                                         \
+        _Pragma("unroll") for (int ch_ = 0; ch_ < RD - 1; ++ch_)                                  \
+            _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) FREE_PIECE(ch_, q_);                 \
     } while (0)
-    // Every global load of the stage is issued before the first value is used (obs + normalisation, layer-1 image, b2|W3|b3;
-    // the first W2 chunk goes out by LDS-DMA right behind them): one exposed latency instead of one per block.  Addresses are
-    // clamped, never predicated -- a guarded load becomes a branch with its own s_waitcnt and serialises the batch.
+    // Every global load of the stage is issued before the first value is used (obs + normalisation, layer-1 image, b2|W3|b3):
+    // one exposed latency instead of one per block.  Addresses are clamped, never predicated -- a guarded load becomes a branch with
+    // its own s_waitcnt and serialises the batch.
     constexpr int kIt = (BM * kIn + NT_ - 1) / NT_;
     float sv[kIt], lo[kIt], hi[kIt], wv[kW1K], tv[6];
     const int64_t last = A.m * kIn - 1;
@@ -534,7 +465,6 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
         tp.step = pstep[view ? pe : 0];
         tp.ci = view && A.v.n_cfg > 1 ? (int)pci[pe] : 0;
     }
-    if constexpr (RD == 0) STAGE0_DMA();
     if constexpr (PRE) tp.nz = noise_draw(A.p, env0 + (tid & (BM - 1)));
 #pragma unroll
     for (int it = 0; it < kIt; ++it) {
@@ -558,10 +488,9 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
         if (tid < kH2P - kH2) tl[kH2 + tid] = 0.0f;                                   // pad rows of b2
         if (tid < (kH2P - kH2) * kOut) tl[kH2P + kH2 * kOut + tid] = 0.0f;            // pad rows of W3
     }
-    if (RD == 0 && tid < 16) { Wc[kKC * kH2 + tid] = 0.0f; Wc[kWcFloats + kKC * kH2 + tid] = 0.0f; }
 
-    // Layer 1 on the matrix pipe (K = 10 = 5 k-steps): rows [32g, 32g+32) x this workgroup's BM columns into Hc[g & 1];
-    // wave w owns column tile w (TM <= 4 tiles).  D layout: row (r&3)+8(r>>2)+4*lh, column lane&31.
+    // Layer 1 on the matrix pipe (K = 10 = 5 k-steps): rows [32g, 32g+32) x this workgroup's BM columns into rows (32g) % HR.. of Hc,
+    // tile by tile (L1_PHASE below shares them out over the waves).  D layout: row (r&3)+8(r>>2)+4*lh, column lane&31.
 /* A operand of k-step s_ (input row j_ = 2 s_ + lh) of row group g: from the LDS image w1 here; k_actg redefines it (registers). */
 #define L1_A(s_, j_, g, which) w1[(j_) * kW1C + 32 * (g) + li]
 #define L1_TILE(g, b, dst)                                                                        \
@@ -626,8 +555,6 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
                 d1_[((r_ & 3) + 8 * (r_ >> 2) + 4 * lh) * BM] = fmaxf(t1_[r_], 0.0f);             \
             }                                                                                     \
     } while (0)
-#define L1_GROUP(g)                                                                               \
-    do { if (wave < TM) L1_TILE(g, wave, Hc + ((g) & 1) * (32 * BM) + TM * li + wave); } while (0)
 
     if constexpr (PRE || PRE2) {
         const bool view = A.do_step != 0;
@@ -644,7 +571,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
     // The ring's first chunks go out only now: issued with stage 0's loads, 256 workgroups x 64 KB of pieces queue in front of the
     // few KB every workgroup is actually waiting for (measured: -0.6 % at 65 536 envs, -1.7 % at 8 192).
     // (small tiles: behind the TailPre row loads below, so that waiting for those does not mean waiting for the pieces)
-    if constexpr (RD != 0 && !PRE) STAGE0_DMA();
+    if constexpr (!PRE) STAGE0_DMA();
     PSTAMP(1);
     /* TM = 4: one wave lays down a whole 32-row group for all four column tiles.  A lane's four env columns m = 4 j + b are adjacent: */
     /* the B operands come as one b128 read per k-step and the result leaves as one b128 store per row (the per-tile form's b32      */
@@ -693,7 +620,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
                 *reinterpret_cast<f32x4 *>(d_ + ((r_ & 3) + 8 * (r_ >> 2) + 4 * lh) * BM) =       \
                     f32x4{fmaxf(t0_[r_], 0.0f), fmaxf(t1_[r_], 0.0f), fmaxf(t2_[r_], 0.0f), fmaxf(t3_[r_], 0.0f)}; \
     } while (0)
-    // One phase of relu(layer 1) in the free-running form: row groups gbase .. gbase + HR / 32 - 1, TM column tiles each, over the four
+    // One phase of relu(layer 1): row groups gbase .. gbase + HR / 32 - 1, TM column tiles each, over the four
     // waves in interleaved pairs
 #define L1_PHASE(gbase)                                                                           \
     do {                                                                                          \
@@ -706,8 +633,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
             L1_TILE2(g0, b0, Hc + ((g0 * 32) % HR) * BM + TM * li + b0, g1, b1, Hc + ((g1 * 32) % HR) * BM + TM * li + b1); \
         }                                                                                         \
     } while (0)
-    if constexpr (RD == 0) L1_GROUP(0);
-    else if constexpr (PRE) {
+    if constexpr (PRE) {
         const f32x4 *rp = reinterpret_cast<const f32x4 *>(tp_tables + tp_row * SHEMS_NCOL);
         const f32x4 ra = rp[0], rb = rp[1];                                    // row idx + 1
         tp.h_cur = tp_tables[(tp_row - 1) * SHEMS_NCOL];                       // h_countdown of row idx
@@ -716,8 +642,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
         tp.nx = Row{ra[0], ra[1], ra[2], ra[3], rb[0], rb[1], rb[2], rb[3]};
         tailpre_store(xP + (tid & (BM - 1)) * kPreDw, tp);
     } else L1_PHASE(0);
-    if constexpr (RD == 0) __syncthreads();                                   // + chunk 0 of the shared stream
-    else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // h1 only: every wave waits for its own ring below
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // h1 only: every wave waits for its own ring below
     PSTAMP(2);
 
     // ---- layer 2: 128 k-steps of 4 x TM MFMA tiles per wave ----------------------------------------------------
@@ -729,7 +654,6 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
     typedef typename FVec<NA>::type AVec;
     typedef typename FVec<TM>::type BVec;
     const int nbase = wave * (32 * NA);
-    const char *wbase_ = W2g + kChunkBytes + (8 * wave + 4) * 1024 + lane * 16;      // piece 8w+4 of chunk 1: the base of this wave's LDS-DMA stream
     // the accumulators start at b2[n] (rows >= 500: 0), so the epilogue is relu + two FMAs per element
 #pragma unroll
     for (int a = 0; a < NA; ++a)
@@ -740,52 +664,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
             for (int b = 0; b < TM; ++b) acc[a][b][r] = bias;
         }
 
-    // One chunk = 8 k-steps x (4 x TM) MFMAs.  The operands of k-step ks+1 are fetched from LDS before the MFMAs of
-    // k-step ks issue (register double buffer; sched_group_barrier pins that order -- left alone the compiler sinks each
-    // ds_read to just before its first use and the wave, alone on its SIMD, eats the LDS latency 16 times per chunk).
-    // ISSUE: 0 = the next chunk is a whole 32-piece chunk (branch-free LDS-DMA, one piece per k-step), 1 = the next chunk is
-    // the last one (rows 240..249 only: source addresses clamped to the end of W2, still branch-free), 2 = nothing to fetch.  ODD: this chunk also produces the next layer-1 group.
-#define CHUNK_BODY(c, ISSUE, ODD, NKS)                                                                             \
-    do {                                                                                                        \
-        const int cur_ = (c) & 1, nxt_ = cur_ ^ 1;                                                              \
-        if (ODD) L1_GROUP(((c) + 1) >> 1);                                                                      \
-        const float *Wb_ = Wc + cur_ * kWcFloats + nbase;                                                       \
-        const float *Hb_ = Hc + (((c) >> 1) & 1) * (32 * BM) + ((c) & 1) * (kKC * BM) + TM * li;                \
-        AVec af_[2];                                                                                            \
-        BVec bf_[2];                                                                                            \
-        af_[0] = act_load_a<NA>(Wb_ + lh * kH2, li);                                                            \
-        bf_[0] = *reinterpret_cast<const BVec *>(Hb_ + lh * BM);                                                \
-        _Pragma("unroll") for (int ks = 0; ks < (NKS); ++ks) {                                                  \
-            if (ks + 1 < (NKS)) {                                                                               \
-                const int kr_ = 2 * (ks + 1) + lh;                                                              \
-                af_[(ks + 1) & 1] = act_load_a<NA>(Wb_ + kr_ * kH2, li);                                        \
-                bf_[(ks + 1) & 1] = *reinterpret_cast<const BVec *>(Hb_ + kr_ * BM);                            \
-            }                                                                                                   \
-            _Pragma("unroll") for (int a = 0; a < NA; ++a)                                                      \
-                _Pragma("unroll") for (int b = 0; b < TM; ++b)                                                  \
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fvec_get<NA>(af_[ks & 1], a), fvec_get<TM>(bf_[ks & 1], b), acc[a][b], 0, 0, 0); \
-            _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) {                                                  \
-                if (NA == 4 ? ks < kDmaKs : ((ks & 1) == 0 && h_ == 0)) {                                       \
-                    const int pc_ = NA == 4 ? wave + 4 * (2 * ks + h_) : wave + 8 * (ks >> 1);                  \
-                    if (ISSUE == 0 && NA == 4) {                                                                \
-                        /* wave w moves the 8 consecutive pieces 8w..8w+7: one 64-bit address per chunk, the */   \
-                        /* piece selected by the instruction's immediate offset (-4096 .. 3072, both sides)  */   \
-                        glds16_piece(wbase_ + (size_t)(c) * kChunkBytes,                                        \
-                                     reinterpret_cast<char *>(Wc + nxt_ * kWcFloats) + (8 * wave + 4) * 1024, 2 * ks + h_); \
-                    } else if (ISSUE == 0)                                                                      \
-                        glds16(W2g + ((c) + 1) * kChunkBytes + pc_ * 1024 + lane * 16,                          \
-                               reinterpret_cast<char *>(Wc + nxt_ * kWcFloats) + pc_ * 1024);                   \
-                    else if (ISSUE == 1)                 /* short last chunk: source clamped to the end of W2 */ \
-                        glds16(W2g + min(((c) + 1) * kChunkBytes + pc_ * 1024 + lane * 16, kTotalBytes - 16),   \
-                               reinterpret_cast<char *>(Wc + nxt_ * kWcFloats) + pc_ * 1024);                   \
-                }                                                                                               \
-            }                                                                                                   \
-        }                                                                                                       \
-        sched_chunk<TM, NA, ISSUE != 2, NKS>();                                                   \
-        __syncthreads();                                                                                        \
-    } while (0)
-
-    // Free-running form: chunk c of a wave = 8 k-steps on its own ring buffer c % RD and rows [16 c, +16) of the resident h1; the
+    // Chunk c of a wave = 8 k-steps on its own ring buffer c % RD and rows [16 c, +16) of the resident h1; the
     // pieces of chunk c + RD - 1 go out during k-steps 0..3 into the buffer chunk c - 1 was read from; at the end the wave waits for
     // ITS OWN chunk c + 1 (vmcnt counts LDS-DMA in issue order: the pieces of younger chunks may stay in flight).  No barrier.
 #define FREE_NPIECES(ch) ((ch) > kChunks - 1 ? 0 : (ch) == kChunks - 1 ? (kH1 - (kChunks - 1) * kKC) / 2 : 8)
@@ -837,63 +716,51 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
         _Pragma("unroll") for (int ks = 6; ks < (NKS); ++ks) FREE_KSTEP(c, ks);                                 \
     } while (0)
 
-    if constexpr (RD == 0) {
-#pragma unroll 1
-    for (int cp = 0; cp < (kChunks - 2) / 2; ++cp) {     // chunks 0..13: the next chunk (1..14) is whole
-        CHUNK_BODY(2 * cp, 0, false, kKC / 2);
-        CHUNK_BODY(2 * cp + 1, 0, true, kKC / 2);
+    {
+        constexpr int keep0_ = free_keep<RD>(-1);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(keep0_) : "memory");        // this wave's chunk 0 has landed
+        __builtin_amdgcn_sched_barrier(0);
     }
-    PSTAMP(3);
-    CHUNK_BODY(kChunks - 2, 1, false, kKC / 2);           // chunk 14 fetches the short last chunk
-    PSTAMP(4);
-    CHUNK_BODY(kChunks - 1, 2, false, (kH1 - (kChunks - 1) * kKC) / 2);   // chunk 15: rows 240..249 only = 5 k-steps
-    } else {
-        {
-            constexpr int keep0_ = free_keep<RD>(-1);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(keep0_) : "memory");        // this wave's chunk 0 has landed
-            __builtin_amdgcn_sched_barrier(0);
+    constexpr int kFreeKsteps = (kChunks - 1) * (kKC / 2) + (kH1 - (kChunks - 1) * kKC) / 2;      // 125 k-steps of two rows
+    AVec af_[3];                                                             // operand ring of three k-steps, carried from chunk to chunk
+    BVec bf_[3];
+#pragma unroll
+    for (int k0 = 0; k0 < 2; ++k0) {
+        af_[k0] = act_load_a<NA>(Wf + (2 * k0 + lh) * 128, li);
+        bf_[k0] = *reinterpret_cast<const BVec *>(Hc + TM * li + (2 * k0 + lh) * BM);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    FREE_CHUNK(0, kKC / 2);  PSTAMP(3); FREE_CHUNK(1, kKC / 2);  FREE_CHUNK(2, kKC / 2);  FREE_CHUNK(3, kKC / 2);
+    FREE_CHUNK(4, kKC / 2);  FREE_CHUNK(5, kKC / 2);  FREE_CHUNK(6, kKC / 2);  FREE_CHUNK(7, kKC / 2);
+    if constexpr (HR < 256) {
+        // every wave has read the first half of h1 to the end (its last requests were waited for): lay down rows 128..255 over it
+        // and restart the operand ring at k-step 64.  The W2 pieces in flight keep flying.
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        [[maybe_unused]] f32x4 ra, rb;
+        if constexpr (PRE2) {
+            const f32x4 *rp = reinterpret_cast<const f32x4 *>(tp_tables + tp_row * SHEMS_NCOL);
+            ra = rp[0]; rb = rp[1];                                                // row idx + 1
+            tp.h_cur = tp_tables[(tp_row - 1) * SHEMS_NCOL];                       // h_countdown of row idx
         }
-        constexpr int kFreeKsteps = (kChunks - 1) * (kKC / 2) + (kH1 - (kChunks - 1) * kKC) / 2;      // 125 k-steps of two rows
-        AVec af_[3];                                                             // operand ring of three k-steps, carried from chunk to chunk
-        BVec bf_[3];
+        L1_PHASE(HR / 32);
+        if constexpr (PRE2) tp.nz = noise_draw(A.p, env0 + (tid & (BM - 1)));
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if constexpr (PRE2) {                                                      // w1 / xT are dead from here on
+            tp.nx = Row{ra[0], ra[1], ra[2], ra[3], rb[0], rb[1], rb[2], rb[3]};
+            tailpre_store(w1 + (tid & (BM - 1)) * kPreDw, tp);
+        }
 #pragma unroll
         for (int k0 = 0; k0 < 2; ++k0) {
-            af_[k0] = act_load_a<NA>(Wf + (2 * k0 + lh) * 128, li);
-            bf_[k0] = *reinterpret_cast<const BVec *>(Hc + TM * li + (2 * k0 + lh) * BM);
+            constexpr int Kp = (kChunks / 2) * (kKC / 2);
+            af_[(Kp + k0) % 3] = act_load_a<NA>(Wf + ((kChunks / 2) % RD) * kFreeChunkFloats + (2 * k0 + lh) * 128, li);
+            bf_[(Kp + k0) % 3] = *reinterpret_cast<const BVec *>(Hc + TM * li + (2 * k0 + lh) * BM);
         }
         __builtin_amdgcn_sched_barrier(0);
-        FREE_CHUNK(0, kKC / 2);  PSTAMP(3); FREE_CHUNK(1, kKC / 2);  FREE_CHUNK(2, kKC / 2);  FREE_CHUNK(3, kKC / 2);
-        FREE_CHUNK(4, kKC / 2);  FREE_CHUNK(5, kKC / 2);  FREE_CHUNK(6, kKC / 2);  FREE_CHUNK(7, kKC / 2);
-        if constexpr (HR < 256) {
-            // every wave has read the first half of h1 to the end (its last requests were waited for): lay down rows 128..255 over it
-            // and restart the operand ring at k-step 64.  The W2 pieces in flight keep flying.
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            [[maybe_unused]] f32x4 ra, rb;
-            if constexpr (PRE2) {
-                const f32x4 *rp = reinterpret_cast<const f32x4 *>(tp_tables + tp_row * SHEMS_NCOL);
-                ra = rp[0]; rb = rp[1];                                                // row idx + 1
-                tp.h_cur = tp_tables[(tp_row - 1) * SHEMS_NCOL];                       // h_countdown of row idx
-            }
-            L1_PHASE(HR / 32);
-            if constexpr (PRE2) tp.nz = noise_draw(A.p, env0 + (tid & (BM - 1)));
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            if constexpr (PRE2) {                                                      // w1 / xT are dead from here on
-                tp.nx = Row{ra[0], ra[1], ra[2], ra[3], rb[0], rb[1], rb[2], rb[3]};
-                tailpre_store(w1 + (tid & (BM - 1)) * kPreDw, tp);
-            }
-#pragma unroll
-            for (int k0 = 0; k0 < 2; ++k0) {
-                constexpr int Kp = (kChunks / 2) * (kKC / 2);
-                af_[(Kp + k0) % 3] = act_load_a<NA>(Wf + ((kChunks / 2) % RD) * kFreeChunkFloats + (2 * k0 + lh) * 128, li);
-                bf_[(Kp + k0) % 3] = *reinterpret_cast<const BVec *>(Hc + TM * li + (2 * k0 + lh) * BM);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        FREE_CHUNK(8, kKC / 2);  FREE_CHUNK(9, kKC / 2);  FREE_CHUNK(10, kKC / 2); FREE_CHUNK(11, kKC / 2);
-        FREE_CHUNK(12, kKC / 2); FREE_CHUNK(13, kKC / 2); FREE_CHUNK(14, kKC / 2);
-        PSTAMP(4);
-        FREE_CHUNK(15, (kH1 - (kChunks - 1) * kKC) / 2);                       // rows 240..249 only = 5 k-steps
     }
+    FREE_CHUNK(8, kKC / 2);  FREE_CHUNK(9, kKC / 2);  FREE_CHUNK(10, kKC / 2); FREE_CHUNK(11, kKC / 2);
+    FREE_CHUNK(12, kKC / 2); FREE_CHUNK(13, kKC / 2); FREE_CHUNK(14, kKC / 2);
+    PSTAMP(4);
+    FREE_CHUNK(15, (kH1 - (kChunks - 1) * kKC) / 2);                       // rows 240..249 only = 5 k-steps
     PSTAMP(10);
 
     // ---- epilogue: relu(acc + b2), layer 3 in the canonical order: one FMA chain per tile, lane halves, tile pairs -> group sums ----
@@ -1663,7 +1530,7 @@ static int pick_tm(int64_t m, int tm_max = 0)
 // learner groups: envs_per_learner is a multiple of 32; tiles of 128 / 64 envs only where they divide it
 static int group_tm_max(int64_t envs_per_learner) { return envs_per_learner % 128 == 0 ? 4 : envs_per_learner % 64 == 0 ? 2 : 1; }
 
-template <int TM, int NW, int RD = 0>
+template <int TM, int NW, int RD>
 static int launch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
 {
     constexpr int BM = 32 * TM;
@@ -1740,30 +1607,38 @@ static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hpara
     return hip_ok(hipGetLastError(), "k_actg launch");
 }
 
-// Which form runs a launch of m envs (the knobs exist for the all-forms test and for A/B runs):
-//   m > 8 192            k_act2           64-env tiles, two workgroups resident per CU            (SHEMS_ACT_FORM4 = 1 / 0: k_act, below)
-//   4 096 < m <= 8 192   k_actg<1, 4, 2, 2>  32-env tiles, two workgroups per tile, ring of 2 chunks: both resident on one CU
-//                        (per-tile reward sums asked for, or SHEMS_ACT_FORM = 8: k_actg<1, 8, 1>, 8 waves = 8 column groups; 10: force the ring-2 split form;
-//                         SHEMS_ACT_FORM = 0 / 2 / 3: k_act<1, 4, .>)
-//   m <= 4 096           k_actg<1, 4, 2>  32-env tiles, two workgroups (4 groups each) per tile   (SHEMS_ACT_FORM = 8 / 9: force one of the two)
-// k_act (SHEMS_ACT_FORM4 = 1: free-running waves, 0: shared W2 stream): 128-env tiles from 32 768 envs, 64-env tiles from 16 384, 32 below.
+// Which form runs a launch of m envs.  SHEMS_ACT_FORM (read once per process) exists for the all-forms test and for A/B runs: every
+// form writes the same bytes.
+//   m > 8 192, one learner   k_act2              64-env tiles, two workgroups resident per CU
+//   4 096 < m <= 8 192       k_actg<1, 4, 2, 2>  32-env tiles, two workgroups per tile, ring of 2 chunks: both resident on one CU
+//   m <= 4 096               k_actg<1, 4, 2, 3>  32-env tiles, two workgroups (4 groups each) per tile, ring of 3 chunks
+//   per-tile reward sums asked for (32-env tiles), or more tiles than the split forms' scratch holds:
+//                            k_actg<1, 8, 1, 3>  one workgroup of 8 waves = 8 column groups per tile
+//   learner groups           k_act<4 | 2, 4, 2> where pick_tm gives 128- / 64-env tiles (from 32 768 / 16 384 envs, and only tiles that divide
+//                            a learner's env block), the k_actg rows above at 32-env tiles; on the tiled W2 layout always k_act<4 | 2 | 1, 4, 2>,
+//                            its only reader, whatever the knob says
+// SHEMS_ACT_FORM = anything: no k_act2 by default, so k_act<4 | 2, 4, 2> at 128- / 64-env tiles; at 32-env tiles
+//   2 / 3   k_act<1, 4, 2> / k_act<1, 4, 3>: the free-running form with a ring of 2 / 3 chunks
+//   8 / 9   k_actg<1, 8, 1, 3> / k_actg<1, 4, 2, 3>: force one of the two
+//   10      k_actg<1, 4, 2, 2>: the ring-2 split form at any size its scratch holds
+//   12      k_act2 at any size (a learner group: where 64-env tiles divide its env blocks)
+// and a value not listed selects nothing of its own: k_actg<1, 8, 1, 3> above 4 096 envs, k_actg<1, 4, 2, 3> up to there.
 static int act_form() { static const int f = []() { const char *e = getenv("SHEMS_ACT_FORM"); return e ? atoi(e) : -1; }(); return f; }
-static int act_form4() { static const int f = []() { const char *e = getenv("SHEMS_ACT_FORM4"); return e ? atoi(e) : 2; }(); return f; }
 // Every form a launch can run, and its profiler name.
-enum ActForm { kAct2, kAct440, kAct442, kAct240, kAct242, kAct140, kAct142, kAct143, kActg1422, kActg1423, kActg1813 };
+enum ActForm { kAct2, kAct442, kAct242, kAct142, kAct143, kActg1422, kActg1423, kActg1813 };
 static const char *act_form_name(ActForm f)
 {
-    static const char *const names[] = {"shems::k_act2", "shems::k_act<4, 4, 0>", "shems::k_act<4, 4, 2>", "shems::k_act<2, 4, 0>",
-                                        "shems::k_act<2, 4, 2>", "shems::k_act<1, 4, 0>", "shems::k_act<1, 4, 2>", "shems::k_act<1, 4, 3>",
-                                        "shems::k_actg<1, 4, 2, 2>", "shems::k_actg<1, 4, 2, 3>", "shems::k_actg<1, 8, 1, 3>"};
+    static const char *const names[] = {"shems::k_act2", "shems::k_act<4, 4, 2>", "shems::k_act<2, 4, 2>", "shems::k_act<1, 4, 2>",
+                                        "shems::k_act<1, 4, 3>", "shems::k_actg<1, 4, 2, 2>", "shems::k_actg<1, 4, 2, 3>",
+                                        "shems::k_actg<1, 8, 1, 3>"};
     return names[f];
 }
 static int act_form_tile_envs(ActForm f)
 {
     switch (f) {
     case kAct2: return 64;
-    case kAct440: case kAct442: return 128;
-    case kAct240: case kAct242: return 64;
+    case kAct442: return 128;
+    case kAct242: return 64;
     default: return 32;
     }
 }
@@ -1773,17 +1648,16 @@ static int act_form_tile_envs(ActForm f)
 // returns and the name functions report it, so the two cannot drift apart.
 static ActForm pick_act_form(int64_t cnt, int tm_max, int gcount, bool w2t, bool want_sum)
 {
-    const int form = act_form(), form4 = act_form4();
+    const int form = act_form();
     if (w2t) {                                                // tiled learner group: the free-running forms read W2 from the tiled regions
         const int tmt = pick_tm(cnt, tm_max);
         return tmt == 4 ? kAct442 : tmt == 2 ? kAct242 : kAct142;
     }
-    if (form4 == 2 && form < 0 && cnt > 8192 && gcount <= 1) return kAct2;
-    if (form4 == 2 && form == 12 && (tm_max == 0 || tm_max >= 2)) return kAct2;    // A/B: the two-per-CU form (64-env tiles) at any size
+    if (form < 0 && cnt > 8192 && gcount <= 1) return kAct2;
+    if (form == 12 && (tm_max == 0 || tm_max >= 2)) return kAct2;    // A/B: the two-per-CU form (64-env tiles) at any size
     const int tm = pick_tm(cnt, tm_max);
-    if (tm == 4) return form4 == 0 ? kAct440 : kAct442;
-    if (tm == 2) return form == 0 || form4 == 0 ? kAct240 : kAct242;
-    if (form == 0) return kAct140;
+    if (tm == 4) return kAct442;
+    if (tm == 2) return kAct242;
     if (form == 2) return kAct142;
     if (form == 3) return kAct143;
     // 4 096 < envs <= 8 192 (round 4): the split form with a ring of TWO chunks -- 76.5 KB per workgroup, so the two halves of a tile's work
@@ -1813,11 +1687,8 @@ static int dispatch_act(const ActArgs &a, hipStream_t st, const shems_group_hpar
     // envs of this launch a.m - a.m0 (a range launch: every form writes the same bytes)
     switch (pick_act_form(a.m - a.m0, a.tm_max, a.gcount, a.w2t != nullptr, want_sum)) {
     case kAct2: return launch_act2(a, st, hp);
-    case kAct440: return launch_act<4, 4>(a, st, hp);
     case kAct442: return launch_act<4, 4, 2>(a, st, hp);
-    case kAct240: return launch_act<2, 4>(a, st, hp);
     case kAct242: return launch_act<2, 4, 2>(a, st, hp);
-    case kAct140: return launch_act<1, 4>(a, st, hp);
     case kAct142: return launch_act<1, 4, 2>(a, st, hp);
     case kAct143: return launch_act<1, 4, 3>(a, st, hp);
     case kActg1422: return launch_actg<1, 4, 2, 2>(a, st, hp);

@@ -118,13 +118,12 @@ def test_noise_kinds_inside_the_fused_step_with_per_env_configs(noise, n):
 
 
 # ------------------------------------------------------------------------------------------------------------ every forced form --
-_FORMS = {"default": {}, "shared": {"SHEMS_ACT_FORM": "0", "SHEMS_ACT_FORM4": "0"}, "free": {"SHEMS_ACT_FORM": "2", "SHEMS_ACT_FORM4": "1"},
-          "ring3": {"SHEMS_ACT_FORM": "3", "SHEMS_ACT_FORM4": "1"}, "group8": {"SHEMS_ACT_FORM": "8"}, "split": {"SHEMS_ACT_FORM": "9"},
+_FORMS = {"default": {}, "free": {"SHEMS_ACT_FORM": "2"},
+          "ring3": {"SHEMS_ACT_FORM": "3"}, "group8": {"SHEMS_ACT_FORM": "8"}, "split": {"SHEMS_ACT_FORM": "9"},
           "two_per_cu_everywhere": {"SHEMS_ACT_FORM": "12"}, "split_ring2": {"SHEMS_ACT_FORM": "10"}}
 # what each form runs at 40 007 / 20 005 / 6 005 envs (128-, 64- and 32-env tiles where the form has them)
 _FORM_KERNELS = {
     "default": ("k_act2", "k_act2", "k_actg<1, 4, 2, 2>"),
-    "shared": ("k_act<4, 4, 0>", "k_act<2, 4, 0>", "k_act<1, 4, 0>"),
     "free": ("k_act<4, 4, 2>", "k_act<2, 4, 2>", "k_act<1, 4, 2>"),
     "ring3": ("k_act<4, 4, 2>", "k_act<2, 4, 2>", "k_act<1, 4, 3>"),
     "group8": ("k_act<4, 4, 2>", "k_act<2, 4, 2>", "k_actg<1, 8, 1, 3>"),
