@@ -243,11 +243,11 @@ int shems_act_step_range_dev(const shems_view *v, const shems_act_params *p, int
                              const shems_replay *ring, const shems_ring_window *window, void *stream);
 /* scale_action (DDPG.jl:178-184) on device: d_a [n][2] in [-1,1] -> d_out [n][2] SoC targets in [0,1]. */
 int shems_scale_action_dev(const float *d_a, int64_t n, float *d_out, void *stream);
-/* The kernel shems_act_step_dev (grouped = 0) / shems_act_step_group_dev (grouped != 0) dispatches for n_envs envs, by the name a
+/* The kernel that shems_act_step_dev (grouped = 0) or else shems_act_step_group_dev dispatches for n_envs envs, by the name a
  * profiler shows (e.g. "shems::k_act2", "shems::k_actg<1, 8, 1, 3>"), NUL-terminated into out[cap]: bench.py's roofline.kernel. */
 int shems_act_step_kernel(int64_t n_envs, int grouped, char *out, int32_t cap);
 /* The same for a learner group of envs_per_learner households per learner (a tile never straddles two learners; tiled != 0: the group's
- * W2 is read from its tiled regions, shems_act_step_group_tiled_dev). */
+ * W2 is read from its tiled regions, t != NULL). */
 int shems_act_step_group_kernel(int64_t n_envs, int64_t envs_per_learner, int tiled, char *out, int32_t cap);
 /* Number of workgroups shems_act_step_dev launches for n envs (length of d_block_reward). */
 int shems_act_step_grid(int64_t n_envs, int64_t *out_blocks);
@@ -436,50 +436,10 @@ typedef struct shems_group {
     int64_t envs_per_learner;  /* act/step only                                           */
 } shems_group;
 
-int shems_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, float *d_a,
-                             double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window,
-                             void *stream);
+/* replay() for every learner in the LATENCY form: the five launches of shems_ddpg_update with grid z = learner, or its four parts. */
 int shems_ddpg_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int64_t ring_len,
                             uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit,
                             double eta_act, double bp1_act, double bp2_act, void *stream);
-/* The same function in its THROUGHPUT form (csrc/shems_gupd.hip): for groups wide enough that nothing is latency-bound any more
- * (the thesis protocol runs 40 seeds x 10 chargers = 400 learners, RL-SHEMS_bs_scheduler_1179_08_on_01-98.sh:67-87) -- plain
- * back-propagation on small tiles, 4 workgroups resident per CU, eight launches for the whole group.  Same sampler, same ADAM
- * arithmetic; the products sum in another order than the five-launch form above, so per learner the two agree to fp32
- * accumulation accuracy (every gradient block within 2e-6 of its max-abs of a float64 evaluation), not bit for bit.
- * flags: SHEMS_TP_STORE_GRAD also leaves the gradients in grad_actor / grad_critic (otherwise they are never materialised;
- * the b3 / layer-1 / W2 / b2 / W3 elements are consumed by ADAM in the lane that finishes them).  Uses d0->ws with a layout of
- * its own: do not mix the two forms on one workspace within one update. */
-enum { SHEMS_TP_STORE_GRAD = 1 };
-int shems_ddpg_group_update_tp(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int64_t ring_len,
-                               uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit,
-                               double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream);
-/* The throughput form on a TILED working layout of the layer-2 state (round 6).  The W2-gradient launches of the form above are its
- * HBM stream -- 32 B in and out per W2 parameter: ADAM moments (Flux.Optimise.ADAM state, DDPG.jl:105-108), parameter and target
- * (soft_update!, DDPG.jl:99-103) -- and in Flux order ([in][out] rows of 500 floats) a 64 x 64 tile of it is 4 x 64 pieces of 256
- * bytes: 3.85 TB/s where one contiguous 64 KB piece per tile reaches 4.78 TB/s (tools/micro/adam_stream.hip).  A tiled region holds,
- * per network, W2 / m / v / target as [4 k-tiles][8 n-tiles][m | v | p | target][64][64] floats (rows / columns padded to 256 / 512
- * with zeros), SHEMS_W2T_FLOATS per learner, at learner 0's pointer + l * stride_bytes like every other block.  While a group
- * trains through these entry points the tiled regions hold the CURRENT layer-2 state and the W2 ranges of the Flux-order blocks
- * (shems_ddpg.actor / critic / actor_t / critic_t / m_* / v_*) are stale; everything else (layer 1, b2, W3, b3) stays in the
- * Flux-order blocks.  shems_group_w2_to_tiled / _to_flux copy the W2 ranges one way or the other (checkpoints, set / get of
- * parameters, the single-learner entry points and the latency form all speak Flux order).  Same arithmetic and summation order as
- * shems_ddpg_group_update_tp: the two leave the same values (tests/test_group_gpu.py holds both to the float64 oracle and to each
- * other bit for bit). */
-enum { SHEMS_W2T_FLOATS = 32 * 4 * 64 * 64 };
-typedef struct shems_group_w2t {
-    float *actor;              /* dev [SHEMS_W2T_FLOATS] of learner 0: actor W2, its moments and actor_target W2  */
-    float *critic;             /* dev [SHEMS_W2T_FLOATS] of learner 0: critic ...                                   */
-} shems_group_w2t;
-int shems_group_w2_to_tiled(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, void *stream);
-int shems_group_w2_to_flux(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, void *stream);
-int shems_ddpg_group_update_tiled(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *t,
-                                  int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit,
-                                  double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream);
-/* shems_act_step_group_dev with every learner's actor W2 read from its tiled region (t->actor; t->critic is not used). */
-int shems_act_step_group_tiled_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
-                                   float *d_a, double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window,
-                                   void *stream);
 int shems_ddpg_group_critic_grad(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g,
                                  int64_t ring_len, uint64_t seed, uint32_t tick, void *stream);
 int shems_ddpg_group_critic_apply(const shems_ddpg *d0, const shems_group *g, double eta, double bp1, double bp2,
@@ -487,13 +447,31 @@ int shems_ddpg_group_critic_apply(const shems_ddpg *d0, const shems_group *g, do
 int shems_ddpg_group_actor_grad(const shems_ddpg *d0, const shems_group *g, void *stream);
 int shems_ddpg_group_actor_apply(const shems_ddpg *d0, const shems_group *g, double eta, double bp1, double bp2,
                                  void *stream);
+/* A TILED working layout of the layer-2 state (round 6).  The W2-gradient launches of the throughput form below are its
+ * HBM stream -- 32 B in and out per W2 parameter: ADAM moments (Flux.Optimise.ADAM state, DDPG.jl:105-108), parameter and target
+ * (soft_update!, DDPG.jl:99-103) -- and in Flux order ([in][out] rows of 500 floats) a 64 x 64 tile of it is 4 x 64 pieces of 256
+ * bytes: 3.85 TB/s where one contiguous 64 KB piece per tile reaches 4.78 TB/s (tools/micro/adam_stream.hip).  A tiled region holds,
+ * per network, W2 / m / v / target as [4 k-tiles][8 n-tiles][m | v | p | target][64][64] floats (rows / columns padded to 256 / 512
+ * with zeros), SHEMS_W2T_FLOATS per learner, at learner 0's pointer + l * stride_bytes like every other block.  While a group
+ * trains with t != NULL the tiled regions hold the CURRENT layer-2 state and the W2 ranges of the Flux-order blocks
+ * (shems_ddpg.actor / critic / actor_t / critic_t / m_* / v_*) are stale; everything else (layer 1, b2, W3, b3) stays in the
+ * Flux-order blocks.  shems_group_w2_to_tiled / _to_flux copy the W2 ranges one way or the other (checkpoints, set / get of
+ * parameters, the single-learner entry points and the latency form all speak Flux order).  Same arithmetic and summation order on
+ * either layout: the two leave the same values (tests/test_group_gpu.py holds both to the float64 oracle and to each other bit for
+ * bit). */
+enum { SHEMS_W2T_FLOATS = 32 * 4 * 64 * 64 };
+typedef struct shems_group_w2t {
+    float *actor;              /* dev [SHEMS_W2T_FLOATS] of learner 0: actor W2, its moments and actor_target W2  */
+    float *critic;             /* dev [SHEMS_W2T_FLOATS] of learner 0: critic ...                                   */
+} shems_group_w2t;
+int shems_group_w2_to_tiled(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, void *stream);
+int shems_group_w2_to_flux(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, void *stream);
 /* ------------------------------------------- per-learner hyper-parameters of a learner group -- */
 /* The thesis's experiment is a hyper-parameter grid (input09_08_on_01-09_eval.jl:62-106: BATCH, noise_act, (L1, L2), (eta_act,
  * eta_crit)).  With one record per learner -- a DEVICE array of g->count records, learner l's is d_hp[l] -- one group runs many grid
- * points at once.  The entry points below are those of the throughput form and of the fused group step with the record's scalars in
- * place of the shared ones: shems_ddpg.gamma / tau / batch of d0 and shems_act_params.noise_mu / noise_sigma of p0 are IGNORED.  The
- * ADAM beta powers stay shared (the learners advance in lockstep).  A record holding d0's / p0's values gives the bits of the shared
- * entry points.  Hidden sizes below (250, 500) need no field: such a learner's networks are zero-padded (ddpg.pad_net) and stay so. */
+ * points at once: the group entry points that take d_hp use the record's scalars in place of the shared ones of d0 / p0.  The
+ * ADAM beta powers stay shared (the learners advance in lockstep).  A record holding d0's / p0's values gives the bits of
+ * d_hp == NULL.  Hidden sizes below (250, 500) need no field: such a learner's networks are zero-padded (ddpg.pad_net) and stay so. */
 typedef struct shems_group_hparams {
     double  eta_act, eta_crit;     /* ADAM(eta), DDPG.jl:105-108: the Float64 value of the Float32 literal (as Agent.eta_*)      */
     float   gamma, tau;            /* DDPG.jl:133, 99-103                                                                        */
@@ -504,18 +482,35 @@ typedef struct shems_group_hparams {
 /* Host-side validation of count records in HOST memory: batch in 1..128, eta finite and > 0, 0 < tau <= 1, 0 <= gamma <= 1,
  * noise_sigma >= 0, every value finite.  SHEMS_ERR_ARG names the first bad learner and field. */
 int shems_group_hparams_check(const shems_group_hparams *host_hp, int32_t count);
-/* shems_act_step_group_dev (t == NULL) / shems_act_step_group_tiled_dev (t != NULL) with learner l's envs drawing their action noise
- * as d_hp[l].noise_mu + d_hp[l].noise_sigma * z (z keyed by the global env index, as there).  Gaussian noise only: p0->noise_kind
- * must be SHEMS_NOISE_GAUSS. */
-int shems_act_step_group_hp_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
-                                const shems_group_hparams *d_hp, float *d_a, double *d_returns_acc, const shems_replay *ring0,
-                                const shems_ring_window *window, void *stream);
-/* shems_ddpg_group_update_tp (t == NULL) / shems_ddpg_group_update_tiled (t != NULL) with learner l's batch (the first batch_l draws of
- * the same minibatch stream, masks, divisors, losses), gamma, tau and eta (k1 = eta_l / (1 - bp1) formed on the device, correctly
- * rounded) from d_hp[l]. */
-int shems_ddpg_group_update_hp(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *t,
-                               const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double bp1_crit,
-                               double bp2_crit, double bp1_act, double bp2_act, int32_t flags, void *stream);
+/* replay() for every learner in the THROUGHPUT form (csrc/shems_gupd.hip): for groups wide enough that nothing is latency-bound any
+ * more (the thesis protocol runs 40 seeds x 10 chargers = 400 learners, RL-SHEMS_bs_scheduler_1179_08_on_01-98.sh:67-87) -- plain
+ * back-propagation on small tiles, 4 workgroups resident per CU, eight launches for the whole group.  Same sampler, same ADAM
+ * arithmetic as shems_ddpg_group_update; the products sum in another order, so per learner the two agree to fp32 accumulation
+ * accuracy (every gradient block within 2e-6 of its max-abs of a float64 evaluation), not bit for bit.
+ *   t:     NULL = every array in Flux order; else the layer-2 state of both networks lives in the tiled regions (both 16-byte
+ *          aligned) and the W2 ranges of the Flux-order blocks are neither read nor written.
+ *   d_hp:  NULL = d0's batch (1..128) / gamma / tau and eta_crit / eta_act for every learner; else an 8-byte aligned device array,
+ *          learner l's batch (the first batch_l draws of the same minibatch stream, masks, divisors, losses), gamma, tau and eta
+ *          (k1 = eta_l / (1 - bp1) formed on the device, correctly rounded) from d_hp[l]; d0's three and eta_crit / eta_act are
+ *          then ignored.
+ *   flags: SHEMS_TP_STORE_GRAD also leaves the gradients in grad_actor / grad_critic (otherwise they are never materialised;
+ *          the b3 / layer-1 / W2 / b2 / W3 elements are consumed by ADAM in the lane that finishes them).
+ * Uses d0->ws with a layout of its own: do not mix the two forms on one workspace within one update. */
+enum { SHEMS_TP_STORE_GRAD = 1 };
+int shems_ddpg_group_update_tp(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *t,
+                               const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
+                               double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags,
+                               void *stream);
+/* The fused vector step (shems_act_step_dev) for every learner of a group, one launch: env i is driven by learner
+ * i / envs_per_learner, draws its noise keyed by its index in the view, and the ring window applies inside each learner's env block.
+ *   t:     NULL = every actor in Flux order; else every learner's actor W2 is read from its tiled region (t->actor, 16-byte
+ *          aligned; t->critic is not used).
+ *   d_hp:  NULL = p0's noise for every learner; else an 8-byte aligned device array, learner l's envs draw
+ *          d_hp[l].noise_mu + d_hp[l].noise_sigma * z (the same z) and p0's noise_mu / noise_sigma are ignored.  Gaussian noise only
+ *          then: p0->noise_kind must be SHEMS_NOISE_GAUSS. */
+int shems_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
+                             const shems_group_hparams *d_hp, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                             const shems_ring_window *window, void *stream);
 /* ------------------------------------------- the wide group form: learner groups on the layer-by-layer path -- */
 /* A learner group whose networks have one padded hidden size (l1, l2) up to 4096 (the tuned grid's (300, 600); smaller learners are
  * zero-padded into it and stay so) and whose learners' batches reach 256.  One update pass holds P = max(128, max_batch rounded up to

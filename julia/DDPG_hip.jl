@@ -406,7 +406,7 @@ pad4(n) = (n + 3) & ~3
 """LearnerGroup(actor_params, critic_params, envs_per_learner): `count = length(actor_params)` independent learners (one flat parameter vector
 each: the scheduler's seeds / chargers), every learner's networks, targets, ADAM moments, tiled layer-2 regions, workspace, normalisation and
 replay ring carved identically out of ONE slab; learner l owns the households [l * E, (l + 1) * E) of the env batch (E a multiple of 32).
-replay / act_step! advance all of them with the same launches (shems_ddpg_group_update_tiled: eight launches for the whole group).
+replay / act_step! advance all of them with the same launches (shems_ddpg_group_update_tp on the tiled layout: eight launches for the whole group).
 While the group trains, the layer-2 state lives in the tiled regions; flux!(g) brings the Flux-order blocks (what learner_params reads) up to date."""
 mutable struct LearnerGroup
     count::Int; envs_per_learner::Int; capacity::Int
@@ -510,26 +510,22 @@ function act_step!(g::LearnerGroup, env::EnvBatch; train::Bool=true, tick::Integ
     p = Ref(ShemsActParams(at(g, :actor), at(g, :s_min), at(g, :s_max), 0f0, g.sigma, Int32(train), UInt32(tick % 0x100000000), g.seed, Int32(0),
                            0f0, 0f0, 0f0, Ptr{Float32}(C_NULL), Ptr{Float32}(C_NULL)))
     ret = returns === nothing ? Ptr{Float64}(C_NULL) : returns.ptr
-    if window > 0
-        w = Ref(ShemsRingWindow(g.pushed % g.capacity, window, window == 1 ? 0 : (g.tick * window) % g.envs_per_learner))
-        check(ccall((:shems_act_step_group_tiled_dev, LIB), Cint,
-                    (Ptr{ShemsView}, Ptr{ShemsActParams}, Ptr{ShemsGroup}, Ptr{ShemsGroupW2T}, Ptr{Float32}, Ptr{Float64}, Ptr{ShemsReplay}, Ptr{ShemsRingWindow}, Ptr{Cvoid}),
-                    Ref(env.view), p, Ref(group_struct(g)), Ref(w2t_struct(g)), C_NULL, ret, Ref(ring_struct(g)), w, C_NULL))
-        g.pushed += window
-    else
-        check(ccall((:shems_act_step_group_tiled_dev, LIB), Cint,
-                    (Ptr{ShemsView}, Ptr{ShemsActParams}, Ptr{ShemsGroup}, Ptr{ShemsGroupW2T}, Ptr{Float32}, Ptr{Float64}, Ptr{ShemsReplay}, Ptr{ShemsRingWindow}, Ptr{Cvoid}),
-                    Ref(env.view), p, Ref(group_struct(g)), Ref(w2t_struct(g)), C_NULL, ret, C_NULL, C_NULL, C_NULL))
-    end
+    # no window: nothing is remembered (ring and window NULL); d_hp NULL: every learner draws with p's sigma
+    ring, w = window > 0 ? (Ref(ring_struct(g)), Ref(ShemsRingWindow(g.pushed % g.capacity, window, window == 1 ? 0 : (g.tick * window) % g.envs_per_learner))) :
+                           (C_NULL, C_NULL)
+    check(ccall((:shems_act_step_group_dev, LIB), Cint,
+                (Ptr{ShemsView}, Ptr{ShemsActParams}, Ptr{ShemsGroup}, Ptr{ShemsGroupW2T}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float64}, Ptr{ShemsReplay}, Ptr{ShemsRingWindow}, Ptr{Cvoid}),
+                Ref(env.view), p, Ref(group_struct(g)), Ref(w2t_struct(g)), C_NULL, C_NULL, ret, ring, w, C_NULL))
+    g.pushed += max(window, 0)
     return nothing
 end
 
 "replay (DDPG.jl:121-145) for every learner of the group: eight launches in all (the throughput form on the tiled layout); minibatch l = key seed + l"
 function replay(g::LearnerGroup; rng_rpl::Integer=g.updates)
     use_tiled!(g)
-    check(ccall((:shems_ddpg_group_update_tiled, LIB), Cint,
-                (Ptr{ShemsDdpg}, Ptr{ShemsReplay}, Ptr{ShemsGroup}, Ptr{ShemsGroupW2T}, Int64, UInt64, UInt32, Float64, Float64, Float64, Float64, Float64, Float64, Int32, Ptr{Cvoid}),
-                Ref(ddpg_struct(g)), Ref(ring_struct(g)), Ref(group_struct(g)), Ref(w2t_struct(g)), min(g.pushed, g.capacity), g.seed, UInt32(rng_rpl % 0x100000000),
+    check(ccall((:shems_ddpg_group_update_tp, LIB), Cint,
+                (Ptr{ShemsDdpg}, Ptr{ShemsReplay}, Ptr{ShemsGroup}, Ptr{ShemsGroupW2T}, Ptr{Cvoid}, Int64, UInt64, UInt32, Float64, Float64, Float64, Float64, Float64, Float64, Int32, Ptr{Cvoid}),
+                Ref(ddpg_struct(g)), Ref(ring_struct(g)), Ref(group_struct(g)), Ref(w2t_struct(g)), C_NULL, min(g.pushed, g.capacity), g.seed, UInt32(rng_rpl % 0x100000000),
                 g.eta_crit, g.bp_critic[1], g.bp_critic[2], g.eta_act, g.bp_actor[1], g.bp_actor[2], Int32(0), C_NULL))
     g.flux_valid = false
     g.bp_critic .*= [0.9, 0.999]

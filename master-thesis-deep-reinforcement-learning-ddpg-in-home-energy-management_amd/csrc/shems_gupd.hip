@@ -1022,7 +1022,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     gw2_body<IN, TL, false>(A, blockIdx.x, blockIdx.y, smem, nullptr);
 }
 
-// ---- the same launches with per-learner hyper-parameters (shems_ddpg_group_update_hp): own names, the bodies above with HP = true ----
+// ---- the same launches with per-learner hyper-parameters (shems_ddpg_group_update_tp with d_hp): own names, the bodies above with HP = true ----
 __global__ __launch_bounds__(256) void k_tp_prep_hp(PrepArgs A, const shems_group_hparams *hp) { prep_body<true>(A, blockIdx.x, blockIdx.y, hp); }
 template <bool QG, int NTL, bool TL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTL == 4 ? 3 : 4, 4))) void k_tp_fwd_hp(FwdArgs A, const shems_group_hparams *hp)
@@ -1159,10 +1159,11 @@ static int check_group_tp(const shems_group *g, const char *fn)
 // t == null: every array in Flux order (round 5's form); else the layer-2 state of both networks lives in the tiled regions.
 // HP: learner l's batch / gamma / tau / eta from hp[l] (device), the *_hp kernels; d->batch / gamma / tau and eta_* are not used.
 template <bool TL, bool HP>
-static int group_update_tp(const char *fn, const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, int64_t ring_len,
-                           uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act,
-                           int32_t flags, void *stream, const shems_group_hparams *hp = nullptr)
+static int group_update_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, const shems_group_hparams *hp,
+                           int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
+                           double bp2_act, int32_t flags, void *stream)
 {
+    const char *fn = "shems_ddpg_group_update_tp";
     if (int rc = check_group_tp(g, fn)) return rc;
     if (!d || !d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
         !d->s_min || !d->s_max || !d->ws || !d->losses)
@@ -1170,7 +1171,8 @@ static int group_update_tp(const char *fn, const shems_ddpg *d, const shems_repl
     if ((flags & SHEMS_TP_STORE_GRAD) && (!d->grad_actor || !d->grad_critic)) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
     if (flags & ~SHEMS_TP_STORE_GRAD) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
     if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
-    if (HP && (!hp || ((uintptr_t)hp & 7) != 0)) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (HP && ((uintptr_t)hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (HP) eta_crit = eta_act = 0.0;        // the *_hp kernels form k1 from the records; the host context's k1 is never read by them
     for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
         if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
     if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
@@ -1214,62 +1216,34 @@ static int group_update_tp(const char *fn, const shems_ddpg *d, const shems_repl
     typedef FwdShape<true, 2> SQ;
     const bool narrow = L < kNarrowBelow;
     const unsigned g8 = 8 * ((L + 7) / 8);
-    if constexpr (HP) {                      // the same eight launches, each reading its learner's record
-        hipLaunchKernelGGL(k_tp_prep_hp, dim3(5, L), dim3(256), 0, st, U.pa, hp);
-        if (narrow) hipLaunchKernelGGL((k_tp_fwd_hp<false, 2, TL>), dim3(3 * SN::TILES, L), dim3(256), SN::LDS, st, U.f1, hp);
-        else hipLaunchKernelGGL((k_tp_fwd_hp<false, 4, TL>), dim3(3 * SW::TILES, L), dim3(256), SW::LDS, st, U.f1, hp);
-        hipLaunchKernelGGL((k_tp_fwd_hp<false, 2, TL>), dim3(SN::TILES, L), dim3(256), SN::LDS, st, U.f2, hp);
-        if (narrow) hipLaunchKernelGGL((k_tp_d1_hp<CIN, 1, TL>), dim3(8 * g8), dim3(256), d1_lds(1), st, U.nc, hp);
-        else hipLaunchKernelGGL((k_tp_d1_hp<CIN, 2, TL>), dim3(4 * g8), dim3(256), d1_lds(2) + SHEMS_D1_PAD, st, U.nc, hp);
-        hipLaunchKernelGGL((k_tp_gw2_hp<CIN, TL>), dim3(GW_WGS, L), dim3(256), GW_LDS, st, U.nc, hp);
-        hipLaunchKernelGGL((k_tp_fwd_hp<true, 2, TL>), dim3(SQ::TILES, L), dim3(256), SQ::LDS, st, U.f5, hp);
-        if (narrow) hipLaunchKernelGGL((k_tp_d1_hp<SIN, 1, TL>), dim3(8 * g8), dim3(256), d1_lds(1), st, U.na, hp);
-        else hipLaunchKernelGGL((k_tp_d1_hp<SIN, 2, TL>), dim3(4 * g8), dim3(256), d1_lds(2) + SHEMS_D1_PAD, st, U.na, hp);
-        hipLaunchKernelGGL((k_tp_gw2_hp<SIN, TL>), dim3(GW_WGS, L), dim3(256), GW_LDS, st, U.na, hp);
-        return hip_ok(hipGetLastError(), "grouped update (throughput form, per-learner hyper-parameters) launches");
-    }
-    hipLaunchKernelGGL(k_tp_prep, dim3(5, L), dim3(256), 0, st, U.pa);
+    // the plain kernel, or with HP its *_hp twin with hp appended: the same eight launches, each reading its learner's record
+    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args) {
+        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, hp);
+        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
+    };
+    launch(k_tp_prep, k_tp_prep_hp, dim3(5, L), 0, U.pa);
     // Few learners: the shapes with twice the workgroups (P1 on 64-wide n-tiles, P3 / P6 on 32-wide k-tiles).  Below kNarrowBelow learners
     // the wide shapes leave CUs without work (P3 at 32 learners: 128 workgroups); measured per grouped update, wide / narrow: 32 learners
     // 247 / 226 us, 48 learners 322 / 320, 64 learners 362 / 372, 128 learners 669 / 695 (profiles/NOTES.md, round-5 log).
-    if (narrow) hipLaunchKernelGGL((k_tp_fwd<false, 2, TL>), dim3(3 * SN::TILES, L), dim3(256), SN::LDS, st, U.f1);
-    else hipLaunchKernelGGL((k_tp_fwd<false, 4, TL>), dim3(3 * SW::TILES, L), dim3(256), SW::LDS, st, U.f1);
-    hipLaunchKernelGGL((k_tp_fwd<false, 2, TL>), dim3(SN::TILES, L), dim3(256), SN::LDS, st, U.f2);
-    if (narrow) hipLaunchKernelGGL((k_tp_d1<CIN, 1, TL>), dim3(8 * g8), dim3(256), d1_lds(1), st, U.nc);
-    else hipLaunchKernelGGL((k_tp_d1<CIN, 2, TL>), dim3(4 * g8), dim3(256), d1_lds(2) + SHEMS_D1_PAD, st, U.nc);
-    hipLaunchKernelGGL((k_tp_gw2<CIN, TL>), dim3(GW_WGS, L), dim3(256), GW_LDS, st, U.nc);
-    hipLaunchKernelGGL((k_tp_fwd<true, 2, TL>), dim3(SQ::TILES, L), dim3(256), SQ::LDS, st, U.f5);
-    if (narrow) hipLaunchKernelGGL((k_tp_d1<SIN, 1, TL>), dim3(8 * g8), dim3(256), d1_lds(1), st, U.na);
-    else hipLaunchKernelGGL((k_tp_d1<SIN, 2, TL>), dim3(4 * g8), dim3(256), d1_lds(2) + SHEMS_D1_PAD, st, U.na);
-    hipLaunchKernelGGL((k_tp_gw2<SIN, TL>), dim3(GW_WGS, L), dim3(256), GW_LDS, st, U.na);
-    return hip_ok(hipGetLastError(), "grouped update (throughput form) launches");
+    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(3 * SN::TILES, L), SN::LDS, U.f1);
+    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(3 * SW::TILES, L), SW::LDS, U.f1);
+    launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(SN::TILES, L), SN::LDS, U.f2);
+    if (narrow) launch(k_tp_d1<CIN, 1, TL>, k_tp_d1_hp<CIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.nc);
+    else launch(k_tp_d1<CIN, 2, TL>, k_tp_d1_hp<CIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.nc);
+    launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, U.nc);
+    launch(k_tp_fwd<true, 2, TL>, k_tp_fwd_hp<true, 2, TL>, dim3(SQ::TILES, L), SQ::LDS, U.f5);
+    if (narrow) launch(k_tp_d1<SIN, 1, TL>, k_tp_d1_hp<SIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.na);
+    else launch(k_tp_d1<SIN, 2, TL>, k_tp_d1_hp<SIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.na);
+    launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.na);
+    return hip_ok(hipGetLastError(), HP ? "grouped update (throughput form, per-learner hyper-parameters) launches" : "grouped update (throughput form) launches");
 }
 
-extern "C" int shems_ddpg_group_update_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, int64_t ring_len, uint64_t seed,
-                                          uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
-                                          double bp2_act, int32_t flags, void *stream)
+extern "C" int shems_ddpg_group_update_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
+                                          const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
+                                          double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream)
 {
-    return group_update_tp<false, false>("shems_ddpg_group_update_tp", d, ring, g, nullptr, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
-                                  flags, stream);
-}
-
-extern "C" int shems_ddpg_group_update_tiled(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, int64_t ring_len,
-                                             uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
-                                             double bp2_act, int32_t flags, void *stream)
-{
-    return group_update_tp<true, false>("shems_ddpg_group_update_tiled", d, ring, g, t, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
-                                 flags, stream);
-}
-
-extern "C" int shems_ddpg_group_update_hp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
-                                          const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double bp1_crit,
-                                          double bp2_crit, double bp1_act, double bp2_act, int32_t flags, void *stream)
-{
-    // (eta_* = 0: the kernels form k1 from the records; the host context's k1 is never read by them)
-    if (t) return group_update_tp<true, true>("shems_ddpg_group_update_hp", d, ring, g, t, ring_len, seed, tick, 0.0, bp1_crit, bp2_crit, 0.0, bp1_act,
-                                              bp2_act, flags, stream, d_hp);
-    return group_update_tp<false, true>("shems_ddpg_group_update_hp", d, ring, g, nullptr, ring_len, seed, tick, 0.0, bp1_crit, bp2_crit, 0.0, bp1_act,
-                                        bp2_act, flags, stream, d_hp);
+    auto *update = t ? (d_hp ? group_update_tp<true, true> : group_update_tp<true, false>) : (d_hp ? group_update_tp<false, true> : group_update_tp<false, false>);
+    return update(d, ring, g, t, d_hp, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags, stream);
 }
 
 static_assert(sizeof(shems_group_hparams) == 40 && offsetof(shems_group_hparams, gamma) == 16 && offsetof(shems_group_hparams, noise_mu) == 24 &&

@@ -244,7 +244,7 @@ __device__ __forceinline__ TailPre tailpre_load(const float *lds)
 // remember (DDPG.jl:148-184, 199-229).  Returns the env's reward (0 when nothing was stepped).
 // obs_lds: the env's 9 raw observations in LDS (the caller staged them), or null = read them from the view.
 // pre_lds: the env's TailPre block in LDS (the caller fetched it ahead), or null = draw / read in place.
-// HP (shems_act_step_group_hp_dev): the Gaussian noise of learner l's envs is hp[l].noise_mu + hp[l].noise_sigma * z.
+// HP (shems_act_step_group_dev with d_hp): the Gaussian noise of learner l's envs is hp[l].noise_mu + hp[l].noise_sigma * z.
 template <bool HP = false>
 __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, float p0, float p1, int64_t learner, int64_t goff,
                                                const float *obs_lds, const float *pre_lds = nullptr, const shems_group_hparams *hp = nullptr)
@@ -352,7 +352,7 @@ constexpr int free_keep(int c)
 }
 
 // (every form a learner group can run is a body with a bool HP: the kernels of the shared entry points instantiate it with false, the
-// *_hp kernels -- own names, shems_act_step_group_hp_dev -- with true)
+// *_hp kernels -- own names, shems_act_step_group_dev with d_hp -- with true)
 template <int TM, int NW, int RD, bool HP>
 __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_hparams *hp)
 {
@@ -1504,7 +1504,7 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
 __global__ __launch_bounds__(256, 2) void k_act2(ActArgs A) { k_act2_body<false>(A, nullptr); }
 __global__ __launch_bounds__(256, 2) void k_act2_hp(ActArgs A, const shems_group_hparams *hp) { k_act2_body<true>(A, hp); }
 
-// hp != null (shems_act_step_group_hp_dev): the *_hp kernel of the same form
+// hp != null (shems_act_step_group_dev with d_hp): the *_hp kernel of the same form
 static int launch_act2(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
 {
     constexpr size_t lds = act2_lds_bytes();
@@ -1787,6 +1787,28 @@ static int check_act(const shems_act_params *p, const char *fn)
     return SHEMS_OK;
 }
 
+// What every step entry starts from: zeros, the view, the policy, one step of all the view's envs.  Callers add what is theirs.
+static void step_args(ActArgs &a, const shems_view *v, const shems_act_params *p)
+{
+    std::memset(&a, 0, sizeof a);
+    a.v = *v; a.p = *p; a.obs = v->obs; a.m = v->n_envs; a.do_step = 1;
+}
+
+// remember!: no ring, no window or an empty window records nothing.  block_envs: the envs one ring serves (the batch, or a learner's block).
+static int attach_ring(const char *fn, ActArgs &a, const shems_replay *ring, const shems_ring_window *window, int64_t block_envs)
+{
+    if (!ring || !window || window->count <= 0) return SHEMS_OK;
+    if (ring->capacity <= 0 || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done)
+        return set_error(SHEMS_ERR_ARG, "%s: incomplete replay ring", fn);
+    if (window->count > ring->capacity || window->count > block_envs || window->pos < 0)
+        return set_error(SHEMS_ERR_ARG, "%s: ring window larger than the ring or its block of %lld envs", fn, (long long)block_envs);
+    if (window->offset < 0 || window->offset >= block_envs)
+        return set_error(SHEMS_ERR_ARG, "%s: ring window offset %lld outside its block of %lld envs", fn, (long long)window->offset,
+                         (long long)block_envs);
+    a.ring = *ring; a.win = *window; a.use_ring = 1;
+    return SHEMS_OK;
+}
+
 int shems_actor_forward_dev(const shems_act_params *p, const float *d_obs, int64_t m, float *d_a, void *stream)
 {
     if (int rc = check_act(p, "shems_actor_forward_dev")) return rc;
@@ -1804,21 +1826,9 @@ int shems_act_step_dev(const shems_view *v, const shems_act_params *p, float *d_
     if (int rc = check_act(p, "shems_act_step_dev")) return rc;
     if (int rc = check_view(v, "shems_act_step_dev")) return rc;
     ActArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.v = *v; a.p = *p; a.obs = v->obs; a.m = v->n_envs; a.a_out = d_a;
-    a.rewards = d_rewards; a.rewards_f32 = d_rewards_f32; a.block_reward = d_block_reward;
-    a.returns_acc = d_returns_acc;
-    a.do_step = 1;
-    if (ring && window && window->count > 0) {
-        if (ring->capacity <= 0 || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done)
-            return set_error(SHEMS_ERR_ARG, "shems_act_step_dev: incomplete replay ring");
-        if (window->count > ring->capacity || window->count > v->n_envs || window->pos < 0)
-            return set_error(SHEMS_ERR_ARG, "shems_act_step_dev: ring window larger than the ring or the batch");
-        if (window->offset < 0 || window->offset >= v->n_envs)
-            return set_error(SHEMS_ERR_ARG, "shems_act_step_dev: ring window offset %lld outside the batch of %lld envs",
-                             (long long)window->offset, (long long)v->n_envs);
-        a.ring = *ring; a.win = *window; a.use_ring = 1;
-    }
+    step_args(a, v, p);
+    a.a_out = d_a; a.rewards = d_rewards; a.rewards_f32 = d_rewards_f32; a.block_reward = d_block_reward; a.returns_acc = d_returns_acc;
+    if (int rc = attach_ring("shems_act_step_dev", a, ring, window, v->n_envs)) return rc;
     return dispatch_act(a, (hipStream_t)stream);
 }
 
@@ -1836,17 +1846,9 @@ int shems_act_step_range_dev(const shems_view *v, const shems_act_params *p, int
         return set_error(SHEMS_ERR_ARG, "shems_act_step_range_dev: envs [%lld, %lld + %lld) outside the batch of %lld", (long long)env_lo,
                          (long long)env_lo, (long long)env_count, (long long)v->n_envs);
     ActArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.v = *v; a.p = *p; a.obs = v->obs; a.m0 = env_lo; a.m = env_lo + env_count;
-    a.rewards_f32 = d_rewards_f32;
-    a.do_step = 1;
-    if (ring && window && window->count > 0) {
-        if (ring->capacity <= 0 || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done)
-            return set_error(SHEMS_ERR_ARG, "shems_act_step_range_dev: incomplete replay ring");
-        if (window->count > ring->capacity || window->count > v->n_envs || window->pos < 0 || window->offset < 0 || window->offset >= v->n_envs)
-            return set_error(SHEMS_ERR_ARG, "shems_act_step_range_dev: ring window outside the ring or the batch");
-        a.ring = *ring; a.win = *window; a.use_ring = 1;
-    }
+    step_args(a, v, p);
+    a.m0 = env_lo; a.m = env_lo + env_count; a.rewards_f32 = d_rewards_f32;
+    if (int rc = attach_ring("shems_act_step_range_dev", a, ring, window, v->n_envs)) return rc;     // the window is defined on the whole batch
     return dispatch_act(a, (hipStream_t)stream);
 }
 
@@ -1868,17 +1870,9 @@ int shems_wide_act_step_dev(const shems_view *v, const shems_act_params *p, int3
     if (int rc = check_act(p, "shems_wide_act_step_dev")) return rc;
     if (int rc = check_view(v, "shems_wide_act_step_dev")) return rc;
     ActArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.v = *v; a.p = *p; a.obs = v->obs; a.m = v->n_envs; a.a_out = d_a;
-    a.rewards = d_rewards; a.rewards_f32 = d_rewards_f32; a.returns_acc = d_returns_acc;
-    a.do_step = 1;
-    if (ring && window && window->count > 0) {
-        if (ring->capacity <= 0 || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done)
-            return set_error(SHEMS_ERR_ARG, "shems_wide_act_step_dev: incomplete replay ring");
-        if (window->count > ring->capacity || window->count > v->n_envs || window->pos < 0 || window->offset < 0 || window->offset >= v->n_envs)
-            return set_error(SHEMS_ERR_ARG, "shems_wide_act_step_dev: ring window outside the ring or the batch");
-        a.ring = *ring; a.win = *window; a.use_ring = 1;
-    }
+    step_args(a, v, p);
+    a.a_out = d_a; a.rewards = d_rewards; a.rewards_f32 = d_rewards_f32; a.returns_acc = d_returns_acc;
+    if (int rc = attach_ring("shems_wide_act_step_dev", a, ring, window, v->n_envs)) return rc;
     return wide_act(a, l1, l2, d_ws, (hipStream_t)stream);
 }
 
@@ -1893,59 +1887,27 @@ static int group_act_args(const char *fn, const shems_view *v, const shems_act_p
     if (g->envs_per_learner < 32 || g->envs_per_learner % 32 != 0 || g->envs_per_learner * g->count != v->n_envs)
         return set_error(SHEMS_ERR_ARG, "%s: envs_per_learner must be a multiple of 32 and count * envs_per_learner == n_envs "
                          "(got %lld x %d for %lld envs)", fn, (long long)g->envs_per_learner, g->count, (long long)v->n_envs);
-    std::memset(&a, 0, sizeof a);
-    a.v = *v; a.p = *p0; a.obs = v->obs; a.m = v->n_envs; a.a_out = d_a;
-    a.returns_acc = d_returns_acc;
-    a.do_step = 1;
+    step_args(a, v, p0);
+    a.a_out = d_a; a.returns_acc = d_returns_acc;
     a.gcount = g->count; a.gstride = g->count > 1 ? g->stride_bytes : 0; a.genvs = g->envs_per_learner;
     a.tm_max = group_tm_max(g->envs_per_learner);
-    if (ring0 && window && window->count > 0) {
-        if (ring0->capacity <= 0 || !ring0->s || !ring0->a || !ring0->r || !ring0->s2 || !ring0->done)
-            return set_error(SHEMS_ERR_ARG, "%s: incomplete replay ring", fn);
-        if (window->count > ring0->capacity || window->count > g->envs_per_learner || window->pos < 0)
-            return set_error(SHEMS_ERR_ARG, "%s: ring window larger than the ring or a learner's env block", fn);
-        if (window->offset < 0 || window->offset >= g->envs_per_learner)
-            return set_error(SHEMS_ERR_ARG, "%s: ring window offset %lld outside a learner's block of %lld envs", fn,
-                             (long long)window->offset, (long long)g->envs_per_learner);
-        a.ring = *ring0; a.win = *window; a.use_ring = 1;
-    }
-    return SHEMS_OK;
+    return attach_ring(fn, a, ring0, window, g->envs_per_learner);
 }
-static int act_step_group(const char *fn, const shems_view *v, const shems_act_params *p0, const shems_group *g, const float *w2t, float *d_a,
-                          double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream,
-                          const shems_group_hparams *hp = nullptr)
+
+int shems_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
+                             const shems_group_hparams *d_hp, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                             const shems_ring_window *window, void *stream)
 {
+    const char *fn = "shems_act_step_group_dev";
     ActArgs a;
     if (int rc = group_act_args(fn, v, p0, g, d_a, d_returns_acc, ring0, window, a)) return rc;
-    a.w2t = w2t;
-    return dispatch_act(a, (hipStream_t)stream, hp);
-}
-
-int shems_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, float *d_a,
-                             double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream)
-{
-    return act_step_group("shems_act_step_group_dev", v, p0, g, nullptr, d_a, d_returns_acc, ring0, window, stream);
-}
-
-int shems_act_step_group_tiled_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t, float *d_a,
-                                   double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream)
-{
-    if (!t || !t->actor || ((uintptr_t)t->actor & 15) != 0)
-        return set_error(SHEMS_ERR_ARG, "shems_act_step_group_tiled_dev: shems_group_w2t.actor must be a 16-byte aligned device pointer");
-    return act_step_group("shems_act_step_group_tiled_dev", v, p0, g, t->actor, d_a, d_returns_acc, ring0, window, stream);
-}
-
-int shems_act_step_group_hp_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
-                                const shems_group_hparams *d_hp, float *d_a, double *d_returns_acc, const shems_replay *ring0,
-                                const shems_ring_window *window, void *stream)
-{
-    const char *fn = "shems_act_step_group_hp_dev";
-    if (!d_hp || ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
-    if (p0 && p0->noise_kind != SHEMS_NOISE_GAUSS)
+    if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (d_hp && p0->noise_kind != SHEMS_NOISE_GAUSS)
         return set_error(SHEMS_ERR_ARG, "%s: per-learner noise is Gaussian only (noise_kind %d)", fn, p0->noise_kind);
     if (t && (!t->actor || ((uintptr_t)t->actor & 15) != 0))
         return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t.actor must be a 16-byte aligned device pointer", fn);
-    return act_step_group(fn, v, p0, g, t ? t->actor : nullptr, d_a, d_returns_acc, ring0, window, stream, d_hp);
+    a.w2t = t ? t->actor : nullptr;
+    return dispatch_act(a, (hipStream_t)stream, d_hp);
 }
 
 int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,

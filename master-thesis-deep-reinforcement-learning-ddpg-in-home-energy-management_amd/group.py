@@ -154,18 +154,16 @@ def _declare_group():
     vp, i64 = C.c_void_p, C.c_int64
     from .ddpg import ActParams, DdpgArgs
     PD, PG, PR, PT = C.POINTER(DdpgArgs), C.POINTER(Group), C.POINTER(_capi.Replay), C.POINTER(GroupW2T)
-    L.shems_act_step_group_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, vp, vp, PR, C.POINTER(RingWindow), vp]
-    L.shems_act_step_group_tiled_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, PT, vp, vp, PR, C.POINTER(RingWindow), vp]
+    L.shems_act_step_group_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, PT, vp, vp, vp, PR, C.POINTER(RingWindow), vp]
     dbl = C.c_double
-    L.shems_ddpg_group_update_tiled.argtypes = [PD, PR, PG, PT, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, dbl, dbl, C.c_int32, vp]
     L.shems_group_w2_to_tiled.argtypes = [PD, PG, PT, vp]
     L.shems_group_w2_to_flux.argtypes = [PD, PG, PT, vp]
     L.shems_act_step_group_kernel.argtypes = [i64, i64, C.c_int, C.c_char_p, C.c_int32]
-    for fn in ("shems_act_step_group_tiled_dev", "shems_ddpg_group_update_tiled", "shems_group_w2_to_tiled", "shems_group_w2_to_flux", "shems_act_step_group_kernel"):
+    for fn in ("shems_group_w2_to_tiled", "shems_group_w2_to_flux", "shems_act_step_group_kernel"):
         getattr(L, fn).restype = C.c_int
     L.shems_ddpg_group_update.argtypes = [PD, PR, PG, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, dbl, dbl, vp]
     L.shems_ddpg_group_update.restype = C.c_int
-    L.shems_ddpg_group_update_tp.argtypes = [PD, PR, PG, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, dbl, dbl, C.c_int32, vp]
+    L.shems_ddpg_group_update_tp.argtypes = [PD, PR, PG, PT, vp, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, dbl, dbl, C.c_int32, vp]
     L.shems_ddpg_group_update_tp.restype = C.c_int
     L.shems_ddpg_group_critic_grad.argtypes = [PD, PR, PG, i64, C.c_uint64, C.c_uint32, vp]
     L.shems_ddpg_group_critic_apply.argtypes = [PD, PG, C.c_double, C.c_double, C.c_double, vp]
@@ -173,14 +171,12 @@ def _declare_group():
     L.shems_ddpg_group_actor_apply.argtypes = [PD, PG, C.c_double, C.c_double, C.c_double, vp]
     L.shems_minmax_group_dev.argtypes = [PR, PG, i64, i64, C.c_uint64, vp, vp, vp]
     L.shems_group_hparams_check.argtypes = [C.POINTER(HParams), C.c_int32]
-    L.shems_act_step_group_hp_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, PT, vp, vp, vp, PR, C.POINTER(RingWindow), vp]
-    L.shems_ddpg_group_update_hp.argtypes = [PD, PR, PG, PT, vp, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, C.c_int32, vp]
     i32 = C.c_int32
     L.shems_group_hparams_check_wide.argtypes = [C.POINTER(HParams), i32, i32]
     L.shems_wide_group_workspace_floats.argtypes = [i32, i32, i32, C.POINTER(i64)]
     L.shems_wide_group_update.argtypes = [PD, PR, PG, i32, i32, vp, i32, i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, dbl, dbl, vp]
     L.shems_wide_act_step_group_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, i32, i32, vp, vp, vp, vp, PR, C.POINTER(RingWindow), vp]
-    for fn in ("shems_group_hparams_check", "shems_act_step_group_hp_dev", "shems_ddpg_group_update_hp", "shems_group_hparams_check_wide",
+    for fn in ("shems_group_hparams_check", "shems_group_hparams_check_wide",
                "shems_wide_group_workspace_floats", "shems_wide_group_update", "shems_wide_act_step_group_dev"):
         getattr(L, fn).restype = C.c_int
     L.shems_group_eval_best_dev.argtypes = [PD, PG, PT, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]
@@ -224,10 +220,10 @@ class LearnerGroup:
         tensors, evaluating a learner through its Agent, or saving), `Agent.set_params` on a learner of the group is noticed by itself,
         any other write into those tensors must be followed by `flux_changed()`.
 
-        hparams: None (every learner trains with today's values through the shared entry points), or `count` mappings, learner l's with
+        hparams: None (every learner trains with today's shared values), or `count` mappings, learner l's with
         the keys of HPARAM_KEYS (eta_act, eta_crit, gamma, tau, sigma, mu, batch, hidden; a missing key takes today's default): the group
-        then runs the throughput form whatever its size, through the per-learner entry points (shems_ddpg_group_update_hp,
-        shems_act_step_group_hp_dev), and learners[l] carries learner l's values.  The records are checked and uploaded once, here.
+        then runs the throughput form whatever its size, with the records as the entry points' d_hp (shems_ddpg_group_update_tp,
+        shems_act_step_group_dev), and learners[l] carries learner l's values.  The records are checked and uploaded once, here.
         Refused, naming the learner: batch > 128, hidden wider than (250, 500), noise_type other than "gn", a per-learner mem_size.
 
         form="wide": the learners run on the layer-by-layer path (csrc/shems_wide.hip), batched over learners -- every launch runs the
@@ -264,6 +260,7 @@ class LearnerGroup:
         if self.form not in ("throughput", "latency", "wide"):
             raise ValueError("form must be 'throughput', 'latency' or 'wide'")
         self.store_grad = False                    # throughput form: also leave the gradients in grad_actor / grad_critic (tests)
+        self.fused = True                          # latency form: one call (False: the four split calls, the same bits)
         self.tiled = (self.form == "throughput" and os.environ.get("SHEMS_GROUP_TILED", "1") != "0") if tiled is None else bool(tiled)
         if self.tiled and self.form != "throughput":
             raise ValueError("the tiled working layout belongs to the throughput form")
@@ -323,7 +320,8 @@ class LearnerGroup:
         self.tick = 0
 
     def _hp_ptr(self):
-        return C.c_void_p(self._hp_dev.data_ptr())
+        """The entry points' d_hp: the device records, or NULL (the shared values)."""
+        return C.c_void_p(self._hp_dev.data_ptr()) if self._hp_dev is not None else None
 
     # ------------------------------------------------------------------
     def struct(self):
@@ -413,28 +411,17 @@ class LearnerGroup:
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
         r0 = self.rings[0].struct()
         w = RingWindow(*window) if window is not None else None
+        ring_w = (C.byref(r0), C.byref(w)) if w is not None else (None, None)
         if self.form == "wide":                    # four launches for the whole group (noise mu / sigma from the records, if any)
             need = C.c_int64(0)
             _capi.check(self.L.shems_wide_act_workspace_floats(*self.hidden, env.n, C.byref(need)))
             if self._act_ws is None or self._act_ws.numel() < need.value:      # (an eval batch may be wider than the training batch)
                 self._act_ws = self.torch.empty(need.value, dtype=self.torch.float32, device=self.device)
-            _capi.check(self.L.shems_wide_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), *self.hidden,
-                                                             self._hp_ptr() if self._hp_dev is not None else None, C.c_void_p(self._act_ws.data_ptr()),
-                                                             ptr(a_out), ptr(returns_acc), C.byref(r0) if w is not None else None,
-                                                             C.byref(w) if w is not None else None, self._stream()))
-        elif self._hp_dev is not None:             # learner l's noise mu / sigma from its record
-            t = self.w2t_struct() if self._use_tiled() else None
-            _capi.check(self.L.shems_act_step_group_hp_dev(C.byref(v), C.byref(p), C.byref(g), C.byref(t) if t is not None else None, self._hp_ptr(),
-                                                           ptr(a_out), ptr(returns_acc), C.byref(r0) if w is not None else None,
-                                                           C.byref(w) if w is not None else None, self._stream()))
-        elif self._use_tiled():
-            t = self.w2t_struct()
-            _capi.check(self.L.shems_act_step_group_tiled_dev(C.byref(v), C.byref(p), C.byref(g), C.byref(t), ptr(a_out), ptr(returns_acc),
-                                                              C.byref(r0) if w is not None else None, C.byref(w) if w is not None else None,
-                                                              self._stream()))
-        else:
-            _capi.check(self.L.shems_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), ptr(a_out), ptr(returns_acc),
-                                                        C.byref(r0) if w is not None else None, C.byref(w) if w is not None else None,
+            _capi.check(self.L.shems_wide_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), *self.hidden, self._hp_ptr(),
+                                                             C.c_void_p(self._act_ws.data_ptr()), ptr(a_out), ptr(returns_acc), *ring_w, self._stream()))
+        else:                                      # one launch; W2 from the tiles where they are current, noise mu / sigma from the records, if any
+            t = C.byref(self.w2t_struct()) if self._use_tiled() else None
+            _capi.check(self.L.shems_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), t, self._hp_ptr(), ptr(a_out), ptr(returns_acc), *ring_w,
                                                         self._stream()))
         if w is not None:
             for ring in self.rings:
@@ -447,38 +434,25 @@ class LearnerGroup:
         d = a0._ddpg_args()
         st = self._stream()
         tick = self.updates if tick is None else tick
+        sample = (len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF)
+        adam_c, adam_a = (a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1]), (a0.eta_act, a0.bp_actor[0], a0.bp_actor[1])
+        tl = self.form != "wide" and self._use_tiled()      # (a tiled group switched to the latency form: its Flux blocks are brought up to date)
         if self.form == "wide":                    # 24 launches for the whole group (csrc/shems_wide.hip)
-            _capi.check(self.L.shems_wide_group_update(C.byref(d), C.byref(r0), C.byref(g), *self.hidden,
-                                                       self._hp_ptr() if self._hp_dev is not None else None, self.max_batch,
-                                                       len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.eta_crit, a0.bp_critic[0],
-                                                       a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1], st))
-        elif self._hp_dev is not None:             # learner l's batch / gamma / tau / eta from its record
-            tl = self._use_tiled()
-            t = self.w2t_struct() if tl else None
-            _capi.check(self.L.shems_ddpg_group_update_hp(C.byref(d), C.byref(r0), C.byref(g), C.byref(t) if tl else None, self._hp_ptr(),
-                                                          len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.bp_critic[0], a0.bp_critic[1],
-                                                          a0.bp_actor[0], a0.bp_actor[1], 1 if self.store_grad else 0, st))
+            _capi.check(self.L.shems_wide_group_update(C.byref(d), C.byref(r0), C.byref(g), *self.hidden, self._hp_ptr(), self.max_batch,
+                                                       *sample, *adam_c, *adam_a, st))
+        elif self.form == "throughput" or self._hp_dev is not None:      # records: batch / gamma / tau / eta per learner, this form only
+            t = C.byref(self.w2t_struct()) if tl else None
+            _capi.check(self.L.shems_ddpg_group_update_tp(C.byref(d), C.byref(r0), C.byref(g), t, self._hp_ptr(), *sample, *adam_c, *adam_a,
+                                                          1 if self.store_grad else 0, st))
             if tl:
                 self._flux_valid = False
-        elif self._use_tiled():
-            t = self.w2t_struct()
-            _capi.check(self.L.shems_ddpg_group_update_tiled(C.byref(d), C.byref(r0), C.byref(g), C.byref(t), len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF,
-                                                             a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1],
-                                                             1 if self.store_grad else 0, st))
-            self._flux_valid = False
-        elif self.form == "throughput":
-            _capi.check(self.L.shems_ddpg_group_update_tp(C.byref(d), C.byref(r0), C.byref(g), len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF,
-                                                          a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1],
-                                                          1 if self.store_grad else 0, st))
-        elif getattr(self, "fused", True):
-            _capi.check(self.L.shems_ddpg_group_update(C.byref(d), C.byref(r0), C.byref(g), len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF,
-                                                       a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1], st))
+        elif self.fused:
+            _capi.check(self.L.shems_ddpg_group_update(C.byref(d), C.byref(r0), C.byref(g), *sample, *adam_c, *adam_a, st))
         else:
-            _capi.check(self.L.shems_ddpg_group_critic_grad(C.byref(d), C.byref(r0), C.byref(g), len(self.rings[0]), self.rng_seed,
-                                                            int(tick) & 0xFFFFFFFF, st))
-            _capi.check(self.L.shems_ddpg_group_critic_apply(C.byref(d), C.byref(g), a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1], st))
+            _capi.check(self.L.shems_ddpg_group_critic_grad(C.byref(d), C.byref(r0), C.byref(g), *sample, st))
+            _capi.check(self.L.shems_ddpg_group_critic_apply(C.byref(d), C.byref(g), *adam_c, st))
             _capi.check(self.L.shems_ddpg_group_actor_grad(C.byref(d), C.byref(g), st))
-            _capi.check(self.L.shems_ddpg_group_actor_apply(C.byref(d), C.byref(g), a0.eta_act, a0.bp_actor[0], a0.bp_actor[1], st))
+            _capi.check(self.L.shems_ddpg_group_actor_apply(C.byref(d), C.byref(g), *adam_a, st))
         for ag in self.learners:                   # the learners advance in lockstep: shared beta powers / update count
             ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
             ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]

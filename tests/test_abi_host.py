@@ -117,7 +117,7 @@ _C_SCALARS = {"int": "Cint", "int32_t": "Int32", "int64_t": "Int64", "uint64_t":
               "uint8_t": "UInt8", "float": "Float32", "double": "Float64", "shems_config": "ShemsConfig", "void": "Cvoid",
               "shems_env": "Cvoid", "shems_view": "ShemsView", "shems_act_params": "ShemsActParams", "shems_replay": "ShemsReplay",
               "shems_ring_window": "ShemsRingWindow", "shems_ddpg": "ShemsDdpg", "shems_train_loop": "ShemsTrainLoop", "shems_dp": "Cvoid",
-              "shems_group": "ShemsGroup", "shems_group_w2t": "ShemsGroupW2T"}
+              "shems_group": "ShemsGroup", "shems_group_w2t": "ShemsGroupW2T", "shems_group_hparams": "Cvoid"}
 
 
 def _julia_types_for(c_arg):
@@ -221,7 +221,7 @@ def test_julia_learner_module_matches_the_header(built_lib):
                                                            "shems_track_dev", "shems_get_view", "shems_reset_seeded_dev", "shems_train_steps",
                                                            "shems_train_loop_release",
                                                            # round 6: learner groups on the tiled working layout
-                                                           "shems_act_step_group_tiled_dev", "shems_ddpg_group_update_tiled", "shems_group_w2_to_tiled",
+                                                           "shems_act_step_group_dev", "shems_ddpg_group_update_tp", "shems_group_w2_to_tiled",
                                                            "shems_group_w2_to_flux", "shems_minmax_group_dev"}
     for name, ret, args in calls:
         assert hasattr(L, name), name

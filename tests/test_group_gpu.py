@@ -444,5 +444,5 @@ def test_group_argument_checks():
     import ctypes as C
     v = env.view()
     p = grp.learners[0]._act_params(False, 0)
-    rc = grp.L.shems_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), None, None, None, None, grp._stream())
+    rc = grp.L.shems_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), None, None, None, None, None, None, grp._stream())
     assert rc != 0
