@@ -629,11 +629,10 @@ class Agent:
         self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
         self.updates += 1
 
-    def enable_data_parallel(self, dist, native=None, direct=False):
+    def enable_data_parallel(self, dist, native=None):
         """Replicas (one per GPU, each with its own env shard and ring) all-reduce gradients over RCCL.  native: a shems_dp communicator
-        (parallel.native_comm) -- the all-reduces then run in the update's own stream, from native code; direct: that record exchanges
-        through peer-mapped inboxes instead (parallel.direct_comm)."""
-        self.sync = GradSync(dist, native=native, direct=direct)
+        (parallel.native_comm) -- the all-reduces then run in the update's own stream, from native code."""
+        self.sync = GradSync(dist, native=native)
         self.sync.broadcast(self.actor, self.critic, self.actor_t, self.critic_t)   # identical initial weights
 
     def _allreduce(self, g):
@@ -836,7 +835,7 @@ class TrainWorkload:
         self.hidden = (int(hidden[0]), int(hidden[1]))       # other than (250, 500): another point of the reference's grids (bench.py --hidden)
         self.agent = Agent(seed=1231, rng_seed=self.env_seed, hidden=self.hidden)   # same initial weights on every rank (config: seed 1231)
         if dist is not None:
-            from .parallel import direct_comm, native_comm
+            from .parallel import native_comm
             import os
             import sys
             log = lambda m: print(m, file=sys.stderr, flush=True)
@@ -848,19 +847,12 @@ class TrainWorkload:
             #   native            RCCL called in the update's own stream from native code (csrc/shems_dp.hip; a second communicator, made by
             #                     vote, self-tested, falling back to torch on any rank's failure): 63.9 us against 80.6-88.1 us per step with a
             #                     one-rank communicator on one GPU.
-            #   direct            no collective: peer-mapped inboxes inside the ADAM sweeps (k_adam_xchg).
-            native, direct = None, False
             how = os.environ.get("SHEMS_DP", "torch")
-            if how not in ("torch", "native", "direct"):
-                raise ValueError("SHEMS_DP must be torch, native or direct")
-            if not self.agent.wide:
-                if how == "direct":
-                    native = direct_comm(dist, log=log)
-                    direct = native is not None
-                if how == "native" or (how == "direct" and native is None):
-                    native = native_comm(dist, log=log)
+            if how not in ("torch", "native"):
+                raise ValueError(f"SHEMS_DP must be torch or native, not {how!r}")
+            native = native_comm(dist, log=log) if how == "native" and not self.agent.wide else None
             self.dp_requested = how
-            self.agent.enable_data_parallel(dist, native=native, direct=direct)
+            self.agent.enable_data_parallel(dist, native=native)
             if os.environ.get("SHEMS_DP_OVERLAP") in ("0", "1"):   # A/B knob: "1" = the critic's all-reduce asynchronous, under the actor's E products
                 self.agent.dp_overlap = os.environ["SHEMS_DP_OVERLAP"] == "1"
         self.ring = ReplayRing(self.mem_size)
@@ -982,15 +974,8 @@ class TrainWorkload:
         if self._native is not None:
             _capi.check(self.agent.L.shems_train_loop_release(C.byref(self._native)))
         # Every rank-local verdict is collected FIRST and exchanged in ONE collective together with the learner's checksum; only then does
-        # anybody raise -- a rank that sees an exchange timeout (normally only some do) must not leave its peers blocked in a collective.
+        # anybody raise -- a rank that sees a problem (normally only some do) must not leave its peers blocked in a collective.
         problems = []
-        if getattr(self.agent.sync, "direct", False):
-            n = C.c_int64(0)
-            self.agent.L.shems_dp_direct_timeouts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
-            self.agent.L.shems_dp_direct_timeouts.restype = C.c_int
-            _capi.check(self.agent.L.shems_dp_direct_timeouts(self.agent.sync.native, C.byref(n), self.agent._stream()))
-            if n.value or self.dp_poisoned():
-                problems.append(f"{n.value} waits of the direct gradient exchange gave up: a peer never delivered, the replicas have diverged")
         try:
             self.env.check_error()
         except Exception as e:                      # noqa: BLE001
@@ -1011,26 +996,15 @@ class TrainWorkload:
         if problems:
             raise RuntimeError("; ".join(problems))
 
-    def dp_poisoned(self):
-        """True once a wait of the direct gradient exchange has given up on this rank (sticky; no synchronisation)."""
-        sync = self.agent.sync
-        if not getattr(sync, "direct", False) or sync.native is None:
-            return False
-        out = C.c_int32(0)
-        self.agent.L.shems_dp_direct_poisoned.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        self.agent.L.shems_dp_direct_poisoned.restype = C.c_int
-        _capi.check(self.agent.L.shems_dp_direct_poisoned(sync.native, C.byref(out)))
-        return bool(out.value)
-
     def close(self):
-        """End of the run: give the native communicator / the direct exchange's mappings back (every rank calls it; idempotent)."""
+        """End of the run: give the native communicator back (every rank calls it; idempotent)."""
         sync = self.agent.sync
         h = getattr(sync, "native", None)
         if h is not None:
             self.torch.cuda.synchronize()
             self.agent.L.shems_dp_destroy.argtypes = [C.c_void_p]
             self.agent.L.shems_dp_destroy.restype = C.c_int
-            sync.native, sync.direct = None, False
+            sync.native = None
             if self._native is not None:
                 self._native.dp = None
             self.agent.L.shems_dp_destroy(h)
@@ -1094,9 +1068,7 @@ class TrainWorkload:
                 loc_avg = time_launches(torch, updates_only, reps)[0] if self.updates else 0.0
                 self.agent.sync = sync
                 gc, ga = torch.zeros_like(self.agent.grad_critic), torch.zeros_like(self.agent.grad_actor)
-                if getattr(sync, "direct", False):  # no all-reduce exists on its own: the exchange is inside the ADAM sweeps
-                    ar = lambda g: None
-                elif sync.native is not None:       # the exchange as the update issues it: RCCL in this stream, from native code
+                if sync.native is not None:         # the exchange as the update issues it: RCCL in this stream, from native code
                     Lc = self.agent.L
                     Lc.shems_dp_allreduce_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
                     Lc.shems_dp_allreduce_sum.restype = C.c_int
@@ -1146,7 +1118,6 @@ class TrainWorkload:
                 "loop": self.loop,
                 "learner_crc32": crc, "dp_overlap": bool(self.agent.dp_overlap and self.agent.sync.world > 1 and self.loop != "native"),   # (the native loop exchanges in program order)
                 "dp_exchange": None if self.agent.sync.world == 1 else (
-                    "direct exchange through peer-mapped inboxes inside the ADAM sweeps (k_adam_xchg), no collective launch" if getattr(self.agent.sync, "direct", False) else
                     "RCCL all-reduce in the update's own stream, issued from native code (shems_ddpg_update_dp)" if self.agent.sync.native is not None else
                     "torch.distributed all_reduce (its own stream)"),
                 "dp_requested": getattr(self, "dp_requested", None),

@@ -13,7 +13,9 @@ Round 4 adds the NATIVE exchange (csrc/shems_dp.hip: ncclAllReduce in the update
 shems_train_steps) on a one-rank shems_dp communicator, whose grad_scale is 1 / its own world = 1:
   D  Agent.replay() -> shems_ddpg_update_dp, host loop          E  the same inside the native loop (shems_train_loop.dp)
   F  a single replica (fused update, native loop)
-D, E and F must end bit-identical (the split form with grad_scale 1 is the fused form's arithmetic).
+D, E and F must end bit-identical (the split form with grad_scale 1 is the fused form's arithmetic).  D and E run a second time with
+Agent.dp_overlap = True: its "leave the actor's E products to shems_ddpg_actor_prepare" flag must not reach the native step (nobody
+there issues them), so the bytes are those of D and E.
 Prints one JSON line."""
 import importlib
 import json
@@ -43,7 +45,6 @@ class HalfWorld(P.GradSync):
         self.dist = dist if collective else None
         self.world, self.rank = 2, 0
         self.native = native
-        self.direct = False
 
 
 NATIVE = P.native_comm(dist)
@@ -77,6 +78,8 @@ out["native_communicator"] = NATIVE is not None
 if NATIVE is not None:
     out["native_host_loop"] = run(False, False, native=NATIVE, loop="host")
     out["native_native_loop"] = run(False, False, native=NATIVE, loop="native")
+    out["native_host_loop_dp_overlap"] = run(True, False, native=NATIVE, loop="host")
+    out["native_native_loop_dp_overlap"] = run(True, False, native=NATIVE, loop="native")
     out["single_replica"] = run(False, False, loop="native", single=True)
 out["replay_us"] = {"async_overlap": times[(True, True, False, False)], "in_order": times[(False, True, False, False)],
                     "no_collective": times[(False, False, False, False)], "native_in_stream": times.get((False, False, True, False)),

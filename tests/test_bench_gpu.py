@@ -227,8 +227,8 @@ def _check_data_parallel_fields(d, world):
     # noise here and may come out below zero; on RCCL the collectives are stream-ordered and it is the k_act time at the shard size)
     assert abs(d["update_us"] - dp["update_us_dp"]) < 1e-6 and abs(d["roofline"]["kernel_avg_us"]) < 1e5      # (seen: 10.2 ms at four gloo ranks on a busy host)
     # how the gradients travel: the line says which path was asked for and which ran.  Round 6: torch.distributed is the DEFAULT at
-    # world > 1 (no path of this code has moved a byte between two GPUs yet; the native RCCL-in-stream form and the direct exchange are
-    # opt-in, SHEMS_DP=native / direct)
+    # world > 1 (no path of this code has moved a byte between two GPUs yet; the native RCCL-in-stream form is opt-in,
+    # SHEMS_DP=native)
     assert d["dp_requested"] == "torch" and d["dp_exchange"].startswith("torch.distributed") and d["loop"] == "host"
     assert d["replica_crc32_distinct"] == 1                             # every rank's learner ended with the same bytes (gathered in finish())
 
@@ -272,14 +272,11 @@ def test_async_gradient_exchange_gives_the_same_bytes():
     assert out[0] == out[1]
 
 
-def test_direct_gradient_exchange_two_ranks_on_one_device():
-    """The direct exchange (SHEMS_DP=direct: peer-mapped inboxes, per-slice epoch flags, the sum in rank order inside the ADAM sweep -- no
-    collective launch) rehearsed as far as one GPU allows: two rank processes on device 0 map each other's inboxes with hipIpcOpenMemHandle
-    (profiles/r04_ipc_probe.json, tools/ipc_kernel_pingpong.hip: kernels of two processes do run concurrently there and see each other's
-    stores).  With two replicas the rank-order sum IS the all-reduce's sum (a + b), so the learner must end with the bytes of the
-    torch.distributed (gloo) path; no exchange wait may have given up (TrainWorkload.finish raises otherwise)."""
+def test_native_request_falls_back_to_torch_two_ranks_on_one_device():
+    """SHEMS_DP=torch and SHEMS_DP=native rehearsed as far as one GPU allows: two rank processes on device 0 over gloo.  The native
+    request cannot be met there, must fall back on every rank, and then leaves the learner with the bytes of the torch.distributed path."""
     out = {}
-    for how in ("torch", "direct", "native"):
+    for how in ("torch", "native"):
         d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "48", "--warmup", "6", "--envs", "4096", "--prewarm-s", "0"],
                  env={"SHEMS_BENCH_ONE_DEVICE": "1", "SHEMS_BENCH_BACKEND": "gloo", "SHEMS_DP": how})
         assert d["n_gpus"] == 2 and d["value"] > 0 and d["dp_requested"] == how
@@ -288,37 +285,8 @@ def test_direct_gradient_exchange_two_ranks_on_one_device():
     # must fall back -- on every rank, by vote -- to torch.distributed; the line says what was asked for and what ran
     assert out["native"]["dp_exchange"].startswith("torch.distributed") and out["native"]["loop"] == "host"
     assert out["native"]["learner_crc32"] == out["torch"]["learner_crc32"]
-    assert out["direct"]["dp_exchange"].startswith("direct exchange") and out["direct"]["loop"] == "native"
     assert out["torch"]["dp_exchange"].startswith("torch.distributed") and out["torch"]["loop"] == "host"
-    assert out["direct"]["learner_crc32"] == out["torch"]["learner_crc32"], (out["direct"]["learner_crc32"], out["torch"]["learner_crc32"])
-    assert out["direct"]["replica_crc32_distinct"] == 1 and out["torch"]["replica_crc32_distinct"] == 1
-    # ADVICE round 4: with SHEMS_DP_OVERLAP=1 Agent._ddpg_args() sets DEFER_ACTOR_E (K2 leaves the actor's E products to
-    # shems_ddpg_actor_prepare).  The native data-parallel step never issues that call: the flag must not reach it (shems_ddpg_update_dp
-    # clears it on its copy, the native loop's record carries flags = 0) -- same bytes as the torch path, and the line says program order.
-    dov = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "48", "--warmup", "6", "--envs", "4096", "--prewarm-s", "0"],
-               env={"SHEMS_BENCH_ONE_DEVICE": "1", "SHEMS_BENCH_BACKEND": "gloo", "SHEMS_DP": "direct", "SHEMS_DP_OVERLAP": "1"})
-    assert dov["loop"] == "native" and dov["dp_overlap"] is False and dov["learner_crc32"] == out["torch"]["learner_crc32"]
-    # four replicas (four rank processes on the one device): the rank-order sum of four gradients is no longer gloo's order, so only the
-    # replicas are held to each other -- all four learners bit-identical after 54 exchanged updates, no wait gave up
-    d4 = _run([sys.executable, "bench.py", "--gpus", "4", "--steps", "48", "--warmup", "6", "--envs", "2048", "--prewarm-s", "0"],
-              env={"SHEMS_BENCH_ONE_DEVICE": "1", "SHEMS_BENCH_BACKEND": "gloo", "SHEMS_DP": "direct"})
-    assert d4["n_gpus"] == 4 and d4["dp_exchange"].startswith("direct exchange") and d4["replica_crc32_distinct"] == 1
-
-
-def test_direct_exchange_late_peer_waits_or_fails_loudly_on_every_rank():
-    """a peer that is late must not produce silently diverged replicas.  tests/dp_direct_late_peer.py: two rank
-    processes on device 0, rank 1 stalls on the host in the middle of the run.  (a) the stall (1 s) is shorter than the wait bound
-    (5 s, the default): rank 0's sweeps wait in the kernel, both ranks finish with the SAME learner bytes.  (b) the stall (2 s) is
-    longer than the bound (set to 300 ms): rank 0's wait gives up and poisons its record -- its enqueued sweeps apply nothing, its next
-    call returns SHEMS_ERR_STATE -- and rank 1, whose next exchange never gets rank 0's slice, ends the same way: BOTH ranks fail.
-    The script exits non-zero for any third outcome (one rank finishing, different checksums)."""
-    script = os.path.join(U.ROOT, "tests", "dp_direct_late_peer.py")
-    a = subprocess.run([sys.executable, script, "5000", "1.0"], cwd=U.ROOT, capture_output=True, text=True, timeout=400)
-    assert a.returncode == 0 and "LATE ok" in a.stdout, (a.stdout[-500:], a.stderr[-1500:])
-    crcs = a.stdout.split("LATE ok")[1].split()
-    assert crcs[0] == crcs[1]
-    b = subprocess.run([sys.executable, script, "300", "2.0"], cwd=U.ROOT, capture_output=True, text=True, timeout=400)
-    assert b.returncode == 0 and "LATE poisoned" in b.stdout, (b.stdout[-500:], b.stderr[-1500:])
+    assert out["torch"]["replica_crc32_distinct"] == 1 and out["native"]["replica_crc32_distinct"] == 1
 
 
 def test_driver_command_rehearsal_at_the_widest_world_one_box_allows():
@@ -345,3 +313,8 @@ def test_rccl_stream_ordering_on_a_one_rank_group():
     # round 4: the native exchange (RCCL in the update's own stream, csrc/shems_dp.hip) on a one-rank communicator = a single replica
     assert d["native_communicator"] is True
     assert d["native_host_loop"] == d["native_native_loop"] == d["single_replica"], d
+    # ADVICE round 4: with SHEMS_DP_OVERLAP=1 Agent._ddpg_args() sets DEFER_ACTOR_E (K2 leaves the actor's E products to
+    # shems_ddpg_actor_prepare).  The native data-parallel step never issues that call: the flag must not reach it (shems_ddpg_update_dp
+    # clears it on its copy, the native loop's record carries flags = 0) -- the same bytes with Agent.dp_overlap set.
+    assert d["native_native_loop_dp_overlap"] == d["native_native_loop"], d
+    assert d["native_host_loop_dp_overlap"] == d["native_host_loop"], d

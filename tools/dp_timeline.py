@@ -15,7 +15,6 @@ class HalfWorld(P.GradSync):
         self.dist = dist if collective else None
         self.world, self.rank = 2, 0
         self.native = native
-        self.direct = False
 native = P.native_comm(dist) if how == "native" else None
 wl = D.TrainWorkload(S, torch, 8192, seed=11, updates=1, loop="native" if how == "native" else "host")
 wl.agent.sync = HalfWorld(how == "torch", native); wl.agent.fused = False
