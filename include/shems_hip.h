@@ -519,6 +519,53 @@ int shems_wide_group_update(const shems_ddpg *d0, const shems_replay *ring0, con
 int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
                                   const shems_group_hparams *d_hp, float *d_ws, float *d_a, double *d_returns_acc, const shems_replay *ring0,
                                   const shems_ring_window *window, void *stream);
+/* ------------------------------------------- per-learner exploration and ring size of a learner group -- */
+/* The reference's live grid (input.jl:58-100) varies MEM_SIZE and the Ornstein-Uhlenbeck noise's theta per point (all 27 points use
+ * noise_type = "ou": OUNoise, DDPG.jl:49-55, 157-158; memory = CircularBuffer{Any}(MEM_SIZE), input.jl:64, 140).  These per-learner
+ * values travel beside d_hp in a second, parallel DEVICE array of g->count records, learner l's is d_xp[l], through the *_x entry
+ * points below; the entry points without _x are their d_xp == NULL case.  ring0->capacity stays what every learner's ring arrays are
+ * carved for: learner l uses slots [0, mem_size_l) of its own. */
+typedef struct shems_group_xparams {
+    float   ou_theta;              /* OUNoise theta of this learner (used when p0->noise_kind == SHEMS_NOISE_OU), DDPG.jl:49-55      */
+    float   ou_dt;                 /* OUNoise dt                                                                                    */
+    int32_t mem_size;              /* this learner's ring capacity, 1..ring0->capacity (input.jl:64, 140): slots [0, mem_size)      */
+    int32_t reserved;              /* 0                                                                                             */
+} shems_group_xparams;             /* 16 bytes */
+/* Host-side validation of count records in HOST memory (DDPG.jl:49-55, input.jl:64): ou_theta finite and >= 0, ou_dt finite and > 0,
+ * mem_size in 1..capacity, reserved 0.  SHEMS_ERR_ARG names the first bad learner and field, as shems_group_hparams_check does. */
+int shems_group_xparams_check(const shems_group_xparams *host_xp, int32_t count, int64_t capacity);
+/* shems_act_step_group_dev with per-learner exploration and ring sizes (DDPG.jl:49-55, 157-158; input.jl:64, 140).  d_hp, d_xp (both
+ * 8-byte aligned device arrays of g->count records) and d_pushed (device int64 [g->count]: the transitions pushed into learner l's
+ * ring so far) are all required.  p0->noise_kind is SHEMS_NOISE_GAUSS (d_hp[l].noise_mu + d_hp[l].noise_sigma * z, as without d_xp)
+ * or SHEMS_NOISE_OU: learner l's envs run X += theta_l (mu_l - X) dt_l + sigma_l sqrt(dt_l) z with mu_l / sigma_l from d_hp[l],
+ * theta_l / dt_l from d_xp[l], X = p0->ou_state[i] for the global env index i and the draw z of shems_act_step_dev.
+ * window->pos is ignored: the env at relative window position rel goes to slot (d_pushed[l] + rel) mod mem_size_l of learner l's
+ * ring.  window->count must not exceed the smallest mem_size and every record must have passed shems_group_xparams_check: both are the
+ * caller's preconditions (the records are device memory, the entry point cannot read them).  The device clamps mem_size to
+ * 1..ring0->capacity and d_pushed[l] to >= 0 only so that no slot outside the ring arrays is written; with a violated precondition
+ * the push lands in a wrong slot without any error -- the clamp makes that memory-safe, not right.  The kernels never write d_pushed. */
+int shems_act_step_group_x_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
+                               const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, float *d_a,
+                               double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream);
+/* shems_wide_act_step_group_dev in the same way (DDPG.jl:49-55, 157-158; input.jl:64, 140). */
+int shems_wide_act_step_group_x_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
+                                    const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, float *d_ws,
+                                    float *d_a, double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window,
+                                    void *stream);
+/* shems_ddpg_group_update_tp with per-learner ring lengths (input.jl:64, 140; getData, MPS:31-42): learner l samples
+ * x mod min(d_pushed[l], d_xp[l].mem_size) where shems_ddpg_group_update_tp samples x mod ring_len.  d_hp, d_xp and d_pushed are
+ * required.  Every learner's length must be >= 1: that is the caller's precondition (the arrays are device memory; the device clamps
+ * the length to 1..ring0->capacity, so a violated precondition samples slot 0 without any error -- memory-safe and free of a division
+ * by zero, but not right). */
+int shems_ddpg_group_update_tp_x(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *t,
+                                 const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, uint64_t seed,
+                                 uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
+                                 double bp2_act, int32_t flags, void *stream);
+/* shems_wide_group_update in the same way (input.jl:64, 140; DDPG.jl:121-145). */
+int shems_wide_group_update_x(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
+                              const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, int32_t max_batch,
+                              uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act,
+                              double bp1_act, double bp2_act, void *stream);
 /* min_max_buffer for every learner of the group (learner l: Philox key seed + l). */
 int shems_minmax_group_dev(const shems_replay *ring0, const shems_group *g, int64_t ring_len, int64_t count,
                            uint64_t seed, float *d_s_min0, float *d_s_max0, void *stream);

@@ -154,8 +154,10 @@ __device__ __forceinline__ void gshift(shems_replay &r, int64_t off)
 
 // grid (5, learners): workgroup 0 samples / gathers / normalises and freezes the output layers, workgroups 1..4 pack one network's
 // frozen layer-1 image each (one launch of 2 000 short workgroups instead of 400 long ones: 49 -> ~10 us at 400 learners)
-template <bool HP>
-__device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, const int l, const shems_group_hparams *hp)
+// XP (shems_ddpg_group_update_tp_x): learner l's ring length is min(pushed[l], xp[l].mem_size) in place of A.ring_len
+template <bool HP, bool XP = false>
+__device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, const int l, const shems_group_hparams *hp,
+                                          const shems_group_xparams *xp = nullptr, const int64_t *pushed = nullptr)
 {
     const int tid = threadIdx.x;
     const int64_t off = (int64_t)l * A.gstride;
@@ -183,11 +185,14 @@ __device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, con
     }
     if constexpr (HP) d.batch = hp_batch(hp[l]);              // the first batch_l draws of the same stream are live
     const uint64_t seed = A.seed + (uint64_t)l;               // learner l: Philox key seed + l (as the latency form)
+    int64_t ring_len = A.ring_len;
+    if constexpr (XP)                                         // clamped to 1..capacity: no division by zero, no slot outside the arrays
+        ring_len = min(max(min(pushed[l], (int64_t)xp[l].mem_size), (int64_t)1), ring.capacity);
     if (tid < BP) {
         const int m = tid;
         const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)seed, (uint32_t)(seed >> 32));
         const uint32_t w = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
-        const int64_t j = (int64_t)(w % (uint32_t)A.ring_len);
+        const int64_t j = (int64_t)(w % (uint32_t)ring_len);
         const bool live = m < d.batch;
         float sv[SIN], s2v[SIN], lo[SIN], hi[SIN];
 #pragma unroll
@@ -1024,6 +1029,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 
 // ---- the same launches with per-learner hyper-parameters (shems_ddpg_group_update_tp with d_hp): own names, the bodies above with HP = true ----
 __global__ __launch_bounds__(256) void k_tp_prep_hp(PrepArgs A, const shems_group_hparams *hp) { prep_body<true>(A, blockIdx.x, blockIdx.y, hp); }
+// (shems_ddpg_group_update_tp_x: the sampler with per-learner ring lengths; the other seven launches are the *_hp kernels)
+__global__ __launch_bounds__(256) void k_tp_prep_x(PrepArgs A, const shems_group_hparams *hp, const shems_group_xparams *xp, const int64_t *pushed)
+{
+    prep_body<true, true>(A, blockIdx.x, blockIdx.y, hp, xp, pushed);
+}
 template <bool QG, int NTL, bool TL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTL == 4 ? 3 : 4, 4))) void k_tp_fwd_hp(FwdArgs A, const shems_group_hparams *hp)
 {
@@ -1158,12 +1168,15 @@ static int check_group_tp(const shems_group *g, const char *fn)
 
 // t == null: every array in Flux order (round 5's form); else the layer-2 state of both networks lives in the tiled regions.
 // HP: learner l's batch / gamma / tau / eta from hp[l] (device), the *_hp kernels; d->batch / gamma / tau and eta_* are not used.
+// xp / pushed (HP only, shems_ddpg_group_update_tp_x): per-learner ring lengths on the device; ring_len is not used then.
 template <bool TL, bool HP>
 static int group_update_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, const shems_group_hparams *hp,
                            int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
-                           double bp2_act, int32_t flags, void *stream)
+                           double bp2_act, int32_t flags, void *stream, const shems_group_xparams *xp = nullptr, const int64_t *pushed = nullptr)
 {
-    const char *fn = "shems_ddpg_group_update_tp";
+    const char *fn = xp ? "shems_ddpg_group_update_tp_x" : "shems_ddpg_group_update_tp";
+    if (xp && (((uintptr_t)xp | (uintptr_t)pushed) & 7) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: d_xp and d_pushed must be 8-byte aligned device arrays of count records", fn);
     if (int rc = check_group_tp(g, fn)) return rc;
     if (!d || !d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
         !d->s_min || !d->s_max || !d->ws || !d->losses)
@@ -1221,7 +1234,8 @@ static int group_update_tp(const shems_ddpg *d, const shems_replay *ring, const 
         if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, hp);
         else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
     };
-    launch(k_tp_prep, k_tp_prep_hp, dim3(5, L), 0, U.pa);
+    if (HP && xp) hipLaunchKernelGGL(k_tp_prep_x, dim3(5, L), dim3(256), 0, st, U.pa, hp, xp, pushed);
+    else launch(k_tp_prep, k_tp_prep_hp, dim3(5, L), 0, U.pa);
     // Few learners: the shapes with twice the workgroups (P1 on 64-wide n-tiles, P3 / P6 on 32-wide k-tiles).  Below kNarrowBelow learners
     // the wide shapes leave CUs without work (P3 at 32 learners: 128 workgroups); measured per grouped update, wide / narrow: 32 learners
     // 247 / 226 us, 48 learners 322 / 320, 64 learners 362 / 372, 128 learners 669 / 695 (profiles/NOTES.md, round-5 log).
@@ -1243,9 +1257,21 @@ extern "C" int shems_ddpg_group_update_tp(const shems_ddpg *d, const shems_repla
                                           double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream)
 {
     auto *update = t ? (d_hp ? group_update_tp<true, true> : group_update_tp<true, false>) : (d_hp ? group_update_tp<false, true> : group_update_tp<false, false>);
-    return update(d, ring, g, t, d_hp, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags, stream);
+    return update(d, ring, g, t, d_hp, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags, stream, nullptr, nullptr);
 }
 
+extern "C" int shems_ddpg_group_update_tp_x(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
+                                            const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, uint64_t seed,
+                                            uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
+                                            double bp2_act, int32_t flags, void *stream)
+{
+    if (!d_hp || !d_xp || !d_pushed) return set_error(SHEMS_ERR_ARG, "shems_ddpg_group_update_tp_x: d_hp, d_xp and d_pushed are all required");
+    auto *update = t ? group_update_tp<true, true> : group_update_tp<false, true>;
+    return update(d, ring, g, t, d_hp, 1, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags, stream, d_xp, d_pushed);
+}
+
+static_assert(sizeof(shems_group_xparams) == 16 && offsetof(shems_group_xparams, ou_dt) == 4 && offsetof(shems_group_xparams, mem_size) == 8 &&
+              offsetof(shems_group_xparams, reserved) == 12, "shems_group_xparams: 16 bytes, the layout of include/shems_hip.h and group.XParams");
 static_assert(sizeof(shems_group_hparams) == 40 && offsetof(shems_group_hparams, gamma) == 16 && offsetof(shems_group_hparams, noise_mu) == 24 &&
               offsetof(shems_group_hparams, batch) == 32, "shems_group_hparams: 40 bytes, the layout of include/shems_hip.h and group.HParams");
 
@@ -1263,6 +1289,22 @@ static int hparams_check(const char *fn, const shems_group_hparams *hp, int32_t 
         if (!(std::isfinite(h.noise_sigma) && h.noise_sigma >= 0.0f))
             return set_error(SHEMS_ERR_ARG, "%s: learner %d: noise_sigma %g must be finite and >= 0", fn, l, (double)h.noise_sigma);
         if (h.reserved != 0) return set_error(SHEMS_ERR_ARG, "%s: learner %d: reserved must be 0", fn, l);
+    }
+    return SHEMS_OK;
+}
+extern "C" int shems_group_xparams_check(const shems_group_xparams *xp, int32_t count, int64_t capacity)
+{
+    const char *fn = "shems_group_xparams_check";
+    if (!xp || count < 1) return set_error(SHEMS_ERR_ARG, "%s: need count >= 1 records", fn);
+    if (capacity < 1 || capacity > INT32_MAX) return set_error(SHEMS_ERR_ARG, "%s: capacity %lld outside 1..2^31 - 1", fn, (long long)capacity);
+    for (int32_t l = 0; l < count; ++l) {
+        const shems_group_xparams &x = xp[l];
+        if (!(std::isfinite(x.ou_theta) && x.ou_theta >= 0.0f))
+            return set_error(SHEMS_ERR_ARG, "%s: learner %d: ou_theta %g must be finite and >= 0", fn, l, (double)x.ou_theta);
+        if (!(std::isfinite(x.ou_dt) && x.ou_dt > 0.0f)) return set_error(SHEMS_ERR_ARG, "%s: learner %d: ou_dt %g must be finite and > 0", fn, l, (double)x.ou_dt);
+        if (x.mem_size < 1 || x.mem_size > capacity)
+            return set_error(SHEMS_ERR_ARG, "%s: learner %d: mem_size %d outside 1..%lld", fn, l, x.mem_size, (long long)capacity);
+        if (x.reserved != 0) return set_error(SHEMS_ERR_ARG, "%s: learner %d: reserved must be 0", fn, l);
     }
     return SHEMS_OK;
 }

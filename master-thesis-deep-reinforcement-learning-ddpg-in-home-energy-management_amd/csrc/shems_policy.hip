@@ -244,10 +244,14 @@ __device__ __forceinline__ TailPre tailpre_load(const float *lds)
 // remember (DDPG.jl:148-184, 199-229).  Returns the env's reward (0 when nothing was stepped).
 // obs_lds: the env's 9 raw observations in LDS (the caller staged them), or null = read them from the view.
 // pre_lds: the env's TailPre block in LDS (the caller fetched it ahead), or null = draw / read in place.
-// HP (shems_act_step_group_dev with d_hp): the Gaussian noise of learner l's envs is hp[l].noise_mu + hp[l].noise_sigma * z.
-template <bool HP = false>
+// HP = 1 (shems_act_step_group_dev with d_hp): the Gaussian noise of learner l's envs is hp[l].noise_mu + hp[l].noise_sigma * z.
+// HP = 2 (shems_act_step_group_x_dev, gx = d_xp / d_pushed): as 1, and the OU noise of learner l's envs runs with hp[l].noise_mu /
+// noise_sigma and xp[l].ou_theta / ou_dt; a remembered env goes to slot (pushed[l] + rel) mod xp[l].mem_size, A.win.pos is not read.
+struct GroupX { const shems_group_xparams *xp; const int64_t *pushed; };
+template <int HP = 0>
 __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, float p0, float p1, int64_t learner, int64_t goff,
-                                               const float *obs_lds, const float *pre_lds = nullptr, const shems_group_hparams *hp = nullptr)
+                                               const float *obs_lds, const float *pre_lds = nullptr, const shems_group_hparams *hp = nullptr,
+                                               const GroupX gx = GroupX{nullptr, nullptr})
 {
     double reward = 0.0;
     {
@@ -267,16 +271,24 @@ __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, floa
                 const float2 z = make_float2(__uint_as_float(nz.a), __uint_as_float(nz.b));
                 if (A.p.noise_kind == SHEMS_NOISE_OU) {                // DDPG.jl:49-55, 157-158
                     float2 X = reinterpret_cast<float2 *>(A.p.ou_state)[i];
-                    const float sdt = A.p.noise_sigma * sqrtf(A.p.ou_dt);
-                    X.x += A.p.ou_theta * (A.p.noise_mu - X.x) * A.p.ou_dt + sdt * z.x;
-                    X.y += A.p.ou_theta * (A.p.noise_mu - X.y) * A.p.ou_dt + sdt * z.y;
+                    if constexpr (HP == 2) {
+                        const float mu = hp[learner].noise_mu, sg = hp[learner].noise_sigma;
+                        const float th = gx.xp[learner].ou_theta, dt = gx.xp[learner].ou_dt;
+                        const float sdt = sg * sqrtf(dt);
+                        X.x += th * (mu - X.x) * dt + sdt * z.x;
+                        X.y += th * (mu - X.y) * dt + sdt * z.y;
+                    } else {
+                        const float sdt = A.p.noise_sigma * sqrtf(A.p.ou_dt);
+                        X.x += A.p.ou_theta * (A.p.noise_mu - X.x) * A.p.ou_dt + sdt * z.x;
+                        X.y += A.p.ou_theta * (A.p.noise_mu - X.y) * A.p.ou_dt + sdt * z.y;
+                    }
                     reinterpret_cast<float2 *>(A.p.ou_state)[i] = X;
                     p0 += X.x;
                     p1 += X.y;
                     nmean = 0.5f * (X.x + X.y);
                 } else {                                               // DDPG.jl:57-61, 159-160: Normal(mu, sigma_act)
                     float n0, n1;
-                    if constexpr (HP) {
+                    if constexpr (HP != 0) {
                         const float mu = hp[learner].noise_mu, sg = hp[learner].noise_sigma;
                         n0 = mu + sg * z.x; n1 = mu + sg * z.y;
                     } else {
@@ -327,7 +339,13 @@ __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, floa
                             ring.s = gsh(ring.s, goff); ring.a = gsh(ring.a, goff); ring.r = gsh(ring.r, goff);
                             ring.s2 = gsh(ring.s2, goff); ring.done = gsh(ring.done, goff);
                         }
-                        ring_push(ring, (A.win.pos + rel) % ring.capacity, s0, a0, a1, (float)reward, obs);
+                        if constexpr (HP == 2) {          // the learner's own push position and ring size (clamped: no slot outside the arrays)
+                            const int64_t cap = min(max((int64_t)gx.xp[learner].mem_size, (int64_t)1), ring.capacity);
+                            const int64_t pos = max(gx.pushed[learner], (int64_t)0);
+                            ring_push(ring, (pos + rel) % cap, s0, a0, a1, (float)reward, obs);
+                        } else {
+                            ring_push(ring, (A.win.pos + rel) % ring.capacity, s0, a0, a1, (float)reward, obs);
+                        }
                     }
                 }
             } else {
@@ -353,8 +371,8 @@ constexpr int free_keep(int c)
 
 // (every form a learner group can run is a body with a bool HP: the kernels of the shared entry points instantiate it with false, the
 // *_hp kernels -- own names, shems_act_step_group_dev with d_hp -- with true)
-template <int TM, int NW, int RD, bool HP>
-__device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_hparams *hp)
+template <int TM, int NW, int RD, int HP>
+__device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_hparams *hp, const GroupX gx = GroupX{nullptr, nullptr})
 {
     static_assert(NW == 4 && RD >= 2 && RD <= 4, "free-running form: 4 waves, ring of 2..4 chunks");
     constexpr int NT_ = 64 * NW;            // threads per workgroup
@@ -817,7 +835,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
             for (int j = 0; j < 2; ++j)
                 hs[hf][j] = ((RED_OF(4 * hf)[tid * 2 + j] + RED_OF(4 * hf + 1)[tid * 2 + j]) + RED_OF(4 * hf + 2)[tid * 2 + j]) + RED_OF(4 * hf + 3)[tid * 2 + j];
         const float p0 = tl[kH2P + kH2P * kOut + 0] + (hs[0][0] + hs[1][0]), p1 = tl[kH2P + kH2P * kOut + 1] + (hs[0][1] + hs[1][1]);   // b3 + (H0 + H1)
-        reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, PRE ? xP + tid * kPreDw : PRE2 ? w1 + tid * kPreDw : nullptr, hp);
+        reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, PRE ? xP + tid * kPreDw : PRE2 ? w1 + tid * kPreDw : nullptr, hp, gx);
     }
     PSTAMP(12);
 #ifndef SHEMS_STAMP_ACT
@@ -830,9 +848,11 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
 #endif
 }
 template <int TM, int NW, int RD>
-__global__ __launch_bounds__(64 * NW, NW / 4) void k_act(ActArgs A) { k_act_body<TM, NW, RD, false>(A, nullptr); }
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_act(ActArgs A) { k_act_body<TM, NW, RD, 0>(A, nullptr); }
 template <int TM, int NW, int RD>
-__global__ __launch_bounds__(64 * NW, NW / 4) void k_act_hp(ActArgs A, const shems_group_hparams *hp) { k_act_body<TM, NW, RD, true>(A, hp); }
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_act_hp(ActArgs A, const shems_group_hparams *hp) { k_act_body<TM, NW, RD, 1>(A, hp); }
+template <int TM, int NW, int RD>
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_act_x(ActArgs A, const shems_group_hparams *hp, GroupX gx) { k_act_body<TM, NW, RD, 2>(A, hp, gx); }
 
 // =====================================================================================================================
 // Column-group forms for small batches: k_actg<TM, NW, NS, RD>.
@@ -884,8 +904,8 @@ __device__ __forceinline__ void g_piece(const char *sbase, uint32_t voff, uint32
     }
 }
 
-template <int TM, int NW, int NS, int RD, bool HP>
-__device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X, const shems_group_hparams *hp)
+template <int TM, int NW, int NS, int RD, int HP>
+__device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X, const shems_group_hparams *hp, const GroupX gx = GroupX{nullptr, nullptr})
 {
     static_assert(NW * NS == 8 && (NW == 4 || NW == 8), "8 column groups per env tile: 8 waves, or two workgroups of 4");
 #ifdef SHEMS_STAMP_ACT
@@ -1185,7 +1205,7 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
     }
     GSTAMP(9, blockIdx.x == 0);
     GSTAMP(11, tile == 0 && fin);
-    if (fin) reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, xP + tid * kPreDw, hp);
+    if (fin) reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, xP + tid * kPreDw, hp, gx);
     GSTAMP(12, tile == 0 && fin);
 #ifndef SHEMS_STAMP_ACT
     if (NS == 1 && A.block_reward) {
@@ -1197,9 +1217,11 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
 #endif
 }
 template <int TM, int NW, int NS, int RD>
-__global__ __launch_bounds__(64 * NW) void k_actg(ActArgs A, ActSplit X) { k_actg_body<TM, NW, NS, RD, false>(A, X, nullptr); }
+__global__ __launch_bounds__(64 * NW) void k_actg(ActArgs A, ActSplit X) { k_actg_body<TM, NW, NS, RD, 0>(A, X, nullptr); }
 template <int TM, int NW, int NS, int RD>
-__global__ __launch_bounds__(64 * NW) void k_actg_hp(ActArgs A, ActSplit X, const shems_group_hparams *hp) { k_actg_body<TM, NW, NS, RD, true>(A, X, hp); }
+__global__ __launch_bounds__(64 * NW) void k_actg_hp(ActArgs A, ActSplit X, const shems_group_hparams *hp) { k_actg_body<TM, NW, NS, RD, 1>(A, X, hp); }
+template <int TM, int NW, int NS, int RD>
+__global__ __launch_bounds__(64 * NW) void k_actg_x(ActArgs A, ActSplit X, const shems_group_hparams *hp, GroupX gx) { k_actg_body<TM, NW, NS, RD, 2>(A, X, hp, gx); }
 
 // =====================================================================================================================
 // k_act2: the fused step for large batches with TWO workgroups resident per CU.
@@ -1228,8 +1250,8 @@ __device__ __forceinline__ void k2_piece(const char *sbase, uint32_t voff, uint3
     if (q == 0) glds16_asm<-1024>(sbase, voff, lds_base); else glds16_asm<0>(sbase, voff, lds_base);
 }
 
-template <bool HP>
-__device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_hparams *hp)
+template <int HP>
+__device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_hparams *hp, const GroupX gx = GroupX{nullptr, nullptr})
 {
     constexpr int TM = 2, BM = 64, NA = 4, NT_ = 256, HR = 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1490,7 +1512,7 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
                 hs[hf][j] = ((r0[tid * 2 + j] + r0[BM * kOut + tid * 2 + j]) + r1[tid * 2 + j]) + r1[BM * kOut + tid * 2 + j];
             }
         const float p0 = tl[kH2P + kH2P * kOut + 0] + (hs[0][0] + hs[1][0]), p1 = tl[kH2P + kH2P * kOut + 1] + (hs[0][1] + hs[1][1]);
-        reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, nullptr, xP + tid * kPreDw, hp);
+        reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, nullptr, xP + tid * kPreDw, hp, gx);
     }
 #ifndef SHEMS_STAMP_ACT
     if (A.block_reward) {
@@ -1501,16 +1523,22 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
     }
 #endif
 }
-__global__ __launch_bounds__(256, 2) void k_act2(ActArgs A) { k_act2_body<false>(A, nullptr); }
-__global__ __launch_bounds__(256, 2) void k_act2_hp(ActArgs A, const shems_group_hparams *hp) { k_act2_body<true>(A, hp); }
+__global__ __launch_bounds__(256, 2) void k_act2(ActArgs A) { k_act2_body<0>(A, nullptr); }
+__global__ __launch_bounds__(256, 2) void k_act2_hp(ActArgs A, const shems_group_hparams *hp) { k_act2_body<1>(A, hp); }
+__global__ __launch_bounds__(256, 2) void k_act2_x(ActArgs A, const shems_group_hparams *hp, GroupX gx) { k_act2_body<2>(A, hp, gx); }
 
-// hp != null (shems_act_step_group_dev with d_hp): the *_hp kernel of the same form
-static int launch_act2(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
+// hp != null (shems_act_step_group_dev with d_hp): the *_hp kernel of the same form; gx != null (shems_act_step_group_x_dev): its *_x kernel
+static int launch_act2(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr, const GroupX *gx = nullptr)
 {
     constexpr size_t lds = act2_lds_bytes();
     static_assert(lds <= 80 * 1024, "k_act2: two workgroups must fit a CU's 160 KB");
-    static std::atomic<uint64_t> optin{0}, optin_hp{0};
+    static std::atomic<uint64_t> optin{0}, optin_hp{0}, optin_x{0};
     const dim3 grid((unsigned)((a.m - a.m0 + 63) / 64));
+    if (gx) {
+        if (int rc = lds_optin(optin_x, reinterpret_cast<const void *>(&k_act2_x), (int)lds, "hipFuncSetAttribute(k_act2_x)")) return rc;
+        hipLaunchKernelGGL(k_act2_x, grid, dim3(256), lds, st, a, hp, *gx);
+        return hip_ok(hipGetLastError(), "k_act2_x launch");
+    }
     if (hp) {
         if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_act2_hp), (int)lds, "hipFuncSetAttribute(k_act2_hp)")) return rc;
         hipLaunchKernelGGL(k_act2_hp, grid, dim3(256), lds, st, a, hp);
@@ -1531,13 +1559,18 @@ static int pick_tm(int64_t m, int tm_max = 0)
 static int group_tm_max(int64_t envs_per_learner) { return envs_per_learner % 128 == 0 ? 4 : envs_per_learner % 64 == 0 ? 2 : 1; }
 
 template <int TM, int NW, int RD>
-static int launch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
+static int launch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr, const GroupX *gx = nullptr)
 {
     constexpr int BM = 32 * TM;
     const size_t lds = act_lds_bytes<TM, NW, RD>();
     static_assert(act_lds_bytes<TM, NW, RD>() <= 160 * 1024, "k_act: LDS image exceeds 160 KB");
-    static std::atomic<uint64_t> optin{0}, optin_hp{0};      // per device: see lds_optin
+    static std::atomic<uint64_t> optin{0}, optin_hp{0}, optin_x{0};      // per device: see lds_optin
     const unsigned grid = (unsigned)((a.m - a.m0 + BM - 1) / BM);
+    if (gx) {
+        if (int rc = lds_optin(optin_x, reinterpret_cast<const void *>(&k_act_x<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act_x)")) return rc;
+        hipLaunchKernelGGL((k_act_x<TM, NW, RD>), dim3(grid), dim3(64 * NW), lds, st, a, hp, *gx);
+        return hip_ok(hipGetLastError(), "k_act_x launch");
+    }
     if (hp) {
         if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_act_hp<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act_hp)")) return rc;
         hipLaunchKernelGGL((k_act_hp<TM, NW, RD>), dim3(grid), dim3(64 * NW), lds, st, a, hp);
@@ -1580,13 +1613,15 @@ static int split_scratch(hipStream_t st, ActSplit *out)
 }
 
 template <int TM, int NW, int NS, int RD>
-static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
+static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr, const GroupX *gx = nullptr)
 {
     constexpr int BM = 32 * TM;
     constexpr size_t lds = actg_lds_bytes<TM, NW, RD>();
     static_assert(lds <= 160 * 1024, "k_actg: LDS image exceeds 160 KB");
-    static std::atomic<uint64_t> optin{0}, optin_hp{0};      // per device: see lds_optin
-    if (hp) {
+    static std::atomic<uint64_t> optin{0}, optin_hp{0}, optin_x{0};      // per device: see lds_optin
+    if (gx) {
+        if (int rc = lds_optin(optin_x, reinterpret_cast<const void *>(&k_actg_x<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg_x)")) return rc;
+    } else if (hp) {
         if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_actg_hp<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg_hp)")) return rc;
     } else if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_actg<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg)")) return rc;
     const int64_t tiles = (a.m - a.m0 + BM - 1) / BM;
@@ -1596,8 +1631,12 @@ static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hpara
         if (split_scratch(st, &x) != SHEMS_OK) {
             // no exchange slab for this (device, stream) -- the 33rd distinct stream of a long-lived process, or hipMalloc failed: the
             // one-workgroup-per-tile form needs none and writes the same bytes
-            return launch_actg<1, 8, 1, RD>(a, st, hp);
+            return launch_actg<1, 8, 1, RD>(a, st, hp, gx);
         }
+    }
+    if (gx) {
+        hipLaunchKernelGGL((k_actg_x<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x, hp, *gx);
+        return hip_ok(hipGetLastError(), "k_actg_x launch");
     }
     if (hp) {
         hipLaunchKernelGGL((k_actg_hp<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x, hp);
@@ -1677,7 +1716,7 @@ static ActForm pick_act_form(int64_t cnt, int tm_max, int gcount, bool w2t, bool
 // in L2 than they win -- 151.9 against 145.7 us at 32 x 2 048 envs)
 static int act_tile_envs(int64_t m) { return act_form_tile_envs(pick_act_form(m, 0, 0, false, true)); }
 
-static int dispatch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr)
+static int dispatch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr, const GroupX *gx = nullptr)
 {
 #ifdef SHEMS_STAMP_ACT
     const bool want_sum = false;                              // stamp builds: block_reward is the stamp buffer
@@ -1686,14 +1725,14 @@ static int dispatch_act(const ActArgs &a, hipStream_t st, const shems_group_hpar
 #endif
     // envs of this launch a.m - a.m0 (a range launch: every form writes the same bytes)
     switch (pick_act_form(a.m - a.m0, a.tm_max, a.gcount, a.w2t != nullptr, want_sum)) {
-    case kAct2: return launch_act2(a, st, hp);
-    case kAct442: return launch_act<4, 4, 2>(a, st, hp);
-    case kAct242: return launch_act<2, 4, 2>(a, st, hp);
-    case kAct142: return launch_act<1, 4, 2>(a, st, hp);
-    case kAct143: return launch_act<1, 4, 3>(a, st, hp);
-    case kActg1422: return launch_actg<1, 4, 2, 2>(a, st, hp);
-    case kActg1423: return launch_actg<1, 4, 2, 3>(a, st, hp);
-    case kActg1813: return launch_actg<1, 8, 1, 3>(a, st, hp);
+    case kAct2: return launch_act2(a, st, hp, gx);
+    case kAct442: return launch_act<4, 4, 2>(a, st, hp, gx);
+    case kAct242: return launch_act<2, 4, 2>(a, st, hp, gx);
+    case kAct142: return launch_act<1, 4, 2>(a, st, hp, gx);
+    case kAct143: return launch_act<1, 4, 3>(a, st, hp, gx);
+    case kActg1422: return launch_actg<1, 4, 2, 2>(a, st, hp, gx);
+    case kActg1423: return launch_actg<1, 4, 2, 3>(a, st, hp, gx);
+    case kActg1813: return launch_actg<1, 8, 1, 3>(a, st, hp, gx);
     }
     return set_error(SHEMS_ERR_ARG, "dispatch_act: no form");
 }
@@ -1715,9 +1754,9 @@ __global__ __launch_bounds__(256) void k_act_tail(ActArgs A, const float *__rest
 
 // A learner group's tail (shems_wide_act_step_group_dev): env i is learner i / genvs's, whose b3, ring and (HP) noise record it uses;
 // its partials are at [learner][p][genvs][2].
-template <bool HP>
-__global__ __launch_bounds__(256) void k_act_tail_g(ActArgs A, const float *__restrict__ part, int n_part, const float *__restrict__ b3_0,
-                                                    const shems_group_hparams *hp)
+template <int HP>
+__device__ __forceinline__ void act_tail_g_body(const ActArgs &A, const float *__restrict__ part, int n_part, const float *__restrict__ b3_0,
+                                                const shems_group_hparams *hp, const GroupX gx = GroupX{nullptr, nullptr})
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= A.m) return;
@@ -1729,7 +1768,18 @@ __global__ __launch_bounds__(256) void k_act_tail_g(ActArgs A, const float *__re
         const float2 v = pp[(int64_t)p * A.genvs];
         p0 += v.x; p1 += v.y;
     }
-    act_env_tail<HP>(A, i, b3[0] + p0, b3[1] + p1, learner, goff, nullptr, nullptr, hp);
+    act_env_tail<HP>(A, i, b3[0] + p0, b3[1] + p1, learner, goff, nullptr, nullptr, hp, gx);
+}
+template <bool HP>
+__global__ __launch_bounds__(256) void k_act_tail_g(ActArgs A, const float *__restrict__ part, int n_part, const float *__restrict__ b3_0,
+                                                    const shems_group_hparams *hp)
+{
+    act_tail_g_body<HP ? 1 : 0>(A, part, n_part, b3_0, hp);
+}
+__global__ __launch_bounds__(256) void k_act_tail_gx(ActArgs A, const float *__restrict__ part, int n_part, const float *__restrict__ b3_0,
+                                                     const shems_group_hparams *hp, GroupX gx)
+{
+    act_tail_g_body<2>(A, part, n_part, b3_0, hp, gx);
 }
 
 static int wide_act(const ActArgs &a, int l1, int l2, float *d_ws, hipStream_t st)
@@ -1894,31 +1944,66 @@ static int group_act_args(const char *fn, const shems_view *v, const shems_act_p
     return attach_ring(fn, a, ring0, window, g->envs_per_learner);
 }
 
+// The *_x entry points' three arrays: all required; OU or Gaussian noise (the records hold no eps-greedy schedule).
+static int check_group_x(const char *fn, const shems_act_params *p0, const shems_group_hparams *d_hp, const shems_group_xparams *d_xp,
+                         const int64_t *d_pushed)
+{
+    if (!d_hp || !d_xp || !d_pushed) return set_error(SHEMS_ERR_ARG, "%s: d_hp, d_xp and d_pushed are all required", fn);
+    if ((((uintptr_t)d_hp | (uintptr_t)d_xp | (uintptr_t)d_pushed) & 7) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: d_hp, d_xp and d_pushed must be 8-byte aligned device arrays of count records", fn);
+    if (p0->noise_kind != SHEMS_NOISE_GAUSS && p0->noise_kind != SHEMS_NOISE_OU)
+        return set_error(SHEMS_ERR_ARG, "%s: per-learner noise is Gaussian or Ornstein-Uhlenbeck (noise_kind %d)", fn, p0->noise_kind);
+    return SHEMS_OK;
+}
+
+// shems_act_step_group_dev (gx == null) and shems_act_step_group_x_dev: one implementation
+static int act_step_group(const char *fn, const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
+                          const shems_group_hparams *d_hp, const GroupX *gx, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                          const shems_ring_window *window, void *stream)
+{
+    ActArgs a;
+    if (int rc = group_act_args(fn, v, p0, g, d_a, d_returns_acc, ring0, window, a)) return rc;
+    if (gx) {
+        if (int rc = check_group_x(fn, p0, d_hp, gx->xp, gx->pushed)) return rc;
+    } else {
+        if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+        if (d_hp && p0->noise_kind != SHEMS_NOISE_GAUSS)
+            return set_error(SHEMS_ERR_ARG, "%s: per-learner noise is Gaussian only (noise_kind %d)", fn, p0->noise_kind);
+    }
+    if (t && (!t->actor || ((uintptr_t)t->actor & 15) != 0))
+        return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t.actor must be a 16-byte aligned device pointer", fn);
+    a.w2t = t ? t->actor : nullptr;
+    return dispatch_act(a, (hipStream_t)stream, d_hp, gx);
+}
+
 int shems_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
                              const shems_group_hparams *d_hp, float *d_a, double *d_returns_acc, const shems_replay *ring0,
                              const shems_ring_window *window, void *stream)
 {
-    const char *fn = "shems_act_step_group_dev";
-    ActArgs a;
-    if (int rc = group_act_args(fn, v, p0, g, d_a, d_returns_acc, ring0, window, a)) return rc;
-    if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
-    if (d_hp && p0->noise_kind != SHEMS_NOISE_GAUSS)
-        return set_error(SHEMS_ERR_ARG, "%s: per-learner noise is Gaussian only (noise_kind %d)", fn, p0->noise_kind);
-    if (t && (!t->actor || ((uintptr_t)t->actor & 15) != 0))
-        return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t.actor must be a 16-byte aligned device pointer", fn);
-    a.w2t = t ? t->actor : nullptr;
-    return dispatch_act(a, (hipStream_t)stream, d_hp);
+    return act_step_group("shems_act_step_group_dev", v, p0, g, t, d_hp, nullptr, d_a, d_returns_acc, ring0, window, stream);
 }
 
-int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
-                                  const shems_group_hparams *d_hp, float *d_ws, float *d_a, double *d_returns_acc, const shems_replay *ring0,
-                                  const shems_ring_window *window, void *stream)
+int shems_act_step_group_x_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, const shems_group_w2t *t,
+                               const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, float *d_a,
+                               double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window, void *stream)
 {
-    const char *fn = "shems_wide_act_step_group_dev";
+    const GroupX gx{d_xp, d_pushed};
+    return act_step_group("shems_act_step_group_x_dev", v, p0, g, t, d_hp, &gx, d_a, d_returns_acc, ring0, window, stream);
+}
+
+// shems_wide_act_step_group_dev (gx == null) and shems_wide_act_step_group_x_dev: one implementation
+static int wide_act_step_group(const char *fn, const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
+                               const shems_group_hparams *d_hp, const GroupX *gx, float *d_ws, float *d_a, double *d_returns_acc,
+                               const shems_replay *ring0, const shems_ring_window *window, void *stream)
+{
     ActArgs a;
     if (int rc = group_act_args(fn, v, p0, g, d_a, d_returns_acc, ring0, window, a)) return rc;
-    if (p0->noise_kind != SHEMS_NOISE_GAUSS) return set_error(SHEMS_ERR_ARG, "%s: a group draws Gaussian noise only (noise_kind %d)", fn, p0->noise_kind);
-    if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (gx) {
+        if (int rc = check_group_x(fn, p0, d_hp, gx->xp, gx->pushed)) return rc;
+    } else {
+        if (p0->noise_kind != SHEMS_NOISE_GAUSS) return set_error(SHEMS_ERR_ARG, "%s: a group draws Gaussian noise only (noise_kind %d)", fn, p0->noise_kind);
+        if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    }
     if (g->count > 65535) return set_error(SHEMS_ERR_ARG, "%s: at most 65535 learners", fn);
     if (!d_ws || ((uintptr_t)d_ws & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: 16-byte aligned workspace required", fn);
     hipStream_t st = (hipStream_t)stream;
@@ -1928,9 +2013,26 @@ int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p
                                       &n_part, st)) return rc;
     const float *b3 = p0->actor + ((int64_t)kIn * l1 + l1 + (int64_t)l1 * l2 + l2 + (int64_t)l2 * kOut);
     const dim3 grid((unsigned)((a.m + 255) / 256));
-    if (d_hp) hipLaunchKernelGGL(k_act_tail_g<true>, grid, dim3(256), 0, st, a, part, n_part, b3, d_hp);
+    if (gx) hipLaunchKernelGGL(k_act_tail_gx, grid, dim3(256), 0, st, a, part, n_part, b3, d_hp, *gx);
+    else if (d_hp) hipLaunchKernelGGL(k_act_tail_g<true>, grid, dim3(256), 0, st, a, part, n_part, b3, d_hp);
     else hipLaunchKernelGGL(k_act_tail_g<false>, grid, dim3(256), 0, st, a, part, n_part, b3, d_hp);
-    return hip_ok(hipGetLastError(), "k_act_tail_g launch");
+    return hip_ok(hipGetLastError(), gx ? "k_act_tail_gx launch" : "k_act_tail_g launch");
+}
+
+int shems_wide_act_step_group_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
+                                  const shems_group_hparams *d_hp, float *d_ws, float *d_a, double *d_returns_acc, const shems_replay *ring0,
+                                  const shems_ring_window *window, void *stream)
+{
+    return wide_act_step_group("shems_wide_act_step_group_dev", v, p0, g, l1, l2, d_hp, nullptr, d_ws, d_a, d_returns_acc, ring0, window, stream);
+}
+
+int shems_wide_act_step_group_x_dev(const shems_view *v, const shems_act_params *p0, const shems_group *g, int32_t l1, int32_t l2,
+                                    const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, float *d_ws,
+                                    float *d_a, double *d_returns_acc, const shems_replay *ring0, const shems_ring_window *window,
+                                    void *stream)
+{
+    const GroupX gx{d_xp, d_pushed};
+    return wide_act_step_group("shems_wide_act_step_group_x_dev", v, p0, g, l1, l2, d_hp, &gx, d_ws, d_a, d_returns_acc, ring0, window, stream);
 }
 
 }  // extern "C"

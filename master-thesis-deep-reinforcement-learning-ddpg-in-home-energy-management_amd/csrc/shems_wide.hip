@@ -295,6 +295,19 @@ __global__ __launch_bounds__(WPMAX) void k_wprep_g(WGroupArgs A)
     const WPrep p{r, A.ring_len, 0, 0, A.seed + (uint64_t)l, A.tick, wg_batch(A, l), A.d0.s_min + l * A.stride, A.d0.s_max + l * A.stride, wg_ws(A, l)};
     wprep_row(p, threadIdx.x);
 }
+// shems_wide_group_update_x: learner l's ring length is min(pushed[l], xp[l].mem_size) in place of A.ring_len (a kernel of its own, so
+// that k_wprep_g stays the code it was)
+__global__ __launch_bounds__(WPMAX) void k_wprep_gx(WGroupArgs A, const shems_group_xparams *xp, const int64_t *pushed)
+{
+    const int l = blockIdx.x;
+    const int64_t off = (int64_t)l * A.stride * 4;
+    shems_replay r = A.ring0;
+    r.s = gsh(r.s, off); r.a = gsh(r.a, off); r.r = gsh(r.r, off); r.s2 = gsh(r.s2, off); r.done = gsh(r.done, off);
+    // clamped to 1..capacity: no division by zero, no slot outside the arrays
+    const int64_t ring_len = min(max(min(pushed[l], (int64_t)xp[l].mem_size), (int64_t)1), r.capacity);
+    const WPrep p{r, ring_len, 0, 0, A.seed + (uint64_t)l, A.tick, wg_batch(A, l), A.d0.s_min + l * A.stride, A.d0.s_max + l * A.stride, wg_ws(A, l)};
+    wprep_row(p, threadIdx.x);
+}
 // a = tanh(P) for the live rows -> a_out [WBP][2] (may be null) and the action columns of a [WBP][11] critic input; workgroup 0: the
 // target actor's head into [s'; a'], workgroup 1: the actor's into a_pi and [s; a_pi]
 __device__ __forceinline__ void wtanh_cat_row(const float *__restrict__ P0, float *__restrict__ a0_out, float *__restrict__ cat0,
@@ -582,11 +595,12 @@ int shems_wide_actor_apply_pub(const shems_ddpg *d, int32_t l1, int32_t l2, doub
 
 /* replay() for every learner of a group on the wide path: the launches of shems_wide_critic_grad_ex, _critic_apply, _actor_grad and
    _actor_apply_pub, each once for all learners (grid z / x = learner). */
-int shems_wide_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
-                            const shems_group_hparams *d_hp, int32_t max_batch, int64_t ring_len, uint64_t seed, uint32_t tick,
-                            double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, void *stream)
+// shems_wide_group_update (d_xp == null) and shems_wide_group_update_x (per-learner ring lengths on the device; ring_len is not used)
+static int wide_group_update(const char *fn, const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
+                             const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, int32_t max_batch,
+                             int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act,
+                             double bp1_act, double bp2_act, void *stream)
 {
-    const char *fn = "shems_wide_group_update";
     if (int rc = check_shape(l1, l2, fn)) return rc;
     if (!d0 || !d0->actor || !d0->critic || !d0->actor_t || !d0->critic_t || !d0->m_actor || !d0->v_actor || !d0->m_critic ||
         !d0->v_critic || !d0->grad_actor || !d0->grad_critic || !d0->s_min || !d0->s_max || !d0->ws || !d0->losses)
@@ -610,7 +624,8 @@ int shems_wide_group_update(const shems_ddpg *d0, const shems_replay *ring0, con
     const WGroupArgs A{*d0, *ring0, stride, ring_len, seed, tick, l1, l2, P, max_batch, d_hp};
     const WWs w = wws(d0->ws, l1, l2, P);                     // learner 0's carve; learner l's is the same + l * stride
     // critic gradient (shems_wide_critic_grad_ex)
-    hipLaunchKernelGGL(k_wprep_g, dim3((unsigned)L), dim3((unsigned)P), 0, st, A);
+    if (d_xp) hipLaunchKernelGGL(k_wprep_gx, dim3((unsigned)L), dim3((unsigned)P), 0, st, A, d_xp, d_pushed);
+    else hipLaunchKernelGGL(k_wprep_g, dim3((unsigned)L), dim3((unsigned)P), 0, st, A);
     const WNet c = wnet(d0->critic, WCIN, l1, l2, 1), a = wnet(d0->actor, WSIN, l1, l2, WAIN);
     const Fwd ft = fwd_of(wnet(d0->actor_t, WSIN, l1, l2, WAIN), w.XS2, w.T1, w.T2, w.PT, P), fc = fwd_of(c, w.XC, w.H1c, w.H2c, w.Q, P),
               fa = fwd_of(a, w.XS, w.H1a, w.H2a, w.PA, P);
@@ -631,6 +646,27 @@ int shems_wide_group_update(const shems_ddpg *d0, const shems_replay *ring0, con
     if (int rc = net_backward(st, a, w.XS, w.H1a, w.H2a, w.D3, d0->grad_actor, w.G1, w.G2, nullptr, w.ONES, P, &grp)) return rc;
     return adam_soft_sweep_group(d0->actor, d0->grad_actor, d0->m_actor, d0->v_actor, d0->actor_t, (int)wnet_size(WSIN, l1, l2, WAIN), eta_act,
                                  bp1_act, bp2_act, d0->tau, L, stride * 4, d_hp, false, st);
+}
+
+int shems_wide_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
+                            const shems_group_hparams *d_hp, int32_t max_batch, int64_t ring_len, uint64_t seed, uint32_t tick,
+                            double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, void *stream)
+{
+    return wide_group_update("shems_wide_group_update", d0, ring0, g, l1, l2, d_hp, nullptr, nullptr, max_batch, ring_len, seed, tick, eta_crit,
+                             bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, stream);
+}
+
+int shems_wide_group_update_x(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
+                              const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, int32_t max_batch,
+                              uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act,
+                              double bp1_act, double bp2_act, void *stream)
+{
+    const char *fn = "shems_wide_group_update_x";
+    if (!d_hp || !d_xp || !d_pushed) return set_error(SHEMS_ERR_ARG, "%s: d_hp, d_xp and d_pushed are all required", fn);
+    if ((((uintptr_t)d_xp | (uintptr_t)d_pushed) & 7) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: d_xp and d_pushed must be 8-byte aligned device arrays of count records", fn);
+    return wide_group_update(fn, d0, ring0, g, l1, l2, d_hp, d_xp, d_pushed, max_batch, 1, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act,
+                             bp1_act, bp2_act, stream);
 }
 
 /* the s rows of the minibatch the last shems_wide_critic_grad_ex sampled (adapt_param_noise!, DDPG.jl:74-87) */

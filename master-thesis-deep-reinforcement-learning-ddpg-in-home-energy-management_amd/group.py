@@ -37,8 +37,16 @@ class HParams(C.Structure):            # shems_group_hparams: one learner's reco
 
 assert C.sizeof(HParams) == 40
 
+
+class XParams(C.Structure):            # shems_group_xparams: one learner's exploration / ring-size record, beside its HParams
+    _fields_ = [("ou_theta", C.c_float), ("ou_dt", C.c_float), ("mem_size", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(XParams) == 16
+
 # keys of a per-learner mapping (LearnerGroup(hparams=...)); a missing key takes today's default
-HPARAM_KEYS = ("eta_act", "eta_crit", "gamma", "tau", "sigma", "mu", "batch", "hidden", "noise_type", "mem_size")
+HPARAM_KEYS = ("eta_act", "eta_crit", "gamma", "tau", "sigma", "mu", "batch", "hidden", "noise_type", "mem_size", "theta")
+GROUP_NOISE = ("gn", "ou")             # the action noise a group can draw (one kind for the whole group); "en" / "pn" run on a single Agent
 MAX_GROUP_BATCH = 128                  # one update pass holds 128 minibatch columns (the group kernels have no sub-batch path)
 MAX_WIDE_BATCH = 256                   # the wide form (form="wide"): one pass of P = max(128, round_up_32(max batch)) columns
 WIDE_HIDDEN = (300, 600)               # the wide form's default padded hidden size: the tuned grid's widest point
@@ -49,10 +57,12 @@ def hparam_defaults(sigma=NOISE_SIGMA):
     return dict(eta_act=ETA_ACT, eta_crit=ETA_CRIT, gamma=GAMMA, tau=TAU, sigma=sigma, mu=0.0, batch=BATCH_SIZE, hidden=(L1, L2))
 
 
-def _hparams_records(count, hparams, sigma, capacity, width=None):
+def _hparams_records(count, hparams, sigma, capacity, width=None, noise_type="gn", theta=0.15):
     """Per-learner mappings -> (full dicts, ctypes array of HParams).  Everything the group kernels cannot hold is refused here, naming the
     learner; the records themselves go through shems_group_hparams_check.  Host only: no device work.
-    width: the wide form's padded hidden size -- batch up to 256 and hidden up to `width` (shems_group_hparams_check_wide)."""
+    width: the wide form's padded hidden size -- batch up to 256 and hidden up to `width` (shems_group_hparams_check_wide).
+    noise_type, theta: the group's (a record's noise_type must be the group's; its theta, "ou" groups only, defaults to the group's).
+    The full dicts also carry noise_type, theta and mem_size (default: capacity) for _xparams_records."""
     hparams = list(hparams)
     if len(hparams) != count:
         raise ValueError(f"hparams holds {len(hparams)} records for a group of {count} learners")
@@ -64,12 +74,17 @@ def _hparams_records(count, hparams, sigma, capacity, width=None):
         if unknown:
             raise ValueError(f"hparams[{l}]: unknown keys {unknown} (known: {', '.join(HPARAM_KEYS)})")
         r = hparam_defaults(sigma)
-        r.update({k: v for k, v in h.items() if k not in ("noise_type", "mem_size")})
-        if h.get("noise_type", "gn") != "gn":
-            raise ValueError(f"hparams[{l}]: noise_type {h['noise_type']!r}: a learner group draws Gaussian action noise only (\"gn\")")
-        if "mem_size" in h and int(h["mem_size"]) != capacity:
-            raise ValueError(f"hparams[{l}]: mem_size {h['mem_size']} differs from the group's ring capacity {capacity}: "
-                             "every learner's ring has the same capacity")
+        r.update({k: v for k, v in h.items() if k not in ("noise_type", "mem_size", "theta")})
+        if h.get("noise_type", noise_type) != noise_type:
+            raise ValueError(f"hparams[{l}]: noise_type {h['noise_type']!r}: every learner of a group draws the group's kind of action noise "
+                             f"(LearnerGroup(noise_type={noise_type!r}))")
+        if "theta" in h and noise_type != "ou":
+            raise ValueError(f"hparams[{l}]: theta {h['theta']} belongs to Ornstein-Uhlenbeck noise: the group draws noise_type={noise_type!r}")
+        if "mem_size" in h and not 1 <= int(h["mem_size"]) <= capacity:
+            raise ValueError(f"hparams[{l}]: mem_size {h['mem_size']} outside 1 .. {capacity}, the ring capacity every learner's slab is "
+                             "carved for (LearnerGroup(capacity=...))")
+        r["noise_type"], r["mem_size"] = noise_type, int(h.get("mem_size", capacity))
+        r["theta"] = float(np.float32(h.get("theta", theta)))
         if width is None and int(r["batch"]) > MAX_GROUP_BATCH:
             raise ValueError(f"hparams[{l}]: batch {r['batch']} > {MAX_GROUP_BATCH}: the group kernels hold one 128-column update pass")
         if width is not None and int(r["batch"]) > MAX_WIDE_BATCH:
@@ -95,6 +110,15 @@ def _hparams_records(count, hparams, sigma, capacity, width=None):
     if rc != _capi.OK:
         raise ValueError(L.shems_last_error().decode("utf-8", "replace"))
     return full, arr
+
+
+def _xparams_records(full, capacity, dt):
+    """The XParams array beside the HParams of _hparams_records' full dicts, through shems_group_xparams_check.  Host only."""
+    arr = (XParams * len(full))(*[XParams(r["theta"], float(np.float32(dt)), r["mem_size"], 0) for r in full])
+    L = _declare_group()
+    if L.shems_group_xparams_check(arr, len(full), int(capacity)) != _capi.OK:
+        raise ValueError(L.shems_last_error().decode("utf-8", "replace"))
+    return arr
 
 
 def _wide_width(hparams, hidden):
@@ -140,6 +164,30 @@ def tuned_grid(job_ids, seeds=1, chargers=1, wide=False):
     return records, points, skipped
 
 
+def input_grid(job_ids, seeds=1, chargers=1):
+    """tuned_grid's twin for the template "input" (RL-SHEMS/input.jl:58-100): 27 points over MEM_SIZE, BATCH_SIZE and (L1, L2, gamma,
+    sigma, theta), every one with noise_type = "ou".  Returns (records, points): `records` holds len(points) x seeds x chargers mappings
+    (eta_*, gamma, tau, sigma, mu = 0, theta, batch, hidden, mem_size, noise_type = "ou"), learner (p * seeds + s) * chargers + c running
+    point points[p], for LearnerGroup(form="wide", noise_type="ou", capacity=INPUT_CAPACITY, hparams=records).  Only the 27 codes 00-26
+    are points of the grid: anything else is refused."""
+    from .main import RunConfig, set_hyperparameters
+    records, points = [], []
+    for jid in job_ids:
+        jid = str(jid)
+        if not jid.isdigit() or not 0 <= int(jid[-2:]) <= 26:
+            raise ValueError(f"JOB_ID {jid!r}: the input template's grid has the 27 points 00 .. 26 (three ternary digits)")
+        cfg = set_hyperparameters(RunConfig(job_id=jid.zfill(2), task_id="0", gpu_id=0, template="input"))
+        rec = dict(eta_act=float(np.float32(cfg.eta_act)), eta_crit=float(np.float32(cfg.eta_crit)), gamma=float(np.float32(cfg.gamma)),
+                   tau=float(np.float32(cfg.tau)), sigma=float(cfg.sigma), mu=0.0, theta=float(cfg.theta), batch=int(cfg.BATCH_SIZE),
+                   hidden=(cfg.L1, cfg.L2), mem_size=int(cfg.MEM_SIZE), noise_type=cfg.noise_type)
+        points.append(jid)
+        records += [dict(rec) for _ in range(int(seeds) * int(chargers))]
+    return records, points
+
+
+INPUT_ALL = tuple(f"{c:02d}" for c in range(27))       # every point of the input template's grid
+INPUT_CAPACITY = 30000                                 # its largest MEM_SIZE: what a group of the grid carves every ring for
+
 TUNED_RUNNABLE = tuple(f"{c:02d}" for c in range(81) if c // 27 != 2 and (c // 3) % 3 != 0)   # the 36 points tuned_grid keeps
 TUNED_ALL = tuple(f"{c:02d}" for c in range(81))                                             # every point: tuned_grid(..., wide=True)
 
@@ -179,6 +227,16 @@ def _declare_group():
     for fn in ("shems_group_hparams_check", "shems_group_hparams_check_wide",
                "shems_wide_group_workspace_floats", "shems_wide_group_update", "shems_wide_act_step_group_dev"):
         getattr(L, fn).restype = C.c_int
+    PX, u64, u32 = C.POINTER(XParams), C.c_uint64, C.c_uint32
+    L.shems_group_xparams_check.argtypes = [PX, i32, i64]
+    L.shems_act_step_group_x_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, PT, vp, vp, vp, vp, vp, PR, C.POINTER(RingWindow), vp]
+    L.shems_wide_act_step_group_x_dev.argtypes = [C.POINTER(_capi.View), C.POINTER(ActParams), PG, i32, i32, vp, vp, vp, vp, vp, vp, PR,
+                                                  C.POINTER(RingWindow), vp]
+    L.shems_ddpg_group_update_tp_x.argtypes = [PD, PR, PG, PT, vp, vp, vp, u64, u32, dbl, dbl, dbl, dbl, dbl, dbl, i32, vp]
+    L.shems_wide_group_update_x.argtypes = [PD, PR, PG, i32, i32, vp, vp, vp, i32, u64, u32, dbl, dbl, dbl, dbl, dbl, dbl, vp]
+    for fn in ("shems_group_xparams_check", "shems_act_step_group_x_dev", "shems_wide_act_step_group_x_dev", "shems_ddpg_group_update_tp_x",
+               "shems_wide_group_update_x"):
+        getattr(L, fn).restype = C.c_int
     L.shems_group_eval_best_dev.argtypes = [PD, PG, PT, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]
     L.shems_group_eval_best_dev.restype = C.c_int
     for fn in ("shems_act_step_group_dev", "shems_ddpg_group_critic_grad", "shems_ddpg_group_critic_apply",
@@ -211,7 +269,7 @@ class LearnerGroup:
     TP_MIN_LEARNERS = 16
 
     def __init__(self, count, envs_per_learner, seed=1231, rng_seed=None, capacity=MEM_SIZE, sigma=NOISE_SIGMA, device=None, form=None, tiled=None,
-                 hparams=None, hidden=None):
+                 hparams=None, hidden=None, noise_type="gn", theta=0.15, dt=1e-2):
         """tiled (throughput form only; default on, SHEMS_GROUP_TILED=0 switches it off): the layer-2 state of both networks (W2, its
         ADAM moments, the target's W2) is kept in the TILED working layout (shems_group_w2t, include/shems_hip.h) while the group trains:
         one contiguous 64 KB piece per 64 x 64 tile for the update's W2-gradient / ADAM launches (4.78 against 3.85 TB/s), read from
@@ -224,7 +282,20 @@ class LearnerGroup:
         the keys of HPARAM_KEYS (eta_act, eta_crit, gamma, tau, sigma, mu, batch, hidden; a missing key takes today's default): the group
         then runs the throughput form whatever its size, with the records as the entry points' d_hp (shems_ddpg_group_update_tp,
         shems_act_step_group_dev), and learners[l] carries learner l's values.  The records are checked and uploaded once, here.
-        Refused, naming the learner: batch > 128, hidden wider than (250, 500), noise_type other than "gn", a per-learner mem_size.
+        Refused, naming the learner: batch > 128, hidden wider than (250, 500), a noise_type other than the group's, theta in a "gn"
+        group, mem_size outside 1 .. capacity.
+
+        noise_type, theta, dt (as Agent's): the action noise of the whole group, "gn" (GNoise) or "ou" (OUNoise, DDPG.jl:49-55: X +=
+        theta (mu - X) dt + sigma sqrt(dt) z per env, the state in `ou_state` [n_envs][2], zeros at first and kept across episodes; a
+        record's theta / sigma / mu are its learner's).  "en" and "pn" stay a single Agent's.  A record's mem_size (1 .. capacity) is
+        its learner's ring size: rings[l] is a ReplayRing(mem_size_l) over the first mem_size_l slots of the ring arrays, which stay
+        carved for `capacity`.  An "ou" group, or one with a mem_size record, runs the throughput or the wide form on the *_x entry
+        points (shems_act_step_group_x_dev, shems_ddpg_group_update_tp_x and their wide twins): the records (built from the shared
+        values when none were given), a second record array (XParams) and the device array `pushed` [count] int64, which holds every
+        ring's push count -- a launch's window position is ignored there, learner l's remembered env at window position rel goes to
+        slot (pushed[l] + rel) mod mem_size_l and its minibatch indexes x mod min(pushed[l], mem_size_l).  `pushed` is uploaded
+        whenever the rings' host counters moved without the group (populate_memory, a test) and advanced on the stream by every step
+        that remembers.  form="latency" takes neither.
 
         form="wide": the learners run on the layer-by-layer path (csrc/shems_wide.hip), batched over learners -- every launch runs the
         whole group.  All networks are zero-padded into one hidden size, `hidden` (default: the elementwise maximum of the records'
@@ -237,25 +308,43 @@ class LearnerGroup:
         self.L = _declare_group()
         self.count, self.envs_per_learner, self.capacity = int(count), int(envs_per_learner), int(capacity)
         self.hparams, self._hp_host, self._hp_dev = None, None, None
+        self._xp_host, self._xp_dev, self._pushed_dev, self._pushed_host, self.ou_state = None, None, None, None, None
         self.hidden = None                         # form "wide": the padded hidden size of every learner's networks
-        if form == "wide":                         # every argument error before any device work
+        if noise_type not in GROUP_NOISE:          # every argument error before any device work
+            raise ValueError(f"noise_type {noise_type!r}: a learner group draws \"gn\" or \"ou\" action noise (\"en\" and \"pn\" run on a single Agent)")
+        self.noise_type, self.theta, self.dt = noise_type, float(theta), float(dt)
+        ou = noise_type == "ou"
+        if hparams is not None:
+            hparams = list(hparams)
+        sized = hparams is not None and any(hasattr(h, "keys") and "mem_size" in h for h in hparams)
+        self._x = ou or sized                      # the *_x entry points: per-learner OU noise / ring sizes
+        if self._x and form == "latency":
+            raise ValueError("Ornstein-Uhlenbeck noise and per-learner mem_size run on the throughput or the wide form: form='latency' takes neither")
+        rec_kw = dict(noise_type=noise_type, theta=self.theta)
+        if form == "wide":
             if tiled:
                 raise ValueError("form='wide' has no tiled working layout: tiled=True is refused")
             tiled = False
             self.hidden = _wide_width(hparams, hidden)
+            if hparams is None and self._x:        # uniform records: the bits of the shared values
+                hparams = [{"hidden": self.hidden} for _ in range(max(self.count, 0))]
             if hparams is not None:
                 if self.count < 1:
                     raise ValueError("a learner group needs count >= 1")
-                self.hparams, self._hp_host = _hparams_records(self.count, hparams, sigma, self.capacity, width=self.hidden)
+                self.hparams, self._hp_host = _hparams_records(self.count, hparams, sigma, self.capacity, width=self.hidden, **rec_kw)
         elif hidden is not None:
             raise ValueError("hidden= belongs to form='wide'")
-        elif hparams is not None:
+        elif hparams is not None or self._x:
             if form == "latency":
                 raise ValueError("per-learner hyper-parameters run on the throughput form: form='latency' cannot take hparams")
             if self.count < 1:
                 raise ValueError("a learner group needs count >= 1")
-            self.hparams, self._hp_host = _hparams_records(self.count, hparams, sigma, self.capacity)
+            self.hparams, self._hp_host = _hparams_records(self.count, hparams if hparams is not None else [{} for _ in range(self.count)], sigma,
+                                                           self.capacity, **rec_kw)
             form = "throughput"
+        if self._x:
+            self._xp_host = _xparams_records(self.hparams, self.capacity, self.dt)
+        self.mem_sizes = [r["mem_size"] for r in self.hparams] if self.hparams is not None else [self.capacity] * max(self.count, 0)
         self.form = form if form is not None else ("throughput" if self.count >= self.TP_MIN_LEARNERS else "latency")
         if self.form not in ("throughput", "latency", "wide"):
             raise ValueError("form must be 'throughput', 'latency' or 'wide'")
@@ -307,21 +396,45 @@ class LearnerGroup:
                 ag = Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=h["sigma"], mu=h["mu"], device=self.device, tensors=tens,
                            hidden=h["hidden"], **wkw)
                 ag.gamma, ag.tau, ag.batch, ag.eta_act, ag.eta_crit = h["gamma"], h["tau"], h["batch"], h["eta_act"], h["eta_crit"]
+                ag.noise_type, ag.theta, ag.dt = self.noise_type, h["theta"], self.dt
                 self.learners.append(ag)
             if self.tiled:
                 self.learners[-1]._before_param_write = self._before_flux_write
-            done = v("ring_done").view(torch.uint8)[:self.capacity]
-            self.rings.append(ReplayRing(self.capacity, tensors=(v("ring_s").view(self.capacity, STATE), v("ring_a").view(self.capacity, ACTION),
-                                                                 v("ring_r"), v("ring_s2").view(self.capacity, STATE), done)))
+            m = self.mem_sizes[l]                  # the learner's ring: the first mem_size slots of arrays carved for `capacity`
+            done = v("ring_done").view(torch.uint8)[:m]
+            self.rings.append(ReplayRing(m, tensors=(v("ring_s").view(self.capacity, STATE)[:m], v("ring_a").view(self.capacity, ACTION)[:m],
+                                                     v("ring_r")[:m], v("ring_s2").view(self.capacity, STATE)[:m], done)))
         if self._hp_host is not None:              # the records, once, in a small device buffer the group owns
             raw = np.frombuffer(bytes(self._hp_host), dtype=np.uint8).copy()
             self._hp_dev = torch.from_numpy(raw).to(self.device)
+        if self._x:
+            raw = np.frombuffer(bytes(self._xp_host), dtype=np.uint8).copy()
+            self._xp_dev = torch.from_numpy(raw).to(self.device)
+            self._pushed_dev = torch.zeros(self.count, dtype=torch.int64, device=self.device)
+            self._pushed_host = [0] * self.count
+            if self.noise_type == "ou":            # OUNoise.X = zeros(Float32, 2) per env; kept across episodes, as Agent.ou_state
+                self.ou_state = torch.zeros((self.n_envs, ACTION), dtype=torch.float32, device=self.device)
         self.updates = 0
         self.tick = 0
 
     def _hp_ptr(self):
         """The entry points' d_hp: the device records, or NULL (the shared values)."""
         return C.c_void_p(self._hp_dev.data_ptr()) if self._hp_dev is not None else None
+
+    def _x_ptrs(self):
+        """The *_x entry points' (d_xp, d_pushed).  `pushed` must hold [ring.pushed for ring in rings] when a launch reads it: the host
+        counters are compared with what the device array was last given (no device work) and uploaded if they moved without the group."""
+        now = [int(r.pushed) for r in self.rings]
+        if now != self._pushed_host:
+            self._pushed_dev.copy_(self.torch.tensor(now, dtype=self.torch.int64), non_blocking=False)
+            self._pushed_host = now
+        return C.c_void_p(self._xp_dev.data_ptr()), C.c_void_p(self._pushed_dev.data_ptr())
+
+    def _ring0(self):
+        """The entry points' ring0: learner 0's ring arrays with the capacity they are carved for (rings[0] may use a prefix of them)."""
+        r0 = self.rings[0].struct()
+        r0.capacity = self.capacity
+        return r0
 
     # ------------------------------------------------------------------
     def struct(self):
@@ -384,12 +497,19 @@ class LearnerGroup:
 
     def min_max_buffer(self, count=None, seed=None):
         """min_max_buffer (MPS:50-53) for every learner in one launch (learner l: Philox key seed + l)."""
-        g, r0 = self.struct(), self.rings[0].struct()
-        n = len(self.rings[0])
-        a0 = self.learners[0]
-        _capi.check(self.L.shems_minmax_group_dev(C.byref(r0), C.byref(g), n, n if count is None else int(count),
-                                                  self.rng_seed if seed is None else int(seed), C.c_void_p(a0.s_min.data_ptr()),
-                                                  C.c_void_p(a0.s_max.data_ptr()), self._stream()))
+        g, r0 = self.struct(), self._ring0()
+        seed = self.rng_seed if seed is None else int(seed)
+        lens = [len(r) for r in self.rings]
+        if len(set(lens)) == 1:
+            n, a0 = lens[0], self.learners[0]
+            _capi.check(self.L.shems_minmax_group_dev(C.byref(r0), C.byref(g), n, n if count is None else int(count), seed,
+                                                      C.c_void_p(a0.s_min.data_ptr()), C.c_void_p(a0.s_max.data_ptr()), self._stream()))
+            return self
+        one = Group(1, 0, 0, self.envs_per_learner)        # rings of different lengths: the same launch per learner, on its own length
+        for l, (ag, ring, n) in enumerate(zip(self.learners, self.rings, lens)):
+            rl = ring.struct()
+            _capi.check(self.L.shems_minmax_group_dev(C.byref(rl), C.byref(one), n, n if count is None else int(count), seed + l,
+                                                      C.c_void_p(ag.s_min.data_ptr()), C.c_void_p(ag.s_max.data_ptr()), self._stream()))
         return self
 
     def act_step(self, env, train=True, tick=None, a_out=None, returns_acc=None, window=None, noise_acc=None, envs_per_learner=None):
@@ -409,28 +529,52 @@ class LearnerGroup:
         a0 = self.learners[0]
         p = a0._act_params(train, self.tick if tick is None else tick, noise_acc=noise_acc)
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-        r0 = self.rings[0].struct()
+        r0 = self._ring0()
         w = RingWindow(*window) if window is not None else None
         ring_w = (C.byref(r0), C.byref(w)) if w is not None else (None, None)
+        if self._x:
+            if w is not None and w.count > min(self.mem_sizes):
+                raise ValueError(f"a window of {w.count} transitions per step exceeds the smallest ring of the group ({min(self.mem_sizes)})")
+            if self.ou_state is not None:          # the group's OU state, one [2] per env of the TRAINING batch; evaluation never reads it
+                if train and env.n != self.n_envs:
+                    raise ValueError("a training step with Ornstein-Uhlenbeck noise runs the group's own env batch (ou_state is keyed by its envs)")
+                p.ou_state = self.ou_state.data_ptr()
+            xptrs = self._x_ptrs()
         if self.form == "wide":                    # four launches for the whole group (noise mu / sigma from the records, if any)
             need = C.c_int64(0)
             _capi.check(self.L.shems_wide_act_workspace_floats(*self.hidden, env.n, C.byref(need)))
             if self._act_ws is None or self._act_ws.numel() < need.value:      # (an eval batch may be wider than the training batch)
                 self._act_ws = self.torch.empty(need.value, dtype=self.torch.float32, device=self.device)
-            _capi.check(self.L.shems_wide_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), *self.hidden, self._hp_ptr(),
-                                                             C.c_void_p(self._act_ws.data_ptr()), ptr(a_out), ptr(returns_acc), *ring_w, self._stream()))
+            if self._x:
+                _capi.check(self.L.shems_wide_act_step_group_x_dev(C.byref(v), C.byref(p), C.byref(g), *self.hidden, self._hp_ptr(), *xptrs,
+                                                                   C.c_void_p(self._act_ws.data_ptr()), ptr(a_out), ptr(returns_acc), *ring_w,
+                                                                   self._stream()))
+            else:
+                _capi.check(self.L.shems_wide_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), *self.hidden, self._hp_ptr(),
+                                                                 C.c_void_p(self._act_ws.data_ptr()), ptr(a_out), ptr(returns_acc), *ring_w, self._stream()))
         else:                                      # one launch; W2 from the tiles where they are current, noise mu / sigma from the records, if any
             t = C.byref(self.w2t_struct()) if self._use_tiled() else None
-            _capi.check(self.L.shems_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), t, self._hp_ptr(), ptr(a_out), ptr(returns_acc), *ring_w,
-                                                        self._stream()))
+            if self._x:
+                _capi.check(self.L.shems_act_step_group_x_dev(C.byref(v), C.byref(p), C.byref(g), t, self._hp_ptr(), *xptrs, ptr(a_out),
+                                                              ptr(returns_acc), *ring_w, self._stream()))
+            else:
+                _capi.check(self.L.shems_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), t, self._hp_ptr(), ptr(a_out), ptr(returns_acc), *ring_w,
+                                                            self._stream()))
         if w is not None:
             for ring in self.rings:
                 ring.pushed += int(window[1])
+            if self._x and int(window[1]) > 0:     # the device counters follow on the stream, after the launch that read them
+                self._pushed_dev.add_(int(window[1]))
+                self._pushed_host = [ring.pushed for ring in self.rings]
 
     def replay(self, tick=None):
         """replay() (DDPG.jl:121-145) for every learner.  form "throughput": eight launches of csrc/shems_gupd.hip; "latency": 5 launches
         in total, grid z = learner (fused = False: the split calls, 7 launches -- the same bits)."""
-        a0, g, r0 = self.learners[0], self.struct(), self.rings[0].struct()
+        if self._x:                                # the *_x entry points' precondition (their lengths are device memory): no empty ring
+            xptrs = self._x_ptrs()                 # (brings the host mirror of `pushed` up to date: one pass over the rings)
+            if min(self._pushed_host) < 1:
+                raise _capi.ShemsError(_capi.ERR_ARG, f"replay(): the ring of learner {self._pushed_host.index(min(self._pushed_host))} is empty")
+        a0, g, r0 = self.learners[0], self.struct(), self._ring0()
         d = a0._ddpg_args()
         st = self._stream()
         tick = self.updates if tick is None else tick
@@ -438,12 +582,20 @@ class LearnerGroup:
         adam_c, adam_a = (a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1]), (a0.eta_act, a0.bp_actor[0], a0.bp_actor[1])
         tl = self.form != "wide" and self._use_tiled()      # (a tiled group switched to the latency form: its Flux blocks are brought up to date)
         if self.form == "wide":                    # 24 launches for the whole group (csrc/shems_wide.hip)
-            _capi.check(self.L.shems_wide_group_update(C.byref(d), C.byref(r0), C.byref(g), *self.hidden, self._hp_ptr(), self.max_batch,
-                                                       *sample, *adam_c, *adam_a, st))
+            if self._x:
+                _capi.check(self.L.shems_wide_group_update_x(C.byref(d), C.byref(r0), C.byref(g), *self.hidden, self._hp_ptr(), *xptrs,
+                                                             self.max_batch, *sample[1:], *adam_c, *adam_a, st))
+            else:
+                _capi.check(self.L.shems_wide_group_update(C.byref(d), C.byref(r0), C.byref(g), *self.hidden, self._hp_ptr(), self.max_batch,
+                                                           *sample, *adam_c, *adam_a, st))
         elif self.form == "throughput" or self._hp_dev is not None:      # records: batch / gamma / tau / eta per learner, this form only
             t = C.byref(self.w2t_struct()) if tl else None
-            _capi.check(self.L.shems_ddpg_group_update_tp(C.byref(d), C.byref(r0), C.byref(g), t, self._hp_ptr(), *sample, *adam_c, *adam_a,
-                                                          1 if self.store_grad else 0, st))
+            if self._x:
+                _capi.check(self.L.shems_ddpg_group_update_tp_x(C.byref(d), C.byref(r0), C.byref(g), t, self._hp_ptr(), *xptrs, *sample[1:],
+                                                                *adam_c, *adam_a, 1 if self.store_grad else 0, st))
+            else:
+                _capi.check(self.L.shems_ddpg_group_update_tp(C.byref(d), C.byref(r0), C.byref(g), t, self._hp_ptr(), *sample, *adam_c, *adam_a,
+                                                              1 if self.store_grad else 0, st))
             if tl:
                 self._flux_valid = False
         elif self.fused:
@@ -462,13 +614,14 @@ class LearnerGroup:
     def ring_window(self, num_steps=72, window_count=None):
         """(count, offset) of the transitions each learner stores at the CURRENT tick.
         window_count None: the vectorised default (SURVEY 8(d) replay-capacity note): a rotating window of min(E, capacity / num_steps)
-        of the learner's E households per step, so the ring spans about one episode of each.
+        of the learner's E households per step, so the ring spans about one episode of each (capacity: the smallest mem_size).
         window_count 1: the reference's ratio -- episode! remembers ONE transition per replay() (DDPG.jl:229-233, push order
         [s, a, r, s', done] MPS:46-47): always household 0 of the learner's block, so that consecutive ring entries are one household's
         trajectory (s' of entry t = s of entry t + 1 inside an episode), as the reference's single env fills its CircularBuffer.
         Any other count: a rotating window of that many households."""
         E = self.envs_per_learner
-        wc = min(E, max(1, self.capacity // int(num_steps))) if window_count is None else int(window_count)
+        smallest = min(getattr(self, "mem_sizes", None) or (self.capacity,))       # (a bare namespace, tests/test_host_logic.py, has only capacity)
+        wc = min(E, max(1, smallest // int(num_steps))) if window_count is None else int(window_count)
         if not 1 <= wc <= E:
             raise ValueError("window_count must be in 1 .. envs_per_learner")
         return wc, (0 if wc == 1 else (self.tick * wc) % E)
