@@ -638,6 +638,50 @@ int shems_wide_batch_slots(const shems_ddpg *d, int32_t l1, int32_t l2, int32_t 
 int shems_wide_track_dev(const shems_view *v, const shems_act_params *p, int32_t l1, int32_t l2, int64_t actor_stride_bytes,
                          int32_t nsteps, double *d_results, int64_t results_env, double *d_returns, void *stream);
 
+/* ------------------------------------------- the perfect-foresight controller -- */
+/* The upper yardstick of the thesis is a perfect-foresight optimiser.  With the series known in advance, the best action sequence of
+ * the environment AS WRITTEN -- action (LU1:283-316), step! (LU1:343-485), next_state! (LU1:264-281), scored by the plain sum of
+ * rewards (MPS:62-89) -- is a finite-horizon dynamic programme over (Soc_b, Soc_ev); csrc/shems_foresight_core.h holds the recursion.
+ * A problem is (table, config, 1-based start row idx0); all problems of one call share the horizon T and the grid counts.
+ *   state nodes    nb x ne: Soc_b[i] = (float)(i * hb), Soc_ev[j] = (float)(j * (1.0 / (ne - 1))), the end nodes exactly soc_max and 1;
+ *                  node index = i * ne + j
+ *   action targets nab x nae in [0, 1]: (float)(a / (double)(count - 1)), 1 for a single point; action index = ab * nae + ae
+ *   V              float64 [n_problems][T + 1][nb * ne], V_T = 0; off the nodes bilinear in float64; the maximum over the actions takes
+ *                  the SMALLEST index among equal maxima. */
+typedef struct shems_foresight_grid {
+    int32_t nb, ne;          /* state nodes, each >= 2 (default 65 x 33: 0.5 * soc_max, the start of reset!(rng = -1), is a node) */
+    int32_t nab, nae;        /* action targets, each >= 1 (default 17 x 17)                                                        */
+} shems_foresight_grid;
+typedef struct shems_foresight_problem {
+    shems_config cfg;        /* table_row0 / nrow name the problem's table in the uploaded row array                              */
+    int32_t idx0;            /* 1-based start row: idx0 >= 1 and idx0 + T <= nrow (a pass of n steps reads row n + 1)              */
+    int32_t reserved;        /* 0                                                                                                  */
+    double  scale_b;         /* (nb - 1) / (double)soc_max, formed ONCE on the host in float64: the device never divides.  Filled   */
+    double  hb;              /* (double)soc_max / (nb - 1).                        by shems_foresight_solve_dev in the device copy   */
+} shems_foresight_problem;   /* 72 bytes */
+/* The backward sweep (LU1:283-316, 343-485, 264-281; MPS:62-89): V_t(node) = max_a { reward + V_{t+1}(state') }, t = T - 1 .. 0, one
+ * launch per hour on `stream` (hours are separated by launch boundaries only), grid = (node tiles, problems); no host synchronisation.
+ * problems: n_problems records in HOST memory, of which cfg and idx0 are read; they are validated here, completed (scale_b, hb) and
+ * copied on `stream` into d_problems, n_problems records of DEVICE memory the caller allocates: what the kernels of the sweep and
+ * shems_foresight_track_dev read.  `problems` may be reused when the call returns.  d_tables [total_rows][8] as in shems_view.
+ * d_V: v_doubles >= n_problems * (T + 1) * nb * ne float64 of device memory, allocated by the caller; d_argmax: int32 [n_problems][T][nb * ne] winning action indices, or NULL.
+ * SHEMS_ERR_ARG, nothing launched: a grid count below its minimum (or a V plane beyond the 150 000 bytes of LDS a workgroup stages),
+ * T < 1, a window running off its table, soc_max <= 0, a V buffer that is too small. */
+int shems_foresight_solve_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                              shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
+                              double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream);
+/* The forward pass (LU1:283-316, 343-485, 264-281; MPS:62-89): the greedy controller on the EXACT env, shaped like shems_track_dev --
+ * one workgroup per env, all T hours in one launch.  Env e belongs to problem d_problem_of_env[e] (NULL: problem 0).  At hour t every
+ * action is evaluated from the env's true (off-grid) state with the same Q as the sweep, the arg-max is taken, and the env is stepped
+ * with that action through the ordinary DRL step (track > 0: penalty kept, 23-column row).  d_returns [n] float64 sums of rewards,
+ * d_results [n][T][23] (results_env = -1) or [T][23] of env results_env, d_targets [n][T][2] float32 the chosen (B_target,
+ * EV_target); each may be NULL.  The envs end in the state T calls of shems_step_dev with those targets leave them in.  An env whose
+ * idx is not its problem's idx0 at entry (or whose problem index is outside 0 .. n_problems - 1) raises view.err = SHEMS_ERR_INDEX
+ * and is not stepped. */
+int shems_foresight_track_dev(const shems_view *v, const shems_foresight_problem *d_problems /* as solve_dev left them */, int32_t n_problems,
+                              const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V,
+                              int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

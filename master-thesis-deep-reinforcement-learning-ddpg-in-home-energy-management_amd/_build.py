@@ -24,6 +24,7 @@ UNITS = [
     ("shems_ddpg.hip", []),
     ("shems_gupd.hip", []),
     ("shems_track.hip", ["-ffp-contract=off"]),
+    ("shems_foresight.hip", ["-ffp-contract=off"]),
     ("shems_wide.hip", []),
     ("shems_train.hip", []),
     ("shems_dp.hip", []),

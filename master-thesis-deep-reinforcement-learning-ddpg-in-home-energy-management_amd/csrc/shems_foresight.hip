@@ -1,0 +1,282 @@
+// shems_foresight.hip -- the perfect-foresight controller: shems_foresight_solve_dev (backward sweep) and shems_foresight_track_dev
+// (greedy forward pass on the exact env).  The recursion itself is csrc/shems_foresight_core.h; this file only spreads it over the GPU.
+//
+// Backward sweep: one launch per hour t = T - 1 .. 0 (an hour needs the whole V_{t+1} plane of its problem, so hours are separated by
+// launch boundaries and by nothing else), grid = (node tiles, problems), 256 threads.  The workgroup stages its problem's V_{t+1} plane
+// (65 x 33 nodes: 17 KB) and the two table rows of the hour in LDS; a wave takes `npw` nodes one after the other, the actions of a node
+// spread over its 64 lanes (lane l: actions l, l + 64, ... in ascending order, so a strict > keeps the smallest index), and the
+// (value, index) maximum is a butterfly over the wave with fs_better -- every lane ends with the same pair, lane 0 stores it.
+// Forward pass: one workgroup per env, all T hours inside the kernel (as k_track); the 256 threads evaluate the actions from the env's
+// true state against V_{t+1} in L2, the maximum goes wave -> LDS -> thread 0, which steps the env with the ordinary DRL step.
+//
+// Compiled with -ffp-contract=off (shems_core.h).
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "shems_env_dev.h"
+#include "shems_foresight_core.h"
+#include "shems_internal.h"
+
+namespace shems {
+
+constexpr int kFsThreads = 256, kFsWaves = kFsThreads / 64;
+constexpr int kFsMaxPlaneBytes = 150000;           // of the 160 KB of LDS a gfx950 workgroup can hold
+
+struct FsSolveArgs {
+    const float *tables;
+    const shems_foresight_problem *prob;
+    FsParams g;
+    int T, t, npw;                                 // npw: nodes per wave (a tile = kFsWaves * npw nodes)
+    double *V;
+    int32_t *arg;
+};
+
+__global__ __launch_bounds__(kFsThreads) void k_fs_zero(double *V, int64_t plane, int64_t stride, int64_t total)
+{
+    const int64_t i = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;       // V_T = 0: the last plane of every problem
+    if (i < total) V[(i / plane) * stride + (stride - plane) + i % plane] = 0.0;
+}
+
+// 4 waves per SIMD: left alone the compiler takes 129 VGPRs, one past the step from 4 resident waves to 3; held to 4 it takes 127, no scratch.
+__global__ __launch_bounds__(kFsThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_fs_backward(FsSolveArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_v[];            // V_{t+1} [nb * ne]
+    __shared__ float s_row[2 * SHEMS_NCOL];                                 // rows idx0 + t and idx0 + t + 1
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.y;
+    const FsParams &g = A.g;
+    const int N = g.nb * g.ne, NA = g.nab * g.nae;
+    const shems_foresight_problem P = A.prob[p];
+    double *Vt = A.V + ((int64_t)p * (A.T + 1) + A.t) * N;
+    const double *Vn = Vt + N;
+    for (int i = tid; i < N; i += kFsThreads) s_v[i] = Vn[i];
+    if (tid < 2 * SHEMS_NCOL) s_row[tid] = A.tables[((int64_t)P.cfg.table_row0 + P.idx0 + A.t - 1) * SHEMS_NCOL + tid];
+    __syncthreads();
+    const float h_cur = s_row[0], h_next = s_row[SHEMS_NCOL], soc_ev_next = s_row[SHEMS_NCOL + 1];
+    for (int k = 0; k < A.npw; ++k) {
+        const int node = ((int)blockIdx.x * kFsWaves + wave) * A.npw + k;   // wave-uniform
+        if (node >= N) break;
+        const int ib = node / g.ne, ie = node - ib * g.ne;
+        const EnvIn s{fs_soc_b_node(P, g.nb, ib), fs_soc_ev_node(g, ie), h_cur, s_row[2], s_row[3], s_row[4]};
+        double best_v = -__builtin_inf();
+        int best_a = kFsNoAction;
+        for (int a = lane; a < NA; a += 64) {
+            const int ab = a / g.nae, ae = a - ab * g.nae;
+            const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), s_v, g, P.scale_b);
+            if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(best_v, off, 64);
+            const int oa = __shfl_xor(best_a, off, 64);
+            if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
+        }
+        if (lane == 0) {
+            Vt[node] = best_v;
+            if (A.arg) A.arg[((int64_t)p * A.T + A.t) * N + node] = best_a;
+        }
+    }
+}
+
+struct FsTrackArgs {
+    shems_view v;
+    const shems_foresight_problem *prob;
+    int n_prob;
+    const int32_t *problem_of_env;
+    FsParams g;
+    int T;
+    const double *V;
+    double *results;                               // [n or 1][T][23] or null
+    int64_t results_env;
+    double *returns;                               // [n] or null
+    float *targets;                                // [n][T][2] or null
+};
+
+__global__ __launch_bounds__(kFsThreads) void k_fs_track(FsTrackArgs A)
+{
+    __shared__ float s_obs[SHEMS_NSTATE];
+    __shared__ double s_bv[kFsWaves];
+    __shared__ int s_ba[kFsWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t e = blockIdx.x;
+    const shems_view &v = A.v;
+    const FsParams &g = A.g;
+    const int N = g.nb * g.ne, NA = g.nab * g.nae;
+    // ---- entry checks, the same answer in every thread ----
+    const int p = A.problem_of_env ? A.problem_of_env[e] : 0;
+    int32_t idx = v.idx[e], step = v.step[e];
+    if (p < 0 || p >= A.n_prob || A.prob[p].idx0 != idx) {
+        if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
+        return;
+    }
+    const shems_foresight_problem P = A.prob[p];
+    const shems_config cfg = load_cfg(v, e);                                // the env's own config steps the env
+    float obs[SHEMS_NSTATE];
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) obs[k] = v.obs[e * SHEMS_NSTATE + k];
+    if (tid < SHEMS_NSTATE) s_obs[tid] = v.obs[e * SHEMS_NSTATE + tid];
+    __syncthreads();
+    double total = 0.0;
+    for (int t = 0; t < A.T; ++t) {
+        if (idx < 1 || idx + 1 > cfg.nrow || idx + 1 > P.cfg.nrow) {       // row idx + 1 does not exist (Julia: BoundsError)
+            if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
+            break;
+        }
+        const double *Vn = A.V + ((int64_t)p * (A.T + 1) + t + 1) * N;
+        const float h_cur = load_h(v.tables, P.cfg.table_row0, idx);
+        const float h_next = load_h(v.tables, P.cfg.table_row0, idx + 1);
+        const float soc_ev_next = v.tables[((int64_t)P.cfg.table_row0 + idx) * SHEMS_NCOL + 1];
+        const EnvIn s{s_obs[0], s_obs[1], s_obs[2], s_obs[3], s_obs[4], s_obs[5]};
+        double best_v = -__builtin_inf();
+        int best_a = kFsNoAction;
+        for (int a = tid; a < NA; a += kFsThreads) {
+            const int ab = a / g.nae, ae = a - ab * g.nae;
+            const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), Vn, g, P.scale_b);
+            if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(best_v, off, 64);
+            const int oa = __shfl_xor(best_a, off, 64);
+            if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
+        }
+        if (lane == 0) { s_bv[wave] = best_v; s_ba[wave] = best_a; }
+        __syncthreads();
+        if (tid == 0) {
+#pragma unroll
+            for (int w = 1; w < kFsWaves; ++w)
+                if (fs_better(s_bv[w], s_ba[w], best_v, best_a)) { best_v = s_bv[w]; best_a = s_ba[w]; }
+            const int a = best_a == kFsNoAction ? 0 : best_a;               // every Q a NaN: cannot happen on finite tables
+            const int ab = a / g.nae, ae = a - ab * g.nae;
+            const float a0 = fs_target(ab, g.nab), a1 = fs_target(ae, g.nae);
+            float pre[SHEMS_NSTATE];
+#pragma unroll
+            for (int k = 0; k < SHEMS_NSTATE; ++k) pre[k] = obs[k];
+            double reward;
+            StepFlows f;
+            float B, EV, Bt, EVt;
+            env_advance(cfg, v.tables, obs, idx, step, a0, a1, SHEMS_TRACK_DRL, reward, f, B, EV, Bt, EVt);   // bounds checked above
+            total += reward;
+            if (A.results && (A.results_env < 0 || A.results_env == e)) {
+                double *r = A.results + ((A.results_env < 0 ? e : 0) * (int64_t)A.T + t) * SHEMS_NRESULT;
+                write_results(r, idx, pre, EVt, EV, reward, f, B, Bt);
+            }
+            if (A.targets) {
+                float *tg = A.targets + (e * (int64_t)A.T + t) * 2;
+                tg[0] = a0; tg[1] = a1;
+            }
+#pragma unroll
+            for (int k = 0; k < SHEMS_NSTATE; ++k) s_obs[k] = obs[k];
+        } else {
+            idx += 1;                                                        // every thread follows the row index
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < SHEMS_NSTATE; ++k) v.obs[e * SHEMS_NSTATE + k] = obs[k];
+        v.idx[e] = idx;
+        v.step[e] = step;
+        if (A.returns) A.returns[e] = total;
+    }
+}
+
+static int fs_params(const shems_foresight_grid *grid, const char *fn, FsParams &g)
+{
+    if (!grid) return set_error(SHEMS_ERR_ARG, "%s: grid is NULL", fn);
+    if (grid->nb < 2 || grid->ne < 2)
+        return set_error(SHEMS_ERR_ARG, "%s: the state grid is %d x %d nodes; each axis needs at least 2", fn, (int)grid->nb, (int)grid->ne);
+    if (grid->nab < 1 || grid->nae < 1)
+        return set_error(SHEMS_ERR_ARG, "%s: the action grid is %d x %d targets; each axis needs at least 1", fn, (int)grid->nab, (int)grid->nae);
+    if ((int64_t)grid->nb * grid->ne * 8 > kFsMaxPlaneBytes)
+        return set_error(SHEMS_ERR_ARG, "%s: a V plane of %d x %d nodes does not fit the %d bytes of LDS a workgroup stages", fn, (int)grid->nb,
+                         (int)grid->ne, kFsMaxPlaneBytes);
+    if ((int64_t)grid->nab * grid->nae > (1 << 24))
+        return set_error(SHEMS_ERR_ARG, "%s: %d x %d action targets are more than 2^24", fn, (int)grid->nab, (int)grid->nae);
+    g.nb = grid->nb; g.ne = grid->ne; g.nab = grid->nab; g.nae = grid->nae;
+    g.scale_e = (double)(grid->ne - 1);
+    g.he = 1.0 / (double)(grid->ne - 1);
+    return SHEMS_OK;
+}
+
+}  // namespace shems
+
+using namespace shems;
+
+extern "C" int shems_foresight_solve_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                                         shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid,
+                                         int32_t T, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream)
+{
+    const char *fn = "shems_foresight_solve_dev";
+    FsParams g;
+    if (int rc = fs_params(grid, fn, g)) return rc;
+    if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; the horizon must be at least 1 hour", fn, (int)T);
+    if (!d_tables || total_rows < 2 || !problems || !d_problems || n_problems < 1 || n_problems > 65535 || !d_V)
+        return set_error(SHEMS_ERR_ARG, "%s: NULL buffer, fewer than 2 table rows, or a problem count outside 1 .. 65535", fn);
+    std::vector<shems_foresight_problem> recs(problems, problems + n_problems);   // validated and completed here, then uploaded
+    for (int32_t p = 0; p < n_problems; ++p) {
+        shems_foresight_problem &P = recs[p];
+        if (P.cfg.table_row0 < 0 || P.cfg.nrow < 2 || (int64_t)P.cfg.table_row0 + P.cfg.nrow > total_rows)
+            return set_error(SHEMS_ERR_ARG, "%s: problem %d names table rows %d .. %lld of %lld", fn, (int)p, (int)P.cfg.table_row0,
+                             (long long)P.cfg.table_row0 + P.cfg.nrow, (long long)total_rows);
+        if (P.idx0 < 1 || (int64_t)P.idx0 + T > P.cfg.nrow)
+            return set_error(SHEMS_ERR_ARG, "%s: problem %d: the window of rows %d .. %lld runs off its table of %d rows (a pass of T steps reads row idx0 + T)",
+                             fn, (int)p, (int)P.idx0, (long long)P.idx0 + T, (int)P.cfg.nrow);
+        if (!(P.cfg.soc_max > 0.0f)) return set_error(SHEMS_ERR_ARG, "%s: problem %d: soc_max = %g must be positive", fn, (int)p, (double)P.cfg.soc_max);
+        P.reserved = 0;
+        P.scale_b = (double)(g.nb - 1) / (double)P.cfg.soc_max;             // the only divisions of the sweep: float64, on the host
+        P.hb = (double)P.cfg.soc_max / (double)(g.nb - 1);
+    }
+    const int64_t N = (int64_t)g.nb * g.ne;
+    if (v_doubles < (int64_t)n_problems * (T + 1) * N)
+        return set_error(SHEMS_ERR_ARG, "%s: the V buffer holds %lld float64; %d problems x %d planes x %lld nodes need %lld", fn, (long long)v_doubles,
+                         (int)n_problems, (int)T + 1, (long long)N, (long long)n_problems * (T + 1) * N);
+    const int lds = (int)(N * 8);
+    static std::atomic<uint64_t> optin{0};                                  // per device, once: the largest plane fs_params admits
+    if (int rc = lds_optin(optin, (const void *)k_fs_backward, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_backward)")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // the records the kernels (and the forward pass) read: ordered on the stream; the runtime has staged a pageable source on return
+    if (int rc = hip_ok(hipMemcpyAsync(d_problems, recs.data(), recs.size() * sizeof(shems_foresight_problem), hipMemcpyHostToDevice, st),
+                        "upload of the problem records"))
+        return rc;
+    const int64_t total = (int64_t)n_problems * N;
+    hipLaunchKernelGGL(k_fs_zero, dim3((unsigned)((total + kFsThreads - 1) / kFsThreads)), dim3(kFsThreads), 0, st, d_V, N, (int64_t)(T + 1) * N, total);
+    if (int rc = hip_ok(hipGetLastError(), "k_fs_zero launch")) return rc;
+    // nodes per wave: the fewest workgroups that still give every CU several (a wave's nodes run one after the other)
+    int npw = 8;
+    while (npw > 1 && ((N + kFsWaves * npw - 1) / (kFsWaves * npw)) * n_problems < 1024) npw >>= 1;
+    FsSolveArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.tables = d_tables; a.prob = d_problems; a.g = g; a.T = T; a.npw = npw; a.V = d_V; a.arg = d_argmax;
+    const dim3 gridDim((unsigned)((N + kFsWaves * npw - 1) / (kFsWaves * npw)), (unsigned)n_problems);
+    for (int t = T - 1; t >= 0; --t) {
+        a.t = t;
+        hipLaunchKernelGGL(k_fs_backward, gridDim, dim3(kFsThreads), lds, st, a);
+    }
+    return hip_ok(hipGetLastError(), "k_fs_backward launch");
+}
+
+extern "C" int shems_foresight_track_dev(const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
+                                         const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V,
+                                         int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
+{
+    const char *fn = "shems_foresight_track_dev";
+    if (int rc = check_view(v, fn)) return rc;
+    FsParams g;
+    if (int rc = fs_params(grid, fn, g)) return rc;
+    if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; the horizon must be at least 1 hour", fn, (int)T);
+    if (!d_problems || n_problems < 1 || !d_V) return set_error(SHEMS_ERR_ARG, "%s: NULL buffer or no problem", fn);
+    const int64_t N = (int64_t)g.nb * g.ne;
+    if (v_doubles < (int64_t)n_problems * (T + 1) * N)
+        return set_error(SHEMS_ERR_ARG, "%s: the V buffer holds %lld float64; %d problems x %d planes x %lld nodes need %lld", fn, (long long)v_doubles,
+                         (int)n_problems, (int)T + 1, (long long)N, (long long)n_problems * (T + 1) * N);
+    if (results_env >= v->n_envs) return set_error(SHEMS_ERR_ARG, "%s: results_env %lld outside the batch", fn, (long long)results_env);
+    FsTrackArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.v = *v; a.prob = d_problems; a.n_prob = n_problems; a.problem_of_env = d_problem_of_env; a.g = g; a.T = T; a.V = d_V;
+    a.results = d_results; a.results_env = results_env; a.returns = d_returns; a.targets = d_targets;
+    hipLaunchKernelGGL(k_fs_track, dim3((unsigned)v->n_envs), dim3(kFsThreads), 0, (hipStream_t)stream, a);
+    return hip_ok(hipGetLastError(), "k_fs_track launch");
+}

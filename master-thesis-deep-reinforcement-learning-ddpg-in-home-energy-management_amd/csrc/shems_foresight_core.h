@@ -1,0 +1,79 @@
+// shems_foresight_core.h -- the recursion of the perfect-foresight controller, written once (host + device functions).
+//
+// With the exogenous series known in advance, the best action sequence of the environment AS WRITTEN is a finite-horizon dynamic
+// programme over the two continuous state values (Soc_b, Soc_ev); the rest of the state is the table row.  One evaluation
+//   Q_t(state, a) = reward of step!(state, a) + V_{t+1}(Soc_b', Soc_ev')
+// runs the env's own arithmetic: action(env, a::ShemsAction) (shems_LU1.jl:283-316), step! (:343-485), the arrival overwrite of
+// next_state! (:264-281); there is no discount -- a pass is scored by the plain sum of its rewards (memory_plotting_saving.jl:62-89).
+// V lives on an NB x NE grid of nodes and is read off the nodes by bilinear interpolation in float64 with ONE fixed order of operations
+// (IEEE add / sub / mul / compare / floor only), so that the device, a host build of this header and a NumPy restatement agree bit for
+// bit.  The maximum over the action grid is the SMALLEST index among equal maxima (fs_better), whatever the shape of the reduction.
+//
+// MUST be compiled with -ffp-contract=off, as shems_core.h.
+#pragma once
+
+#include "shems_core.h"
+
+#pragma clang fp contract(off)
+
+namespace shems {
+
+struct FsParams {               // the grid as a kernel needs it; the two float64 scalars are formed on the host
+    int    nb, ne, nab, nae;
+    double scale_e;             // NE - 1
+    double he;                  // 1.0 / (NE - 1)
+};
+
+// State nodes: Soc_b[i] = (float)(i * hb), hb = (double)soc_max / (NB - 1); Soc_ev[j] = (float)(j * he); the end nodes are exactly
+// soc_max and 1.
+SHEMS_HD float fs_soc_b_node(const shems_foresight_problem &p, int nb, int i)
+{
+    return i == nb - 1 ? p.cfg.soc_max : (float)((double)i * p.hb);
+}
+SHEMS_HD float fs_soc_ev_node(const FsParams &g, int j) { return j == g.ne - 1 ? 1.0f : (float)((double)j * g.he); }
+// Action targets: (float)(a / (double)(n - 1)); the single point of a 1-point axis is 1.
+SHEMS_HD float fs_target(int a, int n) { return n == 1 ? 1.0f : (float)((double)a / (double)(n - 1)); }
+
+// One axis of the interpolation: u = x * scale, i = clamp((int)floor(u), 0, n - 2), f = clamp(u - i, 0, 1).
+SHEMS_HD void fs_axis(double x, double scale, int n, int &i, double &f)
+{
+    const double u = x * scale;
+    double fl = __builtin_floor(u);
+    fl = !(fl > 0.0) ? 0.0 : (fl > (double)(n - 2) ? (double)(n - 2) : fl);      // also catches a NaN
+    i = (int)fl;
+    const double fr = u - fl;
+    f = !(fr > 0.0) ? 0.0 : (fr > 1.0 ? 1.0 : fr);
+}
+
+// V off the nodes.  V: one plane [nb][ne] float64 (any address space the caller can read).
+SHEMS_HD double fs_value(const double *V, const FsParams &g, double scale_b, float soc_b, float soc_ev)
+{
+    int ib, ie;
+    double fb, fe;
+    fs_axis((double)soc_b, scale_b, g.nb, ib, fb);
+    fs_axis((double)soc_ev, g.scale_e, g.ne, ie, fe);
+    const double *r0 = V + (int64_t)ib * g.ne + ie, *r1 = r0 + g.ne;
+    const double V00 = r0[0], V01 = r0[1], V10 = r1[0], V11 = r1[1];
+    return (1.0 - fe) * ((1.0 - fb) * V00 + fb * V10) + fe * ((1.0 - fb) * V01 + fb * V11);
+}
+
+// Q_t(state, (B_target, EV_target)): the DRL step of the env (penalty kept) from `s`, the arrival overwrite with h_countdown of the
+// current row and (h_countdown, soc_ev) of the next one, plus V_{t+1} at the state it leaves.
+SHEMS_HD double fs_q(const shems_config &c, const EnvIn &s, float h_cur, float h_next, float soc_ev_next, float B_target, float EV_target,
+                     const double *V_next, const FsParams &g, double scale_b)
+{
+    float B, EV, soc_b_n, soc_ev_n;
+    double reward;
+    StepFlows f;
+    action_drl(c, s, B_target, EV_target, B, EV);
+    step_flows(c, s, EV_target, B, EV, false, soc_b_n, soc_ev_n, reward, f);
+    if (h_next >= 0.0f && h_cur == -1.0f) soc_ev_n = soc_ev_next;                  // LU1:270-272
+    return reward + fs_value(V_next, g, scale_b, soc_b_n, soc_ev_n);
+}
+
+// (value, index) order of the maximum: greater value, or equal value and smaller index.
+SHEMS_HD bool fs_better(double v, int a, double best_v, int best_a) { return v > best_v || (v == best_v && a < best_a); }
+
+constexpr int kFsNoAction = 0x7fffffff;          // the index of "nothing evaluated yet": loses every tie
+
+}  // namespace shems

@@ -1,0 +1,242 @@
+"""The perfect-foresight controller: the exact dynamic programme of shems_LU1's step! on the GPU.
+
+The thesis scores every controller against two yardsticks: the rule-based "power mode" (harness.inference(track < 0)) and a
+perfect-foresight optimiser.  With the exogenous series known in advance, the best action sequence of the environment AS WRITTEN
+(action shems_LU1.jl:283-316, step! :343-485, next_state! :264-281, scored by the plain sum of rewards,
+memory_plotting_saving.jl:62-89) is a finite-horizon dynamic programme over (Soc_b, Soc_ev):
+
+    solve(tables, configs, idx0, nsteps, grid) -> Values      the backward sweep, V float64 [P][T + 1][nb * ne]  (shems_foresight_solve_dev)
+    track(env, values, problem_of_env, which)                 the greedy controller on the exact env, one launch    (shems_foresight_track_dev)
+
+The arithmetic lives in csrc/shems_foresight_core.h; Values.at restates its interpolation on the host, bit for bit.  A discretised
+value function with a greedy policy is NOT a bound: V_0 at the start state and the achieved return differ by the discretisation error.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import Config
+
+
+class GridStruct(C.Structure):            # shems_foresight_grid
+    _fields_ = [("nb", C.c_int32), ("ne", C.c_int32), ("nab", C.c_int32), ("nae", C.c_int32)]
+
+
+class Problem(C.Structure):               # shems_foresight_problem
+    _fields_ = [("cfg", Config), ("idx0", C.c_int32), ("reserved", C.c_int32), ("scale_b", C.c_double), ("hb", C.c_double)]
+
+
+assert C.sizeof(Problem) == 72 and C.sizeof(GridStruct) == 16
+
+MAX_PLANE_BYTES = 150000                  # a workgroup of the sweep stages one V plane in LDS
+
+
+class Grid:
+    """State nodes nb x ne over [0, soc_max] x [0, 1] and action targets nab x nae over [0, 1]^2.  The default 65 x 33 makes
+    0.5 * soc_max, the start of reset!(rng = -1), a node."""
+
+    def __init__(self, nb=65, ne=33, nab=17, nae=17):
+        self.nb, self.ne, self.nab, self.nae = int(nb), int(ne), int(nab), int(nae)
+        if self.nb < 2 or self.ne < 2:
+            raise ValueError(f"the state grid is {self.nb} x {self.ne} nodes; each axis needs at least 2")
+        if self.nab < 1 or self.nae < 1:
+            raise ValueError(f"the action grid is {self.nab} x {self.nae} targets; each axis needs at least 1")
+        if self.nb * self.ne * 8 > MAX_PLANE_BYTES:
+            raise ValueError(f"a V plane of {self.nb} x {self.ne} nodes does not fit the {MAX_PLANE_BYTES} bytes of LDS a workgroup stages")
+
+    nodes = property(lambda self: self.nb * self.ne)
+    actions = property(lambda self: self.nab * self.nae)
+
+    def struct(self):
+        return GridStruct(self.nb, self.ne, self.nab, self.nae)
+
+    def soc_b_nodes(self, soc_max):
+        """Soc_b[i] = (float)(i * hb), hb = (double)soc_max / (nb - 1); the last node is soc_max itself."""
+        hb = float(np.float32(soc_max)) / (self.nb - 1)
+        x = np.array([np.float32(i * hb) for i in range(self.nb)], np.float32)
+        x[-1] = np.float32(soc_max)
+        return x
+
+    def soc_ev_nodes(self):
+        he = 1.0 / (self.ne - 1)
+        x = np.array([np.float32(j * he) for j in range(self.ne)], np.float32)
+        x[-1] = np.float32(1.0)
+        return x
+
+    @staticmethod
+    def _targets(n):
+        return np.array([1.0] if n == 1 else [np.float32(a / float(n - 1)) for a in range(n)], np.float32)
+
+    def b_targets(self):
+        return self._targets(self.nab)
+
+    def ev_targets(self):
+        return self._targets(self.nae)
+
+    def targets(self):
+        """[nab * nae][2] float32 (B_target, EV_target) in action-index order a = ab * nae + ae."""
+        b, e = self.b_targets(), self.ev_targets()
+        return np.stack([np.repeat(b, self.nae), np.tile(e, self.nab)], 1).astype(np.float32)
+
+    def __repr__(self):
+        return f"Grid(nb={self.nb}, ne={self.ne}, nab={self.nab}, nae={self.nae})"
+
+
+def interpolate(plane, grid, soc_max, soc_b, soc_ev):
+    """V off the nodes, the order of operations of fs_value (csrc/shems_foresight_core.h): per axis u = x * scale,
+    i = clamp(floor(u), 0, n - 2), f = clamp(u - i, 0, 1); V = (1 - fe) ((1 - fb) V00 + fb V10) + fe ((1 - fb) V01 + fb V11), all
+    in float64.  plane: [nb * ne] float64; soc_b / soc_ev: float32 arrays (or scalars)."""
+    V = np.asarray(plane, np.float64).reshape(grid.nb, grid.ne)
+    scale_b = (grid.nb - 1) / float(np.float32(soc_max))
+    scale_e = float(grid.ne - 1)
+
+    def axis(x, scale, n):
+        u = np.asarray(x, np.float32).astype(np.float64) * scale
+        fl = np.clip(np.floor(u), 0.0, float(n - 2))
+        return fl.astype(np.int64), np.clip(u - fl, 0.0, 1.0)
+
+    ib, fb = axis(soc_b, scale_b, grid.nb)
+    ie, fe = axis(soc_ev, scale_e, grid.ne)
+    V00, V01, V10, V11 = V[ib, ie], V[ib, ie + 1], V[ib + 1, ie], V[ib + 1, ie + 1]
+    return (1.0 - fe) * ((1.0 - fb) * V00 + fb * V10) + fe * ((1.0 - fb) * V01 + fb * V11)
+
+
+def make_problems(configs, idx0, nsteps, grid, total_rows=None):
+    """The shems_foresight_problem records of one call, validated on the host (ValueError before any device work).  scale_b / hb
+    are filled for the host side (Values.at); shems_foresight_solve_dev forms the device copy's own."""
+    cfgs = list(configs)
+    T = int(nsteps)
+    if not isinstance(grid, Grid):
+        raise TypeError("grid must be a foresight.Grid")
+    if not cfgs:
+        raise ValueError("solve needs at least one problem")
+    if T < 1:
+        raise ValueError(f"nsteps = {T}; the horizon must be at least 1 hour")
+    starts = [int(idx0)] * len(cfgs) if np.isscalar(idx0) else [int(i) for i in idx0]
+    if len(starts) != len(cfgs):
+        raise ValueError(f"idx0 holds {len(starts)} start rows for {len(cfgs)} problems")
+    recs = (Problem * len(cfgs))()
+    for p, (c, i0) in enumerate(zip(cfgs, starts)):
+        if c.table_row0 < 0 or c.nrow < 2 or (total_rows is not None and c.table_row0 + c.nrow > total_rows):
+            raise ValueError(f"problem {p} names table rows {c.table_row0} .. {c.table_row0 + c.nrow} of {total_rows}")
+        if i0 < 1 or i0 + T > c.nrow:
+            raise ValueError(f"problem {p}: the window of rows {i0} .. {i0 + T} runs off its table of {c.nrow} rows "
+                             "(a pass of n steps reads row n + 1)")
+        if not c.soc_max > 0:
+            raise ValueError(f"problem {p}: soc_max must be positive")
+        recs[p].cfg = c
+        recs[p].idx0 = i0
+        recs[p].scale_b = (grid.nb - 1) / float(c.soc_max)
+        recs[p].hb = float(c.soc_max) / (grid.nb - 1)
+    return recs
+
+
+def _declare(L):
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.shems_foresight_solve_dev.argtypes = [vp, i64, C.POINTER(Problem), vp, i32, C.POINTER(GridStruct), i32, vp, i64, vp, vp]
+    L.shems_foresight_solve_dev.restype = C.c_int
+    L.shems_foresight_track_dev.argtypes = [C.POINTER(_capi.View), vp, i32, vp, C.POINTER(GridStruct), i32, vp, i64, vp, i64, vp, vp, vp]
+    L.shems_foresight_track_dev.restype = C.c_int
+    return L
+
+
+class Values:
+    """What solve leaves on the device: V [P][T + 1][nb * ne] float64, the winning action index of every (problem, hour, node)
+    [P][T][nb * ne] int32, and the problem records the forward pass needs."""
+
+    def __init__(self, grid, nsteps, problems, d_problems, V, argmax, tables=None):
+        self.grid, self.nsteps, self.problems, self.d_problems, self.V, self.argmax, self._tables = grid, int(nsteps), problems, d_problems, V, argmax, tables
+        self.n_problems = len(problems)
+
+    def plane(self, p, t):
+        """V_t of problem p as a host array [nb][ne]."""
+        return self.V[int(p), int(t)].cpu().numpy().reshape(self.grid.nb, self.grid.ne)
+
+    def at(self, p, t, soc_b, soc_ev):
+        """V_t of problem p at an off-grid state: the device's interpolation restated on the host."""
+        out = interpolate(self.V[int(p), int(t)].cpu().numpy(), self.grid, self.problems[int(p)].cfg.soc_max, soc_b, soc_ev)
+        return float(out) if np.ndim(out) == 0 else out
+
+
+def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
+    """The backward sweep for P problems (table, config, 1-based start row) sharing the horizon `nsteps` and the grid: one foreign
+    call enqueues one launch per hour on PyTorch's current stream, no host synchronisation.  tables: a list of [nrow][8] float32
+    tables (configs[p].table_row0 / nrow name problem p's rows in their concatenation, as for ShemsBatch), or a ShemsBatch, whose
+    device-resident tables are then used.  configs: one Config per problem; idx0: one start row, or one per problem."""
+    import torch
+    from .env import ShemsBatch
+    grid = Grid() if grid is None else grid
+    env = tables if isinstance(tables, ShemsBatch) else None
+    rows = None
+    if env is None:
+        tabs = tables if isinstance(tables, (list, tuple)) else [tables]
+        tabs = [np.ascontiguousarray(t, dtype=np.float32) for t in tabs]
+        for t in tabs:
+            if t.ndim != 2 or t.shape[1] != _capi.NCOL:
+                raise ValueError("a table must be [nrow][8] float32")
+        rows = np.ascontiguousarray(np.concatenate(tabs, 0))
+        total_rows = rows.shape[0]
+    else:
+        total_rows = int(env.table_row0[-1] + env.table_nrow[-1])
+    problems = make_problems(configs, idx0, nsteps, grid, total_rows)
+    T, P, N = int(nsteps), len(problems), grid.nodes
+    L = _declare(_capi.lib())
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if env is None:
+        d_tables = torch.from_numpy(rows).to(dev)
+        tab_ptr = d_tables.data_ptr()
+    else:
+        env.use_torch_stream()
+        d_tables = env                                       # keeps the handle (and its tables) alive
+        tab_ptr = env.view().tables
+    d_prob = torch.empty(C.sizeof(problems), dtype=torch.uint8, device=dev)      # filled by the call, read by the sweep and by track
+    V = torch.empty((P, T + 1, N), dtype=torch.float64, device=dev)
+    arg = torch.empty((P, T, N), dtype=torch.int32, device=dev) if want_argmax else None
+    g = grid.struct()
+    _capi.check(L.shems_foresight_solve_dev(C.c_void_p(tab_ptr), total_rows, problems, C.c_void_p(d_prob.data_ptr()), P, C.byref(g), T,
+                                            C.c_void_p(V.data_ptr()), V.numel(), C.c_void_p(arg.data_ptr()) if arg is not None else None,
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return Values(grid, T, problems, d_prob, V, arg, d_tables)
+
+
+def track(env, values, problem_of_env=None, which=-1):
+    """The greedy controller on the exact env, from the envs' CURRENT state (reset them onto their problem's start row first): env e
+    runs values.nsteps hours of problem problem_of_env[e] (None: problem 0) in one launch.  Returns (totals [n] float64, results
+    [n][T][23] float64 -- [1][T][23] of env `which` when which >= 0 --, targets [n][T][2] float32, the chosen (B_target,
+    EV_target)).  An env that does not sit on its problem's start row raises BoundsError and is not stepped."""
+    import torch
+    L = _declare(_capi.lib())
+    n, T = env.n, values.nsteps
+    env.use_torch_stream()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    poe = None
+    if problem_of_env is not None:
+        po = np.ascontiguousarray(problem_of_env, dtype=np.int32)
+        if po.shape != (n,):
+            raise ValueError("problem_of_env must have shape (n_envs,)")
+        poe = torch.from_numpy(po).to(dev)
+    rows = n if which < 0 else 1
+    res = torch.empty((rows, T, _capi.NRESULT), dtype=torch.float64, device=dev)
+    total = torch.zeros(n, dtype=torch.float64, device=dev)
+    tgt = torch.zeros((n, T, 2), dtype=torch.float32, device=dev)
+    v = env.view()
+    g = values.grid.struct()
+    _capi.check(L.shems_foresight_track_dev(C.byref(v), C.c_void_p(values.d_problems.data_ptr()), values.n_problems,
+                                            C.c_void_p(poe.data_ptr()) if poe is not None else None, C.byref(g), T,
+                                            C.c_void_p(values.V.data_ptr()), values.V.numel(), C.c_void_p(res.data_ptr()), int(which),
+                                            C.c_void_p(total.data_ptr()), C.c_void_p(tgt.data_ptr()), env._stream()))
+    out, tot, targets = res.cpu().numpy(), total.cpu().numpy(), tgt.cpu().numpy()      # the pass's one synchronisation
+    env.check_error()
+    return tot, out, targets
+
+
+def problems_of_env(env, idx=None):
+    """One problem per distinct (config, start row) of a batch: returns (configs, idx0, problem_of_env).  idx: the envs' start rows
+    (default: where they sit now)."""
+    idx = np.asarray(env.idx if idx is None else idx, np.int64).reshape(env.n)
+    co = np.zeros(env.n, np.int64) if env.cfg_of_env is None else env.cfg_of_env.astype(np.int64)
+    keys, inv = np.unique(np.stack([co, idx], 1), axis=0, return_inverse=True)
+    return [env.configs[int(k[0])] for k in keys], [int(k[1]) for k in keys], np.asarray(inv, np.int32).reshape(env.n)

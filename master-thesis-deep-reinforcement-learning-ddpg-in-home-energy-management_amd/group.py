@@ -822,6 +822,29 @@ def eval_batch(tables, table_of_learner, count, test_runs=100, maxsteps=1439, ch
     return ShemsBatch(count * E_eval, int(maxsteps), tabs, cfgs, co, device=dev).use_torch_stream()
 
 
+def foresight_scores(env_eval, test_runs=100, grid=None, count=None):
+    """The perfect-foresight return next to score_mean: for an eval_batch, every learner's block is reset with Agent.run_episodes'
+    fixed key exactly as a sweep does (LearnerGroup._eval_returns), the backward sweep runs once per distinct (table, config, start
+    row) over the sweep's 72 hours, the greedy forward pass steps every env, and learner l's number is the mean of its first
+    test_runs returns summed in ascending order (float64 [count]).  count: learners of the batch (default: one block of E_eval =
+    test_runs rounded up to 32 per learner)."""
+    from . import foresight
+    from .env import EnvSlice
+    test_runs = int(test_runs)
+    E_eval = -(-test_runs // 32) * 32 if count is None else env_eval.n // int(count)
+    if test_runs < 1 or E_eval < test_runs or env_eval.n % E_eval:
+        raise ValueError(f"env_eval holds {env_eval.n} envs: not whole blocks of {E_eval} for test_runs = {test_runs} (eval_batch builds it)")
+    L = env_eval.n // E_eval
+    env_eval.use_torch_stream()
+    for l in range(L):
+        EnvSlice(env_eval, l * E_eval, E_eval).reset_(SEED_INI, episode=0)
+    cfgs, idx0, poe = foresight.problems_of_env(env_eval)
+    values = foresight.solve(env_eval, cfgs, idx0, EP_LENGTH_TRAIN, grid, want_argmax=False)
+    totals, _, _ = foresight.track(env_eval, values, poe, which=0)
+    r = totals.reshape(L, E_eval)[:, :test_runs]
+    return np.cumsum(r, axis=1)[:, -1] / test_runs
+
+
 class GroupWorkload:
     """bench.py's "group" step: one fused vector step of all learners' envs + one replay() of every learner."""
 

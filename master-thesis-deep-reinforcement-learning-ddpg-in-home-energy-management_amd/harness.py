@@ -93,6 +93,25 @@ def _track(env, actor, s_min, s_max, stride, track, num_steps, which, keep=None,
     return tot, out
 
 
+def inference_foresight(env, grid=None):
+    """The perfect-foresight pass over the data set: reset!(rng = -1), the backward sweep for the env's table(s) over env.maxsteps
+    hours (foresight.solve: one problem per distinct config of the batch) and the greedy forward pass on the exact env
+    (foresight.track), which steps the envs with the ordinary DRL step (track > 0: penalty kept, 23-column rows).  Returns what
+    inference_many returns -- (sum of rewards [N], results [N][steps][23] float64) -- so the file writers take it."""
+    from . import foresight
+    env.use_torch_stream()
+    env.reset_(-1)
+    cfgs, idx0, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+    values = foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
+    total, results, _ = foresight.track(env, values, poe, which=-1)
+    return total, results
+
+
+def foresight_file_name(job_id, run, case, out_dir="out/tracker"):
+    """The results file of the perfect-foresight pass, next to the rule-based one of results_file_name."""
+    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_foresight.csv")
+
+
 def results_file_name(job_id, run, ep_len, num_ep, l1, l2, case, rng, idx, best=False, out_dir="out/tracker"):
     """File names of write_to_results_file (MPS:170-187)."""
     if best:

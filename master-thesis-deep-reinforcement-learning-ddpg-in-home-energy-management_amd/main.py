@@ -20,6 +20,8 @@ Differences that follow from the platform, all explicit:
   * snapshots are BSON files under the reference's names, laid out as BSON.jl lowers a Chain (bson_chain.py; parity unpinned:
     the reference ships no real .bson to compare with);
   * SHEMS_NUM_ENVS (default 1 = the reference's protocol) trains that many households at once;
+  * SHEMS_FORESIGHT=1 adds, after the tracking block, the perfect-foresight pass over the tracked data set (foresight.py):
+    out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight";
   * random streams are Philox counters keyed by the same seeds (Julia's MersenneTwister streams do not exist outside Julia).
 """
 from __future__ import annotations
@@ -304,6 +306,12 @@ def main(environ=os.environ, cwd=".", log=print):
         path = harness.results_file_name(cfg.job_id, cfg.run, EP_LENGTH["train"], cfg.NUM_EP, cfg.L1, cfg.L2, cfg.case, cfg.track, idx)
         harness.write_to_results_file(results, path)
         harness.write_to_tracker_file(path, seed=idx, best=False, idx=idx, **tk)
+        written.append(path)
+    if environ.get("SHEMS_FORESIGHT") == "1":                            # this build's addition: the upper yardstick on the same table
+        _, results = harness.inference_foresight(env_track)
+        path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case)
+        harness.write_to_results_file(results[0], path)
+        harness.write_to_tracker_file(path, seed="foresight", best=False, idx=0, **tk)
         written.append(path)
     for e in (env_train, env_eval, env_track):
         e.close()

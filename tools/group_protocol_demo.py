@@ -7,7 +7,8 @@ score curve, best_run, and the eval score of the best actor next to the last one
 starts; the wall time of training next to that of all sweeps, and of one learner-by-learner sweep (400 Agent.episode_ calls) for
 comparison.  argv[3] = "latency" runs the same protocol on the five-launch form (fewer episodes advised).  argv[5] = households per
 learner (default 128; any multiple of 32: with argv[4] = 1 only household 0 feeds the learner, so 32 -- the smallest tile of the fused
-kernel -- is the closest this framework comes to the reference's ONE household per learner).
+kernel -- is the closest this framework comes to the reference's ONE household per learner).  The optional flag --foresight (anywhere
+on the command line) adds group.foresight_scores -- the perfect-foresight return on the same 100 starts -- per learner and per charger.
 Writes one JSON document to argv[1]."""
 import importlib
 import json
@@ -24,6 +25,8 @@ S = importlib.import_module(PKG)
 D = importlib.import_module(PKG + ".ddpg")
 G = importlib.import_module(PKG + ".group")
 
+FORESIGHT = "--foresight" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--foresight"]
 out_path = sys.argv[1] if len(sys.argv) > 1 else "group_protocol.json"
 episodes = int(sys.argv[2]) if len(sys.argv) > 2 else 1001
 form = sys.argv[3] if len(sys.argv) > 3 else "throughput"
@@ -91,6 +94,12 @@ doc = {"protocol": f"40 seeds x 10 chargers = 400 learners x {E} households, gro
        "learners_with_best_run": int((best_run > 0).sum()), "per_charger": per_charger,
        "learners": [{"learner": l, "charger": ids[l % len(ids)], "best_run": int(best_run[l]), "best_actor_score": float(best_score[l]),
                      "last_actor_score": float(last_score[l]), "score_mean": [round(float(x), 4) for x in score_mean[l]]} for l in range(L)]}
+if FORESIGHT:                                                # the upper yardstick on the sweeps' own starts (discretised: not a bound)
+    fs = G.foresight_scores(env_eval, TEST_RUNS)
+    for l in range(L):
+        doc["learners"][l]["foresight_score"] = float(fs[l])
+    for k, cid in enumerate(ids):
+        per_charger[str(cid)]["foresight"] = float(fs[k::len(ids)].mean())
 json.dump(doc, open(out_path, "w"), indent=1)
 print(json.dumps({k: doc[k] for k in ("form", "episodes", "sweeps_per_learner", "learners_with_best_run", "train_s", "sweeps_s",
                                       "sweep_share_of_run", "one_sweep_ms", "one_learner_by_learner_sweep_s", "learner_updates_per_s",
