@@ -670,6 +670,26 @@ typedef struct shems_foresight_problem {
 int shems_foresight_solve_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
                               shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
                               double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream);
+/* The receding-horizon controller: the same recursion with a LIMITED forecast.  The reference's optimiser is parameterised for it --
+ * `SHEMS python/run_SHEMS.py` builds its model with h_predict (hours forecast) and h_control (hours applied before it re-plans) and is
+ * only ever run with both equal to the whole series; `horizon` and `control` restate those two parameters:
+ *   horizon H >= 1          hours of forecast, the current hour included;
+ *   control c, 1 <= c <= H  a fresh plan every c hours.
+ * At decision hour t (0-based) the plan in force was made at j = t - t mod c and sees hours j .. hi - 1, hi = min(j + H, T); the
+ * controller takes the first maximum over the action grid of reward_t + U_{t+1}(state'), U_{t+1} = the optimal value of hours
+ * t + 1 .. hi - 1 with terminal value 0 (V[0] of shems_foresight_solve_dev on the window (idx0 + t + 1, hi - (t + 1)); zero when that
+ * length is 0).  csrc/shems_foresight_core.h holds the definition and the schedule.  The output is laid out as solve_dev's, so
+ * shems_foresight_track_dev reads it unchanged: V[p][t] = U_t for t = 1 .. T, V[p][T] = 0, V[p][0] = the value of the first plan at
+ * hour 0; d_argmax[p][t][node] (or NULL) = the action the controller takes at hour t from that node.  With horizon >= T every plane
+ * and index equals solve_dev's bit for bit; with horizon = 1 every plane t >= 1 is zero (the myopic controller).
+ * ONE launch on `stream`, grid = (ceil(T / c) windows, problems): a workgroup runs the sweeps of its window hi - 1 .. j + 1 (and j
+ * where V[p][0] or the arg-max needs it) with two V planes in LDS and stores only planes j + 1 .. min(j + c, T).  Few windows
+ * (problems x windows below the CU count) under-fill the device; for horizon >= T solve_dev is the tool.
+ * Arguments, validation, record completion and upload as shems_foresight_solve_dev; SHEMS_ERR_ARG, nothing launched, also for
+ * horizon < 1, control < 1, control > horizon, and a grid whose TWO planes exceed 150 000 bytes of LDS (129 x 65 fits: 134 160). */
+int shems_foresight_solve_horizon_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                                      shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
+                                      int32_t horizon, int32_t control, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream);
 /* The forward pass (LU1:283-316, 343-485, 264-281; MPS:62-89): the greedy controller on the EXACT env, shaped like shems_track_dev --
  * one workgroup per env, all T hours in one launch.  Env e belongs to problem d_problem_of_env[e] (NULL: problem 0).  At hour t every
  * action is evaluated from the env's true (off-grid) state with the same Q as the sweep, the arg-max is taken, and the env is stepped

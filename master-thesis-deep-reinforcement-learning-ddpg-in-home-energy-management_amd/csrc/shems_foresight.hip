@@ -8,6 +8,10 @@
 // (value, index) maximum is a butterfly over the wave with fs_better -- every lane ends with the same pair, lane 0 stores it.
 // Forward pass: one workgroup per env, all T hours inside the kernel (as k_track); the 256 threads evaluate the actions from the env's
 // true state against V_{t+1} in L2, the maximum goes wave -> LDS -> thread 0, which steps the env with the ordinary DRL step.
+// Receding horizon (shems_foresight_solve_horizon_dev, the schedule: shems_foresight_core.h): one launch, grid = (windows, problems).
+// The sweeps of a window depend only on each other, so its workgroup keeps them in LDS: two planes, hour t reads one and writes the
+// other, a workgroup barrier between sweeps and nothing else; no workgroup waits on another.  Nodes and actions are spread as in the
+// backward sweep (wave w: nodes w, w + waves, ...), and only the planes the forward pass will read leave the CU.
 //
 // Compiled with -ffp-contract=off (shems_core.h).
 #include <hip/hip_runtime.h>
@@ -23,6 +27,13 @@ namespace shems {
 
 constexpr int kFsThreads = 256, kFsWaves = kFsThreads / 64;
 constexpr int kFsMaxPlaneBytes = 150000;           // of the 160 KB of LDS a gfx950 workgroup can hold
+// k_fs_window: 16 waves, all a CU holds at the kernel's registers, in ONE workgroup -- whatever its two planes take of the CU's LDS
+// (34 KB at the default grid, 134 KB at 129 x 65), the CU is full.  A measuring build may set another size (_build.build(defines=...)).
+#ifndef SHEMS_FS_WINDOW_THREADS
+#define SHEMS_FS_WINDOW_THREADS 1024
+#endif
+constexpr int kFsWindowThreads = SHEMS_FS_WINDOW_THREADS;
+static_assert(kFsWindowThreads % 64 == 0 && kFsWindowThreads >= 64 && kFsWindowThreads <= 1024, "whole waves, at most 16");
 
 struct FsSolveArgs {
     const float *tables;
@@ -76,6 +87,77 @@ __global__ __launch_bounds__(kFsThreads) __attribute__((amdgpu_waves_per_eu(4)))
         if (lane == 0) {
             Vt[node] = best_v;
             if (A.arg) A.arg[((int64_t)p * A.T + A.t) * N + node] = best_a;
+        }
+    }
+}
+
+struct FsWindowArgs {
+    const float *tables;
+    const shems_foresight_problem *prob;
+    FsParams g;
+    int T, H, c;                                   // hours of the pass, horizon, control
+    double *V;
+    int32_t *arg;
+};
+
+// One workgroup = one plan: window j = blockIdx.x * c of problem blockIdx.y, hours hi - 1 down to fs_plan_first.  Sweep k stages its
+// two table rows in s_row[k & 1], reads plane k & 1 and writes the other; the one barrier per sweep orders all three (a wave that is
+// one sweep ahead writes what the sweep before the slower waves' current one read).  Registers as k_fs_backward: held to 4 waves per
+// SIMD (128 VGPRs), no scratch.
+__global__ __launch_bounds__(kFsWindowThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_fs_window(FsWindowArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_v[];            // [2][nb * ne]
+    __shared__ float s_row[2][2 * SHEMS_NCOL];                              // rows idx0 + t and idx0 + t + 1 of the sweep's hour
+    constexpr int threads = kFsWindowThreads, waves = threads / 64;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);              // the same in every lane: node indices stay in scalar registers
+    const int p = blockIdx.y, j = (int)blockIdx.x * A.c;
+    const FsParams &g = A.g;
+    const int N = g.nb * g.ne, NA = g.nab * g.nae;
+    const shems_foresight_problem P = A.prob[p];
+    const int hi = fs_plan_end(j, A.H, A.T), lo = fs_plan_first(j, A.arg != nullptr);
+    double *Vp = A.V + (int64_t)p * (A.T + 1) * N;
+    int32_t *argp = A.arg ? A.arg + (int64_t)p * A.T * N : nullptr;
+    const bool zeros_out = fs_plan_keeps_plane(j, A.c, A.T, hi);            // U_hi = 0: the plane the forward pass reads at hour hi - 1
+    for (int i = tid; i < N; i += threads) {
+        s_v[i] = 0.0;
+        if (zeros_out) Vp[(int64_t)hi * N + i] = 0.0;
+    }
+    int cur = 0;
+    for (int t = hi - 1; t >= lo; --t, cur ^= 1) {
+        const float *rows = A.tables + ((int64_t)P.cfg.table_row0 + P.idx0 + t - 1) * SHEMS_NCOL;      // the same address in every lane
+        if (wave == 0) {
+            int l = lane;
+            asm volatile("" : "+v"(l));                                      // formed here: no per-lane address lives across the sweeps
+            if (l < 2 * SHEMS_NCOL) s_row[cur][l] = rows[l];
+        }
+        __syncthreads();
+        const float *row = s_row[cur];
+        const double *Vn = s_v + cur * N;
+        double *Vt = s_v + (cur ^ 1) * N;
+        const bool v_out = fs_plan_keeps_plane(j, A.c, A.T, t), a_out = argp && fs_plan_keeps_argmax(j, A.c, A.T, t);
+        const float h_cur = row[0], h_next = row[SHEMS_NCOL], soc_ev_next = row[SHEMS_NCOL + 1];
+        for (int node = wave; node < N; node += waves) {                    // wave-uniform
+            const int ib = node / g.ne, ie = node - ib * g.ne;
+            const EnvIn s{fs_soc_b_node(P, g.nb, ib), fs_soc_ev_node(g, ie), h_cur, row[2], row[3], row[4]};
+            double best_v = -__builtin_inf();
+            int best_a = kFsNoAction;
+            for (int a = lane; a < NA; a += 64) {
+                const int ab = a / g.nae, ae = a - ab * g.nae;
+                const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), Vn, g, P.scale_b);
+                if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ov = __shfl_xor(best_v, off, 64);
+                const int oa = __shfl_xor(best_a, off, 64);
+                if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
+            }
+            if (lane == 0) {
+                Vt[node] = best_v;
+                if (v_out) Vp[(int64_t)t * N + node] = best_v;
+                if (a_out) argp[(int64_t)t * N + node] = best_a;
+            }
         }
     }
 }
@@ -201,21 +283,17 @@ static int fs_params(const shems_foresight_grid *grid, const char *fn, FsParams 
     return SHEMS_OK;
 }
 
-}  // namespace shems
-
-using namespace shems;
-
-extern "C" int shems_foresight_solve_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
-                                         shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid,
-                                         int32_t T, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream)
+// What both backward entry points check before any HIP call: the grid, T, the buffers and every problem record (`recs` receives the
+// records completed with scale_b / hb, as the kernels read them); fs_check_v: the size of the V buffer.
+static int fs_check_solve(const char *fn, const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                          const shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
+                          const double *d_V, FsParams &g, std::vector<shems_foresight_problem> &recs)
 {
-    const char *fn = "shems_foresight_solve_dev";
-    FsParams g;
     if (int rc = fs_params(grid, fn, g)) return rc;
     if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; the horizon must be at least 1 hour", fn, (int)T);
     if (!d_tables || total_rows < 2 || !problems || !d_problems || n_problems < 1 || n_problems > 65535 || !d_V)
         return set_error(SHEMS_ERR_ARG, "%s: NULL buffer, fewer than 2 table rows, or a problem count outside 1 .. 65535", fn);
-    std::vector<shems_foresight_problem> recs(problems, problems + n_problems);   // validated and completed here, then uploaded
+    recs.assign(problems, problems + n_problems);                            // validated and completed here, then uploaded
     for (int32_t p = 0; p < n_problems; ++p) {
         shems_foresight_problem &P = recs[p];
         if (P.cfg.table_row0 < 0 || P.cfg.nrow < 2 || (int64_t)P.cfg.table_row0 + P.cfg.nrow > total_rows)
@@ -229,18 +307,43 @@ extern "C" int shems_foresight_solve_dev(const float *d_tables, int64_t total_ro
         P.scale_b = (double)(g.nb - 1) / (double)P.cfg.soc_max;             // the only divisions of the sweep: float64, on the host
         P.hb = (double)P.cfg.soc_max / (double)(g.nb - 1);
     }
-    const int64_t N = (int64_t)g.nb * g.ne;
+    return SHEMS_OK;
+}
+
+static int fs_check_v(const char *fn, int32_t n_problems, int32_t T, int64_t N, int64_t v_doubles)
+{
     if (v_doubles < (int64_t)n_problems * (T + 1) * N)
         return set_error(SHEMS_ERR_ARG, "%s: the V buffer holds %lld float64; %d problems x %d planes x %lld nodes need %lld", fn, (long long)v_doubles,
                          (int)n_problems, (int)T + 1, (long long)N, (long long)n_problems * (T + 1) * N);
+    return SHEMS_OK;
+}
+
+// the records the kernels (and the forward pass) read: ordered on the stream; the runtime has staged a pageable source on return
+static int fs_upload(const std::vector<shems_foresight_problem> &recs, shems_foresight_problem *d_problems, hipStream_t st)
+{
+    return hip_ok(hipMemcpyAsync(d_problems, recs.data(), recs.size() * sizeof(shems_foresight_problem), hipMemcpyHostToDevice, st),
+                  "upload of the problem records");
+}
+
+}  // namespace shems
+
+using namespace shems;
+
+extern "C" int shems_foresight_solve_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                                         shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid,
+                                         int32_t T, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream)
+{
+    const char *fn = "shems_foresight_solve_dev";
+    FsParams g;
+    std::vector<shems_foresight_problem> recs;
+    if (int rc = fs_check_solve(fn, d_tables, total_rows, problems, d_problems, n_problems, grid, T, d_V, g, recs)) return rc;
+    const int64_t N = (int64_t)g.nb * g.ne;
+    if (int rc = fs_check_v(fn, n_problems, T, N, v_doubles)) return rc;
     const int lds = (int)(N * 8);
     static std::atomic<uint64_t> optin{0};                                  // per device, once: the largest plane fs_params admits
     if (int rc = lds_optin(optin, (const void *)k_fs_backward, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_backward)")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // the records the kernels (and the forward pass) read: ordered on the stream; the runtime has staged a pageable source on return
-    if (int rc = hip_ok(hipMemcpyAsync(d_problems, recs.data(), recs.size() * sizeof(shems_foresight_problem), hipMemcpyHostToDevice, st),
-                        "upload of the problem records"))
-        return rc;
+    if (int rc = fs_upload(recs, d_problems, st)) return rc;
     const int64_t total = (int64_t)n_problems * N;
     hipLaunchKernelGGL(k_fs_zero, dim3((unsigned)((total + kFsThreads - 1) / kFsThreads)), dim3(kFsThreads), 0, st, d_V, N, (int64_t)(T + 1) * N, total);
     if (int rc = hip_ok(hipGetLastError(), "k_fs_zero launch")) return rc;
@@ -256,6 +359,35 @@ extern "C" int shems_foresight_solve_dev(const float *d_tables, int64_t total_ro
         hipLaunchKernelGGL(k_fs_backward, gridDim, dim3(kFsThreads), lds, st, a);
     }
     return hip_ok(hipGetLastError(), "k_fs_backward launch");
+}
+
+extern "C" int shems_foresight_solve_horizon_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                                                 shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid,
+                                                 int32_t T, int32_t horizon, int32_t control, double *d_V, int64_t v_doubles,
+                                                 int32_t *d_argmax, void *stream)
+{
+    const char *fn = "shems_foresight_solve_horizon_dev";
+    FsParams g;
+    std::vector<shems_foresight_problem> recs;
+    if (int rc = fs_check_solve(fn, d_tables, total_rows, problems, d_problems, n_problems, grid, T, d_V, g, recs)) return rc;
+    if (horizon < 1) return set_error(SHEMS_ERR_ARG, "%s: horizon = %d; a plan sees at least the current hour", fn, (int)horizon);
+    if (control < 1 || control > horizon)
+        return set_error(SHEMS_ERR_ARG, "%s: control = %d; a fresh plan every 1 .. horizon = %d hours", fn, (int)control, (int)horizon);
+    const int64_t N = (int64_t)g.nb * g.ne;
+    if (2 * N * 8 > kFsMaxPlaneBytes)
+        return set_error(SHEMS_ERR_ARG, "%s: the two V planes of %d x %d nodes a window keeps take %lld bytes of LDS; a workgroup has %d for them", fn,
+                         (int)g.nb, (int)g.ne, (long long)(2 * N * 8), kFsMaxPlaneBytes);
+    if (int rc = fs_check_v(fn, n_problems, T, N, v_doubles)) return rc;
+    const int lds = (int)(2 * N * 8);
+    static std::atomic<uint64_t> optin{0};
+    if (int rc = lds_optin(optin, (const void *)k_fs_window, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_window)")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = fs_upload(recs, d_problems, st)) return rc;
+    FsWindowArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.tables = d_tables; a.prob = d_problems; a.g = g; a.T = T; a.H = horizon; a.c = control; a.V = d_V; a.arg = d_argmax;
+    hipLaunchKernelGGL(k_fs_window, dim3((unsigned)fs_plan_windows(T, control), (unsigned)n_problems), dim3(kFsWindowThreads), lds, st, a);
+    return hip_ok(hipGetLastError(), "k_fs_window launch");
 }
 
 extern "C" int shems_foresight_track_dev(const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,

@@ -76,4 +76,27 @@ SHEMS_HD bool fs_better(double v, int a, double best_v, int best_a) { return v >
 
 constexpr int kFsNoAction = 0x7fffffff;          // the index of "nothing evaluated yet": loses every tie
 
+// ---- the receding-horizon schedule (shems_foresight_solve_horizon_dev; foresight.horizon_plan restates it) ----
+// The deployable controller sees a limited forecast.  Two integers are shared by all problems of a call:
+//   horizon H >= 1         hours of forecast, the current hour included;
+//   control c, 1 <= c <= H a fresh plan every c hours.
+// For decision hour t (0-based) of a T-hour pass the plan in force was made at j = t - t mod c; it sees hours j .. hi - 1 with
+// hi = min(j + H, T); the controller takes the first maximum over the action grid of reward_t + U_{t+1}(state'), where U_{t+1} is the
+// optimal value of hours t + 1 .. hi - 1 with terminal value 0: the plane V[0] of the ordinary backward sweep on the window
+// (idx0 + t + 1, nsteps = hi - (t + 1)), the zero plane when that length is 0.  The planes are laid out as the ordinary sweep's, so
+// the forward pass reads them unchanged: V[p][t] = U_t for t = 1 .. T (what the forward pass reads at hour t - 1), V[p][T] = 0,
+// V[p][0] = the value of the first plan at hour 0; argmax[p][t][node] = the action the controller takes at hour t from that node.
+// Window j (the plans are made at j = 0, c, 2c, ...) therefore sweeps hours hi - 1 down to j + 1 -- and hour j itself where its
+// arg-max or V[p][0] is wanted --, and of those it keeps planes j + 1 .. min(j + c, T) and arg-max j .. min(j + c, T) - 1.
+// All arguments are taken as validated (T >= 1, 1 <= c <= H, 0 <= j < T); no sum here can overflow an int.
+SHEMS_HD int fs_plan_windows(int T, int c) { return (T - 1) / c + 1; }                        // ceil(T / c)
+SHEMS_HD int fs_plan_of_hour(int t, int c) { return t - t % c; }                              // j: the hour the plan in force at t was made
+SHEMS_HD int fs_plan_end(int j, int H, int T) { return H < T - j ? j + H : T; }               // hi: the plan sees hours j .. hi - 1
+SHEMS_HD int fs_plan_keep(int j, int c, int T) { return c < T - j ? j + c : T; }              // the last hour window j answers for, + 1
+SHEMS_HD int fs_plan_first(int j, bool want_argmax) { return (want_argmax || j == 0) ? j : j + 1; }   // the earliest hour window j sweeps
+// Where window j's results go: the plane of hour t (a swept hour, or hi with its zeros) into V[p][t], the arg-max of a swept hour t
+// into argmax[p][t].
+SHEMS_HD bool fs_plan_keeps_plane(int j, int c, int T, int t) { return t == 0 || (t > j && t <= fs_plan_keep(j, c, T)); }
+SHEMS_HD bool fs_plan_keeps_argmax(int j, int c, int T, int t) { return t >= j && t < fs_plan_keep(j, c, T); }
+
 }  // namespace shems

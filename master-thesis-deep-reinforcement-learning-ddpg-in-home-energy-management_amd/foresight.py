@@ -7,6 +7,9 @@ memory_plotting_saving.jl:62-89) is a finite-horizon dynamic programme over (Soc
 
     solve(tables, configs, idx0, nsteps, grid) -> Values      the backward sweep, V float64 [P][T + 1][nb * ne]  (shems_foresight_solve_dev)
     track(env, values, problem_of_env, which)                 the greedy controller on the exact env, one launch    (shems_foresight_track_dev)
+    solve_horizon(tables, configs, idx0, nsteps, horizon, control) -> Values
+                                                              the same recursion with `horizon` hours of forecast and a fresh plan
+                                                              every `control` hours, one launch     (shems_foresight_solve_horizon_dev)
 
 The arithmetic lives in csrc/shems_foresight_core.h; Values.at restates its interpolation on the host, bit for bit.  A discretised
 value function with a greedy policy is NOT a bound: V_0 at the start state and the achieved return differ by the discretisation error.
@@ -31,7 +34,7 @@ class Problem(C.Structure):               # shems_foresight_problem
 
 assert C.sizeof(Problem) == 72 and C.sizeof(GridStruct) == 16
 
-MAX_PLANE_BYTES = 150000                  # a workgroup of the sweep stages one V plane in LDS
+MAX_PLANE_BYTES = 150000                  # a workgroup of the sweep stages one V plane in LDS; one of solve_horizon keeps two
 
 
 class Grid:
@@ -138,6 +141,8 @@ def _declare(L):
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.shems_foresight_solve_dev.argtypes = [vp, i64, C.POINTER(Problem), vp, i32, C.POINTER(GridStruct), i32, vp, i64, vp, vp]
     L.shems_foresight_solve_dev.restype = C.c_int
+    L.shems_foresight_solve_horizon_dev.argtypes = [vp, i64, C.POINTER(Problem), vp, i32, C.POINTER(GridStruct), i32, i32, i32, vp, i64, vp, vp]
+    L.shems_foresight_solve_horizon_dev.restype = C.c_int
     L.shems_foresight_track_dev.argtypes = [C.POINTER(_capi.View), vp, i32, vp, C.POINTER(GridStruct), i32, vp, i64, vp, i64, vp, vp, vp]
     L.shems_foresight_track_dev.restype = C.c_int
     return L
@@ -145,11 +150,13 @@ def _declare(L):
 
 class Values:
     """What solve leaves on the device: V [P][T + 1][nb * ne] float64, the winning action index of every (problem, hour, node)
-    [P][T][nb * ne] int32, and the problem records the forward pass needs."""
+    [P][T][nb * ne] int32, and the problem records the forward pass needs.  horizon / control: what solve_horizon was given (None
+    from solve: the whole pass is known)."""
 
-    def __init__(self, grid, nsteps, problems, d_problems, V, argmax, tables=None):
+    def __init__(self, grid, nsteps, problems, d_problems, V, argmax, tables=None, horizon=None, control=None):
         self.grid, self.nsteps, self.problems, self.d_problems, self.V, self.argmax, self._tables = grid, int(nsteps), problems, d_problems, V, argmax, tables
         self.n_problems = len(problems)
+        self.horizon, self.control = horizon, control
 
     def plane(self, p, t):
         """V_t of problem p as a host array [nb][ne]."""
@@ -161,11 +168,28 @@ class Values:
         return float(out) if np.ndim(out) == 0 else out
 
 
-def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
-    """The backward sweep for P problems (table, config, 1-based start row) sharing the horizon `nsteps` and the grid: one foreign
-    call enqueues one launch per hour on PyTorch's current stream, no host synchronisation.  tables: a list of [nrow][8] float32
-    tables (configs[p].table_row0 / nrow name problem p's rows in their concatenation, as for ShemsBatch), or a ShemsBatch, whose
-    device-resident tables are then used.  configs: one Config per problem; idx0: one start row, or one per problem."""
+def horizon_plan(T, horizon, control=1):
+    """The receding-horizon schedule of csrc/shems_foresight_core.h restated: for the decision hours t = 0 .. T - 1, j[t] = the hour
+    the plan in force was made (t - t mod control) and k[t] = the look-ahead length after hour t, hi - (t + 1) with
+    hi = min(j + horizon, T): U_{t+1}, the plane V[p][t + 1], is the value of those k[t] hours (zero for k[t] = 0).  Two int64 arrays."""
+    T, H, c = _check_horizon(T, horizon, control)
+    t = np.arange(T, dtype=np.int64)
+    j = t - t % c
+    return j, np.minimum(j + H, T) - (t + 1)
+
+
+def _check_horizon(T, horizon, control):
+    T, H, c = int(T), int(horizon), int(control)
+    if T < 1:
+        raise ValueError(f"nsteps = {T}; the pass must be at least 1 hour")
+    if H < 1:
+        raise ValueError(f"horizon = {H}; a plan sees at least the current hour")
+    if c < 1 or c > H:
+        raise ValueError(f"control = {c}; a fresh plan every 1 .. horizon = {H} hours")
+    return T, H, c
+
+
+def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, control=None):
     import torch
     from .env import ShemsBatch
     grid = Grid() if grid is None else grid
@@ -183,6 +207,11 @@ def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
         total_rows = int(env.table_row0[-1] + env.table_nrow[-1])
     problems = make_problems(configs, idx0, nsteps, grid, total_rows)
     T, P, N = int(nsteps), len(problems), grid.nodes
+    if horizon is not None:
+        _, horizon, control = _check_horizon(T, horizon, control)
+        if 2 * N * 8 > MAX_PLANE_BYTES:
+            raise ValueError(f"the two V planes of {grid.nb} x {grid.ne} nodes a window keeps take {2 * N * 8} bytes of LDS; "
+                             f"a workgroup has {MAX_PLANE_BYTES} for them")
     L = _declare(_capi.lib())
     dev = torch.device("cuda", torch.cuda.current_device())
     if env is None:
@@ -196,10 +225,35 @@ def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
     V = torch.empty((P, T + 1, N), dtype=torch.float64, device=dev)
     arg = torch.empty((P, T, N), dtype=torch.int32, device=dev) if want_argmax else None
     g = grid.struct()
-    _capi.check(L.shems_foresight_solve_dev(C.c_void_p(tab_ptr), total_rows, problems, C.c_void_p(d_prob.data_ptr()), P, C.byref(g), T,
-                                            C.c_void_p(V.data_ptr()), V.numel(), C.c_void_p(arg.data_ptr()) if arg is not None else None,
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    return Values(grid, T, problems, d_prob, V, arg, d_tables)
+    head = (C.c_void_p(tab_ptr), total_rows, problems, C.c_void_p(d_prob.data_ptr()), P, C.byref(g), T)
+    tail = (C.c_void_p(V.data_ptr()), V.numel(), C.c_void_p(arg.data_ptr()) if arg is not None else None,
+            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if horizon is None:
+        _capi.check(L.shems_foresight_solve_dev(*head, *tail))
+    else:
+        _capi.check(L.shems_foresight_solve_horizon_dev(*head, horizon, control, *tail))
+    return Values(grid, T, problems, d_prob, V, arg, d_tables, horizon, control)
+
+
+def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
+    """The backward sweep for P problems (table, config, 1-based start row) sharing the horizon `nsteps` and the grid: one foreign
+    call enqueues one launch per hour on PyTorch's current stream, no host synchronisation.  tables: a list of [nrow][8] float32
+    tables (configs[p].table_row0 / nrow name problem p's rows in their concatenation, as for ShemsBatch), or a ShemsBatch, whose
+    device-resident tables are then used.  configs: one Config per problem; idx0: one start row, or one per problem."""
+    return _solve(tables, configs, idx0, nsteps, grid, want_argmax)
+
+
+def solve_horizon(tables, configs, idx0, nsteps, horizon, control=1, grid=None, want_argmax=True):
+    """The receding-horizon controller's planes for P problems, arguments as solve: at hour t the plan made at j = t - t mod control
+    sees hours j .. min(j + horizon, nsteps) - 1 (horizon_plan; the definition: csrc/shems_foresight_core.h).  Values.V[p][t] is
+    what track reads at hour t - 1, V[p][0] the value of the first plan, argmax[p][t] the action taken at hour t from each node;
+    with horizon >= nsteps they equal solve's bit for bit.  One launch on PyTorch's current stream (shems_foresight_solve_horizon_dev),
+    one workgroup per (window of `control` hours, problem) with its planes in LDS, no host synchronisation; a state grid whose two
+    planes exceed 150 000 bytes is refused (129 x 65 fits).  The call always runs the window kernel: with few windows (problems x
+    ceil(nsteps / control) below the device's CU count) it under-fills the device, and for horizon >= nsteps solve is the tool."""
+    if horizon is None:
+        raise ValueError("solve_horizon needs a horizon (solve knows the whole pass)")
+    return _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon, control)
 
 
 def track(env, values, problem_of_env=None, which=-1):

@@ -822,12 +822,13 @@ def eval_batch(tables, table_of_learner, count, test_runs=100, maxsteps=1439, ch
     return ShemsBatch(count * E_eval, int(maxsteps), tabs, cfgs, co, device=dev).use_torch_stream()
 
 
-def foresight_scores(env_eval, test_runs=100, grid=None, count=None):
+def foresight_scores(env_eval, test_runs=100, grid=None, count=None, horizon=None, control=1):
     """The perfect-foresight return next to score_mean: for an eval_batch, every learner's block is reset with Agent.run_episodes'
     fixed key exactly as a sweep does (LearnerGroup._eval_returns), the backward sweep runs once per distinct (table, config, start
     row) over the sweep's 72 hours, the greedy forward pass steps every env, and learner l's number is the mean of its first
     test_runs returns summed in ascending order (float64 [count]).  count: learners of the batch (default: one block of E_eval =
-    test_runs rounded up to 32 per learner)."""
+    test_runs rounded up to 32 per learner).  horizon: the receding-horizon controller's return instead (foresight.solve_horizon with
+    `horizon` hours of forecast and a fresh plan every `control` hours)."""
     from . import foresight
     from .env import EnvSlice
     test_runs = int(test_runs)
@@ -839,7 +840,10 @@ def foresight_scores(env_eval, test_runs=100, grid=None, count=None):
     for l in range(L):
         EnvSlice(env_eval, l * E_eval, E_eval).reset_(SEED_INI, episode=0)
     cfgs, idx0, poe = foresight.problems_of_env(env_eval)
-    values = foresight.solve(env_eval, cfgs, idx0, EP_LENGTH_TRAIN, grid, want_argmax=False)
+    if horizon is None:
+        values = foresight.solve(env_eval, cfgs, idx0, EP_LENGTH_TRAIN, grid, want_argmax=False)
+    else:
+        values = foresight.solve_horizon(env_eval, cfgs, idx0, EP_LENGTH_TRAIN, horizon, control, grid, want_argmax=False)
     totals, _, _ = foresight.track(env_eval, values, poe, which=0)
     r = totals.reshape(L, E_eval)[:, :test_runs]
     return np.cumsum(r, axis=1)[:, -1] / test_runs

@@ -93,23 +93,35 @@ def _track(env, actor, s_min, s_max, stride, track, num_steps, which, keep=None,
     return tot, out
 
 
-def inference_foresight(env, grid=None):
+def inference_foresight(env, grid=None, horizon=None, control=1):
     """The perfect-foresight pass over the data set: reset!(rng = -1), the backward sweep for the env's table(s) over env.maxsteps
     hours (foresight.solve: one problem per distinct config of the batch) and the greedy forward pass on the exact env
     (foresight.track), which steps the envs with the ordinary DRL step (track > 0: penalty kept, 23-column rows).  Returns what
-    inference_many returns -- (sum of rewards [N], results [N][steps][23] float64) -- so the file writers take it."""
+    inference_many returns -- (sum of rewards [N], results [N][steps][23] float64) -- so the file writers take it.  horizon: the
+    receding-horizon controller instead (foresight.solve_horizon: `horizon` hours of forecast, a fresh plan every `control` hours)."""
     from . import foresight
     env.use_torch_stream()
     env.reset_(-1)
     cfgs, idx0, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
-    values = foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
+    if horizon is None:
+        values = foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
+    else:
+        values = foresight.solve_horizon(env, cfgs, idx0, env.maxsteps, horizon, control, grid, want_argmax=False)
     total, results, _ = foresight.track(env, values, poe, which=-1)
     return total, results
 
 
-def foresight_file_name(job_id, run, case, out_dir="out/tracker"):
-    """The results file of the perfect-foresight pass, next to the rule-based one of results_file_name."""
-    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_foresight.csv")
+def foresight_seed(horizon=None, control=1):
+    """The tracker's seed column (and the file-name suffix) of a foresight pass: foresight, foresight_h24, foresight_h24_c12."""
+    if horizon is None:
+        return "foresight"
+    return f"foresight_h{int(horizon)}" + (f"_c{int(control)}" if int(control) != 1 else "")
+
+
+def foresight_file_name(job_id, run, case, out_dir="out/tracker", horizon=None, control=1):
+    """The results file of the perfect-foresight pass, next to the rule-based one of results_file_name; with a horizon, of the
+    receding-horizon pass: ..._foresight_h{H}.csv, ..._foresight_h{H}_c{c}.csv when control != 1."""
+    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_{foresight_seed(horizon, control)}.csv")
 
 
 def results_file_name(job_id, run, ep_len, num_ep, l1, l2, case, rng, idx, best=False, out_dir="out/tracker"):

@@ -21,7 +21,9 @@ Differences that follow from the platform, all explicit:
     the reference ships no real .bson to compare with);
   * SHEMS_NUM_ENVS (default 1 = the reference's protocol) trains that many households at once;
   * SHEMS_FORESIGHT=1 adds, after the tracking block, the perfect-foresight pass over the tracked data set (foresight.py):
-    out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight";
+    out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight"; with it,
+    SHEMS_FORESIGHT_HORIZON (hours of forecast: one integer or a comma list) and SHEMS_FORESIGHT_CONTROL (hours between plans,
+    default 1) add one receding-horizon pass per horizon: ..._foresight_h24.csv / ..._foresight_h24_c12.csv, seed = that suffix;
   * random streams are Philox counters keyed by the same seeds (Julia's MersenneTwister streams do not exist outside Julia).
 """
 from __future__ import annotations
@@ -181,6 +183,31 @@ def config_from_env(environ=os.environ):
     return cfg
 
 
+def foresight_horizons(environ=os.environ):
+    """SHEMS_FORESIGHT_HORIZON (one integer or a comma list, each >= 1) and SHEMS_FORESIGHT_CONTROL (one integer, default 1, at most
+    the smallest horizon) -> ([horizons], control); ([], 1) when no horizon is named.  A malformed value is refused by name."""
+    raw, raw_c = environ.get("SHEMS_FORESIGHT_HORIZON"), environ.get("SHEMS_FORESIGHT_CONTROL")
+    try:
+        control = 1 if raw_c is None else int(raw_c)
+    except ValueError:
+        raise ValueError(f"SHEMS_FORESIGHT_CONTROL = {raw_c!r} is not an integer") from None
+    if control < 1:
+        raise ValueError(f"SHEMS_FORESIGHT_CONTROL = {raw_c!r}: a fresh plan every 1 or more hours")
+    if raw is None:
+        if raw_c is not None:
+            raise ValueError("SHEMS_FORESIGHT_CONTROL is set without SHEMS_FORESIGHT_HORIZON")
+        return [], 1
+    try:
+        horizons = [int(x) for x in raw.split(",")]
+    except ValueError:
+        raise ValueError(f"SHEMS_FORESIGHT_HORIZON = {raw!r} is not an integer or a comma list of integers") from None
+    if min(horizons) < 1:
+        raise ValueError(f"SHEMS_FORESIGHT_HORIZON = {raw!r}: a plan sees at least the current hour")
+    if control > min(horizons):
+        raise ValueError(f"SHEMS_FORESIGHT_CONTROL = {control} exceeds a horizon of SHEMS_FORESIGHT_HORIZON = {raw!r}")
+    return horizons, control
+
+
 def _check_supported(cfg):
     # (250, 500): the tuned kernels; smaller: zero-padded into them (ddpg.pad_net); larger -- the grids' (300, 600) --: the layer-by-layer
     # wide path (csrc/shems_wide.hip, ddpg.is_wide)
@@ -214,6 +241,7 @@ def main(environ=os.environ, cwd=".", log=print):
 
     cfg = config_from_env(environ)
     _check_supported(cfg)
+    horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
     os.chdir(cwd)
     torch.cuda.set_device(cfg.gpu_id)                                    # CUDA.device!(gpu_id), MAIN:12-14
     if cfg.seed_run == 1:
@@ -313,6 +341,12 @@ def main(environ=os.environ, cwd=".", log=print):
         harness.write_to_results_file(results[0], path)
         harness.write_to_tracker_file(path, seed="foresight", best=False, idx=0, **tk)
         written.append(path)
+        for h in horizons:                                               # the deployable case: h hours of forecast, a plan every `control`
+            _, results = harness.inference_foresight(env_track, horizon=h, control=control)
+            path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case, horizon=h, control=control)
+            harness.write_to_results_file(results[0], path)
+            harness.write_to_tracker_file(path, seed=harness.foresight_seed(h, control), best=False, idx=0, **tk)
+            written.append(path)
     for e in (env_train, env_eval, env_track):
         e.close()
     log(f"Script with JOB_ID: {cfg.job_id} & TASK_ID: {cfg.task_id} is done!")
