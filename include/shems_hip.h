@@ -655,7 +655,9 @@ typedef struct shems_foresight_grid {
 typedef struct shems_foresight_problem {
     shems_config cfg;        /* table_row0 / nrow name the problem's table in the uploaded row array                              */
     int32_t idx0;            /* 1-based start row: idx0 >= 1 and idx0 + T <= nrow (a pass of n steps reads row n + 1)              */
-    int32_t reserved;        /* 0                                                                                                  */
+    int32_t forecast_off;    /* rows from the table to its forecast table (same nrow, same row array): the forecast of table row r   */
+                             /* is array row table_row0 + forecast_off + r; 0: the truth is the forecast; may be negative.  Read by  */
+                             /* shems_foresight_solve_forecast_dev only: the other solve calls write 0 into the device copy.         */
     double  scale_b;         /* (nb - 1) / (double)soc_max, formed ONCE on the host in float64: the device never divides.  Filled   */
     double  hb;              /* (double)soc_max / (nb - 1).                        by shems_foresight_solve_dev in the device copy   */
 } shems_foresight_problem;   /* 72 bytes */
@@ -701,6 +703,29 @@ int shems_foresight_solve_horizon_dev(const float *d_tables, int64_t total_rows,
 int shems_foresight_track_dev(const shems_view *v, const shems_foresight_problem *d_problems /* as solve_dev left them */, int32_t n_problems,
                               const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V,
                               int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream);
+/* The receding-horizon controller planning on a FORECAST that may be wrong.  The reference's optimiser has the knobs (`SHEMS
+ * python/run_SHEMS.py`: h_predict, h_control) and is only ever fed the true series; here the plan made at hour j reads the TRUE rows
+ * up to j and the rows of the problem's forecast table (forecast_off above) after it: a sweep of hour t inside window j takes its
+ * current row from the truth if t == j and from the forecast otherwise, its next row always from the forecast.  Everything
+ * shems_foresight_solve_horizon_dev defines holds unchanged on that belief (csrc/shems_foresight_core.h: the definition and
+ * fs_belief_off); with forecast_off = 0 in every record, or forecast tables that are byte copies of the truth, every plane and index
+ * equals solve_horizon_dev's bit for bit.  Arguments as shems_foresight_solve_horizon_dev, but cfg, idx0 AND forecast_off of the host
+ * records are read.  SHEMS_ERR_ARG, nothing launched: everything solve_horizon_dev refuses, and a forecast table that leaves the row
+ * array (table_row0 + forecast_off < 0 or table_row0 + forecast_off + nrow > total_rows; the message names the problem and both row
+ * numbers).  ONE launch (k_fs_window_fc). */
+int shems_foresight_solve_forecast_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                                       shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
+                                       int32_t horizon, int32_t control, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream);
+/* The forward pass of that controller (LU1:283-316, 343-485; the arrival overwrite LU1:264-281): as shems_foresight_track_dev, but at
+ * hour t the controller does not yet know row t + 1, so the arrival overwrite inside Q takes h_countdown and soc_ev of the next row
+ * from the FORECAST row (forecast_off of the device records, as solve_forecast_dev left them); h_cur stays the truth's and the env is
+ * stepped on the truth by the ordinary DRL step.  The view's row array must hold the tables the solve call saw, in the same order: an
+ * env whose problem's forecast table does not lie inside view.total_rows raises view.err = SHEMS_ERR_INDEX and is not stepped, like
+ * one that does not sit on its start row. */
+int shems_foresight_track_forecast_dev(const shems_view *v, const shems_foresight_problem *d_problems /* as solve_forecast_dev left them */,
+                                       int32_t n_problems, const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T,
+                                       const double *d_V, int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns,
+                                       float *d_targets, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,9 @@
 // The sweeps of a window depend only on each other, so its workgroup keeps them in LDS: two planes, hour t reads one and writes the
 // other, a workgroup barrier between sweeps and nothing else; no workgroup waits on another.  Nodes and actions are spread as in the
 // backward sweep (wave w: nodes w, w + waves, ...), and only the planes the forward pass will read leave the CU.
+// Planning on a forecast (shems_foresight_solve_forecast_dev / _track_forecast_dev, the belief: shems_foresight_core.h): the same two
+// kernels with their rows taken where fs_belief_off says -- k_fs_window_fc, k_fs_track_fc; the bodies are fs_window_body.h and
+// fs_track_body.h, included into both kernels of a pair.
 //
 // Compiled with -ffp-contract=off (shems_core.h).
 #include <hip/hip_runtime.h>
@@ -106,60 +109,15 @@ struct FsWindowArgs {
 // SIMD (128 VGPRs), no scratch.
 __global__ __launch_bounds__(kFsWindowThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_fs_window(FsWindowArgs A)
 {
-    extern __shared__ __attribute__((aligned(16))) double s_v[];            // [2][nb * ne]
-    __shared__ float s_row[2][2 * SHEMS_NCOL];                              // rows idx0 + t and idx0 + t + 1 of the sweep's hour
-    constexpr int threads = kFsWindowThreads, waves = threads / 64;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);              // the same in every lane: node indices stay in scalar registers
-    const int p = blockIdx.y, j = (int)blockIdx.x * A.c;
-    const FsParams &g = A.g;
-    const int N = g.nb * g.ne, NA = g.nab * g.nae;
-    const shems_foresight_problem P = A.prob[p];
-    const int hi = fs_plan_end(j, A.H, A.T), lo = fs_plan_first(j, A.arg != nullptr);
-    double *Vp = A.V + (int64_t)p * (A.T + 1) * N;
-    int32_t *argp = A.arg ? A.arg + (int64_t)p * A.T * N : nullptr;
-    const bool zeros_out = fs_plan_keeps_plane(j, A.c, A.T, hi);            // U_hi = 0: the plane the forward pass reads at hour hi - 1
-    for (int i = tid; i < N; i += threads) {
-        s_v[i] = 0.0;
-        if (zeros_out) Vp[(int64_t)hi * N + i] = 0.0;
-    }
-    int cur = 0;
-    for (int t = hi - 1; t >= lo; --t, cur ^= 1) {
-        const float *rows = A.tables + ((int64_t)P.cfg.table_row0 + P.idx0 + t - 1) * SHEMS_NCOL;      // the same address in every lane
-        if (wave == 0) {
-            int l = lane;
-            asm volatile("" : "+v"(l));                                      // formed here: no per-lane address lives across the sweeps
-            if (l < 2 * SHEMS_NCOL) s_row[cur][l] = rows[l];
-        }
-        __syncthreads();
-        const float *row = s_row[cur];
-        const double *Vn = s_v + cur * N;
-        double *Vt = s_v + (cur ^ 1) * N;
-        const bool v_out = fs_plan_keeps_plane(j, A.c, A.T, t), a_out = argp && fs_plan_keeps_argmax(j, A.c, A.T, t);
-        const float h_cur = row[0], h_next = row[SHEMS_NCOL], soc_ev_next = row[SHEMS_NCOL + 1];
-        for (int node = wave; node < N; node += waves) {                    // wave-uniform
-            const int ib = node / g.ne, ie = node - ib * g.ne;
-            const EnvIn s{fs_soc_b_node(P, g.nb, ib), fs_soc_ev_node(g, ie), h_cur, row[2], row[3], row[4]};
-            double best_v = -__builtin_inf();
-            int best_a = kFsNoAction;
-            for (int a = lane; a < NA; a += 64) {
-                const int ab = a / g.nae, ae = a - ab * g.nae;
-                const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), Vn, g, P.scale_b);
-                if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ov = __shfl_xor(best_v, off, 64);
-                const int oa = __shfl_xor(best_a, off, 64);
-                if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
-            }
-            if (lane == 0) {
-                Vt[node] = best_v;
-                if (v_out) Vp[(int64_t)t * N + node] = best_v;
-                if (a_out) argp[(int64_t)t * N + node] = best_a;
-            }
-        }
-    }
+    constexpr bool FC = false;
+#include "fs_window_body.h"
+}
+
+// The window kernel under a belief: the same body, the rows of a sweep taken where fs_belief_off says (fs_window_body.h).
+__global__ __launch_bounds__(kFsWindowThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_fs_window_fc(FsWindowArgs A)
+{
+    constexpr bool FC = true;
+#include "fs_window_body.h"
 }
 
 struct FsTrackArgs {
@@ -178,91 +136,15 @@ struct FsTrackArgs {
 
 __global__ __launch_bounds__(kFsThreads) void k_fs_track(FsTrackArgs A)
 {
-    __shared__ float s_obs[SHEMS_NSTATE];
-    __shared__ double s_bv[kFsWaves];
-    __shared__ int s_ba[kFsWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t e = blockIdx.x;
-    const shems_view &v = A.v;
-    const FsParams &g = A.g;
-    const int N = g.nb * g.ne, NA = g.nab * g.nae;
-    // ---- entry checks, the same answer in every thread ----
-    const int p = A.problem_of_env ? A.problem_of_env[e] : 0;
-    int32_t idx = v.idx[e], step = v.step[e];
-    if (p < 0 || p >= A.n_prob || A.prob[p].idx0 != idx) {
-        if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
-        return;
-    }
-    const shems_foresight_problem P = A.prob[p];
-    const shems_config cfg = load_cfg(v, e);                                // the env's own config steps the env
-    float obs[SHEMS_NSTATE];
-#pragma unroll
-    for (int k = 0; k < SHEMS_NSTATE; ++k) obs[k] = v.obs[e * SHEMS_NSTATE + k];
-    if (tid < SHEMS_NSTATE) s_obs[tid] = v.obs[e * SHEMS_NSTATE + tid];
-    __syncthreads();
-    double total = 0.0;
-    for (int t = 0; t < A.T; ++t) {
-        if (idx < 1 || idx + 1 > cfg.nrow || idx + 1 > P.cfg.nrow) {       // row idx + 1 does not exist (Julia: BoundsError)
-            if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
-            break;
-        }
-        const double *Vn = A.V + ((int64_t)p * (A.T + 1) + t + 1) * N;
-        const float h_cur = load_h(v.tables, P.cfg.table_row0, idx);
-        const float h_next = load_h(v.tables, P.cfg.table_row0, idx + 1);
-        const float soc_ev_next = v.tables[((int64_t)P.cfg.table_row0 + idx) * SHEMS_NCOL + 1];
-        const EnvIn s{s_obs[0], s_obs[1], s_obs[2], s_obs[3], s_obs[4], s_obs[5]};
-        double best_v = -__builtin_inf();
-        int best_a = kFsNoAction;
-        for (int a = tid; a < NA; a += kFsThreads) {
-            const int ab = a / g.nae, ae = a - ab * g.nae;
-            const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), Vn, g, P.scale_b);
-            if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(best_v, off, 64);
-            const int oa = __shfl_xor(best_a, off, 64);
-            if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
-        }
-        if (lane == 0) { s_bv[wave] = best_v; s_ba[wave] = best_a; }
-        __syncthreads();
-        if (tid == 0) {
-#pragma unroll
-            for (int w = 1; w < kFsWaves; ++w)
-                if (fs_better(s_bv[w], s_ba[w], best_v, best_a)) { best_v = s_bv[w]; best_a = s_ba[w]; }
-            const int a = best_a == kFsNoAction ? 0 : best_a;               // every Q a NaN: cannot happen on finite tables
-            const int ab = a / g.nae, ae = a - ab * g.nae;
-            const float a0 = fs_target(ab, g.nab), a1 = fs_target(ae, g.nae);
-            float pre[SHEMS_NSTATE];
-#pragma unroll
-            for (int k = 0; k < SHEMS_NSTATE; ++k) pre[k] = obs[k];
-            double reward;
-            StepFlows f;
-            float B, EV, Bt, EVt;
-            env_advance(cfg, v.tables, obs, idx, step, a0, a1, SHEMS_TRACK_DRL, reward, f, B, EV, Bt, EVt);   // bounds checked above
-            total += reward;
-            if (A.results && (A.results_env < 0 || A.results_env == e)) {
-                double *r = A.results + ((A.results_env < 0 ? e : 0) * (int64_t)A.T + t) * SHEMS_NRESULT;
-                write_results(r, idx, pre, EVt, EV, reward, f, B, Bt);
-            }
-            if (A.targets) {
-                float *tg = A.targets + (e * (int64_t)A.T + t) * 2;
-                tg[0] = a0; tg[1] = a1;
-            }
-#pragma unroll
-            for (int k = 0; k < SHEMS_NSTATE; ++k) s_obs[k] = obs[k];
-        } else {
-            idx += 1;                                                        // every thread follows the row index
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < SHEMS_NSTATE; ++k) v.obs[e * SHEMS_NSTATE + k] = obs[k];
-        v.idx[e] = idx;
-        v.step[e] = step;
-        if (A.returns) A.returns[e] = total;
-    }
+    constexpr bool FC = false;
+#include "fs_track_body.h"
+}
+
+// The forward pass under a forecast: the arrival overwrite's next row comes from the forecast table (fs_track_body.h).
+__global__ __launch_bounds__(kFsThreads) void k_fs_track_fc(FsTrackArgs A)
+{
+    constexpr bool FC = true;
+#include "fs_track_body.h"
 }
 
 static int fs_params(const shems_foresight_grid *grid, const char *fn, FsParams &g)
@@ -284,10 +166,11 @@ static int fs_params(const shems_foresight_grid *grid, const char *fn, FsParams 
 }
 
 // What both backward entry points check before any HIP call: the grid, T, the buffers and every problem record (`recs` receives the
-// records completed with scale_b / hb, as the kernels read them); fs_check_v: the size of the V buffer.
+// records completed with scale_b / hb, as the kernels read them; forecast_off is kept and its table held to the row array with
+// `forecast`, written 0 otherwise); fs_check_v: the size of the V buffer.
 static int fs_check_solve(const char *fn, const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
                           const shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
-                          const double *d_V, FsParams &g, std::vector<shems_foresight_problem> &recs)
+                          const double *d_V, FsParams &g, std::vector<shems_foresight_problem> &recs, bool forecast = false)
 {
     if (int rc = fs_params(grid, fn, g)) return rc;
     if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; the horizon must be at least 1 hour", fn, (int)T);
@@ -303,7 +186,11 @@ static int fs_check_solve(const char *fn, const float *d_tables, int64_t total_r
             return set_error(SHEMS_ERR_ARG, "%s: problem %d: the window of rows %d .. %lld runs off its table of %d rows (a pass of T steps reads row idx0 + T)",
                              fn, (int)p, (int)P.idx0, (long long)P.idx0 + T, (int)P.cfg.nrow);
         if (!(P.cfg.soc_max > 0.0f)) return set_error(SHEMS_ERR_ARG, "%s: problem %d: soc_max = %g must be positive", fn, (int)p, (double)P.cfg.soc_max);
-        P.reserved = 0;
+        if (!forecast) P.forecast_off = 0;
+        const int64_t f0 = (int64_t)P.cfg.table_row0 + P.forecast_off;
+        if (f0 < 0 || f0 + P.cfg.nrow > total_rows)
+            return set_error(SHEMS_ERR_ARG, "%s: problem %d: its forecast table (forecast_off = %d) names rows %lld .. %lld of %lld", fn, (int)p,
+                             (int)P.forecast_off, (long long)f0, (long long)(f0 + P.cfg.nrow), (long long)total_rows);
         P.scale_b = (double)(g.nb - 1) / (double)P.cfg.soc_max;             // the only divisions of the sweep: float64, on the host
         P.hb = (double)P.cfg.soc_max / (double)(g.nb - 1);
     }
@@ -361,15 +248,14 @@ extern "C" int shems_foresight_solve_dev(const float *d_tables, int64_t total_ro
     return hip_ok(hipGetLastError(), "k_fs_backward launch");
 }
 
-extern "C" int shems_foresight_solve_horizon_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
-                                                 shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid,
-                                                 int32_t T, int32_t horizon, int32_t control, double *d_V, int64_t v_doubles,
-                                                 int32_t *d_argmax, void *stream)
+// Both window entry points: the checks, the per-kernel LDS opt-in, the upload and the one launch.
+static int fs_solve_window(const char *fn, bool forecast, const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                           shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
+                           int32_t horizon, int32_t control, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream)
 {
-    const char *fn = "shems_foresight_solve_horizon_dev";
     FsParams g;
     std::vector<shems_foresight_problem> recs;
-    if (int rc = fs_check_solve(fn, d_tables, total_rows, problems, d_problems, n_problems, grid, T, d_V, g, recs)) return rc;
+    if (int rc = fs_check_solve(fn, d_tables, total_rows, problems, d_problems, n_problems, grid, T, d_V, g, recs, forecast)) return rc;
     if (horizon < 1) return set_error(SHEMS_ERR_ARG, "%s: horizon = %d; a plan sees at least the current hour", fn, (int)horizon);
     if (control < 1 || control > horizon)
         return set_error(SHEMS_ERR_ARG, "%s: control = %d; a fresh plan every 1 .. horizon = %d hours", fn, (int)control, (int)horizon);
@@ -379,22 +265,46 @@ extern "C" int shems_foresight_solve_horizon_dev(const float *d_tables, int64_t 
                          (int)g.nb, (int)g.ne, (long long)(2 * N * 8), kFsMaxPlaneBytes);
     if (int rc = fs_check_v(fn, n_problems, T, N, v_doubles)) return rc;
     const int lds = (int)(2 * N * 8);
-    static std::atomic<uint64_t> optin{0};
-    if (int rc = lds_optin(optin, (const void *)k_fs_window, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_window)")) return rc;
+    static std::atomic<uint64_t> optin{0}, optin_fc{0};                     // the opt-in is per function
+    if (int rc = forecast ? lds_optin(optin_fc, (const void *)k_fs_window_fc, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_window_fc)")
+                          : lds_optin(optin, (const void *)k_fs_window, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_window)"))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = fs_upload(recs, d_problems, st)) return rc;
     FsWindowArgs a;
     std::memset(&a, 0, sizeof a);
     a.tables = d_tables; a.prob = d_problems; a.g = g; a.T = T; a.H = horizon; a.c = control; a.V = d_V; a.arg = d_argmax;
-    hipLaunchKernelGGL(k_fs_window, dim3((unsigned)fs_plan_windows(T, control), (unsigned)n_problems), dim3(kFsWindowThreads), lds, st, a);
+    const dim3 gridDim((unsigned)fs_plan_windows(T, control), (unsigned)n_problems);
+    if (forecast) {
+        hipLaunchKernelGGL(k_fs_window_fc, gridDim, dim3(kFsWindowThreads), lds, st, a);
+        return hip_ok(hipGetLastError(), "k_fs_window_fc launch");
+    }
+    hipLaunchKernelGGL(k_fs_window, gridDim, dim3(kFsWindowThreads), lds, st, a);
     return hip_ok(hipGetLastError(), "k_fs_window launch");
 }
 
-extern "C" int shems_foresight_track_dev(const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
-                                         const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V,
-                                         int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
+extern "C" int shems_foresight_solve_horizon_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                                                 shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid,
+                                                 int32_t T, int32_t horizon, int32_t control, double *d_V, int64_t v_doubles,
+                                                 int32_t *d_argmax, void *stream)
 {
-    const char *fn = "shems_foresight_track_dev";
+    return fs_solve_window("shems_foresight_solve_horizon_dev", false, d_tables, total_rows, problems, d_problems, n_problems, grid, T, horizon,
+                           control, d_V, v_doubles, d_argmax, stream);
+}
+
+extern "C" int shems_foresight_solve_forecast_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
+                                                  shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid,
+                                                  int32_t T, int32_t horizon, int32_t control, double *d_V, int64_t v_doubles,
+                                                  int32_t *d_argmax, void *stream)
+{
+    return fs_solve_window("shems_foresight_solve_forecast_dev", true, d_tables, total_rows, problems, d_problems, n_problems, grid, T, horizon,
+                           control, d_V, v_doubles, d_argmax, stream);
+}
+
+static int fs_track(const char *fn, bool forecast, const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
+                    const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V, int64_t v_doubles,
+                    double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
+{
     if (int rc = check_view(v, fn)) return rc;
     FsParams g;
     if (int rc = fs_params(grid, fn, g)) return rc;
@@ -409,6 +319,27 @@ extern "C" int shems_foresight_track_dev(const shems_view *v, const shems_foresi
     std::memset(&a, 0, sizeof a);
     a.v = *v; a.prob = d_problems; a.n_prob = n_problems; a.problem_of_env = d_problem_of_env; a.g = g; a.T = T; a.V = d_V;
     a.results = d_results; a.results_env = results_env; a.returns = d_returns; a.targets = d_targets;
+    if (forecast) {
+        hipLaunchKernelGGL(k_fs_track_fc, dim3((unsigned)v->n_envs), dim3(kFsThreads), 0, (hipStream_t)stream, a);
+        return hip_ok(hipGetLastError(), "k_fs_track_fc launch");
+    }
     hipLaunchKernelGGL(k_fs_track, dim3((unsigned)v->n_envs), dim3(kFsThreads), 0, (hipStream_t)stream, a);
     return hip_ok(hipGetLastError(), "k_fs_track launch");
+}
+
+extern "C" int shems_foresight_track_dev(const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
+                                         const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V,
+                                         int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
+{
+    return fs_track("shems_foresight_track_dev", false, v, d_problems, n_problems, d_problem_of_env, grid, T, d_V, v_doubles, d_results,
+                    results_env, d_returns, d_targets, stream);
+}
+
+extern "C" int shems_foresight_track_forecast_dev(const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
+                                                  const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T,
+                                                  const double *d_V, int64_t v_doubles, double *d_results, int64_t results_env,
+                                                  double *d_returns, float *d_targets, void *stream)
+{
+    return fs_track("shems_foresight_track_forecast_dev", true, v, d_problems, n_problems, d_problem_of_env, grid, T, d_V, v_doubles, d_results,
+                    results_env, d_returns, d_targets, stream);
 }

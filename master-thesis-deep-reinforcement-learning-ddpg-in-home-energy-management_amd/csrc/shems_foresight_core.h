@@ -99,4 +99,24 @@ SHEMS_HD int fs_plan_first(int j, bool want_argmax) { return (want_argmax || j =
 SHEMS_HD bool fs_plan_keeps_plane(int j, int c, int T, int t) { return t == 0 || (t > j && t <= fs_plan_keep(j, c, T)); }
 SHEMS_HD bool fs_plan_keeps_argmax(int j, int c, int T, int t) { return t >= j && t < fs_plan_keep(j, c, T); }
 
+// ---- planning on a forecast (shems_foresight_solve_forecast_dev / _track_forecast_dev; foresight.belief_offset restates it) ----
+// The schedule above plans on the TRUE future rows, which no deployable controller has.  A problem may name a FORECAST TABLE: same nrow,
+// in the same uploaded row array [total_rows][8], addressed by a row offset forecast_off -- the forecast of table row r is array row
+// table_row0 + forecast_off + r.  forecast_off = 0: the truth is the forecast; the offset is negative when the forecast table lies
+// before the truth in the array.  One table cannot express a forecast that depends on when it was issued.
+// Belief of the plan made at hour j (j = t - t mod c as above): the row of hour u (table row idx0 + u) is the TRUE row for u <= j and
+// the FORECAST row for u > j.  Everything the schedule defines (hi, U_t, which planes and arg-max are kept, V[p][0], the zero plane at
+// hi) holds unchanged on that belief: a sweep of hour t inside window j takes its current row from the truth if t == j and from the
+// forecast otherwise, and its next row always from the forecast; the sweep of hour hi - 1 = T - 1 reads forecast row idx0 + T, which
+// exists because the forecast table has nrow rows.  argmax[p][t] for t > j is what the plan made at j INTENDS for hour t under its
+// forecast; the forward pass decides again from what it observes.
+// Forward pass: at hour t the controller observes the true state and the true row t (h_cur is the truth's), but not yet row t + 1, so
+// the arrival overwrite inside Q (LU1:264-281) takes h_countdown and soc_ev of the next row from the FORECAST row t + 1; the env is
+// then stepped on the truth by the ordinary DRL step.
+// With forecast_off = 0, or a forecast table that is a byte copy of the truth, every plane, index and forward choice equals the
+// schedule's on the truth bit for bit.
+// fs_belief_off: the offset (in rows, added to table_row0) of the row of hour u in the plan made at hour j.  The forward pass at hour
+// t is the case (u, j) = (t, t) for its current row and (t + 1, t) for its next.
+SHEMS_HD int fs_belief_off(int u, int j, int forecast_off) { return u > j ? forecast_off : 0; }
+
 }  // namespace shems

@@ -10,6 +10,9 @@ memory_plotting_saving.jl:62-89) is a finite-horizon dynamic programme over (Soc
     solve_horizon(tables, configs, idx0, nsteps, horizon, control) -> Values
                                                               the same recursion with `horizon` hours of forecast and a fresh plan
                                                               every `control` hours, one launch     (shems_foresight_solve_horizon_dev)
+    solve_horizon(..., forecast_table=[...]) -> Values        the same controller planning on a forecast that may be wrong
+                                                              (shems_foresight_solve_forecast_dev / _track_forecast_dev)
+    persistence_forecast(table, lag) / append_forecasts       the standard naive forecast: hour t is what it was `lag` hours earlier
 
 The arithmetic lives in csrc/shems_foresight_core.h; Values.at restates its interpolation on the host, bit for bit.  A discretised
 value function with a greedy policy is NOT a bound: V_0 at the start state and the achieved return differ by the discretisation error.
@@ -29,10 +32,10 @@ class GridStruct(C.Structure):            # shems_foresight_grid
 
 
 class Problem(C.Structure):               # shems_foresight_problem
-    _fields_ = [("cfg", Config), ("idx0", C.c_int32), ("reserved", C.c_int32), ("scale_b", C.c_double), ("hb", C.c_double)]
+    _fields_ = [("cfg", Config), ("idx0", C.c_int32), ("forecast_off", C.c_int32), ("scale_b", C.c_double), ("hb", C.c_double)]
 
 
-assert C.sizeof(Problem) == 72 and C.sizeof(GridStruct) == 16
+assert C.sizeof(Problem) == 72 and Problem.forecast_off.offset == 52 and C.sizeof(GridStruct) == 16
 
 MAX_PLANE_BYTES = 150000                  # a workgroup of the sweep stages one V plane in LDS; one of solve_horizon keeps two
 
@@ -107,6 +110,66 @@ def interpolate(plane, grid, soc_max, soc_b, soc_ev):
     return (1.0 - fe) * ((1.0 - fb) * V00 + fb * V10) + fe * ((1.0 - fb) * V01 + fb * V11)
 
 
+def belief_offset(u, j, forecast_off):
+    """fs_belief_off of csrc/shems_foresight_core.h restated: the row offset (added to table_row0) of the row of hour u in the plan made
+    at hour j -- the truth up to the hour the plan is made, the forecast table after it."""
+    return int(forecast_off) if u > j else 0
+
+
+def persistence_forecast(table, lag=24, columns=("electkwh", "PV_generation")):
+    """The standard naive forecast of a [nrow][8] table: the named columns (names of tables.COLUMNS) of row i are those of row i - lag
+    for i >= lag; rows below lag and all other columns are the truth's.  Returns [nrow][8] float32.
+    The default leaves h_countdown / soc_ev true: the observation itself carries the countdown, so the departure is known once the
+    car is plugged in -- and with these two columns true, FUTURE ARRIVALS are known too.  Adding "h_countdown" and "soc_ev" gives the
+    controller that knows nothing ahead.  As a forecast table of solve_horizon it is causal for horizon <= lag (every forecast row is
+    an hour already observed when the plan is made); for horizon > lag it is not, and nothing refuses that."""
+    from .tables import COLUMNS
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    if tab.ndim != 2 or tab.shape[1] != _capi.NCOL:
+        raise ValueError("a table must be [nrow][8] float32")
+    lag = int(lag)
+    if lag < 1 or lag >= tab.shape[0]:
+        raise ValueError(f"lag = {lag}; persistence needs 1 <= lag < nrow = {tab.shape[0]}")
+    cols = []
+    for name in columns:
+        if name not in COLUMNS:
+            raise ValueError(f"unknown column {name!r}; a table holds {COLUMNS}")
+        cols.append(COLUMNS.index(name))
+    out = tab.copy()
+    out[lag:, cols] = tab[:-lag, cols]
+    return out
+
+
+EV_COLUMNS = ("h_countdown", "soc_ev")
+
+
+def append_forecasts(tables, lag=24, columns=("electkwh", "PV_generation")):
+    """The table list of a batch with one persistence forecast per table appended: returns (tables + forecasts, index) with
+    index[k] = the position of table k's forecast in the new list -- an entry of solve_horizon's forecast_table.  Build the
+    ShemsBatch that foresight.track steps from the same list, so that both see the same row array."""
+    tabs = list(tables) if isinstance(tables, (list, tuple)) else [tables]
+    return tabs + [persistence_forecast(t, lag, columns) for t in tabs], [len(tabs) + k for k in range(len(tabs))]
+
+
+def _forecast_offsets(forecast_table, problems, row0, nrow):
+    """forecast_table (one entry per problem: None or the index of a table) -> forecast_off per problem; row0 / nrow: of the tables."""
+    entries = list(forecast_table)
+    if len(entries) != len(problems):
+        raise ValueError(f"forecast_table holds {len(entries)} entries for {len(problems)} problems")
+    offs = []
+    for p, k in enumerate(entries):
+        if k is None:
+            offs.append(0)
+            continue
+        k = int(k)
+        if k < 0 or k >= len(row0):
+            raise ValueError(f"problem {p}: forecast table {k} is outside the {len(row0)} tables")
+        if int(nrow[k]) != problems[p].cfg.nrow:
+            raise ValueError(f"problem {p}: forecast table {k} has {int(nrow[k])} rows, its table {problems[p].cfg.nrow}")
+        offs.append(int(row0[k]) - problems[p].cfg.table_row0)
+    return offs
+
+
 def make_problems(configs, idx0, nsteps, grid, total_rows=None):
     """The shems_foresight_problem records of one call, validated on the host (ValueError before any device work).  scale_b / hb
     are filled for the host side (Values.at); shems_foresight_solve_dev forms the device copy's own."""
@@ -143,20 +206,28 @@ def _declare(L):
     L.shems_foresight_solve_dev.restype = C.c_int
     L.shems_foresight_solve_horizon_dev.argtypes = [vp, i64, C.POINTER(Problem), vp, i32, C.POINTER(GridStruct), i32, i32, i32, vp, i64, vp, vp]
     L.shems_foresight_solve_horizon_dev.restype = C.c_int
+    L.shems_foresight_solve_forecast_dev.argtypes = L.shems_foresight_solve_horizon_dev.argtypes
+    L.shems_foresight_solve_forecast_dev.restype = C.c_int
     L.shems_foresight_track_dev.argtypes = [C.POINTER(_capi.View), vp, i32, vp, C.POINTER(GridStruct), i32, vp, i64, vp, i64, vp, vp, vp]
     L.shems_foresight_track_dev.restype = C.c_int
+    L.shems_foresight_track_forecast_dev.argtypes = L.shems_foresight_track_dev.argtypes
+    L.shems_foresight_track_forecast_dev.restype = C.c_int
     return L
 
 
 class Values:
     """What solve leaves on the device: V [P][T + 1][nb * ne] float64, the winning action index of every (problem, hour, node)
     [P][T][nb * ne] int32, and the problem records the forward pass needs.  horizon / control: what solve_horizon was given (None
-    from solve: the whole pass is known)."""
+    from solve: the whole pass is known).  forecast_off: per problem, the row offset of its forecast table (all 0: the plans saw the
+    truth); total_rows: the length of the row array the solve call saw."""
 
-    def __init__(self, grid, nsteps, problems, d_problems, V, argmax, tables=None, horizon=None, control=None):
+    def __init__(self, grid, nsteps, problems, d_problems, V, argmax, tables=None, horizon=None, control=None, forecast_off=None,
+                 total_rows=None):
         self.grid, self.nsteps, self.problems, self.d_problems, self.V, self.argmax, self._tables = grid, int(nsteps), problems, d_problems, V, argmax, tables
         self.n_problems = len(problems)
         self.horizon, self.control = horizon, control
+        self.forecast_off = [0] * self.n_problems if forecast_off is None else [int(o) for o in forecast_off]
+        self.total_rows = total_rows
 
     def plane(self, p, t):
         """V_t of problem p as a host array [nb][ne]."""
@@ -189,7 +260,7 @@ def _check_horizon(T, horizon, control):
     return T, H, c
 
 
-def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, control=None):
+def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, control=None, forecast_table=None):
     import torch
     from .env import ShemsBatch
     grid = Grid() if grid is None else grid
@@ -203,9 +274,20 @@ def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, contr
                 raise ValueError("a table must be [nrow][8] float32")
         rows = np.ascontiguousarray(np.concatenate(tabs, 0))
         total_rows = rows.shape[0]
+        nrow = [t.shape[0] for t in tabs]
+        row0 = np.cumsum([0] + nrow)[:-1]
     else:
         total_rows = int(env.table_row0[-1] + env.table_nrow[-1])
+        row0, nrow = env.table_row0, env.table_nrow
     problems = make_problems(configs, idx0, nsteps, grid, total_rows)
+    offs = None
+    if forecast_table is not None:
+        forecast_table = list(forecast_table)
+        offs = _forecast_offsets(forecast_table, problems, row0, nrow)
+        for rec, o in zip(problems, offs):
+            rec.forecast_off = o
+        if all(k is None for k in forecast_table):
+            offs = None                                      # no entry set: today's entry point
     T, P, N = int(nsteps), len(problems), grid.nodes
     if horizon is not None:
         _, horizon, control = _check_horizon(T, horizon, control)
@@ -230,9 +312,11 @@ def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, contr
             C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if horizon is None:
         _capi.check(L.shems_foresight_solve_dev(*head, *tail))
-    else:
+    elif offs is None:
         _capi.check(L.shems_foresight_solve_horizon_dev(*head, horizon, control, *tail))
-    return Values(grid, T, problems, d_prob, V, arg, d_tables, horizon, control)
+    else:
+        _capi.check(L.shems_foresight_solve_forecast_dev(*head, horizon, control, *tail))
+    return Values(grid, T, problems, d_prob, V, arg, d_tables, horizon, control, offs, total_rows)
 
 
 def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
@@ -243,24 +327,38 @@ def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
     return _solve(tables, configs, idx0, nsteps, grid, want_argmax)
 
 
-def solve_horizon(tables, configs, idx0, nsteps, horizon, control=1, grid=None, want_argmax=True):
+def solve_horizon(tables, configs, idx0, nsteps, horizon, control=1, grid=None, want_argmax=True, forecast_table=None):
     """The receding-horizon controller's planes for P problems, arguments as solve: at hour t the plan made at j = t - t mod control
     sees hours j .. min(j + horizon, nsteps) - 1 (horizon_plan; the definition: csrc/shems_foresight_core.h).  Values.V[p][t] is
     what track reads at hour t - 1, V[p][0] the value of the first plan, argmax[p][t] the action taken at hour t from each node;
     with horizon >= nsteps they equal solve's bit for bit.  One launch on PyTorch's current stream (shems_foresight_solve_horizon_dev),
     one workgroup per (window of `control` hours, problem) with its planes in LDS, no host synchronisation; a state grid whose two
     planes exceed 150 000 bytes is refused (129 x 65 fits).  The call always runs the window kernel: with few windows (problems x
-    ceil(nsteps / control) below the device's CU count) it under-fills the device, and for horizon >= nsteps solve is the tool."""
+    ceil(nsteps / control) below the device's CU count) it under-fills the device, and for horizon >= nsteps solve is the tool.
+    forecast_table: one entry per problem, None (the plans see the true rows) or the index of that problem's forecast table in
+    `tables` (the list, or the ShemsBatch's own tables; same nrow): the plan made at hour j then reads the true rows up to j and the
+    forecast's after it (the definition: csrc/shems_foresight_core.h; shems_foresight_solve_forecast_dev, one launch), and track
+    takes the arrival overwrite's next row from the forecast.  argmax[p][t] for t > j is what the plan made at j intends under its
+    forecast.  One forecast table cannot depend on when the forecast was issued: persistence_forecast is causal for
+    horizon <= lag and not beyond, and nothing is refused for that.  With every entry None the call is today's."""
     if horizon is None:
         raise ValueError("solve_horizon needs a horizon (solve knows the whole pass)")
-    return _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon, control)
+    return _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon, control, forecast_table)
 
 
 def track(env, values, problem_of_env=None, which=-1):
     """The greedy controller on the exact env, from the envs' CURRENT state (reset them onto their problem's start row first): env e
     runs values.nsteps hours of problem problem_of_env[e] (None: problem 0) in one launch.  Returns (totals [n] float64, results
     [n][T][23] float64 -- [1][T][23] of env `which` when which >= 0 --, targets [n][T][2] float32, the chosen (B_target,
-    EV_target)).  An env that does not sit on its problem's start row raises BoundsError and is not stepped."""
+    EV_target)).  An env that does not sit on its problem's start row raises BoundsError and is not stepped.  Values solved with a
+    forecast table go through shems_foresight_track_forecast_dev, which reads the ENV's row array: the env's batch must hold the
+    same tables in the same order as the solve call saw (a different total row count is a ValueError)."""
+    forecast = any(values.forecast_off)
+    if forecast:
+        env_rows = int(env.table_row0[-1] + env.table_nrow[-1])
+        if values.total_rows != env_rows:
+            raise ValueError(f"the values were solved on a row array of {values.total_rows} rows and the env holds {env_rows}: a forecast "
+                             "pass needs the env's batch to hold the same tables in the same order")
     import torch
     L = _declare(_capi.lib())
     n, T = env.n, values.nsteps
@@ -278,10 +376,11 @@ def track(env, values, problem_of_env=None, which=-1):
     tgt = torch.zeros((n, T, 2), dtype=torch.float32, device=dev)
     v = env.view()
     g = values.grid.struct()
-    _capi.check(L.shems_foresight_track_dev(C.byref(v), C.c_void_p(values.d_problems.data_ptr()), values.n_problems,
-                                            C.c_void_p(poe.data_ptr()) if poe is not None else None, C.byref(g), T,
-                                            C.c_void_p(values.V.data_ptr()), values.V.numel(), C.c_void_p(res.data_ptr()), int(which),
-                                            C.c_void_p(total.data_ptr()), C.c_void_p(tgt.data_ptr()), env._stream()))
+    fn = L.shems_foresight_track_forecast_dev if forecast else L.shems_foresight_track_dev
+    _capi.check(fn(C.byref(v), C.c_void_p(values.d_problems.data_ptr()), values.n_problems,
+                   C.c_void_p(poe.data_ptr()) if poe is not None else None, C.byref(g), T,
+                   C.c_void_p(values.V.data_ptr()), values.V.numel(), C.c_void_p(res.data_ptr()), int(which),
+                   C.c_void_p(total.data_ptr()), C.c_void_p(tgt.data_ptr()), env._stream()))
     out, tot, targets = res.cpu().numpy(), total.cpu().numpy(), tgt.cpu().numpy()      # the pass's one synchronisation
     env.check_error()
     return tot, out, targets

@@ -93,35 +93,51 @@ def _track(env, actor, s_min, s_max, stride, track, num_steps, which, keep=None,
     return tot, out
 
 
-def inference_foresight(env, grid=None, horizon=None, control=1):
+def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=None):
     """The perfect-foresight pass over the data set: reset!(rng = -1), the backward sweep for the env's table(s) over env.maxsteps
     hours (foresight.solve: one problem per distinct config of the batch) and the greedy forward pass on the exact env
     (foresight.track), which steps the envs with the ordinary DRL step (track > 0: penalty kept, 23-column rows).  Returns what
     inference_many returns -- (sum of rewards [N], results [N][steps][23] float64) -- so the file writers take it.  horizon: the
-    receding-horizon controller instead (foresight.solve_horizon: `horizon` hours of forecast, a fresh plan every `control` hours)."""
+    receding-horizon controller instead (foresight.solve_horizon: `horizon` hours of forecast, a fresh plan every `control` hours).
+    forecast_table (needs a horizon): the plans read a forecast instead of the true future rows -- one index into the env's own
+    tables for every problem, or one entry (index or None) per distinct config of the batch in ascending config order, as
+    foresight.problems_of_env lists them; foresight.append_forecasts builds such a table list."""
     from . import foresight
     env.use_torch_stream()
     env.reset_(-1)
     cfgs, idx0, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+    if forecast_table is not None and horizon is None:
+        raise ValueError("a forecast table needs a horizon (the perfect-foresight pass knows the whole series)")
     if horizon is None:
         values = foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
     else:
-        values = foresight.solve_horizon(env, cfgs, idx0, env.maxsteps, horizon, control, grid, want_argmax=False)
+        if forecast_table is not None and np.ndim(forecast_table) == 0:
+            forecast_table = [forecast_table] * len(cfgs)
+        values = foresight.solve_horizon(env, cfgs, idx0, env.maxsteps, horizon, control, grid, want_argmax=False, forecast_table=forecast_table)
     total, results, _ = foresight.track(env, values, poe, which=-1)
     return total, results
 
 
-def foresight_seed(horizon=None, control=1):
-    """The tracker's seed column (and the file-name suffix) of a foresight pass: foresight, foresight_h24, foresight_h24_c12."""
+def foresight_seed(horizon=None, control=1, forecast=None):
+    """The tracker's seed column (and the file-name suffix) of a foresight pass: foresight, foresight_h24, foresight_h24_c12; with a
+    persistence forecast -- forecast = lag, or (lag, ev) with ev true when the EV columns are forecast too -- foresight_h24_p24,
+    foresight_h24_c12_p24ev."""
     if horizon is None:
+        if forecast is not None:
+            raise ValueError("a forecast needs a horizon")
         return "foresight"
-    return f"foresight_h{int(horizon)}" + (f"_c{int(control)}" if int(control) != 1 else "")
+    name = f"foresight_h{int(horizon)}" + (f"_c{int(control)}" if int(control) != 1 else "")
+    if forecast is not None:
+        lag, ev = forecast if isinstance(forecast, (tuple, list)) else (forecast, False)
+        name += f"_p{int(lag)}" + ("ev" if ev else "")
+    return name
 
 
-def foresight_file_name(job_id, run, case, out_dir="out/tracker", horizon=None, control=1):
+def foresight_file_name(job_id, run, case, out_dir="out/tracker", horizon=None, control=1, forecast=None):
     """The results file of the perfect-foresight pass, next to the rule-based one of results_file_name; with a horizon, of the
-    receding-horizon pass: ..._foresight_h{H}.csv, ..._foresight_h{H}_c{c}.csv when control != 1."""
-    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_{foresight_seed(horizon, control)}.csv")
+    receding-horizon pass: ..._foresight_h{H}.csv, ..._foresight_h{H}_c{c}.csv when control != 1; with a persistence forecast
+    (forecast = lag or (lag, ev), see foresight_seed) ..._foresight_h{H}[_c{c}]_p{lag}.csv, _p{lag}ev when the EV columns are forecast."""
+    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_{foresight_seed(horizon, control, forecast)}.csv")
 
 
 def results_file_name(job_id, run, ep_len, num_ep, l1, l2, case, rng, idx, best=False, out_dir="out/tracker"):

@@ -24,6 +24,9 @@ Differences that follow from the platform, all explicit:
     out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight"; with it,
     SHEMS_FORESIGHT_HORIZON (hours of forecast: one integer or a comma list) and SHEMS_FORESIGHT_CONTROL (hours between plans,
     default 1) add one receding-horizon pass per horizon: ..._foresight_h24.csv / ..._foresight_h24_c12.csv, seed = that suffix;
+    SHEMS_FORESIGHT_FORECAST=persistence[:LAG[:ev]] (needs a horizon; LAG default 24 hours) adds, after each of those, the same
+    controller planning on the persistence forecast of load and PV -- with `ev` of h_countdown and soc_ev too --:
+    ..._foresight_h24_p24.csv / ..._foresight_h24_p24ev.csv;
   * random streams are Philox counters keyed by the same seeds (Julia's MersenneTwister streams do not exist outside Julia).
 """
 from __future__ import annotations
@@ -208,6 +211,26 @@ def foresight_horizons(environ=os.environ):
     return horizons, control
 
 
+def foresight_forecast(environ=os.environ):
+    """SHEMS_FORESIGHT_FORECAST = persistence[:LAG[:ev]] -> (lag, ev), None when unset.  It needs SHEMS_FORESIGHT_HORIZON; a
+    malformed value is refused by name."""
+    raw = environ.get("SHEMS_FORESIGHT_FORECAST")
+    if raw is None:
+        return None
+    if environ.get("SHEMS_FORESIGHT_HORIZON") is None:
+        raise ValueError("SHEMS_FORESIGHT_FORECAST is set without SHEMS_FORESIGHT_HORIZON")
+    parts = raw.split(":")
+    if parts[0] != "persistence" or len(parts) > 3 or (len(parts) == 3 and parts[2] != "ev"):
+        raise ValueError(f"SHEMS_FORESIGHT_FORECAST = {raw!r} is not persistence[:LAG[:ev]]")
+    try:
+        lag = 24 if len(parts) == 1 else int(parts[1])
+    except ValueError:
+        raise ValueError(f"SHEMS_FORESIGHT_FORECAST = {raw!r}: LAG is not an integer") from None
+    if lag < 1:
+        raise ValueError(f"SHEMS_FORESIGHT_FORECAST = {raw!r}: a lag of 1 or more hours")
+    return lag, len(parts) == 3
+
+
 def _check_supported(cfg):
     # (250, 500): the tuned kernels; smaller: zero-padded into them (ddpg.pad_net); larger -- the grids' (300, 600) --: the layer-by-layer
     # wide path (csrc/shems_wide.hip, ddpg.is_wide)
@@ -242,6 +265,7 @@ def main(environ=os.environ, cwd=".", log=print):
     cfg = config_from_env(environ)
     _check_supported(cfg)
     horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
+    forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
     os.chdir(cwd)
     torch.cuda.set_device(cfg.gpu_id)                                    # CUDA.device!(gpu_id), MAIN:12-14
     if cfg.seed_run == 1:
@@ -341,12 +365,27 @@ def main(environ=os.environ, cwd=".", log=print):
         harness.write_to_results_file(results[0], path)
         harness.write_to_tracker_file(path, seed="foresight", best=False, idx=0, **tk)
         written.append(path)
+        env_fc = None
+        if forecast is not None:                                         # the same table with its persistence forecast behind it
+            from . import foresight
+            cols = ("electkwh", "PV_generation") + (foresight.EV_COLUMNS if forecast[1] else ())
+            both, fc_index = foresight.append_forecasts([tabs[cfg.run]], forecast[0], cols)
+            env_fc = ShemsBatch(1, EP_LENGTH[cfg.season, cfg.run], both, [make_config(cfg.charger_id, 0, tabs[cfg.run].shape[0])],
+                                device=cfg.gpu_id).use_torch_stream()
         for h in horizons:                                               # the deployable case: h hours of forecast, a plan every `control`
             _, results = harness.inference_foresight(env_track, horizon=h, control=control)
             path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case, horizon=h, control=control)
             harness.write_to_results_file(results[0], path)
             harness.write_to_tracker_file(path, seed=harness.foresight_seed(h, control), best=False, idx=0, **tk)
             written.append(path)
+            if env_fc is not None:                                       # ... and planning on a forecast that is wrong
+                _, results = harness.inference_foresight(env_fc, horizon=h, control=control, forecast_table=fc_index[0])
+                path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case, horizon=h, control=control, forecast=forecast)
+                harness.write_to_results_file(results[0], path)
+                harness.write_to_tracker_file(path, seed=harness.foresight_seed(h, control, forecast), best=False, idx=0, **tk)
+                written.append(path)
+        if env_fc is not None:
+            env_fc.close()
     for e in (env_train, env_eval, env_track):
         e.close()
     log(f"Script with JOB_ID: {cfg.job_id} & TASK_ID: {cfg.task_id} is done!")
