@@ -726,6 +726,22 @@ int shems_foresight_track_forecast_dev(const shems_view *v, const shems_foresigh
                                        int32_t n_problems, const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T,
                                        const double *d_V, int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns,
                                        float *d_targets, void *stream);
+/* The audit of tracked passes: where does a pass lose against V?  Q_t(state, a) = reward of step! (LU1:283-316, 343-485; the arrival
+ * overwrite LU1:264-281) + V_{t+1}(state') is evaluated over the whole action grid from the state a pass was ACTUALLY in, read back from
+ * the reference's 23-column result rows (LU1:476-478; MPS:62-89), whichever controller made them.  csrc/shems_foresight_core.h holds
+ * the definition (row check, state, best_q / achieved_q / v_state, the telescoping identity, and why regret is not a bound).
+ * d_tables / total_rows: the row array the solve call saw; d_problems / n_problems / grid / T / d_V / v_doubles: as that call left
+ * them (planes solved on a forecast table have no audit: the host layer refuses them); d_results [n_pass][T][23] float64;
+ * d_problem_of_pass [n_pass] int32, or NULL: problem 0.  Outputs, all device memory of the caller: d_out [n_pass][T][3] float64
+ * {best_q, achieved_q, v_state}, d_best_action [n_pass][T] int32, d_status [n_pass] int32 -- 0, or SHEMS_ERR_INDEX when a row of the pass
+ * does not sit on table row idx0 + t or d_problem_of_pass names no problem; the offending hours hold NaN and -1, the others are
+ * audited.  d_status is zeroed on `stream`, then ONE launch, grid = (tiles of 4 hours, passes), a wave per hour, the actions over its
+ * lanes; no host synchronisation.  SHEMS_ERR_ARG, nothing launched: what solve_dev refuses of the grid, T < 1, n_problems < 1,
+ * n_pass outside 1 .. 65535, a V buffer that is too small, a NULL where a buffer is required. */
+int shems_foresight_audit_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *d_problems, int32_t n_problems,
+                              const shems_foresight_grid *grid, int32_t T, const double *d_V, int64_t v_doubles, const double *d_results,
+                              int32_t n_pass, const int32_t *d_problem_of_pass, double *d_out, int32_t *d_best_action, int32_t *d_status,
+                              void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@
 // Planning on a forecast (shems_foresight_solve_forecast_dev / _track_forecast_dev, the belief: shems_foresight_core.h): the same two
 // kernels with their rows taken where fs_belief_off says -- k_fs_window_fc, k_fs_track_fc; the bodies are fs_window_body.h and
 // fs_track_body.h, included into both kernels of a pair.
+// The audit of tracked passes (shems_foresight_audit_dev, the definition: shems_foresight_core.h): k_fs_audit, one launch over
+// passes x hours x actions, a wave per hour, V planes read from global memory, no LDS and no barrier.
 //
 // Compiled with -ffp-contract=off (shems_core.h).
 #include <hip/hip_runtime.h>
@@ -145,6 +147,72 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_track_fc(FsTrackArgs A)
 {
     constexpr bool FC = true;
 #include "fs_track_body.h"
+}
+
+struct FsAuditArgs {
+    const float *tables;
+    int64_t total_rows;
+    const shems_foresight_problem *prob;
+    int n_prob;
+    const int32_t *problem_of_pass;                // [n] or null: problem 0
+    FsParams g;
+    int T;
+    const double *V;
+    const double *results;                         // [n][T][23]
+    double *out;                                   // [n][T][3]: best_q, achieved_q, v_state
+    int32_t *best_action;                          // [n][T]
+    int32_t *status;                               // [n], zeroed on the stream before the launch
+};
+
+// The audit of tracked passes (the definition: shems_foresight_core.h).  Hours are independent: grid = (tiles of kFsWaves hours,
+// passes), a wave owns one hour, lane l takes actions l, l + 64, ... against the V_{t+1} plane in global memory (every pass of a
+// problem reads the same plane at the same hour: L2), the fs_better butterfly finishes the maximum, lane 0 adds achieved_q and v_state
+// and stores.  No LDS, no barrier: a wave past the last hour, or one whose row is refused, simply leaves.
+__global__ __launch_bounds__(kFsThreads) void k_fs_audit(FsAuditArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = (int)blockIdx.x * kFsWaves + (int)(threadIdx.x >> 6);     // wave-uniform
+    if (t >= A.T) return;
+    const int64_t e = blockIdx.y;
+    const FsParams &g = A.g;
+    const int N = g.nb * g.ne, NA = g.nab * g.nae;
+    const int p = A.problem_of_pass ? A.problem_of_pass[e] : 0;
+    const double *r = A.results + (e * A.T + t) * SHEMS_NRESULT;
+    double *o = A.out + (e * A.T + t) * 3;
+    shems_foresight_problem P;
+    FsAuditHour h;
+    bool ok = p >= 0 && p < A.n_prob;
+    if (ok) {
+        P = A.prob[p];
+        ok = fs_audit_hour(P, A.tables, A.total_rows, r, t, h);
+    }
+    if (!ok) {                                                              // every writer of status[e] stores the same value
+        if (lane == 0) {
+            o[0] = o[1] = o[2] = __builtin_nan("");
+            A.best_action[e * A.T + t] = -1;
+            A.status[e] = SHEMS_ERR_INDEX;
+        }
+        return;
+    }
+    const double *Vt = A.V + ((int64_t)p * (A.T + 1) + t) * N, *Vn = Vt + N;
+    double best_v = -__builtin_inf();
+    int best_a = kFsNoAction;
+    for (int a = lane; a < NA; a += 64) {
+        const double q = fs_audit_q(P, h, a, Vn, g);
+        if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(best_v, off, 64);
+        const int oa = __shfl_xor(best_a, off, 64);
+        if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
+    }
+    if (lane == 0) {
+        o[0] = best_v;
+        o[1] = fs_audit_achieved(P, r, t + 1 < A.T ? r + SHEMS_NRESULT : nullptr, Vn, g);
+        o[2] = fs_audit_v_state(P, h, Vt, g);
+        A.best_action[e * A.T + t] = best_a == kFsNoAction ? -1 : best_a;   // every Q a NaN: cannot happen on finite tables
+    }
 }
 
 static int fs_params(const shems_foresight_grid *grid, const char *fn, FsParams &g)
@@ -342,4 +410,29 @@ extern "C" int shems_foresight_track_forecast_dev(const shems_view *v, const she
 {
     return fs_track("shems_foresight_track_forecast_dev", true, v, d_problems, n_problems, d_problem_of_env, grid, T, d_V, v_doubles, d_results,
                     results_env, d_returns, d_targets, stream);
+}
+
+extern "C" int shems_foresight_audit_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *d_problems, int32_t n_problems,
+                                         const shems_foresight_grid *grid, int32_t T, const double *d_V, int64_t v_doubles,
+                                         const double *d_results, int32_t n_pass, const int32_t *d_problem_of_pass, double *d_out,
+                                         int32_t *d_best_action, int32_t *d_status, void *stream)
+{
+    const char *fn = "shems_foresight_audit_dev";
+    FsParams g;
+    if (int rc = fs_params(grid, fn, g)) return rc;
+    if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; a pass is at least 1 hour", fn, (int)T);
+    if (!d_tables || total_rows < 2 || !d_problems || n_problems < 1 || !d_V)
+        return set_error(SHEMS_ERR_ARG, "%s: NULL buffer, fewer than 2 table rows, or no problem", fn);
+    if (n_pass < 1 || n_pass > 65535) return set_error(SHEMS_ERR_ARG, "%s: n_pass = %d; one call audits 1 .. 65535 passes", fn, (int)n_pass);
+    if (!d_results || !d_out || !d_best_action || !d_status)
+        return set_error(SHEMS_ERR_ARG, "%s: NULL results, out, best_action or status buffer", fn);
+    if (int rc = fs_check_v(fn, n_problems, T, (int64_t)g.nb * g.ne, v_doubles)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = hip_ok(hipMemsetAsync(d_status, 0, (size_t)n_pass * sizeof(int32_t), st), "hipMemsetAsync(status)")) return rc;
+    FsAuditArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.tables = d_tables; a.total_rows = total_rows; a.prob = d_problems; a.n_prob = n_problems; a.problem_of_pass = d_problem_of_pass;
+    a.g = g; a.T = T; a.V = d_V; a.results = d_results; a.out = d_out; a.best_action = d_best_action; a.status = d_status;
+    hipLaunchKernelGGL(k_fs_audit, dim3((unsigned)((T + kFsWaves - 1) / kFsWaves), (unsigned)n_pass), dim3(kFsThreads), 0, st, a);
+    return hip_ok(hipGetLastError(), "k_fs_audit launch");
 }

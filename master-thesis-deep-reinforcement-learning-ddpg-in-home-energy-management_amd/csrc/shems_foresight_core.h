@@ -119,4 +119,66 @@ SHEMS_HD bool fs_plan_keeps_argmax(int j, int c, int T, int t) { return t >= j &
 // t is the case (u, j) = (t, t) for its current row and (t + 1, t) for its next.
 SHEMS_HD int fs_belief_off(int u, int j, int forecast_off) { return u > j ? forecast_off : 0; }
 
+// ---- the audit of a tracked pass (shems_foresight_audit_dev; tests/foresight_regret_ref.py restates it) ----
+// Where does a pass lose against V?  Given the planes V[p][0 .. T] of a solve call on the TRUE rows and the reference's 23-column result
+// rows of ANY pass over the same T hours (write_results, csrc/shems_env_dev.h: the rule-based controller's, an actor's, a foresight
+// pass's, rows read back from a results file), every (pass, hour) gets three float64 and one index; nothing of the controller is needed.
+// For pass e of problem p at hour t (0-based), r = results[e][t], P = the problem record:
+//   row        idx = (int)r[0] - 1 (column 0 holds the row index AFTER the step); it must equal P.idx0 + t, and rows idx, idx + 1 must
+//              lie inside the row array: otherwise the hour is refused (three NaN, action -1, status[e] = SHEMS_ERR_INDEX);
+//   state      EnvIn{(float)r[22], (float)r[4], (float)r[1], d_e, g_e, p_buy}, the last three from columns 2, 3, 4 of table row idx --
+//              what reset! and next_state! leave in the observation.  The three floats were stored as doubles: the way back is exact;
+//   next row   h_cur, h_next, soc_ev_next from table rows idx and idx + 1, exactly as the forward pass takes them;
+//   best_q, best_a  the first maximum (fs_better) over a = ab * nae + ae of fs_q(P.cfg, state, ..., fs_target(ab), fs_target(ae), V[p][t + 1]);
+//   achieved_q      r[5] + fs_value(V[p][t + 1], Soc_b, Soc_ev of results[e][t + 1]) for t < T - 1.  At t = T - 1 it is r[5] + 0.0: the
+//                   rows do not hold the pass's FINAL state, and V_T = 0 in everything a solve call leaves;
+//   v_state         fs_value(V[p][t], Soc_b, Soc_ev of r).
+// On the host: regret = best_q - achieved_q, discretisation = best_q - v_state.  For the planes of shems_foresight_solve_dev
+//   sum_t regret_t = best_q[0] - sum_t r[5] + sum_{t >= 1} discretisation_t
+// up to float64 rounding: achieved_q[t] = reward_t + v_state[t + 1] for t < T - 1, so the sum telescopes.
+// Regret is NOT a bound: a controller acting off the action grid -- an actor, or the rule-based controller, whose rows carry kWh
+// set-points -- can reach slightly negative values.  For the planes of shems_foresight_solve_horizon_dev best_q is what THAT controller
+// would take from this state, and the identity does not apply.  An audit against a belief (planes solved on a forecast table) is not
+// defined; foresight.audit refuses it.
+struct FsAuditHour {
+    EnvIn s;
+    float h_cur, h_next, soc_ev_next;
+};
+
+// The row check and the state of hour t.  `tables`: the row array [total_rows][8].  False: the hour is refused.
+SHEMS_HD bool fs_audit_hour(const shems_foresight_problem &P, const float *tables, int64_t total_rows, const double *r, int t, FsAuditHour &h)
+{
+    const double x = r[0];
+    if (!(x >= 1.0 && x <= 2147483647.0)) return false;                           // also a NaN: the conversion below is then defined
+    const int idx = (int)x - 1;
+    if (idx < 1 || (int64_t)idx != (int64_t)P.idx0 + t) return false;
+    const int64_t at = (int64_t)P.cfg.table_row0 + idx - 1;                         // array row of table row idx
+    if (P.cfg.table_row0 < 0 || idx + 1 > P.cfg.nrow || at + 2 > total_rows) return false;
+    const float *row = tables + at * SHEMS_NCOL;
+    h.s = EnvIn{(float)r[22], (float)r[4], (float)r[1], row[2], row[3], row[4]};
+    h.h_cur = row[0];
+    h.h_next = row[SHEMS_NCOL];
+    h.soc_ev_next = row[SHEMS_NCOL + 1];
+    return true;
+}
+
+// Q of action index a from the state of the hour; V_next = V[p][t + 1].
+SHEMS_HD double fs_audit_q(const shems_foresight_problem &P, const FsAuditHour &h, int a, const double *V_next, const FsParams &g)
+{
+    const int ab = a / g.nae, ae = a - ab * g.nae;
+    return fs_q(P.cfg, h.s, h.h_cur, h.h_next, h.soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), V_next, g, P.scale_b);
+}
+
+// r_next = results[e][t + 1], or null at t = T - 1.
+SHEMS_HD double fs_audit_achieved(const shems_foresight_problem &P, const double *r, const double *r_next, const double *V_next, const FsParams &g)
+{
+    return r[5] + (r_next ? fs_value(V_next, g, P.scale_b, (float)r_next[22], (float)r_next[4]) : 0.0);
+}
+
+// V_cur = V[p][t].
+SHEMS_HD double fs_audit_v_state(const shems_foresight_problem &P, const FsAuditHour &h, const double *V_cur, const FsParams &g)
+{
+    return fs_value(V_cur, g, P.scale_b, h.s.Soc_b, h.s.Soc_ev);
+}
+
 }  // namespace shems

@@ -111,6 +111,7 @@ class ShemsBatch:
         self.table_nrow = np.array([t.shape[0] for t in tabs], np.int64)
         rows = np.ascontiguousarray(np.concatenate(tabs, 0))
         _capi.check(L.shems_set_tables(self._h, _ptr(rows), rows.shape[0]))
+        self.host_rows = rows                                                # the uploaded row array (foresight.audit reads its phases off it)
         if configs is None:
             configs = [make_config(98, 0, tabs[0].shape[0])]
         self.configs = list(configs)

@@ -13,6 +13,8 @@ memory_plotting_saving.jl:62-89) is a finite-horizon dynamic programme over (Soc
     solve_horizon(..., forecast_table=[...]) -> Values        the same controller planning on a forecast that may be wrong
                                                               (shems_foresight_solve_forecast_dev / _track_forecast_dev)
     persistence_forecast(table, lag) / append_forecasts       the standard naive forecast: hour t is what it was `lag` hours earlier
+    audit(values, results, problem_of_pass) -> Audit          the hourly regret of ANY tracked pass against V, one launch, parallel over
+                                                              passes x hours x actions                   (shems_foresight_audit_dev)
 
 The arithmetic lives in csrc/shems_foresight_core.h; Values.at restates its interpolation on the host, bit for bit.  A discretised
 value function with a greedy policy is NOT a bound: V_0 at the start state and the achieved return differ by the discretisation error.
@@ -212,6 +214,8 @@ def _declare(L):
     L.shems_foresight_track_dev.restype = C.c_int
     L.shems_foresight_track_forecast_dev.argtypes = L.shems_foresight_track_dev.argtypes
     L.shems_foresight_track_forecast_dev.restype = C.c_int
+    L.shems_foresight_audit_dev.argtypes = [vp, i64, vp, i32, C.POINTER(GridStruct), i32, vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    L.shems_foresight_audit_dev.restype = C.c_int
     return L
 
 
@@ -219,15 +223,16 @@ class Values:
     """What solve leaves on the device: V [P][T + 1][nb * ne] float64, the winning action index of every (problem, hour, node)
     [P][T][nb * ne] int32, and the problem records the forward pass needs.  horizon / control: what solve_horizon was given (None
     from solve: the whole pass is known).  forecast_off: per problem, the row offset of its forecast table (all 0: the plans saw the
-    truth); total_rows: the length of the row array the solve call saw."""
+    truth); total_rows: the length of the row array the solve call saw, host_rows: its host copy [total_rows][8]."""
 
     def __init__(self, grid, nsteps, problems, d_problems, V, argmax, tables=None, horizon=None, control=None, forecast_off=None,
-                 total_rows=None):
+                 total_rows=None, host_rows=None):
         self.grid, self.nsteps, self.problems, self.d_problems, self.V, self.argmax, self._tables = grid, int(nsteps), problems, d_problems, V, argmax, tables
         self.n_problems = len(problems)
         self.horizon, self.control = horizon, control
         self.forecast_off = [0] * self.n_problems if forecast_off is None else [int(o) for o in forecast_off]
         self.total_rows = total_rows
+        self.host_rows = host_rows
 
     def plane(self, p, t):
         """V_t of problem p as a host array [nb][ne]."""
@@ -316,7 +321,7 @@ def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, contr
         _capi.check(L.shems_foresight_solve_horizon_dev(*head, horizon, control, *tail))
     else:
         _capi.check(L.shems_foresight_solve_forecast_dev(*head, horizon, control, *tail))
-    return Values(grid, T, problems, d_prob, V, arg, d_tables, horizon, control, offs, total_rows)
+    return Values(grid, T, problems, d_prob, V, arg, d_tables, horizon, control, offs, total_rows, rows if env is None else env.host_rows)
 
 
 def solve(tables, configs, idx0, nsteps, grid=None, want_argmax=True):
@@ -393,3 +398,137 @@ def problems_of_env(env, idx=None):
     co = np.zeros(env.n, np.int64) if env.cfg_of_env is None else env.cfg_of_env.astype(np.int64)
     keys, inv = np.unique(np.stack([co, idx], 1), axis=0, return_inverse=True)
     return [env.configs[int(k[0])] for k in keys], [int(k[1]) for k in keys], np.asarray(inv, np.int32).reshape(env.n)
+
+
+PHASES = ("absent", "arrival", "connected", "departure")
+
+
+class Audit:
+    """What audit returns, all host arrays: best_q, achieved_q, v_state [n][T] float64, best_action [n][T] int32, best_targets
+    [n][T][2] float32 (the grid's (B_target, EV_target) of best_action), regret = best_q - achieved_q and discretisation =
+    best_q - v_state.  Regret is NOT a bound: a controller acting off the action grid (a DDPG actor, or the rule-based controller,
+    whose rows carry kWh set-points) can reach slightly negative values.  For Values from solve,
+        sum_t regret[t] = best_q[0] - return + sum_{t >= 1} discretisation[t]
+    up to float64 rounding (the definition: csrc/shems_foresight_core.h); for Values from solve_horizon best_q is what THAT controller
+    would take from the state, and the identity does not apply."""
+
+    def __init__(self, out, best_action, targets, rewards, phase):
+        self.best_q, self.achieved_q, self.v_state = (np.ascontiguousarray(out[..., k]) for k in range(3))
+        self.best_action = best_action
+        self.best_targets = targets[np.maximum(best_action, 0)]
+        self.best_targets[best_action < 0] = np.nan
+        self.regret = self.best_q - self.achieved_q
+        self.discretisation = self.best_q - self.v_state
+        self.rewards, self.phase = rewards, phase             # [n][T] float64; [n][T] int8, an index into PHASES
+
+    def summary(self):
+        """Per pass, a dict of [n] float64 arrays: "return" (the sum of the rewards column), "regret" and "discretisation" (sums over
+        the hours), and the regret summed by EV phase of the hour -- "absent" (c_ev = -1), "arrival" (c_ev = -1 and the next row's
+        h_countdown >= 0; it takes precedence over absent), "departure" (c_ev = 0), "connected" (every other hour).  The four phase
+        sums add up to "regret" up to rounding."""
+        out = {"return": self.rewards.sum(1), "regret": self.regret.sum(1), "discretisation": self.discretisation.sum(1)}
+        for k, name in enumerate(PHASES):
+            out[name] = np.where(self.phase == k, self.regret, 0.0).sum(1)
+        return out
+
+
+def phases(c_ev, h_next):
+    """The EV phase of an hour as an index into PHASES, from the c_ev column of its results row and h_countdown of the next table row."""
+    c_ev, h_next = np.asarray(c_ev), np.asarray(h_next)
+    ph = np.full(c_ev.shape, PHASES.index("connected"), np.int8)
+    ph[c_ev == 0] = PHASES.index("departure")
+    ph[c_ev == -1] = PHASES.index("absent")
+    ph[(c_ev == -1) & (h_next >= 0)] = PHASES.index("arrival")
+    return ph
+
+
+def _audit_device(values, results, problem_of_pass=None):
+    """audit's checks and its device work: returns (out [n][T][3] float64, best_action [n][T] int32, status [n] int32, the c_ev and
+    rewards columns of the rows as host arrays [n][T], problem_of_pass as an int32 array or None) without judging the status."""
+    if any(values.forecast_off):
+        raise ValueError("the values were solved on a forecast table: an audit against a belief is not defined (audit the pass against "
+                         "the values of a solve on the true rows)")
+    is_tensor = not isinstance(results, np.ndarray) and hasattr(results, "data_ptr")
+    res = results if is_tensor else np.asarray(results, np.float64)
+    if res.ndim == 2:
+        res = res[None]
+    T = values.nsteps
+    if res.ndim != 3 or res.shape[2] != _capi.NRESULT:
+        raise ValueError(f"results must be [n][T][{_capi.NRESULT}] or [T][{_capi.NRESULT}], not {tuple(res.shape)}")
+    if res.shape[1] != T:
+        raise ValueError(f"results hold T = {res.shape[1]} hours and the values were solved for {T}")
+    n = int(res.shape[0])
+    if n < 1 or n > 65535:
+        raise ValueError(f"one call audits 1 .. 65535 passes, not {n}")
+    po = None
+    if problem_of_pass is not None:
+        po = np.ascontiguousarray(problem_of_pass, dtype=np.int32)
+        if po.shape != (n,):
+            raise ValueError(f"problem_of_pass must have shape ({n},), one problem per pass")
+    if is_tensor and not (res.is_cuda and str(res.dtype) == "torch.float64"):
+        raise ValueError("a results tensor must be a float64 CUDA tensor")
+    L = _declare(_capi.lib())
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    env = values._tables if hasattr(values._tables, "use_torch_stream") else None        # a ShemsBatch, or the uploaded tensor
+    if env is not None:
+        env.use_torch_stream()
+        tab_ptr = env.view().tables
+    else:
+        tab_ptr = values._tables.data_ptr()
+    d_res = res.contiguous() if is_tensor else torch.from_numpy(np.ascontiguousarray(res)).to(dev)
+    d_po = torch.from_numpy(po).to(dev) if po is not None else None
+    # one buffer, one copy back: out [n][T][3] float64 | c_ev, rewards of device-resident rows [n][T][2] float64 | best_action [n][T]
+    # int32 | status [n] int32
+    nb_q, nb_col, nb_act = n * T * 24, (n * T * 16 if is_tensor else 0), n * T * 4
+    nb_out = nb_q + nb_col
+    buf = torch.empty(nb_out + nb_act + n * 4, dtype=torch.uint8, device=dev)
+    if is_tensor:
+        buf[nb_q:nb_out].view(torch.float64).view(n, T, 2).copy_(d_res[..., [1, 5]])
+    g = values.grid.struct()
+    _capi.check(L.shems_foresight_audit_dev(C.c_void_p(tab_ptr), int(values.total_rows), C.c_void_p(values.d_problems.data_ptr()),
+                                            values.n_problems, C.byref(g), T, C.c_void_p(values.V.data_ptr()), values.V.numel(),
+                                            C.c_void_p(d_res.data_ptr()), n, C.c_void_p(d_po.data_ptr()) if d_po is not None else None,
+                                            C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + nb_out),
+                                            C.c_void_p(buf.data_ptr() + nb_out + nb_act), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    host = buf.cpu().numpy()                                 # the call's one device-to-host copy (and synchronisation)
+    out = host[:nb_q].view(np.float64).reshape(n, T, 3)
+    cols = host[nb_q:nb_out].view(np.float64).reshape(n, T, 2) if is_tensor else res[..., [1, 5]]
+    act = host[nb_out:nb_out + nb_act].view(np.int32).reshape(n, T)
+    status = host[nb_out + nb_act:].view(np.int32)
+    return out, act, status, np.ascontiguousarray(cols[..., 0]), np.ascontiguousarray(cols[..., 1]), po
+
+
+def audit(values, results, problem_of_pass=None):
+    """The hourly regret of tracked passes against the values of a solve: for every (pass, hour) the best Q over the action grid from
+    the state the pass was ACTUALLY in, the Q the pass achieved and V_t at that state (the definition: csrc/shems_foresight_core.h).
+    results: the reference's 23-column rows (harness.RESULTS_HEADER) of any controller's passes -- rule-based, an actor's,
+    inference_many's, a foresight pass's, rows read back from a results file --, [n][T][23] or [T][23], a NumPy array or a float64
+    CUDA tensor, with T = values.nsteps; pass e belongs to problem problem_of_pass[e] (None: problem 0) and must start on that
+    problem's start row.  The rows of the tables come from the row array the values were solved on.  One launch on PyTorch's current
+    stream (shems_foresight_audit_dev) and one device-to-host copy.  A pass whose rows do not sit on its problem's table rows (or that
+    names no problem) raises BoundsError naming the first such pass.
+    Regret is not a bound (see Audit).  Values from solve_horizon are accepted: best_q is then what that controller would take.
+    Values solved on a forecast table are refused with a ValueError: an audit against a belief is not defined."""
+    out, act, status, c_ev, rewards, po = _audit_device(values, results, problem_of_pass)
+    bad = np.nonzero(status)[0]
+    if bad.size:
+        e = int(bad[0])
+        hours = np.nonzero(act[e] < 0)[0]
+        raise _capi.BoundsError(int(status[e]), f"foresight.audit: pass {e} (problem {0 if po is None else int(po[e])}): the rows of {hours.size} "
+                                f"hour(s), the first hour {int(hours[0]) if hours.size else -1}, do not sit on its problem's table rows "
+                                f"(or it names none of the {values.n_problems} problems)")
+    return Audit(out, act, values.grid.targets(), rewards, _phases_of(values, c_ev, po))
+
+
+def _phases_of(values, c_ev, po):
+    """The EV phase of every (pass, hour): c_ev of the rows, h_countdown of the next table row read from the host copy of the row
+    array the values were solved on."""
+    n, T = c_ev.shape
+    host = values.host_rows
+    h_next = np.empty((n, T), np.float32)
+    for e in range(n):
+        P = values.problems[0 if po is None else int(po[e])]
+        first = P.cfg.table_row0 + P.idx0                    # array row of table row idx0 + 1
+        h_next[e] = host[first:first + T, 0]
+    return phases(c_ev, h_next)

@@ -93,7 +93,18 @@ def _track(env, actor, s_min, s_max, stride, track, num_steps, which, keep=None,
     return tot, out
 
 
-def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=None):
+def foresight_values(env, grid=None):
+    """The perfect-foresight solve of inference_foresight on its own: reset!(rng = -1) and the backward sweep for the env's table(s)
+    over env.maxsteps hours from row 1, one problem per distinct config of the batch.  The Values serve inference_foresight(values=...)
+    and any number of regret_of calls."""
+    from . import foresight
+    env.use_torch_stream()
+    env.reset_(-1)
+    cfgs, idx0, _ = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+    return foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
+
+
+def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=None, values=None):
     """The perfect-foresight pass over the data set: reset!(rng = -1), the backward sweep for the env's table(s) over env.maxsteps
     hours (foresight.solve: one problem per distinct config of the batch) and the greedy forward pass on the exact env
     (foresight.track), which steps the envs with the ordinary DRL step (track > 0: penalty kept, 23-column rows).  Returns what
@@ -101,14 +112,18 @@ def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=
     receding-horizon controller instead (foresight.solve_horizon: `horizon` hours of forecast, a fresh plan every `control` hours).
     forecast_table (needs a horizon): the plans read a forecast instead of the true future rows -- one index into the env's own
     tables for every problem, or one entry (index or None) per distinct config of the batch in ascending config order, as
-    foresight.problems_of_env lists them; foresight.append_forecasts builds such a table list."""
+    foresight.problems_of_env lists them; foresight.append_forecasts builds such a table list.
+    values: the Values of foresight_values(env, grid) (or of any solve for this batch's problems from row 1) to reuse instead of
+    solving again; grid, horizon, control and forecast_table are then not read."""
     from . import foresight
     env.use_torch_stream()
     env.reset_(-1)
     cfgs, idx0, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
     if forecast_table is not None and horizon is None:
         raise ValueError("a forecast table needs a horizon (the perfect-foresight pass knows the whole series)")
-    if horizon is None:
+    if values is not None:
+        pass
+    elif horizon is None:
         values = foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
     else:
         if forecast_table is not None and np.ndim(forecast_table) == 0:
@@ -116,6 +131,53 @@ def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=
         values = foresight.solve_horizon(env, cfgs, idx0, env.maxsteps, horizon, control, grid, want_argmax=False, forecast_table=forecast_table)
     total, results, _ = foresight.track(env, values, poe, which=-1)
     return total, results
+
+
+REGRET_HEADER = ["index", "Soc_b", "Soc_ev", "c_ev", "rewards", "achieved_q", "best_q", "regret", "v_state", "best_B_tar", "best_EV_tar"]
+
+
+def regret_of(env, results, values=None, grid=None):
+    """The hourly regret of tracked passes of `env`'s data set against perfect foresight (foresight.audit): results is one pass
+    [steps][23] (harness.inference, a results file read back) or [P][steps][23] (inference_many, inference_foresight), every pass
+    from reset!(rng = -1) over env.maxsteps hours.  A batch with several configs needs one pass per env (pass e is env e's).  values:
+    foresight_values(env, grid) to reuse (solved here when None).  Returns a foresight.Audit.  Regret is not a bound: a controller
+    acting off the action grid can reach slightly negative values."""
+    from . import foresight
+    if values is None:
+        values = foresight_values(env, grid)
+    n = 1 if np.ndim(results) == 2 else int(np.shape(results)[0])
+    _, _, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+    po = None
+    if values.n_problems > 1:
+        if n != env.n:
+            raise ValueError(f"the batch holds {values.n_problems} problems: regret_of needs one pass per env ({env.n}), not {n}")
+        po = poe
+    return foresight.audit(values, results, po)
+
+
+def regret_file_name(results_path):
+    """The regret file of a results file: its name with _regret before .csv."""
+    root, ext = os.path.splitext(results_path)
+    return root + "_regret" + (ext or ".csv")
+
+
+def write_to_regret_file(audit, results, path, pass_index=0):
+    """One pass of an audit as a CSV next to its results file: per hour the row index, the state the pass was in, its reward, the Q it
+    achieved, the best Q of the action grid from that state, their difference, V_t at the state and the targets of the best action.
+    results: the rows the audit was made of ([steps][23], or [P][steps][23] with pass_index naming the pass)."""
+    res = np.asarray(results, np.float64)
+    res = res[pass_index] if res.ndim == 3 else res
+    e = int(pass_index)
+    if res.ndim != 2 or res.shape[1] != len(RESULTS_HEADER) or res.shape[0] != audit.regret.shape[1]:
+        raise ValueError(f"results must be the [steps][23] rows of the audited pass ({audit.regret.shape[1]} hours)")
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(REGRET_HEADER)
+        for t, r in enumerate(res):
+            w.writerow([repr(float(x)) for x in (r[0], r[22], r[4], r[1], r[5], audit.achieved_q[e, t], audit.best_q[e, t], audit.regret[e, t],
+                                                 audit.v_state[e, t], audit.best_targets[e, t, 0], audit.best_targets[e, t, 1])])
+    return path
 
 
 def foresight_seed(horizon=None, control=1, forecast=None):

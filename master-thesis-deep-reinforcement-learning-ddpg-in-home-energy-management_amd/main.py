@@ -27,6 +27,9 @@ Differences that follow from the platform, all explicit:
     SHEMS_FORESIGHT_FORECAST=persistence[:LAG[:ev]] (needs a horizon; LAG default 24 hours) adds, after each of those, the same
     controller planning on the persistence forecast of load and PV -- with `ev` of h_countdown and soc_ev too --:
     ..._foresight_h24_p24.csv / ..._foresight_h24_p24ev.csv;
+    SHEMS_FORESIGHT_REGRET=1 (needs SHEMS_FORESIGHT=1) adds one <results file>_regret.csv next to every results file of the tracking
+    block -- the hourly regret of that pass against ONE perfect-foresight solve (harness.regret_of; the forecast passes are audited
+    against the truth like the rest);
   * random streams are Philox counters keyed by the same seeds (Julia's MersenneTwister streams do not exist outside Julia).
 """
 from __future__ import annotations
@@ -211,6 +214,16 @@ def foresight_horizons(environ=os.environ):
     return horizons, control
 
 
+def foresight_regret(environ=os.environ):
+    """SHEMS_FORESIGHT_REGRET=1 -> True: one <results file>_regret.csv next to every results file of the tracking block (the hourly
+    regret against ONE perfect-foresight solve, harness.regret_of).  It needs SHEMS_FORESIGHT=1."""
+    if environ.get("SHEMS_FORESIGHT_REGRET") != "1":
+        return False
+    if environ.get("SHEMS_FORESIGHT") != "1":
+        raise ValueError("SHEMS_FORESIGHT_REGRET is set without SHEMS_FORESIGHT=1")
+    return True
+
+
 def foresight_forecast(environ=os.environ):
     """SHEMS_FORESIGHT_FORECAST = persistence[:LAG[:ev]] -> (lag, ev), None when unset.  It needs SHEMS_FORESIGHT_HORIZON; a
     malformed value is refused by name."""
@@ -266,6 +279,7 @@ def main(environ=os.environ, cwd=".", log=print):
     _check_supported(cfg)
     horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
     forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
+    regret = foresight_regret(environ)
     os.chdir(cwd)
     torch.cuda.set_device(cfg.gpu_id)                                    # CUDA.device!(gpu_id), MAIN:12-14
     if cfg.seed_run == 1:
@@ -321,7 +335,7 @@ def main(environ=os.environ, cwd=".", log=print):
         log(f"trained {cfg.NUM_EP} episodes in {time.time() - t0:.1f} s; best evaluation at episode {best_eval}")
 
     # ---- track evaluation (MAIN:87-110) ----
-    written = []
+    written, audited = [], []                                            # audited: (results path, rows) of every pass stepped on the true table
     tk = dict(num_ep=cfg.NUM_EP, l1=cfg.L1, l2=cfg.L2, batch_size=cfg.BATCH_SIZE, mem_size=cfg.MEM_SIZE, min_exp_size=cfg.MEM_SIZE,
               season=cfg.season, run=cfg.run, job_id=cfg.job_id, case=cfg.case)
     if cfg.track == 1 and cfg.seed_run == cfg.num_seeds:
@@ -351,6 +365,7 @@ def main(environ=os.environ, cwd=".", log=print):
                 harness.write_to_results_file(res, path)
                 harness.write_to_tracker_file(path, seed=test_rng_run, best=best, idx=idx, **tk)
                 written.append(path)
+                audited.append((path, res))
         log(f"Evaluation/Testing for TASK_IDs of {cfg.job_id} is finished.")
     elif cfg.track < 0:                                                  # rule-based
         _, results = harness.inference(env_track, None, track=cfg.track)
@@ -359,12 +374,15 @@ def main(environ=os.environ, cwd=".", log=print):
         harness.write_to_results_file(results, path)
         harness.write_to_tracker_file(path, seed=idx, best=False, idx=idx, **tk)
         written.append(path)
+        audited.append((path, results))
     if environ.get("SHEMS_FORESIGHT") == "1":                            # this build's addition: the upper yardstick on the same table
-        _, results = harness.inference_foresight(env_track)
+        values = harness.foresight_values(env_track) if regret else None   # the one perfect-foresight solve every audit below reads
+        _, results = harness.inference_foresight(env_track, values=values)
         path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case)
         harness.write_to_results_file(results[0], path)
         harness.write_to_tracker_file(path, seed="foresight", best=False, idx=0, **tk)
         written.append(path)
+        audited.append((path, results[0]))
         env_fc = None
         if forecast is not None:                                         # the same table with its persistence forecast behind it
             from . import foresight
@@ -378,14 +396,20 @@ def main(environ=os.environ, cwd=".", log=print):
             harness.write_to_results_file(results[0], path)
             harness.write_to_tracker_file(path, seed=harness.foresight_seed(h, control), best=False, idx=0, **tk)
             written.append(path)
+            audited.append((path, results[0]))
             if env_fc is not None:                                       # ... and planning on a forecast that is wrong
                 _, results = harness.inference_foresight(env_fc, horizon=h, control=control, forecast_table=fc_index[0])
                 path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case, horizon=h, control=control, forecast=forecast)
                 harness.write_to_results_file(results[0], path)
                 harness.write_to_tracker_file(path, seed=harness.foresight_seed(h, control, forecast), best=False, idx=0, **tk)
                 written.append(path)
+                audited.append((path, results[0]))                       # stepped on the truth: audited against the truth, not its belief
         if env_fc is not None:
             env_fc.close()
+        if regret:                                                       # all passes in one launch against the one solve
+            audit = harness.regret_of(env_track, np.stack([r for _, r in audited]), values=values)
+            for k, (path, res) in enumerate(audited):
+                written.append(harness.write_to_regret_file(audit, res, harness.regret_file_name(path), pass_index=k))
     for e in (env_train, env_eval, env_track):
         e.close()
     log(f"Script with JOB_ID: {cfg.job_id} & TASK_ID: {cfg.task_id} is done!")
