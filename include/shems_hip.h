@@ -726,6 +726,28 @@ int shems_foresight_track_forecast_dev(const shems_view *v, const shems_foresigh
                                        int32_t n_problems, const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T,
                                        const double *d_V, int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns,
                                        float *d_targets, void *stream);
+/* The forward pass of the same controller HEDGING over K forecasts (LU1:283-316, 343-485; the arrival overwrite LU1:264-281).  An
+ * ensemble problem is one truth (cfg, idx0) with n_scen scenarios, each a forecast table as above with a float64 weight; d_problems
+ * holds n_problems * n_scen records, problem-major, scenario-minor, and d_V their planes, as ONE shems_foresight_solve_forecast_dev
+ * call over those records left them (no new sweep).  At hour t every action is stepped once from the true state; its value is
+ * reward + sum_k w[k] * U^k_{t+1}(Soc_b', Soc_ev'^k), the sum taken in scenario order from +0.0 and the arrival overwrite of scenario k
+ * read from ITS row t + 1; the first maximum wins and the env is stepped on the truth (csrc/shems_foresight_core.h: the definition,
+ * fs_step / fs_q_ens, and why this two-stage programme is optimistic about what is learnt after the first stage).  With n_scen = 1
+ * and weight 1.0 every byte equals shems_foresight_track_forecast_dev's on the same record.
+ * weights: HOST [n_problems][n_scen], validated here, copied on `stream` into d_weights (DEVICE, same size, caller-allocated) and read
+ * there by the kernel; they are used as given (the caller normalises them to sum 1).  The other arguments as
+ * shems_foresight_track_forecast_dev; d_problem_of_env names the PROBLEM (0 .. n_problems - 1), not the record.  ONE launch
+ * (k_fs_track_ens), one workgroup per env, no host synchronisation.  An env that does not sit on idx0 of its problem, whose problem's
+ * n_scen records do not all carry that idx0, table_row0 and nrow, or one of whose scenario tables leaves view.total_rows raises
+ * view.err = SHEMS_ERR_INDEX and is not stepped.  SHEMS_ERR_ARG, nothing launched: everything track_forecast_dev refuses, n_scen
+ * outside 1 .. 16, a NULL weight buffer, a weight that is not finite or is <= 0 (the message names the problem and the scenario),
+ * v_doubles < n_problems * n_scen * (T + 1) * nb * ne. */
+int shems_foresight_track_ensemble_dev(const shems_view *v, const shems_foresight_problem *d_problems /* n_problems * n_scen records as
+                                       solve_forecast_dev left them */, int32_t n_problems, int32_t n_scen, const double *weights
+                                       /* HOST [n_problems][n_scen] */, double *d_weights /* DEVICE, same size, caller-allocated */,
+                                       const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V,
+                                       int64_t v_doubles, double *d_results, int64_t results_env, double *d_returns, float *d_targets,
+                                       void *stream);
 /* The audit of tracked passes: where does a pass lose against V?  Q_t(state, a) = reward of step! (LU1:283-316, 343-485; the arrival
  * overwrite LU1:264-281) + V_{t+1}(state') is evaluated over the whole action grid from the state a pass was ACTUALLY in, read back from
  * the reference's 23-column result rows (LU1:476-478; MPS:62-89), whichever controller made them.  csrc/shems_foresight_core.h holds

@@ -17,6 +17,8 @@
 // fs_track_body.h, included into both kernels of a pair.
 // The audit of tracked passes (shems_foresight_audit_dev, the definition: shems_foresight_core.h): k_fs_audit, one launch over
 // passes x hours x actions, a wave per hour, V planes read from global memory, no LDS and no barrier.
+// Hedging over a forecast ensemble (shems_foresight_track_ensemble_dev, the definition: shems_foresight_core.h): the K scenario sweeps
+// are K records of solve_forecast_dev; k_fs_track_ens is the forward pass that weighs every action against all K planes.
 //
 // Compiled with -ffp-contract=off (shems_core.h).
 #include <hip/hip_runtime.h>
@@ -147,6 +149,131 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_track_fc(FsTrackArgs A)
 {
     constexpr bool FC = true;
 #include "fs_track_body.h"
+}
+
+struct FsTrackEnsArgs {
+    FsTrackArgs t;                                 // prob: n_prob * K records, problem-major, scenario-minor; V: their planes
+    int K;                                         // scenarios per problem, 1 .. kFsMaxScen
+    const double *w;                               // [n_prob][K] weights, device memory
+};
+
+// The forward pass hedging over K scenarios (the definition: shems_foresight_core.h).  Shaped like k_fs_track_fc, its own body: one
+// workgroup per env, all T hours in the launch.  The K weights and row offsets of the workgroup's problem go to LDS once; per hour
+// threads 0 .. K - 1 stage (h_countdown, soc_ev) of every scenario's row t + 1 there, then thread `tid` takes actions tid, tid + 256,
+// ...: the DRL step once (fs_step), then the K lookups against the K planes in global memory (every env of a problem reads the same
+// planes: L2), added in scenario order inside the thread (fs_q_ens) -- no partial sum crosses a lane.  The maximum is k_fs_track's.
+__global__ __launch_bounds__(kFsThreads) void k_fs_track_ens(FsTrackEnsArgs E)
+{
+    __shared__ float s_obs[SHEMS_NSTATE];
+    __shared__ double s_bv[kFsWaves];
+    __shared__ int s_ba[kFsWaves];
+    __shared__ double s_w[kFsMaxScen];
+    __shared__ int s_off[kFsMaxScen];
+    __shared__ float s_hn[kFsMaxScen], s_sn[kFsMaxScen];
+    const FsTrackArgs &A = E.t;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t e = blockIdx.x;
+    const shems_view &v = A.v;
+    const FsParams &g = A.g;
+    const int K = E.K;
+    const int N = g.nb * g.ne, NA = g.nab * g.nae;
+    // ---- entry checks, the same answer in every thread ----
+    const int p = A.problem_of_env ? A.problem_of_env[e] : 0;
+    int32_t idx = v.idx[e], step = v.step[e];
+    bool ok = K >= 1 && K <= kFsMaxScen && p >= 0 && p < A.n_prob && A.prob[(int64_t)p * K].idx0 == idx;
+    if (ok) {
+        const shems_foresight_problem *R = A.prob + (int64_t)p * K;
+        const int32_t row0 = R[0].cfg.table_row0, nrow = R[0].cfg.nrow;
+        ok = row0 >= 0 && nrow >= 2 && (int64_t)row0 + nrow <= v.total_rows;
+        for (int k = 0; k < K; ++k) {
+            const int64_t f0 = (int64_t)row0 + R[k].forecast_off;
+            ok = ok && R[k].idx0 == idx && R[k].cfg.table_row0 == row0 && R[k].cfg.nrow == nrow && f0 >= 0 && f0 + nrow <= v.total_rows;
+        }
+    }
+    if (!ok) {
+        if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
+        return;
+    }
+    const shems_foresight_problem P = A.prob[(int64_t)p * K];              // the truth: scenario 0's record without its offset
+    if (tid < K) {
+        s_w[tid] = E.w[(int64_t)p * K + tid];
+        s_off[tid] = A.prob[(int64_t)p * K + tid].forecast_off;
+    }
+    const shems_config cfg = load_cfg(v, e);                                // the env's own config steps the env
+    float obs[SHEMS_NSTATE];
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) obs[k] = v.obs[e * SHEMS_NSTATE + k];
+    if (tid < SHEMS_NSTATE) s_obs[tid] = v.obs[e * SHEMS_NSTATE + tid];
+    __syncthreads();
+    const int64_t v_stride = (int64_t)(A.T + 1) * N;
+    double total = 0.0;
+    for (int t = 0; t < A.T; ++t) {
+        if (idx < 1 || idx + 1 > cfg.nrow || idx + 1 > P.cfg.nrow) {       // row idx + 1 does not exist (Julia: BoundsError)
+            if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
+            break;
+        }
+        if (tid < K) {                                                      // scenario tid's row t + 1 (inside the array: entry checks)
+            const int64_t next0 = (int64_t)P.cfg.table_row0 + fs_belief_off(t + 1, t, s_off[tid]);
+            s_hn[tid] = load_h(v.tables, next0, idx + 1);
+            s_sn[tid] = v.tables[(next0 + idx) * SHEMS_NCOL + 1];
+        }
+        __syncthreads();
+        const double *Vn = A.V + ((int64_t)p * K * (A.T + 1) + t + 1) * N;  // plane t + 1 of scenario 0
+        const float h_cur = load_h(v.tables, P.cfg.table_row0, idx);
+        const EnvIn s{s_obs[0], s_obs[1], s_obs[2], s_obs[3], s_obs[4], s_obs[5]};
+        double best_v = -__builtin_inf();
+        int best_a = kFsNoAction;
+        for (int a = tid; a < NA; a += kFsThreads) {
+            const int ab = a / g.nae, ae = a - ab * g.nae;
+            const FsStep st = fs_step(P.cfg, s, fs_target(ab, g.nab), fs_target(ae, g.nae));
+            const double q = fs_q_ens(st, h_cur, K, s_w, s_hn, s_sn, Vn, v_stride, g, P.scale_b);
+            if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(best_v, off, 64);
+            const int oa = __shfl_xor(best_a, off, 64);
+            if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
+        }
+        if (lane == 0) { s_bv[wave] = best_v; s_ba[wave] = best_a; }
+        __syncthreads();
+        if (tid == 0) {
+#pragma unroll
+            for (int w = 1; w < kFsWaves; ++w)
+                if (fs_better(s_bv[w], s_ba[w], best_v, best_a)) { best_v = s_bv[w]; best_a = s_ba[w]; }
+            const int a = best_a == kFsNoAction ? 0 : best_a;               // every Q a NaN: cannot happen on finite tables
+            const int ab = a / g.nae, ae = a - ab * g.nae;
+            const float a0 = fs_target(ab, g.nab), a1 = fs_target(ae, g.nae);
+            float pre[SHEMS_NSTATE];
+#pragma unroll
+            for (int k = 0; k < SHEMS_NSTATE; ++k) pre[k] = obs[k];
+            double reward;
+            StepFlows f;
+            float B, EV, Bt, EVt;
+            env_advance(cfg, v.tables, obs, idx, step, a0, a1, SHEMS_TRACK_DRL, reward, f, B, EV, Bt, EVt);   // bounds checked above
+            total += reward;
+            if (A.results && (A.results_env < 0 || A.results_env == e)) {
+                double *r = A.results + ((A.results_env < 0 ? e : 0) * (int64_t)A.T + t) * SHEMS_NRESULT;
+                write_results(r, idx, pre, EVt, EV, reward, f, B, Bt);
+            }
+            if (A.targets) {
+                float *tg = A.targets + (e * (int64_t)A.T + t) * 2;
+                tg[0] = a0; tg[1] = a1;
+            }
+#pragma unroll
+            for (int k = 0; k < SHEMS_NSTATE; ++k) s_obs[k] = obs[k];
+        } else {
+            idx += 1;                                                        // every thread follows the row index
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < SHEMS_NSTATE; ++k) v.obs[e * SHEMS_NSTATE + k] = obs[k];
+        v.idx[e] = idx;
+        v.step[e] = step;
+        if (A.returns) A.returns[e] = total;
+    }
 }
 
 struct FsAuditArgs {
@@ -410,6 +537,44 @@ extern "C" int shems_foresight_track_forecast_dev(const shems_view *v, const she
 {
     return fs_track("shems_foresight_track_forecast_dev", true, v, d_problems, n_problems, d_problem_of_env, grid, T, d_V, v_doubles, d_results,
                     results_env, d_returns, d_targets, stream);
+}
+
+extern "C" int shems_foresight_track_ensemble_dev(const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
+                                                  int32_t n_scen, const double *weights, double *d_weights, const int32_t *d_problem_of_env,
+                                                  const shems_foresight_grid *grid, int32_t T, const double *d_V, int64_t v_doubles,
+                                                  double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
+{
+    const char *fn = "shems_foresight_track_ensemble_dev";
+    if (int rc = check_view(v, fn)) return rc;
+    FsParams g;
+    if (int rc = fs_params(grid, fn, g)) return rc;
+    if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; the horizon must be at least 1 hour", fn, (int)T);
+    if (!d_problems || n_problems < 1 || !d_V) return set_error(SHEMS_ERR_ARG, "%s: NULL buffer or no problem", fn);
+    if (n_scen < 1 || n_scen > kFsMaxScen)
+        return set_error(SHEMS_ERR_ARG, "%s: n_scen = %d; an ensemble holds 1 .. %d scenarios", fn, (int)n_scen, kFsMaxScen);
+    if (!weights || !d_weights) return set_error(SHEMS_ERR_ARG, "%s: NULL weight buffer (host weights or their device copy)", fn);
+    for (int32_t p = 0; p < n_problems; ++p)
+        for (int32_t k = 0; k < n_scen; ++k) {
+            const double w = weights[(int64_t)p * n_scen + k];
+            if (!(w > 0.0) || !(w <= 1.7976931348623157e308))                // also a NaN
+                return set_error(SHEMS_ERR_ARG, "%s: problem %d, scenario %d: weight %g; a weight is finite and > 0", fn, (int)p, (int)k, w);
+        }
+    const int64_t N = (int64_t)g.nb * g.ne, recs = (int64_t)n_problems * n_scen;
+    if (v_doubles < recs * (T + 1) * N)
+        return set_error(SHEMS_ERR_ARG, "%s: the V buffer holds %lld float64; %d problems x %d scenarios x %d planes x %lld nodes need %lld", fn,
+                         (long long)v_doubles, (int)n_problems, (int)n_scen, (int)T + 1, (long long)N, (long long)(recs * (T + 1) * N));
+    if (results_env >= v->n_envs) return set_error(SHEMS_ERR_ARG, "%s: results_env %lld outside the batch", fn, (long long)results_env);
+    hipStream_t st = (hipStream_t)stream;
+    // the weights the kernel reads: ordered on the stream; the runtime has staged a pageable source on return
+    if (int rc = hip_ok(hipMemcpyAsync(d_weights, weights, (size_t)recs * sizeof(double), hipMemcpyHostToDevice, st), "upload of the scenario weights"))
+        return rc;
+    FsTrackEnsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.t.v = *v; a.t.prob = d_problems; a.t.n_prob = n_problems; a.t.problem_of_env = d_problem_of_env; a.t.g = g; a.t.T = T; a.t.V = d_V;
+    a.t.results = d_results; a.t.results_env = results_env; a.t.returns = d_returns; a.t.targets = d_targets;
+    a.K = n_scen; a.w = d_weights;
+    hipLaunchKernelGGL(k_fs_track_ens, dim3((unsigned)v->n_envs), dim3(kFsThreads), 0, st, a);
+    return hip_ok(hipGetLastError(), "k_fs_track_ens launch");
 }
 
 extern "C" int shems_foresight_audit_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *d_problems, int32_t n_problems,

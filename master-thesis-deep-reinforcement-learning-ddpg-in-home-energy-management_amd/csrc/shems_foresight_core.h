@@ -181,4 +181,56 @@ SHEMS_HD double fs_audit_v_state(const shems_foresight_problem &P, const FsAudit
     return fs_value(V_cur, g, P.scale_b, h.s.Soc_b, h.s.Soc_ev);
 }
 
+// ---- hedging over a forecast ENSEMBLE (shems_foresight_track_ensemble_dev; tests/foresight_ensemble_ref.py restates it) ----
+// The forecast controller above treats its one table as certain.  An ensemble problem is ONE truth (cfg, idx0) with K scenarios,
+// 1 <= K <= kFsMaxScen: scenario k is a forecast table in the sense above (forecast_off[k], same nrow, same row array) with a float64
+// weight w[k], finite and > 0.  The host layer normalises the weights to sum 1; nothing here renormalises.
+// Planner: for each scenario k the planes are exactly the forecast controller's on the belief "truth up to j, scenario k after":
+// U^k_t is what shems_foresight_solve_forecast_dev leaves in record p * K + k (problem-major, scenario-minor); no new sweep.
+// Controller: at hour t it observes the true state and the true row t.  For action a the DRL step is taken ONCE (fs_step): its reward
+// and (Soc_b', Soc_ev') do not depend on the scenario.  Then
+//   acc = +0.0
+//   for k = 0 .. K - 1, in this order:
+//       Soc_ev'^k = h_next^k >= 0 && h_cur == -1 ? soc_ev_next^k : Soc_ev'               (LU1:270-272, scenario k's row t + 1)
+//       acc = acc + w[k] * fs_value(V[p * K + k][t + 1], Soc_b', Soc_ev'^k)
+//   Qbar = reward + acc
+// with (h_next^k, soc_ev_next^k) from scenario k's row t + 1 -- fs_belief_off(t + 1, t, forecast_off[k]) -- and h_cur the truth's.
+// The first maximum (fs_better) over a = ab * nae + ae wins, and the env is stepped on the truth by the ordinary DRL step.  The sum
+// over k is in THIS order whatever spreads the work, so that the device, a host build and a NumPy restatement agree bit for bit.
+// This is the two-stage scenario programme: the first decision is common, and after it each scenario is optimised with its OWN
+// foresight.  It is therefore OPTIMISTIC about what is learnt after the first stage -- it values hour t + 1 onwards as if the
+// controller then knew which scenario holds -- and nothing says an ensemble does better than one of its members.
+// K = 1, w = 1.0: 0.0 + 1.0 * v = v, so every choice equals the forecast controller's on that record; the same for one scenario
+// twice at w = (0.5, 0.5), since 0.5 v + 0.5 v is exact.  Three copies at (0.5, 0.25, 0.25) need not: 0.75 v rounds.
+constexpr int kFsMaxScen = 16;
+
+struct FsStep {                 // what the DRL step of one action leaves, before any arrival overwrite
+    double reward;
+    float  soc_b, soc_ev;
+};
+
+SHEMS_HD FsStep fs_step(const shems_config &c, const EnvIn &s, float B_target, float EV_target)
+{
+    float B, EV;
+    FsStep o;
+    StepFlows f;
+    action_drl(c, s, B_target, EV_target, B, EV);
+    step_flows(c, s, EV_target, B, EV, false, o.soc_b, o.soc_ev, o.reward, f);
+    return o;
+}
+
+// Qbar of one action.  w, h_next, soc_ev_next: K entries each, in scenario order (any address space the caller can read); V_next: the
+// plane [t + 1] of scenario 0, the plane of scenario k lies v_stride float64 further per scenario ((T + 1) * nb * ne in what
+// solve_forecast_dev leaves).
+SHEMS_HD double fs_q_ens(const FsStep &st, float h_cur, int K, const double *w, const float *h_next, const float *soc_ev_next,
+                         const double *V_next, int64_t v_stride, const FsParams &g, double scale_b)
+{
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const float soc_ev_n = (h_next[k] >= 0.0f && h_cur == -1.0f) ? soc_ev_next[k] : st.soc_ev;
+        acc = acc + w[k] * fs_value(V_next + (int64_t)k * v_stride, g, scale_b, st.soc_b, soc_ev_n);
+    }
+    return st.reward + acc;
+}
+
 }  // namespace shems

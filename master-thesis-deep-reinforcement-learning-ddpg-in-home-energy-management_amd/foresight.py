@@ -13,6 +13,11 @@ memory_plotting_saving.jl:62-89) is a finite-horizon dynamic programme over (Soc
     solve_horizon(..., forecast_table=[...]) -> Values        the same controller planning on a forecast that may be wrong
                                                               (shems_foresight_solve_forecast_dev / _track_forecast_dev)
     persistence_forecast(table, lag) / append_forecasts       the standard naive forecast: hour t is what it was `lag` hours earlier
+    solve_ensemble(..., scenarios=[[...]], weights) -> EnsembleValues
+                                                              the same controller HEDGING over K forecasts: the K sweeps are K records
+                                                              of the one forecast call, track weighs every action against all K planes
+                                                              (shems_foresight_track_ensemble_dev)
+    analog_scenarios(table, lags) / append_scenarios          the "same hour on previous days" ensemble: one persistence forecast per lag
     audit(values, results, problem_of_pass) -> Audit          the hourly regret of ANY tracked pass against V, one launch, parallel over
                                                               passes x hours x actions                   (shems_foresight_audit_dev)
 
@@ -153,6 +158,34 @@ def append_forecasts(tables, lag=24, columns=("electkwh", "PV_generation")):
     return tabs + [persistence_forecast(t, lag, columns) for t in tabs], [len(tabs) + k for k in range(len(tabs))]
 
 
+ANALOG_LAGS = (24, 48, 72, 96, 120, 144, 168)
+MAX_SCENARIOS = 16                        # kFsMaxScen of csrc/shems_foresight_core.h
+
+
+def analog_scenarios(table, lags=ANALOG_LAGS, columns=("electkwh", "PV_generation")):
+    """The "same hour on previous days" ensemble of a [nrow][8] table: one persistence_forecast per lag, in the order of `lags`
+    (default: the same hour of each of the last seven days).  Returns a list of [nrow][8] float32 tables.  As scenario tables of
+    solve_ensemble the ensemble is causal for horizon <= min(lags) (every scenario row is an hour already observed when the plan is
+    made) and not beyond, and nothing refuses that.  Rows below a lag are the truth's in that member, as in persistence_forecast."""
+    lags = [int(l) for l in lags]
+    if not lags:
+        raise ValueError("analog_scenarios needs at least one lag")
+    return [persistence_forecast(table, lag, columns) for lag in lags]
+
+
+def append_scenarios(tables, lags=ANALOG_LAGS, columns=("electkwh", "PV_generation")):
+    """The table list of a batch with the analog ensemble of every table appended: returns (tables + scenarios, index) with
+    index[k] = the list of positions of table k's scenarios in the new list -- an entry of solve_ensemble's `scenarios`.  Build the
+    ShemsBatch that foresight.track steps from the same list, so that both see the same row array."""
+    tabs = list(tables) if isinstance(tables, (list, tuple)) else [tables]
+    out, index = list(tabs), []
+    for t in tabs:
+        sc = analog_scenarios(t, lags, columns)
+        index.append(list(range(len(out), len(out) + len(sc))))
+        out += sc
+    return out, index
+
+
 def _forecast_offsets(forecast_table, problems, row0, nrow):
     """forecast_table (one entry per problem: None or the index of a table) -> forecast_off per problem; row0 / nrow: of the tables."""
     entries = list(forecast_table)
@@ -214,6 +247,9 @@ def _declare(L):
     L.shems_foresight_track_dev.restype = C.c_int
     L.shems_foresight_track_forecast_dev.argtypes = L.shems_foresight_track_dev.argtypes
     L.shems_foresight_track_forecast_dev.restype = C.c_int
+    L.shems_foresight_track_ensemble_dev.argtypes = [C.POINTER(_capi.View), vp, i32, i32, vp, vp, vp, C.POINTER(GridStruct), i32, vp, i64, vp, i64,
+                                                     vp, vp, vp]
+    L.shems_foresight_track_ensemble_dev.restype = C.c_int
     L.shems_foresight_audit_dev.argtypes = [vp, i64, vp, i32, C.POINTER(GridStruct), i32, vp, i64, vp, i32, vp, vp, vp, vp, vp]
     L.shems_foresight_audit_dev.restype = C.c_int
     return L
@@ -351,13 +387,130 @@ def solve_horizon(tables, configs, idx0, nsteps, horizon, control=1, grid=None, 
     return _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon, control, forecast_table)
 
 
+class EnsembleValues:
+    """What solve_ensemble leaves: `values`, the Values of the ONE forecast solve over its P * K records (record p * K + k: problem p
+    under scenario k), n_scen = K, and weights [P][K] float64, normalised to sum 1 per problem.  track takes it; audit refuses it."""
+
+    def __init__(self, values, n_scen, weights):
+        self.values, self.n_scen = values, int(n_scen)
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64)
+        self.n_problems = self.weights.shape[0]
+        self.grid, self.nsteps, self.horizon, self.control, self.total_rows = values.grid, values.nsteps, values.horizon, values.control, values.total_rows
+
+
+def _table_rows(tables):
+    """(row0, nrow) of the tables of a list / one table / a ShemsBatch, without touching a device."""
+    if hasattr(tables, "table_row0"):
+        return [int(x) for x in tables.table_row0], [int(x) for x in tables.table_nrow]
+    tabs = tables if isinstance(tables, (list, tuple)) else [tables]
+    nrow = [int(np.shape(t)[0]) for t in tabs]
+    return [int(x) for x in np.cumsum([0] + nrow)[:-1]], nrow
+
+
+def ensemble_weights(weights, n_problems, n_scen):
+    """[P][K] float64 weights, normalised to sum 1 per problem: None (equal weights), one vector of K for every problem, or [P][K].
+    A weight that is <= 0 or not finite, or a length that does not match, is a ValueError."""
+    P, K = int(n_problems), int(n_scen)
+    if weights is None:
+        w = np.ones((P, K), np.float64)
+    else:
+        w = np.array(weights, np.float64)
+        if w.shape == (K,):
+            w = np.tile(w, (P, 1))
+        if w.shape != (P, K):
+            raise ValueError(f"weights of shape {np.shape(weights)} for {P} problems x {K} scenarios: one vector of {K}, or [{P}][{K}]")
+    bad = np.argwhere(~(np.isfinite(w) & (w > 0)))
+    if bad.size:
+        p, k = (int(x) for x in bad[0])
+        raise ValueError(f"problem {p}, scenario {k}: weight {w[p, k]!r}; a weight is finite and > 0")
+    return np.ascontiguousarray(w / w.sum(axis=1, keepdims=True))
+
+
+def solve_ensemble(tables, configs, idx0, nsteps, horizon, control=1, scenarios=None, weights=None, grid=None):
+    """The planes of the receding-horizon controller that HEDGES over a forecast ensemble (the definition:
+    csrc/shems_foresight_core.h).  tables, configs, idx0, nsteps, horizon, control, grid as solve_horizon.  scenarios: one list per
+    problem of the K table indices of its scenario tables (1 <= K <= 16, the same K for every problem; append_scenarios builds such
+    lists; an index may name the truth itself); weights: None (equal), K weights for every problem, or [P][K], each finite and > 0,
+    normalised here to sum 1.  The K sweeps of a problem are K records of ONE shems_foresight_solve_forecast_dev call (P * K records,
+    problem-major, scenario-minor, no arg-max); track then weighs every action against all K planes
+    (shems_foresight_track_ensemble_dev).  The controller is the two-stage scenario programme: optimistic about what is learnt after
+    the first decision, and not claimed to beat any of its members.  Refused with a ValueError before any device work: ragged
+    scenario lists, K outside 1 .. 16, a bad weight or weight shape, a scenario table with the wrong nrow or outside the tables."""
+    if horizon is None:
+        raise ValueError("solve_ensemble needs a horizon (solve knows the whole pass)")
+    cfgs = list(configs)
+    if scenarios is None:
+        raise ValueError("solve_ensemble needs the scenarios of every problem (lists of table indices; see append_scenarios)")
+    scen = [list(s) if isinstance(s, (list, tuple, np.ndarray)) else [s] for s in scenarios]
+    if len(scen) != len(cfgs):
+        raise ValueError(f"scenarios holds {len(scen)} lists for {len(cfgs)} problems")
+    K = len(scen[0]) if scen else 0
+    if any(len(s) != K for s in scen):
+        raise ValueError(f"ragged scenario lists ({[len(s) for s in scen]}): every problem takes the same number of scenarios")
+    if K < 1 or K > MAX_SCENARIOS:
+        raise ValueError(f"{K} scenarios; an ensemble holds 1 .. {MAX_SCENARIOS}")
+    w = ensemble_weights(weights, len(cfgs), K)
+    row0, nrow = _table_rows(tables)
+    for p, (c, s) in enumerate(zip(cfgs, scen)):
+        for k, i in enumerate(s):
+            if i is None:
+                continue
+            if int(i) != i or int(i) < 0 or int(i) >= len(row0):
+                raise ValueError(f"problem {p}, scenario {k}: table {i!r} is outside the {len(row0)} tables")
+            if nrow[int(i)] != c.nrow:
+                raise ValueError(f"problem {p}, scenario {k}: table {int(i)} has {nrow[int(i)]} rows, its table {c.nrow}")
+    starts = [int(idx0)] * len(cfgs) if np.isscalar(idx0) else [int(i) for i in idx0]
+    if len(starts) != len(cfgs):
+        raise ValueError(f"idx0 holds {len(starts)} start rows for {len(cfgs)} problems")
+    flat = [None if i is None else int(i) for s in scen for i in s]
+    inner = _solve(tables, [c for c in cfgs for _ in range(K)], [i for i in starts for _ in range(K)], nsteps, grid, False, horizon, control, flat)
+    return EnsembleValues(inner, K, w)
+
+
+def _track_ensemble(env, ens, problem_of_env, which):
+    """track's ensemble branch: shems_foresight_track_ensemble_dev on the inner Values' records and planes."""
+    values = ens.values
+    env_rows = int(env.table_row0[-1] + env.table_nrow[-1])
+    if any(values.forecast_off) and values.total_rows != env_rows:
+        raise ValueError(f"the values were solved on a row array of {values.total_rows} rows and the env holds {env_rows}: a forecast "
+                         "pass needs the env's batch to hold the same tables in the same order")
+    import torch
+    L = _declare(_capi.lib())
+    n, T, P, K = env.n, values.nsteps, ens.n_problems, ens.n_scen
+    env.use_torch_stream()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    poe = None
+    if problem_of_env is not None:
+        po = np.ascontiguousarray(problem_of_env, dtype=np.int32)
+        if po.shape != (n,):
+            raise ValueError("problem_of_env must have shape (n_envs,)")
+        poe = torch.from_numpy(po).to(dev)
+    rows = n if which < 0 else 1
+    res = torch.empty((rows, T, _capi.NRESULT), dtype=torch.float64, device=dev)
+    total = torch.zeros(n, dtype=torch.float64, device=dev)
+    tgt = torch.zeros((n, T, 2), dtype=torch.float32, device=dev)
+    d_w = torch.empty((P, K), dtype=torch.float64, device=dev)              # filled by the call, read by the kernel
+    v = env.view()
+    g = values.grid.struct()
+    _capi.check(L.shems_foresight_track_ensemble_dev(
+        C.byref(v), C.c_void_p(values.d_problems.data_ptr()), P, K, ens.weights.ctypes.data_as(C.c_void_p), C.c_void_p(d_w.data_ptr()),
+        C.c_void_p(poe.data_ptr()) if poe is not None else None, C.byref(g), T, C.c_void_p(values.V.data_ptr()), values.V.numel(),
+        C.c_void_p(res.data_ptr()), int(which), C.c_void_p(total.data_ptr()), C.c_void_p(tgt.data_ptr()), env._stream()))
+    out, tot, targets = res.cpu().numpy(), total.cpu().numpy(), tgt.cpu().numpy()      # the pass's one synchronisation
+    env.check_error()
+    return tot, out, targets
+
+
 def track(env, values, problem_of_env=None, which=-1):
     """The greedy controller on the exact env, from the envs' CURRENT state (reset them onto their problem's start row first): env e
     runs values.nsteps hours of problem problem_of_env[e] (None: problem 0) in one launch.  Returns (totals [n] float64, results
     [n][T][23] float64 -- [1][T][23] of env `which` when which >= 0 --, targets [n][T][2] float32, the chosen (B_target,
     EV_target)).  An env that does not sit on its problem's start row raises BoundsError and is not stepped.  Values solved with a
     forecast table go through shems_foresight_track_forecast_dev, which reads the ENV's row array: the env's batch must hold the
-    same tables in the same order as the solve call saw (a different total row count is a ValueError)."""
+    same tables in the same order as the solve call saw (a different total row count is a ValueError).  EnsembleValues (solve_ensemble)
+    go through shems_foresight_track_ensemble_dev under the same condition; problem_of_env then names the problem, not its records."""
+    if isinstance(values, EnsembleValues):
+        return _track_ensemble(env, values, problem_of_env, which)
     forecast = any(values.forecast_off)
     if forecast:
         env_rows = int(env.table_row0[-1] + env.table_nrow[-1])
@@ -445,6 +598,9 @@ def phases(c_ev, h_next):
 def _audit_device(values, results, problem_of_pass=None):
     """audit's checks and its device work: returns (out [n][T][3] float64, best_action [n][T] int32, status [n] int32, the c_ev and
     rewards columns of the rows as host arrays [n][T], problem_of_pass as an int32 array or None) without judging the status."""
+    if isinstance(values, EnsembleValues):
+        raise ValueError("the values were solved on a forecast ensemble: an audit against a belief is not defined (audit the pass against "
+                         "the values of a solve on the true rows)")
     if any(values.forecast_off):
         raise ValueError("the values were solved on a forecast table: an audit against a belief is not defined (audit the pass against "
                          "the values of a solve on the true rows)")
@@ -509,7 +665,7 @@ def audit(values, results, problem_of_pass=None):
     stream (shems_foresight_audit_dev) and one device-to-host copy.  A pass whose rows do not sit on its problem's table rows (or that
     names no problem) raises BoundsError naming the first such pass.
     Regret is not a bound (see Audit).  Values from solve_horizon are accepted: best_q is then what that controller would take.
-    Values solved on a forecast table are refused with a ValueError: an audit against a belief is not defined."""
+    Values solved on a forecast table, and EnsembleValues, are refused with a ValueError: an audit against a belief is not defined."""
     out, act, status, c_ev, rewards, po = _audit_device(values, results, problem_of_pass)
     bad = np.nonzero(status)[0]
     if bad.size:

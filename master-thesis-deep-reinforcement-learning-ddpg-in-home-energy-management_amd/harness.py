@@ -104,7 +104,7 @@ def foresight_values(env, grid=None):
     return foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
 
 
-def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=None, values=None):
+def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=None, values=None, scenario_tables=None, weights=None):
     """The perfect-foresight pass over the data set: reset!(rng = -1), the backward sweep for the env's table(s) over env.maxsteps
     hours (foresight.solve: one problem per distinct config of the batch) and the greedy forward pass on the exact env
     (foresight.track), which steps the envs with the ordinary DRL step (track > 0: penalty kept, 23-column rows).  Returns what
@@ -114,15 +114,30 @@ def inference_foresight(env, grid=None, horizon=None, control=1, forecast_table=
     tables for every problem, or one entry (index or None) per distinct config of the batch in ascending config order, as
     foresight.problems_of_env lists them; foresight.append_forecasts builds such a table list.
     values: the Values of foresight_values(env, grid) (or of any solve for this batch's problems from row 1) to reuse instead of
-    solving again; grid, horizon, control and forecast_table are then not read."""
+    solving again; grid, horizon, control and forecast_table are then not read.
+    scenario_tables (needs a horizon, excludes forecast_table): the controller hedges over a forecast ensemble
+    (foresight.solve_ensemble) -- the indices of the K scenario tables among the env's own tables for every problem, or one such list
+    per distinct config; foresight.append_scenarios builds such a table list.  weights: as solve_ensemble (None: equal)."""
     from . import foresight
     env.use_torch_stream()
     env.reset_(-1)
     cfgs, idx0, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
     if forecast_table is not None and horizon is None:
         raise ValueError("a forecast table needs a horizon (the perfect-foresight pass knows the whole series)")
+    if scenario_tables is not None or weights is not None:
+        if scenario_tables is None:
+            raise ValueError("weights need scenario_tables")
+        if horizon is None:
+            raise ValueError("scenario tables need a horizon (the perfect-foresight pass knows the whole series)")
+        if forecast_table is not None:
+            raise ValueError("scenario_tables and forecast_table exclude each other (one forecast table is an ensemble of one)")
     if values is not None:
         pass
+    elif scenario_tables is not None:
+        scen = list(scenario_tables)
+        if not scen or np.ndim(scen[0]) == 0:
+            scen = [scen] * len(cfgs)
+        values = foresight.solve_ensemble(env, cfgs, idx0, env.maxsteps, horizon, control, scenarios=scen, weights=weights, grid=grid)
     elif horizon is None:
         values = foresight.solve(env, cfgs, idx0, env.maxsteps, grid, want_argmax=False)
     else:
@@ -183,13 +198,18 @@ def write_to_regret_file(audit, results, path, pass_index=0):
 def foresight_seed(horizon=None, control=1, forecast=None):
     """The tracker's seed column (and the file-name suffix) of a foresight pass: foresight, foresight_h24, foresight_h24_c12; with a
     persistence forecast -- forecast = lag, or (lag, ev) with ev true when the EV columns are forecast too -- foresight_h24_p24,
-    foresight_h24_c12_p24ev."""
+    foresight_h24_c12_p24ev; with the analog ensemble -- forecast = ("analog", lags, ev) -- foresight_h24_a24-48-72, ..._a24-48-72ev."""
     if horizon is None:
         if forecast is not None:
             raise ValueError("a forecast needs a horizon")
         return "foresight"
     name = f"foresight_h{int(horizon)}" + (f"_c{int(control)}" if int(control) != 1 else "")
-    if forecast is not None:
+    if isinstance(forecast, (tuple, list)) and len(forecast) == 3 and forecast[0] == "analog":
+        lags = [int(l) for l in forecast[1]]
+        if not lags:
+            raise ValueError("an analog ensemble needs at least one lag")
+        name += "_a" + "-".join(str(l) for l in lags) + ("ev" if forecast[2] else "")
+    elif forecast is not None:
         lag, ev = forecast if isinstance(forecast, (tuple, list)) else (forecast, False)
         name += f"_p{int(lag)}" + ("ev" if ev else "")
     return name
@@ -198,7 +218,8 @@ def foresight_seed(horizon=None, control=1, forecast=None):
 def foresight_file_name(job_id, run, case, out_dir="out/tracker", horizon=None, control=1, forecast=None):
     """The results file of the perfect-foresight pass, next to the rule-based one of results_file_name; with a horizon, of the
     receding-horizon pass: ..._foresight_h{H}.csv, ..._foresight_h{H}_c{c}.csv when control != 1; with a persistence forecast
-    (forecast = lag or (lag, ev), see foresight_seed) ..._foresight_h{H}[_c{c}]_p{lag}.csv, _p{lag}ev when the EV columns are forecast."""
+    (forecast = lag or (lag, ev), see foresight_seed) ..._foresight_h{H}[_c{c}]_p{lag}.csv, _p{lag}ev when the EV columns are forecast;
+    with the analog ensemble (forecast = ("analog", lags, ev)) ..._foresight_h{H}[_c{c}]_a{lag}-{lag}-....csv, `ev` appended likewise."""
     return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_{foresight_seed(horizon, control, forecast)}.csv")
 
 

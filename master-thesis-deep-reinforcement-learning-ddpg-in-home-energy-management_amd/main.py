@@ -26,7 +26,8 @@ Differences that follow from the platform, all explicit:
     default 1) add one receding-horizon pass per horizon: ..._foresight_h24.csv / ..._foresight_h24_c12.csv, seed = that suffix;
     SHEMS_FORESIGHT_FORECAST=persistence[:LAG[:ev]] (needs a horizon; LAG default 24 hours) adds, after each of those, the same
     controller planning on the persistence forecast of load and PV -- with `ev` of h_countdown and soc_ev too --:
-    ..._foresight_h24_p24.csv / ..._foresight_h24_p24ev.csv;
+    ..._foresight_h24_p24.csv / ..._foresight_h24_p24ev.csv; SHEMS_FORESIGHT_FORECAST=analog:24,48,72[:ev] instead adds the controller
+    that hedges over the analog ensemble of those lags with equal weights (foresight.solve_ensemble): ..._foresight_h24_a24-48-72.csv;
     SHEMS_FORESIGHT_REGRET=1 (needs SHEMS_FORESIGHT=1) adds one <results file>_regret.csv next to every results file of the tracking
     block -- the hourly regret of that pass against ONE perfect-foresight solve (harness.regret_of; the forecast passes are audited
     against the truth like the rest);
@@ -225,14 +226,24 @@ def foresight_regret(environ=os.environ):
 
 
 def foresight_forecast(environ=os.environ):
-    """SHEMS_FORESIGHT_FORECAST = persistence[:LAG[:ev]] -> (lag, ev), None when unset.  It needs SHEMS_FORESIGHT_HORIZON; a
-    malformed value is refused by name."""
+    """SHEMS_FORESIGHT_FORECAST = persistence[:LAG[:ev]] -> (lag, ev), or analog:LAG,LAG,...[:ev] -> ("analog", (lags), ev) (1 .. 16
+    lags, each >= 1); None when unset.  It needs SHEMS_FORESIGHT_HORIZON; a malformed value is refused by name."""
     raw = environ.get("SHEMS_FORESIGHT_FORECAST")
     if raw is None:
         return None
     if environ.get("SHEMS_FORESIGHT_HORIZON") is None:
         raise ValueError("SHEMS_FORESIGHT_FORECAST is set without SHEMS_FORESIGHT_HORIZON")
     parts = raw.split(":")
+    if parts[0] == "analog":
+        if len(parts) not in (2, 3) or (len(parts) == 3 and parts[2] != "ev"):
+            raise ValueError(f"SHEMS_FORESIGHT_FORECAST = {raw!r} is not analog:LAG,LAG,...[:ev]")
+        try:
+            lags = tuple(int(x) for x in parts[1].split(","))
+        except ValueError:
+            raise ValueError(f"SHEMS_FORESIGHT_FORECAST = {raw!r}: the lags are not a comma list of integers") from None
+        if min(lags) < 1 or len(lags) > 16:
+            raise ValueError(f"SHEMS_FORESIGHT_FORECAST = {raw!r}: 1 .. 16 lags of 1 or more hours each")
+        return "analog", lags, len(parts) == 3
     if parts[0] != "persistence" or len(parts) > 3 or (len(parts) == 3 and parts[2] != "ev"):
         raise ValueError(f"SHEMS_FORESIGHT_FORECAST = {raw!r} is not persistence[:LAG[:ev]]")
     try:
@@ -384,10 +395,16 @@ def main(environ=os.environ, cwd=".", log=print):
         written.append(path)
         audited.append((path, results[0]))
         env_fc = None
-        if forecast is not None:                                         # the same table with its persistence forecast behind it
+        fc_kw = {}
+        if forecast is not None:                                         # the same table with its persistence forecast(s) behind it
             from . import foresight
-            cols = ("electkwh", "PV_generation") + (foresight.EV_COLUMNS if forecast[1] else ())
-            both, fc_index = foresight.append_forecasts([tabs[cfg.run]], forecast[0], cols)
+            cols = ("electkwh", "PV_generation") + (foresight.EV_COLUMNS if forecast[-1] else ())
+            if forecast[0] == "analog":                                  # the ensemble: one scenario table per lag, equal weights
+                both, sc_index = foresight.append_scenarios([tabs[cfg.run]], forecast[1], cols)
+                fc_kw = dict(scenario_tables=sc_index[0])
+            else:
+                both, fc_index = foresight.append_forecasts([tabs[cfg.run]], forecast[0], cols)
+                fc_kw = dict(forecast_table=fc_index[0])
             env_fc = ShemsBatch(1, EP_LENGTH[cfg.season, cfg.run], both, [make_config(cfg.charger_id, 0, tabs[cfg.run].shape[0])],
                                 device=cfg.gpu_id).use_torch_stream()
         for h in horizons:                                               # the deployable case: h hours of forecast, a plan every `control`
@@ -398,7 +415,7 @@ def main(environ=os.environ, cwd=".", log=print):
             written.append(path)
             audited.append((path, results[0]))
             if env_fc is not None:                                       # ... and planning on a forecast that is wrong
-                _, results = harness.inference_foresight(env_fc, horizon=h, control=control, forecast_table=fc_index[0])
+                _, results = harness.inference_foresight(env_fc, horizon=h, control=control, **fc_kw)
                 path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case, horizon=h, control=control, forecast=forecast)
                 harness.write_to_results_file(results[0], path)
                 harness.write_to_tracker_file(path, seed=harness.foresight_seed(h, control, forecast), best=False, idx=0, **tk)
