@@ -712,7 +712,7 @@ int shems_foresight_track_dev(const shems_view *v, const shems_foresight_problem
  * equals solve_horizon_dev's bit for bit.  Arguments as shems_foresight_solve_horizon_dev, but cfg, idx0 AND forecast_off of the host
  * records are read.  SHEMS_ERR_ARG, nothing launched: everything solve_horizon_dev refuses, and a forecast table that leaves the row
  * array (table_row0 + forecast_off < 0 or table_row0 + forecast_off + nrow > total_rows; the message names the problem and both row
- * numbers).  ONE launch (k_fs_window_fc). */
+ * numbers).  ONE launch (k_fs_window). */
 int shems_foresight_solve_forecast_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
                                        shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
                                        int32_t horizon, int32_t control, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream);

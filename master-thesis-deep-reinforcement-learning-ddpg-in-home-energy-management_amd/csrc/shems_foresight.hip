@@ -13,12 +13,14 @@
 // other, a workgroup barrier between sweeps and nothing else; no workgroup waits on another.  Nodes and actions are spread as in the
 // backward sweep (wave w: nodes w, w + waves, ...), and only the planes the forward pass will read leave the CU.
 // Planning on a forecast (shems_foresight_solve_forecast_dev / _track_forecast_dev, the belief: shems_foresight_core.h): the same two
-// kernels with their rows taken where fs_belief_off says -- k_fs_window_fc, k_fs_track_fc; the bodies are fs_window_body.h and
-// fs_track_body.h, included into both kernels of a pair.
+// kernels, k_fs_window and k_fs_track, with their rows taken where fs_belief_off says.  The entry point sets the launch-uniform `fc` of
+// the kernel's arguments: 0 on the true rows (forecast_off is then not used, whatever the records hold), 1 under a forecast.
 // The audit of tracked passes (shems_foresight_audit_dev, the definition: shems_foresight_core.h): k_fs_audit, one launch over
 // passes x hours x actions, a wave per hour, V planes read from global memory, no LDS and no barrier.
 // Hedging over a forecast ensemble (shems_foresight_track_ensemble_dev, the definition: shems_foresight_core.h): the K scenario sweeps
 // are K records of solve_forecast_dev; k_fs_track_ens is the forward pass that weighs every action against all K planes.
+// One kernel per role.  What the kernels share exists once: the wave maximum (fs_wave_best, all five reductions) and, for the two forward
+// kernels, the block maximum, thread 0's step-and-record and the final stores (fs_block_best, fs_step_record, fs_track_store).
 //
 // Compiled with -ffp-contract=off (shems_core.h).
 #include <hip/hip_runtime.h>
@@ -41,6 +43,18 @@ constexpr int kFsMaxPlaneBytes = 150000;           // of the 160 KB of LDS a gfx
 #endif
 constexpr int kFsWindowThreads = SHEMS_FS_WINDOW_THREADS;
 static_assert(kFsWindowThreads % 64 == 0 && kFsWindowThreads >= 64 && kFsWindowThreads <= 1024, "whole waves, at most 16");
+
+// The (value, index) maximum over a wave: a butterfly with fs_better, so every lane ends with the same pair -- the first maximum,
+// whatever lane held it.
+__device__ __forceinline__ void fs_wave_best(double &best_v, int &best_a)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(best_v, off, 64);
+        const int oa = __shfl_xor(best_a, off, 64);
+        if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
+    }
+}
 
 struct FsSolveArgs {
     const float *tables;
@@ -85,12 +99,7 @@ __global__ __launch_bounds__(kFsThreads) __attribute__((amdgpu_waves_per_eu(4)))
             const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), s_v, g, P.scale_b);
             if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(best_v, off, 64);
-            const int oa = __shfl_xor(best_a, off, 64);
-            if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
-        }
+        fs_wave_best(best_v, best_a);
         if (lane == 0) {
             Vt[node] = best_v;
             if (A.arg) A.arg[((int64_t)p * A.T + A.t) * N + node] = best_a;
@@ -103,6 +112,7 @@ struct FsWindowArgs {
     const shems_foresight_problem *prob;
     FsParams g;
     int T, H, c;                                   // hours of the pass, horizon, control
+    int fc;                                        // launch-uniform: 1 = the plans read a forecast (the belief: shems_foresight_core.h)
     double *V;
     int32_t *arg;
 };
@@ -111,23 +121,72 @@ struct FsWindowArgs {
 // two table rows in s_row[k & 1], reads plane k & 1 and writes the other; the one barrier per sweep orders all three (a wave that is
 // one sweep ahead writes what the sweep before the slower waves' current one read).  Registers as k_fs_backward: held to 4 waves per
 // SIMD (128 VGPRs), no scratch.
+// A.fc: the plan's belief (shems_foresight_core.h): the two rows of a sweep no longer sit next to each other in memory, so lanes 0-7 of
+// wave 0 load the current row and lanes 8-15 the next, each from its own wave-uniform base formed inside the sweep.
 __global__ __launch_bounds__(kFsWindowThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_fs_window(FsWindowArgs A)
 {
-    constexpr bool FC = false;
-#include "fs_window_body.h"
-}
-
-// The window kernel under a belief: the same body, the rows of a sweep taken where fs_belief_off says (fs_window_body.h).
-__global__ __launch_bounds__(kFsWindowThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_fs_window_fc(FsWindowArgs A)
-{
-    constexpr bool FC = true;
-#include "fs_window_body.h"
+    extern __shared__ __attribute__((aligned(16))) double s_v[];            // [2][nb * ne]
+    __shared__ float s_row[2][2 * SHEMS_NCOL];                              // rows idx0 + t and idx0 + t + 1 of the sweep's hour
+    constexpr int threads = kFsWindowThreads, waves = threads / 64;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);              // the same in every lane: node indices stay in scalar registers
+    const int p = blockIdx.y, j = (int)blockIdx.x * A.c;
+    const FsParams &g = A.g;
+    const int N = g.nb * g.ne, NA = g.nab * g.nae;
+    const shems_foresight_problem P = A.prob[p];
+    const int hi = fs_plan_end(j, A.H, A.T), lo = fs_plan_first(j, A.arg != nullptr);
+    double *Vp = A.V + (int64_t)p * (A.T + 1) * N;
+    int32_t *argp = A.arg ? A.arg + (int64_t)p * A.T * N : nullptr;
+    const bool zeros_out = fs_plan_keeps_plane(j, A.c, A.T, hi);            // U_hi = 0: the plane the forward pass reads at hour hi - 1
+    for (int i = tid; i < N; i += threads) {
+        s_v[i] = 0.0;
+        if (zeros_out) Vp[(int64_t)hi * N + i] = 0.0;
+    }
+    int cur = 0;
+    for (int t = hi - 1; t >= lo; --t, cur ^= 1) {
+        const float *rows = A.tables + ((int64_t)P.cfg.table_row0 + P.idx0 + t - 1) * SHEMS_NCOL;      // the same address in every lane
+        if (wave == 0) {
+            int l = lane;
+            asm volatile("" : "+v"(l));                                      // formed here: no per-lane address lives across the sweeps
+            if (A.fc) {
+                const float *r0 = rows + (int64_t)fs_belief_off(t, j, P.forecast_off) * SHEMS_NCOL;                  // hour t
+                const float *r1 = rows + ((int64_t)fs_belief_off(t + 1, j, P.forecast_off) + 1) * SHEMS_NCOL;        // hour t + 1
+                if (l < 2 * SHEMS_NCOL) s_row[cur][l] = (l < SHEMS_NCOL ? r0 : r1)[l & (SHEMS_NCOL - 1)];
+            } else {
+                if (l < 2 * SHEMS_NCOL) s_row[cur][l] = rows[l];
+            }
+        }
+        __syncthreads();
+        const float *row = s_row[cur];
+        const double *Vn = s_v + cur * N;
+        double *Vt = s_v + (cur ^ 1) * N;
+        const bool v_out = fs_plan_keeps_plane(j, A.c, A.T, t), a_out = argp && fs_plan_keeps_argmax(j, A.c, A.T, t);
+        const float h_cur = row[0], h_next = row[SHEMS_NCOL], soc_ev_next = row[SHEMS_NCOL + 1];
+        for (int node = wave; node < N; node += waves) {                    // wave-uniform
+            const int ib = node / g.ne, ie = node - ib * g.ne;
+            const EnvIn s{fs_soc_b_node(P, g.nb, ib), fs_soc_ev_node(g, ie), h_cur, row[2], row[3], row[4]};
+            double best_v = -__builtin_inf();
+            int best_a = kFsNoAction;
+            for (int a = lane; a < NA; a += 64) {
+                const int ab = a / g.nae, ae = a - ab * g.nae;
+                const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), Vn, g, P.scale_b);
+                if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
+            }
+            fs_wave_best(best_v, best_a);
+            if (lane == 0) {
+                Vt[node] = best_v;
+                if (v_out) Vp[(int64_t)t * N + node] = best_v;
+                if (a_out) argp[(int64_t)t * N + node] = best_a;
+            }
+        }
+    }
 }
 
 struct FsTrackArgs {
     shems_view v;
     const shems_foresight_problem *prob;
     int n_prob;
+    int fc;                                        // launch-uniform: 1 = the next row comes from the record's forecast table
     const int32_t *problem_of_env;
     FsParams g;
     int T;
@@ -138,17 +197,122 @@ struct FsTrackArgs {
     float *targets;                                // [n][T][2] or null
 };
 
-__global__ __launch_bounds__(kFsThreads) void k_fs_track(FsTrackArgs A)
+// ---- what the two forward kernels (k_fs_track, k_fs_track_ens) share: one workgroup of kFsThreads per env ----
+struct FsTrackLds {
+    float obs[SHEMS_NSTATE];                       // the env's state, published by thread 0 after every step
+    double bv[kFsWaves];                           // the waves' maxima
+    int ba[kFsWaves];
+};
+
+// The block maximum: wave -> LDS -> thread 0, which alone ends with the workgroup's pair.  Holds the one barrier between the two.
+__device__ __forceinline__ void fs_block_best(FsTrackLds &S, double &best_v, int &best_a)
 {
-    constexpr bool FC = false;
-#include "fs_track_body.h"
+    const int tid = threadIdx.x;
+    fs_wave_best(best_v, best_a);
+    if ((tid & 63) == 0) { S.bv[tid >> 6] = best_v; S.ba[tid >> 6] = best_a; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < kFsWaves; ++w)
+            if (fs_better(S.bv[w], S.ba[w], best_v, best_a)) { best_v = S.bv[w]; best_a = S.ba[w]; }
+    }
 }
 
-// The forward pass under a forecast: the arrival overwrite's next row comes from the forecast table (fs_track_body.h).
-__global__ __launch_bounds__(kFsThreads) void k_fs_track_fc(FsTrackArgs A)
+// Thread 0's step-and-record of hour t: the winning action steps env e with the ordinary DRL step, the results and targets rows are
+// written and the new state is published in S.obs.  The caller has checked that row idx + 1 exists.
+__device__ __forceinline__ void fs_step_record(const FsTrackArgs &A, const shems_config &cfg, int64_t e, int t, int best_a, FsTrackLds &S,
+                                               float (&obs)[SHEMS_NSTATE], int32_t &idx, int32_t &step, double &total)
 {
-    constexpr bool FC = true;
-#include "fs_track_body.h"
+    const FsParams &g = A.g;
+    const int a = best_a == kFsNoAction ? 0 : best_a;                       // every Q a NaN: cannot happen on finite tables
+    const int ab = a / g.nae, ae = a - ab * g.nae;
+    const float a0 = fs_target(ab, g.nab), a1 = fs_target(ae, g.nae);
+    float pre[SHEMS_NSTATE];
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) pre[k] = obs[k];
+    double reward;
+    StepFlows f;
+    float B, EV, Bt, EVt;
+    env_advance(cfg, A.v.tables, obs, idx, step, a0, a1, SHEMS_TRACK_DRL, reward, f, B, EV, Bt, EVt);
+    total += reward;
+    if (A.results && (A.results_env < 0 || A.results_env == e)) {
+        double *r = A.results + ((A.results_env < 0 ? e : 0) * (int64_t)A.T + t) * SHEMS_NRESULT;
+        write_results(r, idx, pre, EVt, EV, reward, f, B, Bt);
+    }
+    if (A.targets) {
+        float *tg = A.targets + (e * (int64_t)A.T + t) * 2;
+        tg[0] = a0; tg[1] = a1;
+    }
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) S.obs[k] = obs[k];
+}
+
+// Thread 0's final stores: the env where the pass left it, and its total.
+__device__ __forceinline__ void fs_track_store(const FsTrackArgs &A, int64_t e, const float (&obs)[SHEMS_NSTATE], int32_t idx, int32_t step,
+                                               double total)
+{
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) A.v.obs[e * SHEMS_NSTATE + k] = obs[k];
+    A.v.idx[e] = idx;
+    A.v.step[e] = step;
+    if (A.returns) A.returns[e] = total;
+}
+
+// The forward pass on one value function.  A.fc: the controller does not know row t + 1 yet: h_countdown / soc_ev of the next row come
+// from the forecast table, which must lie inside the row array (checked here, against the view's total_rows: the records may come from
+// a solve on another array).  Without it forecast_off is not used and that check is skipped.
+__global__ __launch_bounds__(kFsThreads) void k_fs_track(FsTrackArgs A)
+{
+    __shared__ FsTrackLds S;
+    const int tid = threadIdx.x;
+    const int64_t e = blockIdx.x;
+    const shems_view &v = A.v;
+    const FsParams &g = A.g;
+    const int N = g.nb * g.ne, NA = g.nab * g.nae;
+    // ---- entry checks, the same answer in every thread ----
+    const int p = A.problem_of_env ? A.problem_of_env[e] : 0;
+    int32_t idx = v.idx[e], step = v.step[e];
+    if (p < 0 || p >= A.n_prob || A.prob[p].idx0 != idx) {
+        if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
+        return;
+    }
+    const shems_foresight_problem P = A.prob[p];
+    if (A.fc && ((int64_t)P.cfg.table_row0 + P.forecast_off < 0 || (int64_t)P.cfg.table_row0 + P.forecast_off + P.cfg.nrow > v.total_rows)) {
+        if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
+        return;
+    }
+    const int forecast_off = A.fc ? P.forecast_off : 0;                     // fc == 0: the member is ignored, whatever the record holds
+    const shems_config cfg = load_cfg(v, e);                                // the env's own config steps the env
+    float obs[SHEMS_NSTATE];
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) obs[k] = v.obs[e * SHEMS_NSTATE + k];
+    if (tid < SHEMS_NSTATE) S.obs[tid] = v.obs[e * SHEMS_NSTATE + tid];
+    __syncthreads();
+    double total = 0.0;
+    for (int t = 0; t < A.T; ++t) {
+        if (idx < 1 || idx + 1 > cfg.nrow || idx + 1 > P.cfg.nrow) {       // row idx + 1 does not exist (Julia: BoundsError)
+            if (tid == 0) raise(v.err, SHEMS_ERR_INDEX);
+            break;
+        }
+        const double *Vn = A.V + ((int64_t)p * (A.T + 1) + t + 1) * N;
+        const float h_cur = load_h(v.tables, P.cfg.table_row0, idx);
+        const int64_t next0 = (int64_t)P.cfg.table_row0 + fs_belief_off(t + 1, t, forecast_off);
+        const float h_next = load_h(v.tables, next0, idx + 1);
+        const float soc_ev_next = v.tables[(next0 + idx) * SHEMS_NCOL + 1];
+        const EnvIn s{S.obs[0], S.obs[1], S.obs[2], S.obs[3], S.obs[4], S.obs[5]};
+        double best_v = -__builtin_inf();
+        int best_a = kFsNoAction;
+        for (int a = tid; a < NA; a += kFsThreads) {
+            const int ab = a / g.nae, ae = a - ab * g.nae;
+            const double q = fs_q(P.cfg, s, h_cur, h_next, soc_ev_next, fs_target(ab, g.nab), fs_target(ae, g.nae), Vn, g, P.scale_b);
+            if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
+        }
+        fs_block_best(S, best_v, best_a);
+        if (tid == 0) fs_step_record(A, cfg, e, t, best_a, S, obs, idx, step, total);
+        else idx += 1;                                                       // every thread follows the row index
+        __syncthreads();
+    }
+    if (tid == 0) fs_track_store(A, e, obs, idx, step, total);
 }
 
 struct FsTrackEnsArgs {
@@ -157,21 +321,20 @@ struct FsTrackEnsArgs {
     const double *w;                               // [n_prob][K] weights, device memory
 };
 
-// The forward pass hedging over K scenarios (the definition: shems_foresight_core.h).  Shaped like k_fs_track_fc, its own body: one
+// The forward pass hedging over K scenarios (the definition: shems_foresight_core.h).  Shaped like k_fs_track under a forecast: one
 // workgroup per env, all T hours in the launch.  The K weights and row offsets of the workgroup's problem go to LDS once; per hour
 // threads 0 .. K - 1 stage (h_countdown, soc_ev) of every scenario's row t + 1 there, then thread `tid` takes actions tid, tid + 256,
 // ...: the DRL step once (fs_step), then the K lookups against the K planes in global memory (every env of a problem reads the same
-// planes: L2), added in scenario order inside the thread (fs_q_ens) -- no partial sum crosses a lane.  The maximum is k_fs_track's.
+// planes: L2), added in scenario order inside the thread (fs_q_ens) -- no partial sum crosses a lane.  The maximum, the step and the
+// stores are k_fs_track's (fs_block_best, fs_step_record, fs_track_store).
 __global__ __launch_bounds__(kFsThreads) void k_fs_track_ens(FsTrackEnsArgs E)
 {
-    __shared__ float s_obs[SHEMS_NSTATE];
-    __shared__ double s_bv[kFsWaves];
-    __shared__ int s_ba[kFsWaves];
+    __shared__ FsTrackLds S;
     __shared__ double s_w[kFsMaxScen];
     __shared__ int s_off[kFsMaxScen];
     __shared__ float s_hn[kFsMaxScen], s_sn[kFsMaxScen];
     const FsTrackArgs &A = E.t;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t e = blockIdx.x;
     const shems_view &v = A.v;
     const FsParams &g = A.g;
@@ -203,7 +366,7 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_track_ens(FsTrackEnsArgs E)
     float obs[SHEMS_NSTATE];
 #pragma unroll
     for (int k = 0; k < SHEMS_NSTATE; ++k) obs[k] = v.obs[e * SHEMS_NSTATE + k];
-    if (tid < SHEMS_NSTATE) s_obs[tid] = v.obs[e * SHEMS_NSTATE + tid];
+    if (tid < SHEMS_NSTATE) S.obs[tid] = v.obs[e * SHEMS_NSTATE + tid];
     __syncthreads();
     const int64_t v_stride = (int64_t)(A.T + 1) * N;
     double total = 0.0;
@@ -220,7 +383,7 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_track_ens(FsTrackEnsArgs E)
         __syncthreads();
         const double *Vn = A.V + ((int64_t)p * K * (A.T + 1) + t + 1) * N;  // plane t + 1 of scenario 0
         const float h_cur = load_h(v.tables, P.cfg.table_row0, idx);
-        const EnvIn s{s_obs[0], s_obs[1], s_obs[2], s_obs[3], s_obs[4], s_obs[5]};
+        const EnvIn s{S.obs[0], S.obs[1], S.obs[2], S.obs[3], S.obs[4], S.obs[5]};
         double best_v = -__builtin_inf();
         int best_a = kFsNoAction;
         for (int a = tid; a < NA; a += kFsThreads) {
@@ -229,51 +392,12 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_track_ens(FsTrackEnsArgs E)
             const double q = fs_q_ens(st, h_cur, K, s_w, s_hn, s_sn, Vn, v_stride, g, P.scale_b);
             if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(best_v, off, 64);
-            const int oa = __shfl_xor(best_a, off, 64);
-            if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
-        }
-        if (lane == 0) { s_bv[wave] = best_v; s_ba[wave] = best_a; }
-        __syncthreads();
-        if (tid == 0) {
-#pragma unroll
-            for (int w = 1; w < kFsWaves; ++w)
-                if (fs_better(s_bv[w], s_ba[w], best_v, best_a)) { best_v = s_bv[w]; best_a = s_ba[w]; }
-            const int a = best_a == kFsNoAction ? 0 : best_a;               // every Q a NaN: cannot happen on finite tables
-            const int ab = a / g.nae, ae = a - ab * g.nae;
-            const float a0 = fs_target(ab, g.nab), a1 = fs_target(ae, g.nae);
-            float pre[SHEMS_NSTATE];
-#pragma unroll
-            for (int k = 0; k < SHEMS_NSTATE; ++k) pre[k] = obs[k];
-            double reward;
-            StepFlows f;
-            float B, EV, Bt, EVt;
-            env_advance(cfg, v.tables, obs, idx, step, a0, a1, SHEMS_TRACK_DRL, reward, f, B, EV, Bt, EVt);   // bounds checked above
-            total += reward;
-            if (A.results && (A.results_env < 0 || A.results_env == e)) {
-                double *r = A.results + ((A.results_env < 0 ? e : 0) * (int64_t)A.T + t) * SHEMS_NRESULT;
-                write_results(r, idx, pre, EVt, EV, reward, f, B, Bt);
-            }
-            if (A.targets) {
-                float *tg = A.targets + (e * (int64_t)A.T + t) * 2;
-                tg[0] = a0; tg[1] = a1;
-            }
-#pragma unroll
-            for (int k = 0; k < SHEMS_NSTATE; ++k) s_obs[k] = obs[k];
-        } else {
-            idx += 1;                                                        // every thread follows the row index
-        }
+        fs_block_best(S, best_v, best_a);
+        if (tid == 0) fs_step_record(A, cfg, e, t, best_a, S, obs, idx, step, total);
+        else idx += 1;                                                       // every thread follows the row index
         __syncthreads();
     }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < SHEMS_NSTATE; ++k) v.obs[e * SHEMS_NSTATE + k] = obs[k];
-        v.idx[e] = idx;
-        v.step[e] = step;
-        if (A.returns) A.returns[e] = total;
-    }
+    if (tid == 0) fs_track_store(A, e, obs, idx, step, total);
 }
 
 struct FsAuditArgs {
@@ -328,12 +452,7 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_audit(FsAuditArgs A)
         const double q = fs_audit_q(P, h, a, Vn, g);
         if (fs_better(q, a, best_v, best_a)) { best_v = q; best_a = a; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(best_v, off, 64);
-        const int oa = __shfl_xor(best_a, off, 64);
-        if (fs_better(ov, oa, best_v, best_a)) { best_v = ov; best_a = oa; }
-    }
+    fs_wave_best(best_v, best_a);
     if (lane == 0) {
         o[0] = best_v;
         o[1] = fs_audit_achieved(P, r, t + 1 < A.T ? r + SHEMS_NRESULT : nullptr, Vn, g);
@@ -443,7 +562,7 @@ extern "C" int shems_foresight_solve_dev(const float *d_tables, int64_t total_ro
     return hip_ok(hipGetLastError(), "k_fs_backward launch");
 }
 
-// Both window entry points: the checks, the per-kernel LDS opt-in, the upload and the one launch.
+// Both window entry points: the checks, the kernel's LDS opt-in, the upload and the one launch.
 static int fs_solve_window(const char *fn, bool forecast, const float *d_tables, int64_t total_rows, const shems_foresight_problem *problems,
                            shems_foresight_problem *d_problems, int32_t n_problems, const shems_foresight_grid *grid, int32_t T,
                            int32_t horizon, int32_t control, double *d_V, int64_t v_doubles, int32_t *d_argmax, void *stream)
@@ -460,20 +579,14 @@ static int fs_solve_window(const char *fn, bool forecast, const float *d_tables,
                          (int)g.nb, (int)g.ne, (long long)(2 * N * 8), kFsMaxPlaneBytes);
     if (int rc = fs_check_v(fn, n_problems, T, N, v_doubles)) return rc;
     const int lds = (int)(2 * N * 8);
-    static std::atomic<uint64_t> optin{0}, optin_fc{0};                     // the opt-in is per function
-    if (int rc = forecast ? lds_optin(optin_fc, (const void *)k_fs_window_fc, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_window_fc)")
-                          : lds_optin(optin, (const void *)k_fs_window, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_window)"))
-        return rc;
+    static std::atomic<uint64_t> optin{0};                                  // per device, once (129 x 65 fails at launch without it)
+    if (int rc = lds_optin(optin, (const void *)k_fs_window, kFsMaxPlaneBytes, "hipFuncSetAttribute(k_fs_window)")) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = fs_upload(recs, d_problems, st)) return rc;
     FsWindowArgs a;
     std::memset(&a, 0, sizeof a);
-    a.tables = d_tables; a.prob = d_problems; a.g = g; a.T = T; a.H = horizon; a.c = control; a.V = d_V; a.arg = d_argmax;
+    a.tables = d_tables; a.prob = d_problems; a.g = g; a.T = T; a.H = horizon; a.c = control; a.fc = forecast; a.V = d_V; a.arg = d_argmax;
     const dim3 gridDim((unsigned)fs_plan_windows(T, control), (unsigned)n_problems);
-    if (forecast) {
-        hipLaunchKernelGGL(k_fs_window_fc, gridDim, dim3(kFsWindowThreads), lds, st, a);
-        return hip_ok(hipGetLastError(), "k_fs_window_fc launch");
-    }
     hipLaunchKernelGGL(k_fs_window, gridDim, dim3(kFsWindowThreads), lds, st, a);
     return hip_ok(hipGetLastError(), "k_fs_window launch");
 }
@@ -496,28 +609,35 @@ extern "C" int shems_foresight_solve_forecast_dev(const float *d_tables, int64_t
                            control, d_V, v_doubles, d_argmax, stream);
 }
 
-static int fs_track(const char *fn, bool forecast, const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
-                    const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V, int64_t v_doubles,
-                    double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
+// What the three forward entry points check before any HIP call, in the order the refusals are reported: the view, the grid, T, the
+// buffers, then `check_v(N)` -- the caller's check of the V buffer against its record count (the ensemble's also holds its scenario count
+// and weights, which have this place in the order) --, then results_env.  Fills `a`.
+template <class CheckV>
+static int fs_check_track(const char *fn, int fc, const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
+                          const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V, double *d_results,
+                          int64_t results_env, double *d_returns, float *d_targets, FsTrackArgs &a, CheckV check_v)
 {
     if (int rc = check_view(v, fn)) return rc;
     FsParams g;
     if (int rc = fs_params(grid, fn, g)) return rc;
     if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; the horizon must be at least 1 hour", fn, (int)T);
     if (!d_problems || n_problems < 1 || !d_V) return set_error(SHEMS_ERR_ARG, "%s: NULL buffer or no problem", fn);
-    const int64_t N = (int64_t)g.nb * g.ne;
-    if (v_doubles < (int64_t)n_problems * (T + 1) * N)
-        return set_error(SHEMS_ERR_ARG, "%s: the V buffer holds %lld float64; %d problems x %d planes x %lld nodes need %lld", fn, (long long)v_doubles,
-                         (int)n_problems, (int)T + 1, (long long)N, (long long)n_problems * (T + 1) * N);
+    if (int rc = check_v((int64_t)g.nb * g.ne)) return rc;
     if (results_env >= v->n_envs) return set_error(SHEMS_ERR_ARG, "%s: results_env %lld outside the batch", fn, (long long)results_env);
-    FsTrackArgs a;
     std::memset(&a, 0, sizeof a);
-    a.v = *v; a.prob = d_problems; a.n_prob = n_problems; a.problem_of_env = d_problem_of_env; a.g = g; a.T = T; a.V = d_V;
+    a.v = *v; a.prob = d_problems; a.n_prob = n_problems; a.fc = fc; a.problem_of_env = d_problem_of_env; a.g = g; a.T = T; a.V = d_V;
     a.results = d_results; a.results_env = results_env; a.returns = d_returns; a.targets = d_targets;
-    if (forecast) {
-        hipLaunchKernelGGL(k_fs_track_fc, dim3((unsigned)v->n_envs), dim3(kFsThreads), 0, (hipStream_t)stream, a);
-        return hip_ok(hipGetLastError(), "k_fs_track_fc launch");
-    }
+    return SHEMS_OK;
+}
+
+static int fs_track(const char *fn, bool forecast, const shems_view *v, const shems_foresight_problem *d_problems, int32_t n_problems,
+                    const int32_t *d_problem_of_env, const shems_foresight_grid *grid, int32_t T, const double *d_V, int64_t v_doubles,
+                    double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
+{
+    FsTrackArgs a;
+    if (int rc = fs_check_track(fn, forecast, v, d_problems, n_problems, d_problem_of_env, grid, T, d_V, d_results, results_env, d_returns,
+                                d_targets, a, [&](int64_t N) { return fs_check_v(fn, n_problems, T, N, v_doubles); }))
+        return rc;
     hipLaunchKernelGGL(k_fs_track, dim3((unsigned)v->n_envs), dim3(kFsThreads), 0, (hipStream_t)stream, a);
     return hip_ok(hipGetLastError(), "k_fs_track launch");
 }
@@ -545,33 +665,31 @@ extern "C" int shems_foresight_track_ensemble_dev(const shems_view *v, const she
                                                   double *d_results, int64_t results_env, double *d_returns, float *d_targets, void *stream)
 {
     const char *fn = "shems_foresight_track_ensemble_dev";
-    if (int rc = check_view(v, fn)) return rc;
-    FsParams g;
-    if (int rc = fs_params(grid, fn, g)) return rc;
-    if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; the horizon must be at least 1 hour", fn, (int)T);
-    if (!d_problems || n_problems < 1 || !d_V) return set_error(SHEMS_ERR_ARG, "%s: NULL buffer or no problem", fn);
-    if (n_scen < 1 || n_scen > kFsMaxScen)
-        return set_error(SHEMS_ERR_ARG, "%s: n_scen = %d; an ensemble holds 1 .. %d scenarios", fn, (int)n_scen, kFsMaxScen);
-    if (!weights || !d_weights) return set_error(SHEMS_ERR_ARG, "%s: NULL weight buffer (host weights or their device copy)", fn);
-    for (int32_t p = 0; p < n_problems; ++p)
-        for (int32_t k = 0; k < n_scen; ++k) {
-            const double w = weights[(int64_t)p * n_scen + k];
-            if (!(w > 0.0) || !(w <= 1.7976931348623157e308))                // also a NaN
-                return set_error(SHEMS_ERR_ARG, "%s: problem %d, scenario %d: weight %g; a weight is finite and > 0", fn, (int)p, (int)k, w);
-        }
-    const int64_t N = (int64_t)g.nb * g.ne, recs = (int64_t)n_problems * n_scen;
-    if (v_doubles < recs * (T + 1) * N)
-        return set_error(SHEMS_ERR_ARG, "%s: the V buffer holds %lld float64; %d problems x %d scenarios x %d planes x %lld nodes need %lld", fn,
-                         (long long)v_doubles, (int)n_problems, (int)n_scen, (int)T + 1, (long long)N, (long long)(recs * (T + 1) * N));
-    if (results_env >= v->n_envs) return set_error(SHEMS_ERR_ARG, "%s: results_env %lld outside the batch", fn, (long long)results_env);
+    const int64_t recs = (int64_t)n_problems * n_scen;
+    const auto check_ens = [&](int64_t N) {                                 // the ensemble's own checks
+        if (n_scen < 1 || n_scen > kFsMaxScen)
+            return set_error(SHEMS_ERR_ARG, "%s: n_scen = %d; an ensemble holds 1 .. %d scenarios", fn, (int)n_scen, kFsMaxScen);
+        if (!weights || !d_weights) return set_error(SHEMS_ERR_ARG, "%s: NULL weight buffer (host weights or their device copy)", fn);
+        for (int32_t p = 0; p < n_problems; ++p)
+            for (int32_t k = 0; k < n_scen; ++k) {
+                const double w = weights[(int64_t)p * n_scen + k];
+                if (!(w > 0.0) || !(w <= 1.7976931348623157e308))            // also a NaN
+                    return set_error(SHEMS_ERR_ARG, "%s: problem %d, scenario %d: weight %g; a weight is finite and > 0", fn, (int)p, (int)k, w);
+            }
+        if (v_doubles < recs * (T + 1) * N)
+            return set_error(SHEMS_ERR_ARG, "%s: the V buffer holds %lld float64; %d problems x %d scenarios x %d planes x %lld nodes need %lld", fn,
+                             (long long)v_doubles, (int)n_problems, (int)n_scen, (int)T + 1, (long long)N, (long long)(recs * (T + 1) * N));
+        return (int)SHEMS_OK;
+    };
+    FsTrackEnsArgs a;
+    std::memset(&a, 0, sizeof a);
+    if (int rc = fs_check_track(fn, 1, v, d_problems, n_problems, d_problem_of_env, grid, T, d_V, d_results, results_env, d_returns, d_targets,
+                                a.t, check_ens))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     // the weights the kernel reads: ordered on the stream; the runtime has staged a pageable source on return
     if (int rc = hip_ok(hipMemcpyAsync(d_weights, weights, (size_t)recs * sizeof(double), hipMemcpyHostToDevice, st), "upload of the scenario weights"))
         return rc;
-    FsTrackEnsArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.t.v = *v; a.t.prob = d_problems; a.t.n_prob = n_problems; a.t.problem_of_env = d_problem_of_env; a.t.g = g; a.t.T = T; a.t.V = d_V;
-    a.t.results = d_results; a.t.results_env = results_env; a.t.returns = d_returns; a.t.targets = d_targets;
     a.K = n_scen; a.w = d_weights;
     hipLaunchKernelGGL(k_fs_track_ens, dim3((unsigned)v->n_envs), dim3(kFsThreads), 0, st, a);
     return hip_ok(hipGetLastError(), "k_fs_track_ens launch");

@@ -186,23 +186,37 @@ def append_scenarios(tables, lags=ANALOG_LAGS, columns=("electkwh", "PV_generati
     return out, index
 
 
-def _forecast_offsets(forecast_table, problems, row0, nrow):
-    """forecast_table (one entry per problem: None or the index of a table) -> forecast_off per problem; row0 / nrow: of the tables."""
+def _forecast_offsets(forecast_table, problems, row0, nrow, n_scen=None):
+    """forecast_table (one entry per problem record: None or the index of a table) -> forecast_off per record; row0 / nrow: of the
+    tables.  n_scen: the records are those of an ensemble, n_scen per problem, and a refusal names (problem, scenario); an ensemble also
+    refuses an index that is no integer (a forecast_table entry is truncated)."""
     entries = list(forecast_table)
     if len(entries) != len(problems):
         raise ValueError(f"forecast_table holds {len(entries)} entries for {len(problems)} problems")
     offs = []
-    for p, k in enumerate(entries):
+    for r, k in enumerate(entries):
         if k is None:
             offs.append(0)
             continue
-        k = int(k)
-        if k < 0 or k >= len(row0):
-            raise ValueError(f"problem {p}: forecast table {k} is outside the {len(row0)} tables")
-        if int(nrow[k]) != problems[p].cfg.nrow:
-            raise ValueError(f"problem {p}: forecast table {k} has {int(nrow[k])} rows, its table {problems[p].cfg.nrow}")
-        offs.append(int(row0[k]) - problems[p].cfg.table_row0)
+        i = int(k)
+        if n_scen is None:
+            who, table, shown, ok = f"problem {r}", "forecast table", i, True
+        else:
+            who, table, shown, ok = f"problem {r // n_scen}, scenario {r % n_scen}", "table", repr(k), i == k
+        if not ok or i < 0 or i >= len(row0):
+            raise ValueError(f"{who}: {table} {shown} is outside the {len(row0)} tables")
+        if int(nrow[i]) != problems[r].cfg.nrow:
+            raise ValueError(f"{who}: {table} {i} has {int(nrow[i])} rows, its table {problems[r].cfg.nrow}")
+        offs.append(int(row0[i]) - problems[r].cfg.table_row0)
     return offs
+
+
+def _start_rows(idx0, n_problems):
+    """idx0 (one start row, or one per problem) as a list of n_problems ints."""
+    starts = [int(idx0)] * n_problems if np.isscalar(idx0) else [int(i) for i in idx0]
+    if len(starts) != n_problems:
+        raise ValueError(f"idx0 holds {len(starts)} start rows for {n_problems} problems")
+    return starts
 
 
 def make_problems(configs, idx0, nsteps, grid, total_rows=None):
@@ -216,9 +230,7 @@ def make_problems(configs, idx0, nsteps, grid, total_rows=None):
         raise ValueError("solve needs at least one problem")
     if T < 1:
         raise ValueError(f"nsteps = {T}; the horizon must be at least 1 hour")
-    starts = [int(idx0)] * len(cfgs) if np.isscalar(idx0) else [int(i) for i in idx0]
-    if len(starts) != len(cfgs):
-        raise ValueError(f"idx0 holds {len(starts)} start rows for {len(cfgs)} problems")
+    starts = _start_rows(idx0, len(cfgs))
     recs = (Problem * len(cfgs))()
     for p, (c, i0) in enumerate(zip(cfgs, starts)):
         if c.table_row0 < 0 or c.nrow < 2 or (total_rows is not None and c.table_row0 + c.nrow > total_rows):
@@ -301,7 +313,16 @@ def _check_horizon(T, horizon, control):
     return T, H, c
 
 
-def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, control=None, forecast_table=None):
+def _table_rows(tables):
+    """(row0, nrow) of the tables of a list / one table / a ShemsBatch, without touching a device."""
+    if hasattr(tables, "table_row0"):
+        return [int(x) for x in tables.table_row0], [int(x) for x in tables.table_nrow]
+    tabs = tables if isinstance(tables, (list, tuple)) else [tables]
+    nrow = [int(np.shape(t)[0]) for t in tabs]
+    return [int(x) for x in np.cumsum([0] + nrow)[:-1]], nrow
+
+
+def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, control=None, forecast_table=None, n_scen=None):
     import torch
     from .env import ShemsBatch
     grid = Grid() if grid is None else grid
@@ -314,17 +335,13 @@ def _solve(tables, configs, idx0, nsteps, grid, want_argmax, horizon=None, contr
             if t.ndim != 2 or t.shape[1] != _capi.NCOL:
                 raise ValueError("a table must be [nrow][8] float32")
         rows = np.ascontiguousarray(np.concatenate(tabs, 0))
-        total_rows = rows.shape[0]
-        nrow = [t.shape[0] for t in tabs]
-        row0 = np.cumsum([0] + nrow)[:-1]
-    else:
-        total_rows = int(env.table_row0[-1] + env.table_nrow[-1])
-        row0, nrow = env.table_row0, env.table_nrow
+    row0, nrow = _table_rows(tabs if env is None else env)
+    total_rows = row0[-1] + nrow[-1]
     problems = make_problems(configs, idx0, nsteps, grid, total_rows)
     offs = None
     if forecast_table is not None:
         forecast_table = list(forecast_table)
-        offs = _forecast_offsets(forecast_table, problems, row0, nrow)
+        offs = _forecast_offsets(forecast_table, problems, row0, nrow, n_scen)
         for rec, o in zip(problems, offs):
             rec.forecast_off = o
         if all(k is None for k in forecast_table):
@@ -398,15 +415,6 @@ class EnsembleValues:
         self.grid, self.nsteps, self.horizon, self.control, self.total_rows = values.grid, values.nsteps, values.horizon, values.control, values.total_rows
 
 
-def _table_rows(tables):
-    """(row0, nrow) of the tables of a list / one table / a ShemsBatch, without touching a device."""
-    if hasattr(tables, "table_row0"):
-        return [int(x) for x in tables.table_row0], [int(x) for x in tables.table_nrow]
-    tabs = tables if isinstance(tables, (list, tuple)) else [tables]
-    nrow = [int(np.shape(t)[0]) for t in tabs]
-    return [int(x) for x in np.cumsum([0] + nrow)[:-1]], nrow
-
-
 def ensemble_weights(weights, n_problems, n_scen):
     """[P][K] float64 weights, normalised to sum 1 per problem: None (equal weights), one vector of K for every problem, or [P][K].
     A weight that is <= 0 or not finite, or a length that does not match, is a ValueError."""
@@ -450,55 +458,11 @@ def solve_ensemble(tables, configs, idx0, nsteps, horizon, control=1, scenarios=
     if K < 1 or K > MAX_SCENARIOS:
         raise ValueError(f"{K} scenarios; an ensemble holds 1 .. {MAX_SCENARIOS}")
     w = ensemble_weights(weights, len(cfgs), K)
-    row0, nrow = _table_rows(tables)
-    for p, (c, s) in enumerate(zip(cfgs, scen)):
-        for k, i in enumerate(s):
-            if i is None:
-                continue
-            if int(i) != i or int(i) < 0 or int(i) >= len(row0):
-                raise ValueError(f"problem {p}, scenario {k}: table {i!r} is outside the {len(row0)} tables")
-            if nrow[int(i)] != c.nrow:
-                raise ValueError(f"problem {p}, scenario {k}: table {int(i)} has {nrow[int(i)]} rows, its table {c.nrow}")
-    starts = [int(idx0)] * len(cfgs) if np.isscalar(idx0) else [int(i) for i in idx0]
-    if len(starts) != len(cfgs):
-        raise ValueError(f"idx0 holds {len(starts)} start rows for {len(cfgs)} problems")
-    flat = [None if i is None else int(i) for s in scen for i in s]
-    inner = _solve(tables, [c for c in cfgs for _ in range(K)], [i for i in starts for _ in range(K)], nsteps, grid, False, horizon, control, flat)
+    starts = _start_rows(idx0, len(cfgs))
+    # the records' own refusals (rows, start rows, scenario tables) are make_problems' and _forecast_offsets', before any device work
+    inner = _solve(tables, [c for c in cfgs for _ in range(K)], [i for i in starts for _ in range(K)], nsteps, grid, False, horizon, control,
+                   [i for sc in scen for i in sc], K)
     return EnsembleValues(inner, K, w)
-
-
-def _track_ensemble(env, ens, problem_of_env, which):
-    """track's ensemble branch: shems_foresight_track_ensemble_dev on the inner Values' records and planes."""
-    values = ens.values
-    env_rows = int(env.table_row0[-1] + env.table_nrow[-1])
-    if any(values.forecast_off) and values.total_rows != env_rows:
-        raise ValueError(f"the values were solved on a row array of {values.total_rows} rows and the env holds {env_rows}: a forecast "
-                         "pass needs the env's batch to hold the same tables in the same order")
-    import torch
-    L = _declare(_capi.lib())
-    n, T, P, K = env.n, values.nsteps, ens.n_problems, ens.n_scen
-    env.use_torch_stream()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    poe = None
-    if problem_of_env is not None:
-        po = np.ascontiguousarray(problem_of_env, dtype=np.int32)
-        if po.shape != (n,):
-            raise ValueError("problem_of_env must have shape (n_envs,)")
-        poe = torch.from_numpy(po).to(dev)
-    rows = n if which < 0 else 1
-    res = torch.empty((rows, T, _capi.NRESULT), dtype=torch.float64, device=dev)
-    total = torch.zeros(n, dtype=torch.float64, device=dev)
-    tgt = torch.zeros((n, T, 2), dtype=torch.float32, device=dev)
-    d_w = torch.empty((P, K), dtype=torch.float64, device=dev)              # filled by the call, read by the kernel
-    v = env.view()
-    g = values.grid.struct()
-    _capi.check(L.shems_foresight_track_ensemble_dev(
-        C.byref(v), C.c_void_p(values.d_problems.data_ptr()), P, K, ens.weights.ctypes.data_as(C.c_void_p), C.c_void_p(d_w.data_ptr()),
-        C.c_void_p(poe.data_ptr()) if poe is not None else None, C.byref(g), T, C.c_void_p(values.V.data_ptr()), values.V.numel(),
-        C.c_void_p(res.data_ptr()), int(which), C.c_void_p(total.data_ptr()), C.c_void_p(tgt.data_ptr()), env._stream()))
-    out, tot, targets = res.cpu().numpy(), total.cpu().numpy(), tgt.cpu().numpy()      # the pass's one synchronisation
-    env.check_error()
-    return tot, out, targets
 
 
 def track(env, values, problem_of_env=None, which=-1):
@@ -509,8 +473,9 @@ def track(env, values, problem_of_env=None, which=-1):
     forecast table go through shems_foresight_track_forecast_dev, which reads the ENV's row array: the env's batch must hold the
     same tables in the same order as the solve call saw (a different total row count is a ValueError).  EnsembleValues (solve_ensemble)
     go through shems_foresight_track_ensemble_dev under the same condition; problem_of_env then names the problem, not its records."""
-    if isinstance(values, EnsembleValues):
-        return _track_ensemble(env, values, problem_of_env, which)
+    ens = values if isinstance(values, EnsembleValues) else None
+    if ens is not None:
+        values = ens.values                                  # the one forecast solve: its records and planes
     forecast = any(values.forecast_off)
     if forecast:
         env_rows = int(env.table_row0[-1] + env.table_nrow[-1])
@@ -532,10 +497,15 @@ def track(env, values, problem_of_env=None, which=-1):
     res = torch.empty((rows, T, _capi.NRESULT), dtype=torch.float64, device=dev)
     total = torch.zeros(n, dtype=torch.float64, device=dev)
     tgt = torch.zeros((n, T, 2), dtype=torch.float32, device=dev)
+    if ens is not None:
+        d_w = torch.empty(ens.weights.shape, dtype=torch.float64, device=dev)      # filled by the call, read by the kernel
+        fn, P = L.shems_foresight_track_ensemble_dev, ens.n_problems
+        scen = (ens.n_scen, ens.weights.ctypes.data_as(C.c_void_p), C.c_void_p(d_w.data_ptr()))
+    else:
+        fn, P, scen = L.shems_foresight_track_forecast_dev if forecast else L.shems_foresight_track_dev, values.n_problems, ()
     v = env.view()
     g = values.grid.struct()
-    fn = L.shems_foresight_track_forecast_dev if forecast else L.shems_foresight_track_dev
-    _capi.check(fn(C.byref(v), C.c_void_p(values.d_problems.data_ptr()), values.n_problems,
+    _capi.check(fn(C.byref(v), C.c_void_p(values.d_problems.data_ptr()), P, *scen,
                    C.c_void_p(poe.data_ptr()) if poe is not None else None, C.byref(g), T,
                    C.c_void_p(values.V.data_ptr()), values.V.numel(), C.c_void_p(res.data_ptr()), int(which),
                    C.c_void_p(total.data_ptr()), C.c_void_p(tgt.data_ptr()), env._stream()))

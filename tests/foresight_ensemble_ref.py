@@ -79,16 +79,19 @@ def crafted_planes(which, p):
     return out
 
 
-def controller(which, p, specs, w, V, soc_b, tg=None, res=None, next_from="own"):
+def controller(which, p, specs, w, V, soc_b, tg=None, res=None, next_from="own", actions=None):
     """The ensemble controller of problem p from the start states Soc_b = soc_b [n] on row idx0.  specs: the K scenarios; w: their K
     float64 weights, used as given; V: K arrays [T + 1][N], scenario k's planes.  tg None: the controller runs on its own choices;
     tg [n][T][2]: the trajectory follows those targets instead (a device's), and every choice is what the controller would take from
     the state the trajectory is in; with res [n][T][23] the replayed rewards and rows are compared bitwise.  next_from: "own" (the
     definition: scenario k's candidates are stepped on scenario k's belief), "first" / "last" (every scenario's candidates on the
-    belief of scenario 0 / K - 1: what a kernel that reads one next row for all scenarios would do).
+    belief of scenario 0 / K - 1: what a kernel that reads one next row for all scenarios would do).  actions: (nab, nae) of another
+    action grid than the problem's own.
     Returns a dict: picks [n][T][2] float32, q [n][T][A] float64 (Qbar of every action), totals [n] (the ordered float64 sum of the
     rewards), obs [n][T][9] (the state before each hour), ref (the oracle batch after the pass)."""
     tab, prof, idx0, sh = FR._problem(which, p)
+    if actions is not None:
+        sh = dict(sh, nab=actions[0], nae=actions[1])
     T, K = sh["T"], len(specs)
     assert len(w) == K and len(V) == K
     w = [float(x) for x in w]

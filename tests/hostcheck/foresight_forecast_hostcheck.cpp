@@ -1,6 +1,6 @@
 // foresight_forecast_hostcheck.cpp -- TEST TOOL, not a product path.  A stand-alone program (g++ -ffp-contract=off) that sweeps one
 // problem under the belief of csrc/shems_foresight_core.h -- the plan made at hour j reads the true rows up to j and the forecast
-// table's after it, every row offset taken from fs_belief_off -- with a serial loop that does with fs_q what k_fs_window_fc does on
+// table's after it, every row offset taken from fs_belief_off -- with a serial loop that does with fs_q what k_fs_window does on
 // the GPU, and prints what shems_foresight_solve_forecast_dev would leave, so that a GPU-less container can compare it with the NumPy
 // twin on the composite tables.  The GPU tests (-m gpu) remain the authoritative check.
 //

@@ -34,15 +34,19 @@ def _tabs_s1(specs):
 
 
 _SOLVED = {}
+S1_ACTIONS = (FT.S1["nab"], FT.S1["nae"])
+ACTION_GRIDS = [(5, 3), (9, 9), (17, 17)]    # 15 actions (S1's own); 81: two waves, the second partial; 289: more than the 256 threads
 
 
-def _solve_s1(specs, w, H, c):
-    """EnsembleValues of S1 with the scenario tables behind the truth, solved once per (specs, H, c); the weights are set per call."""
+def _solve_s1(specs, w, H, c, actions=S1_ACTIONS):
+    """EnsembleValues of S1 with the scenario tables behind the truth, on S1's state grid and the action grid `actions` (default: S1's
+    own), solved once per (specs, H, c, actions); the weights are set per call."""
     S, F = U.pkg(), FT.F()
-    if (specs, H, c) not in _SOLVED:
-        _SOLVED[specs, H, c] = F.solve_ensemble(_tabs_s1(specs), FT.configs(S, "s1"), FT.s1()["idx0"], FT.S1["T"], H, c,
-                                                scenarios=[list(range(1, len(specs) + 1))], grid=_grid(F, FT.S1))
-    base = _SOLVED[specs, H, c]
+    key = (specs, H, c, actions)
+    if key not in _SOLVED:
+        _SOLVED[key] = F.solve_ensemble(_tabs_s1(specs), FT.configs(S, "s1"), FT.s1()["idx0"], FT.S1["T"], H, c,
+                                        scenarios=[list(range(1, len(specs) + 1))], grid=_grid(F, dict(FT.S1, nab=actions[0], nae=actions[1])))
+    base = _SOLVED[key]
     return F.EnsembleValues(base.values, len(specs), F.ensemble_weights(w, 1, len(specs)))
 
 
@@ -56,10 +60,10 @@ def _env_s1(S, tabs, soc=None):
     return env
 
 
-def _check_against_numpy(env, totals, res, tg, specs, w, V):
+def _check_against_numpy(env, totals, res, tg, specs, w, V, actions=None):
     """All choices, the rows and rewards replayed through the oracle bitwise, the ordered float64 totals, final state, idx and step."""
     d, T = FT.s1(), FT.S1["T"]
-    run = ER.controller("s1", 0, specs, w, V, _starts(d["prof"]), tg=tg, res=res)
+    run = ER.controller("s1", 0, specs, w, V, _starts(d["prof"]), tg=tg, res=res, actions=actions)
     wrong = np.argwhere((run["picks"] != tg).any(axis=2))
     print(f"K = {len(specs)}, w = {tuple(w)}: {len(wrong)} of {tg.shape[0] * T} choices differ from the NumPy controller; returns {totals}")
     assert len(wrong) == 0, wrong[:10]
@@ -69,22 +73,29 @@ def _check_against_numpy(env, totals, res, tg, specs, w, V):
     return run
 
 
-@pytest.mark.parametrize("H, c", [(6, 1), (6, 4)])
-def test_choices_equal_the_numpy_controller_on_the_oracle(H, c):
-    """S1, six starts, K = 3: persistence of load + PV at lags 3, 6, 9, w = (0.5, 0.25, 0.25)."""
+@pytest.mark.parametrize("H, c, actions", [pytest.param(H, c, a, id=f"{H}-{c}" + ("" if a == S1_ACTIONS else f"-{a[0]}x{a[1]}"))
+                                          for a in ACTION_GRIDS for H, c in [(6, 1), (6, 4)]])     # S1's own grid keeps its ids
+def test_choices_equal_the_numpy_controller_on_the_oracle(H, c, actions):
+    """S1, six starts, K = 3: persistence of load + PV at lags 3, 6, 9, w = (0.5, 0.25, 0.25).
+    The action grid: 5 x 3 is S1's own (less than one wave holds an action; the K planes from the twin).  At 9 x 9 (two waves, the
+    second partial) and 17 x 17 (289 actions on 256 threads: threads 0 .. 32 take two, all four waves contribute) the planes are the
+    device's own forecast solve on that grid (the solve kernels are held to the twin elsewhere); with the EV absent every ae ties, so
+    these grids also hold the first-maximum rule across lanes and across waves."""
     S, F = U.pkg(), FT.F()
     specs = ((3, "lp"), (6, "lp"), (9, "lp"))
-    ens = _solve_s1(specs, W3, H, c)
+    ens = _solve_s1(specs, W3, H, c, actions)
+    g = _grid(F, dict(FT.S1, nab=actions[0], nae=actions[1]))
     assert (ens.n_scen, ens.n_problems, ens.horizon, ens.control) == (3, 1, H, c) and (U.bits64(ens.weights) == U.bits64(np.array([W3]))).all()
     n = FT.s1()["tab"].shape[0]
     assert ens.values.forecast_off == [n, 2 * n, 3 * n] and ens.values.argmax is None and ens.values.V.shape[0] == 3
     env = _env_s1(S, _tabs_s1(specs))
     totals, res, tg = F.track(env, ens, None, which=-1)
     assert res.shape == (6, 30, 23) and tg.shape == (6, 30, 2) and totals.shape == (6,)
-    _check_against_numpy(env, totals, res, tg, specs, W3, [ER.planes("s1", 0, s, H, c) for s in specs])
+    planes = [ER.planes("s1", 0, s, H, c) for s in specs] if actions == S1_ACTIONS else list(ens.values.V.cpu().numpy())
+    _check_against_numpy(env, totals, res, tg, specs, W3, planes, actions)
     assert np.unique(tg.reshape(-1, 2), axis=0).shape[0] > 1
     # the single-forecast lag-6 controller is another one
-    one = F.solve_horizon(_tabs_s1(specs), FT.configs(S, "s1"), FT.s1()["idx0"], 30, H, c, _grid(F, FT.S1), want_argmax=False, forecast_table=[2])
+    one = F.solve_horizon(_tabs_s1(specs), FT.configs(S, "s1"), FT.s1()["idx0"], 30, H, c, g, want_argmax=False, forecast_table=[2])
     o_env = _env_s1(S, _tabs_s1(specs))
     o_tot, _, _ = F.track(o_env, one)
     assert (U.bits64(o_tot) != U.bits64(totals)).any()

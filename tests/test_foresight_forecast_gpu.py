@@ -1,5 +1,5 @@
-"""The receding-horizon foresight controller planning on a forecast, on the GPU (shems_foresight_solve_forecast_dev, k_fs_window_fc;
-shems_foresight_track_forecast_dev, k_fs_track_fc): every stored plane and arg-max against the oracle twin on the composite tables
+"""The receding-horizon foresight controller planning on a forecast, on the GPU (shems_foresight_solve_forecast_dev, k_fs_window with
+fc = 1; shems_foresight_track_forecast_dev, k_fs_track with fc = 1): every stored plane and arg-max against the oracle twin on the composite tables
 (bit for bit), identity with solve_horizon when the forecast is the truth, the existing backward sweep on the composite tables at the
 largest LDS size, the forward pass against a NumPy controller on the oracle, and the host layers on top."""
 import csv
@@ -28,18 +28,28 @@ def _grid(F, shape):
 _SOLVED = {}
 
 
-def _s1(kind, H, c):
+ACTION_GRIDS = [(5, 3), (9, 9), (17, 17)]    # 15 actions (S1's own); 81: two waves, the second partial; 289: more than the 256 threads
+
+
+def _forward_cases(hc):
+    """(H, c) x ACTION_GRIDS as one parameter list; S1's own action grid keeps the ids the cases had before the grid was a parameter."""
+    return [pytest.param(H, c, nab, nae, id=f"{H}-{c}" + ("" if (nab, nae) == ACTION_GRIDS[0] else f"-{nab}x{nae}"))
+            for nab, nae in ACTION_GRIDS for H, c in hc]
+
+
+def _s1(kind, H, c, nab=FT.S1["nab"], nae=FT.S1["nae"]):
     """The device's Values of S1 under (H, c) with the forecast `kind` appended behind the truth (None: solve_horizon on the truth),
-    solved once per process."""
-    if (kind, H, c) not in _SOLVED:
+    on S1's state grid and the action grid nab x nae (default: S1's own), solved once per process."""
+    key = (kind, H, c, nab, nae)
+    if key not in _SOLVED:
         S, F = U.pkg(), FT.F()
         d = FT.s1()
-        cfgs, T, g = FT.configs(S, "s1"), FT.S1["T"], _grid(F, FT.S1)
+        cfgs, T, g = FT.configs(S, "s1"), FT.S1["T"], _grid(F, dict(FT.S1, nab=nab, nae=nae))
         if kind is None:
-            _SOLVED[kind, H, c] = F.solve_horizon([d["tab"]], cfgs, d["idx0"], T, H, c, g)
+            _SOLVED[key] = F.solve_horizon([d["tab"]], cfgs, d["idx0"], T, H, c, g)
         else:
-            _SOLVED[kind, H, c] = F.solve_horizon([d["tab"], FC.forecast("s1", 0, kind)], cfgs, d["idx0"], T, H, c, g, forecast_table=[1])
-    return _SOLVED[kind, H, c]
+            _SOLVED[key] = F.solve_horizon([d["tab"], FC.forecast("s1", 0, kind)], cfgs, d["idx0"], T, H, c, g, forecast_table=[1])
+    return _SOLVED[key]
 
 
 @pytest.mark.parametrize("kind", ["lp", "all"])
@@ -73,7 +83,7 @@ def test_s1_planes_and_argmax_equal_the_twin_on_the_composite_tables(H, c, kind)
 @pytest.mark.parametrize("H, c", [(6, 4), (30, 1)])
 def test_a_forecast_that_is_the_truth_leaves_the_bytes_of_solve_horizon(H, c):
     """forecast_table naming the truth itself (offset 0), a byte copy of the truth behind it, and the copy BEFORE the truth (negative
-    offset): all three run k_fs_window_fc and leave what k_fs_window leaves."""
+    offset): all three run k_fs_window under a forecast (fc = 1) and leave what it leaves on the true rows (fc = 0)."""
     S, F = U.pkg(), FT.F()
     d = FT.s1()
     T, g, n = FT.S1["T"], _grid(F, FT.S1), d["tab"].shape[0]
@@ -121,7 +131,7 @@ def test_s2_four_problems_with_and_without_forecasts_in_one_call():
 
 
 def test_largest_grid_equals_the_backward_sweep_on_the_composite_tables():
-    """129 x 65 nodes: two planes = 134 160 bytes of LDS, which k_fs_window_fc gets only through its own opt-in.  T = 3, H = 2, c = 1,
+    """129 x 65 nodes: two planes = 134 160 bytes of LDS, which k_fs_window gets only through its opt-in.  T = 3, H = 2, c = 1,
     Charger98 eval from row 11 (around an arrival), four-column persistence at lag 2: every plane and arg-max row = row 0 of
     foresight.solve on the composite table of the plan's hour, window by window."""
     S, F = U.pkg(), FT.F()
@@ -156,13 +166,13 @@ def _starts(prof):
     return np.array([0.0, prof.soc_max, np.float32(0.5 * float(prof.soc_max))] + list(draws), np.float32)
 
 
-def _numpy_controller(d, kind, Uplanes, tg, res, next_from):
+def _numpy_controller(d, kind, Uplanes, tg, res, next_from, sh=FT.S1):
     """The choices of a NumPy controller on the oracle along the device's own trajectory (replayed through the oracle with the
     device's targets `tg`, rewards and rows compared bitwise when `res` is given): at hour t, 15 candidate envs per env are stepped
     from the true state on the belief of hour t -- the composite table, whose next row is the forecast's (next_from = "forecast") --
     or on the true table (next_from = "truth"); r + interp(U_{t+1}), first maximum.  Returns (choices [n][T][2], the oracle batch
-    after the pass, the ordered float64 totals)."""
-    sh, T = FT.S1, FT.S1["T"]
+    after the pass, the ordered float64 totals).  sh: the grid (default: S1's own; 15 candidates then)."""
+    T = FT.S1["T"]
     tab, prof = d["tab"], d["prof"]
     soc = _starts(prof)
     n = len(soc)
@@ -204,21 +214,29 @@ def _env_s1(S, kind):
     return env
 
 
-@pytest.mark.parametrize("H, c", [(6, 1), (6, 4)])
-def test_forward_pass_equals_a_numpy_controller_that_steps_its_candidates_on_the_belief(H, c):
+@pytest.mark.parametrize("H, c, nab, nae", _forward_cases([(6, 1), (6, 4)]))
+def test_forward_pass_equals_a_numpy_controller_that_steps_its_candidates_on_the_belief(H, c, nab, nae):
     """foresight.track on the forecast Values, S1, six starts, four-column forecast at lag 6: every choice of every env at every hour,
-    the results rows replayed through the oracle bitwise, the ordered float64 totals, the final state and indices."""
+    the results rows replayed through the oracle bitwise, the ordered float64 totals, the final state and indices.
+    The action grid: 5 x 3 is S1's own (less than one wave holds an action; U from the twin).  At 9 x 9 (two waves, the second
+    partial) and 17 x 17 (289 actions on 256 threads: threads 0 .. 32 take two, all four waves contribute) U is the device's own
+    forecast solve on that grid (the solve kernels are held to the twin elsewhere); with the EV absent every ae ties, so these grids
+    also hold the first-maximum rule across lanes and across waves.  At 17 x 17 also: values solved with a forecast table that is a
+    byte copy of the truth, appended to the batch, track to the bytes of the pass on solve_horizon's values -- one kernel, fc = 1 and
+    fc = 0."""
     S, F = U.pkg(), FT.F()
     d = FT.s1()
-    T = FT.S1["T"]
-    val = _s1("all", H, c)
+    T, sh = FT.S1["T"], dict(FT.S1, nab=nab, nae=nae)
+    own = (nab, nae) == (FT.S1["nab"], FT.S1["nae"])
+    val = _s1("all", H, c, nab, nae)
     env = _env_s1(S, "all")
     n = env.n
     totals, res, tg = F.track(env, val, None, which=-1)
     assert res.shape == (n, T, 23) and tg.shape == (n, T, 2) and totals.shape == (n,)
-    picks, ref, acc = _numpy_controller(d, "all", FC.expected("s1", 0, "all", H, c)[0], tg, res, "forecast")
+    Uplanes = FC.expected("s1", 0, "all", H, c)[0] if own else val.V.cpu().numpy()[0]
+    picks, ref, acc = _numpy_controller(d, "all", Uplanes, tg, res, "forecast", sh)
     wrong = np.argwhere((picks != tg).any(axis=2))
-    print(f"(H, c) = ({H}, {c}): {len(wrong)} of {n * T} choices differ from the NumPy controller; returns {totals}")
+    print(f"(H, c) = ({H}, {c}), {nab} x {nae} actions: {len(wrong)} of {n * T} choices differ from the NumPy controller; returns {totals}")
     assert len(wrong) == 0, wrong[:10]
     assert (U.bits32(env.state) == U.bits32(ref.state())).all()
     assert (env.idx == ref.idx()).all() and (env.step == T).all() and (ref.steps() == T).all()
@@ -226,9 +244,17 @@ def test_forward_pass_equals_a_numpy_controller_that_steps_its_candidates_on_the
     assert np.unique(tg.reshape(-1, 2), axis=0).shape[0] > 1
     # the truth's controller is another one
     t_env = _env_s1(S, "all")
-    t_tot, _, _ = F.track(t_env, _s1(None, H, c))
+    t_tot, t_res, t_tg = F.track(t_env, _s1(None, H, c, nab, nae))
     assert (U.bits64(t_tot) != U.bits64(totals)).any()
     env.close(); t_env.close()
+    if (nab, nae) == (17, 17):
+        c_env = _env_s1(S, "truth")                                          # the batch: the truth and its byte copy behind it
+        c_val = F.solve_horizon([d["tab"], FC.forecast("s1", 0, "truth")], FT.configs(S, "s1"), d["idx0"], T, H, c, _grid(F, sh), forecast_table=[1])
+        assert c_val.forecast_off == [d["tab"].shape[0]]
+        c_tot, c_res, c_tg = F.track(c_env, c_val)
+        assert (U.bits64(c_res) == U.bits64(t_res)).all() and (U.bits32(c_tg) == U.bits32(t_tg)).all()
+        assert (U.bits64(c_tot) == U.bits64(t_tot)).all()
+        c_env.close()
 
 
 def test_forward_pass_takes_the_next_row_from_the_forecast():

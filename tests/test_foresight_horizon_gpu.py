@@ -26,14 +26,25 @@ def _grid(F, shape):
 _SOLVED = {}
 
 
-def _s1(H=None, c=1):
-    """The device's Values of S1 under (H, c) -- H = None: the existing backward sweep --, solved once per process."""
-    if (H, c) not in _SOLVED:
+ACTION_GRIDS = [(5, 3), (9, 9), (17, 17)]    # 15 actions (S1's own); 81: two waves, the second partial; 289: more than the 256 threads
+
+
+def _forward_cases(hc):
+    """(H, c) x ACTION_GRIDS as one parameter list; S1's own action grid keeps the ids the cases had before the grid was a parameter."""
+    return [pytest.param(H, c, nab, nae, id=f"{H}-{c}" + ("" if (nab, nae) == ACTION_GRIDS[0] else f"-{nab}x{nae}"))
+            for nab, nae in ACTION_GRIDS for H, c in hc]
+
+
+def _s1(H=None, c=1, nab=FT.S1["nab"], nae=FT.S1["nae"]):
+    """The device's Values of S1 under (H, c) -- H = None: the existing backward sweep --, on S1's state grid and the action grid
+    nab x nae (default: S1's own), solved once per process."""
+    if (H, c, nab, nae) not in _SOLVED:
         S, F = U.pkg(), FT.F()
         d = FT.s1()
         args = ([d["tab"]], FT.configs(S, "s1"), d["idx0"], FT.S1["T"])
-        _SOLVED[H, c] = F.solve(*args, _grid(F, FT.S1)) if H is None else F.solve_horizon(*args, H, c, _grid(F, FT.S1))
-    return _SOLVED[H, c]
+        g = _grid(F, dict(FT.S1, nab=nab, nae=nae))
+        _SOLVED[H, c, nab, nae] = F.solve(*args, g) if H is None else F.solve_horizon(*args, H, c, g)
+    return _SOLVED[H, c, nab, nae]
 
 
 @pytest.mark.parametrize("H, c", S1_CASES)
@@ -152,19 +163,26 @@ def _starts(prof):
     return np.array([0.0, prof.soc_max, np.float32(0.5 * float(prof.soc_max))] + list(draws), np.float32)
 
 
-@pytest.mark.parametrize("H, c", [(None, 1), (6, 1), (6, 4)])
-def test_forward_pass_equals_a_numpy_receding_horizon_controller_on_the_oracle(H, c):
+@pytest.mark.parametrize("H, c, nab, nae", _forward_cases([(None, 1), (6, 1), (6, 4)]))
+def test_forward_pass_equals_a_numpy_receding_horizon_controller_on_the_oracle(H, c, nab, nae):
     """foresight.track on solve_horizon's Values, S1, six starts.  The results are replayed through the oracle hour by hour (rewards,
     rows, final state, ordered float64 totals), and the target chosen by EVERY env at EVERY hour equals a NumPy controller on the
-    oracle: 15 oracle envs stepped from the env's true state, r + interp(U_{t+1}), first maximum, with U from the twin on the plan's
+    oracle: one oracle env per action (15 on S1's own grid) stepped from the env's true state, r + interp(U_{t+1}), first maximum, with U from the twin on the plan's
     truncated window.  H = None runs the same check on the existing backward sweep's Values (U = the full solve's planes): it passes
-    on the kernels this feature does not touch, which separates a mistake in this test from one in k_fs_window."""
+    on the kernels this feature does not touch, which separates a mistake in this test from one in k_fs_window.
+    The action grid: 5 x 3 is S1's own (less than one wave holds an action).  At 9 x 9 (two waves, the second partial) and 17 x 17
+    (289 actions on 256 threads: threads 0 .. 32 take two, all four waves contribute) U is the device's own solve on that grid (the
+    solve kernels are held to the twin elsewhere); with the EV absent every ae ties, so these grids also hold the first-maximum rule
+    across lanes and across waves."""
     S, F = U.pkg(), FT.F()
     d = FT.s1()
-    T, sh = FT.S1["T"], FT.S1
+    T, sh = FT.S1["T"], dict(FT.S1, nab=nab, nae=nae)
     tab, prof = d["tab"], d["prof"]
-    val = _s1(H, c)
-    Uplanes = d["V"] if H is None else FR.expected("s1", 0, H, c)[0]
+    val = _s1(H, c, nab, nae)
+    if (nab, nae) == (FT.S1["nab"], FT.S1["nae"]):
+        Uplanes = d["V"] if H is None else FR.expected("s1", 0, H, c)[0]
+    else:
+        Uplanes = val.V.cpu().numpy()[0]
     soc = _starts(prof)
     n = len(soc)
     idx = np.full(n, d["idx0"], np.int32)
@@ -193,7 +211,7 @@ def test_forward_pass_equals_a_numpy_receding_horizon_controller_on_the_oracle(H
         assert (U.bits64(r) == U.bits64(res[:, t, 5])).all(), t
         assert (U.bits64(rr) == U.bits64(res[:, t])).all(), t
         acc = acc + r
-    print(f"(H, c) = ({H}, {c}): {len(wrong)} of {n * T} choices differ from the NumPy controller; returns {totals}")
+    print(f"(H, c) = ({H}, {c}), {nab} x {nae} actions: {len(wrong)} of {n * T} choices differ from the NumPy controller; returns {totals}")
     assert not wrong, wrong[:10]
     assert (U.bits32(env.state) == U.bits32(ref.state())).all()
     assert (env.idx == ref.idx()).all() and (env.step == T).all() and (ref.steps() == T).all()

@@ -12,7 +12,7 @@ what is learnt after the first decision, and on a discretised V a wrong forecast
 
 Speed, on the Charger98 test series (2 998 hours), one process, HIP events, one warm-up call, the median of five calls alternated with
 the comparison: the ensemble forward pass (k_fs_track_ens) at K = 1 and K = 7 against foresight.track on forecast values
-(k_fs_track_fc); the solve of 7 records in one call against 7 separate calls.
+(k_fs_track, fc = 1); the solve of 7 records in one call against 7 separate calls.
 
     python tools/foresight_ensemble_demo.py [out.json]    (default profiles/r14_foresight_ensemble.json; needs the GPU, does not read oracle/)
 """

@@ -9,8 +9,8 @@ whole series at the default grid (65 x 33 nodes, 17 x 17 targets):
     (h_countdown and soc_ev too: the controller that knows nothing ahead).
 Nothing about the order of those returns is asserted: a wrong forecast can beat the true one on a discretised V, and does.
 
-Speed, on the Charger98 test series (2 998 hours), one process: the HIP-event time of the forecast solve (k_fs_window_fc) next to
-solve_horizon (k_fs_window) at the same (H, c), each one warm-up call and one timed call.
+Speed, on the Charger98 test series (2 998 hours), one process: the HIP-event time of the forecast solve (k_fs_window, fc = 1) next to
+solve_horizon (k_fs_window, fc = 0) at the same (H, c), each one warm-up call and one timed call.
 
     python tools/foresight_forecast_demo.py [out.json]    (default profiles/r12_foresight_forecast.json; needs the GPU, does not read oracle/)
 """
