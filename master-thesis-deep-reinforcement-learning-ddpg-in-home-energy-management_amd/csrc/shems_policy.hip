@@ -7,7 +7,10 @@
 // which there costs one H2D copy, ~8 tiny kernels at batch 1, one D2H sync and a CSV parse per step.
 //
 // Three kernels share the arithmetic and one CANONICAL COLUMN ORDER (act_col below), so they write the same bytes, and the batch size
-// picks one (dispatch_act):
+// picks one (dispatch_act).  Their MFMA loops are their own (measured, each for its tile and ring); what surrounds the loops exists
+// once, in the block of shared pieces behind act_env_tail: the column order of layer 3 is act_l3_group (a group's sum) + act_finish
+// (b3 + (H0 + H1)), stage 0's clamping rules are the load / store pairs act_obs_*, act_tl_*, act_pre_index and act_row_*, the per-tile
+// reward sum is act_block_reward, and the host launches every form's plain / _hp / _x kernel through ActKernels::launch.  The kernels:
 //   k_act2  > 8 192 envs: 64-env tiles, < 80 KB of LDS and <= 256 registers, so TWO workgroups are resident per CU and one's
 //           latency-bound phases (stage 0, layer 1, layer 3, env tail) run under the other's MFMAs -- the default for large batches;
 //   k_actg  <= 8 192 envs: 32-env tiles, one wave per 64-column group; 8 waves per tile, or two workgroups per tile (<= 4 096 envs)
@@ -357,7 +360,170 @@ __device__ __forceinline__ double act_env_tail(const ActArgs &A, int64_t i, floa
     return reward;
 }
 
-constexpr int kDmaKs = 4;   // the 8 LDS-DMA pieces a wave issues per chunk go out in k-steps 0..3 (two each); the wave waits for
+// =====================================================================================================================
+// What the three bodies (k_act, k_actg, k_act2) share around their MFMA loops: stage 0 as load / store pairs over small register structs
+// (a body issues the loads in its own order and stores when it likes: the pairs impose none), the layer-3 sum of a column group and the
+// finish.  The CANONICAL ORDER of layer 3 and the CLAMPING RULES of stage 0 are defined here and nowhere else.
+
+// (learner, goff, P, s_min, s_max) of the workgroup whose first env is env0: a tile never straddles two learners.
+struct ActWho { int64_t learner, goff; const float *P, *s_min, *s_max; };
+__device__ __forceinline__ ActWho act_who(const ActArgs &A, int64_t env0)
+{
+    const int64_t learner = A.gcount > 1 ? env0 / A.genvs : 0, goff = learner * A.gstride;
+    return ActWho{learner, goff, gsh(A.p.actor, goff), gsh(A.p.s_min, goff), gsh(A.p.s_max, goff)};
+}
+
+// The tile's BM x 9 observations with their s_min / s_max, NT threads.  Addresses are clamped, never predicated -- a guarded load becomes a
+// branch with its own s_waitcnt and serialises the batch; envs past the end of the batch normalise to 0.
+template <int BM, int NT> struct ObsRegs { static constexpr int kIt = (BM * kIn + NT - 1) / NT; float sv[kIt], lo[kIt], hi[kIt]; };
+template <int BM, int NT>
+__device__ __forceinline__ void act_obs_load(const ActArgs &A, const float *s_min, const float *s_max, int64_t env0, int tid, ObsRegs<BM, NT> &R)
+{
+    const int64_t last = A.m * kIn - 1;
+#pragma unroll
+    for (int it = 0; it < R.kIt; ++it) {
+        const int e = min(it * NT + tid, BM * kIn - 1), k = e % kIn;
+        R.sv[it] = A.obs[min(env0 * kIn + e, last)];
+        R.lo[it] = s_min[k];
+        R.hi[it] = s_max[k];
+    }
+}
+// x = normalize(s) -> xT[k][m] (row 9 = 1: the bias input) and, where the body keeps them (RAW), the raw observations -> xR[m][9]
+template <int BM, int NT, bool RAW>
+__device__ __forceinline__ void act_obs_store(const ActArgs &A, int64_t env0, int tid, const ObsRegs<BM, NT> &R, float *xT, float *xR)
+{
+    const int64_t last = A.m * kIn - 1;
+#pragma unroll
+    for (int it = 0; it < R.kIt; ++it) {
+        const int e = it * NT + tid, m = e / kIn, k = e - m * kIn;
+        const float x = (R.sv[it] - R.lo[it]) / ((R.hi[it] - R.lo[it]) + 1e-8f);      // MPS:56
+        if (e < BM * kIn) { xT[k * BM + m] = env0 * kIn + e <= last ? x : 0.0f; if constexpr (RAW) xR[e] = R.sv[it]; }
+    }
+    for (int e = tid; e < BM; e += NT) xT[kIn * BM + e] = 1.0f;
+}
+
+// b2 | W3 | b3 are contiguous in the parameter block (1502 floats): threads 0..255 fetch six each and scatter them into the LDS image
+// tl = b2 [512], W3 [512][2], b3 [2], whose pad rows 500..511 are zero.
+struct TlRegs { float tv[6]; };
+__device__ __forceinline__ void act_tl_load(const float *P, int tid, TlRegs &R)
+{
+#pragma unroll
+    for (int it = 0; it < 6; ++it) R.tv[it] = P[kOffB2 + min(it * 256 + (tid & 255), kH2 + kH2 * kOut + kOut - 1)];
+}
+__device__ __forceinline__ void act_tl_store(int tid, const TlRegs &R, float *tl)
+{
+#pragma unroll
+    for (int it = 0; it < 6; ++it) {
+        const int e = tid < 256 ? it * 256 + tid : 1 << 20;   // source index: [0,500) b2, [500,1500) W3, [1500,1502) b3
+        if (e < kH2) tl[e] = R.tv[it];
+        else if (e < kH2 + kH2 * kOut) tl[kH2P + (e - kH2)] = R.tv[it];
+        else if (e < kH2 + kH2 * kOut + kOut) tl[kH2P + kH2P * kOut + (e - kH2 - kH2 * kOut)] = R.tv[it];
+    }
+    if (tid < kH2P - kH2) tl[kH2 + tid] = 0.0f;                                   // pad rows of b2
+    if (tid < (kH2P - kH2) * kOut) tl[kH2P + kH2 * kOut + tid] = 0.0f;            // pad rows of W3
+}
+
+// TailPre's indices of env min(e, m - 1): idx, step, config index.  Unconditional loads (a predicated one would be sunk into a branch behind
+// an s_waitcnt vmcnt(0)): without a view (actor forward only) the pointers fall back to the parameter block.
+__device__ __forceinline__ void act_pre_index(const ActArgs &A, const float *P, int64_t e, TailPre &tp)
+{
+    const bool view = A.do_step != 0, multi = view && A.v.n_cfg > 1;
+    const int64_t pe = min(e, A.m - 1);
+    const int32_t *pidx = view ? A.v.idx : reinterpret_cast<const int32_t *>(P), *pstep = view ? A.v.step : reinterpret_cast<const int32_t *>(P);
+    const uint16_t *pci = multi ? A.v.cfg_of_env : reinterpret_cast<const uint16_t *>(P);
+    tp.idx = pidx[view ? pe : 0];
+    tp.ci = multi ? (int)pci[pe] : 0;
+    tp.step = pstep[view ? pe : 0];
+}
+// Row idx + 1 (1-based) of the env's table, clamped into the table (env_advance_rows rejects idx + 1 > nrow before it looks at it), and
+// h_countdown of row idx: where they are (act_row_at, hangs off tp.idx / tp.ci), their loads, and their place in the TailPre block.
+struct RowAt { const float *tables; int64_t row; };
+struct RowRegs { f32x4 ra, rb; float h_cur; };
+__device__ __forceinline__ RowAt act_row_at(const ActArgs &A, const float *P, const TailPre &tp)
+{
+    const bool view = A.do_step != 0;
+    const int32_t *pc = view ? reinterpret_cast<const int32_t *>(A.v.cfgs + tp.ci) : reinterpret_cast<const int32_t *>(P);
+    constexpr int o_row0 = offsetof(shems_config, table_row0) / 4, o_nrow = offsetof(shems_config, nrow) / 4;
+    const int32_t row0 = pc[o_row0], nrow = pc[o_nrow];
+    return RowAt{view ? A.v.tables : P, view ? (int64_t)row0 + max(min(tp.idx + 1, nrow), 2) - 1 : 1};
+}
+__device__ __forceinline__ void act_row_load(const RowAt &at, RowRegs &R)
+{
+    const f32x4 *rp = reinterpret_cast<const f32x4 *>(at.tables + at.row * SHEMS_NCOL);
+    R.ra = rp[0]; R.rb = rp[1];                                            // row idx + 1
+    R.h_cur = at.tables[(at.row - 1) * SHEMS_NCOL];                        // h_countdown of row idx
+}
+__device__ __forceinline__ void act_row_store(const RowRegs &R, TailPre &tp)
+{
+    tp.nx = Row{R.ra[0], R.ra[1], R.ra[2], R.ra[3], R.rb[0], R.rb[1], R.rb[2], R.rb[3]};
+    tp.h_cur = R.h_cur;
+}
+
+// Layer 3 of ONE column group in the canonical order (act_col): relu(acc) of the group's two tiles acc[0], acc[1] into one FMA chain per tile
+// and env over a lane's 16 rows, a lane adds the two tile chains, the two lane halves are added, and lane half 0 stores the group sum of env
+// m = TM j + b at dst[m][2].  gbase = the group's first column.  (scalar FMAs: v_pk_fma_f32 on splat operands measured slower, 5 524 ->
+// 5 856 cycles at TM = 4.)  SB: a sched_barrier every SB rows, 0 = none -- the accumulators live in AGPRs, and a barrier keeps the compiler
+// from hoisting every v_accvgpr_read to the top (VGPR pressure).  The reads are the compiler's own, so it pads the MFMA -> read hazard itself
+// (hand-written asm reads also made it shuffle accumulators between AGPRs to satisfy the operand constraints).
+template <int TM, int SB>
+__device__ __forceinline__ void act_l3_group(const f32x16 (*acc)[TM], const float *w3s, int gbase, int li, int lh, float *dst)
+{
+    float u0[TM], u1[TM];                                    // a lane's two tile chains, added
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        float o0[TM], o1[TM];
+#pragma unroll
+        for (int b = 0; b < TM; ++b) { o0[b] = 0.0f; o1[b] = 0.0f; }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (SB > 0 && r % (SB > 0 ? SB : 1) == 0) __builtin_amdgcn_sched_barrier(0);
+            const int n = act_col<2>(gbase, t, (r & 3) + 8 * (r >> 2) + 4 * lh);     // C/D row i of v_mfma_f32_32x32x* -> column n
+            const float2 w3 = *reinterpret_cast<const float2 *>(w3s + 2 * n);       // rows >= 500: zero weights (and finite h)
+#pragma unroll
+            for (int b = 0; b < TM; ++b) {
+                const float h = fmaxf(acc[t][b][r], 0.0f);
+                o0[b] = fmaf(h, w3.x, o0[b]);
+                o1[b] = fmaf(h, w3.y, o1[b]);
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < TM; ++b) {
+            u0[b] = t == 0 ? o0[b] : u0[b] + o0[b];
+            u1[b] = t == 0 ? o1[b] : u1[b] + o1[b];
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < TM; ++b) {
+        const float g0 = u0[b] + __shfl_xor(u0[b], 32, 64), g1 = u1[b] + __shfl_xor(u1[b], 32, 64);   // + the other lane half
+        if (lh == 0) *reinterpret_cast<float2 *>(dst + (TM * li + b) * 2) = make_float2(g0, g1);
+    }
+}
+// The finish for env m, output j: the group sums of a column half in order, H = ((g0 + g1) + g2) + g3 (g: the half's four group-sum
+// blocks [BM][2]), and the output b3 + (H0 + H1).
+__device__ __forceinline__ float act_half_sum(const float *const (&g)[4], int m, int j)
+{
+    return ((g[0][m * 2 + j] + g[1][m * 2 + j]) + g[2][m * 2 + j]) + g[3][m * 2 + j];
+}
+__device__ __forceinline__ float act_out(const float *tl, int j, float h0, float h1) { return tl[kH2P + kH2P * kOut + j] + (h0 + h1); }
+__device__ __forceinline__ void act_finish(const float *tl, const float *const (&lo)[4], const float *const (&hi)[4], int m, float &p0, float &p1)
+{
+    p0 = act_out(tl, 0, act_half_sum(lo, m, 0), act_half_sum(hi, m, 0));
+    p1 = act_out(tl, 1, act_half_sum(lo, m, 1), act_half_sum(hi, m, 1));
+}
+// Per-tile reward sum (one workgroup finished the whole tile) over LDS that is dead by now.  Stamp builds: block_reward is the stamp buffer.
+template <int NW>
+__device__ __forceinline__ void act_block_reward(const ActArgs &A, double reward, float *dead_lds, int64_t tile)
+{
+#ifndef SHEMS_STAMP_ACT
+    if (A.block_reward) {
+        __syncthreads();
+        const double s = block_sum(reward, reinterpret_cast<double *>(dead_lds), NW);
+        if (threadIdx.x == 0) A.block_reward[tile] = s;
+    }
+#endif
+}
+
+constexpr int kDmaKs = 4;  // the 8 LDS-DMA pieces a wave issues per chunk go out in k-steps 0..3 (two each); the wave waits for
                             // them before k-step 6 of the chunk RD - 2 chunks later (ring of 2: the same chunk, two k-steps on)
 // After chunk c the wave needs its chunk c + 1; the LDS-DMA pieces of chunks c + 2 .. c + RD - 1 (8 each, 5 for
 // the short chunk 15) are younger and may stay in flight.
@@ -407,10 +573,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
     int64_t bid = blockIdx.x;
     if (A.gcount > 1 && (gridDim.x & 7) == 0) bid = (int64_t)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const int64_t env0 = A.m0 + bid * BM;
-    const int64_t learner = A.gcount > 1 ? env0 / A.genvs : 0;
-    const int64_t goff = learner * A.gstride;
-    const float *__restrict__ P = gsh(A.p.actor, goff);
-    const float *__restrict__ s_min = gsh(A.p.s_min, goff), *__restrict__ s_max = gsh(A.p.s_max, goff);
+    const auto [learner, goff, P, s_min, s_max] = act_who(A, env0);
 
     // ---- stage 0: x = normalize(s) -> xT[k][m]; layer-1 image, b2/W3/b3 -> LDS (the ring's first RD - 1 chunks follow the first barrier) ----
     // W2 chunk staging, global -> LDS directly (global_load_lds_dwordx4: no staging registers; destination = M0 base + lane*16).
@@ -447,65 +610,30 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
             _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) FREE_PIECE(ch_, q_);                 \
     } while (0)
     // Every global load of the stage is issued before the first value is used (obs + normalisation, layer-1 image, b2|W3|b3):
-    // one exposed latency instead of one per block.  Addresses are clamped, never predicated -- a guarded load becomes a branch with
-    // its own s_waitcnt and serialises the batch.
-    constexpr int kIt = (BM * kIn + NT_ - 1) / NT_;
-    float sv[kIt], lo[kIt], hi[kIt], wv[kW1K], tv[6];
-    const int64_t last = A.m * kIn - 1;
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-        const int e = min(it * NT_ + tid, BM * kIn - 1), k = e % kIn;
-        sv[it] = A.obs[min(env0 * kIn + e, last)];
-        lo[it] = s_min[k];
-        hi[it] = s_max[k];
-    }
+    // one exposed latency instead of one per block (the load / store pairs above).
+    ObsRegs<BM, NT_> xr;
+    TlRegs tr;
+    float wv[kW1K];
+    act_obs_load(A, s_min, s_max, env0, tid, xr);
     {   // w1[j][k]: j < 9 -> W1[j][k], j == 9 -> b1[k]; columns 250..255 zero (thread = column k)
         const int kc = min(tid, kH1 - 1);
 #pragma unroll
         for (int j = 0; j < kW1K; ++j) wv[j] = P[(j == kW1K - 1 ? kIn : min(j, kIn - 1)) * kH1 + kc];
     }
-    // b2 | W3 | b3 are contiguous in the parameter block (1502 floats)
-#pragma unroll
-    for (int it = 0; it < 6; ++it) tv[it] = P[kOffB2 + min(it * 256 + (tid & 255), kH2 + kH2 * kOut + kOut - 1)];
+    act_tl_load(P, tid, tr);
     // Small tiles: what the env tail needs from global memory is fetched now, and its random draws are made while stage 0 waits for
     // its loads (TailPre; at one 32-env tile per workgroup the tail is ~10 % of the kernel and a chain of three dependent global reads).
-    // Every thread does it for env tid % BM (identical values, unconditional LDS stores: a predicated load would be sunk into a branch
-    // behind an s_waitcnt vmcnt(0)); without a view (actor forward only) the pointers fall back to the parameter block.
+    // Every thread does it for env tid % BM (identical values, unconditional LDS stores).
     [[maybe_unused]] TailPre tp;
-    [[maybe_unused]] const float *tp_tables = nullptr;
-    [[maybe_unused]] int64_t tp_row = 0;
-    if constexpr (PRE || PRE2) {
-        const int64_t pe = min(env0 + (tid & (BM - 1)), A.m - 1);
-        const bool view = A.do_step != 0;
-        const int32_t *pidx = view ? A.v.idx : reinterpret_cast<const int32_t *>(P), *pstep = view ? A.v.step : reinterpret_cast<const int32_t *>(P);
-        const uint16_t *pci = view && A.v.n_cfg > 1 ? A.v.cfg_of_env : reinterpret_cast<const uint16_t *>(P);
-        tp.idx = pidx[view ? pe : 0];
-        tp.step = pstep[view ? pe : 0];
-        tp.ci = view && A.v.n_cfg > 1 ? (int)pci[pe] : 0;
-    }
+    [[maybe_unused]] RowAt tp_at = {nullptr, 0};
+    if constexpr (PRE || PRE2) act_pre_index(A, P, env0 + (tid & (BM - 1)), tp);
     if constexpr (PRE) tp.nz = noise_draw(A.p, env0 + (tid & (BM - 1)));
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-        const int e = it * NT_ + tid, m = e / kIn, k = e - m * kIn;
-        const float x = (sv[it] - lo[it]) / ((hi[it] - lo[it]) + 1e-8f);      // MPS:56
-        if (e < BM * kIn) { xT[k * BM + m] = env0 * kIn + e <= last ? x : 0.0f; xR[e] = sv[it]; }
-    }
-    for (int e = tid; e < BM; e += NT_) xT[kIn * BM + e] = 1.0f;                               // row 9 = 1: the bias input
+    act_obs_store<BM, NT_, true>(A, env0, tid, xr, xT, xR);
     if (tid < kW1C) {
 #pragma unroll
         for (int j = 0; j < kW1K; ++j) w1[j * kW1C + tid] = ((j < kIn || j == kW1K - 1) && tid < kH1) ? wv[j] : 0.0f;
     }
-    {
-#pragma unroll
-        for (int it = 0; it < 6; ++it) {
-            const int e = tid < 256 ? it * 256 + tid : 1 << 20;   // source index: [0,500) b2, [500,1500) W3, [1500,1502) b3
-            if (e < kH2) tl[e] = tv[it];
-            else if (e < kH2 + kH2 * kOut) tl[kH2P + (e - kH2)] = tv[it];
-            else if (e < kH2 + kH2 * kOut + kOut) tl[kH2P + kH2P * kOut + (e - kH2 - kH2 * kOut)] = tv[it];
-        }
-        if (tid < kH2P - kH2) tl[kH2 + tid] = 0.0f;                                   // pad rows of b2
-        if (tid < (kH2P - kH2) * kOut) tl[kH2P + kH2 * kOut + tid] = 0.0f;            // pad rows of W3
-    }
+    act_tl_store(tid, tr, tl);
 
     // Layer 1 on the matrix pipe (K = 10 = 5 k-steps): rows [32g, 32g+32) x this workgroup's BM columns into rows (32g) % HR.. of Hc,
     // tile by tile (L1_PHASE below shares them out over the waves).  D layout: row (r&3)+8(r>>2)+4*lh, column lane&31.
@@ -574,15 +702,7 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
             }                                                                                     \
     } while (0)
 
-    if constexpr (PRE || PRE2) {
-        const bool view = A.do_step != 0;
-        const int32_t *pc = view ? reinterpret_cast<const int32_t *>(A.v.cfgs + tp.ci) : reinterpret_cast<const int32_t *>(P);
-        constexpr int o_row0 = offsetof(shems_config, table_row0) / 4, o_nrow = offsetof(shems_config, nrow) / 4;
-        const int32_t row0 = pc[o_row0], nrow = pc[o_nrow];
-        tp_tables = view ? A.v.tables : P;
-        // row idx + 1 (1-based) of the env's table, clamped into the table: env_advance_rows rejects idx + 1 > nrow before it looks at it
-        tp_row = view ? (int64_t)row0 + max(min(tp.idx + 1, nrow), 2) - 1 : 1;
-    }
+    if constexpr (PRE || PRE2) tp_at = act_row_at(A, P, tp);
     // xT, w1 visible.  Only LDS stores are being published: a barrier that does not also drain the W2 pieces in flight (what
     // __syncthreads() would do with its vmcnt(0))
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -652,12 +772,11 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
         }                                                                                         \
     } while (0)
     if constexpr (PRE) {
-        const f32x4 *rp = reinterpret_cast<const f32x4 *>(tp_tables + tp_row * SHEMS_NCOL);
-        const f32x4 ra = rp[0], rb = rp[1];                                    // row idx + 1
-        tp.h_cur = tp_tables[(tp_row - 1) * SHEMS_NCOL];                       // h_countdown of row idx
+        RowRegs rr;
+        act_row_load(tp_at, rr);
         STAGE0_DMA();
         L1_PHASE(0);
-        tp.nx = Row{ra[0], ra[1], ra[2], ra[3], rb[0], rb[1], rb[2], rb[3]};
+        act_row_store(rr, tp);
         tailpre_store(xP + (tid & (BM - 1)) * kPreDw, tp);
     } else L1_PHASE(0);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // h1 only: every wave waits for its own ring below
@@ -754,17 +873,13 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
         // every wave has read the first half of h1 to the end (its last requests were waited for): lay down rows 128..255 over it
         // and restart the operand ring at k-step 64.  The W2 pieces in flight keep flying.
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        [[maybe_unused]] f32x4 ra, rb;
-        if constexpr (PRE2) {
-            const f32x4 *rp = reinterpret_cast<const f32x4 *>(tp_tables + tp_row * SHEMS_NCOL);
-            ra = rp[0]; rb = rp[1];                                                // row idx + 1
-            tp.h_cur = tp_tables[(tp_row - 1) * SHEMS_NCOL];                       // h_countdown of row idx
-        }
+        [[maybe_unused]] RowRegs rr;
+        if constexpr (PRE2) act_row_load(tp_at, rr);
         L1_PHASE(HR / 32);
         if constexpr (PRE2) tp.nz = noise_draw(A.p, env0 + (tid & (BM - 1)));
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if constexpr (PRE2) {                                                      // w1 / xT are dead from here on
-            tp.nx = Row{ra[0], ra[1], ra[2], ra[3], rb[0], rb[1], rb[2], rb[3]};
+            act_row_store(rr, tp);
             tailpre_store(w1 + (tid & (BM - 1)) * kPreDw, tp);
         }
 #pragma unroll
@@ -781,46 +896,11 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
     FREE_CHUNK(15, (kH1 - (kChunks - 1) * kKC) / 2);                       // rows 240..249 only = 5 k-steps
     PSTAMP(10);
 
-    // ---- epilogue: relu(acc + b2), layer 3 in the canonical order: one FMA chain per tile, lane halves, tile pairs -> group sums ----
-    // (scalar FMAs: v_pk_fma_f32 on splat operands measured slower, 5 524 -> 5 856 cycles at TM = 4)
-    const float *w3s = tl + kH2P;
-    // The accumulators live in AGPRs; the sched_barrier every four rows keeps the compiler from hoisting all 64*TM*4
-    // v_accvgpr_reads to the top (VGPR pressure).  The reads are the compiler's own, so it pads the MFMA -> read hazard itself
-    // (hand-written asm reads also made it shuffle accumulators between AGPRs to satisfy the operand constraints).
+    // ---- epilogue: relu(acc + b2), layer 3 of this wave's column groups (act_l3_group).  A sched_barrier every four rows at TM = 4
+    // keeps the W3 LDS reads near their rows (VGPR pressure); small tiles: one per tile, a whole tile's reads in flight ----
 #pragma unroll
-    for (int gl = 0; gl < NA / 2; ++gl) {                        // this wave's column groups
-        float u0[TM], u1[TM];                                    // a lane's two tile chains, added
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int a = 2 * gl + t;
-            float o0[TM], o1[TM];
-#pragma unroll
-            for (int b = 0; b < TM; ++b) { o0[b] = 0.0f; o1[b] = 0.0f; }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if ((r & (TM == 4 ? 3 : 15)) == 0) __builtin_amdgcn_sched_barrier(0);   // TM = 4: keep the W3 LDS reads near their rows (VGPR pressure); small tiles: a whole tile's reads in flight
-                const int n = act_col<NA>(nbase, a, (r & 3) + 8 * (r >> 2) + 4 * lh);   // C/D row i of v_mfma_f32_32x32x* -> column n
-                const float2 w3 = *reinterpret_cast<const float2 *>(w3s + 2 * n);       // rows >= 500: zero weights (and finite h)
-#pragma unroll
-                for (int b = 0; b < TM; ++b) {
-                    const float h = fmaxf(acc[a][b][r], 0.0f);
-                    o0[b] = fmaf(h, w3.x, o0[b]);
-                    o1[b] = fmaf(h, w3.y, o1[b]);
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < TM; ++b) {
-                u0[b] = t == 0 ? o0[b] : u0[b] + o0[b];
-                u1[b] = t == 0 ? o1[b] : u1[b] + o1[b];
-            }
-        }
-        const int g = nbase / 64 + gl;
-#pragma unroll
-        for (int b = 0; b < TM; ++b) {
-            const float g0 = u0[b] + __shfl_xor(u0[b], 32, 64), g1 = u1[b] + __shfl_xor(u1[b], 32, 64);   // + the other lane half
-            if (lh == 0) *reinterpret_cast<float2 *>(RED_OF(g) + (TM * li + b) * 2) = make_float2(g0, g1);
-        }
-    }
+    for (int gl = 0; gl < NA / 2; ++gl)
+        act_l3_group<TM, TM == 4 ? 4 : 16>(acc + 2 * gl, tl + kH2P, nbase + 64 * gl, li, lh, RED_OF(nbase / 64 + gl));
     __syncthreads();
 
     PSTAMP(11);
@@ -828,24 +908,12 @@ __device__ __forceinline__ void k_act_body(const ActArgs &A, const shems_group_h
     double reward = 0.0;
     const int64_t i = env0 + tid;
     if (tid < BM && i < A.m) {
-        float hs[2][2];                                                          // canonical: the two column halves, groups in order
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                hs[hf][j] = ((RED_OF(4 * hf)[tid * 2 + j] + RED_OF(4 * hf + 1)[tid * 2 + j]) + RED_OF(4 * hf + 2)[tid * 2 + j]) + RED_OF(4 * hf + 3)[tid * 2 + j];
-        const float p0 = tl[kH2P + kH2P * kOut + 0] + (hs[0][0] + hs[1][0]), p1 = tl[kH2P + kH2P * kOut + 1] + (hs[0][1] + hs[1][1]);   // b3 + (H0 + H1)
+        float p0, p1;
+        act_finish(tl, {RED_OF(0), RED_OF(1), RED_OF(2), RED_OF(3)}, {RED_OF(4), RED_OF(5), RED_OF(6), RED_OF(7)}, tid, p0, p1);
         reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, PRE ? xP + tid * kPreDw : PRE2 ? w1 + tid * kPreDw : nullptr, hp, gx);
     }
     PSTAMP(12);
-#ifndef SHEMS_STAMP_ACT
-    if (A.block_reward) {
-        __syncthreads();
-        double *red64 = reinterpret_cast<double *>(Wc);     // Wc is dead by now
-        const double s = block_sum(reward, red64, NW);
-        if (tid == 0) A.block_reward[bid] = s;
-    }
-#endif
+    act_block_reward<NW>(A, reward, Wc, bid);                // Wc is dead by now
 }
 template <int TM, int NW, int RD>
 __global__ __launch_bounds__(64 * NW, NW / 4) void k_act(ActArgs A) { k_act_body<TM, NW, RD, 0>(A, nullptr); }
@@ -938,11 +1006,8 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
         else { tile = (int64_t)(T >> 3) * 8 + ((b - full) >> 1); half = (b - full) & 1; }
     }
     const int64_t env0 = A.m0 + tile * BM;
-    const int64_t learner = A.gcount > 1 ? env0 / A.genvs : 0;
-    const int64_t goff = learner * A.gstride;
-    const float *__restrict__ P = gsh(A.p.actor, goff);
-    const float *__restrict__ s_min = gsh(A.p.s_min, goff), *__restrict__ s_max = gsh(A.p.s_max, goff);
-    const int g = half * NW + wave;                          // this wave's column group
+    const auto [learner, goff, P, s_min, s_max] = act_who(A, env0);
+    const int g = half * NW + wave;                         // this wave's column group
     const int nbase = 64 * g;
 
     // ---- stage 0: every global load issued before the first use, addresses clamped, never predicated ------------------------------
@@ -961,25 +1026,10 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
     // asked for first and the row right behind it -- the row then lands during stage 0 instead of holding up the layer-1 phase.
     // One config for the whole batch (the usual case): its table_row0 / nrow come by scalar loads, not behind a per-env config index.
     TailPre tp;
-    const bool view = A.do_step != 0, multi = view && A.v.n_cfg > 1;
-    {
-        const int64_t pe = min(env0 + (tid & (BM - 1)), A.m - 1);
-        const int32_t *pidx = view ? A.v.idx : reinterpret_cast<const int32_t *>(P), *pstep = view ? A.v.step : reinterpret_cast<const int32_t *>(P);
-        const uint16_t *pci = multi ? A.v.cfg_of_env : reinterpret_cast<const uint16_t *>(P);
-        tp.idx = pidx[view ? pe : 0];
-        tp.ci = multi ? (int)pci[pe] : 0;
-        tp.step = pstep[view ? pe : 0];
-    }
-    constexpr int kIt = (BM * kIn + NT_ - 1) / NT_;
-    float sv[kIt], lo[kIt], hi[kIt], tv[6];
-    const int64_t last = A.m * kIn - 1;
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-        const int e = min(it * NT_ + tid, BM * kIn - 1), k = e % kIn;
-        sv[it] = A.obs[min(env0 * kIn + e, last)];
-        lo[it] = s_min[k];
-        hi[it] = s_max[k];
-    }
+    act_pre_index(A, P, env0 + (tid & (BM - 1)), tp);
+    ObsRegs<BM, NT_> xr;
+    TlRegs tr;
+    act_obs_load(A, s_min, s_max, env0, tid, xr);
     // Layer-1 A operands straight from the parameter block (round 4; k_act2 does the same): a wave lays down row groups wave (and
     // wave + 4 when it has two), and lane (li, lh) of a tile of group g multiplies W1[2 s + lh][32 g + li], s = 0..4 (input row 9 = b1)
     // -- ten words per lane, requested here with everything else.  No [10][256] image in LDS: 10 KB less per workgroup, which is what
@@ -998,39 +1048,12 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
             wa_[u][s2] = P[j * kH1 + min(k, kH1 - 1)];
         }
     }
-#pragma unroll
-    for (int it = 0; it < 6; ++it) tv[it] = P[kOffB2 + min(it * 256 + (tid & 255), kH2 + kH2 * kOut + kOut - 1)];
+    act_tl_load(P, tid, tr);
     tp.nz = noise_draw(A.p, env0 + (tid & (BM - 1)));       // Philox + Box-Muller under the loads
-    f32x4 ra, rb;
-    {
-        const int32_t *pc = view ? reinterpret_cast<const int32_t *>(A.v.cfgs + tp.ci) : reinterpret_cast<const int32_t *>(P);
-        constexpr int o_row0 = offsetof(shems_config, table_row0) / 4, o_nrow = offsetof(shems_config, nrow) / 4;
-        const int32_t row0 = pc[o_row0], nrow = pc[o_nrow];
-        const float *tp_tables = view ? A.v.tables : P;
-        // row idx + 1 (1-based) of the env's table, clamped into the table: env_advance_rows rejects idx + 1 > nrow before it looks at it
-        const int64_t tp_row = view ? (int64_t)row0 + max(min(tp.idx + 1, nrow), 2) - 1 : 1;
-        const f32x4 *rp = reinterpret_cast<const f32x4 *>(tp_tables + tp_row * SHEMS_NCOL);
-        ra = rp[0]; rb = rp[1];                                                // row idx + 1
-        tp.h_cur = tp_tables[(tp_row - 1) * SHEMS_NCOL];                       // h_countdown of row idx
-    }
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-        const int e = it * NT_ + tid, m = e / kIn, k = e - m * kIn;
-        const float x = (sv[it] - lo[it]) / ((hi[it] - lo[it]) + 1e-8f);      // MPS:56
-        if (e < BM * kIn) { xT[k * BM + m] = env0 * kIn + e <= last ? x : 0.0f; xR[e] = sv[it]; }
-    }
-    for (int e = tid; e < BM; e += NT_) xT[kIn * BM + e] = 1.0f;                               // row 9 = 1: the bias input
-    {
-#pragma unroll
-        for (int it = 0; it < 6; ++it) {
-            const int e = tid < 256 ? it * 256 + tid : 1 << 20;   // source index: [0,500) b2, [500,1500) W3, [1500,1502) b3
-            if (e < kH2) tl[e] = tv[it];
-            else if (e < kH2 + kH2 * kOut) tl[kH2P + (e - kH2)] = tv[it];
-            else if (e < kH2 + kH2 * kOut + kOut) tl[kH2P + kH2P * kOut + (e - kH2 - kH2 * kOut)] = tv[it];
-        }
-        if (tid < kH2P - kH2) tl[kH2 + tid] = 0.0f;                                   // pad rows of b2
-        if (tid < (kH2P - kH2) * kOut) tl[kH2P + kH2 * kOut + tid] = 0.0f;            // pad rows of W3
-    }
+    RowRegs rr;
+    act_row_load(act_row_at(A, P, tp), rr);
+    act_obs_store<BM, NT_, true>(A, env0, tid, xr, xT, xR);
+    act_tl_store(tid, tr, tl);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");            // xT visible (LDS stores only; the row loads keep flying)
     GSTAMP(1, blockIdx.x == 0);
 #undef L1_A
@@ -1056,7 +1079,7 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
         }
         // the table row has had stage 0's tail and the layer-1 phase to arrive (the compiler's wait for it also covers the ring's
         // first pieces, which it cannot see: they were issued later and the counter retires in order)
-        tp.nx = Row{ra[0], ra[1], ra[2], ra[3], rb[0], rb[1], rb[2], rb[3]};
+        act_row_store(rr, tp);
         tailpre_store(xP + (tid & (BM - 1)) * kPreDw, tp);
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");            // h1 complete; every wave waits for its own ring below
@@ -1136,38 +1159,8 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
 #ifdef SHEMS_STAMP_ACT
     if (lane == 0 && blockIdx.x == 0) reinterpret_cast<unsigned long long *>(A.block_reward)[32 + wave] = __builtin_amdgcn_s_memtime();    // every wave's loop end
 #endif
-    // ---- layer 3 of this group, canonical order (see act_col) ---------------------------------------------------------------------
-    {
-        const float *w3s = tl + kH2P;
-        float u0[TM], u1[TM];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            float o0[TM], o1[TM];
-#pragma unroll
-            for (int b = 0; b < TM; ++b) { o0[b] = 0.0f; o1[b] = 0.0f; }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int n = act_col<2>(nbase, t, (r & 3) + 8 * (r >> 2) + 4 * lh);
-                const float2 w3 = *reinterpret_cast<const float2 *>(w3s + 2 * n);
-#pragma unroll
-                for (int b = 0; b < TM; ++b) {
-                    const float h = fmaxf(acc[t][b][r], 0.0f);
-                    o0[b] = fmaf(h, w3.x, o0[b]);
-                    o1[b] = fmaf(h, w3.y, o1[b]);
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < TM; ++b) {
-                u0[b] = t == 0 ? o0[b] : u0[b] + o0[b];
-                u1[b] = t == 0 ? o1[b] : u1[b] + o1[b];
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < TM; ++b) {
-            const float g0 = u0[b] + __shfl_xor(u0[b], 32, 64), g1 = u1[b] + __shfl_xor(u1[b], 32, 64);
-            if (lh == 0) *reinterpret_cast<float2 *>(red + (g * BM + TM * li + b) * 2) = make_float2(g0, g1);
-        }
-    }
+    // ---- layer 3 of this group, canonical order (act_l3_group) --------------------------------------------------------------------
+    act_l3_group<TM, 0>(acc, tl + kH2P, nbase, li, lh, red + g * (BM * kOut));
     __syncthreads();
     GSTAMP(8, blockIdx.x == 0);
 
@@ -1177,19 +1170,16 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
     bool fin = tid < BM && i < A.m;
     float p0 = 0.0f, p1 = 0.0f;
     if (fin) {
-        // sums of a column half, groups in canonical order (NS = 2: this workgroup holds only its own half's groups)
-        auto half_sum = [&](int hf, int j) {
-            return ((red[((4 * hf) * BM + tid) * 2 + j] + red[((4 * hf + 1) * BM + tid) * 2 + j]) + red[((4 * hf + 2) * BM + tid) * 2 + j]) +
-                   red[((4 * hf + 3) * BM + tid) * 2 + j];
-        };
-        float h00, h01, h10, h11;                                                  // H0 (outputs 0, 1), H1 (outputs 0, 1)
+        // group q's sums (NS = 2: this workgroup holds only its own half's groups)
+        auto red_g = [red](int q) -> const float * { return red + q * (BM * kOut); };
         if constexpr (NS == 1) {
-            h00 = half_sum(0, 0); h01 = half_sum(0, 1); h10 = half_sum(1, 0); h11 = half_sum(1, 1);
+            act_finish(tl, {red_g(0), red_g(1), red_g(2), red_g(3)}, {red_g(4), red_g(5), red_g(6), red_g(7)}, tid, p0, p1);
         } else {
             // The data is the hand-off: ONE 8-byte exchange per env on its slot (agent scope, performed at the memory side, so the two
             // halves meet there whatever XCDs they run on).  Whoever finds the slot empty leaves its sums and is done with this env;
             // whoever finds the other half's sums finishes the env and empties the slot for the next launch.  Nothing is waited for.
-            float m0 = half_sum(half, 0), m1 = half_sum(half, 1);
+            const float *const mine4[4] = {red_g(4 * half), red_g(4 * half + 1), red_g(4 * half + 2), red_g(4 * half + 3)};
+            float m0 = act_half_sum(mine4, tid, 0), m1 = act_half_sum(mine4, tid, 1);
             unsigned long long mine = ((unsigned long long)__float_as_uint(m1) << 32) | __float_as_uint(m0);
             if (mine == kSplitEmpty) { mine = 0x7FC000007FC00000ull; m0 = m1 = __uint_as_float(0x7FC00000u); }   // a NaN pair never takes the empty pattern
             unsigned long long *slot = X.slot + tile * BM + tid;
@@ -1197,24 +1187,15 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
             if (got == kSplitEmpty) fin = false;
             else __hip_atomic_store(slot, kSplitEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const float o0 = __uint_as_float((uint32_t)got), o1 = __uint_as_float((uint32_t)(got >> 32));
-            h00 = half == 0 ? m0 : o0; h01 = half == 0 ? m1 : o1;
-            h10 = half == 0 ? o0 : m0; h11 = half == 0 ? o1 : m1;
+            p0 = act_out(tl, 0, half == 0 ? m0 : o0, half == 0 ? o0 : m0);        // b3 + (H0 + H1), whichever half this is
+            p1 = act_out(tl, 1, half == 0 ? m1 : o1, half == 0 ? o1 : m1);
         }
-        p0 = tl[kH2P + kH2P * kOut + 0] + (h00 + h10);                              // b3 + (H0 + H1)
-        p1 = tl[kH2P + kH2P * kOut + 1] + (h01 + h11);
     }
     GSTAMP(9, blockIdx.x == 0);
     GSTAMP(11, tile == 0 && fin);
     if (fin) reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, A.obs == A.v.obs ? xR + tid * kIn : nullptr, xP + tid * kPreDw, hp, gx);
     GSTAMP(12, tile == 0 && fin);
-#ifndef SHEMS_STAMP_ACT
-    if (NS == 1 && A.block_reward) {
-        __syncthreads();
-        double *red64 = reinterpret_cast<double *>(Wc);     // the rings are dead by now
-        const double s = block_sum(reward, red64, NW);
-        if (tid == 0) A.block_reward[tile] = s;
-    }
-#endif
+    if constexpr (NS == 1) act_block_reward<NW>(A, reward, Wc, tile);         // the rings are dead by now
 }
 template <int TM, int NW, int NS, int RD>
 __global__ __launch_bounds__(64 * NW) void k_actg(ActArgs A, ActSplit X) { k_actg_body<TM, NW, NS, RD, 0>(A, X, nullptr); }
@@ -1266,11 +1247,8 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
     int64_t bid = blockIdx.x;
     if (A.gcount > 1 && (gridDim.x & 7) == 0) bid = (int64_t)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);     // a learner's tiles share an XCD
     const int64_t env0 = A.m0 + bid * BM;
-    const int64_t learner = A.gcount > 1 ? env0 / A.genvs : 0;
-    const int64_t goff = learner * A.gstride;
-    const float *__restrict__ P = gsh(A.p.actor, goff);
-    const float *__restrict__ s_min = gsh(A.p.s_min, goff), *__restrict__ s_max = gsh(A.p.s_max, goff);
-    const int nbase = 128 * wave;                            // this wave's two column groups
+    const auto [learner, goff, P, s_min, s_max] = act_who(A, env0);
+    const int nbase = 128 * wave;                           // this wave's two column groups
 
     // ---- stage 0 --------------------------------------------------------------------------------------------------------------
     const char *W2g = reinterpret_cast<const char *>(P + kOffW2);
@@ -1282,27 +1260,11 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
     for (int q = 0; q < 2; ++q) wvoff[q] = (uint32_t)((lane >> 5) * (kH2 * 4) + (lane & 31) * 16 + q * (2 * kH2 * 4) - (q - 1) * 1024);
 #define K2_PIECE(chunk, q) k2_piece(wsbase + (size_t)(chunk) * (k2CR * kH2 * 4), wvoff[q], ring_lds + ((chunk) % k2RD) * (k2CF * 4), (q))
     TailPre tp;
-    const bool view = A.do_step != 0, multi = view && A.v.n_cfg > 1;
-    {
-        const int64_t pe = min(env0 + (tid & (BM - 1)), A.m - 1);
-        const int32_t *pidx = view ? A.v.idx : reinterpret_cast<const int32_t *>(P), *pstep = view ? A.v.step : reinterpret_cast<const int32_t *>(P);
-        const uint16_t *pci = multi ? A.v.cfg_of_env : reinterpret_cast<const uint16_t *>(P);
-        tp.idx = pidx[view ? pe : 0];
-        tp.ci = multi ? (int)pci[pe] : 0;
-        tp.step = pstep[view ? pe : 0];
-    }
-    constexpr int kIt = (BM * kIn + NT_ - 1) / NT_;          // 3
-    float sv[kIt], lo[kIt], hi[kIt], tv[6];
-    const int64_t last = A.m * kIn - 1;
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-        const int e = min(it * NT_ + tid, BM * kIn - 1), k = e % kIn;
-        sv[it] = A.obs[min(env0 * kIn + e, last)];
-        lo[it] = s_min[k];
-        hi[it] = s_max[k];
-    }
-#pragma unroll
-    for (int it = 0; it < 6; ++it) tv[it] = P[kOffB2 + min(it * 256 + tid, kH2 + kH2 * kOut + kOut - 1)];
+    act_pre_index(A, P, env0 + (tid & (BM - 1)), tp);
+    ObsRegs<BM, NT_> xr;
+    TlRegs tr;
+    act_obs_load(A, s_min, s_max, env0, tid, xr);
+    act_tl_load(P, tid, tr);
     // layer-1 weights of this wave's two tiles of the FIRST half, straight from the parameter block: tile t = wave + 4 u (u = 0, 1) of the
     // 8 (row group, env tile) pairs; W1[j][k] and b1[k] are contiguous (row 9 of the "image" is b1), columns >= 250 are zero
 #define K2_L1_LOAD(gbase, a0_, a1_, kA_, kB_)                                                     \
@@ -1316,35 +1278,10 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
     float wa0[kW1K / 2], wb0[kW1K / 2];
     K2_L1_LOAD(0, wa0, wb0, kA0, kB0)
     tp.nz = noise_draw(A.p, env0 + (tid & (BM - 1)));
-    f32x4 ra, rb;
-    {
-        const int32_t *pc = view ? reinterpret_cast<const int32_t *>(A.v.cfgs + tp.ci) : reinterpret_cast<const int32_t *>(P);
-        constexpr int o_row0 = offsetof(shems_config, table_row0) / 4, o_nrow = offsetof(shems_config, nrow) / 4;
-        const int32_t row0 = pc[o_row0], nrow = pc[o_nrow];
-        const float *tp_tables = view ? A.v.tables : P;
-        const int64_t tp_row = view ? (int64_t)row0 + max(min(tp.idx + 1, nrow), 2) - 1 : 1;
-        const f32x4 *rp = reinterpret_cast<const f32x4 *>(tp_tables + tp_row * SHEMS_NCOL);
-        ra = rp[0]; rb = rp[1];
-        tp.h_cur = tp_tables[(tp_row - 1) * SHEMS_NCOL];
-    }
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-        const int e = it * NT_ + tid, m = e / kIn, k = e - m * kIn;
-        const float x = (sv[it] - lo[it]) / ((hi[it] - lo[it]) + 1e-8f);      // MPS:56
-        if (e < BM * kIn) xT[k * BM + m] = env0 * kIn + e <= last ? x : 0.0f;
-    }
-    if (tid < BM) xT[kIn * BM + tid] = 1.0f;                                                   // row 9 = 1: the bias input
-    {
-#pragma unroll
-        for (int it = 0; it < 6; ++it) {
-            const int e = it * 256 + tid;                        // source index: [0,500) b2, [500,1500) W3, [1500,1502) b3
-            if (e < kH2) tl[e] = tv[it];
-            else if (e < kH2 + kH2 * kOut) tl[kH2P + (e - kH2)] = tv[it];
-            else if (e < kH2 + kH2 * kOut + kOut) tl[kH2P + kH2P * kOut + (e - kH2 - kH2 * kOut)] = tv[it];
-        }
-        if (tid < kH2P - kH2) tl[kH2 + tid] = 0.0f;
-        if (tid < (kH2P - kH2) * kOut) tl[kH2P + kH2 * kOut + tid] = 0.0f;
-    }
+    RowRegs rr;
+    act_row_load(act_row_at(A, P, tp), rr);
+    act_obs_store<BM, NT_, false>(A, env0, tid, xr, xT, nullptr);                            // no raw copy: the tail reads its observations from global memory
+    act_tl_store(tid, tr, tl);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");            // xT visible
     // the ring's first three chunks
 #pragma unroll
@@ -1395,7 +1332,7 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
         const int kA1 = 128 + kA0, kB1 = 128 + kB0;
         K2_L1_LOAD(4, wa1, wb1, kA1, kB1)
     }
-    tp.nx = Row{ra[0], ra[1], ra[2], ra[3], rb[0], rb[1], rb[2], rb[3]};
+    act_row_store(rr, tp);
     tailpre_store(xP + (tid & (BM - 1)) * kPreDw, tp);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");            // first half of h1 complete
 
@@ -1465,88 +1402,62 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
     K2_K16(64); K2_K16(80); K2_K16(96); K2_K4(112); K2_K4(116); K2_K4(120); K2_KSTEP(124);
 
     // ---- layer 3, canonical order; the group sums go to the start of this wave's own (dead) ring ---------------------------------
-    const float *w3s = tl + kH2P;
 #pragma unroll
-    for (int gl = 0; gl < 2; ++gl) {
-        float u0[TM], u1[TM];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int a = 2 * gl + t;
-            float o0[TM], o1[TM];
-#pragma unroll
-            for (int b = 0; b < TM; ++b) { o0[b] = 0.0f; o1[b] = 0.0f; }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int n = act_col<NA>(nbase, a, (r & 3) + 8 * (r >> 2) + 4 * lh);
-                const float2 w3 = *reinterpret_cast<const float2 *>(w3s + 2 * n);
-#pragma unroll
-                for (int b = 0; b < TM; ++b) {
-                    const float h = fmaxf(acc[a][b][r], 0.0f);
-                    o0[b] = fmaf(h, w3.x, o0[b]);
-                    o1[b] = fmaf(h, w3.y, o1[b]);
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < TM; ++b) {
-                u0[b] = t == 0 ? o0[b] : u0[b] + o0[b];
-                u1[b] = t == 0 ? o1[b] : u1[b] + o1[b];
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < TM; ++b) {
-            const float g0 = u0[b] + __shfl_xor(u0[b], 32, 64), g1 = u1[b] + __shfl_xor(u1[b], 32, 64);
-            if (lh == 0) *reinterpret_cast<float2 *>(Wf + gl * (BM * kOut) + (TM * li + b) * 2) = make_float2(g0, g1);
-        }
-    }
+    for (int gl = 0; gl < 2; ++gl) act_l3_group<TM, 0>(acc + 2 * gl, tl + kH2P, nbase + 64 * gl, li, lh, Wf + gl * (BM * kOut));
     __syncthreads();
     double reward = 0.0;
     const int64_t i = env0 + tid;
     if (tid < BM && i < A.m) {
-        float hs[2][2];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                // group g = 4 hf + q lives in wave g / 2's ring, slot g % 2
-                const float *r0 = Wc + (2 * hf) * (k2RD * k2CF), *r1 = Wc + (2 * hf + 1) * (k2RD * k2CF);
-                hs[hf][j] = ((r0[tid * 2 + j] + r0[BM * kOut + tid * 2 + j]) + r1[tid * 2 + j]) + r1[BM * kOut + tid * 2 + j];
-            }
-        const float p0 = tl[kH2P + kH2P * kOut + 0] + (hs[0][0] + hs[1][0]), p1 = tl[kH2P + kH2P * kOut + 1] + (hs[0][1] + hs[1][1]);
+        // group g lives in wave g / 2's ring, slot g % 2
+        auto red_g = [Wc](int g) -> const float * { return Wc + (g >> 1) * (k2RD * k2CF) + (g & 1) * (BM * kOut); };
+        float p0, p1;
+        act_finish(tl, {red_g(0), red_g(1), red_g(2), red_g(3)}, {red_g(4), red_g(5), red_g(6), red_g(7)}, tid, p0, p1);
         reward = act_env_tail<HP>(A, i, p0, p1, learner, goff, nullptr, xP + tid * kPreDw, hp, gx);
     }
-#ifndef SHEMS_STAMP_ACT
-    if (A.block_reward) {
-        __syncthreads();
-        double *red64 = reinterpret_cast<double *>(Hc);      // h1 is dead by now
-        const double s = block_sum(reward, red64, 4);
-        if (tid == 0) A.block_reward[bid] = s;
-    }
-#endif
+    act_block_reward<4>(A, reward, Hc, bid);                 // h1 is dead by now
 }
 __global__ __launch_bounds__(256, 2) void k_act2(ActArgs A) { k_act2_body<0>(A, nullptr); }
 __global__ __launch_bounds__(256, 2) void k_act2_hp(ActArgs A, const shems_group_hparams *hp) { k_act2_body<1>(A, hp); }
 __global__ __launch_bounds__(256, 2) void k_act2_x(ActArgs A, const shems_group_hparams *hp, GroupX gx) { k_act2_body<2>(A, hp, gx); }
 
-// hp != null (shems_act_step_group_dev with d_hp): the *_hp kernel of the same form; gx != null (shems_act_step_group_x_dev): its *_x kernel
+// One form's three kernels and their LDS opt-in state (per kernel and device: see lds_optin).  launch() runs the plain kernel, or with
+// hp != null (shems_act_step_group_dev with d_hp) the *_hp kernel, or with gx != null (shems_act_step_group_x_dev) the *_x kernel, after
+// the leading arguments `lead` (ActArgs; k_actg: ActArgs, ActSplit).
+template <class... Lead>
+struct ActKernels {
+    typedef void (*Plain)(Lead...);
+    typedef void (*WithHp)(Lead..., const shems_group_hparams *);
+    typedef void (*WithX)(Lead..., const shems_group_hparams *, GroupX);
+    Plain plain; WithHp with_hp; WithX with_x;
+    std::atomic<uint64_t> optin[3];
+    char what_attr[3][48], what_launch[3][32];               // "hipFuncSetAttribute(k_act2_hp)", "k_act2_hp launch"
+
+    ActKernels(const char *name, Plain k, WithHp k_hp, WithX k_x) : plain(k), with_hp(k_hp), with_x(k_x), optin{}
+    {
+        static const char *const suffix[3] = {"", "_hp", "_x"};
+        for (int v = 0; v < 3; ++v) {
+            snprintf(what_attr[v], sizeof what_attr[v], "hipFuncSetAttribute(%s%s)", name, suffix[v]);
+            snprintf(what_launch[v], sizeof what_launch[v], "%s%s launch", name, suffix[v]);
+        }
+    }
+    int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const shems_group_hparams *hp, const GroupX *gx, const Lead &...lead)
+    {
+        const int v = gx ? 2 : hp ? 1 : 0;
+        const void *fn = v == 2 ? reinterpret_cast<const void *>(with_x) : v == 1 ? reinterpret_cast<const void *>(with_hp) : reinterpret_cast<const void *>(plain);
+        if (int rc = lds_optin(optin[v], fn, (int)lds, what_attr[v])) return rc;
+        if (v == 2) hipLaunchKernelGGL(with_x, grid, block, lds, st, lead..., hp, *gx);
+        else if (v == 1) hipLaunchKernelGGL(with_hp, grid, block, lds, st, lead..., hp);
+        else hipLaunchKernelGGL(plain, grid, block, lds, st, lead...);
+        return hip_ok(hipGetLastError(), what_launch[v]);
+    }
+};
+
 static int launch_act2(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr, const GroupX *gx = nullptr)
 {
     constexpr size_t lds = act2_lds_bytes();
     static_assert(lds <= 80 * 1024, "k_act2: two workgroups must fit a CU's 160 KB");
-    static std::atomic<uint64_t> optin{0}, optin_hp{0}, optin_x{0};
-    const dim3 grid((unsigned)((a.m - a.m0 + 63) / 64));
-    if (gx) {
-        if (int rc = lds_optin(optin_x, reinterpret_cast<const void *>(&k_act2_x), (int)lds, "hipFuncSetAttribute(k_act2_x)")) return rc;
-        hipLaunchKernelGGL(k_act2_x, grid, dim3(256), lds, st, a, hp, *gx);
-        return hip_ok(hipGetLastError(), "k_act2_x launch");
-    }
-    if (hp) {
-        if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_act2_hp), (int)lds, "hipFuncSetAttribute(k_act2_hp)")) return rc;
-        hipLaunchKernelGGL(k_act2_hp, grid, dim3(256), lds, st, a, hp);
-        return hip_ok(hipGetLastError(), "k_act2_hp launch");
-    }
-    if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_act2), (int)lds, "hipFuncSetAttribute(k_act2)")) return rc;
-    hipLaunchKernelGGL(k_act2, grid, dim3(256), lds, st, a);
-    return hip_ok(hipGetLastError(), "k_act2 launch");
+    static ActKernels<ActArgs> form("k_act2", k_act2, k_act2_hp, k_act2_x);
+    return form.launch(dim3((unsigned)((a.m - a.m0 + 63) / 64)), dim3(256), lds, st, hp, gx, a);
 }
 
 // BM: as large as keeps >= 2 workgroups per CU's worth of tiles (256 CUs); smaller batches use smaller tiles.
@@ -1562,23 +1473,10 @@ template <int TM, int NW, int RD>
 static int launch_act(const ActArgs &a, hipStream_t st, const shems_group_hparams *hp = nullptr, const GroupX *gx = nullptr)
 {
     constexpr int BM = 32 * TM;
-    const size_t lds = act_lds_bytes<TM, NW, RD>();
-    static_assert(act_lds_bytes<TM, NW, RD>() <= 160 * 1024, "k_act: LDS image exceeds 160 KB");
-    static std::atomic<uint64_t> optin{0}, optin_hp{0}, optin_x{0};      // per device: see lds_optin
-    const unsigned grid = (unsigned)((a.m - a.m0 + BM - 1) / BM);
-    if (gx) {
-        if (int rc = lds_optin(optin_x, reinterpret_cast<const void *>(&k_act_x<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act_x)")) return rc;
-        hipLaunchKernelGGL((k_act_x<TM, NW, RD>), dim3(grid), dim3(64 * NW), lds, st, a, hp, *gx);
-        return hip_ok(hipGetLastError(), "k_act_x launch");
-    }
-    if (hp) {
-        if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_act_hp<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act_hp)")) return rc;
-        hipLaunchKernelGGL((k_act_hp<TM, NW, RD>), dim3(grid), dim3(64 * NW), lds, st, a, hp);
-        return hip_ok(hipGetLastError(), "k_act_hp launch");
-    }
-    if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_act<TM, NW, RD>), (int)lds, "hipFuncSetAttribute(k_act)")) return rc;
-    hipLaunchKernelGGL((k_act<TM, NW, RD>), dim3(grid), dim3(64 * NW), lds, st, a);
-    return hip_ok(hipGetLastError(), "k_act launch");
+    constexpr size_t lds = act_lds_bytes<TM, NW, RD>();
+    static_assert(lds <= 160 * 1024, "k_act: LDS image exceeds 160 KB");
+    static ActKernels<ActArgs> form("k_act", k_act<TM, NW, RD>, k_act_hp<TM, NW, RD>, k_act_x<TM, NW, RD>);
+    return form.launch(dim3((unsigned)((a.m - a.m0 + BM - 1) / BM)), dim3(64 * NW), lds, st, hp, gx, a);
 }
 
 // Exchange slots of the column-split form, one slab per (device, stream): two streams may run the kernel at once and must not share
@@ -1618,12 +1516,7 @@ static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hpara
     constexpr int BM = 32 * TM;
     constexpr size_t lds = actg_lds_bytes<TM, NW, RD>();
     static_assert(lds <= 160 * 1024, "k_actg: LDS image exceeds 160 KB");
-    static std::atomic<uint64_t> optin{0}, optin_hp{0}, optin_x{0};      // per device: see lds_optin
-    if (gx) {
-        if (int rc = lds_optin(optin_x, reinterpret_cast<const void *>(&k_actg_x<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg_x)")) return rc;
-    } else if (hp) {
-        if (int rc = lds_optin(optin_hp, reinterpret_cast<const void *>(&k_actg_hp<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg_hp)")) return rc;
-    } else if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_actg<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg)")) return rc;
+    static ActKernels<ActArgs, ActSplit> form("k_actg", k_actg<TM, NW, NS, RD>, k_actg_hp<TM, NW, NS, RD>, k_actg_x<TM, NW, NS, RD>);
     const int64_t tiles = (a.m - a.m0 + BM - 1) / BM;
     ActSplit x = {nullptr};
     if constexpr (NS == 2) {
@@ -1634,16 +1527,7 @@ static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hpara
             return launch_actg<1, 8, 1, RD>(a, st, hp, gx);
         }
     }
-    if (gx) {
-        hipLaunchKernelGGL((k_actg_x<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x, hp, *gx);
-        return hip_ok(hipGetLastError(), "k_actg_x launch");
-    }
-    if (hp) {
-        hipLaunchKernelGGL((k_actg_hp<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x, hp);
-        return hip_ok(hipGetLastError(), "k_actg_hp launch");
-    }
-    hipLaunchKernelGGL((k_actg<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x);
-    return hip_ok(hipGetLastError(), "k_actg launch");
+    return form.launch(dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, hp, gx, a, x);
 }
 
 // Which form runs a launch of m envs.  SHEMS_ACT_FORM (read once per process) exists for the all-forms test and for A/B runs: every
