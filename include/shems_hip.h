@@ -328,6 +328,16 @@ int shems_ddpg_actor_apply(const shems_ddpg *d, double eta, double bp1, double b
  * vector step reads while this stream already works on the next update). */
 int shems_ddpg_actor_apply_pub(const shems_ddpg *d, double eta, double bp1, double bp2, double grad_scale,
                                float *d_publish, void *stream);
+/* One SUPERVISED update of the actor on demonstrations (behaviour cloning; the reference has no such step):
+ *   loss = Flux.mse(actor(normalize(s)), a_demo), the mean over the 2 * batch elements,
+ * on a minibatch the ordinary sampler draws from `ring` (shems_ddpg_sample_indices predicts the slots), of which only s and a are
+ * read.  Three dependent launches (csrc/shems_ddpg.hip): the actor's forward pass with the gather, the actor's two E products, and
+ * the actor's gradient launch with the cloning head, d3[o][m] = (a_pi - a_demo) (1 - a_pi^2) / batch; ADAM and the soft update of
+ * actor_t ride in the gradient launch as in shems_ddpg_update (tau = 1 keeps actor_t equal to actor: 1 p + 0 t).  grad_actor
+ * receives the complete gradient and losses[1] the loss; the critic, its target, its moments, grad_critic and losses[0] are not
+ * touched.  Arguments and validation as shems_ddpg_update's for the actor. */
+int shems_ddpg_clone_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                            double eta, double bp1, double bp2, float *d_publish, void *stream);
 /* The minibatch indices of (seed, tick): host helper for tests (same Philox as the device). */
 int shems_ddpg_sample_indices(uint64_t seed, uint32_t tick, int32_t batch, int64_t ring_len, int64_t *out);
 /* ------------------------------------------ data-parallel replicas -- */
@@ -764,6 +774,23 @@ int shems_foresight_audit_dev(const float *d_tables, int64_t total_rows, const s
                               const shems_foresight_grid *grid, int32_t T, const double *d_V, int64_t v_doubles, const double *d_results,
                               int32_t n_pass, const int32_t *d_problem_of_pass, double *d_out, int32_t *d_best_action, int32_t *d_status,
                               void *stream);
+/* Demonstrations from tracked passes: the 23-column rows (LU1:476-478; MPS:62-89) of ANY pass plus a label per hour become
+ * (observation, action) pairs in a replay ring, for the supervised update of the actor (shems_ddpg_clone_update).  The definition --
+ * fs_demo_hour: the audit's row check and state, observations 6 .. 8 from table row idx as reset! / next_state! leave them
+ * (LU1:264-281), the label a = (float)(2.0 * (double)target - 1.0) -- is in csrc/shems_foresight_core.h.
+ * d_tables / total_rows / d_problems / n_problems / grid / T / d_results / n_pass / d_problem_of_pass: as shems_foresight_audit_dev
+ * takes them (no V is read).  Exactly one label source: d_targets [n_pass][T][2] float32 in [0, 1], as shems_foresight_track_dev
+ * writes them, or d_best_action [n_pass][T] int32 action indices, as the audit writes them (the labels at the states ANOTHER
+ * controller visited).  Pass e, hour t goes to slot (pos + e * T + t) mod ring->capacity; only s and a of that slot are written,
+ * r, s2 and done are not touched.  An hour whose row check fails or whose index label is not an action of the grid (the audit's
+ * -1) leaves its slot untouched and sets d_status[e] = SHEMS_ERR_INDEX; the other hours are written.  d_status [n_pass] int32 is
+ * zeroed on `stream`, then ONE launch (k_fs_demos, a thread per hour); no host synchronisation.  SHEMS_ERR_ARG, nothing launched:
+ * what the audit refuses of the grid, T and n_pass, a NULL where a buffer is required, both label sources or neither,
+ * n_pass * T > capacity, pos outside 0 .. capacity - 1. */
+int shems_foresight_demos_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *d_problems, int32_t n_problems,
+                              const shems_foresight_grid *grid, int32_t T, const double *d_results, int32_t n_pass,
+                              const int32_t *d_problem_of_pass, const float *d_targets, const int32_t *d_best_action,
+                              const shems_replay *ring, int64_t pos, int32_t *d_status, void *stream);
 
 #ifdef __cplusplus
 }

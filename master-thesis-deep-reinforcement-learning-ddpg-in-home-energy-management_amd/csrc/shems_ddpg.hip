@@ -323,12 +323,14 @@ struct PrepArgs {
 // workgroup, which writes everything later launches read to the workspace: normalize(s), normalize(s'), a, r, done,
 // d(-mean q)/dq and the sampled slots.  Split in a load and a store half so that the gather (whose addresses need no memory: the
 // slot comes from the counter RNG) is in flight together with every other load of the workgroup's first phase.
+// CLONE (the supervised update, shems_ddpg_clone_update): a ring of demonstrations holds s and a only -- s', r and done are never read.
 struct PrepRegs { float s[SIN], s2[SIN], lo[SIN], hi[SIN], a[2], r, dn; int64_t j; };
+template <bool CLONE = false>
 __device__ __forceinline__ void prep_load(const PrepArgs &A, int m, int which, bool publish, PrepRegs &R)
 {
     const shems_ddpg &d = A.d;
     const shems_replay &ring = A.ring;
-    const bool want_s2 = publish || which == 0, want_s = publish || which != 0, want_a = publish || which == 1;
+    const bool want_s2 = !CLONE && (publish || which == 0), want_s = publish || which != 0, want_a = publish || which == 1;
     const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)A.seed, (uint32_t)(A.seed >> 32));
     const uint32_t w = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
     int64_t j = (int64_t)(w % (uint32_t)(A.ring_len - A.excl_count));
@@ -342,8 +344,12 @@ __device__ __forceinline__ void prep_load(const PrepArgs &A, int m, int which, b
     }
     R.a[0] = want_a ? ring.a[j * 2] : 0.0f;
     R.a[1] = want_a ? ring.a[j * 2 + 1] : 0.0f;
-    R.r = publish ? ring.r[j] : 0.0f;
-    R.dn = publish ? (ring.done[j] ? 1.0f : 0.0f) : 0.0f;
+    if constexpr (CLONE) {
+        R.r = 0.0f; R.dn = 0.0f;
+    } else {
+        R.r = publish ? ring.r[j] : 0.0f;
+        R.dn = publish ? (ring.done[j] ? 1.0f : 0.0f) : 0.0f;
+    }
 }
 // xs (LDS input block, or null) has `xstride` columns; this thread's column goes to slot `xcol`.
 __device__ __forceinline__ void prep_store(const PrepArgs &A, int m, float *xs, int xcol, int xstride, int which, bool publish, const PrepRegs &R)
@@ -415,7 +421,7 @@ template <bool QG> struct FwdShape {
     static constexpr int LDS = (256 * WST + W1K * 32 + W1K * W1C + 256 + 4 * 16 * 64 + 4 * 2 * 32 + (QG ? 32 * 32 + 4 * 2 * 32 : 0)) * 4;
 };
 
-template <int IN, int PREP, bool QG>
+template <int IN, int PREP, bool QG, bool CLONE = false>
 __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const PrepArgs *pa, int bx, int job)
 {
     typedef FwdShape<QG> SH;
@@ -444,13 +450,18 @@ __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const Pre
         if (duty == 0) {
             if (tid < BP) {
                 PrepRegs pr;
-                prep_load(*pa, tid, 0, true, pr);
+                prep_load<CLONE>(*pa, tid, 0, true, pr);
                 prep_store(*pa, tid, nullptr, 0, 0, 0, true, pr);
             }
         } else if (duty <= 4) {
             const int net = duty - 1;
+            if constexpr (CLONE) { if (net != SLOT_ACTOR) return; }          // the supervised update reads the actor's image alone
             const float *Pn = net == SLOT_ACTOR_T ? d.actor_t : net == SLOT_CRITIC_T ? d.critic_t : net == SLOT_CRITIC ? d.critic : d.actor;
             pack_w1m(Pn, (net == SLOT_CRITIC_T || net == SLOT_CRITIC) ? CIN : SIN, w1t_of(d.ws, net));
+        } else if constexpr (CLONE) {                                         // the actor's output layer alone
+            float *ws = d.ws;
+            for (int e = tid; e < 1024; e += 256) ws[WS_FW3A + e] = e < 2 * H2N ? d.actor[off_w3(SIN) + e] : 0.0f;
+            if (tid < 2) ws[WS_FB3 + 2 + tid] = d.actor[off_b3(SIN, 2) + tid];
         } else {
             float *ws = d.ws;
             for (int e = tid; e < 512; e += 256) ws[WS_FW3C + e] = e < H2N ? d.critic[off_w3(CIN) + e] : 0.0f;
@@ -488,7 +499,7 @@ __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const Pre
     // First launch of an update: no separate sample/gather/pack launch.  Every tile workgroup samples the minibatch and gathers +
     // normalises what its network reads straight into its LDS input block, and packs the layer-1 image it needs from the
     // parameter block; the extra workgroups (above) publish the workspace copies for the later launches.
-    if (PREP == 1 && tid < 32) prep_load(*pa, mbase + tid, J.which, false, pr);
+    if (PREP == 1 && tid < 32) prep_load<CLONE>(*pa, mbase + tid, J.which, false, pr);
     // W2[0..255][n0..n0+31] (rows of 128 B, 8 float4 each): 2048 float4, 8 per thread.  Rows 250..255 are copies of row 249 (clamped
     // address): they only ever multiply layer-1 activations that are exactly zero (the image has no columns >= 250), in the forward
     // product, and in QG's backward product they feed output rows whose relu mask is off.  Columns >= 500 of the last tile read the
@@ -1147,6 +1158,49 @@ __device__ __forceinline__ void head_actor(const shems_ddpg &d, const HeadRegs &
     }
 }
 
+// ---- cloning head (shems_ddpg_clone_update), evaluated in the prologue of every workgroup of k_grad_clone ------------------
+// loss = Flux.mse(a_pi, a_demo) over the 2 * batch elements, a_pi = tanh(b3 + the NT layer-3 partials of K1's actor pass), added
+// in build_x_store's order; d3[o][m] = (a_pi - a_demo) (1 - a_pi^2) / batch for m < batch, 0 in the pad columns.  b3 comes from the
+// copy K1 froze: workgroup 0 updates it in place during this launch.  Workgroup 0 publishes a_pi, d3, gb3 and losses[1].
+__device__ __forceinline__ void head_clone_load(const shems_ddpg &d, HeadRegs &R)
+{
+    const float *ws = d.ws;
+    const int t = threadIdx.x, o = t >> 7, m = t & 127;
+    const float *P3 = slot(d.ws, SLOT_ACTOR) + SL_P3;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) R.v[i] = P3[(i * 2 + o) * BP + m];
+    R.s[0] = ws[WS_FB3 + 2 + o];
+    R.s[1] = ws[WS_AT + t];
+    R.s[2] = R.s[3] = 0.0f;
+}
+__device__ __forceinline__ void head_clone(const shems_ddpg &d, const HeadRegs &R, float *d3 /*LDS [2][BP]*/, float *red /*LDS [8]*/, bool publisher,
+                                           const AdamCtx *fuse)
+{
+    float *ws = d.ws;
+    const int t = threadIdx.x, m = t & 127;
+    float acc = R.s[0];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) acc += R.v[i];
+    const float a = tanhf(acc);                                // Dense(500, 2, tanh)
+    const float diff = m < d.batch ? a - R.s[1] : 0.0f;
+    const float g = diff * (1.0f - a * a) / (float)d.batch;    // d mse / d a_pi = 2 diff / (2 batch), then through tanh
+    d3[t] = g;
+    if (publisher) {
+        ws[WS_API + t] = a;
+        ws[WS_D3A + t] = g;
+        const float sg = wave_sum(g), sl = wave_sum(diff * diff);
+        if ((t & 63) == 0) { red[t >> 6] = sg; red[4 + (t >> 6)] = sl; }
+        __syncthreads();
+        if (t == 0) {
+            const float g0 = red[0] + red[1], g1 = red[2] + red[3];
+            d.grad_actor[off_b3(SIN, 2) + 0] = g0;
+            d.grad_actor[off_b3(SIN, 2) + 1] = g1;
+            d.losses[1] = ((red[4] + red[5]) + (red[6] + red[7])) / (2.0f * (float)d.batch);     // Flux.mse
+            if (fuse) { adam_elem(*fuse, off_b3(SIN, 2), g0); adam_elem(*fuse, off_b3(SIN, 2) + 1, g1); }
+        }
+    }
+}
+
 // ---- K3 / K5: every gradient block of one network, by batch contractions only -------------------------------------------
 // D2[n][m] = (sum_o W3[n][o] d3[o][m]) * (h2[n][m] > 0) is generated while staging, never stored.
 //   W workgroups (kt, nt): gW2[32 k][32 n] = sum_m h1[k][m] D2[n][m], one 16 x 16 block per wave over the whole batch
@@ -1164,7 +1218,7 @@ struct GradArgs {
     const float *w3f;      // frozen W3 [512][out]
     float *grad;           // gradient block
     const float *E0, *E1;  // [NQ][250][BP] partial E of output 0 / 1 (E1 null for the critic)
-    int head;              // 1 = critic loss head, 2 = actor head
+    int head;              // 1 = critic loss head, 2 = actor head, 3 = cloning head (k_grad_clone: chosen at compile time)
     int fuse;              // apply ADAM + soft update here
     shems_ddpg dd;         // for the heads
     AdamCtx c;
@@ -1238,7 +1292,8 @@ __device__ __forceinline__ void l1row_wave(const L1Row<IN, OUT> &R, const float 
     for (int j = 0; j < IN; ++j) gout[j] = wave_sum(R.x[0][j] * dv[0] + R.x[1][j] * dv[1]);
 }
 
-template <int IN, int OUT>
+// CLONE: the supervised update's instantiation (k_grad_clone) takes the cloning head at compile time; otherwise GradArgs.head decides.
+template <int IN, int OUT, bool CLONE = false>
 __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx)
 {
     // bx: this workgroup's index within the gradient grid
@@ -1266,9 +1321,11 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
         HeadRegs hr;
         L1Row<IN, OUT> R;
         l1row_load<IN, OUT>(A, min(k, H1N - 1), lane, R);
-        if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
+        if constexpr (CLONE) head_clone_load(A.dd, hr);
+        else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
         STAMP(kRegion, 1);
-        if (A.head == 1) head_loss(A.dd, hr, d3, red, false, nullptr); else head_actor(A.dd, hr, d3, red, false, nullptr);
+        if constexpr (CLONE) head_clone(A.dd, hr, d3, red, false, nullptr);
+        else if (A.head == 1) head_loss(A.dd, hr, d3, red, false, nullptr); else head_actor(A.dd, hr, d3, red, false, nullptr);
         __syncthreads();
         STAMP(kRegion, 2);
         if (k >= H1N) return;
@@ -1322,12 +1379,14 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
         w3v = A.w3f[(nrow0 + (t >> 1)) * OUT + min(o, OUT - 1)];                              // frozen copy: 512 rows, zero padded
     }
     HeadRegs hr;
-    if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
+    if constexpr (CLONE) head_clone_load(A.dd, hr);
+    else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
     if (is_w) {
         build_x_store<IN>(A.x, xr, xs, false);
         if (tid < 96) *reinterpret_cast<f32x4 *>(w1 + (tid >> 3) * 32 + 4 * (tid & 7)) = wq;
     }
-    if (A.head == 1) head_loss(A.dd, hr, d3, red, publisher, fz); else head_actor(A.dd, hr, d3, red, publisher, fz);
+    if constexpr (CLONE) head_clone(A.dd, hr, d3, red, publisher, fz);
+    else if (A.head == 1) head_loss(A.dd, hr, d3, red, publisher, fz); else head_actor(A.dd, hr, d3, red, publisher, fz);
     if (tid < 2 * 32) w3s[tid] = (tid & 1) < OUT ? w3v : 0.0f;
     STAMP(kRegion, 1);
     __syncthreads();
@@ -1513,6 +1572,26 @@ __global__ __launch_bounds__(256) void k_action_distance(const float *__restrict
     if (threadIdx.x == 0) out[0] = sqrtf(((part[0] + part[1]) + (part[2] + part[3])) / (float)count);
 }
 
+// ---- the two kernels of the supervised update (shems_ddpg_clone_update) ----
+// The first launch of the supervised update (shems_ddpg_clone_update): K1's actor job alone -- 64 tile workgroups + the publishing
+// workgroups it needs (the minibatch, the actor's layer-1 image, the actor's frozen output layer).  An instantiation of its own, so
+// that k_fwd, which replay() runs, keeps its code and registers; defined behind every other kernel of this file, so that those also
+// keep their places in the code object.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_fwd_clone(FwdArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const FwdJob J = A.job[0];
+    const PrepArgs pa = A.pa;
+    fwd_body<SIN, 1, false, true>(J, smem, &pa, (int)blockIdx.x, 0);
+}
+
+// The gradient launch of the supervised update: the actor's blocks with the cloning head, an instantiation of its own (see k_fwd_clone).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_grad_clone(GradArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    grad_body<SIN, 2, true>(A, smem, (int)blockIdx.x);
+}
+
 constexpr int FWD_LDS = FwdShape<false>::LDS, QG_LDS = FWD_LDS > QG16_LDS ? FWD_LDS : QG16_LDS;
 constexpr int MID_LDS = FWD_LDS > E_LDS ? FWD_LDS : E_LDS;
 static_assert(QG_LDS <= 160 * 1024, "one workgroup's LDS");
@@ -1522,6 +1601,14 @@ static int set_lds_attrs()
     if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd), QG_LDS, "attr k_fwd")) return rc;
     if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid), MID_LDS, "attr k_mid")) return rc;
     if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad), GR_LDS, "attr k_grad")) return rc;
+    return SHEMS_OK;
+}
+// The supervised update's two kernels: asked by shems_ddpg_clone_update alone, so that the calls replay() makes stay as they are.
+static int set_lds_attrs_clone()
+{
+    static std::atomic<uint64_t> m_fwd{0}, m_grad{0};
+    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_clone), FWD_LDS, "attr k_fwd_clone")) return rc;
+    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_clone), GR_LDS, "attr k_grad_clone")) return rc;
     return SHEMS_OK;
 }
 
@@ -1727,6 +1814,38 @@ int shems_ddpg_update(const shems_ddpg *d, const shems_replay *ring, int64_t rin
     const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr}, sa{eta_act, bp1_act, bp2_act, 1.0, d_publish};
     if (int rc = critic_side(d, ring, ring_len, seed, tick, excl_pos, excl_count, 1, 0, &sc, stream)) return rc;
     return actor_side(d, 1, 0, &sa, stream);
+}
+
+/* One supervised update of the actor on demonstrations: K1's actor job alone, the actor's two E products, the actor's gradient
+ * launch with the cloning head (ADAM + soft update inside).  Nothing of the critic is written. */
+int shems_ddpg_clone_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                            double eta, double bp1, double bp2, float *d_publish, void *stream)
+{
+    const char *fn = "shems_ddpg_clone_update";
+    if (int rc = check_adam(bp1, bp2, fn)) return rc;
+    if (int rc = check_ddpg(d, fn)) return rc;
+    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
+        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    if (int rc = set_lds_attrs_clone()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = d->ws, *SA = slot(ws, SLOT_ACTOR);
+    const XSrc none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const XSrc x_s{ws + WS_XT, nullptr, nullptr, nullptr, nullptr};
+    const AdamScalars sa{eta, bp1, bp2, 1.0, d_publish};
+    FwdArgs f;
+    std::memset(&f, 0, sizeof f);
+    f.job[0] = FwdJob{nullptr, d->actor, SIN, 2, 2, none, SA + SL_H2, SA + SL_P3, nullptr, nullptr};
+    f.prep = 1;
+    f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, 0, 0};
+    hipLaunchKernelGGL(k_fwd_clone, dim3(NT * (BP / 32) + 6), dim3(256), FWD_LDS, st, f);
+    if (int rc = actor_e_launch(d, 1, 0, st)) return rc;
+    GradArgs g;
+    std::memset(&g, 0, sizeof g);
+    g.w1t = w1t_of(ws, SLOT_ACTOR); g.P = d->actor; g.in = SIN; g.out = 2; g.x = x_s; g.H2 = SA + SL_H2; g.w3f = ws + WS_FW3A;
+    g.grad = d->grad_actor; g.E0 = SA + SL_EP; g.E1 = ws + WS_EA1; g.head = 3; g.fuse = 1; g.dd = *d; g.gstride = 0;
+    g.c = adam_ctx(d, false, sa);
+    hipLaunchKernelGGL(k_grad_clone, dim3(GR_NW + GR_NG + GR_NR), dim3(256), GR_LDS, st, g);
+    return hip_ok(hipGetLastError(), "ddpg clone-update launches");
 }
 
 int shems_ddpg_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int64_t ring_len, uint64_t seed,

@@ -461,6 +461,51 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_audit(FsAuditArgs A)
     }
 }
 
+// ---- demonstrations: result rows + labels -> (observation, action) pairs in a replay ring (fs_demo_hour, csrc/shems_foresight_core.h) ----
+struct FsDemosArgs {
+    const float *tables;
+    int64_t total_rows;
+    const shems_foresight_problem *prob;
+    int n_prob;
+    const int32_t *problem_of_pass;
+    FsParams g;
+    int T;
+    const double *results;
+    const float *targets;              // [n_pass][T][2], or null
+    const int32_t *best_action;        // [n_pass][T], or null (exactly one of the two is given)
+    float *s, *a;                      // the ring's observation and action arrays
+    int64_t capacity, pos;
+    int32_t *status;
+};
+
+// Grid = (tiles of kFsThreads hours, passes), one thread per hour: a few hundred bytes in, eleven floats out, nothing shared.  The
+// entry point has held n_pass * T to the capacity, so no two threads write one slot; a refused hour leaves its slot alone.
+__global__ __launch_bounds__(kFsThreads) void k_fs_demos(FsDemosArgs A)
+{
+    const int t = (int)blockIdx.x * kFsThreads + (int)threadIdx.x;
+    if (t >= A.T) return;
+    const int64_t e = blockIdx.y;
+    const int p = A.problem_of_pass ? A.problem_of_pass[e] : 0;
+    const int64_t at = e * A.T + t;
+    FsDemo d;
+    bool ok = p >= 0 && p < A.n_prob;
+    if (ok) {
+        const shems_foresight_problem P = A.prob[p];
+        ok = fs_demo_hour(P, A.tables, A.total_rows, A.results + at * SHEMS_NRESULT, t, A.targets ? A.targets + at * 2 : nullptr,
+                          A.best_action ? A.best_action[at] : -1, A.g, d);
+    }
+    if (!ok) {                                                              // every writer of status[e] stores the same value
+        A.status[e] = SHEMS_ERR_INDEX;
+        return;
+    }
+    const int64_t slot = fs_demo_slot(A.pos, e, A.T, t, A.capacity);
+    float *ps = A.s + slot * SHEMS_NSTATE;
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) ps[k] = d.s[k];
+    A.a[slot * 2] = d.a[0];
+    A.a[slot * 2 + 1] = d.a[1];
+}
+
 static int fs_params(const shems_foresight_grid *grid, const char *fn, FsParams &g)
 {
     if (!grid) return set_error(SHEMS_ERR_ARG, "%s: grid is NULL", fn);
@@ -718,4 +763,38 @@ extern "C" int shems_foresight_audit_dev(const float *d_tables, int64_t total_ro
     a.g = g; a.T = T; a.V = d_V; a.results = d_results; a.out = d_out; a.best_action = d_best_action; a.status = d_status;
     hipLaunchKernelGGL(k_fs_audit, dim3((unsigned)((T + kFsWaves - 1) / kFsWaves), (unsigned)n_pass), dim3(kFsThreads), 0, st, a);
     return hip_ok(hipGetLastError(), "k_fs_audit launch");
+}
+
+extern "C" int shems_foresight_demos_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *d_problems, int32_t n_problems,
+                                         const shems_foresight_grid *grid, int32_t T, const double *d_results, int32_t n_pass,
+                                         const int32_t *d_problem_of_pass, const float *d_targets, const int32_t *d_best_action,
+                                         const shems_replay *ring, int64_t pos, int32_t *d_status, void *stream)
+{
+    const char *fn = "shems_foresight_demos_dev";
+    FsParams g;
+    if (int rc = fs_params(grid, fn, g)) return rc;
+    if (T < 1) return set_error(SHEMS_ERR_ARG, "%s: T = %d; a pass is at least 1 hour", fn, (int)T);
+    if (!d_tables || total_rows < 2 || !d_problems || n_problems < 1)
+        return set_error(SHEMS_ERR_ARG, "%s: NULL buffer, fewer than 2 table rows, or no problem", fn);
+    if (n_pass < 1 || n_pass > 65535) return set_error(SHEMS_ERR_ARG, "%s: n_pass = %d; one call converts 1 .. 65535 passes", fn, (int)n_pass);
+    if (!d_results || !d_status) return set_error(SHEMS_ERR_ARG, "%s: NULL results or status buffer", fn);
+    if ((d_targets != nullptr) == (d_best_action != nullptr))
+        return set_error(SHEMS_ERR_ARG, "%s: exactly one label source: %s", fn, d_targets ? "both d_targets and d_best_action are given" : "neither d_targets nor d_best_action is given");
+    if (!ring || !ring->s || !ring->a) return set_error(SHEMS_ERR_ARG, "%s: NULL ring, or a ring without s or a", fn);
+    switch (fs_demo_check_ring(ring->capacity, pos, n_pass, T)) {
+    case 1: return set_error(SHEMS_ERR_ARG, "%s: the ring's capacity is %lld", fn, (long long)ring->capacity);
+    case 2: return set_error(SHEMS_ERR_ARG, "%s: %d passes x %d hours are %lld pairs; the ring's capacity is %lld", fn, (int)n_pass, (int)T,
+                             (long long)n_pass * T, (long long)ring->capacity);
+    case 3: return set_error(SHEMS_ERR_ARG, "%s: pos = %lld lies outside the ring of %lld slots", fn, (long long)pos, (long long)ring->capacity);
+    default: break;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = hip_ok(hipMemsetAsync(d_status, 0, (size_t)n_pass * sizeof(int32_t), st), "hipMemsetAsync(status)")) return rc;
+    FsDemosArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.tables = d_tables; a.total_rows = total_rows; a.prob = d_problems; a.n_prob = n_problems; a.problem_of_pass = d_problem_of_pass;
+    a.g = g; a.T = T; a.results = d_results; a.targets = d_targets; a.best_action = d_best_action; a.s = ring->s; a.a = ring->a;
+    a.capacity = ring->capacity; a.pos = pos; a.status = d_status;
+    hipLaunchKernelGGL(k_fs_demos, dim3((unsigned)((T + kFsThreads - 1) / kFsThreads), (unsigned)n_pass), dim3(kFsThreads), 0, st, a);
+    return hip_ok(hipGetLastError(), "k_fs_demos launch");
 }

@@ -181,6 +181,56 @@ SHEMS_HD double fs_audit_v_state(const shems_foresight_problem &P, const FsAudit
     return fs_value(V_cur, g, P.scale_b, h.s.Soc_b, h.s.Soc_ev);
 }
 
+// ---- demonstrations from tracked passes (shems_foresight_demos_dev; tests/imitation_ref.py restates it) ----
+// What a 9-input actor would have to answer at the states a pass was in: every (pass, hour) becomes one (observation, action) pair.
+//   observation  s[0..5] = the EnvIn of fs_audit_hour (same row check, same way back from the float64 columns), s[6..8] = columns
+//                5, 6, 7 of table row idx (h_cos, h_sin, season), as reset! / next_state! leave them (csrc/shems_env_dev.h): the nine
+//                floats shems_get_state shows before the step that wrote the row;
+//   label        a = (float)(2.0 * (double)target - 1.0) per axis, the inverse of scale_action (exact for dyadic targets k/2, k/4, ...;
+//                within one float32 rounding otherwise), so that labels at targets 0 and 1 are exactly -1 and +1.  The target is given
+//                (what shems_foresight_track_dev wrote), or it is (fs_target(ab, nab), fs_target(ae, nae)) of an action index
+//                a = ab * nae + ae (what the audit wrote): the DAgger label at a state ANOTHER controller visited.
+// An hour whose row check fails, or whose index label is outside 0 .. nab * nae - 1 (the audit's -1), gives no pair.
+struct FsDemo {
+    float s[SHEMS_NSTATE];
+    float a[2];
+};
+
+SHEMS_HD float fs_demo_label(float target) { return (float)(2.0 * (double)target - 1.0); }
+
+// target: the two targets of the hour, or null: `action` is an index into the action grid.  False: the hour gives no pair.
+SHEMS_HD bool fs_demo_hour(const shems_foresight_problem &P, const float *tables, int64_t total_rows, const double *r, int t,
+                           const float *target, int action, const FsParams &g, FsDemo &d)
+{
+    FsAuditHour h;
+    if (!fs_audit_hour(P, tables, total_rows, r, t, h)) return false;
+    float tb, te;
+    if (target) {
+        tb = target[0]; te = target[1];
+    } else {
+        if (action < 0 || action >= g.nab * g.nae) return false;
+        const int ab = action / g.nae, ae = action - ab * g.nae;
+        tb = fs_target(ab, g.nab); te = fs_target(ae, g.nae);
+    }
+    const float *row = tables + ((int64_t)P.cfg.table_row0 + ((int64_t)P.idx0 + t) - 1) * SHEMS_NCOL;      // table row idx: checked above
+    d.s[0] = h.s.Soc_b; d.s[1] = h.s.Soc_ev; d.s[2] = h.s.c_ev; d.s[3] = h.s.d_e; d.s[4] = h.s.g_e; d.s[5] = h.s.p_buy;
+    d.s[6] = row[5]; d.s[7] = row[6]; d.s[8] = row[7];
+    d.a[0] = fs_demo_label(tb); d.a[1] = fs_demo_label(te);
+    return true;
+}
+
+// The ring slot of (pass e, hour t) when the first pair goes to slot `pos`: passes one after the other, wrapping.
+SHEMS_HD int64_t fs_demo_slot(int64_t pos, int64_t e, int T, int t, int64_t capacity) { return (pos + e * T + t) % capacity; }
+
+// What the entry point refuses of the ring before anything is launched (0: accepted).
+SHEMS_HD int fs_demo_check_ring(int64_t capacity, int64_t pos, int64_t n_pass, int64_t T)
+{
+    if (capacity < 1) return 1;
+    if (n_pass * T > capacity) return 2;
+    if (pos < 0 || pos >= capacity) return 3;
+    return 0;
+}
+
 // ---- hedging over a forecast ENSEMBLE (shems_foresight_track_ensemble_dev; tests/foresight_ensemble_ref.py restates it) ----
 // The forecast controller above treats its one table as certain.  An ensemble problem is ONE truth (cfg, idx0) with K scenarios,
 // 1 <= K <= kFsMaxScen: scenario k is a forecast table in the sense above (forecast_off[k], same nrow, same row array) with a float64

@@ -100,6 +100,8 @@ def _declare():
     dbl = C.c_double
     L.shems_ddpg_update.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, i64, i64, dbl, dbl, dbl, dbl, dbl, dbl, vp, vp]
     L.shems_ddpg_update.restype = C.c_int
+    L.shems_ddpg_clone_update.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, vp, vp]
+    L.shems_ddpg_clone_update.restype = C.c_int
     L.shems_ddpg_critic_grad.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, vp]
     L.shems_ddpg_critic_grad_ex.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, i64, i64, vp]
     L.shems_ddpg_critic_grad_ex.restype = C.c_int
@@ -357,6 +359,7 @@ class Agent:
         self.bp_actor = [0.9, 0.999]               # Flux ADAM state beta^t (Float64), advanced after every step
         self.bp_critic = [0.9, 0.999]
         self.updates = 0
+        self.clones = 0                            # supervised updates on demonstrations (clone); they advance bp_actor, not `updates`
         self.sync = GradSync(None)                 # replicas exchange gradients through this (RCCL)
         self.dp_overlap = False                    # data parallel: True = the critic's gradient all-reduce runs asynchronously under the actor's E
                                                    # products (shems_ddpg_actor_prepare); False = everything in program order (same bits).
@@ -693,6 +696,33 @@ class Agent:
         self._actor_apply_pub(d, gs, publish, st)
         self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
         self.updates += 1
+
+    def clone(self, demos, tick=None, tau=1.0, publish=None):
+        """One SUPERVISED update of the actor on demonstrations (imitation.Demos, or any ring whose s and a hold (observation,
+        action) pairs): loss = Flux.mse(actor(normalize(s)), a_demo) on a minibatch the ordinary sampler draws (sample_indices(tick,
+        len(demos)) predicts the slots), ADAM(eta_act) on the actor and the soft update of actor_t with `tau` in the gradient launch
+        (shems_ddpg_clone_update: three launches, nothing of the critic is touched).  tau = 1.0 keeps actor_t equal to the actor bit
+        for bit (1 p + 0 t): a pre-trained actor starts DDPG with its target on itself.  The loss lands in losses[1].  bp_actor
+        advances as in replay(); the step counts in `clones` (the default tick), `updates` does not move.  publish: a tensor that
+        also receives the updated actor.  Networks up to (250, 500) (smaller ones through pad_net), batch <= 128, one replica."""
+        if self.wide or is_wide(self.hidden):
+            raise NotImplementedError(f"clone: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no supervised update")
+        if self.batch > self.MAX_PASS_BATCH:
+            raise NotImplementedError(f"clone: BATCH_SIZE = {self.batch}; the supervised update holds at most {self.MAX_PASS_BATCH} columns")
+        if self.sync.world > 1:
+            raise NotImplementedError("clone: data-parallel replicas do not exchange the supervised gradient")
+        if getattr(self, "_before_param_write", None) is not None:
+            raise NotImplementedError("clone: a learner of a learner group keeps its own working layout")
+        self._same_device(None, demos)
+        d = self._ddpg_args()
+        d.tau = float(tau)
+        rs = demos.struct()
+        tick = self.clones if tick is None else tick
+        _capi.check(self.L.shems_ddpg_clone_update(C.byref(d), C.byref(rs), len(demos), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_act,
+                                                   self.bp_actor[0], self.bp_actor[1],
+                                                   C.c_void_p(publish.data_ptr()) if publish is not None else None, self._stream()))
+        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
+        self.clones += 1
 
     def sample_indices(self, tick, ring_len, batch=None):
         batch = self.batch if batch is None else int(batch)

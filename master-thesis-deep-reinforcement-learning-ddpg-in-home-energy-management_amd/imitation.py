@@ -1,0 +1,161 @@
+"""The actor trained by imitation of the foresight controller (this build's addition; the reference has no supervised step).
+
+The foresight controller (foresight.py) knows the future rows; the DDPG actor sees nine numbers.  How much of the foresight return
+can such an actor hold at all?  Three pieces answer it, all on the GPU:
+
+  * demonstrations: the 23-column rows of a tracked pass plus one label per hour become (observation, action) pairs in a ring
+    (shems_foresight_demos_dev, one launch; the definition: fs_demo_hour in csrc/shems_foresight_core.h).  The label is either the
+    targets the foresight pass itself chose (from_foresight) or, for a pass of ANY controller, the best action of the audit at the
+    states that pass actually visited (from_pass) -- the DAgger label;
+  * the supervised update: ddpg.Agent.clone, loss = Flux.mse(actor(normalize(s)), a_demo) (shems_ddpg_clone_update, three launches);
+  * dagger: round 0 clones the foresight pass, every later round runs the current actor, labels the states it visited and trains on.
+
+Nothing here seeds the DDPG ring or pre-trains the critic: DDPG fine-tuning after cloning starts from an untrained critic.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi, foresight
+from .replay import ReplayRing
+
+
+class Demos(ReplayRing):
+    """A ring of demonstrations, shaped like the replay ring (ddpg.Agent.clone and min_max_buffer take it): zero-allocated, only s
+    and a are ever written (r, s2 and done stay zero and are never read), and its length grows with what was written -- `pushed`
+    counts the pairs, the next one goes to slot `pos`."""
+
+    def __init__(self, capacity, device=None):
+        super().__init__(capacity, device=device)
+
+
+def _declare(L):
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.shems_foresight_demos_dev.argtypes = [vp, i64, vp, i32, C.POINTER(foresight.GridStruct), i32, vp, i32, vp, vp, vp,
+                                            C.POINTER(_capi.Replay), i64, vp, vp]
+    L.shems_foresight_demos_dev.restype = C.c_int
+    return L
+
+
+def _check_values(values, what):
+    if isinstance(values, foresight.EnsembleValues):
+        raise ValueError(f"{what}: the values were solved on a forecast ensemble (pass the Values of a solve on the true rows)")
+    return values
+
+
+def _write(values, results, problem_of_pass, demos, targets=None, best_action=None):
+    """The demos call for n passes [n][T][23] with one label source (host arrays): one launch on PyTorch's current stream, one copy
+    back of the status words.  Raises BoundsError naming the first refused pass and leaves the length alone; otherwise the length
+    grows by n * T."""
+    import torch
+    res = np.ascontiguousarray(results, np.float64)
+    n, T = int(res.shape[0]), values.nsteps
+    if res.ndim != 3 or res.shape[1] != T or res.shape[2] != _capi.NRESULT:
+        raise ValueError(f"results must be [n][{T}][{_capi.NRESULT}], not {tuple(res.shape)}")
+    L = _declare(_capi.lib())
+    dev = demos.s.device
+    env = values._tables if hasattr(values._tables, "use_torch_stream") else None        # a ShemsBatch, or the uploaded tensor
+    if env is not None:
+        env.use_torch_stream()
+        tab_ptr = env.view().tables
+    else:
+        tab_ptr = values._tables.data_ptr()
+    d_res = torch.from_numpy(res).to(dev)
+    d_po = torch.from_numpy(np.ascontiguousarray(problem_of_pass, np.int32)).to(dev) if problem_of_pass is not None else None
+    d_tgt = torch.from_numpy(np.ascontiguousarray(targets, np.float32).reshape(n, T, 2)).to(dev) if targets is not None else None
+    d_act = torch.from_numpy(np.ascontiguousarray(best_action, np.int32).reshape(n, T)).to(dev) if best_action is not None else None
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    g = values.grid.struct()
+    rs = demos.struct()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _capi.check(L.shems_foresight_demos_dev(C.c_void_p(tab_ptr), int(values.total_rows), C.c_void_p(values.d_problems.data_ptr()),
+                                            values.n_problems, C.byref(g), T, ptr(d_res), n, ptr(d_po), ptr(d_tgt), ptr(d_act), C.byref(rs),
+                                            demos.pos, ptr(status), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    st = status.cpu().numpy()                                # the call's one synchronisation
+    bad = np.nonzero(st)[0]
+    if bad.size:
+        e = int(bad[0])
+        raise _capi.BoundsError(int(st[e]), f"imitation: pass {e}: a row does not sit on its problem's table rows, it names none of the "
+                                f"{values.n_problems} problems, or an hour has no label (best_action -1); the ring's length is unchanged")
+    demos.pushed += n * T
+
+
+def from_foresight(env, values, demos, problem_of_env=None, which=-1):
+    """The foresight controller's own pass as demonstrations: foresight.track from the envs' CURRENT state (reset them onto their
+    problem's start row first), then every (env, hour) -- or those of env `which` alone -- goes into `demos` with the targets that
+    pass chose.  `values`: whatever foresight.track takes (a forecast controller's targets are labels like any other).  Returns what
+    foresight.track returns (totals, results, targets)."""
+    ens = values if isinstance(values, foresight.EnsembleValues) else None
+    inner = ens.values if ens is not None else values
+    total, results, targets = foresight.track(env, values, problem_of_env, which=which)
+    po = None if problem_of_env is None else np.asarray(problem_of_env, np.int32).reshape(env.n)
+    if ens is not None and po is not None:
+        po = po * ens.n_scen                                 # the first record of the problem: every scenario shares its truth
+    if which >= 0:
+        targets = targets[which:which + 1]
+        po = None if po is None else po[which:which + 1]
+    _write(inner, results, po, demos, targets=targets)
+    return total, results, targets
+
+
+def from_pass(values, results, demos, problem_of_pass=None):
+    """The DAgger labels of passes of ANY controller: foresight.audit of the rows ([n][T][23] or [T][23]) against `values`, then every
+    (pass, hour) goes into `demos` with the audit's best action at the state the pass was in.  Values solved on a forecast, and
+    EnsembleValues, are refused as audit refuses them.  Returns the Audit."""
+    _check_values(values, "from_pass")
+    audit = foresight.audit(values, results, problem_of_pass)
+    res = np.asarray(results, np.float64)
+    _write(values, res[None] if res.ndim == 2 else res, problem_of_pass, demos, best_action=audit.best_action)
+    return audit
+
+
+def dagger(agent, env, values, demos, rounds, steps_per_round, tau=1.0):
+    """Dataset aggregation on one data set: every pass starts from reset!(rng = -1) and runs values.nsteps hours; `values` is the
+    perfect-foresight solve of env's table from row 1 (harness.foresight_values(env)).
+      round 0          the foresight controller's pass (env 0's) goes into `demos`, the normalisation is set from it
+                       (agent.min_max_buffer) and `steps_per_round` clone steps follow: plain behaviour cloning;
+      round r >= 1     the CURRENT actor's pass (harness.inference), labelled by the audit at the states it visited (from_pass),
+                       is appended, and `steps_per_round` clone steps follow on everything gathered so far.
+    All device work goes on PyTorch's current stream.  Returns one dict per round: "return" (round 0: the foresight pass's, later:
+    the return of the actor that round started with), "loss" (losses[1] after the round's last step) and "demos" (the ring's length)."""
+    from . import harness
+    rounds, steps = int(rounds), int(steps_per_round)
+    if rounds < 1 or steps < 1:
+        raise ValueError(f"dagger: {rounds} rounds x {steps} steps; at least one of each")
+    _check_values(values, "dagger")
+    out = []
+    for r in range(rounds):
+        if r == 0:
+            env.use_torch_stream()
+            env.reset_(-1)
+            _, _, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+            total, _, _ = from_foresight(env, values, demos, poe, which=0)
+            agent.min_max_buffer(demos)
+            ret = float(total[0])
+        else:
+            total, res = harness.inference(env, agent, track=1, num_steps=values.nsteps)
+            _, _, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+            from_pass(values, res, demos, poe[:1] if values.n_problems > 1 else None)
+            ret = float(total[0])
+        for _ in range(steps):
+            agent.clone(demos, tau=tau)
+        out.append({"return": ret, "loss": float(agent.losses[1].item()), "demos": len(demos)})
+    return out
+
+
+IMITATION_HEADER = ["round", "return", "loss", "demos"]
+
+
+def write_to_imitation_file(rounds, path):
+    """dagger's per-round figures as a CSV beside the foresight results file."""
+    import csv
+    import os
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(IMITATION_HEADER)
+        for k, r in enumerate(rounds):
+            w.writerow([k, repr(float(r["return"])), repr(float(r["loss"])), int(r["demos"])])
+    return path

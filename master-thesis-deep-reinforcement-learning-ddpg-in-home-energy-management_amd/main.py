@@ -28,6 +28,8 @@ Differences that follow from the platform, all explicit:
     controller planning on the persistence forecast of load and PV -- with `ev` of h_countdown and soc_ev too --:
     ..._foresight_h24_p24.csv / ..._foresight_h24_p24ev.csv; SHEMS_FORESIGHT_FORECAST=analog:24,48,72[:ev] instead adds the controller
     that hedges over the analog ensemble of those lags with equal weights (foresight.solve_ensemble): ..._foresight_h24_a24-48-72.csv;
+    SHEMS_FORESIGHT_IMITATE=<rounds>x<steps> (needs SHEMS_FORESIGHT=1) trains a fresh actor by imitation of the foresight pass
+    (imitation.dagger) and writes its per-round figures to ..._results_<case>_imitation.csv;
     SHEMS_FORESIGHT_REGRET=1 (needs SHEMS_FORESIGHT=1) adds one <results file>_regret.csv next to every results file of the tracking
     block -- the hourly regret of that pass against ONE perfect-foresight solve (harness.regret_of; the forecast passes are audited
     against the truth like the rest);
@@ -225,6 +227,31 @@ def foresight_regret(environ=os.environ):
     return True
 
 
+def foresight_imitate(environ=os.environ):
+    """SHEMS_FORESIGHT_IMITATE=<rounds>x<steps> -> (rounds, steps), both >= 1: after the foresight pass a FRESH actor is trained by
+    imitation of it (imitation.dagger: round 0 clones the foresight pass, every later round adds the audit's labels at the states the
+    current actor visited), <steps> supervised updates per round; the per-round figures go to ..._results_<case>_imitation.csv beside
+    the foresight file.  None when unset.  It needs SHEMS_FORESIGHT=1; a malformed value is refused by name."""
+    raw = environ.get("SHEMS_FORESIGHT_IMITATE")
+    if raw is None:
+        return None
+    if environ.get("SHEMS_FORESIGHT") != "1":
+        raise ValueError("SHEMS_FORESIGHT_IMITATE is set without SHEMS_FORESIGHT=1")
+    parts = raw.lower().split("x")
+    try:
+        rounds, steps = (int(x) for x in parts)
+    except ValueError:
+        raise ValueError(f"SHEMS_FORESIGHT_IMITATE = {raw!r} is not <rounds>x<steps>") from None
+    if rounds < 1 or steps < 1:
+        raise ValueError(f"SHEMS_FORESIGHT_IMITATE = {raw!r}: at least one round of at least one step")
+    return rounds, steps
+
+
+def imitation_file_name(job_id, run, case, out_dir="out/tracker"):
+    """The per-round figures of SHEMS_FORESIGHT_IMITATE, beside harness.foresight_file_name's file."""
+    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_imitation.csv")
+
+
 def foresight_forecast(environ=os.environ):
     """SHEMS_FORESIGHT_FORECAST = persistence[:LAG[:ev]] -> (lag, ev), or analog:LAG,LAG,...[:ev] -> ("analog", (lags), ev) (1 .. 16
     lags, each >= 1); None when unset.  It needs SHEMS_FORESIGHT_HORIZON; a malformed value is refused by name."""
@@ -291,6 +318,10 @@ def main(environ=os.environ, cwd=".", log=print):
     horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
     forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
     regret = foresight_regret(environ)
+    imitate = foresight_imitate(environ)
+    if imitate is not None and (cfg.L1 > 250 or cfg.L2 > 500 or cfg.BATCH_SIZE > 128):
+        raise ValueError(f"SHEMS_FORESIGHT_IMITATE: the supervised update holds networks up to (250, 500) and batches up to 128, not "
+                         f"({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE}")
     os.chdir(cwd)
     torch.cuda.set_device(cfg.gpu_id)                                    # CUDA.device!(gpu_id), MAIN:12-14
     if cfg.seed_run == 1:
@@ -387,7 +418,7 @@ def main(environ=os.environ, cwd=".", log=print):
         written.append(path)
         audited.append((path, results))
     if environ.get("SHEMS_FORESIGHT") == "1":                            # this build's addition: the upper yardstick on the same table
-        values = harness.foresight_values(env_track) if regret else None   # the one perfect-foresight solve every audit below reads
+        values = harness.foresight_values(env_track) if regret or imitate is not None else None   # the one perfect-foresight solve every audit below reads
         _, results = harness.inference_foresight(env_track, values=values)
         path = harness.foresight_file_name(cfg.job_id, cfg.run, cfg.case)
         harness.write_to_results_file(results[0], path)
@@ -427,6 +458,13 @@ def main(environ=os.environ, cwd=".", log=print):
             audit = harness.regret_of(env_track, np.stack([r for _, r in audited]), values=values)
             for k, (path, res) in enumerate(audited):
                 written.append(harness.write_to_regret_file(audit, res, harness.regret_file_name(path), pass_index=k))
+        if imitate is not None:                                          # a fresh actor trained by imitation of the foresight pass
+            from . import imitation
+            pupil = D.Agent(seed=cfg.rng_run, hidden=(cfg.L1, cfg.L2))
+            pupil.batch, pupil.eta_act = cfg.BATCH_SIZE, float(np.float32(cfg.eta_act))
+            demos = imitation.Demos(imitate[0] * EP_LENGTH[cfg.season, cfg.run])
+            figures = imitation.dagger(pupil, env_track, values, demos, imitate[0], imitate[1])
+            written.append(imitation.write_to_imitation_file(figures, imitation_file_name(cfg.job_id, cfg.run, cfg.case)))
     for e in (env_train, env_eval, env_track):
         e.close()
     log(f"Script with JOB_ID: {cfg.job_id} & TASK_ID: {cfg.task_id} is done!")
