@@ -338,6 +338,14 @@ int shems_ddpg_actor_apply_pub(const shems_ddpg *d, double eta, double bp1, doub
  * touched.  Arguments and validation as shems_ddpg_update's for the actor. */
 int shems_ddpg_clone_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                             double eta, double bp1, double bp2, float *d_publish, void *stream);
+/* One CRITIC-ONLY update (policy evaluation): update_model!(critic, ...) and soft_update!(critic_target, critic) of DDPG.jl:131-137
+ * and 143, in three launches of the update's own kernels -- the first without the actor's forward job, the second without the actor's
+ * two E products, the third the critic's gradient with ADAM and the soft update inside.  actor, actor_t, m_actor, v_actor, grad_actor
+ * and losses[1] are not touched.  From the same state, ring, seed and tick it leaves the bits of shems_ddpg_critic_grad followed by
+ * shems_ddpg_critic_apply(grad_scale = 1) in critic, critic_t, m_critic, v_critic, grad_critic and losses[0].  Arguments and
+ * validation as shems_ddpg_update's for the critic. */
+int shems_ddpg_critic_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                             double eta, double bp1, double bp2, void *stream);
 /* The minibatch indices of (seed, tick): host helper for tests (same Philox as the device). */
 int shems_ddpg_sample_indices(uint64_t seed, uint32_t tick, int32_t batch, int64_t ring_len, int64_t *out);
 /* ------------------------------------------ data-parallel replicas -- */
@@ -791,6 +799,26 @@ int shems_foresight_demos_dev(const float *d_tables, int64_t total_rows, const s
                               const shems_foresight_grid *grid, int32_t T, const double *d_results, int32_t n_pass,
                               const int32_t *d_problem_of_pass, const float *d_targets, const int32_t *d_best_action,
                               const shems_replay *ring, int64_t pos, int32_t *d_status, void *stream);
+/* Transitions from tracked passes: the rows of DRL-mode passes become full replay slots (s, a, r, s', done), so that a ring can be
+ * seeded and a critic fitted from passes that are tracked anyway (shems_ddpg_critic_update).  The definition -- fs_transition_hour,
+ * fs_returns -- is in csrc/shems_foresight_core.h: s and s' are the observations of rows t and t + 1, a the labels of the targets the
+ * rows record (columns 21 and 2), r = (float)reward; the return-to-go is G[T - 1] = r[T - 1], G[t] = r[t] + (double)gamma * G[t + 1]
+ * in float64, in that order.  Rows of a RULE-BASED pass record no targets: they would give wrong actions, and nothing checks it.
+ * mode SHEMS_FS_TRANS_TD: the slot holds (s, a, r, s', 0).  SHEMS_FS_TRANS_MC: it holds (s, a, (float)G[t], s', 1), so that the update's
+ * y = r + gamma (1 - done) q' is G[t] and no network is bootstrapped from.  tail (1 .. T - 1): hours t >= T - tail give no transition
+ * (G still sums over all T hours); pass e, hour t goes to slot (pos + e * (T - tail) + t) mod ring->capacity.
+ * d_returns [n_pass][T] float64 receives G (required for MC, optional for TD).  TD: an hour whose row check (hour t or t + 1) fails or
+ * whose reward is not finite leaves its slot untouched and sets d_status[e] = SHEMS_ERR_INDEX; the other hours are written.  MC: a pass
+ * any of whose T hours fails gives no transition, its status is set and its row of d_returns holds NaN.  d_status [n_pass] int32 is
+ * zeroed on `stream`, then k_fs_returns (only with d_returns: a wave per pass) and k_fs_transitions (a thread per hour); no host
+ * synchronisation.  SHEMS_ERR_ARG, nothing launched: T < 2, tail outside 1 .. T - 1, an unknown mode, MC without d_returns, gamma
+ * outside [0, 1] or not finite, a ring without all five arrays, n_pass * (T - tail) > capacity, pos outside the ring, n_pass outside
+ * 1 .. 65535, a NULL where a buffer is required. */
+enum { SHEMS_FS_TRANS_TD = 0, SHEMS_FS_TRANS_MC = 1 };
+int shems_foresight_transitions_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *d_problems,
+                                    int32_t n_problems, int32_t T, const double *d_results, int32_t n_pass,
+                                    const int32_t *d_problem_of_pass, int32_t mode, float gamma, int32_t tail, double *d_returns,
+                                    const shems_replay *ring, int64_t pos, int32_t *d_status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -294,6 +294,16 @@ function replay(ag::Agent, memory::ReplayRing; rng_rpl::Integer=ag.updates)
     return nothing
 end
 
+"evaluate!(ag, memory; rng_rpl): the critic half of replay() alone (DDPG.jl:131-137, 143) -- policy evaluation, the actor is left alone; three launches"
+function evaluate!(ag::Agent, memory::ReplayRing; rng_rpl::Integer=ag.updates)
+    check(ccall((:shems_ddpg_critic_update, LIB), Cint,
+                (Ptr{ShemsDdpg}, Ptr{ShemsReplay}, Int64, UInt64, UInt32, Float64, Float64, Float64, Ptr{Cvoid}),
+                Ref(ddpg_struct(ag)), Ref(ring_struct(memory)), length(memory), ag.seed, rng_rpl % 0x100000000,
+                ag.eta_crit, ag.bp_critic[1], ag.bp_critic[2], C_NULL))
+    ag.bp_critic .*= [0.9, 0.999]
+    return nothing
+end
+
 """train_steps!(ag, env, memory, k; t, episode, rng_ep): k vector steps of the training hour loop of episode! (DDPG.jl:195-234) -- act, step!,
 remember, replay() -- enqueued by ONE foreign call (shems_train_steps, program order): what `for _ in 1:k act_step!(...); replay(...) end` launches,
 without a ccall per launch.  `t` = vector steps done so far in this run (noise tick, window rotation, episode boundaries every EP_LENGTH

@@ -1668,7 +1668,8 @@ static int actor_e_launch(const shems_ddpg *d, unsigned L, int64_t gs, hipStream
 }
 
 static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
-                       int64_t excl_pos, int64_t excl_count, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream)
+                       int64_t excl_pos, int64_t excl_count, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream,
+                       bool critic_only = false)
 {
     if (int rc = check_ddpg(d, "shems_ddpg_critic_grad")) return rc;
     if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
@@ -1692,7 +1693,8 @@ static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ri
     f.job[2] = FwdJob{nullptr, d->actor, SIN, 2, 2, none, SA + SL_H2, SA + SL_P3, nullptr, nullptr};
     f.prep = 1;
     f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count};
-    hipLaunchKernelGGL(k_fwd, dim3(3 * (fgx + 6), 1, L), dim3(256), flds, st, f);      // + 6 publishing workgroups per job (see fwd_body)
+    // + 6 publishing workgroups per job (see fwd_body); they do their work in job 0, so the critic-only update drops job 2 whole
+    hipLaunchKernelGGL(k_fwd, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
     // K2: critic_target on [s'; actor_target(s')] | E of the critic | E of the actor's two outputs
     MidArgs m;
     std::memset(&m, 0, sizeof m);
@@ -1701,7 +1703,7 @@ static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ri
     m.e[0] = EJob{d->critic, CIN, 1, 0, SC + SL_H2, SC + SL_EP};
     m.e[1] = EJob{d->actor, SIN, 2, 0, SA + SL_H2, SA + SL_EP};
     m.e[2] = EJob{d->actor, SIN, 2, 1, SA + SL_H2, ws + WS_EA1};
-    const bool defer_ea = !fuse && (d->flags & SHEMS_DDPG_DEFER_ACTOR_E) != 0;       // the caller runs shems_ddpg_actor_prepare later
+    const bool defer_ea = critic_only || (!fuse && (d->flags & SHEMS_DDPG_DEFER_ACTOR_E) != 0);   // the caller runs shems_ddpg_actor_prepare later, or never
     hipLaunchKernelGGL(k_mid, dim3(fgx + (defer_ea ? 1 : 3) * KT * NQ, 1, L), dim3(256), MID_LDS, st, m);
     // K3: critic gradient (+ ADAM + soft update)
     GradArgs g;
@@ -1846,6 +1848,15 @@ int shems_ddpg_clone_update(const shems_ddpg *d, const shems_replay *ring, int64
     g.c = adam_ctx(d, false, sa);
     hipLaunchKernelGGL(k_grad_clone, dim3(GR_NW + GR_NG + GR_NR), dim3(256), GR_LDS, st, g);
     return hip_ok(hipGetLastError(), "ddpg clone-update launches");
+}
+
+/* Policy evaluation: the critic side of replay() alone, with K1 and K2 cut down to what the critic reads (critic_side). */
+int shems_ddpg_critic_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                             double eta, double bp1, double bp2, void *stream)
+{
+    if (int rc = check_adam(bp1, bp2, "shems_ddpg_critic_update")) return rc;
+    const AdamScalars sc{eta, bp1, bp2, 1.0, nullptr};
+    return critic_side(d, ring, ring_len, seed, tick, 0, 0, 1, 0, &sc, stream, true);
 }
 
 int shems_ddpg_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int64_t ring_len, uint64_t seed,

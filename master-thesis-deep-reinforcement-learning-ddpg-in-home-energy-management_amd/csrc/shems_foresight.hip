@@ -506,6 +506,124 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_demos(FsDemosArgs A)
     A.a[slot * 2 + 1] = d.a[1];
 }
 
+// ---- transitions: result rows -> (s, a, r, s', done) in a replay ring, and the returns-to-go of the passes (fs_transition_hour,
+// fs_returns, csrc/shems_foresight_core.h) ----
+struct FsTransArgs {
+    const float *tables;
+    int64_t total_rows;
+    const shems_foresight_problem *prob;
+    int n_prob;
+    const int32_t *problem_of_pass;
+    int T, tail, mode;
+    float gamma;
+    const double *results;
+    double *returns;                   // [n_pass][T], or null (TD only)
+    float *s, *a, *r, *s2;             // the ring's arrays
+    uint8_t *done;
+    int64_t capacity, pos;
+    int32_t *status;
+};
+
+__device__ __forceinline__ double fs_wave_lane(double x, int lane)         // lane: uniform
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane), hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
+    return __hiloint2double(hi, lo);
+}
+
+// One wave per pass.  The recurrence is one dependent chain per pass: the wave takes the pass in chunks of 64 hours from the end, every
+// lane loads and checks ITS hour (the next chunk's loads are issued before this chunk's chain), then all lanes walk the chunk's 64
+// steps together on rewards read out of each other's registers -- the chain never waits for memory -- and lane j keeps step j's value.
+// G[T - 1] is read before the loop and only the last chunk, which may be short, is walked with a bound: a step of a full chunk is the
+// product, the sum and six instructions beside them.  The order of fs_returns, whatever T.  A refused pass (MC's verdict, core
+// header) gets fs_returns_refused() in every hour, which is what k_fs_transitions reads of it; status[e] is written in MC mode only.
+__global__ __launch_bounds__(64) void k_fs_returns(FsTransArgs A)
+{
+    const int lane = (int)threadIdx.x;
+    const int64_t e = blockIdx.x;
+    const int p = A.problem_of_pass ? A.problem_of_pass[e] : 0;
+    const bool known = p >= 0 && p < A.n_prob;
+    const shems_foresight_problem P = A.prob[known ? p : 0];
+    const double *res = A.results + e * A.T * SHEMS_NRESULT;
+    double *out = A.returns + e * A.T;
+    const double g = (double)A.gamma;
+    auto load = [&](int c, double &rew, bool &ok) {
+        const int t = c * 64 + lane;
+        rew = 0.0; ok = true;
+        if (t < A.T) {
+            const double *r = res + (int64_t)t * SHEMS_NRESULT;
+            rew = r[5];
+            ok = fs_returns_hour_ok(P, A.tables, A.total_rows, r, t);
+        }
+    };
+    const int last = A.T - 1, nchunk = last / 64 + 1;
+    bool bad = !known, ok, ok_next = true;
+    double rew, rew_next = 0.0;
+    load(nchunk - 1, rew, ok);
+    double G = fs_wave_lane(rew, last & 63);                                // G[T - 1] = r[T - 1][5]: the chain starts at hour T - 2
+    auto step = [&](int j, double &mine) {                                  // j: uniform
+        G = fs_return_step(fs_wave_lane(rew, j), g, G);
+        if (lane == j) mine = G;
+    };
+    for (int c = nchunk - 1; c >= 0; --c) {
+        if (c > 0) load(c - 1, rew_next, ok_next);
+        bad = bad || !ok;
+        double mine = G;                                                    // the lane of hour T - 1 keeps this; every other lane that stores takes a step's
+        if (c == nchunk - 1) {                                              // the one chunk that may be short: hours T - 2 down to its first
+#pragma unroll 1
+            for (int j = (last & 63) - 1; j >= 0; --j) step(j, mine);
+        } else {
+#pragma unroll 1
+            for (int q = 3; q >= 0; --q) {                                  // 16 rewards in scalar registers at a time, no branch inside
+#pragma unroll
+                for (int u = 15; u >= 0; --u) step(q * 16 + u, mine);
+            }
+        }
+        if (c * 64 + lane < A.T) out[c * 64 + lane] = mine;
+        rew = rew_next; ok = ok_next;
+    }
+    if (__any(bad)) {
+        for (int t = lane; t < A.T; t += 64) out[t] = fs_returns_refused();     // the same lane stored hour t above
+        if (A.mode == SHEMS_FS_TRANS_MC && lane == 0) A.status[e] = SHEMS_ERR_INDEX;
+    }
+}
+
+// Grid = (tiles of kFsThreads hours, passes), one thread per hour with a successor, as k_fs_demos.  The entry point has held
+// n_pass * (T - tail) to the capacity, so no two threads write one slot.  MC: the verdict of the pass is the NaN k_fs_returns left in
+// its first return (not the status word, which the host reads); every writer of status[e] stores the same value.
+__global__ __launch_bounds__(kFsThreads) void k_fs_transitions(FsTransArgs A)
+{
+    const int t = (int)blockIdx.x * kFsThreads + (int)threadIdx.x;
+    const int keep = A.T - A.tail;
+    if (t >= keep) return;
+    const int64_t e = blockIdx.y;
+    const bool mc = A.mode == SHEMS_FS_TRANS_MC;
+    float ret = 0.0f;
+    if (mc) {
+        const double G0 = A.returns[e * A.T];
+        if (G0 != G0) return;
+        ret = (float)A.returns[e * A.T + t];
+    }
+    const int p = A.problem_of_pass ? A.problem_of_pass[e] : 0;
+    FsTransition x;
+    bool ok = p >= 0 && p < A.n_prob;
+    if (ok) {
+        const shems_foresight_problem P = A.prob[p];
+        ok = fs_transition_hour(P, A.tables, A.total_rows, A.results + (e * A.T + t) * SHEMS_NRESULT, t, x);
+    }
+    if (!ok) {
+        A.status[e] = SHEMS_ERR_INDEX;
+        return;
+    }
+    const int64_t slot = fs_demo_slot(A.pos, e, keep, t, A.capacity);
+    float *ps = A.s + slot * SHEMS_NSTATE, *ps2 = A.s2 + slot * SHEMS_NSTATE;
+#pragma unroll
+    for (int k = 0; k < SHEMS_NSTATE; ++k) { ps[k] = x.d.s[k]; ps2[k] = x.s2[k]; }
+    A.a[slot * 2] = x.d.a[0];
+    A.a[slot * 2 + 1] = x.d.a[1];
+    A.r[slot] = mc ? ret : x.rew;
+    A.done[slot] = mc ? 1 : 0;
+}
+
 static int fs_params(const shems_foresight_grid *grid, const char *fn, FsParams &g)
 {
     if (!grid) return set_error(SHEMS_ERR_ARG, "%s: grid is NULL", fn);
@@ -797,4 +915,45 @@ extern "C" int shems_foresight_demos_dev(const float *d_tables, int64_t total_ro
     a.capacity = ring->capacity; a.pos = pos; a.status = d_status;
     hipLaunchKernelGGL(k_fs_demos, dim3((unsigned)((T + kFsThreads - 1) / kFsThreads), (unsigned)n_pass), dim3(kFsThreads), 0, st, a);
     return hip_ok(hipGetLastError(), "k_fs_demos launch");
+}
+
+extern "C" int shems_foresight_transitions_dev(const float *d_tables, int64_t total_rows, const shems_foresight_problem *d_problems,
+                                               int32_t n_problems, int32_t T, const double *d_results, int32_t n_pass,
+                                               const int32_t *d_problem_of_pass, int32_t mode, float gamma, int32_t tail, double *d_returns,
+                                               const shems_replay *ring, int64_t pos, int32_t *d_status, void *stream)
+{
+    const char *fn = "shems_foresight_transitions_dev";
+    if (T < 2) return set_error(SHEMS_ERR_ARG, "%s: T = %d; a transition needs a successor hour, so a pass is at least 2 hours", fn, (int)T);
+    if (tail < 1 || tail >= T) return set_error(SHEMS_ERR_ARG, "%s: tail = %d lies outside 1 .. T - 1 = %d", fn, (int)tail, (int)T - 1);
+    if (mode != SHEMS_FS_TRANS_TD && mode != SHEMS_FS_TRANS_MC) return set_error(SHEMS_ERR_ARG, "%s: mode = %d is neither TD (0) nor MC (1)", fn, (int)mode);
+    if (mode == SHEMS_FS_TRANS_MC && !d_returns) return set_error(SHEMS_ERR_ARG, "%s: MC mode needs d_returns", fn);
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return set_error(SHEMS_ERR_ARG, "%s: gamma = %g lies outside [0, 1]", fn, (double)gamma);
+    if (!d_tables || total_rows < 2 || !d_problems || n_problems < 1)
+        return set_error(SHEMS_ERR_ARG, "%s: NULL buffer, fewer than 2 table rows, or no problem", fn);
+    if (n_pass < 1 || n_pass > 65535) return set_error(SHEMS_ERR_ARG, "%s: n_pass = %d; one call converts 1 .. 65535 passes", fn, (int)n_pass);
+    if (!d_results || !d_status) return set_error(SHEMS_ERR_ARG, "%s: NULL results or status buffer", fn);
+    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done)
+        return set_error(SHEMS_ERR_ARG, "%s: NULL ring, or a ring without all of s, a, r, s2 and done", fn);
+    const int keep = T - tail;
+    switch (fs_demo_check_ring(ring->capacity, pos, n_pass, keep)) {
+    case 1: return set_error(SHEMS_ERR_ARG, "%s: the ring's capacity is %lld", fn, (long long)ring->capacity);
+    case 2: return set_error(SHEMS_ERR_ARG, "%s: %d passes x %d hours are %lld transitions; the ring's capacity is %lld", fn, (int)n_pass, keep,
+                             (long long)n_pass * keep, (long long)ring->capacity);
+    case 3: return set_error(SHEMS_ERR_ARG, "%s: pos = %lld lies outside the ring of %lld slots", fn, (long long)pos, (long long)ring->capacity);
+    default: break;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = hip_ok(hipMemsetAsync(d_status, 0, (size_t)n_pass * sizeof(int32_t), st), "hipMemsetAsync(status)")) return rc;
+    FsTransArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.tables = d_tables; a.total_rows = total_rows; a.prob = d_problems; a.n_prob = n_problems; a.problem_of_pass = d_problem_of_pass;
+    a.T = T; a.tail = tail; a.mode = mode; a.gamma = gamma; a.results = d_results; a.returns = d_returns;
+    a.s = ring->s; a.a = ring->a; a.r = ring->r; a.s2 = ring->s2; a.done = ring->done;
+    a.capacity = ring->capacity; a.pos = pos; a.status = d_status;
+    if (d_returns) {
+        hipLaunchKernelGGL(k_fs_returns, dim3((unsigned)n_pass), dim3(64), 0, st, a);
+        if (int rc = hip_ok(hipGetLastError(), "k_fs_returns launch")) return rc;
+    }
+    hipLaunchKernelGGL(k_fs_transitions, dim3((unsigned)((keep + kFsThreads - 1) / kFsThreads), (unsigned)n_pass), dim3(kFsThreads), 0, st, a);
+    return hip_ok(hipGetLastError(), "k_fs_transitions launch");
 }

@@ -231,6 +231,80 @@ SHEMS_HD int fs_demo_check_ring(int64_t capacity, int64_t pos, int64_t n_pass, i
     return 0;
 }
 
+// ---- transitions from tracked passes (shems_foresight_transitions_dev; tests/warmstart_ref.py restates it) ----
+// The rows of a DRL-mode pass hold everything a replay slot holds: every (pass, hour) with a successor becomes (s, a, r, s', done).
+//   s, s2   the observations of fs_demo_hour for rows t and t + 1: the `pre` state of the next row IS the state after this step;
+//   a       (fs_demo_label((float)r[21]), fs_demo_label((float)r[2])): columns 21 (B_target) and 2 (EV_target) hold the two targets
+//           after scale_action (write_results, csrc/shems_env_dev.h).  Rows of a RULE-BASED pass record targets 0 and kWh set-points
+//           there: they would give wrong actions, and nothing here can tell them apart;
+//   rew     (float)r[5], as the fused step converts the reward before ring_push.
+// The hour is refused if the row check of hour t or of hour t + 1 fails, or r[5] is not finite.
+// Return-to-go of a pass, float64, sequentially from the end, g = (double)gamma:
+//   G[T - 1] = r[T - 1][5];   G[t] = r[t][5] + g * G[t + 1]      (the product rounded, then the sum: fs_return_step)
+// This order is the definition.  Env and tracked policy are deterministic, so G[t] is the exact Q^pi(s_t, a_t) of the controller that
+// made the pass -- up to the hours the end of the pass cuts off, which is what `tail` is for.
+//   SHEMS_FS_TRANS_TD   the slot holds (s, a, rew, s2, done = 0): the bytes the reference's `remember` would store;
+//   SHEMS_FS_TRANS_MC   the slot holds (s, a, (float)G[t], s2, done = 1): the update forms y = r + gamma (1 - done) q' = G[t] exactly.
+// tail (1 <= tail < T): hours t >= T - tail give no transition; G still sums over all T hours.  (pass e, hour t) goes to slot
+// fs_demo_slot(pos, e, T - tail, t, capacity).  TD: a refused hour leaves its slot alone, the rest of the pass is written.  MC: a pass
+// ANY of whose T hours fails its row check or has a non-finite reward gives no transition at all (fs_returns_hour_ok) and its row of
+// returns is fs_returns_refused() in every hour.  That NaN in G[e][0] is also the per-pass verdict the transitions kernel reads: an
+// accepted pass cannot produce one (its rewards are finite; with g > 0 an overflow gives an infinity, which r + g * inf keeps, and
+// with g = 0 nothing is carried).
+struct FsTransition {
+    FsDemo d;                        // s and a
+    float s2[SHEMS_NSTATE];
+    float rew;
+};
+
+SHEMS_HD bool fs_finite(double x) { return x - x == 0.0; }
+
+SHEMS_HD bool fs_transition_hour(const shems_foresight_problem &P, const float *tables, int64_t total_rows, const double *r, int t,
+                                 FsTransition &x)
+{
+    const float target[2] = {(float)r[21], (float)r[2]};
+    const FsParams none{};                                                          // targets are given: the action grid is not read
+    FsDemo next;
+    if (!fs_demo_hour(P, tables, total_rows, r, t, target, -1, none, x.d)) return false;
+    if (!fs_demo_hour(P, tables, total_rows, r + SHEMS_NRESULT, t + 1, target, -1, none, next)) return false;
+    if (!fs_finite(r[5])) return false;
+    for (int k = 0; k < SHEMS_NSTATE; ++k) x.s2[k] = next.s[k];
+    x.rew = (float)r[5];
+    return true;
+}
+
+// What the returns of a pass need of EVERY hour (MC's verdict).
+SHEMS_HD bool fs_returns_hour_ok(const shems_foresight_problem &P, const float *tables, int64_t total_rows, const double *r, int t)
+{
+    FsAuditHour h;
+    return fs_audit_hour(P, tables, total_rows, r, t, h) && fs_finite(r[5]);
+}
+
+SHEMS_HD double fs_return_step(double reward, double g, double G_next)
+{
+    const double carried = g * G_next;
+    return reward + carried;
+}
+
+SHEMS_HD double fs_returns_refused() { return __builtin_nan(""); }
+
+// The returns of one pass, serially (a host build; the device spreads the row checks over a wave and keeps this chain).  res: the T
+// rows of the pass, G: T float64 out.  False: the pass is refused and G holds fs_returns_refused().
+SHEMS_HD bool fs_returns(const shems_foresight_problem &P, const float *tables, int64_t total_rows, const double *res, int T, float gamma,
+                         double *G)
+{
+    const double g = (double)gamma;
+    bool ok = true;
+    for (int t = T - 1; t >= 0; --t) {
+        const double *r = res + (int64_t)t * SHEMS_NRESULT;
+        ok = fs_returns_hour_ok(P, tables, total_rows, r, t) && ok;
+        G[t] = t == T - 1 ? r[5] : fs_return_step(r[5], g, G[t + 1]);
+    }
+    if (!ok)
+        for (int t = 0; t < T; ++t) G[t] = fs_returns_refused();
+    return ok;
+}
+
 // ---- hedging over a forecast ENSEMBLE (shems_foresight_track_ensemble_dev; tests/foresight_ensemble_ref.py restates it) ----
 // The forecast controller above treats its one table as certain.  An ensemble problem is ONE truth (cfg, idx0) with K scenarios,
 // 1 <= K <= kFsMaxScen: scenario k is a forecast table in the sense above (forecast_off[k], same nrow, same row array) with a float64

@@ -102,6 +102,8 @@ def _declare():
     L.shems_ddpg_update.restype = C.c_int
     L.shems_ddpg_clone_update.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, vp, vp]
     L.shems_ddpg_clone_update.restype = C.c_int
+    L.shems_ddpg_critic_update.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, vp]
+    L.shems_ddpg_critic_update.restype = C.c_int
     L.shems_ddpg_critic_grad.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, vp]
     L.shems_ddpg_critic_grad_ex.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, i64, i64, vp]
     L.shems_ddpg_critic_grad_ex.restype = C.c_int
@@ -360,6 +362,7 @@ class Agent:
         self.bp_critic = [0.9, 0.999]
         self.updates = 0
         self.clones = 0                            # supervised updates on demonstrations (clone); they advance bp_actor, not `updates`
+        self.evaluations = 0                       # critic-only updates (evaluate); they advance bp_critic, not `updates`
         self.sync = GradSync(None)                 # replicas exchange gradients through this (RCCL)
         self.dp_overlap = False                    # data parallel: True = the critic's gradient all-reduce runs asynchronously under the actor's E
                                                    # products (shems_ddpg_actor_prepare); False = everything in program order (same bits).
@@ -723,6 +726,33 @@ class Agent:
                                                    C.c_void_p(publish.data_ptr()) if publish is not None else None, self._stream()))
         self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
         self.clones += 1
+
+    def evaluate(self, ring, tick=None, tau=None):
+        """One CRITIC-ONLY update (policy evaluation) from `ring`: update_model!(critic, ...) and soft_update!(critic_target, critic) of
+        replay() (DDPG.jl:131-137, 143) with the actor left alone (shems_ddpg_critic_update: three launches; actor, actor_t, their
+        moments, grad_actor and losses[1] are not touched).  The targets are the update's own, y = r + gamma (1 - done) critic_t(s',
+        actor_t(s')): on a ring of imitation.transitions(mode="mc") (done = 1, r = the return-to-go) that is regression on fixed
+        targets, and losses[0] is the calibration error of the critic on the minibatch.  bp_critic advances as in replay(); the step
+        counts in `evaluations` (the default tick), `updates` and `clones` do not move.  tau: the soft update's, None = the agent's.
+        It leaves the bits of _critic_grad_ex + _critic_apply.  Networks up to (250, 500), batch <= 128, one replica."""
+        if self.wide or is_wide(self.hidden):
+            raise NotImplementedError(f"evaluate: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no critic-only update")
+        if self.batch > self.MAX_PASS_BATCH:
+            raise NotImplementedError(f"evaluate: BATCH_SIZE = {self.batch}; the critic-only update holds at most {self.MAX_PASS_BATCH} columns")
+        if self.sync.world > 1:
+            raise NotImplementedError("evaluate: data-parallel replicas do not exchange the critic-only gradient")
+        if getattr(self, "_before_param_write", None) is not None:
+            raise NotImplementedError("evaluate: a learner of a learner group keeps its own working layout")
+        self._same_device(None, ring)
+        d = self._ddpg_args()
+        if tau is not None:
+            d.tau = float(tau)
+        rs = ring.struct()
+        tick = self.evaluations if tick is None else tick
+        _capi.check(self.L.shems_ddpg_critic_update(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_crit,
+                                                    self.bp_critic[0], self.bp_critic[1], self._stream()))
+        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
+        self.evaluations += 1
 
     def sample_indices(self, tick, ring_len, batch=None):
         batch = self.batch if batch is None else int(batch)

@@ -10,7 +10,15 @@ can such an actor hold at all?  Three pieces answer it, all on the GPU:
   * the supervised update: ddpg.Agent.clone, loss = Flux.mse(actor(normalize(s)), a_demo) (shems_ddpg_clone_update, three launches);
   * dagger: round 0 clones the foresight pass, every later round runs the current actor, labels the states it visited and trains on.
 
-Nothing here seeds the DDPG ring or pre-trains the critic: DDPG fine-tuning after cloning starts from an untrained critic.
+A cloned actor with a freshly initialised critic forgets what cloning taught it: the first actor gradients of DDPG come from a critic
+that knows nothing.  Three more pieces join the two (the definition: fs_transition_hour and fs_returns in the same header):
+
+  * transitions: the rows of a DRL-mode pass become full replay slots (s, a, r, s', done) (shems_foresight_transitions_dev), either
+    as the reference's `remember` would store them ("td") or with the discounted return-to-go of the pass as the reward and done = 1
+    ("mc"): env and tracked policy are deterministic, so that return is the exact Q of the controller that made the pass, and a
+    critic can be regressed on it without bootstrapping from itself;
+  * the critic-only update: ddpg.Agent.evaluate (shems_ddpg_critic_update, three launches, the actor is left alone);
+  * warm_start: dagger, one pass of the resulting actor, its transitions, and a number of critic-only updates on them.
 """
 from __future__ import annotations
 
@@ -36,6 +44,9 @@ def _declare(L):
     L.shems_foresight_demos_dev.argtypes = [vp, i64, vp, i32, C.POINTER(foresight.GridStruct), i32, vp, i32, vp, vp, vp,
                                             C.POINTER(_capi.Replay), i64, vp, vp]
     L.shems_foresight_demos_dev.restype = C.c_int
+    L.shems_foresight_transitions_dev.argtypes = [vp, i64, vp, i32, i32, vp, i32, vp, i32, C.c_float, i32, vp, C.POINTER(_capi.Replay), i64,
+                                                  vp, vp]
+    L.shems_foresight_transitions_dev.restype = C.c_int
     return L
 
 
@@ -145,7 +156,123 @@ def dagger(agent, env, values, demos, rounds, steps_per_round, tau=1.0):
     return out
 
 
+TRANSITION_MODES = {"td": 0, "mc": 1}                        # SHEMS_FS_TRANS_TD / SHEMS_FS_TRANS_MC
+
+
+def default_tail(mode, gamma, T):
+    """td: 1, every hour that has a successor.  mc: the smallest k with gamma^k <= 0.01, capped at T - 1 -- the hours whose return the
+    end of the pass cuts short by more than a hundredth of its weight are dropped."""
+    if mode == "td":
+        return 1
+    k, w = 1, float(gamma)
+    while w > 0.01 and k < T - 1:
+        k, w = k + 1, w * float(gamma)
+    return k
+
+
+def transitions(values, results, ring, problem_of_pass=None, mode="td", gamma=None, tail=None):
+    """Full transitions (s, a, r, s', done) of n tracked passes ([n][T][23] or [T][23] host rows) into `ring` from its push position:
+    one C call on PyTorch's current stream (shems_foresight_transitions_dev), one copy back of the status words.
+      mode "td"   the slot holds (s, a, float32 reward, s', 0), the bytes `remember` would store: the ring can go straight on as the
+                  replay ring of episode_ / run_episodes;
+      mode "mc"   the slot holds (s, a, float32 G[t], s', 1) with G the discounted return-to-go of the pass in float64
+                  (G[T - 1] = r[T - 1], G[t] = r[t] + gamma G[t + 1]): the update's target is G[t] itself.  Such slots must never meet
+                  bootstrapped training (done = 1 would cut every target short): keep them in a ring of their own.
+    tail: hours t >= T - tail give no transition (default_tail); n * (T - tail) must fit the capacity.  gamma: ddpg.GAMMA.
+    `values`: a Values or an EnsembleValues, of which only the problems and the tables are read; problem_of_pass names the problem.
+    The rows must come from DRL-mode passes (an actor's, the foresight controller's): a RULE-BASED pass records no targets (columns
+    21 and 2 hold 0 and kWh set-points), its actions would be wrong, and nothing checks it.
+    Raises BoundsError naming the first refused pass and leaves ring.pushed alone; otherwise ring.pushed grows by n * (T - tail).
+    Returns the returns [n][T] float64 in "mc" mode, None in "td" mode."""
+    import torch
+    from . import ddpg
+    if mode not in TRANSITION_MODES:
+        raise ValueError(f"transitions: mode {mode!r} is neither 'td' nor 'mc'")
+    ens = values if isinstance(values, foresight.EnsembleValues) else None
+    inner = ens.values if ens is not None else values
+    res = np.ascontiguousarray(results, np.float64)
+    if res.ndim == 2:
+        res = res[None]
+    T = inner.nsteps
+    if res.ndim != 3 or res.shape[1] != T or res.shape[2] != _capi.NRESULT:
+        raise ValueError(f"results must be [n][{T}][{_capi.NRESULT}], not {tuple(res.shape)}")
+    n = int(res.shape[0])
+    gamma = ddpg.GAMMA if gamma is None else float(gamma)
+    tail = default_tail(mode, gamma, T) if tail is None else int(tail)
+    po = None if problem_of_pass is None else np.ascontiguousarray(problem_of_pass, np.int32).reshape(n)
+    if ens is not None and po is not None:
+        po = po * ens.n_scen                                 # the first record of the problem: every scenario shares its truth
+    L = _declare(_capi.lib())
+    dev = ring.s.device
+    env = inner._tables if hasattr(inner._tables, "use_torch_stream") else None          # a ShemsBatch, or the uploaded tensor
+    if env is not None:
+        env.use_torch_stream()
+        tab_ptr = env.view().tables
+    else:
+        tab_ptr = inner._tables.data_ptr()
+    d_res = torch.from_numpy(res).to(dev)
+    d_po = torch.from_numpy(po).to(dev) if po is not None else None
+    d_ret = torch.empty((n, T), dtype=torch.float64, device=dev) if mode == "mc" else None
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    rs = ring.struct()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _capi.check(L.shems_foresight_transitions_dev(C.c_void_p(tab_ptr), int(inner.total_rows), C.c_void_p(inner.d_problems.data_ptr()),
+                                                  inner.n_problems, T, ptr(d_res), n, ptr(d_po), TRANSITION_MODES[mode], gamma, tail,
+                                                  ptr(d_ret), C.byref(rs), ring.pos, ptr(status),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    st = status.cpu().numpy()                                # the call's one synchronisation
+    bad = np.nonzero(st)[0]
+    if bad.size:
+        e = int(bad[0])
+        raise _capi.BoundsError(int(st[e]), f"transitions: pass {e}: a row does not sit on its problem's table rows, a reward is not finite, or "
+                                f"it names none of the {inner.n_problems} problems; the ring's length is unchanged")
+    ring.pushed += n * (T - tail)
+    return d_ret.cpu().numpy() if d_ret is not None else None
+
+
+def warm_start(agent, env, values, demos, ring, rounds, steps_per_round, critic_steps, mode="mc", tau=1.0):
+    """A cloned actor AND a critic that knows it: dagger(agent, env, values, demos, rounds, steps_per_round, tau) as it stands, then
+    one pass of the resulting actor (harness.inference), its transitions into `ring` in `mode`, and `critic_steps` critic-only updates
+    (agent.evaluate) on that ring.  The normalisation is the one dagger set from the foresight pass; agent.min_max_buffer(ring) would
+    run only if dagger had not set one.  Everything goes on PyTorch's current stream.
+    With mode "td" the same ring can go straight on as the agent's replay ring for episode_ / run_episodes.  With "mc" its slots carry
+    done = 1 and a return as the reward: bootstrapped training must never sample them (every target would be cut to r, with r a
+    return), so the caller seeds a second "td" ring (transitions(..., mode="td")) for the fine-tuning.
+    Returns dagger's per-round records followed by one dict {"critic_loss_first", "critic_loss_last", "transitions"}: losses[0]
+    after the first and the last critic step, and the ring's length."""
+    from . import harness
+    critic_steps = int(critic_steps)
+    if critic_steps < 1:
+        raise ValueError(f"warm_start: {critic_steps} critic steps; at least one")
+    if mode not in TRANSITION_MODES:
+        raise ValueError(f"warm_start: mode {mode!r} is neither 'td' nor 'mc'")
+    out = dagger(agent, env, values, demos, rounds, steps_per_round, tau=tau)
+    _, res = harness.inference(env, agent, track=1, num_steps=values.nsteps)
+    _, _, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+    transitions(values, res, ring, poe[:1] if values.n_problems > 1 else None, mode=mode, gamma=agent.gamma)
+    first = last = None
+    for k in range(critic_steps):
+        agent.evaluate(ring)
+        if k == 0 or k == critic_steps - 1:
+            last = float(agent.losses[0].item())
+            first = last if k == 0 else first
+    return out + [{"critic_loss_first": first, "critic_loss_last": last, "transitions": len(ring)}]
+
+
 IMITATION_HEADER = ["round", "return", "loss", "demos"]
+WARMSTART_HEADER = ["critic_loss_first", "critic_loss_last"]
+
+
+def write_to_warmstart_file(figures, path):
+    """warm_start's critic figures (its last record) as a CSV beside the imitation file."""
+    import csv
+    import os
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(WARMSTART_HEADER)
+        w.writerow([repr(float(figures[k])) for k in WARMSTART_HEADER])
+    return path
 
 
 def write_to_imitation_file(rounds, path):

@@ -30,6 +30,8 @@ Differences that follow from the platform, all explicit:
     that hedges over the analog ensemble of those lags with equal weights (foresight.solve_ensemble): ..._foresight_h24_a24-48-72.csv;
     SHEMS_FORESIGHT_IMITATE=<rounds>x<steps> (needs SHEMS_FORESIGHT=1) trains a fresh actor by imitation of the foresight pass
     (imitation.dagger) and writes its per-round figures to ..._results_<case>_imitation.csv;
+    SHEMS_FORESIGHT_WARMSTART=<critic_steps>[:td|:mc] (needs SHEMS_FORESIGHT_IMITATE) then fits the same agent's critic on the
+    transitions of one pass of the cloned actor (imitation.warm_start) and writes ..._results_<case>_warmstart.csv;
     SHEMS_FORESIGHT_REGRET=1 (needs SHEMS_FORESIGHT=1) adds one <results file>_regret.csv next to every results file of the tracking
     block -- the hourly regret of that pass against ONE perfect-foresight solve (harness.regret_of; the forecast passes are audited
     against the truth like the rest);
@@ -247,6 +249,33 @@ def foresight_imitate(environ=os.environ):
     return rounds, steps
 
 
+def foresight_warmstart(environ=os.environ):
+    """SHEMS_FORESIGHT_WARMSTART=<critic_steps>[:td|:mc] -> (critic_steps >= 1, mode; "mc" when none is named): after the imitation
+    block the SAME agent's critic is fitted by that many critic-only updates on the transitions of one pass of the cloned actor
+    (imitation.warm_start); critic_loss_first and critic_loss_last go to ..._results_<case>_warmstart.csv beside the imitation file.
+    None when unset.  It needs SHEMS_FORESIGHT_IMITATE; a malformed value is refused by name."""
+    raw = environ.get("SHEMS_FORESIGHT_WARMSTART")
+    if raw is None:
+        return None
+    if environ.get("SHEMS_FORESIGHT_IMITATE") is None:
+        raise ValueError("SHEMS_FORESIGHT_WARMSTART is set without SHEMS_FORESIGHT_IMITATE")
+    parts = raw.lower().split(":")
+    try:
+        steps = int(parts[0])
+    except ValueError:
+        steps = None
+    if steps is None or len(parts) > 2 or (len(parts) == 2 and parts[1] not in ("td", "mc")):
+        raise ValueError(f"SHEMS_FORESIGHT_WARMSTART = {raw!r} is not <critic_steps>[:td|:mc]")
+    if steps < 1:
+        raise ValueError(f"SHEMS_FORESIGHT_WARMSTART = {raw!r}: at least one critic step")
+    return steps, parts[1] if len(parts) == 2 else "mc"
+
+
+def warmstart_file_name(job_id, run, case, out_dir="out/tracker"):
+    """The critic figures of SHEMS_FORESIGHT_WARMSTART, beside imitation_file_name's file."""
+    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_warmstart.csv")
+
+
 def imitation_file_name(job_id, run, case, out_dir="out/tracker"):
     """The per-round figures of SHEMS_FORESIGHT_IMITATE, beside harness.foresight_file_name's file."""
     return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_imitation.csv")
@@ -319,6 +348,7 @@ def main(environ=os.environ, cwd=".", log=print):
     forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
     regret = foresight_regret(environ)
     imitate = foresight_imitate(environ)
+    warmstart = foresight_warmstart(environ)
     if imitate is not None and (cfg.L1 > 250 or cfg.L2 > 500 or cfg.BATCH_SIZE > 128):
         raise ValueError(f"SHEMS_FORESIGHT_IMITATE: the supervised update holds networks up to (250, 500) and batches up to 128, not "
                          f"({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE}")
@@ -463,8 +493,17 @@ def main(environ=os.environ, cwd=".", log=print):
             pupil = D.Agent(seed=cfg.rng_run, hidden=(cfg.L1, cfg.L2))
             pupil.batch, pupil.eta_act = cfg.BATCH_SIZE, float(np.float32(cfg.eta_act))
             demos = imitation.Demos(imitate[0] * EP_LENGTH[cfg.season, cfg.run])
-            figures = imitation.dagger(pupil, env_track, values, demos, imitate[0], imitate[1])
+            if warmstart is None:
+                figures = imitation.dagger(pupil, env_track, values, demos, imitate[0], imitate[1])
+            else:                                                        # the same agent's critic fitted on a pass of the cloned actor
+                pupil.gamma, pupil.tau = float(np.float32(cfg.gamma)), float(np.float32(cfg.tau))
+                pupil.eta_crit = float(np.float32(cfg.eta_crit))
+                fitted = D.ReplayRing(EP_LENGTH[cfg.season, cfg.run])
+                *figures, critic = imitation.warm_start(pupil, env_track, values, demos, fitted, imitate[0], imitate[1], warmstart[0],
+                                                        mode=warmstart[1])
             written.append(imitation.write_to_imitation_file(figures, imitation_file_name(cfg.job_id, cfg.run, cfg.case)))
+            if warmstart is not None:
+                written.append(imitation.write_to_warmstart_file(critic, warmstart_file_name(cfg.job_id, cfg.run, cfg.case)))
     for e in (env_train, env_eval, env_track):
         e.close()
     log(f"Script with JOB_ID: {cfg.job_id} & TASK_ID: {cfg.task_id} is done!")
