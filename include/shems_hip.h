@@ -467,6 +467,21 @@ typedef struct shems_group_w2t {
 } shems_group_w2t;
 int shems_group_w2_to_tiled(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, void *stream);
 int shems_group_w2_to_flux(const shems_ddpg *d0, const shems_group *g, const shems_group_w2t *t, void *stream);
+/* The same working layout for a SINGLE learner.  In Flux order the 250 x 500 layer-2 state has a row pitch of 2 000 bytes and starts at
+ * byte 10 000 (actor) / 12 000 (critic) of its block, so every 128-byte row piece a 32 x 32 gradient tile of shems_ddpg_update reads and
+ * writes (m, v, parameter, target) straddles two lines; on tiles it is one (tools/micro/w2_single_layout.hip).
+ *   shems_ddpg_tiled_enter   copies the W2 ranges of d's eight blocks into the regions t (128-byte aligned, SHEMS_W2T_FLOATS each) on
+ *                            `stream` and records d's blocks: from here on the regions hold the current layer-2 state and the W2
+ *                            ranges of the Flux-order blocks are stale (the contract above).
+ *   shems_ddpg_tiled_leave   copies them back on `stream` and forgets the learner.
+ *   shems_ddpg_tiled_current *out = 1 between the two, else 0.
+ * Between enter and leave shems_ddpg_update (d_publish must be NULL), shems_act_step_dev and shems_train_steps' ordered loop, called
+ * with the same blocks, work on the regions and leave the bits the Flux-order form leaves.  Every other entry point that reads or
+ * writes one of the eight blocks in Flux order returns SHEMS_ERR_STATE and launches nothing.  The record is host state of the process,
+ * keyed by the blocks' addresses: leave before the blocks are freed. */
+int shems_ddpg_tiled_enter(const shems_ddpg *d, const shems_group_w2t *t, void *stream);
+int shems_ddpg_tiled_leave(const shems_ddpg *d, void *stream);
+int shems_ddpg_tiled_current(const shems_ddpg *d, int32_t *out);
 /* ------------------------------------------- per-learner hyper-parameters of a learner group -- */
 /* The thesis's experiment is a hyper-parameter grid (input09_08_on_01-09_eval.jl:62-106: BATCH, noise_act, (L1, L2), (eta_act,
  * eta_crit)).  With one record per learner -- a DEVICE array of g->count records, learner l's is d_hp[l] -- one group runs many grid

@@ -68,6 +68,12 @@ __host__ __device__ constexpr int off_w2(int in) { return in * H1N + H1N; }
 __host__ __device__ constexpr int off_b2(int in) { return off_w2(in) + H1N * H2N; }
 __host__ __device__ constexpr int off_w3(int in) { return off_b2(in) + H2N; }
 __host__ __device__ constexpr int off_b3(int in, int out) { return off_w3(in) + H2N * out; }
+// Tiled working layout of the layer-2 state (shems_group_w2t: [4 k-tiles][8 n-tiles][m | v | p | target][64][64] floats, pads zero): the
+// TILED instantiations below take W2[k][n], k < 256, n < 512, from ONE array of a region -- base = region + W2T_TILE * {0 m, 1 v, 2 p,
+// 3 target} -- at this index.  A 32-float row piece of a 32 x 32 sub-tile is one 128-byte line; in Flux order (row pitch 2 000 bytes, W2
+// at byte 10 000 / 12 000) every such piece straddles two.
+constexpr int W2T_TILE = 64 * 64;
+__device__ __forceinline__ int w2t_idx(int k, int n) { return ((k >> 6) * 8 + (n >> 6)) * (4 * W2T_TILE) + (k & 63) * 64 + (n & 63); }
 
 // ---- workspace carve (floats) --------------------------------------------------------------------
 constexpr int64_t WS_XT = 0;                         // [9][BP]  normalize(s)
@@ -394,6 +400,7 @@ struct FwdJob {
     float *P3;             // [NT][2][BP] layer-3 partials of this n-tile
     const float *d3q;      // QG: [BP] upstream gradient of q (-1/B, 0 in the pad columns)
     float *DAP;            // QG: [NT][2][BP] partial d loss / d a_pi
+    const float *W2t;      // TILED: this network's p or target array of the tiled region (see w2t_idx); W2 of P is stale then
 };
 struct FwdArgs { FwdJob job[3]; int64_t gstride; int prep; PrepArgs pa; };   // prep: 1 = this launch opens the update (K1), 2 = K4
 __device__ __forceinline__ void gshift(FwdJob &J, int64_t off)
@@ -421,7 +428,7 @@ template <bool QG> struct FwdShape {
     static constexpr int LDS = (256 * WST + W1K * 32 + W1K * W1C + 256 + 4 * 16 * 64 + 4 * 2 * 32 + (QG ? 32 * 32 + 4 * 2 * 32 : 0)) * 4;
 };
 
-template <int IN, int PREP, bool QG, bool CLONE = false>
+template <int IN, int PREP, bool QG, bool CLONE = false, bool TILED = false>
 __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const PrepArgs *pa, int bx, int job)
 {
     typedef FwdShape<QG> SH;
@@ -509,7 +516,8 @@ __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const Pre
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
         const int e = it * 256 + tid, k = e >> 3, c = e & 7;
-        wv[it] = *reinterpret_cast<const f32x4 *>(W2 + (int64_t)min(k, H1N - 1) * H2N + n0 + 4 * c);
+        if constexpr (TILED) wv[it] = *reinterpret_cast<const f32x4 *>(J.W2t + w2t_idx(k, n0 + 4 * c));      // (pad rows / columns: zeros)
+        else wv[it] = *reinterpret_cast<const f32x4 *>(W2 + (int64_t)min(k, H1N - 1) * H2N + n0 + 4 * c);
     }
     // ---- consume the layer-1 operands ----
     if (PREP == 1) {
@@ -675,6 +683,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int QG16_WST = 20;                                   // W2 panel row stride: 16-B aligned rows, both operand reads conflict-free
 constexpr int QG16_LDS = (256 * QG16_WST + W1K * 32 + W1K * W1C + 256 + 4 * 2 * 4 * 64 + 4 * 64 + 16 * 32 + 4 * 2 * 2 * 64) * 4;
 
+template <bool TILED = false>
 __device__ __forceinline__ void qg16_body(const FwdJob &J, float *smem, int bx)
 {
     constexpr bool wt = false;                 // (round 3's merged K4 + K5 launch stored these write-through; removed in round 4, see WS_SYNC)
@@ -705,7 +714,8 @@ __device__ __forceinline__ void qg16_body(const FwdJob &J, float *smem, int bx)
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int e = it * 256 + tid, k = e >> 2, c4 = e & 3;
-        wv[it] = *reinterpret_cast<const f32x4 *>(W2 + (int64_t)min(k, H1N - 1) * H2N + n0 + 4 * c4);
+        if constexpr (TILED) wv[it] = *reinterpret_cast<const f32x4 *>(J.W2t + w2t_idx(k, n0 + 4 * c4));
+        else wv[it] = *reinterpret_cast<const f32x4 *>(W2 + (int64_t)min(k, H1N - 1) * H2N + n0 + 4 * c4);
     }
     xt_store<CIN>(J.x, xr, mbase, xs, ntile == 0, wt);        // (the four column tiles of n-tile 0 publish actor(s) between them)
     pack_w1m_store(pk, CIN, w1);
@@ -876,10 +886,12 @@ struct EJob {
     int in, out, col;      // col = j
     const float *H2;       // [500][BP]
     float *EP;             // [NQ][250][BP]
+    const float *W2t;      // TILED: the network's p array of the tiled region
 };
 struct MidArgs { FwdJob fwd; EJob e[3]; int64_t gstride; int nfwd; };
 constexpr int E_LDS = (NQW * BP + 32 * (NQW + 1) + NQW) * 4;
 
+template <bool TILED = false>
 __device__ __forceinline__ void e_body(const EJob &E, int b, float *smem)
 {
     float *Bt = smem;                          // [64 n][128 m]  M panel
@@ -897,7 +909,8 @@ __device__ __forceinline__ void e_body(const EJob &E, int b, float *smem)
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int e = u * 256 + tid, kl = e >> 6, nl = e & 63, k = kt * 32 + kl, n = nb + nl;
-        wvp[u] = W2p[(int64_t)min(k, H1N - 1) * H2N + min(n, H2N - 1)];     // clamped copies: rows k >= 250 are never stored, columns
+        if constexpr (TILED) wvp[u] = E.W2t[w2t_idx(k, n)];                   // (a block's 64 columns: one row of one tile, 256 contiguous bytes)
+        else wvp[u] = W2p[(int64_t)min(k, H1N - 1) * H2N + min(n, H2N - 1)];     // clamped copies: rows k >= 250 are never stored, columns
                                                                               // n >= 500 meet the zero rows of the M panel below
     }
     w3v = P[off_w3(E.in) + min(nb + min(tid, NQW - 1), H2N - 1) * E.out + E.col];
@@ -1223,6 +1236,7 @@ struct GradArgs {
     shems_ddpg dd;         // for the heads
     AdamCtx c;
     int64_t gstride;       // learner groups: byte stride between learners (0 = single learner)
+    float *w2t;            // TILED: the network's tiled region; the W2 ranges of c.mt / c.vt / c.p / c.target are stale then
 };
 __device__ __forceinline__ void gshift(GradArgs &B, int64_t off)
 {
@@ -1293,7 +1307,7 @@ __device__ __forceinline__ void l1row_wave(const L1Row<IN, OUT> &R, const float 
 }
 
 // CLONE: the supervised update's instantiation (k_grad_clone) takes the cloning head at compile time; otherwise GradArgs.head decides.
-template <int IN, int OUT, bool CLONE = false>
+template <int IN, int OUT, bool CLONE = false, bool TILED = false>
 __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx)
 {
     // bx: this workgroup's index within the gradient grid
@@ -1350,8 +1364,17 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
     constexpr int WOWN = 4;                     // elements of gW2 a lane finishes and owns
     float hv[HVN];
     int widx[WOWN];
+    [[maybe_unused]] int tidx[WOWN];            // TILED: the same elements in the region's arrays (the gradient block stays in Flux order)
+    [[maybe_unused]] AdamCtx cw;
+    if constexpr (TILED) {
+        cw = A.c;
+        cw.mt = A.w2t; cw.vt = A.w2t + W2T_TILE; cw.p = A.w2t + 2 * W2T_TILE; cw.target = A.w2t + 3 * W2T_TILE; cw.publish = nullptr;
+    }
 #pragma unroll
-    for (int r = 0; r < WOWN; ++r) widx[r] = -1;
+    for (int r = 0; r < WOWN; ++r) {
+        widx[r] = -1;
+        if constexpr (TILED) tidx[r] = -1;
+    }
     AdamRegs<WOWN> ar;
     if (is_w) {
 #pragma unroll
@@ -1361,8 +1384,10 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
             // wave w finishes the 16 x 16 block (k half w >> 1, n half w & 1), D[i = 4 g + r][j = c], r < 4
             const int k = kt * 32 + 16 * (wave >> 1) + 4 * (lane >> 4) + r, n = nt * GR_WN + 16 * (wave & 1) + (lane & 15);
             widx[r] = (k < H1N && n < H2N) ? off_w2(IN) + k * H2N + n : -1;
+            if constexpr (TILED) tidx[r] = (k < H1N && n < H2N) ? w2t_idx(k, n) : -1;
         }
-        adam_load<WOWN>(A.c, widx, ar);         // moments, parameter, target: requested with the first burst, consumed after the tile (requested
+        if constexpr (TILED) adam_load<WOWN>(cw, tidx, ar);
+        else adam_load<WOWN>(A.c, widx, ar);        // moments, parameter, target: requested with the first burst, consumed after the tile (requested
                                                 // BEHIND the head's loads instead, round 4: 36.9 against 36.2 us per update -- slower)
     }
     XRegs<IN> xr;
@@ -1446,7 +1471,8 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
                 if (widx[r] >= 0) gW2[widx[r] - off_w2(IN)] = val[r];
             }
             STAMP(kRegion, 6);
-            if (fz) adam_apply<WOWN>(*fz, widx, val, ar);
+            if constexpr (TILED) { if (fz) adam_apply<WOWN>(cw, tidx, val, ar); }
+            else if (fz) adam_apply<WOWN>(*fz, widx, val, ar);
             STAMP(kRegion, 7);
         }
     } else {
@@ -1592,6 +1618,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     grad_body<SIN, 2, true>(A, smem, (int)blockIdx.x);
 }
 
+// replay() of a single learner on the tiled working layout (shems_ddpg_tiled_enter): the three kernels with W2, its moments and its
+// target taken from the regions (FwdJob.W2t / EJob.W2t / GradArgs.w2t) -- the same workgroups, tiles, summation orders and ADAM
+// function, so the bits of k_fwd / k_mid / k_grad.  Instantiations of their own, behind the others (see k_fwd_clone).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_fwd_t(FwdArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int kPerJob = NT * (BP / 32) + 6;
+    const int job = A.prep == 1 ? (int)blockIdx.x / kPerJob : 0, bx = (int)blockIdx.x - job * kPerJob;
+    const FwdJob J = job == 0 ? A.job[0] : job == 1 ? A.job[1] : A.job[2];
+    if (A.prep == 1) {
+        const PrepArgs pa = A.pa;
+        if (J.in == SIN) fwd_body<SIN, 1, false, false, true>(J, smem, &pa, bx, job); else fwd_body<CIN, 1, false, false, true>(J, smem, &pa, bx, job);
+        return;
+    }
+    qg16_body<true>(J, smem, bx);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_mid_t(MidArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if ((int)blockIdx.x < A.nfwd) {
+        const FwdJob J = A.fwd;
+        fwd_body<CIN, 0, false, false, true>(J, smem, nullptr, (int)blockIdx.x, 0);
+        return;
+    }
+    const int e = (int)blockIdx.x - A.nfwd;
+    const int set = e / (KT * NQ);
+    const EJob E = set == 0 ? A.e[0] : set == 1 ? A.e[1] : A.e[2];
+    e_body<true>(E, e % (KT * NQ), smem);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_grad_t(GradArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (A.in == SIN) grad_body<SIN, 2, false, true>(A, smem, (int)blockIdx.x); else grad_body<CIN, 1, false, true>(A, smem, (int)blockIdx.x);
+}
+
 constexpr int FWD_LDS = FwdShape<false>::LDS, QG_LDS = FWD_LDS > QG16_LDS ? FWD_LDS : QG16_LDS;
 constexpr int MID_LDS = FWD_LDS > E_LDS ? FWD_LDS : E_LDS;
 static_assert(QG_LDS <= 160 * 1024, "one workgroup's LDS");
@@ -1611,12 +1672,59 @@ static int set_lds_attrs_clone()
     if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_clone), GR_LDS, "attr k_grad_clone")) return rc;
     return SHEMS_OK;
 }
+static int set_lds_attrs_tiled()
+{
+    static std::atomic<uint64_t> m_fwd{0}, m_mid{0}, m_grad{0};
+    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_t), QG_LDS, "attr k_fwd_t")) return rc;
+    if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid_t), MID_LDS, "attr k_mid_t")) return rc;
+    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_t), GR_LDS, "attr k_grad_t")) return rc;
+    return SHEMS_OK;
+}
+
+// ---- single learners on the tiled working layout: who they are ------------------------------------------------------------------
+// shems_ddpg_tiled_enter records a learner's eight Flux-order blocks (parameters, targets, moments) with its regions; until
+// shems_ddpg_tiled_leave the W2 ranges of those blocks are stale.  Every entry point that would read or write such a block in Flux
+// order asks here first (check_ddpg below, check_act in shems_policy.hip, the group and wide entry points) and returns SHEMS_ERR_STATE;
+// shems_ddpg_update and shems_act_step_dev take the regions from here instead.  Host state only, a handful of entries.
+namespace {
+struct TiledLearner { const float *blk[8]; shems_group_w2t t; };
+TiledLearner g_tiled[16];
+int g_ntiled = 0;
+std::atomic_flag g_tiled_lock = ATOMIC_FLAG_INIT;
+struct TiledGuard {
+    TiledGuard() { while (g_tiled_lock.test_and_set(std::memory_order_acquire)) {} }
+    ~TiledGuard() { g_tiled_lock.clear(std::memory_order_release); }
+};
+int tiled_find(const float *block)
+{
+    for (int i = 0; i < g_ntiled; ++i)
+        for (const float *b : g_tiled[i].blk)
+            if (b == block) return i;
+    return -1;
+}
+}  // namespace
+bool w2t_lookup(const float *block, shems_group_w2t *out)
+{
+    if (!block) return false;
+    TiledGuard lock;
+    const int i = tiled_find(block);
+    if (i >= 0 && out) *out = g_tiled[i].t;
+    return i >= 0;
+}
+int w2t_flux_guard(const float *block, const char *fn)
+{
+    if (!w2t_lookup(block, nullptr)) return SHEMS_OK;
+    return set_error(SHEMS_ERR_STATE, "%s: this learner's layer-2 state lives in its tiled regions (shems_ddpg_tiled_enter); call "
+                                      "shems_ddpg_tiled_leave before a Flux-order entry point", fn);
+}
 
 }  // namespace shems
 
 using namespace shems;
 
-static int check_ddpg(const shems_ddpg *d, const char *fn)
+// t: where the caller reads the layer-2 state from the tiled regions (shems_ddpg_update); every other caller speaks Flux order and is
+// refused while the regions are current.
+static int check_ddpg(const shems_ddpg *d, const char *fn, const shems_group_w2t *t = nullptr)
 {
     if (!d || !d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic ||
         !d->v_critic || !d->grad_actor || !d->grad_critic || !d->s_min || !d->s_max || !d->ws || !d->losses)
@@ -1624,6 +1732,9 @@ static int check_ddpg(const shems_ddpg *d, const char *fn)
     if (d->batch < 1 || d->batch > BP) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
     for (const float *p : {d->actor, d->critic, d->actor_t, d->critic_t})
         if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks must be 16-byte aligned", fn);
+    if (t) return set_lds_attrs_tiled();
+    for (const float *p : {d->actor, d->critic, d->actor_t, d->critic_t, d->m_actor, d->v_actor, d->m_critic, d->v_critic})
+        if (int rc = w2t_flux_guard(p, fn)) return rc;
     return set_lds_attrs();
 }
 
@@ -1669,9 +1780,10 @@ static int actor_e_launch(const shems_ddpg *d, unsigned L, int64_t gs, hipStream
 
 static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                        int64_t excl_pos, int64_t excl_count, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream,
-                       bool critic_only = false)
+                       bool critic_only = false, const shems_group_w2t *t = nullptr)
 {
-    if (int rc = check_ddpg(d, "shems_ddpg_critic_grad")) return rc;
+    // t: a single learner on the tiled working layout (L == 1, fused): W2 / moments / targets from the regions, the *_t kernels
+    if (int rc = check_ddpg(d, "shems_ddpg_critic_grad", t)) return rc;
     if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
         return set_error(SHEMS_ERR_ARG, "shems_ddpg_critic_grad: bad replay ring / length");
     if (excl_count < 0 || excl_pos < 0 || (excl_count > 0 && (ring_len != ring->capacity || excl_count >= ring_len)))
@@ -1693,8 +1805,10 @@ static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ri
     f.job[2] = FwdJob{nullptr, d->actor, SIN, 2, 2, none, SA + SL_H2, SA + SL_P3, nullptr, nullptr};
     f.prep = 1;
     f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count};
+    if (t) { f.job[0].W2t = t->actor + 3 * W2T_TILE; f.job[1].W2t = t->critic + 2 * W2T_TILE; f.job[2].W2t = t->actor + 2 * W2T_TILE; }
     // + 6 publishing workgroups per job (see fwd_body); they do their work in job 0, so the critic-only update drops job 2 whole
-    hipLaunchKernelGGL(k_fwd, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
+    if (t) hipLaunchKernelGGL(k_fwd_t, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
+    else hipLaunchKernelGGL(k_fwd, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
     // K2: critic_target on [s'; actor_target(s')] | E of the critic | E of the actor's two outputs
     MidArgs m;
     std::memset(&m, 0, sizeof m);
@@ -1703,22 +1817,29 @@ static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ri
     m.e[0] = EJob{d->critic, CIN, 1, 0, SC + SL_H2, SC + SL_EP};
     m.e[1] = EJob{d->actor, SIN, 2, 0, SA + SL_H2, SA + SL_EP};
     m.e[2] = EJob{d->actor, SIN, 2, 1, SA + SL_H2, ws + WS_EA1};
+    if (t) {
+        m.fwd.W2t = t->critic + 3 * W2T_TILE; m.e[0].W2t = t->critic + 2 * W2T_TILE;
+        m.e[1].W2t = m.e[2].W2t = t->actor + 2 * W2T_TILE;
+    }
     const bool defer_ea = critic_only || (!fuse && (d->flags & SHEMS_DDPG_DEFER_ACTOR_E) != 0);   // the caller runs shems_ddpg_actor_prepare later, or never
-    hipLaunchKernelGGL(k_mid, dim3(fgx + (defer_ea ? 1 : 3) * KT * NQ, 1, L), dim3(256), MID_LDS, st, m);
+    if (t) hipLaunchKernelGGL(k_mid_t, dim3(fgx + (defer_ea ? 1 : 3) * KT * NQ, 1, L), dim3(256), MID_LDS, st, m);
+    else hipLaunchKernelGGL(k_mid, dim3(fgx + (defer_ea ? 1 : 3) * KT * NQ, 1, L), dim3(256), MID_LDS, st, m);
     // K3: critic gradient (+ ADAM + soft update)
     GradArgs g;
     std::memset(&g, 0, sizeof g);
     g.w1t = w1t_of(ws, SLOT_CRITIC); g.P = d->critic; g.in = CIN; g.out = 1; g.x = x_sa; g.H2 = SC + SL_H2; g.w3f = ws + WS_FW3C;
     g.grad = d->grad_critic; g.E0 = SC + SL_EP; g.E1 = nullptr; g.head = 1; g.fuse = fuse ? 1 : 0; g.dd = *d; g.gstride = gs;
     g.c = adam_ctx(d, true, fuse ? *fuse : AdamScalars{0, 0.5, 0.5, 1.0, nullptr});
-    hipLaunchKernelGGL(k_grad, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
+    g.w2t = t ? t->critic : nullptr;
+    if (t) hipLaunchKernelGGL(k_grad_t, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
+    else hipLaunchKernelGGL(k_grad, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
     return hip_ok(hipGetLastError(), "ddpg critic-side launches");
 }
 
 // K4 + K5: the actor side (DDPG.jl:137-140), through the critic as it stands now (already updated)
-static int actor_side(const shems_ddpg *d, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream)
+static int actor_side(const shems_ddpg *d, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream, const shems_group_w2t *t = nullptr)
 {
-    if (int rc = check_ddpg(d, "shems_ddpg_actor_grad")) return rc;
+    if (int rc = check_ddpg(d, "shems_ddpg_actor_grad", t)) return rc;
     hipStream_t st = (hipStream_t)stream;
     float *ws = d->ws;
     // critic on [s; a_pi], a_pi = tanh(b3 + partials of the actor pass); workgroup 0 publishes a_pi for K5's head
@@ -1736,6 +1857,12 @@ static int actor_side(const shems_ddpg *d, unsigned L, int64_t gs, const AdamSca
     g.w1t = w1t_of(ws, SLOT_ACTOR); g.P = d->actor; g.in = SIN; g.out = 2; g.x = x_s; g.H2 = SA + SL_H2; g.w3f = ws + WS_FW3A;
     g.grad = d->grad_actor; g.E0 = SA + SL_EP; g.E1 = ws + WS_EA1; g.head = 2; g.fuse = fuse ? 1 : 0; g.dd = *d; g.gstride = gs;
     g.c = adam_ctx(d, false, fuse ? *fuse : AdamScalars{0, 0.5, 0.5, 1.0, nullptr});
+    if (t) {
+        f.job[0].W2t = t->critic + 2 * W2T_TILE; g.w2t = t->actor;
+        hipLaunchKernelGGL(k_fwd_t, dim3(fgx, 1, L), dim3(256), QG16_LDS, st, f);
+        hipLaunchKernelGGL(k_grad_t, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
+        return hip_ok(hipGetLastError(), "ddpg actor-side launches");
+    }
     hipLaunchKernelGGL(k_fwd, dim3(fgx, 1, L), dim3(256), QG16_LDS, st, f);
     hipLaunchKernelGGL(k_grad, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
     return hip_ok(hipGetLastError(), "ddpg actor-side launches");
@@ -1814,8 +1941,50 @@ int shems_ddpg_update(const shems_ddpg *d, const shems_replay *ring, int64_t rin
     if (int rc = check_adam(bp1_crit, bp2_crit, "shems_ddpg_update")) return rc;
     if (int rc = check_adam(bp1_act, bp2_act, "shems_ddpg_update")) return rc;
     const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr}, sa{eta_act, bp1_act, bp2_act, 1.0, d_publish};
+    shems_group_w2t t;
+    if (d && w2t_lookup(d->actor, &t)) {
+        // the second copy of the updated actor (the pipelined modes) is a Flux-order block: its W2 range would need the scattered stores back
+        if (d_publish) return set_error(SHEMS_ERR_STATE, "shems_ddpg_update: d_publish is not written from the tiled working layout");
+        if (int rc = critic_side(d, ring, ring_len, seed, tick, excl_pos, excl_count, 1, 0, &sc, stream, false, &t)) return rc;
+        return actor_side(d, 1, 0, &sa, stream, &t);
+    }
     if (int rc = critic_side(d, ring, ring_len, seed, tick, excl_pos, excl_count, 1, 0, &sc, stream)) return rc;
     return actor_side(d, 1, 0, &sa, stream);
+}
+
+/* A single learner on the tiled working layout: see shems_hip.h. */
+int shems_ddpg_tiled_enter(const shems_ddpg *d, const shems_group_w2t *t, void *stream)
+{
+    const char *fn = "shems_ddpg_tiled_enter";
+    if (int rc = check_ddpg(d, fn)) return rc;                 // (a learner that has entered already: SHEMS_ERR_STATE)
+    if (!t || !t->actor || !t->critic || ((uintptr_t)t->actor & 127) != 0 || ((uintptr_t)t->critic & 127) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t needs two 128-byte aligned device regions", fn);
+    const shems_group one{1, 0, 0, 0};
+    if (int rc = shems_group_w2_to_tiled(d, &one, t, stream)) return rc;
+    TiledGuard lock;
+    if (g_ntiled == (int)(sizeof g_tiled / sizeof g_tiled[0])) return set_error(SHEMS_ERR_STATE, "%s: too many learners on the tiled layout", fn);
+    g_tiled[g_ntiled++] = TiledLearner{{d->actor, d->critic, d->actor_t, d->critic_t, d->m_actor, d->v_actor, d->m_critic, d->v_critic}, *t};
+    return SHEMS_OK;
+}
+
+int shems_ddpg_tiled_leave(const shems_ddpg *d, void *stream)
+{
+    const char *fn = "shems_ddpg_tiled_leave";
+    shems_group_w2t t;
+    if (!d || !w2t_lookup(d->actor, &t)) return set_error(SHEMS_ERR_STATE, "%s: this learner is not on the tiled layout", fn);
+    const shems_group one{1, 0, 0, 0};
+    if (int rc = shems_group_w2_to_flux(d, &one, &t, stream)) return rc;
+    TiledGuard lock;
+    const int i = tiled_find(d->actor);
+    if (i >= 0) g_tiled[i] = g_tiled[--g_ntiled];
+    return SHEMS_OK;
+}
+
+int shems_ddpg_tiled_current(const shems_ddpg *d, int32_t *out)
+{
+    if (!d || !out) return set_error(SHEMS_ERR_ARG, "shems_ddpg_tiled_current: NULL");
+    *out = w2t_lookup(d->actor, nullptr) ? 1 : 0;
+    return SHEMS_OK;
 }
 
 /* One supervised update of the actor on demonstrations: K1's actor job alone, the actor's two E products, the actor's gradient

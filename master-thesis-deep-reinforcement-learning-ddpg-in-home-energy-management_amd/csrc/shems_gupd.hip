@@ -1188,6 +1188,7 @@ static int group_update_tp(const shems_ddpg *d, const shems_replay *ring, const 
     if (HP) eta_crit = eta_act = 0.0;        // the *_hp kernels form k1 from the records; the host context's k1 is never read by them
     for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
         if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
+    if (int rc = w2t_flux_guard(d->actor, fn)) return rc;       // (a single learner's own tiled mode, shems_ddpg_tiled_enter: not a group's t)
     if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
         return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
     for (double bp : {bp1_crit, bp2_crit, bp1_act, bp2_act})
@@ -1359,6 +1360,7 @@ extern "C" int shems_group_eval_best_dev(const shems_ddpg *d0, const shems_group
     if (runs < 1 || runs > e_eval)
         return set_error(SHEMS_ERR_ARG, "%s: runs must be in 1..envs_per_learner = %lld (got %d)", fn, (long long)e_eval, runs);
     if (!d0 || !d0->actor || !d0->s_min || !d0->s_max) return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg needs actor, s_min and s_max", fn);
+    if (int rc = w2t_flux_guard(d0->actor, fn)) return rc;
     const bool wide = l1 != 0 || l2 != 0;
     int64_t n_actor = SHEMS_ACTOR_PARAMS;
     if (wide) {

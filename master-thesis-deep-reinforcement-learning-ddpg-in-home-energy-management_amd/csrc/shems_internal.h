@@ -25,6 +25,11 @@ inline int lds_optin(std::atomic<uint64_t> &mask, const void *fn, int bytes, con
 // throughput form of the grouped update (shems_gupd.hip) carves its own, smaller, layout out of the same block.
 constexpr int64_t kTpWsFloats = 1902568;
 int check_view(const shems_view *v, const char *fn);    // every entry point that dereferences a caller-built view (shems_env.hip)
+// Single learners on the tiled working layout (shems_ddpg_tiled_enter, shems_ddpg.hip).  w2t_lookup: is `block` one of such a learner's
+// eight Flux-order blocks (parameters, targets, moments)?  Its regions go to *out (may be null).  w2t_flux_guard: SHEMS_ERR_STATE if
+// so -- what every entry point that reads or writes such a block in Flux order calls before it launches anything.
+bool w2t_lookup(const float *block, shems_group_w2t *out);
+int w2t_flux_guard(const float *block, const char *fn);
 // ADAM (Flux 0.12.1) + soft target update over n consecutive parameters, the data-parallel path's sweep (shems_ddpg.hip: k_adam_soft)
 // on any parameter count: the wide-network path (shems_wide.hip) applies its gradients with it.
 int adam_soft_sweep(float *p, const float *g, float *m, float *v, float *target, float *publish, int n, double eta, double bp1, double bp2,

@@ -972,7 +972,9 @@ __device__ __forceinline__ void g_piece(const char *sbase, uint32_t voff, uint32
     }
 }
 
-template <int TM, int NW, int NS, int RD, int HP>
+// TILED (k_actg_t, a single learner on the tiled working layout): column group g is n-tile g of the actor's region A.w2t, a row of it 256
+// contiguous bytes of the tile's p array; chunk c = rows 16 (c & 3) .. of k-tile c / 4.  The same three-part address with other constants.
+template <int TM, int NW, int NS, int RD, int HP, bool TILED = false>
 __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X, const shems_group_hparams *hp, const GroupX gx = GroupX{nullptr, nullptr})
 {
     static_assert(NW * NS == 8 && (NW == 4 || NW == 8), "8 column groups per env tile: 8 waves, or two workgroups of 4");
@@ -1016,12 +1018,15 @@ __device__ __forceinline__ void k_actg_body(const ActArgs &A, const ActSplit &X,
     const uint32_t ring_lds = lds_addr(Wg) + 2 * 1024;       // piece 2 of ring buffer 0
     // piece q of a chunk = its rows 4 q .. 4 q + 3, 16 lanes (256 B) per row; LDS image linear.  One wave-uniform base per chunk, four
     // constant lane offsets, the instruction's immediate (added to the global AND the LDS address) selects the LDS piece.
-    const char *gsbase = W2g + g * 256;
+    constexpr size_t kGTlTile = 4 * 64 * 64 * 4, kGTlP = 2 * 64 * 64 * 4;      // bytes: one tile's four arrays; offset of its p array
+    const char *gsbase = TILED ? reinterpret_cast<const char *>(A.w2t) + kGTlP + (size_t)g * kGTlTile : W2g + g * 256;
     uint32_t gvoff[kGPieces];
 #pragma unroll
-    for (int q = 0; q < kGPieces; ++q) gvoff[q] = (uint32_t)((4 * q + (lane >> 4)) * (kH2 * 4) + (lane & 15) * 16 - (q - 2) * 1024);
+    for (int q = 0; q < kGPieces; ++q)
+        gvoff[q] = (uint32_t)((4 * q + (lane >> 4)) * (TILED ? 256 : kH2 * 4) + (lane & 15) * 16 - (q - 2) * 1024);
+#define G_CHUNK_OFF(chunk) (TILED ? (size_t)((chunk) >> 2) * (8 * kGTlTile) + (size_t)((chunk) & 3) * (kKC * 256) : (size_t)(chunk) * (kKC * kH2 * 4))
 #define G_PIECE(chunk, q)                                                                         \
-    g_piece(gsbase + (size_t)(chunk) * (kKC * kH2 * 4), gvoff[q], ring_lds + ((chunk) % RD) * (kGChunkFloats * 4), (q))
+    g_piece(gsbase + G_CHUNK_OFF(chunk), gvoff[q], ring_lds + ((chunk) % RD) * (kGChunkFloats * 4), (q))
     // The env tail's inputs lead the burst (TailPre; every thread for env tid % BM): the table row idx + 1 hangs off idx, so idx is
     // asked for first and the row right behind it -- the row then lands during stage 0 instead of holding up the layer-1 phase.
     // One config for the whole batch (the usual case): its table_row0 / nrow come by scalar loads, not behind a per-env config index.
@@ -1203,6 +1208,8 @@ template <int TM, int NW, int NS, int RD>
 __global__ __launch_bounds__(64 * NW) void k_actg_hp(ActArgs A, ActSplit X, const shems_group_hparams *hp) { k_actg_body<TM, NW, NS, RD, 1>(A, X, hp); }
 template <int TM, int NW, int NS, int RD>
 __global__ __launch_bounds__(64 * NW) void k_actg_x(ActArgs A, ActSplit X, const shems_group_hparams *hp, GroupX gx) { k_actg_body<TM, NW, NS, RD, 2>(A, X, hp, gx); }
+template <int TM, int NW, int NS, int RD>
+__global__ __launch_bounds__(64 * NW) void k_actg_t(ActArgs A, ActSplit X) { k_actg_body<TM, NW, NS, RD, 0, true>(A, X, nullptr); }
 
 // =====================================================================================================================
 // k_act2: the fused step for large batches with TWO workgroups resident per CU.
@@ -1231,7 +1238,16 @@ __device__ __forceinline__ void k2_piece(const char *sbase, uint32_t voff, uint3
     if (q == 0) glds16_asm<-1024>(sbase, voff, lds_base); else glds16_asm<0>(sbase, voff, lds_base);
 }
 
-template <int HP>
+// TILED (k_act2_t, a single learner on the tiled working layout): the W2 stream comes from the p arrays of the actor's region A.w2t, with
+// the three-part address of k_act's tiled source and this kernel's chunk shape -- chunk ch = rows 4 (ch & 15) .. of k-tile ch / 16, a
+// piece = rows 2 q, 2 q + 1 of the two 64-column tiles 2 w, 2 w + 1 (lanes 0..15 / 16..31 of each half wave), 256 contiguous bytes per
+// row and tile: four whole lines per 512-byte segment where Flux order touches five.  Pad rows / columns are zeros there.
+constexpr size_t k2TlTile = 4 * 64 * 64 * 4, k2TlP = 2 * 64 * 64 * 4;        // bytes: one tile's four arrays; offset of its p array
+template <bool TILED> constexpr size_t k2_chunk_off(int ch)
+{
+    return TILED ? (size_t)(ch >> 4) * (8 * k2TlTile) + (size_t)(ch & 15) * (k2CR * 256) : (size_t)ch * (k2CR * kH2 * 4);
+}
+template <int HP, bool TILED = false>
 __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_hparams *hp, const GroupX gx = GroupX{nullptr, nullptr})
 {
     constexpr int TM = 2, BM = 64, NA = 4, NT_ = 256, HR = 128;
@@ -1254,11 +1270,13 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
     const char *W2g = reinterpret_cast<const char *>(P + kOffW2);
     float *Wf = Wc + wave * (k2RD * k2CF);
     const uint32_t ring_lds = lds_addr(Wf) + 1024;           // piece 1 of ring buffer 0
-    const char *wsbase = W2g + wave * 512;
+    const char *wsbase = TILED ? reinterpret_cast<const char *>(A.w2t) + k2TlP + (size_t)wave * (2 * k2TlTile) : W2g + wave * 512;
     uint32_t wvoff[2];
 #pragma unroll
-    for (int q = 0; q < 2; ++q) wvoff[q] = (uint32_t)((lane >> 5) * (kH2 * 4) + (lane & 31) * 16 + q * (2 * kH2 * 4) - (q - 1) * 1024);
-#define K2_PIECE(chunk, q) k2_piece(wsbase + (size_t)(chunk) * (k2CR * kH2 * 4), wvoff[q], ring_lds + ((chunk) % k2RD) * (k2CF * 4), (q))
+    for (int q = 0; q < 2; ++q)
+        wvoff[q] = TILED ? (uint32_t)(((lane & 31) >> 4) * k2TlTile + (lane >> 5) * 256 + (lane & 15) * 16 + q * 512 - (q - 1) * 1024)
+                         : (uint32_t)((lane >> 5) * (kH2 * 4) + (lane & 31) * 16 + q * (2 * kH2 * 4) - (q - 1) * 1024);
+#define K2_PIECE(chunk, q) k2_piece(wsbase + k2_chunk_off<TILED>(chunk), wvoff[q], ring_lds + ((chunk) % k2RD) * (k2CF * 4), (q))
     TailPre tp;
     act_pre_index(A, P, env0 + (tid & (BM - 1)), tp);
     ObsRegs<BM, NT_> xr;
@@ -1419,6 +1437,7 @@ __device__ __forceinline__ void k_act2_body(const ActArgs &A, const shems_group_
 __global__ __launch_bounds__(256, 2) void k_act2(ActArgs A) { k_act2_body<0>(A, nullptr); }
 __global__ __launch_bounds__(256, 2) void k_act2_hp(ActArgs A, const shems_group_hparams *hp) { k_act2_body<1>(A, hp); }
 __global__ __launch_bounds__(256, 2) void k_act2_x(ActArgs A, const shems_group_hparams *hp, GroupX gx) { k_act2_body<2>(A, hp, gx); }
+__global__ __launch_bounds__(256, 2) void k_act2_t(ActArgs A) { k_act2_body<0, true>(A, nullptr); }
 
 // One form's three kernels and their LDS opt-in state (per kernel and device: see lds_optin).  launch() runs the plain kernel, or with
 // hp != null (shems_act_step_group_dev with d_hp) the *_hp kernel, or with gx != null (shems_act_step_group_x_dev) the *_x kernel, after
@@ -1456,6 +1475,12 @@ static int launch_act2(const ActArgs &a, hipStream_t st, const shems_group_hpara
 {
     constexpr size_t lds = act2_lds_bytes();
     static_assert(lds <= 80 * 1024, "k_act2: two workgroups must fit a CU's 160 KB");
+    if (a.w2t) {                                              // a single learner on the tiled working layout (pick_act_form)
+        static std::atomic<uint64_t> optin{0};
+        if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_act2_t), (int)lds, "hipFuncSetAttribute(k_act2_t)")) return rc;
+        hipLaunchKernelGGL(k_act2_t, dim3((unsigned)((a.m - a.m0 + 63) / 64)), dim3(256), lds, st, a);
+        return hip_ok(hipGetLastError(), "k_act2_t launch");
+    }
     static ActKernels<ActArgs> form("k_act2", k_act2, k_act2_hp, k_act2_x);
     return form.launch(dim3((unsigned)((a.m - a.m0 + 63) / 64)), dim3(256), lds, st, hp, gx, a);
 }
@@ -1527,6 +1552,12 @@ static int launch_actg(const ActArgs &a, hipStream_t st, const shems_group_hpara
             return launch_actg<1, 8, 1, RD>(a, st, hp, gx);
         }
     }
+    if (a.w2t) {                                              // a single learner on the tiled working layout (pick_act_form)
+        static std::atomic<uint64_t> optin{0};
+        if (int rc = lds_optin(optin, reinterpret_cast<const void *>(&k_actg_t<TM, NW, NS, RD>), (int)lds, "hipFuncSetAttribute(k_actg_t)")) return rc;
+        hipLaunchKernelGGL((k_actg_t<TM, NW, NS, RD>), dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, a, x);
+        return hip_ok(hipGetLastError(), "k_actg_t launch");
+    }
     return form.launch(dim3((unsigned)(tiles * NS)), dim3(64 * NW), lds, st, hp, gx, a, x);
 }
 
@@ -1572,7 +1603,9 @@ static int act_form_tile_envs(ActForm f)
 static ActForm pick_act_form(int64_t cnt, int tm_max, int gcount, bool w2t, bool want_sum)
 {
     const int form = act_form();
-    if (w2t) {                                                // tiled learner group: the free-running forms read W2 from the tiled regions
+    // (a single learner on tiles -- gcount == 0, shems_ddpg_tiled_enter -- takes the choice below like one in Flux order: every form has a
+    // tiled W2 source, k_act in its own kernels and k_act2 / k_actg in their twins k_act2_t / k_actg_t)
+    if (w2t && gcount > 0) {                                  // tiled learner group: the free-running forms read W2 from the tiled regions
         const int tmt = pick_tm(cnt, tm_max);
         return tmt == 4 ? kAct442 : tmt == 2 ? kAct242 : kAct142;
     }
@@ -1712,12 +1745,16 @@ int shems_act_step_group_kernel(int64_t n_envs, int64_t envs_per_learner, int ti
     return SHEMS_OK;
 }
 
-static int check_act(const shems_act_params *p, const char *fn)
+// tiled: the entry points that can read W2 from a single learner's tiled regions (shems_ddpg_tiled_enter) get them here (zeros: Flux
+// order); every other entry point is refused while the regions hold the actor's current layer-2 state.
+static int check_act(const shems_act_params *p, const char *fn, shems_group_w2t *tiled = nullptr)
 {
     if (!p || !p->actor || !p->s_min || !p->s_max) return set_error(SHEMS_ERR_ARG, "%s: actor / s_min / s_max required", fn);
     if (p->noise_kind < SHEMS_NOISE_GAUSS || p->noise_kind > SHEMS_NOISE_EPS) return set_error(SHEMS_ERR_ARG, "%s: unknown noise_kind %d", fn, p->noise_kind);
     if (p->train && p->noise_kind == SHEMS_NOISE_OU && !p->ou_state) return set_error(SHEMS_ERR_ARG, "%s: OU noise needs ou_state", fn);
     if (((uintptr_t)p->actor & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: actor parameter block must be 16-byte aligned", fn);
+    if (!tiled) return w2t_flux_guard(p->actor, fn);
+    if (!w2t_lookup(p->actor, tiled)) *tiled = shems_group_w2t{nullptr, nullptr};
     return SHEMS_OK;
 }
 
@@ -1745,11 +1782,12 @@ static int attach_ring(const char *fn, ActArgs &a, const shems_replay *ring, con
 
 int shems_actor_forward_dev(const shems_act_params *p, const float *d_obs, int64_t m, float *d_a, void *stream)
 {
-    if (int rc = check_act(p, "shems_actor_forward_dev")) return rc;
+    shems_group_w2t t;
+    if (int rc = check_act(p, "shems_actor_forward_dev", &t)) return rc;
     if (!d_obs || !d_a || m <= 0) return set_error(SHEMS_ERR_ARG, "shems_actor_forward_dev: bad buffers");
     ActArgs a;
     std::memset(&a, 0, sizeof a);
-    a.p = *p; a.obs = d_obs; a.m = m; a.a_out = d_a;
+    a.p = *p; a.obs = d_obs; a.m = m; a.a_out = d_a; a.w2t = t.actor;
     return dispatch_act(a, (hipStream_t)stream);
 }
 
@@ -1757,10 +1795,12 @@ int shems_act_step_dev(const shems_view *v, const shems_act_params *p, float *d_
                        float *d_rewards_f32, double *d_block_reward, double *d_returns_acc,
                        const shems_replay *ring, const shems_ring_window *window, void *stream)
 {
-    if (int rc = check_act(p, "shems_act_step_dev")) return rc;
+    shems_group_w2t t;
+    if (int rc = check_act(p, "shems_act_step_dev", &t)) return rc;
     if (int rc = check_view(v, "shems_act_step_dev")) return rc;
     ActArgs a;
     step_args(a, v, p);
+    a.w2t = t.actor;
     a.a_out = d_a; a.rewards = d_rewards; a.rewards_f32 = d_rewards_f32; a.block_reward = d_block_reward; a.returns_acc = d_returns_acc;
     if (int rc = attach_ring("shems_act_step_dev", a, ring, window, v->n_envs)) return rc;
     return dispatch_act(a, (hipStream_t)stream);
@@ -1774,14 +1814,15 @@ extern "C" {
 int shems_act_step_range_dev(const shems_view *v, const shems_act_params *p, int64_t env_lo, int64_t env_count, float *d_rewards_f32,
                              const shems_replay *ring, const shems_ring_window *window, void *stream)
 {
-    if (int rc = check_act(p, "shems_act_step_range_dev")) return rc;
+    shems_group_w2t t;
+    if (int rc = check_act(p, "shems_act_step_range_dev", &t)) return rc;
     if (int rc = check_view(v, "shems_act_step_range_dev")) return rc;
     if (env_lo < 0 || env_count <= 0 || env_lo + env_count > v->n_envs)
         return set_error(SHEMS_ERR_ARG, "shems_act_step_range_dev: envs [%lld, %lld + %lld) outside the batch of %lld", (long long)env_lo,
                          (long long)env_lo, (long long)env_count, (long long)v->n_envs);
     ActArgs a;
     step_args(a, v, p);
-    a.m0 = env_lo; a.m = env_lo + env_count; a.rewards_f32 = d_rewards_f32;
+    a.m0 = env_lo; a.m = env_lo + env_count; a.rewards_f32 = d_rewards_f32; a.w2t = t.actor;
     if (int rc = attach_ring("shems_act_step_range_dev", a, ring, window, v->n_envs)) return rc;     // the window is defined on the whole batch
     return dispatch_act(a, (hipStream_t)stream);
 }

@@ -321,6 +321,7 @@ extern "C" int shems_track_dev(const shems_view *v, const shems_act_params *p, i
         if (!p || !p->actor || !p->s_min || !p->s_max) return set_error(SHEMS_ERR_ARG, "shems_track_dev: actor / s_min / s_max required for track > 0");
         if (((uintptr_t)p->actor & 15) != 0 || (actor_stride_bytes & 15) != 0 || actor_stride_bytes < 0)
             return set_error(SHEMS_ERR_ARG, "shems_track_dev: actor block and stride must be 16-byte aligned");
+        if (int rc = w2t_flux_guard(p->actor, "shems_track_dev")) return rc;
         a.actor = p->actor; a.s_min = p->s_min; a.s_max = p->s_max; a.stride = actor_stride_bytes;
     }
     a.track_mode = track_mode > 0 ? SHEMS_TRACK_DRL : SHEMS_TRACK_RULE;
@@ -344,6 +345,7 @@ extern "C" int shems_wide_track_dev(const shems_view *v, const shems_act_params 
     if (!p || !p->actor || !p->s_min || !p->s_max) return set_error(SHEMS_ERR_ARG, "shems_wide_track_dev: actor / s_min / s_max required");
     if (((uintptr_t)p->actor & 15) != 0 || (actor_stride_bytes & 15) != 0 || actor_stride_bytes < 0)
         return set_error(SHEMS_ERR_ARG, "shems_wide_track_dev: actor block and stride must be 16-byte aligned");
+    if (int rc = w2t_flux_guard(p->actor, "shems_wide_track_dev")) return rc;
     TrackArgs a;
     std::memset(&a, 0, sizeof a);
     a.v = *v;

@@ -430,6 +430,8 @@ static int check_wide(const shems_ddpg *d, int l1, int l2, const char *fn)
         !d->v_critic || !d->grad_actor || !d->grad_critic || !d->s_min || !d->s_max || !d->ws || !d->losses)
         return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
     if (d->batch < 1 || d->batch > WBP) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
+    for (const float *p : {d->actor, d->critic, d->actor_t, d->critic_t, d->m_actor, d->v_actor, d->m_critic, d->v_critic})
+        if (int rc = w2t_flux_guard(p, fn)) return rc;
     return SHEMS_OK;
 }
 
@@ -617,6 +619,7 @@ static int wide_group_update(const char *fn, const shems_ddpg *d0, const shems_r
                           (const void *)d0->m_actor, (const void *)d0->v_actor, (const void *)d0->m_critic, (const void *)d0->v_critic,
                           (const void *)d0->grad_actor, (const void *)d0->grad_critic})
         if (((uintptr_t)q & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter, moment and gradient blocks must be 16-byte aligned", fn);
+    if (int rc = w2t_flux_guard(d0->actor, fn)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int L = g->count, P = pass_width(max_batch);
     const int64_t stride = g->count > 1 ? g->stride_bytes / 4 : 0;

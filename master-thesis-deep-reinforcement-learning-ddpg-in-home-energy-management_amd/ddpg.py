@@ -55,6 +55,13 @@ class DdpgArgs(C.Structure):           # shems_ddpg
                [("gamma", C.c_float), ("tau", C.c_float), ("batch", C.c_int32), ("flags", C.c_int32)]
 
 
+class W2T(C.Structure):                # shems_group_w2t: the tiled regions of one learner's layer-2 state (actor's, critic's)
+    _fields_ = [("actor", C.c_void_p), ("critic", C.c_void_p)]
+
+
+W2T_FLOATS = 32 * 4 * 64 * 64          # SHEMS_W2T_FLOATS: [4 k-tiles][8 n-tiles][m | v | p | target][64][64] per network
+
+
 class RingWindow(C.Structure):         # shems_ring_window
     _fields_ = [("pos", C.c_int64), ("count", C.c_int64), ("offset", C.c_int64)]
 
@@ -100,6 +107,11 @@ def _declare():
     dbl = C.c_double
     L.shems_ddpg_update.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, i64, i64, dbl, dbl, dbl, dbl, dbl, dbl, vp, vp]
     L.shems_ddpg_update.restype = C.c_int
+    L.shems_ddpg_tiled_enter.argtypes = [PD, C.POINTER(W2T), vp]
+    L.shems_ddpg_tiled_leave.argtypes = [PD, vp]
+    L.shems_ddpg_tiled_current.argtypes = [PD, C.POINTER(C.c_int32)]
+    for fn in ("shems_ddpg_tiled_enter", "shems_ddpg_tiled_leave", "shems_ddpg_tiled_current"):
+        getattr(L, fn).restype = C.c_int
     L.shems_ddpg_clone_update.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, vp, vp]
     L.shems_ddpg_clone_update.restype = C.c_int
     L.shems_ddpg_critic_update.argtypes = [PD, C.POINTER(_capi.Replay), i64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, vp]
@@ -372,6 +384,60 @@ class Agent:
         self.fused = True                          # single replica: replay() = ONE call, shems_ddpg_update (5 launches, ADAM inside the
                                                    # gradient launches); False = the split calls the data-parallel path uses (same bits)
 
+    # ---- the tiled working layout of the layer-2 state (shems_ddpg_tiled_enter, include/shems_hip.h) ------------------------------------
+    # With tiled_mode on, the fused replay() and the fused step keep W2, its ADAM moments and the targets' W2 of both networks in two
+    # tiled regions; the W2 ranges of the eight Flux-order tensors below are stale meanwhile.  The tensors are properties: reading one
+    # (or writing one: set_params, restore, a checkpoint) first brings the Flux-order view up to date (flux_()), so nobody is handed
+    # stale bytes; the launches that work on the regions take the raw tensors (_blk).  The native library keeps the same record and
+    # refuses every Flux-order entry point in between (SHEMS_ERR_STATE).
+    _W2_BLOCKS = ("actor", "critic", "actor_t", "critic_t", "m_actor", "v_actor", "m_critic", "v_critic")
+    tiled_mode = False                             # asked for (use_tiled)
+    _tiled_current = False                         # the regions hold the current layer-2 state
+    _w2t = None                                    # [2][SHEMS_W2T_FLOATS]: the actor's region, the critic's
+
+    def _blk(self, k):
+        return self.__dict__["_blk_" + k]
+
+    def use_tiled(self, on=True):
+        """Switch the tiled working mode on or off (off: the Flux-order view is brought up to date first)."""
+        if on and self.wide:
+            raise NotImplementedError("the tiled working layout belongs to the tuned (250, 500) kernels")
+        if not on:
+            self.flux_()
+        self.tiled_mode = bool(on)
+        return self
+
+    def _enter_tiled(self):
+        """Before a launch that works on the regions.  True: they are current now.  Only where replay() is the one-call form
+        (shems_ddpg_update: one replica, no parameter noise, one pass): every other form speaks Flux order, so the Flux-order view is
+        made current instead -- also when the learner's exchange or form was changed after the mode was switched on."""
+        if not (self.tiled_mode and self.fused and self.sync.world == 1 and self.noise_type != "pn" and not self.wide
+                and self.batch <= self.MAX_PASS_BATCH):
+            self.flux_()
+            return False
+        if not self._tiled_current:
+            if self._w2t is None:
+                self._w2t = self.torch.zeros(2, W2T_FLOATS, dtype=self.torch.float32, device=self.device)
+            t = W2T(self._w2t[0].data_ptr(), self._w2t[1].data_ptr())
+            d = self._ddpg_args(raw=True)
+            _capi.check(self.L.shems_ddpg_tiled_enter(C.byref(d), C.byref(t), self._stream()))
+            self._tiled_current = True
+        return self._tiled_current
+
+    def flux_(self):
+        """Bring the W2 ranges of the Flux-order tensors up to date and make them the current copy again."""
+        if self._tiled_current:
+            d = self._ddpg_args(raw=True)
+            _capi.check(self.L.shems_ddpg_tiled_leave(C.byref(d), self._stream()))
+            self._tiled_current = False
+        return self
+
+    def __del__(self):
+        try:                                       # the native record is keyed by the blocks' addresses: forget it with them
+            self.flux_()
+        except Exception:                          # noqa: BLE001 (interpreter shutdown)
+            pass
+
     # ------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
@@ -448,7 +514,8 @@ class Agent:
         self.s_max.copy_(t.as_tensor(np.asarray(s_max, f32)))
 
     def _act_params(self, train, tick, actor=None, noise_acc=None):
-        a = self.actor if actor is None else actor
+        # (the learner's own actor: the raw block -- while the regions are current the fused step reads W2 from them)
+        a = self._blk("actor") if actor is None else actor
         return ActParams(a.data_ptr(), self.s_min.data_ptr(), self.s_max.data_ptr(), self.mu, self.sigma,
                          1 if train else 0, int(tick) & 0xFFFFFFFF, self.rng_seed, NOISE_KINDS[self.noise_type], self.theta,
                          self.dt, self.eps, self.ou_state.data_ptr() if self.ou_state is not None else None,
@@ -559,13 +626,17 @@ class Agent:
     # ---------------------------------------------------------------- learner
     MAX_PASS_BATCH = 128                           # minibatch columns one update pass holds (csrc/shems_ddpg.hip: BP)
 
-    def _ddpg_args(self, sub=None):
-        """sub: a sub-batch record (its own workspace, gradient buffers, losses, size) of a minibatch wider than one pass."""
+    def _ddpg_args(self, sub=None, raw=False):
+        """sub: a sub-batch record (its own workspace, gradient buffers, losses, size) of a minibatch wider than one pass.  raw: for a
+        launch that works on the tiled regions (or enters / leaves them); every other caller gets the Flux-order view, up to date."""
+        if not raw:
+            self.flux_()
+        B = self._blk
         ga, gc, ws, ls, b = ((self.grad_actor, self.grad_critic, self.ws, self.losses, self.batch) if sub is None else
                              (sub["ga"], sub["gc"], sub["ws"], sub["losses"], sub["batch"]))
         defer = self.sync.world > 1 and self.dp_overlap and sub is None and self.batch <= self.MAX_PASS_BATCH and not self.wide
-        return DdpgArgs(self.actor.data_ptr(), self.critic.data_ptr(), self.actor_t.data_ptr(), self.critic_t.data_ptr(),
-                        self.m_actor.data_ptr(), self.v_actor.data_ptr(), self.m_critic.data_ptr(), self.v_critic.data_ptr(),
+        return DdpgArgs(B("actor").data_ptr(), B("critic").data_ptr(), B("actor_t").data_ptr(), B("critic_t").data_ptr(),
+                        B("m_actor").data_ptr(), B("v_actor").data_ptr(), B("m_critic").data_ptr(), B("v_critic").data_ptr(),
                         ga.data_ptr(), gc.data_ptr(), self.s_min.data_ptr(), self.s_max.data_ptr(),
                         ws.data_ptr(), ls.data_ptr(), self.gamma, self.tau, b,
                         1 if defer else 0)                                                    # SHEMS_DDPG_DEFER_ACTOR_E
@@ -648,7 +719,8 @@ class Agent:
         """replay(; rng_rpl) (DDPG.jl:121-145): one DDPG update from `ring`.  exclude = (pos, count): ring slots another
         stream is writing right now (pipelined mode); publish = tensor that also receives the updated actor."""
         self._same_device(None, ring)
-        d = self._ddpg_args()
+        # the one-call form works on the tiled regions where the mode is on (the second copy `publish` is a Flux-order block: not from tiles)
+        d = self._ddpg_args(raw=True) if publish is None and self._enter_tiled() else self._ddpg_args()
         st = self._stream()
         rs = ring.struct()
         tick = self.updates if tick is None else tick
@@ -860,6 +932,26 @@ class Agent:
         return total_reward, score_mean, best_run, best_actor
 
 
+def _w2_block_property(k):
+    def get(self):
+        self.flux_()
+        return self.__dict__["_blk_" + k]
+
+    def put(self, v):
+        self.flux_()
+        self.__dict__["_blk_" + k] = v
+    return property(get, put)
+
+
+for _k in Agent._W2_BLOCKS:
+    setattr(Agent, _k, _w2_block_property(_k))
+del _k
+
+
+AGENT_TILED_DEFAULT = "1"              # TrainWorkload's default for SHEMS_AGENT_TILED.  On since the A/B runs of DESIGN.md 4: replay() 35.2 ->
+                                       # 32.6 us as the sum of its kernels' means, 166.2 -> 163.4 us per vector step at 65 536 envs
+
+
 class TrainWorkload:
     """bench.py's "train" step: the body of the reference's episode! loop for all envs of a rank at once --
     act + noise + scale_action + step! + remember (one fused launch) and `updates` x replay() (5 launches
@@ -936,6 +1028,14 @@ class TrainWorkload:
             raise NotImplementedError("pipelined modes run the tuned (250, 500) kernels: a wide network's actor copies are not in their layout")
         self.loop = loop
         self._native = None
+        # The single learner's layer-2 state on the tiled working layout (Agent.use_tiled): the ordered native loop on the tuned kernels.
+        # SHEMS_AGENT_TILED=1 / 0 selects it / Flux order for A/B runs; the pipelined modes publish Flux-order actor copies and stay there.
+        import os
+        want = os.environ.get("SHEMS_AGENT_TILED", AGENT_TILED_DEFAULT)
+        if want not in ("0", "1"):
+            raise ValueError(f"SHEMS_AGENT_TILED must be 0 or 1, not {want!r}")
+        self.tiled = want == "1" and loop == "native" and not self.overlap and self.agent.sync.world == 1
+        self.agent.use_tiled(self.tiled)
         if self.overlap:
             # Pipelined mode: replay(t) runs on a second stream while the fused act/step kernel of step t runs on the main
             # one.  act(t) still uses the actor produced by replay(t-1), exactly as in the sequential loop; the one deviation
@@ -966,7 +1066,7 @@ class TrainWorkload:
             L = TrainLoop()
             L.view = self.env.view()
             L.act = ag._act_params(True, 0)
-            L.ddpg = ag._ddpg_args()
+            L.ddpg = ag._ddpg_args(raw=True)         # (the blocks' addresses: which copy of the layer-2 state is current is steps()'s business)
             L.ddpg.flags = 0                     # the native data-parallel step runs both exchanges in program order: K2 keeps the actor's E
                                                  # products (the DEFER_ACTOR_E form belongs to Agent.replay's asynchronous torch path only)
             L.ring = self.ring.struct()
@@ -991,6 +1091,7 @@ class TrainWorkload:
             return
         ag = self.agent
         L = self._native_loop()
+        ag._enter_tiled()                          # (or the Flux-order view made current, where the learner's update is not the one-call form)
         st2 = C.c_void_p(self.upd_stream.cuda_stream) if self.overlap else None
         try:
             _capi.check(ag.L.shems_train_steps(C.byref(L), int(k), ag._stream(), st2))
@@ -1175,7 +1276,7 @@ class TrainWorkload:
                 "updates_per_step": self.updates, "batch_size": BATCH_SIZE, "mem_size": self.mem_size,
                 "replay_mode": "scaled (capacity 72 N, every env inserts)" if self.scaled_replay else "window (MEM_SIZE = 24 000, 333 envs insert per step)",
                 "overlap": {LOOP_ORDERED: False, LOOP_PIPELINED: "pipelined", LOOP_PIPELINED_EXACT: "exact"}[self.overlap_mode],
-                "loop": self.loop,
+                "loop": self.loop, "agent_w2_layout": "tiled" if self.tiled else "Flux order",
                 "learner_crc32": crc, "dp_overlap": bool(self.agent.dp_overlap and self.agent.sync.world > 1 and self.loop != "native"),   # (the native loop exchanges in program order)
                 "dp_exchange": None if self.agent.sync.world == 1 else (
                     "RCCL all-reduce in the update's own stream, issued from native code (shems_ddpg_update_dp)" if self.agent.sync.native is not None else
