@@ -594,6 +594,29 @@ int shems_ddpg_group_update_tp_x(const shems_ddpg *d0, const shems_replay *ring0
                                  const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, uint64_t seed,
                                  uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
                                  double bp2_act, int32_t flags, void *stream);
+/* The supervised update (shems_ddpg_clone_update's definition) for every learner of a group, throughput form, four launches:
+ *   loss_l = Flux.mse(actor_l(normalize(s)), a_demo) on the first batch_l draws of the stream (seed + l, tick) from learner l's ring,
+ * then ADAM on the actor and the soft update of actor_t (d0->tau or the record's; 1 keeps actor_t == actor bit for bit).  The
+ * sampler, a forward launch with the actor(s) job alone, the actor's D1 launch with the cloning head (d3[o][m] = (a_pi - a_demo)
+ * (1 - a_pi^2) / batch_l, 0 in the pad columns; losses[1] sums the squared differences per 64-lane wave by butterfly, then
+ * ((w0 + w1) + w2) + w3, / (2 batch_l)), and the update's W2-gradient launch.  Only s and a of a slot are read (ring0->r, s2 and done
+ * may be NULL); the critic, its target, its moments, grad_critic and losses[0] are not touched.
+ *   ring0, ring_stride_bytes: learner l's ring arrays are ring0's + l * ring_stride_bytes -- a stride of the ring's own, which may be
+ *          g->stride_bytes (rings inside the slabs) or anything else (demonstrations outside them): a non-negative multiple of 4, not
+ *          0 when g->count > 1.  Every learner samples x mod ring_len (1..ring0->capacity).
+ *   t, d_hp, flags: as shems_ddpg_group_update_tp (d_hp: the record's batch, eta_act and tau; eta is ignored then).
+ * Everything shems_ddpg_group_update_tp refuses for the buffers read here is refused with SHEMS_ERR_ARG before any launch. */
+int shems_ddpg_group_clone_update_tp(const shems_ddpg *d0, const shems_replay *ring0, int64_t ring_stride_bytes, const shems_group *g,
+                                     const shems_group_w2t *t, const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed,
+                                     uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream);
+/* The critic-only update (shems_ddpg_critic_update's definition: update_model!(critic), soft_update!(critic_target, critic)) for every
+ * learner of a group, throughput form, five launches: the sampler and the first five launches of shems_ddpg_group_update_tp without
+ * the actor(s) job.  From the same state, ring, seed and tick it leaves in critic, critic_t, m_critic, v_critic, grad_critic and
+ * losses[0] the bits of shems_ddpg_group_update_tp; actor, actor_t, m_actor, v_actor, grad_actor and losses[1] are not touched.
+ * The ring needs all five arrays; ring0 / ring_stride_bytes, t, d_hp (batch, gamma, eta_crit, tau) and flags as above. */
+int shems_ddpg_group_critic_update_tp(const shems_ddpg *d0, const shems_replay *ring0, int64_t ring_stride_bytes, const shems_group *g,
+                                      const shems_group_w2t *t, const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed,
+                                      uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream);
 /* shems_wide_group_update in the same way (input.jl:64, 140; DDPG.jl:121-145). */
 int shems_wide_group_update_x(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
                               const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, int32_t max_batch,

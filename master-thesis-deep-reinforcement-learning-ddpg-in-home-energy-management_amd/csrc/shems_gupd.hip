@@ -29,6 +29,10 @@
 //   P5 k_tp_fwd<QG> updated critic on [s; actor(s)], forward and input gradient per n-tile          (DDPG.jl:117-119, 140)
 //   P6 k_tp_d1     actor: through tanh, D1, layer-1 gradient + ADAM
 //   P7 k_tp_gw2    actor: gW2 + ADAM + soft update, gb2, gW3                                        (DDPG.jl:140-143)
+// Two subsets of these launches are updates of their own (behind the kernels above): the grouped SUPERVISED update
+// (shems_ddpg_group_clone_update_tp: a sampler with a ring stride of its own, P1 with the actor(s) job alone, P6 with the cloning head
+// chosen at compile time, P7) and the grouped CRITIC-ONLY update (shems_ddpg_group_critic_update_tp: that sampler, P1 without the
+// actor(s) job, P2, P3, P4 -- the bits of the critic half of the sequence above).
 // Summation orders differ from the latency form (64-wide n-tiles, chunked contractions): per learner the results agree with it to
 // fp32 accumulation accuracy, not bit for bit -- the parity test holds every gradient block of every learner to the float64
 // evaluation with the same bound as the latency form (tests/test_group_gpu.py).
@@ -120,6 +124,14 @@ __device__ __forceinline__ void hp_adam(AdamCtx &c, const shems_group_hparams &h
     c.eta = critic ? h.eta_crit : h.eta_act;
     c.k1 = c.eta / (1.0 - c.bp1);
     c.tau = h.tau;
+}
+
+// a workgroup-uniform double moved into scalar registers (the same bits)
+__device__ __forceinline__ double uniform_f64(double x)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(x);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
 __device__ __forceinline__ void adam_at(const AdamCtx &c, int i, float g, bool store_grad)
@@ -596,6 +608,38 @@ __device__ __forceinline__ void head_actor(const NetArgs &A, const shems_ddpg &d
         }
     }
 }
+// The cloning head (shems_ddpg_group_clone_update_tp): loss = Flux.mse(actor(normalize(s)), a_demo), the mean over the 2 * batch
+// elements.  a_pi = tanh(b3 + the NT layer-3 partials of the actor pass), the frozen b3 first and the partials in ascending n-tile order
+// (the order in which fwd_body forms an actor pass's action); d3[o][m] = (a_pi - a_demo)(1 - a_pi^2) / batch, 0 in the pad columns.
+// a_demo [2][BP] lies where the full sampler keeps r and done (TP_ADEMO).  The loss sums in ONE order: per wave of 64 lanes the butterfly
+// of wave_sum64 over its 64 squared differences, then ((w0 + w1) + w2) + w3 with waves 0, 1 = output 0 (columns 0..63, 64..127) and
+// waves 2, 3 = output 1, divided by float(2 batch).
+constexpr int64_t TP_ADEMO = TP_R;
+static_assert(TP_DONE == TP_R + BP, "a_demo [2][BP] takes the r and done rows of the full sampler");
+__device__ __forceinline__ void head_clone(const NetArgs &A, const shems_ddpg &d, const AdamCtx &c, float *d3s, float *red, bool publisher)
+{
+    float *ws = d.ws;
+    const int t = threadIdx.x, o = t >> 7, m = t & 127;
+    const float *Pa = p3_of(ws, NET_ACTOR);
+    float z = ws[TP_FB3 + 2 + o];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) z += Pa[(i * 2 + o) * BP + m];
+    const float a = tanhf(z);                                  // Dense(500, 2, tanh)
+    const float diff = m < d.batch ? a - ws[TP_ADEMO + t] : 0.0f;
+    const float g = diff * (1.0f - a * a) / (float)d.batch;    // d mse / d a_pi = (a_pi - a_demo) / batch, through tanh
+    d3s[t] = g;
+    if (publisher) {
+        ws[TP_D3A + t] = g;
+        const float sl = wave_sum64(diff * diff), sg = wave_sum64(g);
+        if ((t & 63) == 0) { red[t >> 6] = sl; red[4 + (t >> 6)] = sg; }
+        __syncthreads();
+        if (t == 0) {
+            d.losses[1] = (((red[0] + red[1]) + red[2]) + red[3]) / (float)(2 * d.batch);
+            adam_at(c, off_b3(SIN, 2), red[4] + red[5], A.store_grad != 0);
+            adam_at(c, off_b3(SIN, 2) + 1, red[6] + red[7], A.store_grad != 0);
+        }
+    }
+}
 
 // ================================================================================================================================
 // P3 / P6: D1' [m][k] = mask1 .* sum_n D2[n][m] W2[k][n] for one 64-wide k-tile and the whole batch, D2[n][m] = (sum_o W3[n][o]
@@ -614,7 +658,8 @@ constexpr unsigned kNarrowBelow = 48;
 constexpr int d1_ring(int KT) { return 2 * 32 * KT * D1_S > 4 * KT * 8 * 64 ? 2 * 32 * KT * D1_S : 4 * KT * 8 * 64; }      // floats: the ring, later the four waves' gW1 partials
 constexpr int d1_lds(int KT) { return (d1_ring(KT) + 1024 + 2 * BP + 8 + W1K * BP + W1K * 32 * KT) * 4; }
 
-template <int IN, int KT, bool TL, bool HP>
+// CLONE: the supervised update's instantiation (k_tp_d1_clone) takes the cloning head at compile time; otherwise NetArgs.head decides.
+template <int IN, int KT, bool TL, bool HP, bool CLONE = false>
 __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp)
 {
     typedef NetOf<IN> N;
@@ -636,6 +681,9 @@ __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const in
         const shems_group_hparams h = hp[by];
         d.gamma = h.gamma; d.batch = hp_batch(h);
         hp_adam(c, h, N::critic);
+        // (the quotient is formed on the vector ALU and lives to the kernel's end: left in vector registers it is the one value the narrow
+        // Flux-order form spills, 12 bytes of scratch in k_tp_d1_hp<SIN, 1, false>; the new instantiations keep it in scalar registers)
+        if constexpr (CLONE) c.k1 = uniform_f64(c.k1);
     }
     float *ws = d.ws;
     const float *__restrict__ P = c.p;
@@ -684,7 +732,8 @@ __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const in
     for (int s = 0; s < 6; ++s) xv[s] = X[s * 256 + tid];
 #pragma unroll
     for (int s = 0; s < WLN; ++s) { const int e = min(s * 256 + tid, W1K * KW - 1); wlv[s] = w1i[(e / KW) * W1C + k0 + e % KW]; }
-    if (A.head == 1) head_critic(A, d, c, d3s, red, kt == 0); else head_actor(A, d, c, d3s, red, kt == 0);
+    if constexpr (CLONE) head_clone(A, d, c, d3s, red, kt == 0);
+    else if (A.head == 1) head_critic(A, d, c, d3s, red, kt == 0); else head_actor(A, d, c, d3s, red, kt == 0);
     reinterpret_cast<f32x4 *>(w3s)[tid] = w3v;
 #pragma unroll
     for (int s = 0; s < 6; ++s) xs[s * 256 + tid] = xv[s];
@@ -1005,14 +1054,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTL == 4 ? 
 // profiles/r06_fwd_persistent_ab.txt.)
 // A learner's k-tile workgroups (T = 8 / KT of them) read the same 256 KB of relu(layer 2): they are placed on ONE XCD (workgroup id
 // mod 8 picks the XCD and its L2), consecutive in its dispatch order -- learner = 8 (q / T) + xcd, k-tile = q mod T with q = id / 8.
-template <int IN, int KT, bool TL, bool HP>
+template <int IN, int KT, bool TL, bool HP, bool CLONE = false>
 __device__ __forceinline__ void d1_entry(const NetArgs &A, float *smem, const shems_group_hparams *hp)
 {
     constexpr unsigned T = 8 / KT;
     const unsigned id = blockIdx.x, xcd = id & 7u, q = id >> 3;
     const unsigned learner = 8u * (q / T) + xcd;
     if (learner >= (unsigned)A.learners) return;
-    d1_body<IN, KT, TL, HP>(A, (int)(q % T), (int)learner, smem, hp);
+    d1_body<IN, KT, TL, HP, CLONE>(A, (int)(q % T), (int)learner, smem, hp);
 }
 template <int IN, int KT, bool TL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1(NetArgs A)
@@ -1051,6 +1100,98 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     gw2_body<IN, TL, true>(A, blockIdx.x, blockIdx.y, smem, hp);
+}
+
+// ================================================================================================================================
+// The grouped supervised and critic-only updates (shems_ddpg_group_clone_update_tp / _critic_update_tp): their own sampler and the
+// actor's D1 launch with the cloning head; every other launch of theirs is one of the kernels above.
+// The sampler shifts the ring by a stride of ITS OWN (demonstrations and an "mc" ring of returns live outside the learners' slabs);
+// the images come from prep_body's own roles.  Role 0 writes what prep_body's writes, from the same expressions (the critic-only update
+// leaves the bits of the update's critic half); CLONE reads s and a of a slot alone, leaves a_demo in TP_ADEMO and zeros in the action
+// rows of the input block (the actor's image has zeros there: the rows must only be finite), and freezes the actor's output layer alone.
+// grid (CLONE ? 2 : 5, learners): CLONE's workgroup 1 packs the actor's image.
+// ================================================================================================================================
+struct PrepRingArgs { PrepArgs p; int64_t rstride; };
+template <bool HP, bool CLONE>
+__device__ __forceinline__ void prep_ring_body(const PrepRingArgs &R, const int role, const int l, const shems_group_hparams *hp)
+{
+    const PrepArgs &A = R.p;
+    if (role > 0) { prep_body<HP>(A, CLONE ? 1 + NET_ACTOR : role, l, hp); return; }
+    const int tid = threadIdx.x;
+    shems_ddpg d = A.d;
+    shems_replay ring = A.ring;
+    gshift(d, (int64_t)l * A.gstride); gshift(ring, (int64_t)l * R.rstride);
+    float *ws = d.ws;
+    if constexpr (HP) d.batch = hp_batch(hp[l]);
+    const uint64_t seed = A.seed + (uint64_t)l;
+    if (tid < BP) {
+        const int m = tid;
+        const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)seed, (uint32_t)(seed >> 32));
+        const uint32_t w = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
+        const int64_t j = (int64_t)(w % (uint32_t)A.ring_len);
+        const bool live = m < d.batch;
+        float sv[SIN], s2v[SIN], lo[SIN], hi[SIN];
+#pragma unroll
+        for (int k = 0; k < SIN; ++k) {
+            sv[k] = ring.s[j * SIN + k]; lo[k] = d.s_min[k]; hi[k] = d.s_max[k];
+            if constexpr (!CLONE) s2v[k] = ring.s2[j * SIN + k];
+        }
+        const float a0 = ring.a[j * 2], a1 = ring.a[j * 2 + 1];
+#pragma unroll
+        for (int k = 0; k < SIN; ++k) {
+            const float den = (hi[k] - lo[k]) + 1e-8f;                                     // MPS:56
+            ws[TP_X + k * BP + m] = live ? (sv[k] - lo[k]) / den : 0.0f;
+            if constexpr (!CLONE) ws[TP_X2 + k * BP + m] = live ? (s2v[k] - lo[k]) / den : 0.0f;
+        }
+        ws[TP_X + 11 * BP + m] = 1.0f;
+        if constexpr (CLONE) {
+            ws[TP_X + 9 * BP + m] = 0.0f; ws[TP_X + 10 * BP + m] = 0.0f;
+            ws[TP_ADEMO + m] = live ? a0 : 0.0f;
+            ws[TP_ADEMO + BP + m] = live ? a1 : 0.0f;
+        } else {
+            const float rr = ring.r[j];
+            const bool dn = ring.done[j] != 0;
+            ws[TP_X + 9 * BP + m] = live ? a0 : 0.0f;
+            ws[TP_X + 10 * BP + m] = live ? a1 : 0.0f;
+            ws[TP_X2 + 9 * BP + m] = 0.0f; ws[TP_X2 + 10 * BP + m] = 0.0f; ws[TP_X2 + 11 * BP + m] = 1.0f;
+            ws[TP_R + m] = live ? rr : 0.0f;
+            ws[TP_DONE + m] = live && dn ? 1.0f : 0.0f;
+        }
+        reinterpret_cast<int32_t *>(ws + TP_IDX)[m] = live ? (int32_t)j : -1;
+    }
+    // frozen output layers
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int e = it * 256 + tid, n = e >> 1, o = e & 1;
+        ws[TP_FW3A + e] = n < H2N ? d.actor[off_w3(SIN) + min(e, 2 * H2N - 1)] : 0.0f;
+        if constexpr (!CLONE) ws[TP_FW3C + e] = (n < H2N && o == 0) ? d.critic[off_w3(CIN) + min(n, H2N - 1)] : 0.0f;
+    }
+    if constexpr (CLONE) {
+        if (tid < 2) ws[TP_FB3 + 2 + tid] = d.actor[off_b3(SIN, 2) + tid];
+    } else if (tid < 8)
+        ws[TP_FB3 + tid] = tid == 0 ? d.critic[off_b3(CIN, 1)] : tid == 1 ? d.critic_t[off_b3(CIN, 1)]
+                         : tid == 2 ? d.actor[off_b3(SIN, 2)] : tid == 3 ? d.actor[off_b3(SIN, 2) + 1]
+                         : tid == 4 ? d.actor_t[off_b3(SIN, 2)] : tid == 5 ? d.actor_t[off_b3(SIN, 2) + 1] : 0.0f;
+}
+template <bool CLONE>
+__global__ __launch_bounds__(256) void k_tp_prep_ring(PrepRingArgs R) { prep_ring_body<false, CLONE>(R, blockIdx.x, blockIdx.y, nullptr); }
+template <bool CLONE>
+__global__ __launch_bounds__(256) void k_tp_prep_ring_hp(PrepRingArgs R, const shems_group_hparams *hp)
+{
+    prep_ring_body<true, CLONE>(R, blockIdx.x, blockIdx.y, hp);
+}
+// the actor's D1 launch with the cloning head: d1_body's instantiation of its own, the twins of k_tp_d1<SIN, ..> / k_tp_d1_hp<SIN, ..>
+template <int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1_clone(NetArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<SIN, KT, TL, false, true>(A, smem, nullptr);
+}
+template <int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1_clone_hp(NetArgs A, const shems_group_hparams *hp)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<SIN, KT, TL, true, true>(A, smem, hp);
 }
 
 // (Round 5 also built two ways of running the HBM-bound phases (P4, P7) under the MFMA-bound ones (P1, P2, P5) of OTHER learners: cohorts
@@ -1269,6 +1410,108 @@ extern "C" int shems_ddpg_group_update_tp_x(const shems_ddpg *d, const shems_rep
     if (!d_hp || !d_xp || !d_pushed) return set_error(SHEMS_ERR_ARG, "shems_ddpg_group_update_tp_x: d_hp, d_xp and d_pushed are all required");
     auto *update = t ? group_update_tp<true, true> : group_update_tp<false, true>;
     return update(d, ring, g, t, d_hp, 1, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags, stream, d_xp, d_pushed);
+}
+
+// ---- the grouped supervised update (CLONE) and the grouped critic-only update: subsets of the launches above ----------------------
+//   CLONE   sampler | forward with the actor(s) job alone (one third of P1's grid) | the actor's D1 with the cloning head | the actor's gW2
+//   else    sampler | P1 with the actor_target(s') and critic(s, a) jobs | P2 | P3 | P4 -- the update's own kernels on the update's own
+//           inputs: the critic half of group_update_tp, bit for bit
+// The ring is learner 0's arrays + l * ring_stride bytes (its own stride: the rings need not live in the slabs).
+template <bool TL, bool HP, bool CLONE>
+static int group_half_tp(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride, const shems_group *g, const shems_group_w2t *t,
+                         const shems_group_hparams *hp, int64_t ring_len, uint64_t seed, uint32_t tick, double eta, double bp1, double bp2,
+                         int32_t flags, void *stream)
+{
+    const char *fn = CLONE ? "shems_ddpg_group_clone_update_tp" : "shems_ddpg_group_critic_update_tp";
+    if (int rc = check_group_tp(g, fn)) return rc;
+    if (ring_stride < 0 || (ring_stride & 3) != 0 || (g->count > 1 && ring_stride == 0))
+        return set_error(SHEMS_ERR_ARG, "%s: bad ring stride %lld: a non-negative multiple of 4 bytes, and not 0 for more than one learner", fn,
+                         (long long)ring_stride);
+    if (!d || !d->actor || !d->actor_t || !d->s_min || !d->s_max || !d->ws || !d->losses ||
+        (CLONE ? (!d->m_actor || !d->v_actor) : (!d->critic || !d->critic_t || !d->m_critic || !d->v_critic)))
+        return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
+    if ((flags & SHEMS_TP_STORE_GRAD) && !(CLONE ? d->grad_actor : d->grad_critic)) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs the gradient buffer", fn);
+    if (flags & ~SHEMS_TP_STORE_GRAD) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
+    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
+    if (HP && ((uintptr_t)hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (HP) eta = 0.0;                       // the *_hp kernels form k1 from the records
+    for (const float *p : {(const float *)d->actor, (const float *)d->actor_t, (const float *)d->ws, (const float *)(CLONE ? d->actor : d->critic),
+                           (const float *)(CLONE ? d->actor_t : d->critic_t)})
+        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
+    if (int rc = w2t_flux_guard(d->actor, fn)) return rc;       // (a single learner's own tiled mode, shems_ddpg_tiled_enter: not a group's t)
+    if (!ring || !ring->s || !ring->a || (!CLONE && (!ring->r || !ring->s2 || !ring->done)))
+        return set_error(SHEMS_ERR_ARG, CLONE ? "%s: the demonstration ring needs s and a" : "%s: the ring needs s, a, r, s2 and done", fn);
+    if (ring_len < 1 || ring_len > ring->capacity) return set_error(SHEMS_ERR_ARG, "%s: bad ring length", fn);
+    for (double bp : {bp1, bp2})
+        if (!(bp > 0.0 && bp < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
+    if (TL) if (int rc = check_w2t(t, fn)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned L = (unsigned)g->count;
+    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
+    const int sg = (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0;
+    float *ws = d->ws;
+    float *ta = TL ? t->actor : nullptr, *tc = TL ? t->critic : nullptr;
+    auto arr = [](float *region, int a) -> const float * { return region ? region + a * TL_TILE : nullptr; };
+    struct { PrepRingArgs pa; FwdArgs f1, f2; NetArgs n; } U;
+    std::memset(&U, 0, sizeof U);
+    U.pa = PrepRingArgs{PrepArgs{*d, *ring, ring_len, gs, seed, tick}, g->count > 1 ? ring_stride : 0};
+    for (FwdArgs *f : {&U.f1, &U.f2}) { f->gstride = gs; f->batch = d->batch; }
+    if (CLONE) {
+        U.f1.job[0] = FwdJob{arr(ta, TL_P), d->actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
+        U.n = NetArgs{*d, ta, AdamCtx{d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
+                                      eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau}, gs, 2, sg, (int)L};
+    } else {                                 // the jobs, P2 and the critic's NetArgs exactly as group_update_tp fills them
+        U.f1.job[0] = FwdJob{arr(ta, TL_T), d->actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
+        U.f1.job[1] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, NET_CRITIC), nullptr, nullptr, nullptr, ws + TP_H2C, p3_of(ws, NET_CRITIC), nullptr, CIN, 1};
+        U.f2.job[0] = FwdJob{arr(tc, TL_T), d->critic_t, ws + TP_X2, w1i_of(ws, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, nullptr, nullptr,
+                             p3_of(ws, NET_CRITIC_T), nullptr, CIN, 1};
+        U.n = NetArgs{*d, tc, AdamCtx{d->critic, d->grad_critic, d->m_critic, d->v_critic, d->critic_t, nullptr, SHEMS_CRITIC_PARAMS, (int)CIN,
+                                      eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau}, gs, 1, sg, (int)L};
+    }
+    typedef FwdShape<false, 4> SW;
+    typedef FwdShape<false, 2> SN;
+    const bool narrow = L < kNarrowBelow;
+    const unsigned g8 = 8 * ((L + 7) / 8);
+    constexpr unsigned JOBS = CLONE ? 1 : 2;
+    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args) {
+        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, hp);
+        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
+    };
+    launch(k_tp_prep_ring<CLONE>, k_tp_prep_ring_hp<CLONE>, dim3(CLONE ? 2 : 5, L), 0, U.pa);
+    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(JOBS * SN::TILES, L), SN::LDS, U.f1);
+    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(JOBS * SW::TILES, L), SW::LDS, U.f1);
+    if constexpr (CLONE) {
+        if (narrow) launch(k_tp_d1_clone<1, TL>, k_tp_d1_clone_hp<1, TL>, dim3(8 * g8), d1_lds(1), U.n);
+        else launch(k_tp_d1_clone<2, TL>, k_tp_d1_clone_hp<2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.n);
+        launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.n);
+    } else {
+        launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(SN::TILES, L), SN::LDS, U.f2);
+        if (narrow) launch(k_tp_d1<CIN, 1, TL>, k_tp_d1_hp<CIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.n);
+        else launch(k_tp_d1<CIN, 2, TL>, k_tp_d1_hp<CIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.n);
+        launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, U.n);
+    }
+    return hip_ok(hipGetLastError(), CLONE ? "grouped supervised update (throughput form) launches" : "grouped critic-only update (throughput form) launches");
+}
+template <bool CLONE>
+static int group_half_tp_pick(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride, const shems_group *g, const shems_group_w2t *t,
+                              const shems_group_hparams *hp, int64_t ring_len, uint64_t seed, uint32_t tick, double eta, double bp1, double bp2,
+                              int32_t flags, void *stream)
+{
+    auto *half = t ? (hp ? group_half_tp<true, true, CLONE> : group_half_tp<true, false, CLONE>)
+                   : (hp ? group_half_tp<false, true, CLONE> : group_half_tp<false, false, CLONE>);
+    return half(d, ring, ring_stride, g, t, hp, ring_len, seed, tick, eta, bp1, bp2, flags, stream);
+}
+extern "C" int shems_ddpg_group_clone_update_tp(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride_bytes, const shems_group *g,
+                                                const shems_group_w2t *t, const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed,
+                                                uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream)
+{
+    return group_half_tp_pick<true>(d, ring, ring_stride_bytes, g, t, d_hp, ring_len, seed, tick, eta, bp1, bp2, flags, stream);
+}
+extern "C" int shems_ddpg_group_critic_update_tp(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride_bytes, const shems_group *g,
+                                                 const shems_group_w2t *t, const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed,
+                                                 uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream)
+{
+    return group_half_tp_pick<false>(d, ring, ring_stride_bytes, g, t, d_hp, ring_len, seed, tick, eta, bp1, bp2, flags, stream);
 }
 
 static_assert(sizeof(shems_group_xparams) == 16 && offsetof(shems_group_xparams, ou_dt) == 4 && offsetof(shems_group_xparams, mem_size) == 8 &&

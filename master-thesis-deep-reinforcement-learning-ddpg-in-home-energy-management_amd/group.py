@@ -239,6 +239,9 @@ def _declare_group():
         getattr(L, fn).restype = C.c_int
     L.shems_group_eval_best_dev.argtypes = [PD, PG, PT, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]
     L.shems_group_eval_best_dev.restype = C.c_int
+    for fn in ("shems_ddpg_group_clone_update_tp", "shems_ddpg_group_critic_update_tp"):
+        getattr(L, fn).argtypes = [PD, PR, i64, PG, PT, vp, i64, u64, u32, dbl, dbl, dbl, i32, vp]
+        getattr(L, fn).restype = C.c_int
     for fn in ("shems_act_step_group_dev", "shems_ddpg_group_critic_grad", "shems_ddpg_group_critic_apply",
                "shems_ddpg_group_actor_grad", "shems_ddpg_group_actor_apply", "shems_minmax_group_dev"):
         getattr(L, fn).restype = C.c_int
@@ -415,6 +418,9 @@ class LearnerGroup:
             if self.noise_type == "ou":            # OUNoise.X = zeros(Float32, 2) per env; kept across episodes, as Agent.ou_state
                 self.ou_state = torch.zeros((self.n_envs, ACTION), dtype=torch.float32, device=self.device)
         self.updates = 0
+        self.clones = 0                            # grouped supervised updates (clone); they advance bp_actor, not `updates`
+        self.evaluations = 0                       # grouped critic-only updates (evaluate); they advance bp_critic, not `updates`
+        self._hp_variants = {}                     # record arrays of clone / evaluate with a tau of the call's: built once per (kind, tau)
         self.tick = 0
 
     def _hp_ptr(self):
@@ -610,6 +616,91 @@ class LearnerGroup:
             ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
             ag.updates += 1
         self.updates += 1
+
+    # ---- grouped imitation: the supervised and the critic-only update for every learner ------------------------------------------------
+    def _hp_variant(self, tau):
+        """The group's records with the call's tau in place of the learners' (clone, evaluate(tau=...)): a second device record array,
+        built and checked once per tau.  The kernels read the learner's batch and eta (and gamma) from it as from the group's own."""
+        tau = float(np.float32(tau))
+        if tau not in self._hp_variants:
+            arr = (HParams * self.count)(*[HParams(r["eta_act"], r["eta_crit"], r["gamma"], tau, r["mu"], r["sigma"], r["batch"], 0) for r in self.hparams])
+            if self.L.shems_group_hparams_check(arr, self.count) != _capi.OK:
+                raise ValueError(self.L.shems_last_error().decode("utf-8", "replace"))
+            self._hp_variants[tau] = self.torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+        return C.c_void_p(self._hp_variants[tau].data_ptr())
+
+    def _group_rings(self, rings, what):
+        """(ring objects, learner 0's shems_replay, ring stride in bytes, the shared length) of a clone / evaluate call: `rings` is an
+        imitation.GroupDemos / GroupRings (rings[l], struct0(), stride_bytes) or None, the group's own rings inside the slabs."""
+        if self.form == "wide":
+            raise NotImplementedError(f"{what}: the wide group form runs layer by layer (shems_wide_*), which has no {what} update")
+        if rings is None:
+            objs, r0, stride = self.rings, self._ring0(), self.slab_floats * 4
+        else:
+            if len(rings.rings) != self.count:
+                raise ValueError(f"{what}: {len(rings.rings)} rings for a group of {self.count} learners")
+            if rings.rings[0].s.device != self.device:
+                raise ValueError(f"{what}: the rings live on {rings.rings[0].s.device}, the group on {self.device}")
+            objs, r0, stride = rings.rings, rings.struct0(), int(rings.stride_bytes)
+        lens = sorted({len(r) for r in objs})
+        if len(lens) != 1:
+            raise ValueError(f"{what}: the rings hold unequal lengths ({lens[0]} .. {lens[-1]}): a grouped update samples every learner's "
+                             "ring with one shared length")
+        return objs, r0, stride, lens[0]
+
+    def _half_update(self, what, rings, tick, tau, critic):
+        objs, r0, stride, n = self._group_rings(rings, what)
+        if tau is not None and not 0.0 < float(tau) <= 1.0:
+            raise ValueError(f"{what}: tau {tau} outside (0, 1]")
+        a0 = self.learners[0]
+        count = self.evaluations if critic else self.clones
+        tick = count if tick is None else tick
+        if self.form == "throughput" or self._hp_dev is not None:
+            tl = self._use_tiled()
+            d, g = a0._ddpg_args(), self.struct()
+            if tau is not None:
+                d.tau = float(tau)
+            hp = None if self._hp_dev is None else (self._hp_ptr() if tau is None else self._hp_variant(tau))
+            t = C.byref(self.w2t_struct()) if tl else None
+            fn = self.L.shems_ddpg_group_critic_update_tp if critic else self.L.shems_ddpg_group_clone_update_tp
+            adam = (a0.eta_crit, *a0.bp_critic) if critic else (a0.eta_act, *a0.bp_actor)
+            _capi.check(fn(C.byref(d), C.byref(r0), stride, C.byref(g), t, hp, n, self.rng_seed, int(tick) & 0xFFFFFFFF, *adam,
+                           1 if self.store_grad else 0, self._stream()))
+            if tl:
+                self._flux_valid = False
+            for ag in self.learners:               # the learners advance in lockstep, as in replay()
+                if critic:
+                    ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
+                    ag.evaluations += 1
+                else:
+                    ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
+                    ag.clones += 1
+        else:                                      # latency form: the single-learner call on every learner's views, the same bits
+            self._use_tiled()
+            for ag, ring in zip(self.learners, objs):
+                ag.evaluate(ring, tick=tick, tau=tau) if critic else ag.clone(ring, tick=tick, tau=tau)
+        if critic:
+            self.evaluations += 1
+        else:
+            self.clones += 1
+
+    def clone(self, demos, tick=None, tau=1.0):
+        """One SUPERVISED update of every learner's actor on its own demonstration ring (imitation.GroupDemos): Agent.clone's definition,
+        loss_l = Flux.mse(actor_l(normalize(s)), a_demo) on the first batch_l draws of the stream (rng_seed + l, tick).  Throughput form:
+        four launches for the whole group (shems_ddpg_group_clone_update_tp), with per-learner records the learner's eta_act and batch
+        and the call's tau; latency form: learners[l].clone(demos.rings[l]) learner by learner; wide form: NotImplementedError.
+        Nothing of the critics is touched.  tau = 1.0 keeps every actor_t equal to its actor bit for bit.  bp_actor advances in lockstep
+        as in replay(); the step counts in `clones` (the default tick), `updates` does not move.  On a tiled group the Flux-order view
+        goes stale, as after replay().  Demonstration rings of unequal length are refused."""
+        self._half_update("clone", demos, tick, tau, critic=False)
+
+    def evaluate(self, rings=None, tick=None, tau=None):
+        """One CRITIC-ONLY update of every learner (Agent.evaluate's definition) from `rings` -- an imitation.GroupRings, or None for the
+        group's own rings.  Throughput form: five launches, the update's own kernels (shems_ddpg_group_critic_update_tp): from the same
+        state, ring, seed and tick the critic side holds the bits replay() leaves there, and nothing of the actors is touched.  Latency
+        form: learners[l].evaluate(rings.rings[l]); wide form: NotImplementedError.  tau: None = the learners' own.  bp_critic advances
+        in lockstep; the step counts in `evaluations` (the default tick)."""
+        self._half_update("evaluate", rings, tick, tau, critic=True)
 
     def ring_window(self, num_steps=72, window_count=None):
         """(count, offset) of the transitions each learner stores at the CURRENT tick.

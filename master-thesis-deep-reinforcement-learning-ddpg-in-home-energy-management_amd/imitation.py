@@ -19,6 +19,10 @@ that knows nothing.  Three more pieces join the two (the definition: fs_transiti
     critic can be regressed on it without bootstrapping from itself;
   * the critic-only update: ddpg.Agent.evaluate (shems_ddpg_critic_update, three launches, the actor is left alone);
   * warm_start: dagger, one pass of the resulting actor, its transitions, and a number of critic-only updates on them.
+
+The same for a learner group (group.LearnerGroup.clone / evaluate: every learner's update in four / five launches): GroupDemos and
+GroupRings hold one ring per learner in one allocation with a constant stride, dagger_group and warm_start_group run the rounds for
+all learners at once (one tracking launch and one audit per round; the passes go into the rings learner by learner).
 """
 from __future__ import annotations
 
@@ -35,8 +39,59 @@ class Demos(ReplayRing):
     and a are ever written (r, s2 and done stay zero and are never read), and its length grows with what was written -- `pushed`
     counts the pairs, the next one goes to slot `pos`."""
 
-    def __init__(self, capacity, device=None):
-        super().__init__(capacity, device=device)
+    def __init__(self, capacity, device=None, tensors=None):
+        super().__init__(capacity, device=device, tensors=tensors)
+
+
+def ring_slab_floats(capacity):
+    """(offsets, floats) of one learner's ring arrays inside a GroupDemos / GroupRings allocation: s [capacity][9], a [capacity][2],
+    r [capacity], s2 [capacity][9], done [capacity] bytes, every array on a 16-byte boundary.  Host arithmetic only."""
+    capacity = int(capacity)
+    if capacity < 1:
+        raise ValueError(f"a ring needs capacity >= 1, not {capacity}")
+    offs, off = {}, 0
+    for name, n in (("s", capacity * _capi.NSTATE), ("a", capacity * _capi.NACTION), ("r", capacity), ("s2", capacity * _capi.NSTATE),
+                    ("done", (capacity + 3) // 4)):
+        offs[name] = (off, n)
+        off = (off + n + 3) & ~3
+    return offs, off
+
+
+class GroupRings:
+    """`count` replay rings of `capacity` slots as views of ONE allocation with a constant stride: ring l's arrays are ring 0's plus
+    l * stride_bytes, which is what LearnerGroup.evaluate hands to shems_ddpg_group_critic_update_tp (rings[l], struct0(),
+    stride_bytes).  rings[l] is an ordinary ReplayRing: imitation.transitions fills it, Agent.evaluate takes it.  Such a ring lives
+    outside the learners' slabs: an "mc" ring of returns (done = 1 in every slot) must never be the ring bootstrapped training samples,
+    so it is never the group's own."""
+    ring_class = ReplayRing
+
+    def __init__(self, count, capacity, device=None):
+        import torch
+        self.count, self.capacity = int(count), int(capacity)
+        if self.count < 1:
+            raise ValueError(f"a ring group needs count >= 1, not {count}")
+        self.layout, self.floats = ring_slab_floats(self.capacity)
+        self.stride_bytes = 4 * self.floats
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.slab = torch.zeros((self.count, self.floats), dtype=torch.float32, device=self.device)
+        self.rings = []
+        for l in range(self.count):
+            v = lambda name: self.slab[l, self.layout[name][0]:self.layout[name][0] + self.layout[name][1]]
+            tens = (v("s").view(self.capacity, _capi.NSTATE), v("a").view(self.capacity, _capi.NACTION), v("r"),
+                    v("s2").view(self.capacity, _capi.NSTATE), v("done").view(torch.uint8)[:self.capacity])
+            self.rings.append(self.ring_class(self.capacity, tensors=tens))
+
+    def struct0(self):
+        return self.rings[0].struct()
+
+    def __len__(self):
+        return self.count
+
+
+class GroupDemos(GroupRings):
+    """`count` Demos rings in one allocation (GroupRings' layout): learner l's demonstrations for LearnerGroup.clone.  Every imitation
+    function that takes a Demos takes rings[l]."""
+    ring_class = Demos
 
 
 def _declare(L):
@@ -257,6 +312,106 @@ def warm_start(agent, env, values, demos, ring, rounds, steps_per_round, critic_
             last = float(agent.losses[0].item())
             first = last if k == 0 else first
     return out + [{"critic_loss_first": first, "critic_loss_last": last, "transitions": len(ring)}]
+
+
+def _group_check(grp, env, demos, what):
+    if env.n != grp.count:
+        raise ValueError(f"{what}: the env batch holds {env.n} envs for a group of {grp.count} learners (one env per learner, env l on "
+                         "learner l's table and config)")
+    if len(demos.rings) != grp.count:
+        raise ValueError(f"{what}: {len(demos.rings)} rings for a group of {grp.count} learners")
+
+
+def _group_passes(grp, env, values):
+    """Every learner's CURRENT actor through one harness.inference_many launch, env l with learner l's actor and normalisation."""
+    from . import harness
+    grp.flux_()
+    o, n = grp.layout["actor"]
+    lo, hi = grp.layout["s_min"][0], grp.layout["s_max"][0]
+    return harness.inference_many(env, grp.slab[:, o:o + n], grp.slab[:, lo:lo + _capi.NSTATE], grp.slab[:, hi:hi + _capi.NSTATE],
+                                  num_steps=values.nsteps)
+
+
+def _group_losses(grp, k):
+    """losses[k] of every learner, [count] float64 on the host (one copy)."""
+    o = grp.layout["losses"][0]
+    return grp.slab[:, o + k].cpu().numpy().astype(np.float64)
+
+
+def dagger_group(grp, env, values, demos, rounds, steps_per_round, tau=1.0):
+    """dagger for a learner group: `env` holds ONE env per learner (env l on learner l's table and config), `values` one problem per
+    distinct config (harness.foresight_values(env)), `demos` a GroupDemos.
+      round 0          the foresight pass of every env (one foresight.track), learner l's pass into demos.rings[l] with the targets it
+                       chose; learner l's normalisation is what learners[l].min_max_buffer(demos.rings[l]) sets;
+      round r >= 1     grp.flux_(), all current actors through ONE harness.inference_many launch, ONE foresight.audit over the count
+                       passes, and pass l appended to demos.rings[l] with the audit's labels.
+    The passes go into the rings learner by learner (count calls of shems_foresight_demos_dev per round); then `steps_per_round`
+    grp.clone(demos, tau=tau) steps follow.  Returns one dict per round: "return" [count] (round 0: the foresight passes', later: of
+    the actors the round started with), "loss_first" / "loss" [count] (losses[1] after the round's first and last step), "demos" (the
+    rings' shared length) and "host_s" (wall time of the round's tracking, audit and demos calls, which synchronise)."""
+    import time
+    rounds, steps = int(rounds), int(steps_per_round)
+    if rounds < 1 or steps < 1:
+        raise ValueError(f"dagger_group: {rounds} rounds x {steps} steps; at least one of each")
+    _check_values(values, "dagger_group")
+    _group_check(grp, env, demos, "dagger_group")
+    out = []
+    for r in range(rounds):
+        t0 = time.perf_counter()
+        env.use_torch_stream()
+        env.reset_(-1)
+        _, _, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+        po = (lambda l: poe[l:l + 1]) if values.n_problems > 1 else (lambda l: None)
+        if r == 0:
+            total, res, targets = foresight.track(env, values, poe, which=-1)
+            for l in range(grp.count):
+                _write(values, res[l:l + 1], po(l), demos.rings[l], targets=targets[l:l + 1])
+                grp.learners[l].min_max_buffer(demos.rings[l])
+        else:
+            total, res = _group_passes(grp, env, values)
+            audit = foresight.audit(values, res, poe if values.n_problems > 1 else None)
+            for l in range(grp.count):
+                _write(values, res[l:l + 1], po(l), demos.rings[l], best_action=audit.best_action[l:l + 1])
+        host_s = time.perf_counter() - t0
+        first = None
+        for k in range(steps):
+            grp.clone(demos, tau=tau)
+            if k == 0:
+                first = _group_losses(grp, 1)
+        last = _group_losses(grp, 1) if steps > 1 else first
+        out.append({"return": np.asarray(total, np.float64).copy(), "loss_first": first, "loss": last, "demos": len(demos.rings[0]),
+                    "host_s": host_s})
+    return out
+
+
+def warm_start_group(grp, env, values, demos, ring, rounds, steps_per_round, critic_steps, mode="mc", tau=1.0):
+    """warm_start for a learner group: dagger_group as it stands, then one pass of every resulting actor (one inference_many launch),
+    imitation.transitions of pass l into ring.rings[l] (`ring`: a GroupRings; None: the group's own rings, "td" only, which then go
+    straight on as the replay rings) in `mode`, and `critic_steps` grp.evaluate(ring) steps.
+    An "mc" ring (done = 1, returns as rewards) must not be the ring bootstrapped training samples: the group's own rings are refused.
+    Returns dagger_group's per-round records followed by one dict {"critic_loss_first", "critic_loss_last"} ([count] arrays:
+    losses[0] after the first and the last critic step) and "transitions" (the rings' shared length)."""
+    critic_steps = int(critic_steps)
+    if critic_steps < 1:
+        raise ValueError(f"warm_start_group: {critic_steps} critic steps; at least one")
+    if mode not in TRANSITION_MODES:
+        raise ValueError(f"warm_start_group: mode {mode!r} is neither 'td' nor 'mc'")
+    rings = grp.rings if ring is None else ring.rings          # None: the group's own rings ("td": they go straight on as the replay rings)
+    _group_check(grp, env, grp if ring is None else ring, "warm_start_group")
+    if mode == "mc" and any(a is b for a, b in zip(rings, grp.rings)):
+        raise ValueError("warm_start_group: an 'mc' ring holds returns with done = 1 and must not be the group's training ring")
+    out = dagger_group(grp, env, values, demos, rounds, steps_per_round, tau=tau)
+    _, res = _group_passes(grp, env, values)
+    _, _, poe = foresight.problems_of_env(env, np.ones(env.n, np.int64))
+    for l in range(grp.count):
+        transitions(values, res[l:l + 1], rings[l], poe[l:l + 1] if values.n_problems > 1 else None, mode=mode, gamma=grp.learners[l].gamma)
+    first = last = None
+    for k in range(critic_steps):
+        grp.evaluate(ring)
+        if k == 0 or k == critic_steps - 1:
+            last = _group_losses(grp, 0)
+            first = last if k == 0 else first
+    return out + [{"critic_loss_first": first, "critic_loss_last": last, "transitions": len(rings[0])}]
 
 
 IMITATION_HEADER = ["round", "return", "loss", "demos"]
