@@ -346,6 +346,41 @@ int shems_ddpg_clone_update(const shems_ddpg *d, const shems_replay *ring, int64
  * validation as shems_ddpg_update's for the critic. */
 int shems_ddpg_critic_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                              double eta, double bp1, double bp2, void *stream);
+/* ------------------------------------------------------------ TD3 update -- */
+/* One update of TD3 (Fujimoto, van Hoof, Meger 2018: twin critics, target-policy smoothing, delayed actor) in this library's
+ * conventions: Float32 arithmetic, Flux 0.12.1 ADAM, the order of replay() (DDPG.jl:121-145), the minibatch of
+ * shems_ddpg_sample_indices(seed, tick).  The reference carries the hyper-parameter (noise_trg = 0.2f0, input.jl:231) and no algorithm
+ * file; the definition is this one:
+ *   1. gather and normalise the minibatch as replay() does (columns m >= batch are padding and enter no sum);
+ *   2. (z0, z1)[m] = Box-Muller on words x, y of the Philox4x32-10 block at counter (m, 0, tick, 0x5452474E), key seed (the act
+ *      noise's transform on a stream tag of its own); eps = clamp(sigma_trg z, -clip_trg, clip_trg);
+ *      a~' = clamp(actor_t(s'_n) + eps, -1, 1);
+ *   3. q'_i = critic_i_t([s'_n; a~']), y = r + gamma (1 - done) min(q'_1, q'_2) -- one y for both critics;
+ *   4. each critic i: gradient of Flux.mse(critic_i([s_n; a]), y), ADAM(eta_crit) with its own moments and the shared powers;
+ *      losses[0] and losses2[0] receive the two mse values;
+ *   5. update_policy = 1: the actor's gradient of -mean(critic_1([s_n; actor(s_n)])) through the UPDATED critic 1 (DDPG.jl:137-140),
+ *      ADAM(eta_act), losses[1]; soft updates of actor_t, critic_t and critic2_t with tau.
+ *      update_policy = 0: actor, actor_t, m_actor, v_actor, grad_actor and losses[1] are not touched, and both critic targets keep
+ *      their values (the soft update runs with tau = 0: 1 t + 0 p).
+ * The beta powers are host state as for shems_ddpg_update: the critics' advance on every update, the actor's on policy steps.
+ * `d` is the learner exactly as shems_ddpg_update takes it (actor + critic 1, Flux order); the second critic has blocks of its own
+ * [129001], which must not overlap critic 1's.  ws2: shems_td3_workspace_floats() floats, zeroed once; after an update it begins
+ * with a~' [2][128], y [128], q'_1 [128], q'_2 [128].  Three dependent launches, five on a policy step (csrc/shems_ddpg.hip).
+ * SHEMS_ERR_ARG, nothing launched: whatever shems_ddpg_update refuses; a NULL, misaligned or overlapping critic-2 buffer; sigma_trg or
+ * clip_trg negative or not finite; update_policy outside {0, 1}.  SHEMS_ERR_STATE: a learner between shems_ddpg_tiled_enter and
+ * shems_ddpg_tiled_leave.  With sigma_trg = 0 and critic 2 a copy of critic 1, update_policy = 1 leaves shems_ddpg_update's bits. */
+typedef struct shems_td3 {
+    shems_ddpg d;                                   /* actor + critic 1, as for shems_ddpg_update                     */
+    float *critic2, *critic2_t;                     /* [129001] each                                                 */
+    float *m_critic2, *v_critic2, *grad_critic2;    /* [129001] each                                                 */
+    float *ws2;                                     /* shems_td3_workspace_floats() floats, zeroed once              */
+    float *losses2;                                 /* [1] out: mse of critic 2                                      */
+    float sigma_trg, clip_trg;                      /* 0.2 (input.jl:231), 0.5                                       */
+} shems_td3;
+int shems_td3_workspace_floats(int64_t *out);
+int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                     double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act,
+                     int update_policy, void *stream);
 /* The minibatch indices of (seed, tick): host helper for tests (same Philox as the device). */
 int shems_ddpg_sample_indices(uint64_t seed, uint32_t tick, int32_t batch, int64_t ring_len, int64_t *out);
 /* ------------------------------------------ data-parallel replicas -- */

@@ -32,6 +32,9 @@
 // Other rules kept from round 1: operands staged into LDS with wide independent loads, ALL of a phase's global loads issued
 // before the first wait, clamped and never predicated; partial slabs summed in a fixed order (bitwise reproducible; no float
 // atomics, no device-scope fences).
+// TD3 (shems_td3_update) is built from the same bodies: K1 with a second critic's job, K2 with both target critics on the smoothed
+// target action and both critics' E products, K3 on a doubled grid with the twin head; its actor side is K4 + K5 as they are.  See the
+// block in front of k_fwd_td3.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -40,6 +43,7 @@
 #include "philox.h"
 #include "shems_internal.h"
 #include "shems_adam.h"
+#include "shems_td3_core.h"
 
 namespace shems {
 
@@ -252,6 +256,32 @@ __device__ __forceinline__ void xt_store(const XSrc &s, const XTRegs<IN> &R, int
     }
 }
 
+// TD3 (shems_td3_update): the action rows of the TARGET critics' input are the smoothed target action a~' = clamp(tanh(...) + eps, -1, 1),
+// eps from the target-noise stream of (seed, tick) -- shems_td3_core.h holds the arithmetic; the Box-Muller transform is gauss_pair's of
+// shems_policy.hip on that stream.  xt_store's compile-time sibling: same loads (xt_load), same summation order, so sigma_trg = 0 gives
+// xt_store's bits.  Both target critics form the same a~'; the publisher of the first stores it for the tests and the host.
+struct Td3Noise { uint64_t seed; uint32_t tick; float sigma, clip; };
+__device__ __forceinline__ void xt_store_smooth(const XSrc &s, const XTRegs<CIN> &R, int mbase, float *xs /*LDS [12][32]*/, bool publisher, const Td3Noise &tn)
+{
+    const int tid = threadIdx.x;
+    xs[tid] = R.v[0];
+    xs[256 + (tid & 31)] = R.v[1];
+    if (tid < 32) xs[11 * 32 + tid] = 1.0f;                                       // bias row
+    if (tid < 64) {
+        float acc = R.ab[1];
+#pragma unroll
+        for (int q = 0; q < NT; ++q) acc += R.p[q];
+        const int o = tid >> 5, m = mbase + (tid & 31);
+        const u32x4 x = td3_block(tn.seed, tn.tick, (uint32_t)m);
+        const float r = sqrtf(-2.0f * logf(td3_u1(x)));
+        float sn, cs;
+        sincosf(6.28318530717958647692f * td3_u2(x), &sn, &cs);
+        const float a = td3_smooth(tanhf(acc), td3_eps(tn.sigma, tn.clip, o == 0 ? r * cs : r * sn));
+        if (publisher && s.publish) s.publish[o * BP + m] = a;
+        xs[SIN * 32 + tid] = a;
+    }
+}
+
 // Layer 1 also runs on the matrix pipe: pre[k][m] = sum_j w1m[j][k] * xs[j][m] with K = 12 = 6 MFMA k-steps, where
 //   w1m [12][256] = rows 0..in-1: W1[j][k]; row 11: b1[k]; everything else (rows in..10, columns 250..255) zero
 //   xs  [12][BP]  = rows 0..in-1: the network input; row 11: 1.0 (bias); rows in..10 zero.
@@ -428,8 +458,8 @@ template <bool QG> struct FwdShape {
     static constexpr int LDS = (256 * WST + W1K * 32 + W1K * W1C + 256 + 4 * 16 * 64 + 4 * 2 * 32 + (QG ? 32 * 32 + 4 * 2 * 32 : 0)) * 4;
 };
 
-template <int IN, int PREP, bool QG, bool CLONE = false, bool TILED = false>
-__device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const PrepArgs *pa, int bx, int job)
+template <int IN, int PREP, bool QG, bool CLONE = false, bool TILED = false, bool SMOOTH = false>
+__device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const PrepArgs *pa, int bx, int job, const Td3Noise *tn = nullptr)
 {
     typedef FwdShape<QG> SH;
     constexpr int WST = SH::WST;
@@ -523,7 +553,8 @@ __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const Pre
     if (PREP == 1) {
         if (tid < 32) prep_store(*pa, mbase + tid, xs, tid, 32, J.which, false, pr);
     } else {
-        xt_store<IN>(J.x, xr, mbase, xs, ntile == 0);          // (the four column tiles of n-tile 0 publish actor(s) between them)
+        if constexpr (SMOOTH) xt_store_smooth(J.x, xr, mbase, xs, ntile == 0, *tn);     // TD3's target critics: [s'; a~']
+        else xt_store<IN>(J.x, xr, mbase, xs, ntile == 0);     // (the four column tiles of n-tile 0 publish actor(s) between them)
     }
     if (PREP == 0) stage_w1m_store(wr, w1); else pack_w1m_store(pk, IN, w1);
     ep[tid] = epv * ep_keep;                   // unconditional (threads >= 96 write copies of entry 95 into the unused slots): a store under
@@ -1214,6 +1245,76 @@ __device__ __forceinline__ void head_clone(const shems_ddpg &d, const HeadRegs &
     }
 }
 
+// ---- TD3: the second workspace block and the twin head (shems_td3_update) --------------------------------------------------
+// ws2 carve (floats).  The first four arrays are what shems_hip.h promises a caller can read after an update.
+constexpr int64_t W2_AT = 0;                          // [2][BP]  a~' = clamp(actor_t(s') + eps, -1, 1)
+constexpr int64_t W2_Y = W2_AT + AIN * BP;            // [BP]     y = r + gamma (1 - done) min(q'1, q'2)
+constexpr int64_t W2_QT1 = W2_Y + BP;                 // [BP]     q'1 = critic_t([s'; a~'])
+constexpr int64_t W2_QT2 = W2_QT1 + BP;               // [BP]     q'2 = critic2_t([s'; a~'])
+constexpr int64_t W2_Q = W2_QT2 + BP;                 // [BP]     critic2([s; a])
+constexpr int64_t W2_D3C = W2_Q + BP;                 // [BP]     dq of critic 2's loss
+constexpr int64_t W2_FW3C = W2_D3C + BP;              // [512]    frozen critic2 W3 (rows >= 500 zero)
+constexpr int64_t W2_FB3 = W2_FW3C + 512;             // [8]      frozen b3: critic2, critic2_t
+constexpr int64_t W2_W1T = W2_FB3 + 8;                // [2][12][256] packed layer-1 images: critic2_t, critic2
+constexpr int64_t W2_PT = W2_W1T + 2 * 12 * 256;      // [NT][2][BP]  layer-3 partials of critic2_t
+constexpr int64_t W2_SLOT = W2_PT + NT * 2 * BP;      // critic2's slot: SL_H2, SL_P3, SL_EP
+constexpr int64_t W2_FLOATS = W2_SLOT + SL_SIZE;
+static_assert(W2_W1T % 4 == 0 && W2_SLOT % 4 == 0 && W2_FW3C % 4 == 0, "16-byte aligned blocks");
+
+// The twin head, in the prologue of every workgroup of k_grad_td3 (head_loss's compile-time sibling): both target critics' layer-3
+// partials and frozen b3 give q'1 and q'2, their minimum gives y (the same y for both critics), the differentiated critic's own
+// partials give q; d3[0][m] = 2 (q - y) / B.  Summation orders are head_loss's.  Workgroup 0 of each critic's half publishes.
+struct TwinHead {
+    const float *Pt1, *Pt2;            // [NT][2][BP] partials of critic_t, critic2_t on [s'; a~']
+    const float *Pc;                   // [NT][2][BP] partials of the differentiated critic on [s; a]
+    const float *b3t1, *b3t2, *b3c;    // frozen copies (K1)
+    float *y, *q, *dq;                 // [BP] each, published
+    float *qt1, *qt2;                  // [BP] each, or null
+};
+struct TwinRegs { float v[3 * NT]; float s[5]; };
+__device__ __forceinline__ void head_twin_load(const shems_ddpg &d, const TwinHead &h, TwinRegs &R)
+{
+    const float *ws = d.ws;
+    const int m = threadIdx.x & 127;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) { R.v[i] = h.Pt1[(i * 2) * BP + m]; R.v[NT + i] = h.Pt2[(i * 2) * BP + m]; R.v[2 * NT + i] = h.Pc[(i * 2) * BP + m]; }
+    R.s[0] = h.b3t1[0];
+    R.s[1] = h.b3t2[0];
+    R.s[2] = h.b3c[0];
+    R.s[3] = ws[WS_R + m];
+    R.s[4] = ws[WS_DONE + m];
+}
+__device__ __forceinline__ void head_twin(const shems_ddpg &d, const TwinHead &h, const TwinRegs &R, float *d3 /*LDS [2][BP]*/, float *red /*LDS [8]*/,
+                                          bool publisher, const AdamCtx *fuse)
+{
+    const int t = threadIdx.x, m = t & 127;
+    float dq = 0.0f, diff = 0.0f;
+    if (t < BP) {
+        float q1 = R.s[0], q2 = R.s[1], q = R.s[2];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) { q1 += R.v[i]; q2 += R.v[NT + i]; q += R.v[2 * NT + i]; }
+        const float y = td3_y(R.s[3], d.gamma, R.s[4], td3_min(q1, q2));
+        diff = m < d.batch ? q - y : 0.0f;
+        dq = 2.0f * diff / (float)d.batch;                                                  // d mse / d q
+        if (publisher) {
+            h.y[m] = y; h.q[m] = q; h.dq[m] = dq;
+            if (h.qt1) { h.qt1[m] = q1; h.qt2[m] = q2; }
+        }
+    }
+    d3[t] = t < BP ? dq : 0.0f;
+    if (publisher) {
+        const float s1 = wave_sum(diff * diff), s2 = wave_sum(dq);
+        if ((t & 63) == 0) { red[t >> 6] = s1; red[4 + (t >> 6)] = s2; }
+        __syncthreads();
+        if (t == 0) {
+            d.losses[0] = (red[0] + red[1]) / (float)d.batch;                               // Flux.mse
+            const float g = red[4] + red[5];
+            d.grad_critic[off_b3(CIN, 1)] = g;
+            if (fuse) adam_elem(*fuse, off_b3(CIN, 1), g);
+        }
+    }
+}
+
 // ---- K3 / K5: every gradient block of one network, by batch contractions only -------------------------------------------
 // D2[n][m] = (sum_o W3[n][o] d3[o][m]) * (h2[n][m] > 0) is generated while staging, never stored.
 //   W workgroups (kt, nt): gW2[32 k][32 n] = sum_m h1[k][m] D2[n][m], one 16 x 16 block per wave over the whole batch
@@ -1307,8 +1408,8 @@ __device__ __forceinline__ void l1row_wave(const L1Row<IN, OUT> &R, const float 
 }
 
 // CLONE: the supervised update's instantiation (k_grad_clone) takes the cloning head at compile time; otherwise GradArgs.head decides.
-template <int IN, int OUT, bool CLONE = false, bool TILED = false>
-__device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx)
+template <int IN, int OUT, bool CLONE = false, bool TILED = false, bool TWIN = false>
+__device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx, const TwinHead *th = nullptr)
 {
     // bx: this workgroup's index within the gradient grid
     float *Bt = smem;                          // W: [32 n][GR_PS] D2 panel
@@ -1335,10 +1436,13 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
         HeadRegs hr;
         L1Row<IN, OUT> R;
         l1row_load<IN, OUT>(A, min(k, H1N - 1), lane, R);
-        if constexpr (CLONE) head_clone_load(A.dd, hr);
+        [[maybe_unused]] TwinRegs tr;
+        if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
+        else if constexpr (CLONE) head_clone_load(A.dd, hr);
         else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
         STAMP(kRegion, 1);
-        if constexpr (CLONE) head_clone(A.dd, hr, d3, red, false, nullptr);
+        if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, false, nullptr);
+        else if constexpr (CLONE) head_clone(A.dd, hr, d3, red, false, nullptr);
         else if (A.head == 1) head_loss(A.dd, hr, d3, red, false, nullptr); else head_actor(A.dd, hr, d3, red, false, nullptr);
         __syncthreads();
         STAMP(kRegion, 2);
@@ -1404,13 +1508,16 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
         w3v = A.w3f[(nrow0 + (t >> 1)) * OUT + min(o, OUT - 1)];                              // frozen copy: 512 rows, zero padded
     }
     HeadRegs hr;
-    if constexpr (CLONE) head_clone_load(A.dd, hr);
+    [[maybe_unused]] TwinRegs tr;
+    if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
+    else if constexpr (CLONE) head_clone_load(A.dd, hr);
     else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
     if (is_w) {
         build_x_store<IN>(A.x, xr, xs, false);
         if (tid < 96) *reinterpret_cast<f32x4 *>(w1 + (tid >> 3) * 32 + 4 * (tid & 7)) = wq;
     }
-    if constexpr (CLONE) head_clone(A.dd, hr, d3, red, publisher, fz);
+    if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, publisher, fz);
+    else if constexpr (CLONE) head_clone(A.dd, hr, d3, red, publisher, fz);
     else if (A.head == 1) head_loss(A.dd, hr, d3, red, publisher, fz); else head_actor(A.dd, hr, d3, red, publisher, fz);
     if (tid < 2 * 32) w3s[tid] = (tid & 1) < OUT ? w3v : 0.0f;
     STAMP(kRegion, 1);
@@ -1653,6 +1760,60 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     if (A.in == SIN) grad_body<SIN, 2, false, true>(A, smem, (int)blockIdx.x); else grad_body<CIN, 1, false, true>(A, smem, (int)blockIdx.x);
 }
 
+// ---- TD3 (shems_td3_update): the three launches of the twin-critic side, instantiations of their own behind the others (see
+// k_fwd_clone).  Both critics ride in the same launches; the actor side of a policy step is replay()'s own K4 + K5 (k_fwd, k_grad).
+//   T1  k_fwd_td3   actor_t(s') | critic(s, a) | critic2(s, a) [| actor(s) on a policy step]      K1 with up to four jobs
+//   T2  k_mid_td3   critic_t(s', a~') | critic2_t(s', a~') | E_c | E_c2 [| E_a0, E_a1]            both target passes smooth the action
+//   T3  k_grad_td3  critic | critic2: every gradient block + ADAM + soft update (tau = 0 off a policy step), the twin head in front
+// T1's job 0 does K1's publishing duties as they are; the publishing workgroups of job 1, idle in K1, do the second critic's: the
+// layer-1 images of critic2_t and critic2 and the frozen output layer of critic2 go to ws2.
+struct Td3FwdArgs { FwdJob job[4]; PrepArgs pa; const float *c2, *c2t; float *ws2; };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_fwd_td3(Td3FwdArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int kTiles = NT * (BP / 32), kPerJob = kTiles + 6;
+    const int job = (int)blockIdx.x / kPerJob, bx = (int)blockIdx.x - job * kPerJob, tid = threadIdx.x;
+    if (job == 1 && bx >= kTiles) {
+        const int duty = bx - kTiles;
+        float *ws2 = A.ws2;
+        if (duty == 1) pack_w1m(A.c2t, CIN, ws2 + W2_W1T);
+        else if (duty == 2) pack_w1m(A.c2, CIN, ws2 + W2_W1T + 12 * 256);
+        else if (duty == 3) {
+            for (int e = tid; e < 512; e += 256) ws2[W2_FW3C + e] = e < H2N ? A.c2[off_w3(CIN) + e] : 0.0f;
+            if (tid < 8) ws2[W2_FB3 + tid] = tid == 0 ? A.c2[off_b3(CIN, 1)] : tid == 1 ? A.c2t[off_b3(CIN, 1)] : 0.0f;
+        }
+        return;
+    }
+    const FwdJob J = job == 0 ? A.job[0] : job == 1 ? A.job[1] : job == 2 ? A.job[2] : A.job[3];
+    const PrepArgs pa = A.pa;
+    if (J.in == SIN) fwd_body<SIN, 1, false>(J, smem, &pa, bx, job); else fwd_body<CIN, 1, false>(J, smem, &pa, bx, job);
+}
+struct Td3MidArgs { FwdJob fwd[2]; EJob e[4]; Td3Noise tn; };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_mid_td3(Td3MidArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int kTiles = NT * (BP / 32);
+    if ((int)blockIdx.x < 2 * kTiles) {
+        const FwdJob J = (int)blockIdx.x < kTiles ? A.fwd[0] : A.fwd[1];
+        const Td3Noise tn = A.tn;
+        fwd_body<CIN, 0, false, false, false, true>(J, smem, nullptr, (int)blockIdx.x % kTiles, 0, &tn);
+        return;
+    }
+    const int e = (int)blockIdx.x - 2 * kTiles;
+    const int set = e / (KT * NQ);
+    const EJob E = set == 0 ? A.e[0] : set == 1 ? A.e[1] : set == 2 ? A.e[2] : A.e[3];
+    e_body(E, e % (KT * NQ), smem);
+}
+struct Td3GradArgs { GradArgs g[2]; TwinHead h[2]; };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_grad_td3(Td3GradArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int kPer = GR_NW + GR_NG + GR_NR;
+    // (two calls, not one call on a selected record: selecting between two argument blocks of this size would spill the scalar file)
+    if ((int)blockIdx.x < kPer) grad_body<CIN, 1, false, false, true>(A.g[0], smem, (int)blockIdx.x, &A.h[0]);
+    else grad_body<CIN, 1, false, false, true>(A.g[1], smem, (int)blockIdx.x - kPer, &A.h[1]);
+}
+
 constexpr int FWD_LDS = FwdShape<false>::LDS, QG_LDS = FWD_LDS > QG16_LDS ? FWD_LDS : QG16_LDS;
 constexpr int MID_LDS = FWD_LDS > E_LDS ? FWD_LDS : E_LDS;
 static_assert(QG_LDS <= 160 * 1024, "one workgroup's LDS");
@@ -1678,6 +1839,15 @@ static int set_lds_attrs_tiled()
     if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_t), QG_LDS, "attr k_fwd_t")) return rc;
     if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid_t), MID_LDS, "attr k_mid_t")) return rc;
     if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_t), GR_LDS, "attr k_grad_t")) return rc;
+    return SHEMS_OK;
+}
+
+static int set_lds_attrs_td3()
+{
+    static std::atomic<uint64_t> m_fwd{0}, m_mid{0}, m_grad{0};
+    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_td3), FWD_LDS, "attr k_fwd_td3")) return rc;
+    if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid_td3), MID_LDS, "attr k_mid_td3")) return rc;
+    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_td3), GR_LDS, "attr k_grad_td3")) return rc;
     return SHEMS_OK;
 }
 
@@ -2026,6 +2196,109 @@ int shems_ddpg_critic_update(const shems_ddpg *d, const shems_replay *ring, int6
     if (int rc = check_adam(bp1, bp2, "shems_ddpg_critic_update")) return rc;
     const AdamScalars sc{eta, bp1, bp2, 1.0, nullptr};
     return critic_side(d, ring, ring_len, seed, tick, 0, 0, 1, 0, &sc, stream, true);
+}
+
+int shems_td3_workspace_floats(int64_t *out)
+{
+    if (!out) return set_error(SHEMS_ERR_ARG, "shems_td3_workspace_floats: NULL");
+    *out = W2_FLOATS;
+    return SHEMS_OK;
+}
+
+/* One TD3 update: see shems_hip.h.  Three launches with both critics in each (k_fwd_td3, k_mid_td3, k_grad_td3); a policy step adds
+ * replay()'s own K4 + K5 through the updated critic 1. */
+int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
+                     double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy, void *stream)
+{
+    const char *fn = "shems_td3_update";
+    if (!t) return set_error(SHEMS_ERR_ARG, "%s: NULL", fn);
+    const shems_ddpg *d = &t->d;
+    if (int rc = check_adam(bp1_crit, bp2_crit, fn)) return rc;
+    if (int rc = check_adam(bp1_act, bp2_act, fn)) return rc;
+    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
+        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    if (update_policy != 0 && update_policy != 1) return set_error(SHEMS_ERR_ARG, "%s: update_policy must be 0 or 1 (got %d)", fn, update_policy);
+    if (!(t->sigma_trg >= 0.0f) || !(t->clip_trg >= 0.0f) || t->sigma_trg > 3.0e38f || t->clip_trg > 3.0e38f)
+        return set_error(SHEMS_ERR_ARG, "%s: sigma_trg and clip_trg must be finite and >= 0", fn);
+    if (!t->critic2 || !t->critic2_t || !t->m_critic2 || !t->v_critic2 || !t->grad_critic2 || !t->ws2 || !t->losses2)
+        return set_error(SHEMS_ERR_ARG, "%s: shems_td3 has a NULL critic-2 buffer", fn);
+    for (const float *p : {(const float *)t->critic2, (const float *)t->critic2_t, (const float *)t->ws2})
+        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: critic-2 parameter blocks and ws2 must be 16-byte aligned", fn);
+    for (const float *p : {(const float *)t->m_critic2, (const float *)t->v_critic2, (const float *)t->grad_critic2, (const float *)t->losses2})
+        if (((uintptr_t)p & 3) != 0) return set_error(SHEMS_ERR_ARG, "%s: critic-2 buffers must be float aligned", fn);
+    if (d->critic && d->critic_t && d->m_critic && d->v_critic && d->grad_critic) {
+        const float *one[5] = {d->critic, d->critic_t, d->m_critic, d->v_critic, d->grad_critic};
+        const float *two[5] = {t->critic2, t->critic2_t, t->m_critic2, t->v_critic2, t->grad_critic2};
+        for (int i = 0; i < 5; ++i)
+            for (int j = 0; j < 5; ++j) {
+                if (two[i] < one[j] + SHEMS_CRITIC_PARAMS && one[j] < two[i] + SHEMS_CRITIC_PARAMS)
+                    return set_error(SHEMS_ERR_ARG, "%s: a critic-2 buffer overlaps one of critic 1's", fn);
+                if (i < j && two[i] < two[j] + SHEMS_CRITIC_PARAMS && two[j] < two[i] + SHEMS_CRITIC_PARAMS)
+                    return set_error(SHEMS_ERR_ARG, "%s: two critic-2 buffers overlap", fn);
+            }
+        if (d->ws && t->ws2 < d->ws + WS_FLOATS && d->ws < t->ws2 + W2_FLOATS) return set_error(SHEMS_ERR_ARG, "%s: ws2 overlaps ws", fn);
+        if (d->losses && t->losses2 < d->losses + 2 && d->losses < t->losses2 + 1) return set_error(SHEMS_ERR_ARG, "%s: losses2 overlaps losses", fn);
+    }
+    if (int rc = check_ddpg(d, fn)) return rc;                 // NULLs, batch, alignment; a learner on the tiled layout: SHEMS_ERR_STATE
+    if (int rc = set_lds_attrs_td3()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = d->ws, *ws2 = t->ws2;
+    const XSrc none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const XSrc x_sa{ws + WS_XT, ws + WS_AT, nullptr, nullptr, nullptr};
+    float *SC = slot(ws, SLOT_CRITIC), *SA = slot(ws, SLOT_ACTOR), *S2 = ws2 + W2_SLOT;
+    float *PT1 = slot(ws, SLOT_CRITIC_T) + SL_P3, *PT2 = ws2 + W2_PT, *PAT = slot(ws, SLOT_ACTOR_T) + SL_P3;
+    const unsigned tiles = NT * (BP / 32);
+    // T1
+    Td3FwdArgs f;
+    std::memset(&f, 0, sizeof f);
+    f.job[0] = FwdJob{nullptr, d->actor_t, SIN, 2, 0, none, nullptr, PAT, nullptr, nullptr};
+    f.job[1] = FwdJob{nullptr, d->critic, CIN, 1, 1, none, SC + SL_H2, SC + SL_P3, nullptr, nullptr};
+    f.job[2] = FwdJob{nullptr, t->critic2, CIN, 1, 1, none, S2 + SL_H2, S2 + SL_P3, nullptr, nullptr};
+    f.job[3] = FwdJob{nullptr, d->actor, SIN, 2, 2, none, SA + SL_H2, SA + SL_P3, nullptr, nullptr};
+    f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, 0, 0};
+    f.c2 = t->critic2; f.c2t = t->critic2_t; f.ws2 = ws2;
+    hipLaunchKernelGGL(k_fwd_td3, dim3((update_policy ? 4 : 3) * (tiles + 6)), dim3(256), FWD_LDS, st, f);
+    // T2
+    Td3MidArgs m;
+    std::memset(&m, 0, sizeof m);
+    const XSrc x_s2a{ws + WS_X2T, nullptr, PAT, d->actor_t + off_b3(SIN, 2), ws2 + W2_AT};
+    XSrc x_s2b = x_s2a;
+    x_s2b.publish = nullptr;
+    m.fwd[0] = FwdJob{w1t_of(ws, SLOT_CRITIC_T), d->critic_t, CIN, 1, 0, x_s2a, nullptr, PT1, nullptr, nullptr};
+    m.fwd[1] = FwdJob{ws2 + W2_W1T, t->critic2_t, CIN, 1, 0, x_s2b, nullptr, PT2, nullptr, nullptr};
+    m.e[0] = EJob{d->critic, CIN, 1, 0, SC + SL_H2, SC + SL_EP};
+    m.e[1] = EJob{t->critic2, CIN, 1, 0, S2 + SL_H2, S2 + SL_EP};
+    m.e[2] = EJob{d->actor, SIN, 2, 0, SA + SL_H2, SA + SL_EP};
+    m.e[3] = EJob{d->actor, SIN, 2, 1, SA + SL_H2, ws + WS_EA1};
+    m.tn = Td3Noise{seed, tick, t->sigma_trg, t->clip_trg};
+    hipLaunchKernelGGL(k_mid_td3, dim3(2 * tiles + (update_policy ? 4 : 2) * KT * NQ), dim3(256), MID_LDS, st, m);
+    // T3: off a policy step the critics' targets stay (tau = 0: 1 t + 0 p)
+    const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr};
+    shems_ddpg d2 = *d;
+    d2.critic = t->critic2; d2.critic_t = t->critic2_t; d2.m_critic = t->m_critic2; d2.v_critic = t->v_critic2;
+    d2.grad_critic = t->grad_critic2; d2.losses = t->losses2;
+    Td3GradArgs g;
+    std::memset(&g, 0, sizeof g);
+    for (int i = 0; i < 2; ++i) {
+        const shems_ddpg *di = i == 0 ? d : &d2;
+        float *Si = i == 0 ? SC : S2;
+        GradArgs &G = g.g[i];
+        G.w1t = i == 0 ? w1t_of(ws, SLOT_CRITIC) : ws2 + W2_W1T + 12 * 256;
+        G.P = di->critic; G.in = CIN; G.out = 1; G.x = x_sa; G.H2 = Si + SL_H2; G.w3f = i == 0 ? ws + WS_FW3C : ws2 + W2_FW3C;
+        G.grad = di->grad_critic; G.E0 = Si + SL_EP; G.E1 = nullptr; G.head = 1; G.fuse = 1; G.dd = *di; G.gstride = 0;
+        G.c = adam_ctx(di, true, sc);
+        if (!update_policy) G.c.tau = 0.0f;
+        g.h[i] = i == 0 ? TwinHead{PT1, PT2, SC + SL_P3, ws + WS_FB3 + 1, ws2 + W2_FB3 + 1, ws + WS_FB3 + 0, ws + WS_Y, ws + WS_Q, ws + WS_D3C,
+                                   ws2 + W2_QT1, ws2 + W2_QT2}
+                        : TwinHead{PT1, PT2, S2 + SL_P3, ws + WS_FB3 + 1, ws2 + W2_FB3 + 1, ws2 + W2_FB3 + 0, ws2 + W2_Y, ws2 + W2_Q, ws2 + W2_D3C,
+                                   nullptr, nullptr};
+    }
+    hipLaunchKernelGGL(k_grad_td3, dim3(2 * (GR_NW + GR_NG + GR_NR)), dim3(256), GR_LDS, st, g);
+    if (int rc = hip_ok(hipGetLastError(), "td3 critic-side launches")) return rc;
+    if (!update_policy) return SHEMS_OK;
+    // the actor through the updated critic 1, ADAM, the actor's soft update: replay()'s K4 + K5 as they are (DDPG.jl:137-140)
+    const AdamScalars sa{eta_act, bp1_act, bp2_act, 1.0, nullptr};
+    return actor_side(d, 1, 0, &sa, stream);
 }
 
 int shems_ddpg_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int64_t ring_len, uint64_t seed,

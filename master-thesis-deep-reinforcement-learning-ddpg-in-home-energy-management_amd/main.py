@@ -20,6 +20,8 @@ Differences that follow from the platform, all explicit:
   * snapshots are BSON files under the reference's names, laid out as BSON.jl lowers a Chain (bson_chain.py; parity unpinned:
     the reference ships no real .bson to compare with);
   * SHEMS_NUM_ENVS (default 1 = the reference's protocol) trains that many households at once;
+  * SHEMS_ALGO=td3[:d[:sigma_trg[:clip_trg]]] trains a td3.TD3Agent (twin critics, target smoothing, the actor every d-th update;
+    defaults 2, 0.2, 0.5) and appends _td3-d<d>-s<sigma>-c<clip> to <case>; unset or `ddpg`: today's bytes and file names;
   * SHEMS_FORESIGHT=1 adds, after the tracking block, the perfect-foresight pass over the tracked data set (foresight.py):
     out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight"; with it,
     SHEMS_FORESIGHT_HORIZON (hours of forecast: one integer or a comma list) and SHEMS_FORESIGHT_CONTROL (hours between plans,
@@ -99,6 +101,7 @@ class RunConfig:
     BATCH_SIZE: int = 120
     MEM_SIZE: int = 24000
     noise_type: str = "gn"
+    algo_suffix: str = ""                        # SHEMS_ALGO=td3...: "_td3-d<d>-s<sigma>-c<clip>" (td3.case_suffix); DDPG: nothing
 
     @property
     def charger_id(self):
@@ -118,6 +121,10 @@ class RunConfig:
 
     @property
     def case(self):
+        return self._case_ddpg + self.algo_suffix
+
+    @property
+    def _case_ddpg(self):
         if self.track < 0:                               # INPUT:143-144
             return f"{self.Charger_ID}_rule_based_{julia_float(self.track, f32=False) if self.track != int(self.track) else int(self.track)}"
         f = julia_float
@@ -192,6 +199,14 @@ def config_from_env(environ=os.environ):
         if v is not None:
             setattr(cfg, name, cast(v))
     return cfg
+
+
+def algo_from_env(environ=os.environ):
+    """SHEMS_ALGO = ddpg (or unset) -> ("ddpg", None): today's bytes and file names.  td3[:d[:sigma_trg[:clip_trg]]] -> ("td3",
+    dict(policy_delay, sigma_trg, clip_trg)) (defaults 2, the input's noise_trg = 0.2, 0.5): a td3.TD3Agent is trained and the `case`
+    string gains _td3-d<d>-s<sigma>-c<clip>.  Any other value or a malformed field is refused by name."""
+    from .td3 import parse_algo
+    return parse_algo(environ.get("SHEMS_ALGO"))
 
 
 def foresight_horizons(environ=os.environ):
@@ -344,6 +359,13 @@ def main(environ=os.environ, cwd=".", log=print):
 
     cfg = config_from_env(environ)
     _check_supported(cfg)
+    algo, td3_hp = algo_from_env(environ)
+    if algo == "td3":
+        from . import td3 as T
+        if cfg.L1 > 250 or cfg.L2 > 500 or cfg.BATCH_SIZE > 128 or cfg.noise_type == "pn":
+            raise ValueError(f"SHEMS_ALGO=td3: the twin-critic update holds networks up to (250, 500), batches up to 128 and no parameter "
+                             f"noise, not ({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE} with noise_type = {cfg.noise_type!r}")
+        cfg.algo_suffix = T.case_suffix(**td3_hp)
     horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
     forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
     regret = foresight_regret(environ)
@@ -380,8 +402,12 @@ def main(environ=os.environ, cwd=".", log=print):
     env_track = mk(1, EP_LENGTH[cfg.season, cfg.run], tabs[cfg.run])
 
     D.GAMMA, D.TAU = cfg.gamma, cfg.tau
-    agent = D.Agent(seed=cfg.rng_run, sigma=cfg.noise_act if cfg.noise_type == "gn" else cfg.sigma, noise_type=cfg.noise_type, theta=cfg.theta,
-                    hidden=(cfg.L1, cfg.L2))
+    if algo == "td3":
+        agent = T.TD3Agent(seed=cfg.rng_run, sigma=cfg.noise_act if cfg.noise_type == "gn" else cfg.sigma, noise_type=cfg.noise_type,
+                           theta=cfg.theta, hidden=(cfg.L1, cfg.L2), **td3_hp)
+    else:
+        agent = D.Agent(seed=cfg.rng_run, sigma=cfg.noise_act if cfg.noise_type == "gn" else cfg.sigma, noise_type=cfg.noise_type,
+                        theta=cfg.theta, hidden=(cfg.L1, cfg.L2))
     agent.gamma, agent.tau, agent.batch = float(np.float32(cfg.gamma)), float(np.float32(cfg.tau)), cfg.BATCH_SIZE
     agent.eta_act, agent.eta_crit = float(np.float32(cfg.eta_act)), float(np.float32(cfg.eta_crit))
     ring = D.ReplayRing(cfg.MEM_SIZE)
