@@ -652,6 +652,37 @@ int shems_ddpg_group_clone_update_tp(const shems_ddpg *d0, const shems_replay *r
 int shems_ddpg_group_critic_update_tp(const shems_ddpg *d0, const shems_replay *ring0, int64_t ring_stride_bytes, const shems_group *g,
                                       const shems_group_w2t *t, const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed,
                                       uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream);
+/* TD3 for every learner of a group, throughput form: shems_td3_update's definition (steps 1-5 above it) per learner l,
+ * with two group conventions: learner l's minibatch is the first batch_l draws of the Philox key seed + l at `tick` (what
+ * shems_ddpg_group_update_tp samples), and its target noise is the block (m, 0, tick, 0x5452474E) of the SAME key seed + l.  sigma_trg,
+ * clip_trg (t0's) and update_policy are the group's; the beta powers advance in lockstep (the critics' on every update, the actor's
+ * on policy steps: host state).  Both critics take an ADAM step on every update; update_policy = 1 adds the actor's step through the
+ * UPDATED critic 1 and the three soft updates; update_policy = 0 touches nothing of the actor and both critic targets keep their bytes
+ * (the critic launches run with tau = 0: 1 t + 0 p).
+ *   t0     learner 0's shems_td3; every block of learner l, critic 2's and ws2 included, lies at + l * g->stride_bytes.  ws2:
+ *          shems_td3_group_workspace_floats() floats per learner (it mirrors the throughput carve of ws where critic 2's launches
+ *          read it); after an update ws2 + SHEMS_TD3_GROUP_WS2_PUB holds a~' [2][128], y [128], q'_1 [128], q'_2 [128] (columns >=
+ *          batch_l are padding).
+ *   w, w2t_critic2   NULL, NULL: Flux order.  Else the tiled layout: w as for shems_ddpg_group_update_tp and a third region of
+ *          SHEMS_W2T_FLOATS per learner with W2 | m | v | target of critic 2 (shems_group_w2_to_tiled / _to_flux convert it when given
+ *          a shems_ddpg whose critic fields name critic 2's blocks and a shems_group_w2t whose critic names this region).
+ *   d_hp, d_hp_hold  per-learner records as for shems_ddpg_group_update_tp; d_hp_hold holds the same records with tau = 0 and is what
+ *          the critic launches read when update_policy = 0 (required then; the host builds it, shems_group_hparams_check is not asked).
+ *   flags  SHEMS_TP_STORE_GRAD also leaves grad_critic2.
+ * Seven launches, ten on a policy step (csrc/shems_gupd.hip): the sampler, P1 of shems_ddpg_group_update_tp (without the actor(s) job
+ * off a policy step), both target critics on the smoothed action beside critic 2's forward pass, one D1 launch with the twin head per
+ * critic, the unchanged W2-gradient / ADAM launch per critic; then P5-P7 of shems_ddpg_group_update_tp.  With sigma_trg = 0 and critic 2
+ * a copy of critic 1, update_policy = 1 leaves shems_ddpg_group_update_tp's bits.
+ * SHEMS_ERR_ARG, nothing launched: whatever shems_ddpg_group_update_tp refuses; a NULL, misaligned or critic-1-overlapping critic-2
+ * block; w2t_critic2 without w or w without w2t_critic2; d_hp_hold missing when d_hp is given and update_policy = 0; sigma_trg or
+ * clip_trg negative or not finite; update_policy outside {0, 1}.  SHEMS_ERR_STATE: a learner between shems_ddpg_tiled_enter and
+ * shems_ddpg_tiled_leave. */
+#define SHEMS_TD3_GROUP_WS2_PUB 31112
+int shems_td3_group_workspace_floats(int64_t *out);
+int shems_td3_group_update_tp(const shems_td3 *t0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *w,
+                              float *w2t_critic2, const shems_group_hparams *d_hp, const shems_group_hparams *d_hp_hold, int64_t ring_len,
+                              uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act,
+                              double bp1_act, double bp2_act, int update_policy, int32_t flags, void *stream);
 /* shems_wide_group_update in the same way (input.jl:64, 140; DDPG.jl:121-145). */
 int shems_wide_group_update_x(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
                               const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, int32_t max_batch,

@@ -33,6 +33,9 @@
 // (shems_ddpg_group_clone_update_tp: a sampler with a ring stride of its own, P1 with the actor(s) job alone, P6 with the cloning head
 // chosen at compile time, P7) and the grouped CRITIC-ONLY update (shems_ddpg_group_critic_update_tp: that sampler, P1 without the
 // actor(s) job, P2, P3, P4 -- the bits of the critic half of the sequence above).
+// TD3 for groups (shems_td3_group_update_tp) is a second critic walked by the same kernels: a sampler of its own
+// (k_tp_prep_td3), P1, a forward launch whose target jobs smooth the action (k_tp_fwd_smooth), P3 with the twin head and P4 once per
+// critic (k_tp_d1_twin, k_tp_gw2), and on a policy step P5-P7 -- seven launches, ten on a policy step (the block in front of k_tp_prep_td3).
 // Summation orders differ from the latency form (64-wide n-tiles, chunked contractions): per learner the results agree with it to
 // fp32 accumulation accuracy, not bit for bit -- the parity test holds every gradient block of every learner to the float64
 // evaluation with the same bound as the latency form (tests/test_group_gpu.py).
@@ -46,6 +49,7 @@
 #include "philox.h"
 #include "shems_adam.h"
 #include "shems_internal.h"
+#include "shems_td3_core.h"
 
 namespace shems {
 namespace tp {
@@ -338,8 +342,13 @@ template <bool QG, int NTL_> struct FwdShape {
     static constexpr int LDS = (W1K * W1C + NW * 4 + 2 * 32 * S) * 4;
 };
 
-template <bool QG, int NTL_, bool TL, bool HP>
-__device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp)
+// SMOOTH (TD3 for groups, k_tp_fwd_smooth): a job with ap3 takes the SMOOTHED target action a~' = clamp(tanh(..) + eps, -1, 1) into its
+// action rows -- the same loads and the same summation of the actor-target partials, then learner `by`'s draw of the target-noise stream
+// (key seed + by), the clip and the clamp of shems_td3_core.h.  sigma_trg = 0 leaves the bits of the plain path.
+struct TpNoise { uint64_t seed; uint32_t tick; float sigma, clip; };
+template <bool QG, int NTL_, bool TL, bool HP, bool SMOOTH = false>
+__device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp,
+                                         const TpNoise *tn = nullptr)
 {
     typedef FwdShape<QG, NTL_> SH;
     constexpr int S = SH::S, NTL = SH::NTL, NW = SH::NW;
@@ -399,6 +408,14 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bx, const i
 #pragma unroll
         for (int t = 0; t < NT; ++t) { a0 += pa3[2 * t]; a1 += pa3[2 * t + 1]; }
         a0 = tanhf(a0); a1 = tanhf(a1);          // Dense(500, 2, tanh)
+        if constexpr (SMOOTH) {                  // column m's block of the learner's own stream; Box-Muller as gauss_pair (shems_policy.hip)
+            const u32x4 x = td3_block(tn->seed + (uint64_t)by, tn->tick, (uint32_t)m);
+            const float rr = sqrtf(-2.0f * logf(td3_u1(x)));
+            float sn, cs;
+            sincosf(6.28318530717958647692f * td3_u2(x), &sn, &cs);
+            a0 = td3_smooth(a0, td3_eps(tn->sigma, tn->clip, rr * cs));
+            a1 = td3_smooth(a1, td3_eps(tn->sigma, tn->clip, rr * sn));
+        }
         if (lh == 1) xreg[4] = a0; else xreg[5] = a1;          // row 9 = (s 4, lh 1), row 10 = (s 5, lh 0)
         if (J.api && nt == 0) J.api[lh * BP + m] = lh ? a1 : a0;
     }
@@ -641,6 +658,53 @@ __device__ __forceinline__ void head_clone(const NetArgs &A, const shems_ddpg &d
     }
 }
 
+// The twin head (shems_td3_group_update_tp, k_tp_d1_twin): head_critic with TD3's target.  Both target critics' layer-3 partials and
+// frozen b3 give q'1 (critic 1's workspace) and q'2 (critic 2's), td3_min and td3_y give the one y of both critics; the differentiated
+// critic's own q, dq, loss and b3 gradient are head_critic's, in head_critic's summation orders (equal target critics leave its bits).
+// The publishing workgroup also stores y, q'1, q'2 [3][BP] at `pub`.  d.ws is the DIFFERENTIATED critic's workspace (critic 2: ws2, which
+// mirrors the carve where NetOf<CIN> points); r and done are read from critic 1's.
+struct TwinX { const float *ws1, *ws2; float *pub; };
+// td3_y's expression (shems_td3_core.h) with head_critic's rounding.  In every instantiation of d1_body the compiler forms head_critic's
+// y = r + gamma (1 - done) q' as a rounded product and an add (it pairs that add with the last add of q into one packed add, so no fused
+// multiply-add appears; read in the ISA of all sixteen k_tp_d1 / k_tp_d1_hp kernels), while td3_y inlined beside the twin minimum is
+// contracted into one.  The degenerate case (sigma_trg = 0, equal critics) must leave head_critic's bits, so the contraction is pinned
+// off here: this is also the arithmetic of the host check of shems_td3_core.h (-ffp-contract=off) and of tests/td3_ref.py.
+__device__ __forceinline__ float td3_y_rounded(float r, float gamma, float done, float qmin)
+{
+#pragma clang fp contract(off)
+    return r + gamma * (1.0f - done) * qmin;
+}
+__device__ __forceinline__ void head_twin(const NetArgs &A, const shems_ddpg &d, const AdamCtx &c, float *d3s, float *red, bool publisher,
+                                          const TwinX &X, const int64_t off)
+{
+    const float *ws = d.ws, *w1 = gsh(X.ws1, off), *w2 = gsh(X.ws2, off);
+    float *pub = gsh(X.pub, off);
+    const int t = threadIdx.x, m = t & 127;
+    float dq = 0.0f, diff = 0.0f;
+    if (t < BP) {
+        const float *Pt1 = w1 + TP_P3 + (int64_t)NET_CRITIC_T * NT * 2 * BP, *Pt2 = w2 + TP_P3 + (int64_t)NET_CRITIC_T * NT * 2 * BP;
+        const float *Pc = ws + TP_P3 + (int64_t)NET_CRITIC * NT * 2 * BP;
+        float q1 = w1[TP_FB3 + 1], q2 = w2[TP_FB3 + 1], q = ws[TP_FB3 + 0];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) { q1 += Pt1[(i * 2) * BP + m]; q2 += Pt2[(i * 2) * BP + m]; q += Pc[(i * 2) * BP + m]; }
+        const float y = td3_y_rounded(w1[TP_R + m], d.gamma, w1[TP_DONE + m], td3_min(q1, q2));
+        diff = m < d.batch ? q - y : 0.0f;
+        dq = 2.0f * diff / (float)d.batch;                                                  // d mse / d q
+        if (publisher) { pub[m] = y; pub[BP + m] = q1; pub[2 * BP + m] = q2; }
+    }
+    d3s[t] = t < BP ? dq : 0.0f;
+    if (publisher) {
+        d.ws[TP_D3C + t] = t < BP ? dq : 0.0f;
+        const float s1 = wave_sum64(diff * diff), s2 = wave_sum64(dq);
+        if ((t & 63) == 0) { red[t >> 6] = s1; red[4 + (t >> 6)] = s2; }
+        __syncthreads();
+        if (t == 0) {
+            d.losses[0] = (red[0] + red[1]) / (float)d.batch;                               // Flux.mse
+            adam_at(c, off_b3(CIN, 1), red[4] + red[5], A.store_grad != 0);
+        }
+    }
+}
+
 // ================================================================================================================================
 // P3 / P6: D1' [m][k] = mask1 .* sum_n D2[n][m] W2[k][n] for one 64-wide k-tile and the whole batch, D2[n][m] = (sum_o W3[n][o]
 // d3[o][m]) (h2[n][m] > 0) generated from relu(layer 2) as it is loaded -- straight into MFMA operand layout, no LDS; the weights
@@ -658,9 +722,11 @@ constexpr unsigned kNarrowBelow = 48;
 constexpr int d1_ring(int KT) { return 2 * 32 * KT * D1_S > 4 * KT * 8 * 64 ? 2 * 32 * KT * D1_S : 4 * KT * 8 * 64; }      // floats: the ring, later the four waves' gW1 partials
 constexpr int d1_lds(int KT) { return (d1_ring(KT) + 1024 + 2 * BP + 8 + W1K * BP + W1K * 32 * KT) * 4; }
 
-// CLONE: the supervised update's instantiation (k_tp_d1_clone) takes the cloning head at compile time; otherwise NetArgs.head decides.
-template <int IN, int KT, bool TL, bool HP, bool CLONE = false>
-__device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp)
+// CLONE: the supervised update's instantiation (k_tp_d1_clone) takes the cloning head at compile time; TWIN: TD3's (k_tp_d1_twin) the twin
+// head; otherwise NetArgs.head decides.
+template <int IN, int KT, bool TL, bool HP, bool CLONE = false, bool TWIN = false>
+__device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp,
+                                        const TwinX *tx = nullptr)
 {
     typedef NetOf<IN> N;
     constexpr int OUT = N::OUT;
@@ -683,7 +749,7 @@ __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const in
         hp_adam(c, h, N::critic);
         // (the quotient is formed on the vector ALU and lives to the kernel's end: left in vector registers it is the one value the narrow
         // Flux-order form spills, 12 bytes of scratch in k_tp_d1_hp<SIN, 1, false>; the new instantiations keep it in scalar registers)
-        if constexpr (CLONE) c.k1 = uniform_f64(c.k1);
+        if constexpr (CLONE || TWIN) c.k1 = uniform_f64(c.k1);
     }
     float *ws = d.ws;
     const float *__restrict__ P = c.p;
@@ -733,6 +799,7 @@ __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const in
 #pragma unroll
     for (int s = 0; s < WLN; ++s) { const int e = min(s * 256 + tid, W1K * KW - 1); wlv[s] = w1i[(e / KW) * W1C + k0 + e % KW]; }
     if constexpr (CLONE) head_clone(A, d, c, d3s, red, kt == 0);
+    else if constexpr (TWIN) head_twin(A, d, c, d3s, red, kt == 0, *tx, off);
     else if (A.head == 1) head_critic(A, d, c, d3s, red, kt == 0); else head_actor(A, d, c, d3s, red, kt == 0);
     reinterpret_cast<f32x4 *>(w3s)[tid] = w3v;
 #pragma unroll
@@ -1054,14 +1121,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTL == 4 ? 
 // profiles/r06_fwd_persistent_ab.txt.)
 // A learner's k-tile workgroups (T = 8 / KT of them) read the same 256 KB of relu(layer 2): they are placed on ONE XCD (workgroup id
 // mod 8 picks the XCD and its L2), consecutive in its dispatch order -- learner = 8 (q / T) + xcd, k-tile = q mod T with q = id / 8.
-template <int IN, int KT, bool TL, bool HP, bool CLONE = false>
-__device__ __forceinline__ void d1_entry(const NetArgs &A, float *smem, const shems_group_hparams *hp)
+template <int IN, int KT, bool TL, bool HP, bool CLONE = false, bool TWIN = false>
+__device__ __forceinline__ void d1_entry(const NetArgs &A, float *smem, const shems_group_hparams *hp, const TwinX *tx = nullptr)
 {
     constexpr unsigned T = 8 / KT;
     const unsigned id = blockIdx.x, xcd = id & 7u, q = id >> 3;
     const unsigned learner = 8u * (q / T) + xcd;
     if (learner >= (unsigned)A.learners) return;
-    d1_body<IN, KT, TL, HP, CLONE>(A, (int)(q % T), (int)learner, smem, hp);
+    d1_body<IN, KT, TL, HP, CLONE, TWIN>(A, (int)(q % T), (int)learner, smem, hp, tx);
 }
 template <int IN, int KT, bool TL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1(NetArgs A)
@@ -1192,6 +1259,94 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     d1_entry<SIN, KT, TL, true, true>(A, smem, hp);
+}
+
+// ================================================================================================================================
+// TD3 for groups (shems_td3_group_update_tp; include/shems_hip.h): a second critic beside every learner's first.
+// Critic 2 has a workspace of its own, ws2, which MIRRORS the carve above wherever NetOf<CIN> and the forward jobs point: the unchanged
+// k_tp_gw2<CIN> and d1_body walk critic 2 through a NetArgs whose shems_ddpg names critic 2's blocks and ws2.
+//   ws2 + TP_X      [12][BP] the input block [s; a; 1] again (the sampler writes both)
+//   ws2 + TP_W1I    slot NET_CRITIC_T: critic2_t's layer-1 image, slot NET_CRITIC: critic2's, slot IMG_CRITIC_NEW: critic2's after its update (unread)
+//   ws2 + TP_FW3C   frozen W3 of critic2;  ws2 + TP_FB3: [0] b3 of critic2, [1] b3 of critic2_t
+//   ws2 + TP_P3     pass NET_CRITIC_T: critic2_t(s', a~') partials, pass NET_CRITIC: critic2(s, a) partials
+//   ws2 + TP_D3C    dq of critic 2's loss;  ws2 + TP_H2C: relu(layer 2) of critic2(s, a)
+//   ws2 + T2_AT     [2][BP] a~' (n-tile 0 of critic_t's pass);  T2_PUB: y, q'1, q'2 [3][BP] from critic 1's head, T2_PUB2: from critic 2's
+// (T2_* take the rows the actor's input gradient has in ws; TP_X2, TP_R, TP_DONE, TP_IDX and the actor slots of ws2 are not used.)
+// ================================================================================================================================
+constexpr int64_t T2_AT = TP_DAP;
+constexpr int64_t T2_PUB = T2_AT + 2 * BP;
+constexpr int64_t T2_PUB2 = T2_PUB + 3 * BP;
+constexpr int64_t T2_FLOATS = TP_H2A;              // (no second relu(layer 2) block: ws2 ends where the actor's begins in ws)
+static_assert(T2_PUB2 + 3 * BP <= TP_D3C, "the published rows fit the input gradient's block");
+static_assert(T2_AT == SHEMS_TD3_GROUP_WS2_PUB && T2_AT % 4 == 0, "shems_hip.h names where the published rows begin");
+
+// The sampler: roles 0..4 are prep_body's on the learner's own record; role 0 then repeats its input block in ws2; roles 5, 6 are
+// prep_body's image roles on a record whose critic blocks and workspace are critic 2's (critic2_t, critic2); role 5 also freezes critic
+// 2's output layers (prep_body's expressions for critic 1's).  grid (7, learners).
+struct PrepTd3Args { PrepArgs p; float *critic2, *critic2_t, *ws2; };
+template <bool HP>
+__device__ __forceinline__ void prep_td3_body(const PrepTd3Args &T, const int role, const int l, const shems_group_hparams *hp)
+{
+    const int tid = threadIdx.x;
+    const int64_t off = (int64_t)l * T.p.gstride;
+    if (role < 5) {
+        prep_body<HP>(T.p, role, l, hp);
+        if (role == 0 && tid < BP) {             // (thread m wrote every row of column m itself)
+            const float *ws = gsh(T.p.d.ws, off);
+            float *ws2 = gsh(T.ws2, off);
+            float v[W1K];
+#pragma unroll
+            for (int k = 0; k < W1K; ++k) v[k] = ws[TP_X + k * BP + tid];
+#pragma unroll
+            for (int k = 0; k < W1K; ++k) ws2[TP_X + k * BP + tid] = v[k];
+        }
+        return;
+    }
+    PrepArgs A = T.p;
+    A.d.critic = T.critic2; A.d.critic_t = T.critic2_t; A.d.ws = T.ws2;
+    prep_body<HP>(A, 1 + (role == 5 ? NET_CRITIC_T : NET_CRITIC), l, hp);
+    if (role == 5) {
+        const float *c2 = gsh(T.critic2, off), *c2t = gsh(T.critic2_t, off);
+        float *ws2 = gsh(T.ws2, off);
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int e = it * 256 + tid, n = e >> 1, o = e & 1;
+            const float wc = c2[off_w3(CIN) + min(n, H2N - 1)];
+            ws2[TP_FW3C + e] = (n < H2N && o == 0) ? wc : 0.0f;
+        }
+        if (tid < 8) ws2[TP_FB3 + tid] = tid == 0 ? c2[off_b3(CIN, 1)] : tid == 1 ? c2t[off_b3(CIN, 1)] : 0.0f;
+    }
+}
+__global__ __launch_bounds__(256) void k_tp_prep_td3(PrepTd3Args T) { prep_td3_body<false>(T, blockIdx.x, blockIdx.y, nullptr); }
+__global__ __launch_bounds__(256) void k_tp_prep_td3_hp(PrepTd3Args T, const shems_group_hparams *hp) { prep_td3_body<true>(T, blockIdx.x, blockIdx.y, hp); }
+
+// T2: critic_t(s', a~') | critic2_t(s', a~') | critic2(s, a) on 64-wide n-tiles: fwd_body's SMOOTH instantiation, the twin of k_tp_fwd<false, 2, TL>
+struct FwdSmoothArgs { FwdArgs f; TpNoise tn; };
+template <bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_tp_fwd_smooth(FwdSmoothArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    fwd_body<false, 2, TL, false, true>(A.f, blockIdx.x, blockIdx.y, smem, nullptr, &A.tn);
+}
+template <bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_tp_fwd_smooth_hp(FwdSmoothArgs A, const shems_group_hparams *hp)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    fwd_body<false, 2, TL, true, true>(A.f, blockIdx.x, blockIdx.y, smem, hp, &A.tn);
+}
+// T3: a critic's D1 launch with the twin head, the twins of k_tp_d1<CIN, ..> / k_tp_d1_hp<CIN, ..> (one launch per critic)
+struct TwinArgs { NetArgs n; TwinX x; };
+template <int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1_twin(TwinArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<CIN, KT, TL, false, false, true>(A.n, smem, nullptr, &A.x);
+}
+template <int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1_twin_hp(TwinArgs A, const shems_group_hparams *hp)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<CIN, KT, TL, true, false, true>(A.n, smem, hp, &A.x);
 }
 
 // (Round 5 also built two ways of running the HBM-bound phases (P4, P7) under the MFMA-bound ones (P1, P2, P5) of OTHER learners: cohorts
@@ -1512,6 +1667,158 @@ extern "C" int shems_ddpg_group_critic_update_tp(const shems_ddpg *d, const shem
                                                  uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream)
 {
     return group_half_tp_pick<false>(d, ring, ring_stride_bytes, g, t, d_hp, ring_len, seed, tick, eta, bp1, bp2, flags, stream);
+}
+
+// ---- TD3 for groups: seven launches, ten on a policy step -----------------------------------------------------------------------------
+//   sampler k_tp_prep_td3 | T1 = P1 (actor(s) job on a policy step only) | T2 k_tp_fwd_smooth | T3 k_tp_d1_twin for critic 1, again for
+//   critic 2 | T4 k_tp_gw2<CIN> for critic 1, again for critic 2 | policy step: P5, P6, P7 as group_update_tp launches them.
+// Off a policy step the critic launches run with tau = 0 (1 t + 0 p: the targets keep their bytes): d->tau = 0 in their records, or
+// hp_hold (the records with tau = 0) in the place of hp.
+extern "C" int shems_td3_group_workspace_floats(int64_t *out)
+{
+    if (!out) return set_error(SHEMS_ERR_ARG, "shems_td3_group_workspace_floats: NULL");
+    *out = T2_FLOATS;
+    return SHEMS_OK;
+}
+
+template <bool TL, bool HP>
+static int td3_group_update_tp(const shems_td3 *t0, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, float *w2t_critic2,
+                               const shems_group_hparams *hp, const shems_group_hparams *hp_hold, int64_t ring_len, uint64_t seed, uint32_t tick,
+                               double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy,
+                               int32_t flags, void *stream)
+{
+    const char *fn = "shems_td3_group_update_tp";
+    const shems_ddpg *d = &t0->d;
+    if (int rc = check_group_tp(g, fn)) return rc;
+    if (!d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
+        !d->s_min || !d->s_max || !d->ws || !d->losses)
+        return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
+    if (!t0->critic2 || !t0->critic2_t || !t0->m_critic2 || !t0->v_critic2 || !t0->ws2 || !t0->losses2)
+        return set_error(SHEMS_ERR_ARG, "%s: shems_td3 has a NULL critic-2 buffer", fn);
+    if ((flags & SHEMS_TP_STORE_GRAD) && (!d->grad_actor || !d->grad_critic || !t0->grad_critic2))
+        return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
+    if (flags & ~SHEMS_TP_STORE_GRAD) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
+    if (update_policy != 0 && update_policy != 1) return set_error(SHEMS_ERR_ARG, "%s: update_policy must be 0 or 1 (got %d)", fn, update_policy);
+    if (!(t0->sigma_trg >= 0.0f) || !(t0->clip_trg >= 0.0f) || t0->sigma_trg > 3.0e38f || t0->clip_trg > 3.0e38f)
+        return set_error(SHEMS_ERR_ARG, "%s: sigma_trg and clip_trg must be finite and >= 0", fn);
+    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
+    if (HP && (((uintptr_t)hp | (uintptr_t)hp_hold) & 7) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: d_hp and d_hp_hold must be 8-byte aligned device arrays of count records", fn);
+    if (HP && !update_policy && !hp_hold)
+        return set_error(SHEMS_ERR_ARG, "%s: update_policy = 0 with d_hp needs d_hp_hold (the records with tau = 0)", fn);
+    if (HP) eta_crit = eta_act = 0.0;        // the *_hp kernels form k1 from the records
+    for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
+        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
+    for (const float *p : {(const float *)t0->critic2, (const float *)t0->critic2_t, (const float *)t0->m_critic2, (const float *)t0->v_critic2,
+                           (const float *)t0->ws2})
+        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: critic-2 blocks and ws2 must be 16-byte aligned", fn);
+    if (((uintptr_t)t0->grad_critic2 & 15) != 0 || ((uintptr_t)t0->losses2 & 3) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: grad_critic2 must be 16-byte and losses2 float aligned", fn);
+    {
+        const float *one[5] = {d->critic, d->critic_t, d->m_critic, d->v_critic, d->grad_critic};
+        const float *two[5] = {t0->critic2, t0->critic2_t, t0->m_critic2, t0->v_critic2, t0->grad_critic2};
+        for (int i = 0; i < 5; ++i)
+            for (int j = 0; j < 5; ++j) {
+                if (two[i] && one[j] && two[i] < one[j] + SHEMS_CRITIC_PARAMS && one[j] < two[i] + SHEMS_CRITIC_PARAMS)
+                    return set_error(SHEMS_ERR_ARG, "%s: a critic-2 buffer overlaps one of critic 1's", fn);
+                if (i < j && two[i] && two[j] && two[i] < two[j] + SHEMS_CRITIC_PARAMS && two[j] < two[i] + SHEMS_CRITIC_PARAMS)
+                    return set_error(SHEMS_ERR_ARG, "%s: two critic-2 buffers overlap", fn);
+            }
+        if (t0->ws2 < d->ws + TP_FLOATS && d->ws < t0->ws2 + T2_FLOATS) return set_error(SHEMS_ERR_ARG, "%s: ws2 overlaps ws", fn);
+        if (t0->losses2 < d->losses + 2 && d->losses < t0->losses2 + 1) return set_error(SHEMS_ERR_ARG, "%s: losses2 overlaps losses", fn);
+    }
+    if (int rc = w2t_flux_guard(d->actor, fn)) return rc;       // (a single learner's own tiled mode, shems_ddpg_tiled_enter: not a group's t)
+    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
+        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    for (double bp : {bp1_crit, bp2_crit, bp1_act, bp2_act})
+        if (!(bp > 0.0 && bp < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
+    if (TL) {
+        if (int rc = check_w2t(t, fn)) return rc;
+        if (((uintptr_t)w2t_critic2 & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: the tiled regions must be 16-byte aligned", fn);
+        if (w2t_critic2 < t->critic + SHEMS_W2T_FLOATS && t->critic < w2t_critic2 + SHEMS_W2T_FLOATS)
+            return set_error(SHEMS_ERR_ARG, "%s: critic 2's tiled region overlaps critic 1's", fn);
+        if (w2t_critic2 < t->actor + SHEMS_W2T_FLOATS && t->actor < w2t_critic2 + SHEMS_W2T_FLOATS)
+            return set_error(SHEMS_ERR_ARG, "%s: critic 2's tiled region overlaps the actor's", fn);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned L = (unsigned)g->count;
+    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
+    const int sg = (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0;
+    float *ws = d->ws, *ws2 = t0->ws2;
+    float *ta = TL ? t->actor : nullptr, *tc = TL ? t->critic : nullptr, *tc2 = TL ? w2t_critic2 : nullptr;
+    auto arr = [](float *region, int a) -> const float * { return region ? region + a * TL_TILE : nullptr; };
+    // the records of the critic launches: critic 2's names critic 2's blocks, ws2 and losses2; off a policy step both hold tau = 0
+    shems_ddpg d1 = *d, d2 = *d;
+    d2.critic = t0->critic2; d2.critic_t = t0->critic2_t; d2.m_critic = t0->m_critic2; d2.v_critic = t0->v_critic2;
+    d2.grad_critic = t0->grad_critic2; d2.ws = ws2; d2.losses = t0->losses2;
+    if (!update_policy) d1.tau = d2.tau = 0.0f;
+    auto critic_ctx = [&](const shems_ddpg &x) {
+        return AdamCtx{x.critic, x.grad_critic, x.m_critic, x.v_critic, x.critic_t, nullptr, SHEMS_CRITIC_PARAMS, (int)CIN,
+                       eta_crit, bp1_crit, bp2_crit, 1.0, eta_crit / (1.0 - bp1_crit), 1.0 / (1.0 - bp2_crit), x.tau};
+    };
+    struct { PrepTd3Args pa; FwdArgs f1, f5; FwdSmoothArgs f2; TwinArgs n1, n2; NetArgs na; } U;
+    std::memset(&U, 0, sizeof U);
+    U.pa = PrepTd3Args{PrepArgs{*d, *ring, ring_len, gs, seed, tick}, t0->critic2, t0->critic2_t, ws2};
+    for (FwdArgs *f : {&U.f1, &U.f2.f, &U.f5}) { f->gstride = gs; f->batch = d->batch; }
+    // T1 = P1 of group_update_tp
+    U.f1.job[0] = FwdJob{arr(ta, TL_T), d->actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
+    U.f1.job[1] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, NET_CRITIC), nullptr, nullptr, nullptr, ws + TP_H2C, p3_of(ws, NET_CRITIC), nullptr, CIN, 1};
+    U.f1.job[2] = FwdJob{arr(ta, TL_P), d->actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
+    // T2: both target critics on [s'; a~'] (the first publishes a~'), critic 2 on [s; a]
+    U.f2.f.job[0] = FwdJob{arr(tc, TL_T), d->critic_t, ws + TP_X2, w1i_of(ws, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, ws2 + T2_AT, nullptr,
+                           p3_of(ws, NET_CRITIC_T), nullptr, CIN, 1};
+    U.f2.f.job[1] = FwdJob{arr(tc2, TL_T), t0->critic2_t, ws + TP_X2, w1i_of(ws2, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, nullptr, nullptr,
+                           p3_of(ws2, NET_CRITIC_T), nullptr, CIN, 1};
+    U.f2.f.job[2] = FwdJob{arr(tc2, TL_P), t0->critic2, ws + TP_X, w1i_of(ws2, NET_CRITIC), nullptr, nullptr, nullptr, ws2 + TP_H2C, p3_of(ws2, NET_CRITIC), nullptr, CIN, 1};
+    U.f2.tn = TpNoise{seed, tick, t0->sigma_trg, t0->clip_trg};
+    // P5 of group_update_tp
+    U.f5.job[0] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, IMG_CRITIC_NEW), p3_of(ws, NET_ACTOR), ws + TP_FB3 + 2, ws + TP_API, nullptr, p3_of(ws, PASS_CRITIC2),
+                         ws + TP_DAP, CIN, 1};
+    U.n1 = TwinArgs{NetArgs{d1, tc, critic_ctx(d1), gs, 1, sg, (int)L}, TwinX{ws, ws2, ws2 + T2_PUB}};
+    U.n2 = TwinArgs{NetArgs{d2, tc2, critic_ctx(d2), gs, 1, sg, (int)L}, TwinX{ws, ws2, ws2 + T2_PUB2}};
+    U.na = NetArgs{*d, ta, AdamCtx{d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
+                                   eta_act, bp1_act, bp2_act, 1.0, eta_act / (1.0 - bp1_act), 1.0 / (1.0 - bp2_act), d->tau}, gs, 2, sg, (int)L};
+    typedef FwdShape<false, 4> SW;
+    typedef FwdShape<false, 2> SN;
+    typedef FwdShape<true, 2> SQ;
+    const bool narrow = L < kNarrowBelow;
+    const unsigned g8 = 8 * ((L + 7) / 8);
+    const unsigned JOBS = update_policy ? 3 : 2;
+    const shems_group_hparams *hpc = update_policy ? hp : hp_hold;      // the critic launches' records
+    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args, const shems_group_hparams *rec) {
+        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, rec);
+        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
+    };
+    launch(k_tp_prep_td3, k_tp_prep_td3_hp, dim3(7, L), 0, U.pa, hp);
+    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(JOBS * SN::TILES, L), SN::LDS, U.f1, hp);
+    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(JOBS * SW::TILES, L), SW::LDS, U.f1, hp);
+    launch(k_tp_fwd_smooth<TL>, k_tp_fwd_smooth_hp<TL>, dim3(3 * SN::TILES, L), SN::LDS, U.f2, hp);
+    for (const TwinArgs *n : {&U.n1, &U.n2}) {
+        if (narrow) launch(k_tp_d1_twin<1, TL>, k_tp_d1_twin_hp<1, TL>, dim3(8 * g8), d1_lds(1), *n, hpc);
+        else launch(k_tp_d1_twin<2, TL>, k_tp_d1_twin_hp<2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, *n, hpc);
+    }
+    for (const TwinArgs *n : {&U.n1, &U.n2}) launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, n->n, hpc);
+    if (update_policy) {
+        launch(k_tp_fwd<true, 2, TL>, k_tp_fwd_hp<true, 2, TL>, dim3(SQ::TILES, L), SQ::LDS, U.f5, hp);
+        if (narrow) launch(k_tp_d1<SIN, 1, TL>, k_tp_d1_hp<SIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.na, hp);
+        else launch(k_tp_d1<SIN, 2, TL>, k_tp_d1_hp<SIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.na, hp);
+        launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.na, hp);
+    }
+    return hip_ok(hipGetLastError(), "grouped TD3 update (throughput form) launches");
+}
+
+extern "C" int shems_td3_group_update_tp(const shems_td3 *t0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *w,
+                                         float *w2t_critic2, const shems_group_hparams *d_hp, const shems_group_hparams *d_hp_hold, int64_t ring_len,
+                                         uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act,
+                                         double bp1_act, double bp2_act, int update_policy, int32_t flags, void *stream)
+{
+    if (!t0) return set_error(SHEMS_ERR_ARG, "shems_td3_group_update_tp: NULL");
+    if ((w != nullptr) != (w2t_critic2 != nullptr))
+        return set_error(SHEMS_ERR_ARG, "shems_td3_group_update_tp: the tiled layout needs w AND w2t_critic2 (or neither: Flux order)");
+    auto *update = w ? (d_hp ? td3_group_update_tp<true, true> : td3_group_update_tp<true, false>)
+                     : (d_hp ? td3_group_update_tp<false, true> : td3_group_update_tp<false, false>);
+    return update(t0, ring0, g, w, w2t_critic2, d_hp, d_hp_hold, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
+                  update_policy, flags, stream);
 }
 
 static_assert(sizeof(shems_group_xparams) == 16 && offsetof(shems_group_xparams, ou_dt) == 4 && offsetof(shems_group_xparams, mem_size) == 8 &&

@@ -261,6 +261,24 @@ def _pad4(n):
     return (int(n) + 3) & ~3
 
 
+def slab_layout(n_actor, n_critic, ws_floats, capacity, tiled, extra=()):
+    """One learner's slab: ({name: (float offset, floats)}, slab_floats).  Every block starts on a 16-byte boundary (float offsets are
+    multiples of 4).  extra: further (name, floats) blocks of a subclass (LearnerGroup._extra_blocks), carved AFTER ring_done, so that
+    no offset of a DDPG group depends on them.  Host only: no device work."""
+    layout, off = {}, 0
+    for name, n in (("actor", n_actor), ("critic", n_critic), ("actor_t", n_actor), ("critic_t", n_critic),
+                    ("m_actor", n_actor), ("v_actor", n_actor), ("m_critic", n_critic), ("v_critic", n_critic),
+                    ("w2t_actor", W2T_FLOATS if tiled else 0), ("w2t_critic", W2T_FLOATS if tiled else 0),
+                    ("grad_actor", n_actor), ("grad_critic", n_critic), ("s_min", STATE), ("s_max", STATE), ("losses", 2),
+                    ("ws", ws_floats), ("ring_s", capacity * STATE), ("ring_a", capacity * ACTION),
+                    ("ring_r", capacity), ("ring_s2", capacity * STATE), ("ring_done", (capacity + 3) // 4), *extra):
+        if name in layout:
+            raise ValueError(f"slab_layout: block {name!r} twice")
+        layout[name] = (off, int(n))
+        off = _pad4(off + n)
+    return layout, off
+
+
 class LearnerGroup:
     """`count` independent learners, learner l seeded with (seed + l) for its network initialisation and (rng_seed + l)
     for its minibatch stream; exploration noise is keyed per env, so it differs between learners by construction."""
@@ -270,6 +288,7 @@ class LearnerGroup:
     # bit-identical to Agent.replay), "wide" = the layer-by-layer path of csrc/shems_wide.hip with a learner dimension (24 launches; networks
     # up to 4096 wide, batches up to 256).  Default: throughput from TP_MIN_LEARNERS learners up.
     TP_MIN_LEARNERS = 16
+    has_evaluate = True                    # evaluate() exists (imitation.warm_start_group asks before it trains anything)
 
     def __init__(self, count, envs_per_learner, seed=1231, rng_seed=None, capacity=MEM_SIZE, sigma=NOISE_SIGMA, device=None, form=None, tiled=None,
                  hparams=None, hidden=None, noise_type="gn", theta=0.15, dt=1e-2):
@@ -373,16 +392,8 @@ class LearnerGroup:
         else:
             _capi.check(self.L.shems_ddpg_workspace_floats(C.byref(nws)))
         self._act_ws = None                        # form "wide": scratch of the fused step (shems_wide_act_workspace_floats)
-        # one slab per learner; every block starts on a 16-byte boundary (float offsets are multiples of 4)
-        layout, off = {}, 0
-        for name, n in (("actor", n_actor), ("critic", n_critic), ("actor_t", n_actor), ("critic_t", n_critic),
-                        ("m_actor", n_actor), ("v_actor", n_actor), ("m_critic", n_critic), ("v_critic", n_critic),
-                        ("w2t_actor", W2T_FLOATS if self.tiled else 0), ("w2t_critic", W2T_FLOATS if self.tiled else 0),
-                        ("grad_actor", n_actor), ("grad_critic", n_critic), ("s_min", STATE), ("s_max", STATE), ("losses", 2),
-                        ("ws", nws.value), ("ring_s", self.capacity * STATE), ("ring_a", self.capacity * ACTION),
-                        ("ring_r", self.capacity), ("ring_s2", self.capacity * STATE), ("ring_done", (self.capacity + 3) // 4)):
-            layout[name] = (off, int(n))
-            off = _pad4(off + n)
+        # one slab per learner (slab_layout); a subclass appends blocks of its own behind the ring
+        layout, off = slab_layout(n_actor, n_critic, nws.value, self.capacity, self.tiled, self._extra_blocks(n_critic))
         self.layout, self.slab_floats = layout, off
         self.slab = torch.zeros((self.count, self.slab_floats), dtype=torch.float32, device=self.device)
         self.learners, self.rings = [], []
@@ -422,6 +433,11 @@ class LearnerGroup:
         self.evaluations = 0                       # grouped critic-only updates (evaluate); they advance bp_critic, not `updates`
         self._hp_variants = {}                     # record arrays of clone / evaluate with a tau of the call's: built once per (kind, tau)
         self.tick = 0
+
+    def _extra_blocks(self, n_critic):
+        """(name, floats) blocks a subclass keeps in every learner's slab, carved after ring_done (td3.TD3LearnerGroup: the second
+        critic).  Called once by __init__ after form / tiled are decided."""
+        return ()
 
     def _hp_ptr(self):
         """The entry points' d_hp: the device records, or NULL (the shared values)."""
@@ -618,13 +634,15 @@ class LearnerGroup:
         self.updates += 1
 
     # ---- grouped imitation: the supervised and the critic-only update for every learner ------------------------------------------------
-    def _hp_variant(self, tau):
+    def _hp_variant(self, tau, check=True):
         """The group's records with the call's tau in place of the learners' (clone, evaluate(tau=...)): a second device record array,
-        built and checked once per tau.  The kernels read the learner's batch and eta (and gamma) from it as from the group's own."""
+        built and checked once per tau.  The kernels read the learner's batch and eta (and gamma) from it as from the group's own.
+        check=False: the copy is not shown to shems_group_hparams_check (tau = 0, which it refuses, holds the targets of a TD3 group
+        off a policy step; every other field comes from the checked records)."""
         tau = float(np.float32(tau))
         if tau not in self._hp_variants:
             arr = (HParams * self.count)(*[HParams(r["eta_act"], r["eta_crit"], r["gamma"], tau, r["mu"], r["sigma"], r["batch"], 0) for r in self.hparams])
-            if self.L.shems_group_hparams_check(arr, self.count) != _capi.OK:
+            if check and self.L.shems_group_hparams_check(arr, self.count) != _capi.OK:
                 raise ValueError(self.L.shems_last_error().decode("utf-8", "replace"))
             self._hp_variants[tau] = self.torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
         return C.c_void_p(self._hp_variants[tau].data_ptr())

@@ -391,6 +391,9 @@ def warm_start_group(grp, env, values, demos, ring, rounds, steps_per_round, cri
     An "mc" ring (done = 1, returns as rewards) must not be the ring bootstrapped training samples: the group's own rings are refused.
     Returns dagger_group's per-round records followed by one dict {"critic_loss_first", "critic_loss_last"} ([count] arrays:
     losses[0] after the first and the last critic step) and "transitions" (the rings' shared length)."""
+    if not getattr(grp, "has_evaluate", True):                 # (before dagger_group trains anything: a group without the critic-only update)
+        raise NotImplementedError(f"warm_start_group: {type(grp).__name__} has no evaluate() -- the critic-only update of ONE critic -- so "
+                                  "its critics cannot be fitted here; nothing was trained")
     critic_steps = int(critic_steps)
     if critic_steps < 1:
         raise ValueError(f"warm_start_group: {critic_steps} critic steps; at least one")

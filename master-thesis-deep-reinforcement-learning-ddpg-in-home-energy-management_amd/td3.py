@@ -6,12 +6,15 @@ replay() (DDPG.jl:121-145): Float32 arithmetic, Flux 0.12.1 ADAM, the minibatch 
 
     TD3Agent(Agent)        the DDPG learner plus a second critic (critic2, critic2_t, m_critic2, v_critic2, grad_critic2, losses2);
                            replay() is one TD3 update: update u (0-based) is a policy step when is_policy_step(u, policy_delay)
+    TD3LearnerGroup(LearnerGroup)   `count` independent TD3 learners in the same launches (shems_td3_group_update_tp, throughput form): a second
+                           critic per learner behind the ring of every slab; replay() follows the same schedule in lockstep
     is_policy_step(u, d)   the schedule
     parse_algo(value)      SHEMS_ALGO of the entry script
 
 act, act_step, episode_, run_episodes, populate_memory, min_max_buffer and clone are the Agent's.  What TD3 does not cover is refused by
 name (NotImplementedError), never run as DDPG: networks wider than (250, 500), batches above 128, parameter noise, data-parallel
-replicas, the tiled working layout, evaluate(), learners of a learner group, the pipelined forms of replay() (exclude / publish).
+replicas, the tiled working layout, evaluate(), a TD3Agent on a group's slab (a group of TD3 learners is a TD3LearnerGroup), the pipelined forms
+of replay() (exclude / publish); for a TD3LearnerGroup see its docstring.
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ import numpy as np
 
 from . import _capi
 from . import ddpg as D
+from . import group as G
 
 SIGMA_TRG, CLIP_TRG, POLICY_DELAY = 0.2, 0.5, 2        # input.jl:231; the paper's clip and delay
 CRITIC2_SEED_OFFSET = 1000
@@ -86,6 +90,211 @@ def _declare():
     return L
 
 
+GROUP_WS2_PUB = 31112                                  # SHEMS_TD3_GROUP_WS2_PUB: a~' [2][128] | y | q'1 | q'2 inside a group learner's ws2
+CRITIC2_BLOCKS = ("critic2", "critic2_t", "m_critic2", "v_critic2", "grad_critic2")
+
+
+def group_extra_blocks(n_critic, tiled, ws2_floats):
+    """The blocks a TD3 learner group appends to every learner's slab, behind ring_done (group.slab_layout(extra=...)).  Host only."""
+    return tuple((n, int(n_critic)) for n in CRITIC2_BLOCKS) + (("w2t_critic2", G.W2T_FLOATS if tiled else 0), ("ws2", int(ws2_floats)),
+                                                                 ("losses2", 1))
+
+
+def group_refusals(form=None, noise_type="gn", hparams=None, hidden=None, sigma_trg=SIGMA_TRG, clip_trg=CLIP_TRG, policy_delay=POLICY_DELAY):
+    """What TD3LearnerGroup refuses before any device work, each by name."""
+    if form in ("latency", "wide"):
+        raise NotImplementedError(f"TD3 learner group: form={form!r} has no twin-critic update; the group runs the throughput form "
+                                  "(shems_td3_group_update_tp) whatever its count")
+    if form not in (None, "throughput"):
+        raise ValueError("form must be 'throughput'")
+    if noise_type == "ou":
+        raise NotImplementedError("TD3 learner group: Ornstein-Uhlenbeck noise runs on the *_x entry points, which have no twin-critic update")
+    if hidden is not None:
+        raise NotImplementedError("TD3 learner group: hidden= belongs to form='wide', which has no twin-critic update")
+    for l, h in enumerate(hparams or ()):
+        if hasattr(h, "keys") and "mem_size" in h:
+            raise NotImplementedError(f"TD3 learner group: hparams[{l}]: per-learner mem_size runs on the *_x entry points, which have no "
+                                      "twin-critic update")
+        if hasattr(h, "keys") and int(h.get("batch", 0)) > BP:
+            raise NotImplementedError(f"TD3 learner group: hparams[{l}]: batch {h['batch']} > {BP}: the twin-critic update holds one "
+                                      f"{BP}-column pass")
+        if hasattr(h, "keys") and "hidden" in h and D.is_wide(tuple(int(x) for x in h["hidden"])):
+            raise NotImplementedError(f"TD3 learner group: hparams[{l}]: hidden {tuple(h['hidden'])} is wider than ({D.L1}, {D.L2}): the "
+                                      "wide form has no twin-critic update")
+    if not (math.isfinite(float(sigma_trg)) and float(sigma_trg) >= 0.0 and math.isfinite(float(clip_trg)) and float(clip_trg) >= 0.0):
+        raise ValueError(f"TD3 learner group: sigma_trg = {sigma_trg}, clip_trg = {clip_trg} must be finite and >= 0")
+    is_policy_step(0, policy_delay)                          # (refuses d < 1)
+
+
+def _declare_group():
+    L = G._declare_group()
+    _declare()
+    if getattr(L, "_td3_group_declared", False):
+        return L
+    dbl, vp = C.c_double, C.c_void_p
+    L.shems_td3_group_workspace_floats.argtypes = [C.POINTER(C.c_int64)]
+    L.shems_td3_group_workspace_floats.restype = C.c_int
+    L.shems_td3_group_update_tp.argtypes = [C.POINTER(Td3Args), C.POINTER(_capi.Replay), C.POINTER(G.Group), C.POINTER(G.GroupW2T), vp, vp, vp,
+                                            C.c_int64, C.c_uint64, C.c_uint32, dbl, dbl, dbl, dbl, dbl, dbl, C.c_int, C.c_int32, vp]
+    L.shems_td3_group_update_tp.restype = C.c_int
+    L._td3_group_declared = True
+    return L
+
+
+class TD3LearnerGroup(G.LearnerGroup):
+    """`count` independent TD3 learners advanced by the same launches (shems_td3_group_update_tp): a LearnerGroup whose slabs also hold a
+    second critic per learner (critic2, critic2_t, m_critic2, v_critic2, grad_critic2, w2t_critic2 on the tiled layout, ws2, losses2 --
+    carved behind the ring, so every offset of a DDPG group is unchanged).  Learner l's critic 2 is initialised from seed + l +
+    critic2_seed_offset, as TD3Agent initialises its own.  sigma_trg, clip_trg and policy_delay are the group's; the schedule runs in
+    lockstep.  Throughput form only, whatever the count.  act_step, populate_memory, min_max_buffer, ring_window, episode_, eval_scores,
+    run_episodes, clone and imitation.dagger_group are the LearnerGroup's (they read or train the actor only).  Refused by name
+    (NotImplementedError): form 'latency' / 'wide', "ou" noise and per-learner mem_size (the *_x entry points), batch > 128, wide hidden
+    sizes, evaluate() and with it imitation.warm_start_group."""
+
+    has_evaluate = False
+
+    def __init__(self, count, envs_per_learner, sigma_trg=SIGMA_TRG, clip_trg=CLIP_TRG, policy_delay=POLICY_DELAY,
+                 critic2_seed_offset=CRITIC2_SEED_OFFSET, **kw):
+        if kw.get("hparams") is not None:
+            kw["hparams"] = list(kw["hparams"])              # (a generator is walked once, here)
+        group_refusals(kw.get("form"), kw.get("noise_type", "gn"), kw.get("hparams"), kw.get("hidden"), sigma_trg, clip_trg, policy_delay)
+        kw["form"] = "throughput"
+        self.sigma_trg, self.clip_trg, self.policy_delay = float(sigma_trg), float(clip_trg), int(policy_delay)
+        self.critic2_seed_offset = int(critic2_seed_offset)
+        super().__init__(count, envs_per_learner, **kw)
+        self.L = _declare_group()
+        t = self.torch
+        for l, ag in enumerate(self.learners):
+            c2 = D.pad_net(D.init_params(ag.seed + self.critic2_seed_offset, D.STATE + D.ACTION, 1, 1, ag.hidden), D.STATE + D.ACTION, 1, ag.hidden)
+            self.critic2_of(l).copy_(t.from_numpy(c2))
+            self.critic2_t_of(l).copy_(self.critic2_of(l))
+        self._tiled_valid = False                            # (critic 2's Flux-order blocks were just written)
+
+    def _extra_blocks(self, n_critic):
+        nws = C.c_int64(0)
+        _capi.check(_declare_group().shems_td3_group_workspace_floats(C.byref(nws)))
+        return group_extra_blocks(n_critic, self.tiled, nws.value)
+
+    # ---- views ----
+    def _view(self, l, name):
+        o, n = self.layout[name]
+        return self.slab[l, o:o + n]
+
+    def critic2_of(self, l):
+        """Learner l's critic 2 in Flux order (on a tiled group: current after flux_())."""
+        return self._view(l, "critic2")
+
+    def critic2_t_of(self, l):
+        return self._view(l, "critic2_t")
+
+    def a_smooth(self, l):
+        """a~' = clamp(actor_t(s') + eps, -1, 1) of learner l's last update, [2][128] (columns >= batch_l are padding)."""
+        return self._view(l, "ws2")[GROUP_WS2_PUB:GROUP_WS2_PUB + 2 * BP].view(2, BP)
+
+    def y_target(self, l):
+        return self._view(l, "ws2")[GROUP_WS2_PUB + 2 * BP:GROUP_WS2_PUB + 3 * BP]
+
+    def q_target1(self, l):
+        return self._view(l, "ws2")[GROUP_WS2_PUB + 3 * BP:GROUP_WS2_PUB + 4 * BP]
+
+    def q_target2(self, l):
+        return self._view(l, "ws2")[GROUP_WS2_PUB + 4 * BP:GROUP_WS2_PUB + 5 * BP]
+
+    @property
+    def losses2(self):
+        """[count] the mse of every learner's critic 2 at its last update."""
+        o = self.layout["losses2"][0]
+        return self.slab[:, o]
+
+    # ---- the tiled layout covers critic 2: the layout launches again, on the record whose critic fields name critic 2's blocks ----
+    def _td3_args(self):
+        """Learner 0's shems_td3: its shems_ddpg and the critic-2 blocks of its slab."""
+        a0 = self.learners[0]
+        p = lambda name: self.slab.data_ptr() + 4 * self.layout[name][0]
+        return Td3Args(a0._ddpg_args(), p("critic2"), p("critic2_t"), p("m_critic2"), p("v_critic2"), p("grad_critic2"), p("ws2"), p("losses2"),
+                       self.sigma_trg, self.clip_trg)
+
+    def _critic2_alias(self):
+        """(shems_ddpg, shems_group_w2t) that name critic 2 where critic 1 stands: what shems_group_w2_to_tiled / _to_flux take for it."""
+        t3, w = self._td3_args(), self.w2t_struct()
+        d = t3.d
+        d.critic, d.critic_t, d.m_critic, d.v_critic, d.grad_critic = t3.critic2, t3.critic2_t, t3.m_critic2, t3.v_critic2, t3.grad_critic2
+        return d, G.GroupW2T(w.actor, self.slab.data_ptr() + 4 * self.layout["w2t_critic2"][0])
+
+    def _use_tiled(self):
+        was = self._tiled_valid
+        on = super()._use_tiled()
+        if on and not was:
+            d, w = self._critic2_alias()
+            g = self.struct()
+            _capi.check(self.L.shems_group_w2_to_tiled(C.byref(d), C.byref(g), C.byref(w), self._stream()))
+        return on
+
+    def flux_(self):
+        stale = self.tiled and not self._flux_valid
+        super().flux_()
+        if stale:
+            d, w = self._critic2_alias()
+            g = self.struct()
+            _capi.check(self.L.shems_group_w2_to_flux(C.byref(d), C.byref(g), C.byref(w), self._stream()))
+        return self
+
+    def set_params(self, l, actor=None, critic=None, sync_targets=True, critic2=None):
+        """learners[l].set_params, and critic2: a flat Flux-layout vector of learner l's critic size (padded here) or of the (250, 500)
+        layout, as TD3Agent.set_params takes it."""
+        ag = self.learners[l]
+        ag.set_params(actor=actor, critic=critic, sync_targets=sync_targets)
+        if critic2 is not None:
+            v = np.asarray(critic2, D.f32)
+            n_own = D.net_size(D.STATE + D.ACTION, 1, ag.hidden)
+            if v.size not in (ag.n_critic, n_own):
+                raise ValueError(f"set_params: critic2 has {v.size} parameters; a {ag.hidden} network holds {n_own}")
+            if v.size != ag.n_critic:
+                v = D.pad_net(v, D.STATE + D.ACTION, 1, ag.hidden)
+            self._before_flux_write()
+            self.critic2_of(l).copy_(self.torch.as_tensor(v))
+            if sync_targets:
+                self.critic2_t_of(l).copy_(self.critic2_of(l))
+
+    # ---- refused paths ----
+    def evaluate(self, rings=None, tick=None, tau=None):
+        raise NotImplementedError("TD3 learner group: evaluate() is the critic-only update of ONE critic; the twin critics have none "
+                                  "(and so imitation.warm_start_group does not run on a TD3 group)")
+
+    def _hold_ptr(self):
+        if self._hp_dev is None:
+            return None
+        return self._hp_variant(0.0, check=False)
+
+    def replay(self, tick=None, update_policy=None):
+        """One TD3 update of every learner (shems_td3_group_update_tp: seven launches, ten on a policy step).  update_policy: None = the
+        schedule, is_policy_step(self.updates, self.policy_delay).  bp_critic advances on every update, bp_actor on policy steps, both
+        in lockstep over the learners; `updates` counts updates.  On a tiled group the Flux-order view goes stale, critic 2 included."""
+        if self.form != "throughput":
+            raise NotImplementedError(f"TD3 learner group: form={self.form!r} has no twin-critic update")
+        policy = is_policy_step(self.updates, self.policy_delay) if update_policy is None else bool(update_policy)
+        a0, g, r0 = self.learners[0], self.struct(), self._ring0()
+        if self._hp_dev is None and a0.batch > BP:
+            raise NotImplementedError(f"TD3 learner group: batch {a0.batch} > {BP}: the twin-critic update holds one {BP}-column pass")
+        tl = self._use_tiled()
+        t3 = self._td3_args()
+        tick = self.updates if tick is None else tick
+        w = C.byref(self.w2t_struct()) if tl else None
+        w2 = C.c_void_p(self.slab.data_ptr() + 4 * self.layout["w2t_critic2"][0]) if tl else None
+        _capi.check(self.L.shems_td3_group_update_tp(C.byref(t3), C.byref(r0), C.byref(g), w, w2, self._hp_ptr(), self._hold_ptr(),
+                                                     len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.eta_crit, a0.bp_critic[0],
+                                                     a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1], 1 if policy else 0,
+                                                     1 if self.store_grad else 0, self._stream()))
+        if tl:
+            self._flux_valid = False
+        for ag in self.learners:
+            ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
+            if policy:
+                ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
+            ag.updates += 1
+        self.updates += 1
+
+
 class TD3Agent(D.Agent):
     """The TD3 learner state on one GPU: an Agent and a second critic."""
 
@@ -100,7 +309,8 @@ class TD3Agent(D.Agent):
             raise NotImplementedError("TD3: parameter noise (noise_type = 'pn') adapts between getData and the updates of replay(); "
                                       "the TD3 update is one call")
         if kw.get("tensors") is not None:
-            raise NotImplementedError("TD3: a learner of a learner group keeps its state in the group's slab, which holds no second critic")
+            raise NotImplementedError("TD3: a learner of a learner group keeps its state in the group's slab; twin critics for a group are "
+                                      "td3.TD3LearnerGroup")
         if not (math.isfinite(float(sigma_trg)) and float(sigma_trg) >= 0.0 and math.isfinite(float(clip_trg)) and float(clip_trg) >= 0.0):
             raise ValueError(f"TD3: sigma_trg = {sigma_trg}, clip_trg = {clip_trg} must be finite and >= 0")
         is_policy_step(0, policy_delay)                      # (refuses d < 1)
