@@ -381,6 +381,55 @@ int shems_td3_workspace_floats(int64_t *out);
 int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                      double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act,
                      int update_policy, void *stream);
+/* ------------------------------------------- prioritized replay update -- */
+/* Prioritized experience replay (Schaul et al. 2016, proportional variant) for the single learner, in replay()'s conventions.  The
+ * reference has no such sampler; the definition is this one (csrc/shems_per_core.h states it again with every summation order;
+ * DESIGN.md 4p).  A prioritized ring is a shems_replay plus prio [capacity] (pi_j = p_j^alpha >= 0, the power applied) and pmax [1]
+ * (the running maximum of every pi ever written; 1.0 at the start, never decreasing).  One update with (alpha, beta, eps_p), the
+ * freshly pushed range (fresh_pos, fresh_count) and (seed, tick):
+ *   1. the fresh_count slots from fresh_pos (mod capacity) receive pmax[0] before anything is summed; fresh_count >= capacity = all;
+ *   2. the slots [0, ring_len) are cut into blocks of 256 (the last zero-padded): S_b = ((s0 + s1) + s2) + s3 over the four chunk sums
+ *      of 64 slots, each a balanced pairwise tree; C_b = C_{b-1} + S_b in block order; T = C_last.  No atomics, fixed orders;
+ *   3. column m < batch: u_m = (w >> 8) 2^-24 with w = word m & 3 of the Philox4x32-10 block at counter (m >> 2, 0, tick, 0x50455253),
+ *      key seed; t_m = (m + u_m) * (T / batch), uncontracted; j_m = the first slot whose running sum exceeds t_m (the first block with
+ *      C_b > t_m, then C_{b-1} + pi in slot order inside it; where rounding leaves no such slot, the last slot with pi > 0 of the
+ *      block the search ended in), at most ring_len - 1.  Pad columns publish slot -1;
+ *   4. w_m = (ring_len pi_{j_m} / T)^(-beta) / max over the live columns (powf: tolerance class; beta = 0 gives exactly 1.0f), pad
+ *      columns 0;
+ *   5. replay() (DDPG.jl:121-145) on the columns j_m with the critic's head weighted: diff = q - y, dq = 2 w_m diff / batch,
+ *      losses[0] = sum w_m diff^2 / batch in head_loss's order; the actor's side, both ADAM steps and the soft updates unchanged;
+ *   6. pi_{j_m} <- (|diff_m| + eps_p)^alpha for every live column (the highest column wins a slot drawn twice);
+ *      pmax[0] <- max(pmax[0], max_m pi);
+ *   7. the beta powers and the tick are host state, as for shems_ddpg_update.
+ * Six dependent launches: k_per_sample (steps 1-4, one workgroup), then K1..K5 with K1 and K3 as the instantiations k_fwd_per /
+ * k_grad_per, which read the published slots and weights; step 6 rides in k_grad_per's publishing workgroup.
+ * ws: shems_per_workspace_floats(capacity) floats; after a draw it holds T, the largest raw weight, the number of blocks (int32), one
+ * reserved word, then slots [128] (int32), weights [128], u [128], t [128], S_b [nb], C_b [nb], nb = ceil(ring_len / 256).
+ * beta is read on every call, so the host may anneal it. */
+typedef struct shems_per {
+    float *prio;                 /* [capacity] pi, 16-byte aligned                                   */
+    float *pmax;                 /* [1] running maximum, 1.0 at the start                            */
+    float *ws;                   /* shems_per_workspace_floats(capacity) floats, 16-byte aligned     */
+    float alpha, beta, eps_p;    /* 0.6, 0.4, 1e-6 (the paper's proportional variant)                */
+    int32_t reserved;
+} shems_per;
+int shems_per_workspace_floats(int64_t capacity, int64_t *out);
+/* Steps 1-4 alone (tests, a Julia caller).  SHEMS_ERR_ARG as shems_ddpg_update_per's for the ring's own arguments. */
+int shems_per_sample_dev(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count,
+                         uint64_t seed, uint32_t tick, int32_t batch, void *stream);
+/* Step 5 on slots and weights the caller supplies (d_idx [128] int32, -1 in the pad columns; d_w [128]): no sampler launch, no
+ * write-back.  With d_idx = shems_ddpg_sample_indices(seed, tick) and weights of 1.0 it leaves shems_ddpg_update's bits. */
+int shems_ddpg_update_given(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, const int32_t *d_idx,
+                            const float *d_w, double eta_crit, double bp1_crit, double bp2_crit,
+                            double eta_act, double bp1_act, double bp2_act, void *stream);
+/* Steps 1-6.  SHEMS_ERR_ARG, nothing launched: whatever shems_ddpg_update refuses; a NULL, misaligned or overlapping prio / pmax /
+ * workspace; alpha, beta or eps_p negative or not finite, beta > 1; ring_len outside 1..capacity; capacity above 262144 (the sampler's
+ * one workgroup keeps every block sum in LDS); a fresh range that starts outside the ring or, on a ring not yet full, leaves the
+ * filled slots.  SHEMS_ERR_STATE: a learner between shems_ddpg_tiled_enter and shems_ddpg_tiled_leave. */
+int shems_ddpg_update_per(const shems_ddpg *d, const shems_replay *ring, const shems_per *per, int64_t ring_len,
+                          int64_t fresh_pos, int64_t fresh_count, uint64_t seed, uint32_t tick,
+                          double eta_crit, double bp1_crit, double bp2_crit,
+                          double eta_act, double bp1_act, double bp2_act, void *stream);
 /* The minibatch indices of (seed, tick): host helper for tests (same Philox as the device). */
 int shems_ddpg_sample_indices(uint64_t seed, uint32_t tick, int32_t batch, int64_t ring_len, int64_t *out);
 /* ------------------------------------------ data-parallel replicas -- */

@@ -89,6 +89,40 @@ def _declare(L):
     return sigs
 
 
+class PerArgs(C.Structure):            # shems_per
+    _fields_ = [("prio", C.c_void_p), ("pmax", C.c_void_p), ("ws", C.c_void_p),
+                ("alpha", C.c_float), ("beta", C.c_float), ("eps_p", C.c_float), ("reserved", C.c_int32)]
+
+
+PER_MAX_SLOTS = 262144                 # kPerMaxSlots: the sampler's one workgroup keeps every block sum in LDS
+PER_COLS = 128
+PW_T, PW_IDX, PW_W, PW_U, PW_TM, PW_S = 0, 4, 132, 260, 388, 516     # the workspace carve of csrc/shems_per_core.h (floats)
+
+
+def _per_sigs():
+    vp, i64, i32, u64, u32, dbl = C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32, C.c_double
+    PP, PR_ = C.POINTER(PerArgs), C.POINTER(Replay)
+    return {                                    # (shems_ddpg * is passed as a void pointer: its mirror lives in ddpg.py)
+        "shems_per_workspace_floats": [i64, C.POINTER(i64)],
+        "shems_per_sample_dev": [PP, i64, i64, i64, i64, u64, u32, i32, vp],
+        "shems_ddpg_update_given": [vp, PR_, i64, vp, vp, dbl, dbl, dbl, dbl, dbl, dbl, vp],
+        "shems_ddpg_update_per": [vp, PR_, PP, i64, i64, i64, u64, u32, dbl, dbl, dbl, dbl, dbl, dbl, vp],
+    }
+
+
+def declare_per():
+    """The prototypes of the prioritized-replay entry points (_per_sigs: compared with include/shems_hip.h by tests/test_per_host.py)."""
+    L = lib()
+    if getattr(L, "_per_declared", False):
+        return L
+    for name, args in _per_sigs().items():
+        fn = getattr(L, name)
+        fn.argtypes = args
+        fn.restype = C.c_int
+    L._per_declared = True
+    return L
+
+
 def exported_symbols():
     """Names include/shems_hip.h declares (used by the CPU-side ABI test)."""
     import re

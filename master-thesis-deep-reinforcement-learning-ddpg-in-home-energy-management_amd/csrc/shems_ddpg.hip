@@ -37,6 +37,7 @@
 // block in front of k_fwd_td3.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 
@@ -44,6 +45,7 @@
 #include "shems_internal.h"
 #include "shems_adam.h"
 #include "shems_td3_core.h"
+#include "shems_per_core.h"
 
 namespace shems {
 
@@ -361,16 +363,23 @@ struct PrepArgs {
 // slot comes from the counter RNG) is in flight together with every other load of the workgroup's first phase.
 // CLONE (the supervised update, shems_ddpg_clone_update): a ring of demonstrations holds s and a only -- s', r and done are never read.
 struct PrepRegs { float s[SIN], s2[SIN], lo[SIN], hi[SIN], a[2], r, dn; int64_t j; };
-template <bool CLONE = false>
-__device__ __forceinline__ void prep_load(const PrepArgs &A, int m, int which, bool publish, PrepRegs &R)
+// GIVEN (shems_ddpg_update_given / shems_ddpg_update_per): the slot of column m comes from a published index array -- the prioritized
+// sampler's, or the caller's -- in the place of the Philox draw; -1 (a pad column) and anything outside the ring gather a valid slot.
+template <bool CLONE = false, bool GIVEN = false>
+__device__ __forceinline__ void prep_load(const PrepArgs &A, int m, int which, bool publish, PrepRegs &R, const int32_t *gidx = nullptr)
 {
     const shems_ddpg &d = A.d;
     const shems_replay &ring = A.ring;
     const bool want_s2 = !CLONE && (publish || which == 0), want_s = publish || which != 0, want_a = publish || which == 1;
-    const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)A.seed, (uint32_t)(A.seed >> 32));
-    const uint32_t w = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
-    int64_t j = (int64_t)(w % (uint32_t)(A.ring_len - A.excl_count));
-    if (A.excl_count > 0) j = (A.excl_pos + A.excl_count + j) % ring.capacity;         // skip the window another stream is writing
+    int64_t j;
+    if constexpr (GIVEN) {
+        j = min(max((int64_t)gidx[m], (int64_t)0), A.ring_len - 1);
+    } else {
+        const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)A.seed, (uint32_t)(A.seed >> 32));
+        const uint32_t w = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
+        j = (int64_t)(w % (uint32_t)(A.ring_len - A.excl_count));
+        if (A.excl_count > 0) j = (A.excl_pos + A.excl_count + j) % ring.capacity;     // skip the window another stream is writing
+    }
     R.j = j;                                                                            // (pad columns m >= batch gather a valid slot too and discard it)
 #pragma unroll
     for (int k = 0; k < SIN; ++k) {
@@ -458,8 +467,9 @@ template <bool QG> struct FwdShape {
     static constexpr int LDS = (256 * WST + W1K * 32 + W1K * W1C + 256 + 4 * 16 * 64 + 4 * 2 * 32 + (QG ? 32 * 32 + 4 * 2 * 32 : 0)) * 4;
 };
 
-template <int IN, int PREP, bool QG, bool CLONE = false, bool TILED = false, bool SMOOTH = false>
-__device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const PrepArgs *pa, int bx, int job, const Td3Noise *tn = nullptr)
+template <int IN, int PREP, bool QG, bool CLONE = false, bool TILED = false, bool SMOOTH = false, bool GIVEN = false>
+__device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const PrepArgs *pa, int bx, int job, const Td3Noise *tn = nullptr,
+                                         const int32_t *gidx = nullptr)
 {
     typedef FwdShape<QG> SH;
     constexpr int WST = SH::WST;
@@ -487,7 +497,7 @@ __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const Pre
         if (duty == 0) {
             if (tid < BP) {
                 PrepRegs pr;
-                prep_load<CLONE>(*pa, tid, 0, true, pr);
+                prep_load<CLONE, GIVEN>(*pa, tid, 0, true, pr, gidx);
                 prep_store(*pa, tid, nullptr, 0, 0, 0, true, pr);
             }
         } else if (duty <= 4) {
@@ -536,7 +546,7 @@ __device__ __forceinline__ void fwd_body(const FwdJob &J, float *smem, const Pre
     // First launch of an update: no separate sample/gather/pack launch.  Every tile workgroup samples the minibatch and gathers +
     // normalises what its network reads straight into its LDS input block, and packs the layer-1 image it needs from the
     // parameter block; the extra workgroups (above) publish the workspace copies for the later launches.
-    if (PREP == 1 && tid < 32) prep_load<CLONE>(*pa, mbase + tid, J.which, false, pr);
+    if (PREP == 1 && tid < 32) prep_load<CLONE, GIVEN>(*pa, mbase + tid, J.which, false, pr, gidx);
     // W2[0..255][n0..n0+31] (rows of 128 B, 8 float4 each): 2048 float4, 8 per thread.  Rows 250..255 are copies of row 249 (clamped
     // address): they only ever multiply layer-1 activations that are exactly zero (the image has no columns >= 250), in the forward
     // product, and in QG's backward product they feed output rows whose relu mask is off.  Columns >= 500 of the last tile read the
@@ -1315,6 +1325,79 @@ __device__ __forceinline__ void head_twin(const shems_ddpg &d, const TwinHead &h
     }
 }
 
+// ---- prioritized replay (shems_ddpg_update_given / shems_ddpg_update_per): the weighted critic head ------------------------------
+// head_loss's compile-time sibling, in the prologue of every workgroup of k_grad_per: the same loads (head_loss_load) and summation
+// orders with dq = 2 w diff / B and losses[0] = sum w diff^2 / B, so weights of 1.0 give head_loss's bits.  Workgroup 0 publishes as
+// head_loss does and, when asked (shems_ddpg_update_per), writes the drawn slots' new priorities back (shems_per_core.h, step 6): one
+// writer per slot -- the highest column that drew it, decided over the 128 slots in LDS -- and pmax raised to the largest new priority.
+struct PerHead {
+    const float *w;                    // [BP] importance weights (0 in the pad columns)
+    const int32_t *idx;                // [BP] the drawn slots (write-back)
+    float *prio, *pmax;                // write-back targets, or null: no write-back
+    int64_t ring_len;
+    float alpha, eps_p;
+};
+struct PerRegs { float w; int32_t j; float pm0; };
+__device__ __forceinline__ void head_per_load(const PerHead &h, PerRegs &R, bool publisher)
+{
+    const int m = threadIdx.x & 127;
+    R.w = h.w[m];
+    R.j = (publisher && h.prio) ? h.idx[m] : -1;                  // the slots: the write-back's workgroup alone (uniform per workgroup)
+    R.pm0 = (publisher && h.prio) ? h.pmax[0] : 0.0f;             // pmax as it stands, fetched with the head's other loads
+}
+__device__ __forceinline__ void head_per(const shems_ddpg &d, const PerHead &h, const HeadRegs &R, const PerRegs &G, float *d3 /*LDS [2][BP]*/,
+                                         float *red /*LDS [8]*/, float *scr /*LDS, >= BP + 2 words*/, bool publisher, const AdamCtx *fuse)
+{
+    float *ws = d.ws;
+    const int t = threadIdx.x, m = t & 127;
+    float dq = 0.0f, diff = 0.0f;
+    if (t < BP) {
+        float q2 = R.s[0], q = R.s[1];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) { q2 += R.v[i]; q += R.v[NT + i]; }
+        const float y = R.s[2] + d.gamma * (1.0f - R.s[3]) * q2;                                  // DDPG.jl:133
+        diff = m < d.batch ? q - y : 0.0f;
+        dq = 2.0f * G.w * diff / (float)d.batch;                                            // d (sum w diff^2 / B) / d q
+        if (publisher) { ws[WS_Y + m] = y; ws[WS_Q + m] = q; ws[WS_D3C + m] = dq; }
+    }
+    d3[t] = t < BP ? dq : 0.0f;
+    if (publisher) {
+        const bool wb = h.prio != nullptr, live = t < BP && m < d.batch;
+        const int32_t j = (int32_t)min(max((int64_t)G.j, (int64_t)0), h.ring_len - 1);
+        float pnew = 0.0f;
+        int32_t *sj = reinterpret_cast<int32_t *>(scr);
+        if (wb) {
+            if (live) pnew = per_priority(diff, h.eps_p, h.alpha);
+            if (t < BP) sj[t] = live ? j : -1;
+            float pm = pnew;                                                                // >= 0; threads outside the batch hold 0
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) pm = fmaxf(pm, __shfl_xor(pm, off, 64));
+            if ((t & 63) == 0 && t < BP) scr[BP + (t >> 6)] = pm;
+        }
+        const float wd = G.w * diff;                                                        // (w diff) diff: the product wave_sum takes has head_loss's
+        const float s1 = wave_sum(wd * diff), s2 = wave_sum(dq);                            // shape, so w = 1 contracts into its first add the same way
+        if ((t & 63) == 0) { red[t >> 6] = s1; red[4 + (t >> 6)] = s2; }
+        __syncthreads();
+        if (t == 0) {
+            d.losses[0] = (red[0] + red[1]) / (float)d.batch;
+            const float g = red[4] + red[5];
+            d.grad_critic[off_b3(CIN, 1)] = g;
+            if (fuse) adam_elem(*fuse, off_b3(CIN, 1), g);
+            if (wb) h.pmax[0] = fmaxf(G.pm0, fmaxf(scr[BP], scr[BP + 1]));
+        }
+        if (wb && live) {
+            bool last = true;
+            const int4 *sj4 = reinterpret_cast<const int4 *>(sj);
+#pragma unroll
+            for (int c = 0; c < BP / 4; ++c) {
+                const int4 v = sj4[c];
+                last = last && !((4 * c + 0 > t && v.x == j) || (4 * c + 1 > t && v.y == j) || (4 * c + 2 > t && v.z == j) || (4 * c + 3 > t && v.w == j));
+            }
+            if (last) h.prio[j] = pnew;
+        }
+    }
+}
+
 // ---- K3 / K5: every gradient block of one network, by batch contractions only -------------------------------------------
 // D2[n][m] = (sum_o W3[n][o] d3[o][m]) * (h2[n][m] > 0) is generated while staging, never stored.
 //   W workgroups (kt, nt): gW2[32 k][32 n] = sum_m h1[k][m] D2[n][m], one 16 x 16 block per wave over the whole batch
@@ -1408,8 +1491,9 @@ __device__ __forceinline__ void l1row_wave(const L1Row<IN, OUT> &R, const float 
 }
 
 // CLONE: the supervised update's instantiation (k_grad_clone) takes the cloning head at compile time; otherwise GradArgs.head decides.
-template <int IN, int OUT, bool CLONE = false, bool TILED = false, bool TWIN = false>
-__device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx, const TwinHead *th = nullptr)
+// PER: the weighted critic head of the prioritized update (k_grad_per), head_loss's compile-time sibling.
+template <int IN, int OUT, bool CLONE = false, bool TILED = false, bool TWIN = false, bool PER = false>
+__device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx, const TwinHead *th = nullptr, const PerHead *ph = nullptr)
 {
     // bx: this workgroup's index within the gradient grid
     float *Bt = smem;                          // W: [32 n][GR_PS] D2 panel
@@ -1437,11 +1521,14 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
         L1Row<IN, OUT> R;
         l1row_load<IN, OUT>(A, min(k, H1N - 1), lane, R);
         [[maybe_unused]] TwinRegs tr;
-        if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
+        [[maybe_unused]] PerRegs pg;
+        if constexpr (PER) { head_loss_load(A.dd, hr); head_per_load(*ph, pg, false); }
+        else if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
         else if constexpr (CLONE) head_clone_load(A.dd, hr);
         else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
         STAMP(kRegion, 1);
-        if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, false, nullptr);
+        if constexpr (PER) head_per(A.dd, *ph, hr, pg, d3, red, smem, false, nullptr);
+        else if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, false, nullptr);
         else if constexpr (CLONE) head_clone(A.dd, hr, d3, red, false, nullptr);
         else if (A.head == 1) head_loss(A.dd, hr, d3, red, false, nullptr); else head_actor(A.dd, hr, d3, red, false, nullptr);
         __syncthreads();
@@ -1509,14 +1596,17 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
     }
     HeadRegs hr;
     [[maybe_unused]] TwinRegs tr;
-    if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
+    [[maybe_unused]] PerRegs pg;
+    if constexpr (PER) { head_loss_load(A.dd, hr); head_per_load(*ph, pg, publisher); }
+    else if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
     else if constexpr (CLONE) head_clone_load(A.dd, hr);
     else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
     if (is_w) {
         build_x_store<IN>(A.x, xr, xs, false);
         if (tid < 96) *reinterpret_cast<f32x4 *>(w1 + (tid >> 3) * 32 + 4 * (tid & 7)) = wq;
     }
-    if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, publisher, fz);
+    if constexpr (PER) head_per(A.dd, *ph, hr, pg, d3, red, Bt, publisher, fz);      // (Bt: free until the barrier behind the heads)
+    else if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, publisher, fz);
     else if constexpr (CLONE) head_clone(A.dd, hr, d3, red, publisher, fz);
     else if (A.head == 1) head_loss(A.dd, hr, d3, red, publisher, fz); else head_actor(A.dd, hr, d3, red, publisher, fz);
     if (tid < 2 * 32) w3s[tid] = (tid & 1) < OUT ? w3v : 0.0f;
@@ -1814,6 +1904,110 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     else grad_body<CIN, 1, false, false, true>(A.g[1], smem, (int)blockIdx.x - kPer, &A.h[1]);
 }
 
+// ---- prioritized replay: the sampler launch and the GIVEN instantiations of K1 and K3, behind the others (see k_fwd_clone) ----
+// k_per_sample, ONE workgroup of 1024 threads (steps 1-4 of shems_per_core.h): at 24 000 slots the ring's priorities are 96 KB, 24
+// floats per thread in coalesced waves; the chunk sums (one wave_sum each), the block sums and the running sums stay in LDS, so the 128
+// columns search them without another launch.  Wave v takes chunk v & 3 of the blocks (v >> 2) + 4 i, eight of them per round of loads.
+struct PerSampleArgs {
+    float *prio; const float *pmax; float *ws;
+    int64_t capacity, ring_len, fresh_pos, fresh_count;
+    uint64_t seed; uint32_t tick; int batch; float beta;
+};
+__global__ __launch_bounds__(1024) void k_per_sample(PerSampleArgs A)
+{
+    __shared__ float sc[kPerMaxSlots / kPerChunk];          // chunk sums
+    __shared__ float sS[kPerMaxSlots / kPerBlock], sC[kPerMaxSlots / kPerBlock];
+    __shared__ float sraw[kPerCols];
+    __shared__ int slast;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nb = (int)per_blocks(A.ring_len);
+    const float pmax = A.pmax[0];
+    // steps 1 + 2a: fresh slots take pmax (stored, and used from the register); every chunk's tree sum
+    for (int b0 = 0; b0 < nb; b0 += 32) {                  // eight chunks per wave and round: at 24 000 slots three rounds of loads
+        float x[8];
+        int64_t jj[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            jj[i] = ((int64_t)(b0 + (wave >> 2) + 4 * i) * 4 + (wave & 3)) * kPerChunk + lane;
+            x[i] = A.prio[min(jj[i], A.ring_len - 1)];                                       // clamped, consumed under the bound below
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool in = jj[i] < A.ring_len;
+            if (in && per_fresh(jj[i], A.fresh_pos, A.fresh_count, A.capacity)) { x[i] = pmax; A.prio[jj[i]] = pmax; }
+            const float s = wave_sum(in ? x[i] : 0.0f);
+            const int c = (b0 + (wave >> 2) + 4 * i) * 4 + (wave & 3);
+            if (lane == 0 && c < 4 * nb) sc[c] = s;
+        }
+    }
+    __syncthreads();
+    // step 2b: block sums, then the running sums in block order (one thread; the reads of sixteen blocks go out together)
+    for (int b = tid; b < nb; b += 1024) sS[b] = per_block_sum(sc[4 * b], sc[4 * b + 1], sc[4 * b + 2], sc[4 * b + 3]);
+    __syncthreads();
+    if (tid == 0) {
+        float run = 0.0f;
+        int lastpos = 0;
+#pragma unroll 16
+        for (int b = 0; b < nb; ++b) {
+            const float s = sS[b];
+            run = b == 0 ? s : run + s;
+            sC[b] = run;
+            lastpos = s > 0.0f ? b : lastpos;
+        }
+        slast = lastpos;
+    }
+    __syncthreads();
+    for (int b = tid; b < nb; b += 1024) { A.ws[PW_S + b] = sS[b]; A.ws[PW_S + nb + b] = sC[b]; }
+    const float T = sC[nb - 1];
+    // steps 3 + 4: one column per thread
+    float raw = 0.0f;
+    int64_t j = 0;
+    float u = 0.0f, tm = 0.0f;
+    if (tid < kPerCols) {
+        u = per_u(A.seed, A.tick, tid);
+        tm = per_target(tid, u, T, A.batch);
+        int lo = 0, hi = nb;                                        // first b with C_b > t (C never decreases): bisection
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (sC[mid] > tm) hi = mid; else lo = mid + 1; }
+        const int b = lo < nb ? lo : slast;
+        const float *prio = A.prio;
+        const int cap = (int)A.capacity, fp = (int)A.fresh_pos, fc = (int)min(A.fresh_count, A.capacity);      // (all <= kPerMaxSlots)
+        auto at = [=](int q) { const float v = prio[q]; return per_fresh32(q, fp, fc, cap) ? pmax : v; };
+        j = per_search_block(b, b > 0 ? sC[b - 1] : 0.0f, tm, (int)A.ring_len, at);
+        raw = per_raw_weight(A.ring_len, at((int)j), T, A.beta);
+        sraw[tid] = tid < A.batch ? raw : 0.0f;
+    }
+    __syncthreads();
+    if (tid < kPerCols) {
+        float mx = 0.0f;
+        for (int m = 0; m < kPerCols; ++m) mx = fmaxf(mx, sraw[m]);
+        const bool live = tid < A.batch;
+        reinterpret_cast<int32_t *>(A.ws + PW_IDX)[tid] = live ? (int32_t)j : -1;
+        A.ws[PW_W + tid] = live ? raw / mx : 0.0f;
+        A.ws[PW_U + tid] = u;
+        A.ws[PW_TM + tid] = tm;
+        if (tid == 0) { A.ws[PW_T] = T; A.ws[PW_T + 1] = mx; reinterpret_cast<int32_t *>(A.ws + PW_T)[2] = nb; A.ws[PW_T + 3] = 0.0f; }
+    }
+}
+
+// K1 and K3 of the prioritized update: k_fwd's three jobs with prep_load<GIVEN>, the critic's gradient launch with the weighted head.
+struct PerFwdArgs { FwdArgs f; const int32_t *idx; };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_fwd_per(PerFwdArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int kPerJob = NT * (BP / 32) + 6;
+    const int job = (int)blockIdx.x / kPerJob, bx = (int)blockIdx.x - job * kPerJob;
+    const FwdJob J = job == 0 ? A.f.job[0] : job == 1 ? A.f.job[1] : A.f.job[2];
+    const PrepArgs pa = A.f.pa;
+    if (J.in == SIN) fwd_body<SIN, 1, false, false, false, false, true>(J, smem, &pa, bx, job, nullptr, A.idx);
+    else fwd_body<CIN, 1, false, false, false, false, true>(J, smem, &pa, bx, job, nullptr, A.idx);
+}
+struct PerGradArgs { GradArgs g; PerHead h; };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_grad_per(PerGradArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    grad_body<CIN, 1, false, false, false, true>(A.g, smem, (int)blockIdx.x, nullptr, &A.h);
+}
+
 constexpr int FWD_LDS = FwdShape<false>::LDS, QG_LDS = FWD_LDS > QG16_LDS ? FWD_LDS : QG16_LDS;
 constexpr int MID_LDS = FWD_LDS > E_LDS ? FWD_LDS : E_LDS;
 static_assert(QG_LDS <= 160 * 1024, "one workgroup's LDS");
@@ -1839,6 +2033,14 @@ static int set_lds_attrs_tiled()
     if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_t), QG_LDS, "attr k_fwd_t")) return rc;
     if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid_t), MID_LDS, "attr k_mid_t")) return rc;
     if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_t), GR_LDS, "attr k_grad_t")) return rc;
+    return SHEMS_OK;
+}
+
+static int set_lds_attrs_per()
+{
+    static std::atomic<uint64_t> m_fwd{0}, m_grad{0};
+    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_per), FWD_LDS, "attr k_fwd_per")) return rc;
+    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_per), GR_LDS, "attr k_grad_per")) return rc;
     return SHEMS_OK;
 }
 
@@ -1932,6 +2134,8 @@ static AdamCtx adam_ctx(const shems_ddpg *d, bool critic, const AdamScalars &s)
                             s.eta, s.bp1, s.bp2, s.gscale, k1, ic2, d->tau};
 }
 
+struct GivenLaunch { const int32_t *idx; PerHead h; };
+
 // K1 + K2 + K3: the critic side of replay() (DDPG.jl:123-135).  fuse: K3 applies ADAM + the soft target update itself.
 // Data-parallel form only: the actor's two E products, when shems_ddpg.flags asked critic_grad to leave them out of K2 so that they
 // can run under the critic's gradient all-reduce (they need nothing the critic update produces).
@@ -1950,8 +2154,9 @@ static int actor_e_launch(const shems_ddpg *d, unsigned L, int64_t gs, hipStream
 
 static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                        int64_t excl_pos, int64_t excl_count, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream,
-                       bool critic_only = false, const shems_group_w2t *t = nullptr)
+                       bool critic_only = false, const shems_group_w2t *t = nullptr, const GivenLaunch *gv = nullptr)
 {
+    // gv: slots and weights are given (shems_ddpg_update_given): K1 and K3 are k_fwd_per / k_grad_per, K2 is the same launch
     // t: a single learner on the tiled working layout (L == 1, fused): W2 / moments / targets from the regions, the *_t kernels
     if (int rc = check_ddpg(d, "shems_ddpg_critic_grad", t)) return rc;
     if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
@@ -1977,7 +2182,8 @@ static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ri
     f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count};
     if (t) { f.job[0].W2t = t->actor + 3 * W2T_TILE; f.job[1].W2t = t->critic + 2 * W2T_TILE; f.job[2].W2t = t->actor + 2 * W2T_TILE; }
     // + 6 publishing workgroups per job (see fwd_body); they do their work in job 0, so the critic-only update drops job 2 whole
-    if (t) hipLaunchKernelGGL(k_fwd_t, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
+    if (gv) hipLaunchKernelGGL(k_fwd_per, dim3(3 * (fgx + 6), 1, 1), dim3(256), flds, st, PerFwdArgs{f, gv->idx});
+    else if (t) hipLaunchKernelGGL(k_fwd_t, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
     else hipLaunchKernelGGL(k_fwd, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
     // K2: critic_target on [s'; actor_target(s')] | E of the critic | E of the actor's two outputs
     MidArgs m;
@@ -2001,7 +2207,8 @@ static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ri
     g.grad = d->grad_critic; g.E0 = SC + SL_EP; g.E1 = nullptr; g.head = 1; g.fuse = fuse ? 1 : 0; g.dd = *d; g.gstride = gs;
     g.c = adam_ctx(d, true, fuse ? *fuse : AdamScalars{0, 0.5, 0.5, 1.0, nullptr});
     g.w2t = t ? t->critic : nullptr;
-    if (t) hipLaunchKernelGGL(k_grad_t, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
+    if (gv) hipLaunchKernelGGL(k_grad_per, dim3(GR_NW + GR_NG + GR_NR, 1, 1), dim3(256), GR_LDS, st, PerGradArgs{g, gv->h});
+    else if (t) hipLaunchKernelGGL(k_grad_t, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
     else hipLaunchKernelGGL(k_grad, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
     return hip_ok(hipGetLastError(), "ddpg critic-side launches");
 }
@@ -2196,6 +2403,104 @@ int shems_ddpg_critic_update(const shems_ddpg *d, const shems_replay *ring, int6
     if (int rc = check_adam(bp1, bp2, "shems_ddpg_critic_update")) return rc;
     const AdamScalars sc{eta, bp1, bp2, 1.0, nullptr};
     return critic_side(d, ring, ring_len, seed, tick, 0, 0, 1, 0, &sc, stream, true);
+}
+
+/* ---- prioritized replay (shems_per_core.h) ---- */
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+// everything shems_ddpg_update refuses for (d, ring, ring_len), with nothing launched
+static int check_given(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, double bp1c, double bp2c, double bp1a, double bp2a,
+                       const char *fn)
+{
+    if (int rc = check_adam(bp1c, bp2c, fn)) return rc;
+    if (int rc = check_adam(bp1a, bp2a, fn)) return rc;
+    if (int rc = check_ddpg(d, fn)) return rc;
+    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
+        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    return set_lds_attrs_per();
+}
+static int check_per(const shems_per *per, const shems_ddpg *d, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count,
+                     int32_t batch, const char *fn)
+{
+    if (!per || !per->prio || !per->pmax || !per->ws) return set_error(SHEMS_ERR_ARG, "%s: shems_per has a NULL buffer", fn);
+    if (capacity < 1 || capacity > kPerMaxSlots)
+        return set_error(SHEMS_ERR_ARG, "%s: a prioritized ring holds 1..%lld slots (got %lld)", fn, (long long)kPerMaxSlots, (long long)capacity);
+    if (ring_len < 1 || ring_len > capacity) return set_error(SHEMS_ERR_ARG, "%s: ring_len must be in 1..capacity", fn);
+    if (batch < 1 || batch > kPerCols) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, batch);
+    if (((uintptr_t)per->prio & 15) != 0 || ((uintptr_t)per->ws & 15) != 0 || ((uintptr_t)per->pmax & 3) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: prio and the workspace must be 16-byte aligned, pmax 4-byte aligned", fn);
+    const size_t np = (size_t)capacity * 4, nw = (size_t)per_ws_floats(capacity) * 4;
+    if (ranges_overlap(per->prio, np, per->ws, nw) || ranges_overlap(per->prio, np, per->pmax, 4) || ranges_overlap(per->ws, nw, per->pmax, 4))
+        return set_error(SHEMS_ERR_ARG, "%s: prio, pmax and the workspace overlap", fn);
+    if (d && d->ws && (ranges_overlap(per->prio, np, d->ws, (size_t)WS_FLOATS * 4) || ranges_overlap(per->ws, nw, d->ws, (size_t)WS_FLOATS * 4) ||
+                       ranges_overlap(per->pmax, 4, d->ws, (size_t)WS_FLOATS * 4)))
+        return set_error(SHEMS_ERR_ARG, "%s: the prioritized ring's arrays overlap the learner's workspace", fn);
+    for (const float v : {per->alpha, per->beta, per->eps_p})
+        if (!(v >= 0.0f) || !std::isfinite(v)) return set_error(SHEMS_ERR_ARG, "%s: alpha, beta and eps_p must be finite and >= 0", fn);
+    if (per->beta > 1.0f) return set_error(SHEMS_ERR_ARG, "%s: beta must be in [0, 1] (got %g)", fn, (double)per->beta);
+    if (fresh_pos < 0 || fresh_pos >= capacity || fresh_count < 0)
+        return set_error(SHEMS_ERR_ARG, "%s: the fresh range must start inside the ring and have a count >= 0", fn);
+    if (fresh_count > 0 && fresh_count < capacity && ring_len < capacity && fresh_pos + fresh_count > ring_len)
+        return set_error(SHEMS_ERR_ARG, "%s: the fresh range [%lld, +%lld) leaves the %lld filled slots", fn, (long long)fresh_pos,
+                         (long long)fresh_count, (long long)ring_len);
+    return SHEMS_OK;
+}
+static int per_sample_launch(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed,
+                             uint32_t tick, int32_t batch, hipStream_t st)
+{
+    const PerSampleArgs a{per->prio, per->pmax, per->ws, capacity, ring_len, fresh_pos, fresh_count, seed, tick, batch, per->beta};
+    hipLaunchKernelGGL(k_per_sample, dim3(1), dim3(1024), 0, st, a);
+    return hip_ok(hipGetLastError(), "k_per_sample launch");
+}
+
+int shems_per_workspace_floats(int64_t capacity, int64_t *out)
+{
+    if (!out || capacity < 1 || capacity > kPerMaxSlots) return set_error(SHEMS_ERR_ARG, "shems_per_workspace_floats: capacity must be in 1..262144");
+    *out = per_ws_floats(capacity);
+    return SHEMS_OK;
+}
+
+int shems_per_sample_dev(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed,
+                         uint32_t tick, int32_t batch, void *stream)
+{
+    if (int rc = check_per(per, nullptr, capacity, ring_len, fresh_pos, fresh_count, batch, "shems_per_sample_dev")) return rc;
+    return per_sample_launch(per, capacity, ring_len, fresh_pos, fresh_count, seed, tick, batch, (hipStream_t)stream);
+}
+
+static int update_given_launch(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, const GivenLaunch &gv, const AdamScalars &sc,
+                               const AdamScalars &sa, void *stream)
+{
+    if (int rc = critic_side(d, ring, ring_len, 0, 0, 0, 0, 1, 0, &sc, stream, false, nullptr, &gv)) return rc;
+    return actor_side(d, 1, 0, &sa, stream);
+}
+
+int shems_ddpg_update_given(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, const int32_t *d_idx, const float *d_w,
+                            double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, void *stream)
+{
+    const char *fn = "shems_ddpg_update_given";
+    if (int rc = check_given(d, ring, ring_len, bp1_crit, bp2_crit, bp1_act, bp2_act, fn)) return rc;
+    if (!d_idx || !d_w || ((uintptr_t)d_idx & 3) != 0 || ((uintptr_t)d_w & 3) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: d_idx and d_w must be device arrays of 128 elements", fn);
+    const GivenLaunch gv{d_idx, PerHead{d_w, d_idx, nullptr, nullptr, ring_len, 0.0f, 0.0f}};
+    const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr}, sa{eta_act, bp1_act, bp2_act, 1.0, nullptr};
+    return update_given_launch(d, ring, ring_len, gv, sc, sa, stream);
+}
+
+int shems_ddpg_update_per(const shems_ddpg *d, const shems_replay *ring, const shems_per *per, int64_t ring_len, int64_t fresh_pos,
+                          int64_t fresh_count, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit,
+                          double eta_act, double bp1_act, double bp2_act, void *stream)
+{
+    const char *fn = "shems_ddpg_update_per";
+    if (int rc = check_given(d, ring, ring_len, bp1_crit, bp2_crit, bp1_act, bp2_act, fn)) return rc;
+    if (int rc = check_per(per, d, ring->capacity, ring_len, fresh_pos, fresh_count, d->batch, fn)) return rc;
+    if (int rc = per_sample_launch(per, ring->capacity, ring_len, fresh_pos, fresh_count, seed, tick, d->batch, (hipStream_t)stream)) return rc;
+    const int32_t *idx = reinterpret_cast<const int32_t *>(per->ws + PW_IDX);
+    const GivenLaunch gv{idx, PerHead{per->ws + PW_W, idx, per->prio, per->pmax, ring_len, per->alpha, per->eps_p}};
+    const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr}, sa{eta_act, bp1_act, bp2_act, 1.0, nullptr};
+    return update_given_launch(d, ring, ring_len, gv, sc, sa, stream);
 }
 
 int shems_td3_workspace_floats(int64_t *out)

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .parallel import GradSync, shard_envs  # noqa: F401
-from .replay import ReplayRing
+from .replay import PrioritizedRing, ReplayRing, _declare_per
 
 L1, L2, STATE, ACTION = 250, 500, 9, 2
 N_ACTOR, N_CRITIC = 129002, 129001
@@ -47,6 +47,15 @@ def eps_schedule(current_episode, mem_size=24000, ep_length=72, zeta=EPS_ZETA, x
     """sample_noise(en::EpsNoise) (DDPG.jl:69-72): xi = Float32(max(0.5 - zeta * (current_episode - MEM_SIZE / EP_LENGTH), xi_min)),
     evaluated in Float64 (0.5 and the quotient are Float64) and rounded once.  No upper clamp: episode 1 gives 0.666."""
     return float(np.float32(max(0.5 - zeta * (current_episode - mem_size / ep_length), xi_min)))
+
+
+def anneal_beta(beta0, update, total):
+    """The importance exponent's linear schedule (Schaul et al. 2016, 3.4): beta0 at update 0, 1.0 from update `total` on.  A host
+    function: the prioritized update reads beta on every call."""
+    beta0 = float(beta0)
+    if not 0.0 <= beta0 <= 1.0 or total < 1 or update < 0:
+        raise ValueError(f"anneal_beta: beta0 in [0, 1], total >= 1, update >= 0 (got {beta0!r}, {update!r}, {total!r})")
+    return min(1.0, beta0 + (1.0 - beta0) * (float(update) / float(total)))
 
 
 class DdpgArgs(C.Structure):           # shems_ddpg
@@ -717,8 +726,11 @@ class Agent:
 
     def replay(self, ring, tick=None, exclude=None, publish=None):
         """replay(; rng_rpl) (DDPG.jl:121-145): one DDPG update from `ring`.  exclude = (pos, count): ring slots another
-        stream is writing right now (pipelined mode); publish = tensor that also receives the updated actor."""
+        stream is writing right now (pipelined mode); publish = tensor that also receives the updated actor.  A
+        replay.PrioritizedRing takes the prioritized update (_replay_per)."""
         self._same_device(None, ring)
+        if isinstance(ring, PrioritizedRing):
+            return self._replay_per(ring, tick, exclude, publish)
         # the one-call form works on the tiled regions where the mode is on (the second copy `publish` is a Flux-order block: not from tiles)
         d = self._ddpg_args(raw=True) if publish is None and self._enter_tiled() else self._ddpg_args()
         st = self._stream()
@@ -772,6 +784,60 @@ class Agent:
         self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
         self.updates += 1
 
+    def _replay_per(self, ring, tick=None, exclude=None, publish=None):
+        """replay() on a prioritized ring (shems_ddpg_update_per: the sampler launch, then K1..K5 with the weighted critic head and
+        the priority write-back in K3; include/shems_hip.h states the definition).  The pushes since the ring's last update are its
+        fresh range; bp_critic, bp_actor and `updates` advance as in replay().  Everything the six launches do not cover is refused
+        by name, never run as the uniform update."""
+        if exclude is not None or publish is not None:
+            raise NotImplementedError("prioritized replay: the pipelined forms of replay() (exclude / publish) belong to shems_ddpg_update")
+        if self.batch > self.MAX_PASS_BATCH:
+            raise NotImplementedError(f"prioritized replay: BATCH_SIZE = {self.batch}; the sampler draws at most {self.MAX_PASS_BATCH} columns")
+        if self.wide or is_wide(self.hidden):
+            raise NotImplementedError(f"prioritized replay: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no weighted head")
+        if self.noise_type == "pn":
+            raise NotImplementedError("prioritized replay: parameter noise (noise_type = 'pn') adapts between getData and the updates of replay()")
+        if self.sync.world > 1:
+            raise NotImplementedError("prioritized replay: data-parallel replicas do not exchange priorities")
+        if self.tiled_mode:
+            raise NotImplementedError("prioritized replay: the tiled working layout (use_tiled)")
+        if getattr(self, "_before_param_write", None) is not None:
+            raise NotImplementedError("prioritized replay: a learner of a learner group keeps its own working layout")
+        if not self.fused:
+            raise NotImplementedError("prioritized replay: the split form of replay() (fused = False)")
+        L = _declare_per()
+        d = self._ddpg_args()
+        rs, ps = ring.struct(), ring.per_struct()
+        tick = self.updates if tick is None else tick
+        fresh_pos, fresh_count = ring.fresh_range()
+        _capi.check(L.shems_ddpg_update_per(C.byref(d), C.byref(rs), C.byref(ps), len(ring), fresh_pos, fresh_count, self.rng_seed,
+                                            int(tick) & 0xFFFFFFFF, self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act,
+                                            self.bp_actor[0], self.bp_actor[1], self._stream()))
+        ring.covered = ring.pushed
+        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
+        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
+        self.updates += 1
+
+    def replay_given(self, ring, idx, weights):
+        """replay() on slots and weights the caller supplies (shems_ddpg_update_given): idx int32 [128] (-1 in the pad columns) and
+        weights float32 [128], device tensors.  No sampler launch, no write-back; with idx = sample_indices(tick, len(ring)) and
+        weights of 1.0 it leaves replay()'s bits.  State advances as in replay()."""
+        if self.batch > self.MAX_PASS_BATCH or self.wide or is_wide(self.hidden) or self.noise_type == "pn" or self.sync.world > 1 or \
+                self.tiled_mode or getattr(self, "_before_param_write", None) is not None or not self.fused:
+            raise NotImplementedError("replay_given: one replica on the tuned kernels in Flux order, the one-call form, batch <= 128, no parameter noise")
+        t = self.torch
+        if idx.dtype != t.int32 or weights.dtype != t.float32 or idx.numel() != 128 or weights.numel() != 128:
+            raise ValueError("replay_given: idx int32 [128], weights float32 [128]")
+        self._same_device(None, ring)
+        d = self._ddpg_args()
+        rs = ring.struct()
+        _capi.check(_declare_per().shems_ddpg_update_given(C.byref(d), C.byref(rs), len(ring), idx.data_ptr(), weights.data_ptr(), self.eta_crit,
+                                                           self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
+                                                           self.bp_actor[1], self._stream()))
+        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
+        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
+        self.updates += 1
+
     def clone(self, demos, tick=None, tau=1.0, publish=None):
         """One SUPERVISED update of the actor on demonstrations (imitation.Demos, or any ring whose s and a hold (observation,
         action) pairs): loss = Flux.mse(actor(normalize(s)), a_demo) on a minibatch the ordinary sampler draws (sample_indices(tick,
@@ -780,6 +846,8 @@ class Agent:
         for bit (1 p + 0 t): a pre-trained actor starts DDPG with its target on itself.  The loss lands in losses[1].  bp_actor
         advances as in replay(); the step counts in `clones` (the default tick), `updates` does not move.  publish: a tensor that
         also receives the updated actor.  Networks up to (250, 500) (smaller ones through pad_net), batch <= 128, one replica."""
+        if isinstance(demos, PrioritizedRing):
+            raise NotImplementedError("clone: the supervised update draws uniformly; a PrioritizedRing has no cloning form")
         if self.wide or is_wide(self.hidden):
             raise NotImplementedError(f"clone: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no supervised update")
         if self.batch > self.MAX_PASS_BATCH:
@@ -807,6 +875,8 @@ class Agent:
         targets, and losses[0] is the calibration error of the critic on the minibatch.  bp_critic advances as in replay(); the step
         counts in `evaluations` (the default tick), `updates` and `clones` do not move.  tau: the soft update's, None = the agent's.
         It leaves the bits of _critic_grad_ex + _critic_apply.  Networks up to (250, 500), batch <= 128, one replica."""
+        if isinstance(ring, PrioritizedRing):
+            raise NotImplementedError("evaluate: the critic-only update draws uniformly; a PrioritizedRing has no critic-only form")
         if self.wide or is_wide(self.hidden):
             raise NotImplementedError(f"evaluate: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no critic-only update")
         if self.batch > self.MAX_PASS_BATCH:
@@ -902,16 +972,21 @@ class Agent:
         return returns
 
     def run_episodes(self, env_train, env_eval, ring, num_ep, test_every=100, test_runs=100, seed=None,
-                     updates_per_step=1, on_eval=None, on_best=None):
+                     updates_per_step=1, on_eval=None, on_best=None, anneal_beta_from=None):
         """run_episodes (DDPG.jl:244-298): train episodes, an evaluation sweep every `test_every` episodes
         (when i % test_every == 1) and a snapshot of the best-scoring actor.  Returns
-        (total_reward [num_ep], score_mean [ceil(num_ep/test_every)], best_run, best_actor)."""
+        (total_reward [num_ep], score_mean [ceil(num_ep/test_every)], best_run, best_actor).  anneal_beta_from: on a
+        replay.PrioritizedRing, beta of episode i is anneal_beta(anneal_beta_from, i - 1, num_ep - 1): linear, exactly 1.0 in the last episode."""
         seed = self.seed if seed is None else int(seed)
+        if anneal_beta_from is not None and not isinstance(ring, PrioritizedRing):
+            raise ValueError("anneal_beta_from needs a PrioritizedRing")
         total_reward = np.zeros(num_ep, np.float32)
         self.noise_mean = np.zeros(num_ep, np.float32)                              # noise_mean[i] (DDPG.jl:255), mean over the batch's envs
         score_mean = np.zeros(-(-num_ep // test_every), np.float64)
         best_score, best_run, best_actor = -100000.0, 0, None
         for i in range(1, num_ep + 1):
+            if anneal_beta_from is not None:
+                ring.beta = anneal_beta(anneal_beta_from, i - 1, max(1, num_ep - 1))
             ret = self.episode_(env_train, ring, train=True, rng_ep=seed, episode=i, updates_per_step=updates_per_step)
             total_reward[i - 1] = self.sync.mean_scalar(ret.mean().item(), env_train.n)
             self.noise_mean[i - 1] = self.sync.mean_scalar(self.last_noise.mean().item(), env_train.n)

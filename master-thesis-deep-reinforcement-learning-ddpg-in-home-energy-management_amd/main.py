@@ -22,6 +22,8 @@ Differences that follow from the platform, all explicit:
   * SHEMS_NUM_ENVS (default 1 = the reference's protocol) trains that many households at once;
   * SHEMS_ALGO=td3[:d[:sigma_trg[:clip_trg]]] trains a td3.TD3Agent (twin critics, target smoothing, the actor every d-th update;
     defaults 2, 0.2, 0.5) and appends _td3-d<d>-s<sigma>-c<clip> to <case>; unset or `ddpg`: today's bytes and file names;
+  * SHEMS_REPLAY=per[:alpha[:beta0]] trains from a replay.PrioritizedRing (proportional prioritized replay, beta annealed from beta0
+    to 1 over the run; defaults 0.6, 0.4) and appends _per-a<alpha>-b<beta0> to <case>; unset or `uniform`: today's bytes and names;
   * SHEMS_FORESIGHT=1 adds, after the tracking block, the perfect-foresight pass over the tracked data set (foresight.py):
     out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight"; with it,
     SHEMS_FORESIGHT_HORIZON (hours of forecast: one integer or a comma list) and SHEMS_FORESIGHT_CONTROL (hours between plans,
@@ -42,6 +44,7 @@ Differences that follow from the platform, all explicit:
 from __future__ import annotations
 
 import dataclasses
+import math
 import os
 import sys
 import time
@@ -199,6 +202,37 @@ def config_from_env(environ=os.environ):
         if v is not None:
             setattr(cfg, name, cast(v))
     return cfg
+
+
+def parse_replay(value):
+    """SHEMS_REPLAY -> ("uniform", None) when unset or "uniform": today's bytes and file names.  per[:alpha[:beta0]] -> ("per",
+    dict(alpha, beta0)): a replay.PrioritizedRing with beta annealed linearly from beta0 to 1 over the run (defaults 0.6, 0.4).
+    Anything else is refused by name."""
+    if value is None or value == "uniform":
+        return "uniform", None
+    parts = str(value).split(":")
+    if parts[0] != "per" or len(parts) > 3:
+        raise ValueError(f"SHEMS_REPLAY = {value!r} is not uniform or per[:alpha[:beta0]]")
+    out = dict(alpha=0.6, beta0=0.4)
+    try:
+        for key, raw in zip(("alpha", "beta0"), parts[1:]):
+            out[key] = float(raw)
+    except ValueError:
+        raise ValueError(f"SHEMS_REPLAY = {value!r}: alpha and beta0 are numbers") from None
+    if not (math.isfinite(out["alpha"]) and out["alpha"] >= 0.0):
+        raise ValueError(f"SHEMS_REPLAY = {value!r}: alpha must be finite and >= 0")
+    if not (math.isfinite(out["beta0"]) and 0.0 <= out["beta0"] <= 1.0):
+        raise ValueError(f"SHEMS_REPLAY = {value!r}: beta0 must be in [0, 1]")
+    return "per", out
+
+
+def replay_case_suffix(alpha, beta0):
+    """What the entry script appends to its `case` string for a prioritized run, behind the algorithm's own suffix."""
+    return f"_per-a{float(alpha):g}-b{float(beta0):g}"
+
+
+def replay_from_env(environ=os.environ):
+    return parse_replay(environ.get("SHEMS_REPLAY"))
 
 
 def algo_from_env(environ=os.environ):
@@ -366,11 +400,21 @@ def main(environ=os.environ, cwd=".", log=print):
             raise ValueError(f"SHEMS_ALGO=td3: the twin-critic update holds networks up to (250, 500), batches up to 128 and no parameter "
                              f"noise, not ({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE} with noise_type = {cfg.noise_type!r}")
         cfg.algo_suffix = T.case_suffix(**td3_hp)
+    replay_kind, per_hp = replay_from_env(environ)
+    if replay_kind == "per":
+        if algo == "td3":
+            raise NotImplementedError("SHEMS_REPLAY=per with SHEMS_ALGO=td3: the twin-critic update has no weighted head")
+        if cfg.L1 > 250 or cfg.L2 > 500 or cfg.BATCH_SIZE > 128 or cfg.noise_type == "pn":
+            raise ValueError(f"SHEMS_REPLAY=per: the prioritized update holds networks up to (250, 500), batches up to 128 and no parameter "
+                             f"noise, not ({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE} with noise_type = {cfg.noise_type!r}")
+        cfg.algo_suffix += replay_case_suffix(**per_hp)
     horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
     forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
     regret = foresight_regret(environ)
     imitate = foresight_imitate(environ)
     warmstart = foresight_warmstart(environ)
+    if imitate is not None and replay_kind == "per":
+        raise NotImplementedError("SHEMS_REPLAY=per with SHEMS_FORESIGHT_IMITATE: the supervised and critic-only updates draw uniformly")
     if imitate is not None and (cfg.L1 > 250 or cfg.L2 > 500 or cfg.BATCH_SIZE > 128):
         raise ValueError(f"SHEMS_FORESIGHT_IMITATE: the supervised update holds networks up to (250, 500) and batches up to 128, not "
                          f"({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE}")
@@ -410,7 +454,7 @@ def main(environ=os.environ, cwd=".", log=print):
                         theta=cfg.theta, hidden=(cfg.L1, cfg.L2))
     agent.gamma, agent.tau, agent.batch = float(np.float32(cfg.gamma)), float(np.float32(cfg.tau)), cfg.BATCH_SIZE
     agent.eta_act, agent.eta_crit = float(np.float32(cfg.eta_act)), float(np.float32(cfg.eta_crit))
-    ring = D.ReplayRing(cfg.MEM_SIZE)
+    ring = D.PrioritizedRing(cfg.MEM_SIZE, alpha=per_hp["alpha"], beta=per_hp["beta0"]) if replay_kind == "per" else D.ReplayRing(cfg.MEM_SIZE)
     ck = dict(ep_len=EP_LENGTH["train"], num_ep=cfg.NUM_EP, l1=cfg.L1, l2=cfg.L2, case=cfg.case)
 
     # ---- Memory Buffer (MAIN:27-30) ----
@@ -427,7 +471,8 @@ def main(environ=os.environ, cwd=".", log=print):
             checkpoint.save(actor, total_reward, score_mean, i, agent.noise_mean, idx=i, rng=cfg.rng_run, path="temp", **ck)
 
         total_reward, score_mean, best_eval, _ = agent.run_episodes(env_train, env_eval, ring, cfg.NUM_EP, test_every=cfg.test_every,
-                                                                    test_runs=cfg.test_runs, seed=cfg.rng_run, on_best=on_best)
+                                                                    test_runs=cfg.test_runs, seed=cfg.rng_run, on_best=on_best,
+                                                                    **(dict(anneal_beta_from=per_hp["beta0"]) if replay_kind == "per" else {}))
         noise_mean = agent.noise_mean
         checkpoint.save(agent.export_actor(), total_reward, score_mean, best_eval, noise_mean, idx=cfg.NUM_EP, rng=cfg.rng_run, **ck)   # MAIN:45-46
         log(f"trained {cfg.NUM_EP} episodes in {time.time() - t0:.1f} s; best evaluation at episode {best_eval}")

@@ -383,9 +383,14 @@ class TD3Agent(D.Agent):
         return Td3Args(self._ddpg_args(), p(self.critic2), p(self.critic2_t), p(self.m_critic2), p(self.v_critic2), p(self.grad_critic2),
                        p(self.ws2), p(self.losses2), self.sigma_trg, self.clip_trg)
 
+    def replay_given(self, ring, idx, weights):
+        raise NotImplementedError("TD3: replay_given is the single-critic update (shems_ddpg_update_given); the twin critics have none")
+
     def replay(self, ring, tick=None, exclude=None, publish=None, update_policy=None):
         """One TD3 update from `ring` (shems_td3_update).  update_policy: None = the schedule, is_policy_step(self.updates,
         self.policy_delay).  bp_critic advances on every update, bp_actor on policy steps; `updates` counts updates."""
+        if isinstance(ring, D.PrioritizedRing):
+            raise NotImplementedError("TD3: the twin-critic update has no weighted head; a PrioritizedRing belongs to ddpg.Agent")
         if exclude is not None or publish is not None:
             raise NotImplementedError("TD3: the pipelined forms of replay() (exclude / publish) belong to shems_ddpg_update")
         if self.batch > self.MAX_PASS_BATCH:
