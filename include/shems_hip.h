@@ -732,6 +732,41 @@ int shems_td3_group_update_tp(const shems_td3 *t0, const shems_replay *ring0, co
                               float *w2t_critic2, const shems_group_hparams *d_hp, const shems_group_hparams *d_hp_hold, int64_t ring_len,
                               uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act,
                               double bp1_act, double bp2_act, int update_policy, int32_t flags, void *stream);
+/* Prioritized replay for every learner of a group, throughput form: shems_ddpg_update_per's seven steps per learner l,
+ * with the group's conventions.  Learner l's Philox key is seed + l on the stream tag 0x50455253 (what shems_ddpg_group_update_tp's
+ * sampler does on its own tag); with records the first batch_l columns are live, t_m = (m + u_m) (T_l / batch_l), and the weight
+ * maximum runs over learner l's live columns.  ring_len, fresh_pos and fresh_count are the group's (the rings advance in lockstep);
+ * alpha, beta and eps_p are per0's, shared; beta is read on every call.  prio [capacity], pmax [1] (1.0 at the start) and the sampler
+ * workspace (shems_per_workspace_floats(capacity) floats) are per learner: per0 names learner 0's, learner l's lie at
+ * + l * g->stride_bytes.  Step 5 is shems_ddpg_group_update_tp's critic head with dq = 2 w diff / batch and losses[0] =
+ * sum (w diff) diff / batch in that head's summation order: weights of 1.0 leave its bits.  Step 6 (pi <- (|diff| + eps_p)^alpha, the
+ * highest column wins a slot drawn twice, pmax only ever raised) is done by each learner's publishing workgroup of the critic's D1
+ * launch.  Nine launches: the sampler (one workgroup of 1024 threads per learner), then shems_ddpg_group_update_tp's eight with the
+ * sampler role reading the published slots and the critic's D1 launch carrying the weighted head; narrow shapes below 48 learners.
+ *   flags: SHEMS_TP_STORE_GRAD as above.  SHEMS_TP_PER_GIVEN: no sampler launch and no write-back -- the caller has filled every
+ *          learner's slots (workspace floats 4..131 as int32, -1 in the pad columns) and weights (floats 132..259); prio and pmax keep
+ *          their bytes.  With the slots of shems_ddpg_sample_indices(seed + l, tick) and weights of 1.0 the update leaves
+ *          shems_ddpg_group_update_tp's bits.
+ * SHEMS_ERR_ARG, nothing launched: whatever shems_ddpg_group_update_tp refuses; whatever shems_ddpg_update_per refuses for the
+ * prioritized ring's own arguments (with records the batches are the records'); a per0 block that is NULL or misaligned, overlaps
+ * one of learner 0's DDPG blocks, its workspace, its tiled regions or its ring, or (more than one learner) ends beyond one stride
+ * of the lowest of those blocks; unknown flag bits.  SHEMS_ERR_STATE: a learner between shems_ddpg_tiled_enter and
+ * shems_ddpg_tiled_leave.
+ * After an update learner l's workspace holds y [128] and q [128] at float SHEMS_TP_PER_PUB (columns >= batch_l are padding): the new
+ * priorities are formed from diff = q - y. */
+enum { SHEMS_TP_PER_GIVEN = 2 };
+#define SHEMS_TP_PER_PUB 165000
+int shems_ddpg_group_update_per_tp(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *t,
+                                   const shems_group_hparams *d_hp, const shems_per *per0, int64_t ring_len, int64_t fresh_pos,
+                                   int64_t fresh_count, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit,
+                                   double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream);
+/* The sampler launch alone (steps 1-4 for every learner; tests, a Julia caller).  d_hp: NULL = `batch` live columns for every
+ * learner, else learner l's batch from d_hp[l] (`batch` is ignored).  SHEMS_ERR_ARG as above for g, d_hp and per0; this call is not
+ * told where a slab begins, so it holds the three blocks to one stride of the lowest of THEM only: that they lie inside the learner's
+ * slab is the caller's to see to. */
+int shems_per_group_sample_dev(const shems_per *per0, const shems_group *g, const shems_group_hparams *d_hp, int64_t capacity,
+                               int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed, uint32_t tick,
+                               int32_t batch, void *stream);
 /* shems_wide_group_update in the same way (input.jl:64, 140; DDPG.jl:121-145). */
 int shems_wide_group_update_x(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int32_t l1, int32_t l2,
                               const shems_group_hparams *d_hp, const shems_group_xparams *d_xp, const int64_t *d_pushed, int32_t max_batch,

@@ -123,6 +123,33 @@ def declare_per():
     return L
 
 
+TP_STORE_GRAD, TP_PER_GIVEN = 1, 2     # flags of the grouped throughput updates (SHEMS_TP_*)
+
+
+def _group_per_sigs():
+    """Prioritized replay for learner groups (shems_ddpg *, shems_group *, shems_group_w2t * and the record array go as void pointers:
+    their mirrors live in ddpg.py / group.py)."""
+    vp, i64, i32, u64, u32, dbl = C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32, C.c_double
+    PP, PR_ = C.POINTER(PerArgs), C.POINTER(Replay)
+    return {
+        "shems_ddpg_group_update_per_tp": [vp, PR_, vp, vp, vp, PP, i64, i64, i64, u64, u32, dbl, dbl, dbl, dbl, dbl, dbl, i32, vp],
+        "shems_per_group_sample_dev": [PP, vp, vp, i64, i64, i64, i64, u64, u32, i32, vp],
+    }
+
+
+def declare_group_per():
+    """The prototypes of _group_per_sigs (compared with include/shems_hip.h by tests/test_group_per_host.py)."""
+    L = declare_per()
+    if getattr(L, "_group_per_declared", False):
+        return L
+    for name, args in _group_per_sigs().items():
+        fn = getattr(L, name)
+        fn.argtypes = args
+        fn.restype = C.c_int
+    L._group_per_declared = True
+    return L
+
+
 def exported_symbols():
     """Names include/shems_hip.h declares (used by the CPU-side ABI test)."""
     import re

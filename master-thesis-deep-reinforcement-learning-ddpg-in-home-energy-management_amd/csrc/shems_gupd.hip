@@ -49,6 +49,7 @@
 #include "philox.h"
 #include "shems_adam.h"
 #include "shems_internal.h"
+#include "shems_per_core.h"
 #include "shems_td3_core.h"
 
 namespace shems {
@@ -171,9 +172,11 @@ __device__ __forceinline__ void gshift(shems_replay &r, int64_t off)
 // grid (5, learners): workgroup 0 samples / gathers / normalises and freezes the output layers, workgroups 1..4 pack one network's
 // frozen layer-1 image each (one launch of 2 000 short workgroups instead of 400 long ones: 49 -> ~10 us at 400 learners)
 // XP (shems_ddpg_group_update_tp_x): learner l's ring length is min(pushed[l], xp[l].mem_size) in place of A.ring_len
-template <bool HP, bool XP = false>
+// PER (shems_ddpg_group_update_per_tp): column m's slot is the one published in learner l's sampler workspace (pws: learner 0's, PW_IDX;
+// -1 in the pad columns, which gather slot 0 and store zeros / -1 as ever) in place of the Philox draw
+template <bool HP, bool XP = false, bool PER = false>
 __device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, const int l, const shems_group_hparams *hp,
-                                          const shems_group_xparams *xp = nullptr, const int64_t *pushed = nullptr)
+                                          const shems_group_xparams *xp = nullptr, const int64_t *pushed = nullptr, const float *pws = nullptr)
 {
     const int tid = threadIdx.x;
     const int64_t off = (int64_t)l * A.gstride;
@@ -206,9 +209,14 @@ __device__ __forceinline__ void prep_body(const PrepArgs &A, const int role, con
         ring_len = min(max(min(pushed[l], (int64_t)xp[l].mem_size), (int64_t)1), ring.capacity);
     if (tid < BP) {
         const int m = tid;
-        const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)seed, (uint32_t)(seed >> 32));
-        const uint32_t w = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
-        const int64_t j = (int64_t)(w % (uint32_t)ring_len);
+        int64_t j;
+        if constexpr (PER) {                     // clamped into the filled slots whatever the workspace holds
+            j = min(max((int64_t)reinterpret_cast<const int32_t *>(gsh(pws, off) + PW_IDX)[m], (int64_t)0), ring_len - 1);
+        } else {
+            const u32x4 x = philox4x32_10((uint32_t)(m >> 2), 0u, A.tick, kStreamSample, (uint32_t)seed, (uint32_t)(seed >> 32));
+            const uint32_t w = (m & 3) == 0 ? x.x : (m & 3) == 1 ? x.y : (m & 3) == 2 ? x.z : x.w;
+            j = (int64_t)(w % (uint32_t)ring_len);
+        }
         const bool live = m < d.batch;
         float sv[SIN], s2v[SIN], lo[SIN], hi[SIN];
 #pragma unroll
@@ -705,6 +713,88 @@ __device__ __forceinline__ void head_twin(const NetArgs &A, const shems_ddpg &d,
     }
 }
 
+// The weighted head of prioritized replay (shems_ddpg_group_update_per_tp, k_tp_d1_per; shems_per_core.h steps 5 and 6): head_critic with
+// dq = 2 w diff / B and losses[0] = sum (w diff) diff / B in head_critic's summation orders, the importance weights w [BP] read by every
+// workgroup of the learner from its sampler workspace (PW_W; 0 in the pad columns).  Weights of 1.0 leave head_critic's bits: y is
+// head_critic's rounded product and add (pinned, as td3_y_rounded), 2 * 1 * diff and (1 * diff) * diff are head_critic's operands.
+// The publishing workgroup also writes the drawn slots' new priorities back when X.prio is set: pi = (|diff| + eps_p)^alpha, ONE writer
+// per slot -- the highest live column that drew it, decided over the 128 slots in LDS (scr: the weight ring, not yet filled) -- and
+// pmax = max(pmax, every new pi).  Slots are clamped into [0, ring_len) before they index anything.  It also publishes y and q [2][BP]
+// at ws + TP_PERQ (diff = q - y is what the priorities are formed from).
+constexpr int64_t TP_PERQ = TP_FLOATS;            // [2][BP] y, q of the weighted head (behind the carve above: no other launch touches it)
+static_assert(TP_PERQ == SHEMS_TP_PER_PUB && TP_PERQ % 4 == 0 && TP_PERQ + 2 * BP <= kTpWsFloats, "shems_hip.h names where y and q are published");
+struct PerX {
+    const float *pw;                   // learner 0's sampler workspace (PW_IDX, PW_W)
+    float *prio, *pmax;                // learner 0's write-back targets, or null: no write-back (SHEMS_TP_PER_GIVEN)
+    int64_t ring_len;
+    float alpha, eps_p;
+};
+__device__ __forceinline__ float per_y_rounded(float r, float gamma, float done, float q2)
+{
+#pragma clang fp contract(off)
+    return r + gamma * (1.0f - done) * q2;
+}
+__device__ __forceinline__ void head_critic_per(const NetArgs &A, const shems_ddpg &d, const AdamCtx &c, float *d3s, float *red, bool publisher,
+                                                const PerX &X, const int64_t off, float *scr /*LDS, >= BP + 2 words*/)
+{
+    float *ws = d.ws;
+    const float *pw = gsh(X.pw, off);
+    const int t = threadIdx.x, m = t & 127;
+    float dq = 0.0f, diff = 0.0f, wm = 0.0f;
+    if (t < BP) {
+        const float *Pt = p3_of(ws, NET_CRITIC_T), *Pc = p3_of(ws, NET_CRITIC);
+        float q2 = ws[TP_FB3 + 1], q = ws[TP_FB3 + 0];
+        wm = pw[PW_W + m];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) { q2 += Pt[(i * 2) * BP + m]; q += Pc[(i * 2) * BP + m]; }
+        const float y = per_y_rounded(ws[TP_R + m], d.gamma, ws[TP_DONE + m], q2);           // DDPG.jl:133
+        diff = m < d.batch ? q - y : 0.0f;
+        dq = 2.0f * wm * diff / (float)d.batch;                                             // d (sum w diff^2 / B) / d q
+        if (publisher) { ws[TP_PERQ + m] = y; ws[TP_PERQ + BP + m] = q; }
+    }
+    d3s[t] = t < BP ? dq : 0.0f;
+    if (publisher) {
+        d.ws[TP_D3C + t] = t < BP ? dq : 0.0f;
+        const bool wb = X.prio != nullptr, live = t < BP && m < d.batch;               // (wb: the same for every thread of the launch)
+        float *prio = gsh(X.prio, off), *pmax = gsh(X.pmax, off);
+        int32_t *sj = reinterpret_cast<int32_t *>(scr);
+        int32_t j = 0;
+        float pnew = 0.0f, pm0 = 0.0f;
+        if (wb) {
+            if (t < BP) j = (int32_t)min(max((int64_t)reinterpret_cast<const int32_t *>(pw + PW_IDX)[m], (int64_t)0), X.ring_len - 1);
+            if (t == 0) pm0 = pmax[0];
+            if (live) pnew = per_priority(diff, X.eps_p, X.alpha);
+            if (t < BP) sj[t] = live ? j : -1;
+            float pm = pnew;                                                                // >= 0; threads outside the batch hold 0
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) pm = fmaxf(pm, __shfl_xor(pm, o, 64));
+            if ((t & 63) == 0 && t < BP) scr[BP + (t >> 6)] = pm;
+        }
+        const float wd = wm * diff;                                                         // (w diff) diff: head_critic's product shape
+        const float s1 = wave_sum64(wd * diff), s2 = wave_sum64(dq);
+        if ((t & 63) == 0) { red[t >> 6] = s1; red[4 + (t >> 6)] = s2; }
+        __syncthreads();
+        if (t == 0) {
+            d.losses[0] = (red[0] + red[1]) / (float)d.batch;
+            adam_at(c, off_b3(CIN, 1), red[4] + red[5], A.store_grad != 0);
+            if (wb) pmax[0] = fmaxf(pm0, fmaxf(scr[BP], scr[BP + 1]));                      // only ever raised
+        }
+        if (wb) {
+            if (live) {
+                bool last = true;
+                const int4 *sj4 = reinterpret_cast<const int4 *>(sj);
+#pragma unroll
+                for (int q = 0; q < BP / 4; ++q) {
+                    const int4 v = sj4[q];
+                    last = last && !((4 * q + 0 > t && v.x == j) || (4 * q + 1 > t && v.y == j) || (4 * q + 2 > t && v.z == j) || (4 * q + 3 > t && v.w == j));
+                }
+                if (last) prio[j] = pnew;
+            }
+            __syncthreads();                     // scr is the weight ring: the caller fills it next
+        }
+    }
+}
+
 // ================================================================================================================================
 // P3 / P6: D1' [m][k] = mask1 .* sum_n D2[n][m] W2[k][n] for one 64-wide k-tile and the whole batch, D2[n][m] = (sum_o W3[n][o]
 // d3[o][m]) (h2[n][m] > 0) generated from relu(layer 2) as it is loaded -- straight into MFMA operand layout, no LDS; the weights
@@ -723,10 +813,10 @@ constexpr int d1_ring(int KT) { return 2 * 32 * KT * D1_S > 4 * KT * 8 * 64 ? 2 
 constexpr int d1_lds(int KT) { return (d1_ring(KT) + 1024 + 2 * BP + 8 + W1K * BP + W1K * 32 * KT) * 4; }
 
 // CLONE: the supervised update's instantiation (k_tp_d1_clone) takes the cloning head at compile time; TWIN: TD3's (k_tp_d1_twin) the twin
-// head; otherwise NetArgs.head decides.
-template <int IN, int KT, bool TL, bool HP, bool CLONE = false, bool TWIN = false>
+// head, PER: prioritized replay's (k_tp_d1_per) the weighted head; otherwise NetArgs.head decides.
+template <int IN, int KT, bool TL, bool HP, bool CLONE = false, bool TWIN = false, bool PER = false>
 __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const int by, float *smem, const shems_group_hparams *hp,
-                                        const TwinX *tx = nullptr)
+                                        const TwinX *tx = nullptr, const PerX *px = nullptr)
 {
     typedef NetOf<IN> N;
     constexpr int OUT = N::OUT;
@@ -749,7 +839,7 @@ __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const in
         hp_adam(c, h, N::critic);
         // (the quotient is formed on the vector ALU and lives to the kernel's end: left in vector registers it is the one value the narrow
         // Flux-order form spills, 12 bytes of scratch in k_tp_d1_hp<SIN, 1, false>; the new instantiations keep it in scalar registers)
-        if constexpr (CLONE || TWIN) c.k1 = uniform_f64(c.k1);
+        if constexpr (CLONE || TWIN || PER) c.k1 = uniform_f64(c.k1);
     }
     float *ws = d.ws;
     const float *__restrict__ P = c.p;
@@ -800,6 +890,7 @@ __device__ __forceinline__ void d1_body(const NetArgs &A, const int bx, const in
     for (int s = 0; s < WLN; ++s) { const int e = min(s * 256 + tid, W1K * KW - 1); wlv[s] = w1i[(e / KW) * W1C + k0 + e % KW]; }
     if constexpr (CLONE) head_clone(A, d, c, d3s, red, kt == 0);
     else if constexpr (TWIN) head_twin(A, d, c, d3s, red, kt == 0, *tx, off);
+    else if constexpr (PER) head_critic_per(A, d, c, d3s, red, kt == 0, *px, off, ring);
     else if (A.head == 1) head_critic(A, d, c, d3s, red, kt == 0); else head_actor(A, d, c, d3s, red, kt == 0);
     reinterpret_cast<f32x4 *>(w3s)[tid] = w3v;
 #pragma unroll
@@ -1121,14 +1212,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTL == 4 ? 
 // profiles/r06_fwd_persistent_ab.txt.)
 // A learner's k-tile workgroups (T = 8 / KT of them) read the same 256 KB of relu(layer 2): they are placed on ONE XCD (workgroup id
 // mod 8 picks the XCD and its L2), consecutive in its dispatch order -- learner = 8 (q / T) + xcd, k-tile = q mod T with q = id / 8.
-template <int IN, int KT, bool TL, bool HP, bool CLONE = false, bool TWIN = false>
-__device__ __forceinline__ void d1_entry(const NetArgs &A, float *smem, const shems_group_hparams *hp, const TwinX *tx = nullptr)
+template <int IN, int KT, bool TL, bool HP, bool CLONE = false, bool TWIN = false, bool PER = false>
+__device__ __forceinline__ void d1_entry(const NetArgs &A, float *smem, const shems_group_hparams *hp, const TwinX *tx = nullptr,
+                                         const PerX *px = nullptr)
 {
     constexpr unsigned T = 8 / KT;
     const unsigned id = blockIdx.x, xcd = id & 7u, q = id >> 3;
     const unsigned learner = 8u * (q / T) + xcd;
     if (learner >= (unsigned)A.learners) return;
-    d1_body<IN, KT, TL, HP, CLONE, TWIN>(A, (int)(q % T), (int)learner, smem, hp, tx);
+    d1_body<IN, KT, TL, HP, CLONE, TWIN, PER>(A, (int)(q % T), (int)learner, smem, hp, tx, px);
 }
 template <int IN, int KT, bool TL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1(NetArgs A)
@@ -1347,6 +1439,131 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     d1_entry<CIN, KT, TL, true, false, true>(A.n, smem, hp, &A.x);
+}
+
+// ================================================================================================================================
+// Prioritized replay for groups (shems_ddpg_group_update_per_tp; include/shems_hip.h): every learner draws its minibatch
+// by priority (shems_per_core.h, steps 1-4 per learner with the Philox key seed + l on kStreamPer), the critic's head is weighted and
+// the drawn slots' priorities are written back.  prio [capacity], pmax [1] and the sampler workspace per_ws lie in every learner's slab
+// (learner l's at learner 0's + l * gstride).  Nine launches:
+//   S  k_tp_per_sample    grid (learners), 1024 threads: steps 1-4 on learner l's arrays -- the arithmetic and summation orders of
+//                         k_per_sample (shems_ddpg.hip), whose body this repeats (that kernel keeps its code: its chunk sums are DPP adds,
+//                         these the xor butterfly of wave_sum64, the same balanced tree and so the same bits); batch_l from the record
+//   P0 k_tp_prep_per      prep_body<.., PER>: role 0 gathers the published slots
+//   P1, P2                unchanged
+//   P3 k_tp_d1_per        d1_body<.., PER>: the weighted head; the publishing workgroup (kt == 0) writes the priorities back
+//   P4 .. P7              unchanged (P4 reads the weighted dq P3 published)
+// SHEMS_TP_PER_GIVEN: no S and no write-back (X.prio null); the caller has filled every learner's PW_IDX / PW_W.
+// ================================================================================================================================
+struct PerGroupSampleArgs {
+    float *prio; const float *pmax; float *ws;       // learner 0's
+    int64_t gstride, capacity, ring_len, fresh_pos, fresh_count;
+    uint64_t seed; uint32_t tick; int batch; float beta;
+};
+template <bool HP>
+__device__ __forceinline__ void per_sample_body(const PerGroupSampleArgs &A, const int l, const shems_group_hparams *hp)
+{
+    __shared__ float sc[kPerMaxSlots / kPerChunk];          // chunk sums
+    __shared__ float sS[kPerMaxSlots / kPerBlock], sC[kPerMaxSlots / kPerBlock];
+    __shared__ float sraw[kPerCols];
+    __shared__ int slast;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t off = (int64_t)l * A.gstride;
+    float *gprio = gsh(A.prio, off);
+    float *gws = gsh(A.ws, off);
+    const uint64_t seed = A.seed + (uint64_t)l;             // learner l: Philox key seed + l (prep_body's convention)
+    int batch = A.batch;
+    if constexpr (HP) batch = hp_batch(hp[l]);
+    const int nb = (int)per_blocks(A.ring_len);
+    const float pmax = gsh(A.pmax, off)[0];
+    // steps 1 + 2a: fresh slots take pmax (stored, and used from the register); every chunk's tree sum
+    for (int b0 = 0; b0 < nb; b0 += 32) {                  // eight chunks per wave and round
+        float x[8];
+        int64_t jj[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            jj[i] = ((int64_t)(b0 + (wave >> 2) + 4 * i) * 4 + (wave & 3)) * kPerChunk + lane;
+            x[i] = gprio[min(jj[i], A.ring_len - 1)];                                        // clamped, consumed under the bound below
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool in = jj[i] < A.ring_len;
+            if (in && per_fresh(jj[i], A.fresh_pos, A.fresh_count, A.capacity)) { x[i] = pmax; gprio[jj[i]] = pmax; }
+            const float s = wave_sum64(in ? x[i] : 0.0f);
+            const int c = (b0 + (wave >> 2) + 4 * i) * 4 + (wave & 3);
+            if (lane == 0 && c < 4 * nb) sc[c] = s;
+        }
+    }
+    __syncthreads();
+    // step 2b: block sums, then the running sums in block order (one thread)
+    for (int b = tid; b < nb; b += 1024) sS[b] = per_block_sum(sc[4 * b], sc[4 * b + 1], sc[4 * b + 2], sc[4 * b + 3]);
+    __syncthreads();
+    if (tid == 0) {
+        float run = 0.0f;
+        int lastpos = 0;
+#pragma unroll 16
+        for (int b = 0; b < nb; ++b) {
+            const float s = sS[b];
+            run = b == 0 ? s : run + s;
+            sC[b] = run;
+            lastpos = s > 0.0f ? b : lastpos;
+        }
+        slast = lastpos;
+    }
+    __syncthreads();
+    for (int b = tid; b < nb; b += 1024) { gws[PW_S + b] = sS[b]; gws[PW_S + nb + b] = sC[b]; }
+    const float T = sC[nb - 1];
+    // steps 3 + 4: one column per thread
+    float raw = 0.0f;
+    int64_t j = 0;
+    float u = 0.0f, tm = 0.0f;
+    if (tid < kPerCols) {
+        u = per_u(seed, A.tick, tid);
+        tm = per_target(tid, u, T, batch);
+        int lo = 0, hi = nb;                                        // first b with C_b > t (C never decreases): bisection
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (sC[mid] > tm) hi = mid; else lo = mid + 1; }
+        const int b = lo < nb ? lo : slast;
+        const float *prio = gprio;
+        const int cap = (int)A.capacity, fp = (int)A.fresh_pos, fc = (int)min(A.fresh_count, A.capacity);      // (all <= kPerMaxSlots)
+        auto at = [=](int q) { const float v = prio[q]; return per_fresh32(q, fp, fc, cap) ? pmax : v; };
+        j = per_search_block(b, b > 0 ? sC[b - 1] : 0.0f, tm, (int)A.ring_len, at);
+        raw = per_raw_weight(A.ring_len, at((int)j), T, A.beta);
+        sraw[tid] = tid < batch ? raw : 0.0f;
+    }
+    __syncthreads();
+    if (tid < kPerCols) {
+        float mx = 0.0f;
+        for (int m = 0; m < kPerCols; ++m) mx = fmaxf(mx, sraw[m]);
+        const bool live = tid < batch;
+        reinterpret_cast<int32_t *>(gws + PW_IDX)[tid] = live ? (int32_t)j : -1;
+        gws[PW_W + tid] = live ? raw / mx : 0.0f;
+        gws[PW_U + tid] = u;
+        gws[PW_TM + tid] = tm;
+        if (tid == 0) { gws[PW_T] = T; gws[PW_T + 1] = mx; reinterpret_cast<int32_t *>(gws + PW_T)[2] = nb; gws[PW_T + 3] = 0.0f; }
+    }
+}
+__global__ __launch_bounds__(1024) void k_tp_per_sample(PerGroupSampleArgs A) { per_sample_body<false>(A, blockIdx.x, nullptr); }
+__global__ __launch_bounds__(1024) void k_tp_per_sample_hp(PerGroupSampleArgs A, const shems_group_hparams *hp) { per_sample_body<true>(A, blockIdx.x, hp); }
+
+struct PrepPerArgs { PrepArgs p; const float *pw; };
+__global__ __launch_bounds__(256) void k_tp_prep_per(PrepPerArgs R) { prep_body<false, false, true>(R.p, blockIdx.x, blockIdx.y, nullptr, nullptr, nullptr, R.pw); }
+__global__ __launch_bounds__(256) void k_tp_prep_per_hp(PrepPerArgs R, const shems_group_hparams *hp)
+{
+    prep_body<true, false, true>(R.p, blockIdx.x, blockIdx.y, hp, nullptr, nullptr, R.pw);
+}
+// P3 with the weighted head: the twins of k_tp_d1<CIN, ..> / k_tp_d1_hp<CIN, ..>
+struct PerD1Args { NetArgs n; PerX x; };
+template <int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1_per(PerD1Args A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<CIN, KT, TL, false, false, false, true>(A.n, smem, nullptr, nullptr, &A.x);
+}
+template <int KT, bool TL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_tp_d1_per_hp(PerD1Args A, const shems_group_hparams *hp)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    d1_entry<CIN, KT, TL, true, false, false, true>(A.n, smem, hp, nullptr, &A.x);
 }
 
 // (Round 5 also built two ways of running the HBM-bound phases (P4, P7) under the MFMA-bound ones (P1, P2, P5) of OTHER learners: cohorts
@@ -1819,6 +2036,180 @@ extern "C" int shems_td3_group_update_tp(const shems_td3 *t0, const shems_replay
                      : (d_hp ? td3_group_update_tp<false, true> : td3_group_update_tp<false, false>);
     return update(t0, ring0, g, w, w2t_critic2, d_hp, d_hp_hold, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
                   update_policy, flags, stream);
+}
+
+// ---- prioritized replay for groups: S, P0 (k_tp_prep_per), P1, P2, P3 (k_tp_d1_per), P4 .. P7 -----------------------------------------
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+// What shems_ddpg_update_per refuses for the prioritized ring's own arguments (check_per of shems_ddpg.hip, repeated here so that
+// that file keeps its text), for learner 0's shems_per.  batch <= 0: the batches are per-learner records on the device (not looked at).
+static int check_per_group(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, int32_t batch,
+                           const char *fn)
+{
+    if (!per || !per->prio || !per->pmax || !per->ws) return set_error(SHEMS_ERR_ARG, "%s: shems_per has a NULL buffer", fn);
+    if (capacity < 1 || capacity > kPerMaxSlots)
+        return set_error(SHEMS_ERR_ARG, "%s: a prioritized ring holds 1..%lld slots (got %lld)", fn, (long long)kPerMaxSlots, (long long)capacity);
+    if (ring_len < 1 || ring_len > capacity) return set_error(SHEMS_ERR_ARG, "%s: ring_len must be in 1..capacity", fn);
+    if (batch > kPerCols || batch == 0) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, batch);
+    if (((uintptr_t)per->prio & 15) != 0 || ((uintptr_t)per->ws & 15) != 0 || ((uintptr_t)per->pmax & 3) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: prio and the workspace must be 16-byte aligned, pmax 4-byte aligned", fn);
+    const size_t np = (size_t)capacity * 4, nw = (size_t)per_ws_floats(capacity) * 4;
+    if (ranges_overlap(per->prio, np, per->ws, nw) || ranges_overlap(per->prio, np, per->pmax, 4) || ranges_overlap(per->ws, nw, per->pmax, 4))
+        return set_error(SHEMS_ERR_ARG, "%s: prio, pmax and the workspace overlap", fn);
+    for (const float v : {per->alpha, per->beta, per->eps_p})
+        if (!(v >= 0.0f) || !std::isfinite(v)) return set_error(SHEMS_ERR_ARG, "%s: alpha, beta and eps_p must be finite and >= 0", fn);
+    if (per->beta > 1.0f) return set_error(SHEMS_ERR_ARG, "%s: beta must be in [0, 1] (got %g)", fn, (double)per->beta);
+    if (fresh_pos < 0 || fresh_pos >= capacity || fresh_count < 0)
+        return set_error(SHEMS_ERR_ARG, "%s: the fresh range must start inside the ring and have a count >= 0", fn);
+    if (fresh_count > 0 && fresh_count < capacity && ring_len < capacity && fresh_pos + fresh_count > ring_len)
+        return set_error(SHEMS_ERR_ARG, "%s: the fresh range [%lld, +%lld) leaves the %lld filled slots", fn, (long long)fresh_pos,
+                         (long long)fresh_count, (long long)ring_len);
+    return SHEMS_OK;
+}
+// The three blocks of learner 0's shems_per against the slab: with more than one learner they must end inside one stride of the lowest
+// of `blocks` and of themselves (learner l's copy would otherwise reach into learner l + 1's slab), and overlap none of `blocks`.
+struct SlabBlock { const void *p; size_t bytes; };
+static int check_per_slab(const shems_per *per, int64_t capacity, const shems_group *g, const SlabBlock *blocks, int nblocks, const char *fn)
+{
+    const SlabBlock pb[3] = {{per->prio, (size_t)capacity * 4}, {per->pmax, 4}, {per->ws, (size_t)per_ws_floats(capacity) * 4}};
+    uintptr_t lo = (uintptr_t)per->prio;
+    for (const SlabBlock &b : pb) lo = (uintptr_t)b.p < lo ? (uintptr_t)b.p : lo;
+    for (int i = 0; i < nblocks; ++i)
+        if (blocks[i].p && (uintptr_t)blocks[i].p < lo) lo = (uintptr_t)blocks[i].p;
+    for (const SlabBlock &b : pb) {
+        for (int i = 0; i < nblocks; ++i)
+            if (blocks[i].p && ranges_overlap(b.p, b.bytes, blocks[i].p, blocks[i].bytes))
+                return set_error(SHEMS_ERR_ARG, "%s: the prioritized ring's arrays overlap a block of the learner (DDPG blocks, workspace or ring)", fn);
+        if (g->count > 1 && (uintptr_t)b.p + b.bytes > lo + (uintptr_t)g->stride_bytes)
+            return set_error(SHEMS_ERR_ARG, "%s: the prioritized ring's arrays run past the slab stride of %lld bytes", fn, (long long)g->stride_bytes);
+    }
+    return SHEMS_OK;
+}
+static int per_group_sample_launch(const shems_per *per, const shems_group *g, const shems_group_hparams *hp, int64_t capacity, int64_t ring_len,
+                                   int64_t fresh_pos, int64_t fresh_count, uint64_t seed, uint32_t tick, int32_t batch, hipStream_t st)
+{
+    const PerGroupSampleArgs a{per->prio, per->pmax, per->ws, g->count > 1 ? g->stride_bytes : 0, capacity, ring_len, fresh_pos, fresh_count,
+                               seed, tick, batch, per->beta};
+    if (hp) hipLaunchKernelGGL(k_tp_per_sample_hp, dim3((unsigned)g->count), dim3(1024), 0, st, a, hp);
+    else hipLaunchKernelGGL(k_tp_per_sample, dim3((unsigned)g->count), dim3(1024), 0, st, a);
+    return hip_ok(hipGetLastError(), "k_tp_per_sample launch");
+}
+
+extern "C" int shems_per_group_sample_dev(const shems_per *per0, const shems_group *g, const shems_group_hparams *d_hp, int64_t capacity,
+                                          int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed, uint32_t tick, int32_t batch,
+                                          void *stream)
+{
+    const char *fn = "shems_per_group_sample_dev";
+    if (int rc = check_group_tp(g, fn)) return rc;
+    if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (int rc = check_per_group(per0, capacity, ring_len, fresh_pos, fresh_count, d_hp ? -1 : (batch < 1 ? 0 : batch), fn)) return rc;
+    if (int rc = check_per_slab(per0, capacity, g, nullptr, 0, fn)) return rc;
+    return per_group_sample_launch(per0, g, d_hp, capacity, ring_len, fresh_pos, fresh_count, seed, tick, batch, (hipStream_t)stream);
+}
+
+template <bool TL, bool HP>
+static int group_update_per_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, const shems_group_hparams *hp,
+                               const shems_per *per, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed, uint32_t tick,
+                               double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags,
+                               void *stream)
+{
+    const char *fn = "shems_ddpg_group_update_per_tp";
+    // ---- whatever shems_ddpg_group_update_tp refuses ----
+    if (int rc = check_group_tp(g, fn)) return rc;
+    if (!d || !d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
+        !d->s_min || !d->s_max || !d->ws || !d->losses)
+        return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
+    if ((flags & SHEMS_TP_STORE_GRAD) && (!d->grad_actor || !d->grad_critic)) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
+    if (flags & ~(SHEMS_TP_STORE_GRAD | SHEMS_TP_PER_GIVEN)) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
+    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
+    if (HP && ((uintptr_t)hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    if (HP) eta_crit = eta_act = 0.0;        // the *_hp kernels form k1 from the records
+    for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
+        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
+    if (int rc = w2t_flux_guard(d->actor, fn)) return rc;
+    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
+        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    for (double bp : {bp1_crit, bp2_crit, bp1_act, bp2_act})
+        if (!(bp > 0.0 && bp < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
+    if (TL) if (int rc = check_w2t(t, fn)) return rc;
+    // ---- the prioritized ring's own arguments, and its blocks against the slab ----
+    if (int rc = check_per_group(per, ring->capacity, ring_len, fresh_pos, fresh_count, HP ? -1 : d->batch, fn)) return rc;
+    {
+        const size_t na = (size_t)SHEMS_ACTOR_PARAMS * 4, nc = (size_t)SHEMS_CRITIC_PARAMS * 4, cap = (size_t)ring->capacity;
+        const SlabBlock blocks[] = {
+            {d->actor, na}, {d->critic, nc}, {d->actor_t, na}, {d->critic_t, nc}, {d->m_actor, na}, {d->v_actor, na}, {d->m_critic, nc}, {d->v_critic, nc},
+            {d->grad_actor, na}, {d->grad_critic, nc}, {d->s_min, SHEMS_NSTATE * 4}, {d->s_max, SHEMS_NSTATE * 4}, {d->ws, (size_t)kTpWsFloats * 4},
+            {d->losses, 8}, {ring->s, cap * SHEMS_NSTATE * 4}, {ring->a, cap * 2 * 4}, {ring->r, cap * 4}, {ring->s2, cap * SHEMS_NSTATE * 4},
+            {ring->done, cap}, {TL ? t->actor : nullptr, (size_t)SHEMS_W2T_FLOATS * 4}, {TL ? t->critic : nullptr, (size_t)SHEMS_W2T_FLOATS * 4}};
+        if (int rc = check_per_slab(per, ring->capacity, g, blocks, (int)(sizeof blocks / sizeof blocks[0]), fn)) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned L = (unsigned)g->count;
+    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
+    const int sg = (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0;
+    const bool given = (flags & SHEMS_TP_PER_GIVEN) != 0;
+    float *ws = d->ws;
+    float *ta = TL ? t->actor : nullptr, *tc = TL ? t->critic : nullptr;
+    auto arr = [](float *region, int a) -> const float * { return region ? region + a * TL_TILE : nullptr; };
+    auto adam_ctx = [&](bool critic) {
+        const double eta = critic ? eta_crit : eta_act, bp1 = critic ? bp1_crit : bp1_act, bp2 = critic ? bp2_crit : bp2_act;
+        return critic ? AdamCtx{d->critic, d->grad_critic, d->m_critic, d->v_critic, d->critic_t, nullptr, SHEMS_CRITIC_PARAMS, (int)CIN,
+                                eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau}
+                      : AdamCtx{d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
+                                eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau};
+    };
+    // the jobs and records exactly as group_update_tp fills them
+    struct { PrepPerArgs pa; FwdArgs f1, f2, f5; PerD1Args nc; NetArgs ng, na; } U;
+    std::memset(&U, 0, sizeof U);
+    U.pa = PrepPerArgs{PrepArgs{*d, *ring, ring_len, gs, seed, tick}, per->ws};
+    for (FwdArgs *f : {&U.f1, &U.f2, &U.f5}) { f->gstride = gs; f->batch = d->batch; }
+    U.f1.job[0] = FwdJob{arr(ta, TL_T), d->actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
+    U.f1.job[1] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, NET_CRITIC), nullptr, nullptr, nullptr, ws + TP_H2C, p3_of(ws, NET_CRITIC), nullptr, CIN, 1};
+    U.f1.job[2] = FwdJob{arr(ta, TL_P), d->actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
+    U.f2.job[0] = FwdJob{arr(tc, TL_T), d->critic_t, ws + TP_X2, w1i_of(ws, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, nullptr, nullptr,
+                         p3_of(ws, NET_CRITIC_T), nullptr, CIN, 1};
+    U.f5.job[0] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, IMG_CRITIC_NEW), p3_of(ws, NET_ACTOR), ws + TP_FB3 + 2, ws + TP_API, nullptr, p3_of(ws, PASS_CRITIC2),
+                         ws + TP_DAP, CIN, 1};
+    U.ng = NetArgs{*d, tc, adam_ctx(true), gs, 1, sg, (int)L};
+    U.nc = PerD1Args{U.ng, PerX{per->ws, given ? nullptr : per->prio, given ? nullptr : per->pmax, ring_len, per->alpha, per->eps_p}};
+    U.na = NetArgs{*d, ta, adam_ctx(false), gs, 2, sg, (int)L};
+    typedef FwdShape<false, 4> SW;
+    typedef FwdShape<false, 2> SN;
+    typedef FwdShape<true, 2> SQ;
+    const bool narrow = L < kNarrowBelow;
+    const unsigned g8 = 8 * ((L + 7) / 8);
+    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args) {
+        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, hp);
+        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
+    };
+    if (!given)
+        if (int rc = per_group_sample_launch(per, g, HP ? hp : nullptr, ring->capacity, ring_len, fresh_pos, fresh_count, seed, tick, d->batch, st)) return rc;
+    launch(k_tp_prep_per, k_tp_prep_per_hp, dim3(5, L), 0, U.pa);
+    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(3 * SN::TILES, L), SN::LDS, U.f1);
+    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(3 * SW::TILES, L), SW::LDS, U.f1);
+    launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(SN::TILES, L), SN::LDS, U.f2);
+    if (narrow) launch(k_tp_d1_per<1, TL>, k_tp_d1_per_hp<1, TL>, dim3(8 * g8), d1_lds(1), U.nc);
+    else launch(k_tp_d1_per<2, TL>, k_tp_d1_per_hp<2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.nc);
+    launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, U.ng);
+    launch(k_tp_fwd<true, 2, TL>, k_tp_fwd_hp<true, 2, TL>, dim3(SQ::TILES, L), SQ::LDS, U.f5);
+    if (narrow) launch(k_tp_d1<SIN, 1, TL>, k_tp_d1_hp<SIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.na);
+    else launch(k_tp_d1<SIN, 2, TL>, k_tp_d1_hp<SIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.na);
+    launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.na);
+    return hip_ok(hipGetLastError(), "grouped prioritized update (throughput form) launches");
+}
+
+extern "C" int shems_ddpg_group_update_per_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
+                                              const shems_group_hparams *d_hp, const shems_per *per, int64_t ring_len, int64_t fresh_pos,
+                                              int64_t fresh_count, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit,
+                                              double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream)
+{
+    auto *update = t ? (d_hp ? group_update_per_tp<true, true> : group_update_per_tp<true, false>)
+                     : (d_hp ? group_update_per_tp<false, true> : group_update_per_tp<false, false>);
+    return update(d, ring, g, t, d_hp, per, ring_len, fresh_pos, fresh_count, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags,
+                  stream);
 }
 
 static_assert(sizeof(shems_group_xparams) == 16 && offsetof(shems_group_xparams, ou_dt) == 4 && offsetof(shems_group_xparams, mem_size) == 8 &&

@@ -18,8 +18,8 @@ import numpy as np
 
 from . import _capi
 from .ddpg import (ACTION, BATCH_SIZE, EP_LENGTH_TRAIN, ETA_ACT, ETA_CRIT, GAMMA, L1, L2, MEM_SIZE, N_ACTOR, N_CRITIC, NOISE_SIGMA, SEED_INI,
-                   STATE, TAU, Agent, RingWindow, _declare, act_kernel_name, unpad_net, unpad_net_from)
-from .replay import ReplayRing
+                   STATE, TAU, Agent, RingWindow, _declare, act_kernel_name, anneal_beta, unpad_net, unpad_net_from)
+from .replay import PER_COLS, PER_MAX_SLOTS, PW_IDX, PW_W, PerArgs, ReplayRing, per_workspace_floats
 
 
 class Group(C.Structure):              # shems_group
@@ -839,6 +839,191 @@ class LearnerGroup:
         E_eval = run_episodes_check(self.count, self.n_envs, self.n_envs, getattr(env_eval, "n", None), 1, 1, test_runs)
         r = self._eval_returns(env_eval, E_eval).view(self.count, E_eval)[:, :int(test_runs)].cpu().numpy()
         return np.cumsum(r, axis=1)[:, -1] / int(test_runs)
+
+
+def per_extra_blocks(capacity):
+    """The (name, floats) blocks a prioritized group keeps in every learner's slab behind ring_done: the priorities, pmax (padded to 16
+    bytes) and the sampler workspace.  Host only."""
+    return (("per_prio", int(capacity)), ("per_pmax", 4), ("per_ws", per_workspace_floats(int(capacity))))
+
+
+def per_group_refusals(form=None, noise_type="gn", hparams=None, hidden=None, capacity=MEM_SIZE, alpha=0.6, beta=0.4, eps=1e-6):
+    """What PrioritizedLearnerGroup refuses before any device work, each by name."""
+    import math
+    if form in ("latency", "wide"):
+        raise NotImplementedError(f"prioritized learner group: form={form!r} has no weighted head; the group runs the throughput form "
+                                  "(shems_ddpg_group_update_per_tp) whatever its count")
+    if form not in (None, "throughput"):
+        raise ValueError("form must be 'throughput'")
+    if noise_type == "ou":
+        raise NotImplementedError("prioritized learner group: Ornstein-Uhlenbeck noise runs on the *_x entry points, which have no prioritized update")
+    if hidden is not None:
+        raise NotImplementedError("prioritized learner group: hidden= belongs to form='wide', which has no prioritized update")
+    for l, h in enumerate(hparams or ()):
+        if hasattr(h, "keys") and "mem_size" in h:
+            raise NotImplementedError(f"prioritized learner group: hparams[{l}]: per-learner mem_size runs on the *_x entry points, which have no "
+                                      "prioritized update (the rings advance in lockstep)")
+        if hasattr(h, "keys") and int(h.get("batch", 0)) > MAX_GROUP_BATCH:
+            raise NotImplementedError(f"prioritized learner group: hparams[{l}]: batch {h['batch']} > {MAX_GROUP_BATCH}: the sampler draws at most "
+                                      f"{MAX_GROUP_BATCH} columns")
+        if hasattr(h, "keys") and "hidden" in h and (int(h["hidden"][0]) > L1 or int(h["hidden"][1]) > L2):
+            raise NotImplementedError(f"prioritized learner group: hparams[{l}]: hidden {tuple(h['hidden'])} is wider than ({L1}, {L2}): the wide "
+                                      "form has no prioritized update")
+    if int(capacity) > PER_MAX_SLOTS:
+        raise NotImplementedError(f"prioritized learner group: capacity {int(capacity)} > {PER_MAX_SLOTS}: a learner's sampler workgroup keeps "
+                                  "every block sum in LDS")
+    for name, v in (("alpha", alpha), ("beta", beta), ("eps", eps)):
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f"prioritized learner group: {name} = {v!r} must be finite and >= 0")
+    if beta > 1.0:
+        raise ValueError(f"prioritized learner group: beta = {beta!r} must be in [0, 1]")
+
+
+class PrioritizedLearnerGroup(LearnerGroup):
+    """`count` independent DDPG learners that each draw their minibatch by priority (proportional prioritized replay, Schaul et al. 2016;
+    shems_ddpg_group_update_per_tp): a LearnerGroup whose slabs also hold prio [capacity], pmax and the sampler workspace
+    per learner, carved behind the ring, so every offset of a DDPG group is unchanged.  alpha, beta and eps are the group's; beta is
+    read at every update (run_episodes(anneal_beta_from=...) anneals it).  `covered` counts the pushes whose priorities are set, for
+    the whole group: the rings advance in lockstep, and the pushes since the last update (populate_memory's, the fused step's window)
+    receive each learner's pmax before its draw.  Throughput form only, whatever the count.  act_step, populate_memory, min_max_buffer,
+    ring_window, eval_scores, clone (it reads the demonstration rings, not the priorities) and flux_() are the LearnerGroup's.  Refused by
+    name (NotImplementedError): form 'latency' / 'wide', "ou" noise and per-learner mem_size (the *_x entry points), batch > 128, wide
+    hidden sizes, capacity > 262144, evaluate() and with it imitation.warm_start_group, a class that is also a TD3LearnerGroup."""
+
+    has_evaluate = False
+
+    def __init__(self, count, envs_per_learner, alpha=0.6, beta=0.4, eps=1e-6, **kw):
+        if any(c.__name__ == "TD3LearnerGroup" for c in type(self).__mro__):
+            raise NotImplementedError("prioritized learner group: the twin-critic update (TD3LearnerGroup) has no weighted head")
+        if kw.get("hparams") is not None:
+            kw["hparams"] = list(kw["hparams"])              # (a generator is walked once, here)
+        per_group_refusals(kw.get("form"), kw.get("noise_type", "gn"), kw.get("hparams"), kw.get("hidden"), kw.get("capacity", MEM_SIZE),
+                           alpha, beta, eps)
+        kw["form"] = "throughput"
+        self.alpha, self.beta, self.eps = float(alpha), float(beta), float(eps)
+        self._anneal = None                                  # (beta0, num_ep) while run_episodes(anneal_beta_from=beta0) runs
+        super().__init__(count, envs_per_learner, **kw)
+        self.LP = _capi.declare_group_per()
+        self.slab[:, self.layout["per_pmax"][0]] = 1.0       # pmax: 1.0 at the start
+        self.covered = 0                                     # pushes whose priorities are set (host state, the whole group's)
+
+    def _extra_blocks(self, n_critic):
+        return per_extra_blocks(self.capacity)
+
+    # ---- views ----
+    def _view(self, l, name):
+        o, n = self.layout[name]
+        return self.slab[l, o:o + n]
+
+    def prio_of(self, l):
+        """Learner l's priorities pi = p^alpha, [capacity]."""
+        return self._view(l, "per_prio")
+
+    def pmax_of(self, l):
+        """Learner l's running maximum of every pi ever written, [1]."""
+        return self._view(l, "per_pmax")[:1]
+
+    def sampled_of(self, l):
+        """The slots of learner l's last draw, int32 [128] (-1 in the pad columns)."""
+        return self._view(l, "per_ws")[PW_IDX:PW_IDX + PER_COLS].view(self.torch.int32)
+
+    def weights_of(self, l):
+        """The importance weights of learner l's last draw, [128] (0 in the pad columns)."""
+        return self._view(l, "per_ws")[PW_W:PW_W + PER_COLS]
+
+    def fresh_range(self):
+        """(fresh_pos, fresh_count) of the next update: the pushes since `covered` (PrioritizedRing.fresh_range for the group)."""
+        n = self.rings[0].pushed - self.covered
+        if n < 0:
+            raise ValueError("prioritized learner group: pushed went backwards")
+        return self.covered % self.capacity, min(n, self.capacity)
+
+    def per_struct(self):
+        """Learner 0's shems_per (learner l's arrays lie at + l * the slab stride)."""
+        p = lambda name: self.slab.data_ptr() + 4 * self.layout[name][0]
+        return PerArgs(p("per_prio"), p("per_pmax"), p("per_ws"), self.alpha, self.beta, self.eps, 0)
+
+    def per_sample(self, tick=None, fresh=None, batch=None):
+        """The sampler launch alone (shems_per_group_sample_dev): fresh fill, sums, draw and weights of every learner, as the next
+        replay() would draw them.  fresh: (pos, count) in place of fresh_range(); `covered` does not move."""
+        a0, g, per = self.learners[0], self.struct(), self.per_struct()
+        pos, cnt = self.fresh_range() if fresh is None else fresh
+        tick = self.updates if tick is None else tick
+        _capi.check(self.LP.shems_per_group_sample_dev(C.byref(per), C.byref(g), self._hp_ptr(), self.capacity, len(self.rings[0]), int(pos),
+                                                       int(cnt), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.batch if batch is None else int(batch),
+                                                       self._stream()))
+
+    # ---- refused paths ----
+    def evaluate(self, rings=None, tick=None, tau=None):
+        raise NotImplementedError("prioritized learner group: evaluate() is the critic-only update on a uniform draw; the prioritized group "
+                                  "has none (and so imitation.warm_start_group does not run on it)")
+
+    def _update(self, tick, flags):
+        if self.form != "throughput":
+            raise NotImplementedError(f"prioritized learner group: form={self.form!r} has no weighted head")
+        a0, g, r0 = self.learners[0], self.struct(), self._ring0()
+        if self._hp_dev is None and a0.batch > MAX_GROUP_BATCH:
+            raise NotImplementedError(f"prioritized learner group: batch {a0.batch} > {MAX_GROUP_BATCH}: the sampler draws at most "
+                                      f"{MAX_GROUP_BATCH} columns")
+        tl = self._use_tiled()
+        d, per = a0._ddpg_args(), self.per_struct()
+        tick = self.updates if tick is None else tick
+        t = C.byref(self.w2t_struct()) if tl else None
+        fresh_pos, fresh_count = self.fresh_range()
+        _capi.check(self.LP.shems_ddpg_group_update_per_tp(C.byref(d), C.byref(r0), C.byref(g), t, self._hp_ptr(), C.byref(per), len(self.rings[0]),
+                                                           fresh_pos, fresh_count, self.rng_seed, int(tick) & 0xFFFFFFFF, a0.eta_crit,
+                                                           a0.bp_critic[0], a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1],
+                                                           flags | (_capi.TP_STORE_GRAD if self.store_grad else 0), self._stream()))
+        if tl:
+            self._flux_valid = False
+        for ag in self.learners:                   # the learners advance in lockstep, as in LearnerGroup.replay()
+            ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
+            ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
+            ag.updates += 1
+        self.updates += 1
+
+    def replay(self, tick=None):
+        """One prioritized update of every learner (shems_ddpg_group_update_per_tp: nine launches).  The pushes since `covered` are the
+        fresh range; bp_critic, bp_actor and `updates` advance as in LearnerGroup.replay().  On a tiled group the Flux-order view goes
+        stale, as after LearnerGroup.replay()."""
+        self._update(tick, 0)
+        self.covered = self.rings[0].pushed
+
+    def replay_given(self, idx, weights):
+        """replay() on slots and weights the caller supplies (SHEMS_TP_PER_GIVEN): idx int32 [count][128] (-1 in the pad columns) and
+        weights float32 [count][128], device tensors, copied into the learners' sampler workspaces.  No sampler launch, no write-back,
+        `covered` does not move; with learner l's idx = sample_indices(rng_seed + l, tick) and weights of 1.0 it leaves
+        LearnerGroup.replay()'s bits.  State advances as in replay()."""
+        t = self.torch
+        shape = (self.count, PER_COLS)
+        if idx.dtype != t.int32 or weights.dtype != t.float32 or tuple(idx.shape) != shape or tuple(weights.shape) != shape:
+            raise ValueError(f"replay_given: idx int32 {list(shape)}, weights float32 {list(shape)}")
+        if idx.device != self.device or weights.device != self.device:
+            raise ValueError(f"replay_given: idx and weights must live on {self.device}")
+        o = self.layout["per_ws"][0]
+        self.slab[:, o + PW_IDX:o + PW_IDX + PER_COLS].view(t.int32).copy_(idx)
+        self.slab[:, o + PW_W:o + PW_W + PER_COLS].copy_(weights)
+        self._update(None, _capi.TP_PER_GIVEN)
+
+    def episode_(self, env, train=True, num_steps=None, rng_ep=0, episode=0, window_count=None, noise_acc=None):
+        if train and self._anneal is not None:     # Agent.run_episodes' rule: linear in the episode, exactly 1.0 in the last one
+            beta0, num_ep = self._anneal
+            self.beta = anneal_beta(beta0, int(episode) - 1, max(1, num_ep - 1))
+        return super().episode_(env, train=train, num_steps=num_steps, rng_ep=rng_ep, episode=episode, window_count=window_count,
+                                noise_acc=noise_acc)
+
+    def run_episodes(self, env_train, env_eval, num_ep, test_every=100, test_runs=100, seed=None, window_count=None, on_eval=None,
+                     on_best=None, anneal_beta_from=None):
+        """LearnerGroup.run_episodes on prioritized updates.  anneal_beta_from: beta of episode i is anneal_beta(anneal_beta_from, i - 1,
+        num_ep - 1): linear in the episode, exactly 1.0 in the last one (Agent.run_episodes' rule); None keeps `beta` as it stands."""
+        if anneal_beta_from is not None:
+            anneal_beta(anneal_beta_from, 0, 1)              # (refuses a beta0 outside [0, 1] before anything runs)
+            self._anneal = (float(anneal_beta_from), int(num_ep))
+        try:
+            return super().run_episodes(env_train, env_eval, num_ep, test_every=test_every, test_runs=test_runs, seed=seed,
+                                        window_count=window_count, on_eval=on_eval, on_best=on_best)
+        finally:
+            self._anneal = None
 
 
 def run_episodes_check(count, n_envs, n_train, n_eval, num_ep, test_every, test_runs):
