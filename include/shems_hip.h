@@ -1008,6 +1008,55 @@ int shems_foresight_transitions_dev(const float *d_tables, int64_t total_rows, c
                                     const int32_t *d_problem_of_pass, int32_t mode, float gamma, int32_t tail, double *d_returns,
                                     const shems_replay *ring, int64_t pos, int32_t *d_status, void *stream);
 
+/* ------------------------------------------ multi-step (n-step) returns -- */
+/* n-step transitions (s_t, a_t, G_t, s_{t+n}) with G_t = sum_{k<n} gamma^k r_{t+k} and y = G + gamma^n q'(s_{t+n}), as in Rainbow and
+ * D4PG (csrc/shems_nstep_core.h holds the arithmetic).  They change only what a ring holds: every update entry point
+ * reads such a ring as any other and receives gamma_n in its `gamma` field.
+ *   Full windows only.  The env has no terminal state, so an episode of T hours contributes the T - n + 1 transitions that start at
+ *     hours 0 .. T - n.  The last n - 1 hours start no transition; their rewards do enter the earlier windows.  Episode starts are drawn
+ *     over the whole table, so no table row is lost as a start state.  Every stored transition has the same discount gamma^n.
+ *   History is per episode: a window never spans a reset.
+ *   The return is evaluated from the ring's own Float32(reward) values by Horner's rule in float64, newest first:
+ *       acc = (double) r_{t+n-1};   for k = n-2 .. 0: acc = (double) r_{t+k} + (double) gamma32 * acc;   G32 = (float) acc
+ *     (rounded product, then add: no fma; the unit is built with -ffp-contract=off).  gamma32 is the Float32 one-step discount.
+ *   The discount is computed on the host, once: gamma_n = float32(g64 * g64 * ... * g64), g64 = float64(gamma32), n factors multiplied
+ *     left to right in float64.  There is no device pow.
+ *   done of an emitted transition is the newest one-step transition's byte (always 0 in this env).
+ *   1 <= n <= SHEMS_NSTEP_MAX and n <= T.  n = 1 reproduces the one-step ring's bytes.
+ *
+ * The fold, per vector step: the unchanged fused step writes its one-step transitions of the STATIONARY window of households
+ * [0, window) -- shems_ring_window{0, window, 0} -- into a staging shems_replay of capacity >= window (slot j = household j).
+ * shems_nstep_fold_dev then stores (s, a, r) of hour `hour` (counted from the episode's reset) into history slot hour mod n and, for
+ * hour >= n - 1, emits (hist_s[o], hist_a[o], G, stage.s2, stage.done), o = (hour + 1) mod n, of household j into ring slot
+ * (ring_pos + j) mod capacity; for hour < n - 1 it emits nothing (the caller advances its push counter by `window` only when
+ * hour >= n - 1).  One launch, threads flat over the window's elements.  SHEMS_ERR_ARG, nothing launched: n outside 1 ..
+ * SHEMS_NSTEP_MAX, window < 1, hour < 0, ring_pos < 0, a NULL, a ring or staging ring without all five arrays or smaller than the
+ * window. */
+#define SHEMS_NSTEP_MAX 16
+typedef struct shems_nstep {
+    int32_t  n;              /* steps per return, 1 .. SHEMS_NSTEP_MAX                  */
+    int32_t  reserved;
+    int64_t  window;         /* households folded per step                               */
+    float    gamma;          /* gamma32: the Float32 ONE-step discount                   */
+    int32_t  reserved2;
+    float   *hist_s;         /* dev [n][window][9]                                       */
+    float   *hist_a;         /* dev [n][window][2]                                       */
+    float   *hist_r;         /* dev [n][window]                                          */
+} shems_nstep;
+int shems_nstep_fold_dev(const shems_nstep *ns, const shems_replay *stage, const shems_replay *ring, int64_t ring_pos, int32_t hour,
+                         void *stream);
+/* The same for every learner of a group in ONE launch: learner l's history, staging and ring arrays lie at learner 0's pointers
+ * + l * g->stride_bytes.  d_gamma1: dev float [g->count] of one-step discounts; NULL = ns0->gamma for all learners. */
+int shems_nstep_group_fold_dev(const shems_nstep *ns0, const shems_replay *stage0, const shems_replay *ring0, const shems_group *g,
+                               const float *d_gamma1, int64_t ring_pos, int32_t hour, void *stream);
+/* The bulk form, for populate_memory: src holds episode e's hour t at slot e * steps + t (what shems_rollout_dev writes into a ring of
+ * that capacity from position 0).  With m = steps - n + 1, transition (e, t), t < m, goes to slot (ring_pos + e * m + t) mod capacity;
+ * pushes that a later push of the same call would overwrite (order < episodes * m - capacity) are skipped, as in shems_rollout_dev.
+ * The caller advances its push counter by episodes * m.  SHEMS_ERR_ARG: n outside 1 .. SHEMS_NSTEP_MAX, steps < n, episodes < 1, a
+ * source smaller than episodes * steps, src and ring the same arrays. */
+int shems_nstep_from_episodes_dev(const shems_replay *src, int64_t episodes, int64_t steps, int32_t n, float gamma,
+                                  const shems_replay *ring, int64_t ring_pos, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

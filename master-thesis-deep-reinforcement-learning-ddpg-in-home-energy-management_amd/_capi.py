@@ -150,6 +150,38 @@ def declare_group_per():
     return L
 
 
+class NStepArgs(C.Structure):          # shems_nstep
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("window", C.c_int64), ("gamma", C.c_float), ("reserved2", C.c_int32),
+                ("hist_s", C.c_void_p), ("hist_a", C.c_void_p), ("hist_r", C.c_void_p)]
+
+
+NSTEP_MAX = 16                         # SHEMS_NSTEP_MAX
+
+
+def _nstep_sigs():
+    """Multi-step returns (shems_group * goes as a void pointer: its mirror lives in group.py)."""
+    vp, i64, i32, f = C.c_void_p, C.c_int64, C.c_int32, C.c_float
+    PN, PR_ = C.POINTER(NStepArgs), C.POINTER(Replay)
+    return {
+        "shems_nstep_fold_dev": [PN, PR_, PR_, i64, i32, vp],
+        "shems_nstep_group_fold_dev": [PN, PR_, PR_, vp, vp, i64, i32, vp],
+        "shems_nstep_from_episodes_dev": [PR_, i64, i64, i32, f, PR_, i64, vp],
+    }
+
+
+def declare_nstep():
+    """The prototypes of _nstep_sigs (compared with include/shems_hip.h by tests/test_nstep_host.py)."""
+    L = lib()
+    if getattr(L, "_nstep_declared", False):
+        return L
+    for name, args in _nstep_sigs().items():
+        fn = getattr(L, name)
+        fn.argtypes = args
+        fn.restype = C.c_int
+    L._nstep_declared = True
+    return L
+
+
 def exported_symbols():
     """Names include/shems_hip.h declares (used by the CPU-side ABI test)."""
     import re

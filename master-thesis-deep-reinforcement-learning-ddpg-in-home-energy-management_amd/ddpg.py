@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .parallel import GradSync, shard_envs  # noqa: F401
-from .replay import PrioritizedRing, ReplayRing, _declare_per
+from .replay import NStepWindow, PrioritizedRing, ReplayRing, _declare_per, check_n_step, nstep_from_episodes, nstep_gamma
 
 L1, L2, STATE, ACTION = 250, 500, 9, 2
 N_ACTOR, N_CRITIC = 129002, 129001
@@ -311,14 +311,18 @@ class Agent:
     """The DDPG learner state on one GPU (one replica under data parallelism)."""
 
     def __init__(self, seed=1231, device=None, sigma=NOISE_SIGMA, mu=0.0, rng_seed=None, noise_type="gn", theta=0.15,
-                 dt=1e-2, eps=0.5, tensors=None, hidden=(L1, L2), wide=None, layout=None):
+                 dt=1e-2, eps=0.5, tensors=None, hidden=(L1, L2), wide=None, layout=None, n_step=1):
         """tensors: dict of float32 device views (actor, critic, actor_t, critic_t, m_actor, v_actor, m_critic, v_critic,
         grad_actor, grad_critic, s_min, s_max, ws, losses) in memory the caller owns -- a learner group's slab -- instead
         of buffers allocated here.  wide: None = by size (is_wide); True = the layer-by-layer path whatever the size (tests hold the two
         implementations against each other at (250, 500)).  layout (wide path only): the hidden size the networks are zero-padded into
         and the wide kernels run at (a wide learner group's width, group.LearnerGroup(form="wide")); None = `hidden`.  export_* and
-        set_params speak `hidden`."""
+        set_params speak `hidden`.  n_step: the steps of a multi-step return (1 .. 16, include/shems_hip.h): with n_step > 1 the
+        training episodes push (s_t, a_t, G_t, s_{t+n}) through a replay.NStepWindow, populate_memory converts whole episodes, and
+        every update of this agent bootstraps with gamma_n; `gamma` stays the one-step discount."""
         import torch
+        self.n_step = check_n_step(n_step)             # (an argument error before any device work)
+        self._nstep = None                         # the NStepWindow of the training episodes, made on first use
         self.torch = torch
         self.L = _declare()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -633,6 +637,26 @@ class Agent:
                                               C.byref(window) if window is not None else None, self._stream()))
 
     # ---------------------------------------------------------------- learner
+    @property
+    def gamma_n(self):
+        """The discount of every update's bootstrap: gamma itself, or nstep_gamma(gamma, n_step) of an n-step learner."""
+        return self.gamma if self.n_step == 1 else nstep_gamma(self.gamma, self.n_step)
+
+    def _nstep_refusals(self, what, num_steps):
+        """What an n-step learner cannot do, by name, before any device work."""
+        if self.sync.world > 1:
+            raise NotImplementedError(f"{what}: n_step = {self.n_step} with data-parallel replicas (sync.world = {self.sync.world}): "
+                                      "the n-step ring is built per replica and has no exchange")
+        if int(num_steps) < self.n_step:
+            raise ValueError(f"{what}: num_steps = {int(num_steps)} < n_step = {self.n_step}: an episode must hold one full window")
+
+    def nstep_window(self, window_count):
+        """The agent's replay.NStepWindow for `window_count` households (kept between episodes while the count and gamma stay)."""
+        w = self._nstep
+        if w is None or w.window_count != int(window_count) or w.gamma != float(f32(self.gamma)) or w.n != self.n_step:
+            w = self._nstep = NStepWindow(self.n_step, window_count, self.gamma, device=self.device)
+        return w
+
     MAX_PASS_BATCH = 128                           # minibatch columns one update pass holds (csrc/shems_ddpg.hip: BP)
 
     def _ddpg_args(self, sub=None, raw=False):
@@ -647,7 +671,7 @@ class Agent:
         return DdpgArgs(B("actor").data_ptr(), B("critic").data_ptr(), B("actor_t").data_ptr(), B("critic_t").data_ptr(),
                         B("m_actor").data_ptr(), B("v_actor").data_ptr(), B("m_critic").data_ptr(), B("v_critic").data_ptr(),
                         ga.data_ptr(), gc.data_ptr(), self.s_min.data_ptr(), self.s_max.data_ptr(),
-                        ws.data_ptr(), ls.data_ptr(), self.gamma, self.tau, b,
+                        ws.data_ptr(), ls.data_ptr(), self.gamma_n, self.tau, b,
                         1 if defer else 0)                                                    # SHEMS_DDPG_DEFER_ACTOR_E
 
     def sub_batches(self):
@@ -718,7 +742,11 @@ class Agent:
     def enable_data_parallel(self, dist, native=None):
         """Replicas (one per GPU, each with its own env shard and ring) all-reduce gradients over RCCL.  native: a shems_dp communicator
         (parallel.native_comm) -- the all-reduces then run in the update's own stream, from native code."""
-        self.sync = GradSync(dist, native=native)
+        sync = GradSync(dist, native=native)
+        if self.n_step > 1 and sync.world > 1:     # refused before the agent holds the replicas' sync
+            raise NotImplementedError(f"enable_data_parallel: n_step = {self.n_step} with data-parallel replicas (sync.world = {sync.world}): "
+                                      "the n-step ring is built per replica and has no exchange")
+        self.sync = sync
         self.sync.broadcast(self.actor, self.critic, self.actor_t, self.critic_t)   # identical initial weights
 
     def _allreduce(self, g):
@@ -927,12 +955,36 @@ class Agent:
         reference runs ceil(MEM/72) sequential 72-step episodes; here that many envs of the batch run
         them in ONE launch (shems_rollout_dev) and push in the reference's episode-major order."""
         self._same_device(env, ring)
+        if self.n_step > 1:
+            return self.populate_memory_nstep(env, ring, seed=seed)
         seed = self.rng_seed if seed is None else int(seed)
         nsteps = env.maxsteps
         n_ep = -(-ring.capacity // nsteps)                    # episodes until length(memory) >= MIN_EXP_SIZE
         while len(ring) < ring.capacity:
             env.reset_(seed, episode=0x7FFF0000 + ring.pushed // max(1, nsteps))
             env.rollout("random", nsteps, seed=seed + ring.pushed, ring=ring, ring_envs=min(env.n, n_ep))
+        return ring
+
+    def populate_memory_nstep(self, env, ring, seed=None, n_step=None, scratch=None):
+        """populate_memory of an n-step learner: every round rolls its episodes out into a scratch ring (one-step transitions, episode e's
+        hour t at slot e * nsteps + t) and converts them with shems_nstep_from_episodes_dev.  The rounds mirror populate_memory's and the
+        reset / action keys come from the destination ring's `pushed`, so n_step = 1 leaves populate_memory's bytes.  scratch: a ring of
+        at least min(env.n, episodes) * nsteps slots to reuse (a learner group shares one)."""
+        self._same_device(env, ring)
+        n = self.n_step if n_step is None else check_n_step(n_step)
+        nsteps = env.maxsteps
+        self._nstep_refusals("populate_memory", nsteps)
+        seed = self.rng_seed if seed is None else int(seed)
+        m = nsteps - n + 1                                    # transitions per episode
+        n_ep = -(-ring.capacity // m)
+        E = min(env.n, n_ep)
+        if scratch is None or scratch.capacity < E * nsteps:
+            scratch = ReplayRing(E * nsteps, device=self.device)
+        while len(ring) < ring.capacity:
+            env.reset_(seed, episode=0x7FFF0000 + ring.pushed // max(1, m))
+            scratch.pushed = 0
+            env.rollout("random", nsteps, seed=seed + ring.pushed, ring=scratch, ring_envs=E)
+            nstep_from_episodes(scratch, E, nsteps, n, self.gamma, ring, stream=self._stream())
         return ring
 
     def episode_(self, env, ring=None, train=True, num_steps=None, rng_ep=0, episode=0, updates_per_step=1,
@@ -955,17 +1007,33 @@ class Agent:
             raise ValueError("training episodes need a replay ring")
         if window_count is None and ring is not None:
             window_count = min(env.n, max(1, ring.capacity // num_steps))       # SURVEY.md 8(d) replay-capacity note
+        nsw = None
+        if train and self.n_step > 1:
+            # an n-step learner: the step writes the STATIONARY window of households [0, window_count) into the staging ring, the fold
+            # behind it pushes from hour n_step - 1 on (replay.NStepWindow); history is per episode
+            self._nstep_refusals("episode_", num_steps)
+            if not 1 <= int(window_count) <= min(env.n, ring.capacity):
+                raise ValueError(f"episode_: window_count = {window_count} outside 1 .. min(env.n, ring.capacity)")
+            if len(ring) == 0:
+                raise ValueError(f"episode_: n_step = {self.n_step} on an empty ring: the first {self.n_step - 1} hours of an episode push "
+                                 "nothing, so the updates of those hours need a filled ring (populate_memory)")
+            nsw = self.nstep_window(window_count)
         for step in range(num_steps):
             tick = (int(episode) * 4096 + step) & 0xFFFFFFFF
             win = None
-            if train:
+            if nsw is not None:
+                win = RingWindow(*nsw.window)
+            elif train:
                 win = RingWindow(ring.pos, window_count, (self.tick * window_count) % env.n)
-            self.act_step(env, train=train, tick=tick, returns_acc=returns, ring=ring if train else None, window=win,
-                          noise_acc=self.last_noise)
+            self.act_step(env, train=train, tick=tick, returns_acc=returns, ring=(nsw.stage if nsw is not None else ring) if train else None,
+                          window=win, noise_acc=self.last_noise)
             if train and self.noise_type == "pn":
                 self.last_noise += float(self.pn_sigma)                           # act() returns pn.sigma_current as the "noise" (DDPG.jl:155)
-            if train:
+            if nsw is not None:
+                nsw.fold(ring, step, stream=self._stream())
+            elif train:
                 ring.pushed += window_count
+            if train:
                 for _ in range(updates_per_step):
                     self.replay(ring)
                 self.tick += 1                                                  # rotates the replay window: training steps only
@@ -1036,12 +1104,17 @@ class TrainWorkload:
     dtype = "f32"
     EP_LEN = EP_LENGTH_TRAIN
 
-    def __init__(self, S, torch, n, seed, updates=1, dist=None, overlap=False, mixed=False, scaled_replay=False, hidden=(L1, L2), loop=None):
+    def __init__(self, S, torch, n, seed, updates=1, dist=None, overlap=False, mixed=False, scaled_replay=False, hidden=(L1, L2), loop=None, n_step=1):
         """overlap: False = the reference's order; True / "pipelined" = replay(t) under the fused launch of step t, sampling the ring as
         it stood before step t's inserts; "exact" = the window's envs stepped first, replay(t) under the rest of the batch: the ordered
         loop's bytes.  loop: "native" = the steps are enqueued by shems_train_steps (one foreign call for k steps),
         "host" = one foreign call per launch from this class; None = native wherever the learner is a single replica on the tuned
-        kernels (data parallel replicas exchange gradients through torch.distributed between launches, wide networks take their own path)."""
+        kernels (data parallel replicas exchange gradients through torch.distributed between launches, wide networks take their own path).
+        n_step: only 1.  The workload and its native loop (loop="native", shems_train_steps) have no n-step mode: n_step > 1 is refused by
+        name; multi-step returns train through Agent(n_step=...).run_episodes."""
+        if check_n_step(n_step) > 1:
+            raise NotImplementedError(f"n_step = {n_step}: TrainWorkload and the native loop (loop='native', shems_train_steps) have no "
+                                      "n-step mode; train an Agent(n_step=...) through episode_ / run_episodes")
         self.S, self.torch, self.n, self.updates = S, torch, int(n), int(updates)
         self.overlap_mode = {False: LOOP_ORDERED, None: LOOP_ORDERED, True: LOOP_PIPELINED, "pipelined": LOOP_PIPELINED,
                              "exact": LOOP_PIPELINED_EXACT}[overlap]

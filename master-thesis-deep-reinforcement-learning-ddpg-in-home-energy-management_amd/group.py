@@ -19,7 +19,7 @@ import numpy as np
 from . import _capi
 from .ddpg import (ACTION, BATCH_SIZE, EP_LENGTH_TRAIN, ETA_ACT, ETA_CRIT, GAMMA, L1, L2, MEM_SIZE, N_ACTOR, N_CRITIC, NOISE_SIGMA, SEED_INI,
                    STATE, TAU, Agent, RingWindow, _declare, act_kernel_name, anneal_beta, unpad_net, unpad_net_from)
-from .replay import PER_COLS, PER_MAX_SLOTS, PW_IDX, PW_W, PerArgs, ReplayRing, per_workspace_floats
+from .replay import PER_COLS, PER_MAX_SLOTS, PW_IDX, PW_W, PerArgs, ReplayRing, per_workspace_floats, check_n_step, nstep_gamma
 
 
 class Group(C.Structure):              # shems_group
@@ -57,12 +57,13 @@ def hparam_defaults(sigma=NOISE_SIGMA):
     return dict(eta_act=ETA_ACT, eta_crit=ETA_CRIT, gamma=GAMMA, tau=TAU, sigma=sigma, mu=0.0, batch=BATCH_SIZE, hidden=(L1, L2))
 
 
-def _hparams_records(count, hparams, sigma, capacity, width=None, noise_type="gn", theta=0.15):
+def _hparams_records(count, hparams, sigma, capacity, width=None, noise_type="gn", theta=0.15, n_step=1):
     """Per-learner mappings -> (full dicts, ctypes array of HParams).  Everything the group kernels cannot hold is refused here, naming the
     learner; the records themselves go through shems_group_hparams_check.  Host only: no device work.
     width: the wide form's padded hidden size -- batch up to 256 and hidden up to `width` (shems_group_hparams_check_wide).
     noise_type, theta: the group's (a record's noise_type must be the group's; its theta, "ou" groups only, defaults to the group's).
-    The full dicts also carry noise_type, theta and mem_size (default: capacity) for _xparams_records."""
+    The full dicts also carry noise_type, theta and mem_size (default: capacity) for _xparams_records.  n_step: the records' `gamma` field
+    holds nstep_gamma(gamma_l, n_step), what the updates bootstrap with (the dicts keep the one-step gamma_l)."""
     hparams = list(hparams)
     if len(hparams) != count:
         raise ValueError(f"hparams holds {len(hparams)} records for a group of {count} learners")
@@ -103,13 +104,36 @@ def _hparams_records(count, hparams, sigma, capacity, width=None, noise_type="gn
         for k in ("gamma", "tau", "sigma", "mu"):
             r[k] = float(np.float32(r[k]))
         full.append(r)
-    arr = (HParams * count)(*[HParams(r["eta_act"], r["eta_crit"], r["gamma"], r["tau"], r["mu"], r["sigma"], r["batch"], 0) for r in full])
+    arr = (HParams * count)(*[HParams(r["eta_act"], r["eta_crit"], nstep_gamma(r["gamma"], n_step), r["tau"], r["mu"], r["sigma"], r["batch"], 0)
+                              for r in full])
     L = _declare_group()
     rc = (L.shems_group_hparams_check(arr, count) if width is None else
           L.shems_group_hparams_check_wide(arr, count, max(r["batch"] for r in full)))
     if rc != _capi.OK:
         raise ValueError(L.shems_last_error().decode("utf-8", "replace"))
     return full, arr
+
+
+def nstep_extra_blocks(n_step, envs_per_learner):
+    """The (name, floats) blocks an n_step > 1 group keeps in every learner's slab behind everything else: the staging ring and the
+    history of envs_per_learner households (shems_nstep).  n_step = 1: nothing.  Host only."""
+    n, E = int(n_step), int(envs_per_learner)
+    if n == 1:
+        return ()
+    return (("ns_stage_s", E * STATE), ("ns_stage_a", E * ACTION), ("ns_stage_r", E), ("ns_stage_s2", E * STATE), ("ns_stage_done", (E + 3) // 4),
+            ("ns_hist_s", n * E * STATE), ("ns_hist_a", n * E * ACTION), ("ns_hist_r", n * E))
+
+
+def nstep_group_refusals(form, noise_type, sized):
+    """What an n_step > 1 group refuses before any device work, each by name."""
+    if form == "wide":
+        raise NotImplementedError("n-step learner group: form='wide' (the layer-by-layer path) has no n-step mode")
+    if noise_type == "ou":
+        raise NotImplementedError("n-step learner group: Ornstein-Uhlenbeck noise ('ou') runs on the *_x entry points, which read device push "
+                                  "counters the fold does not keep")
+    if sized:
+        raise NotImplementedError("n-step learner group: per-learner mem_size runs on the *_x entry points, which read device push counters "
+                                  "the fold does not keep (the rings advance in lockstep)")
 
 
 def _xparams_records(full, capacity, dt):
@@ -291,7 +315,7 @@ class LearnerGroup:
     has_evaluate = True                    # evaluate() exists (imitation.warm_start_group asks before it trains anything)
 
     def __init__(self, count, envs_per_learner, seed=1231, rng_seed=None, capacity=MEM_SIZE, sigma=NOISE_SIGMA, device=None, form=None, tiled=None,
-                 hparams=None, hidden=None, noise_type="gn", theta=0.15, dt=1e-2):
+                 hparams=None, hidden=None, noise_type="gn", theta=0.15, dt=1e-2, n_step=1):
         """tiled (throughput form only; default on, SHEMS_GROUP_TILED=0 switches it off): the layer-2 state of both networks (W2, its
         ADAM moments, the target's W2) is kept in the TILED working layout (shems_group_w2t, include/shems_hip.h) while the group trains:
         one contiguous 64 KB piece per 64 x 64 tile for the update's W2-gradient / ADAM launches (4.78 against 3.85 TB/s), read from
@@ -323,7 +347,13 @@ class LearnerGroup:
         whole group.  All networks are zero-padded into one hidden size, `hidden` (default: the elementwise maximum of the records'
         hidden, or (300, 600) without records; up to 4096); a record may then hold batch up to 256 and any hidden size up to `hidden`.
         learners[l] is learner l's wide Agent at its own size (export_* / set_params).  Without hparams every learner trains with
-        learners[0]'s batch (<= 128), gamma, tau and eta.  No tiled layout."""
+        learners[0]'s batch (<= 128), gamma, tau and eta.  No tiled layout.
+
+        n_step (1 .. 16): multi-step returns (include/shems_hip.h).  With n_step > 1 every learner's slab also holds a
+        staging ring and the history of envs_per_learner households, carved behind the subclass's blocks (no existing offset moves; an
+        n_step = 1 group carves nothing); ring_window is the stationary (window_count, 0); act_step writes the window into the staging
+        rings and nstep_fold(hour) -- one launch for the group -- pushes from hour n_step - 1 on; the records (and learners[l].gamma_n)
+        carry gamma_l^n, learners[l].gamma stays gamma_l.  Refused by name: form="wide", "ou" noise, per-learner mem_size."""
         import os
         import torch
         self.torch = torch
@@ -339,10 +369,13 @@ class LearnerGroup:
         if hparams is not None:
             hparams = list(hparams)
         sized = hparams is not None and any(hasattr(h, "keys") and "mem_size" in h for h in hparams)
+        self.n_step = check_n_step(n_step)
+        if self.n_step > 1:
+            nstep_group_refusals(form, noise_type, sized)
         self._x = ou or sized                      # the *_x entry points: per-learner OU noise / ring sizes
         if self._x and form == "latency":
             raise ValueError("Ornstein-Uhlenbeck noise and per-learner mem_size run on the throughput or the wide form: form='latency' takes neither")
-        rec_kw = dict(noise_type=noise_type, theta=self.theta)
+        rec_kw = dict(noise_type=noise_type, theta=self.theta, n_step=self.n_step)
         if form == "wide":
             if tiled:
                 raise ValueError("form='wide' has no tiled working layout: tiled=True is refused")
@@ -393,7 +426,8 @@ class LearnerGroup:
             _capi.check(self.L.shems_ddpg_workspace_floats(C.byref(nws)))
         self._act_ws = None                        # form "wide": scratch of the fused step (shems_wide_act_workspace_floats)
         # one slab per learner (slab_layout); a subclass appends blocks of its own behind the ring
-        layout, off = slab_layout(n_actor, n_critic, nws.value, self.capacity, self.tiled, self._extra_blocks(n_critic))
+        layout, off = slab_layout(n_actor, n_critic, nws.value, self.capacity, self.tiled,
+                                  (*self._extra_blocks(n_critic), *nstep_extra_blocks(self.n_step, self.envs_per_learner)))
         self.layout, self.slab_floats = layout, off
         self.slab = torch.zeros((self.count, self.slab_floats), dtype=torch.float32, device=self.device)
         self.learners, self.rings = [], []
@@ -404,11 +438,11 @@ class LearnerGroup:
             wkw = dict(wide=True, layout=self.hidden) if self.form == "wide" else {}
             if self.hparams is None:
                 self.learners.append(Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=sigma, device=self.device, tensors=tens,
-                                           **(dict(wkw, hidden=self.hidden) if wkw else {})))
+                                           n_step=self.n_step, **(dict(wkw, hidden=self.hidden) if wkw else {})))
             else:                                  # smaller networks come zero-padded (ddpg.pad_net / pad_net_to) and stay so under training
                 h = self.hparams[l]
                 ag = Agent(seed=self.seed + l, rng_seed=self.rng_seed + l, sigma=h["sigma"], mu=h["mu"], device=self.device, tensors=tens,
-                           hidden=h["hidden"], **wkw)
+                           hidden=h["hidden"], n_step=self.n_step, **wkw)
                 ag.gamma, ag.tau, ag.batch, ag.eta_act, ag.eta_crit = h["gamma"], h["tau"], h["batch"], h["eta_act"], h["eta_crit"]
                 ag.noise_type, ag.theta, ag.dt = self.noise_type, h["theta"], self.dt
                 self.learners.append(ag)
@@ -421,6 +455,11 @@ class LearnerGroup:
         if self._hp_host is not None:              # the records, once, in a small device buffer the group owns
             raw = np.frombuffer(bytes(self._hp_host), dtype=np.uint8).copy()
             self._hp_dev = torch.from_numpy(raw).to(self.device)
+        self._gamma1_dev, self._ns_window = None, None
+        if self.n_step > 1:
+            self.LN = _capi.declare_nstep()
+            if self.hparams is not None:           # the fold's one-step discounts (the records hold gamma_l^n)
+                self._gamma1_dev = torch.tensor([r["gamma"] for r in self.hparams], dtype=torch.float32).to(self.device)
         if self._x:
             raw = np.frombuffer(bytes(self._xp_host), dtype=np.uint8).copy()
             self._xp_dev = torch.from_numpy(raw).to(self.device)
@@ -451,6 +490,37 @@ class LearnerGroup:
             self._pushed_dev.copy_(self.torch.tensor(now, dtype=self.torch.int64), non_blocking=False)
             self._pushed_host = now
         return C.c_void_p(self._xp_dev.data_ptr()), C.c_void_p(self._pushed_dev.data_ptr())
+
+    # ---- multi-step returns ---------------------------------------------------------------------------------------------------------
+    def _ns_view(self, l, name):
+        o, n = self.layout[name]
+        return self.slab[l, o:o + n]
+
+    def stage_of(self, l):
+        """Learner l's staging ring (n_step > 1): the one-step transitions of its window's households as the last training step left
+        them, a ReplayRing over envs_per_learner slots (slot j = household j of the learner's block)."""
+        E, v = self.envs_per_learner, lambda name: self._ns_view(l, name)
+        return ReplayRing(E, tensors=(v("ns_stage_s").view(E, STATE), v("ns_stage_a").view(E, ACTION), v("ns_stage_r"),
+                                      v("ns_stage_s2").view(E, STATE), v("ns_stage_done").view(self.torch.uint8)[:E]))
+
+    def nstep_fold(self, hour):
+        """shems_nstep_group_fold_dev behind the training step of hour `hour` of the episode: one launch folds every learner's staging
+        window (the count of the last act_step) into its history and, from hour n_step - 1 on, pushes it into its ring; the rings'
+        push counters advance only then.  Returns True when it pushed."""
+        if self.n_step == 1 or self._ns_window is None:
+            raise ValueError("nstep_fold: an n_step > 1 group folds behind an act_step with a window")
+        wc = self._ns_window
+        p = lambda name: self.slab.data_ptr() + 4 * self.layout[name][0]
+        ns = _capi.NStepArgs(self.n_step, 0, wc, float(np.float32(self.learners[0].gamma)), 0, p("ns_hist_s"), p("ns_hist_a"), p("ns_hist_r"))
+        s0, r0, g = self.stage_of(0).struct(), self._ring0(), self.struct()
+        g1 = C.c_void_p(self._gamma1_dev.data_ptr()) if self._gamma1_dev is not None else None
+        _capi.check(self.LN.shems_nstep_group_fold_dev(C.byref(ns), C.byref(s0), C.byref(r0), C.byref(g), g1, self.rings[0].pos, int(hour),
+                                                       self._stream()))
+        pushed = int(hour) >= self.n_step - 1
+        if pushed:
+            for ring in self.rings:
+                ring.pushed += wc
+        return pushed
 
     def _ring0(self):
         """The entry points' ring0: learner 0's ring arrays with the capacity they are carved for (rings[0] may use a prefix of them)."""
@@ -513,8 +583,17 @@ class LearnerGroup:
         """populate_memory (MPS:9-29) per learner on its own env block (learner l: seed + l)."""
         seed = self.rng_seed if seed is None else int(seed)
         E = self.envs_per_learner
+        scratch = None
+        if self.n_step > 1:                        # every learner converts through one shared scratch ring (Agent.populate_memory_nstep)
+            m = env.maxsteps - self.n_step + 1
+            if m < 1:
+                raise ValueError(f"populate_memory: num_steps = {env.maxsteps} < n_step = {self.n_step}: an episode must hold one full window")
+            scratch = ReplayRing(min(E, -(-self.capacity // m)) * env.maxsteps, device=self.device)
         for l, (ag, ring) in enumerate(zip(self.learners, self.rings)):
-            ag.populate_memory(env.slice(l * E, E), ring, seed=seed + l)
+            if self.n_step > 1:
+                ag.populate_memory_nstep(env.slice(l * E, E), ring, seed=seed + l, scratch=scratch)
+            else:
+                ag.populate_memory(env.slice(l * E, E), ring, seed=seed + l)
         return self
 
     def min_max_buffer(self, count=None, seed=None):
@@ -553,6 +632,12 @@ class LearnerGroup:
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
         r0 = self._ring0()
         w = RingWindow(*window) if window is not None else None
+        if w is not None and self.n_step > 1:      # the stationary window into the staging rings; nstep_fold pushes and counts
+            if w.offset != 0 or not 1 <= w.count <= min(epl, self.capacity):
+                raise ValueError(f"act_step: an n_step = {self.n_step} group remembers the stationary window (count, 0) of ring_window, "
+                                 f"count in 1 .. min(envs_per_learner, capacity); got count {w.count}, offset {w.offset}")
+            r0, w = self.stage_of(0).struct(), RingWindow(0, w.count, 0)
+            self._ns_window = int(w.count)
         ring_w = (C.byref(r0), C.byref(w)) if w is not None else (None, None)
         if self._x:
             if w is not None and w.count > min(self.mem_sizes):
@@ -582,7 +667,7 @@ class LearnerGroup:
             else:
                 _capi.check(self.L.shems_act_step_group_dev(C.byref(v), C.byref(p), C.byref(g), t, self._hp_ptr(), ptr(a_out), ptr(returns_acc), *ring_w,
                                                             self._stream()))
-        if w is not None:
+        if w is not None and self.n_step == 1:
             for ring in self.rings:
                 ring.pushed += int(window[1])
             if self._x and int(window[1]) > 0:     # the device counters follow on the stream, after the launch that read them
@@ -641,7 +726,8 @@ class LearnerGroup:
         off a policy step; every other field comes from the checked records)."""
         tau = float(np.float32(tau))
         if tau not in self._hp_variants:
-            arr = (HParams * self.count)(*[HParams(r["eta_act"], r["eta_crit"], r["gamma"], tau, r["mu"], r["sigma"], r["batch"], 0) for r in self.hparams])
+            arr = (HParams * self.count)(*[HParams(r["eta_act"], r["eta_crit"], nstep_gamma(r["gamma"], self.n_step), tau, r["mu"], r["sigma"],
+                                                   r["batch"], 0) for r in self.hparams])
             if check and self.L.shems_group_hparams_check(arr, self.count) != _capi.OK:
                 raise ValueError(self.L.shems_last_error().decode("utf-8", "replace"))
             self._hp_variants[tau] = self.torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
@@ -733,6 +819,8 @@ class LearnerGroup:
         wc = min(E, max(1, smallest // int(num_steps))) if window_count is None else int(window_count)
         if not 1 <= wc <= E:
             raise ValueError("window_count must be in 1 .. envs_per_learner")
+        if getattr(self, "n_step", 1) > 1:         # n-step: the same households every hour, so that the history follows them
+            return wc, 0
         return wc, (0 if wc == 1 else (self.tick * wc) % E)
 
     def episode_(self, env, train=True, num_steps=None, rng_ep=0, episode=0, window_count=None, noise_acc=None):
@@ -741,12 +829,20 @@ class LearnerGroup:
         noise_acc: float32 [count * E] device tensor that accumulates every env's act() noise mean (Agent.last_noise)."""
         t = self.torch
         num_steps = env.maxsteps if num_steps is None else int(num_steps)
+        if train and self.n_step > 1:
+            if num_steps < self.n_step:
+                raise ValueError(f"episode_: num_steps = {num_steps} < n_step = {self.n_step}: an episode must hold one full window")
+            if len(self.rings[0]) == 0:
+                raise ValueError(f"episode_: n_step = {self.n_step} on empty rings: the first {self.n_step - 1} hours of an episode push "
+                                 "nothing, so the updates of those hours need filled rings (populate_memory)")
         env.reset_(rng_ep, episode=episode) if rng_ep != -1 else env.reset_(-1)
         returns = t.zeros(env.n, dtype=t.float64, device=self.device)
         for step in range(num_steps):
             tick = (int(episode) * 4096 + step) & 0xFFFFFFFF
             win = (self.rings[0].pos, *self.ring_window(num_steps, window_count)) if train else None
             self.act_step(env, train=train, tick=tick, returns_acc=returns, window=win, noise_acc=noise_acc)
+            if train and self.n_step > 1:
+                self.nstep_fold(step)
             if train:
                 self.replay()
             self.tick += 1

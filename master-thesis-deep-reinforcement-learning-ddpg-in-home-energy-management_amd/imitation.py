@@ -285,6 +285,15 @@ def transitions(values, results, ring, problem_of_pass=None, mode="td", gamma=No
     return d_ret.cpu().numpy() if d_ret is not None else None
 
 
+def _refuse_n_step(what, learner):
+    """The warm start seeds ONE-step transitions and fits the critic on them: an n-step learner (Agent / LearnerGroup(n_step > 1)), whose
+    every update bootstraps with gamma^n, is refused by name before anything is trained."""
+    n = int(getattr(learner, "n_step", 1))
+    if n > 1:
+        raise NotImplementedError(f"{what}: n_step = {n}: the warm start's transitions are one-step (s, a, r, s'), which this learner's "
+                                  f"updates would bootstrap with gamma^{n}; nothing was trained")
+
+
 def warm_start(agent, env, values, demos, ring, rounds, steps_per_round, critic_steps, mode="mc", tau=1.0):
     """A cloned actor AND a critic that knows it: dagger(agent, env, values, demos, rounds, steps_per_round, tau) as it stands, then
     one pass of the resulting actor (harness.inference), its transitions into `ring` in `mode`, and `critic_steps` critic-only updates
@@ -296,6 +305,7 @@ def warm_start(agent, env, values, demos, ring, rounds, steps_per_round, critic_
     Returns dagger's per-round records followed by one dict {"critic_loss_first", "critic_loss_last", "transitions"}: losses[0]
     after the first and the last critic step, and the ring's length."""
     from . import harness
+    _refuse_n_step("warm_start", agent)
     critic_steps = int(critic_steps)
     if critic_steps < 1:
         raise ValueError(f"warm_start: {critic_steps} critic steps; at least one")
@@ -391,6 +401,7 @@ def warm_start_group(grp, env, values, demos, ring, rounds, steps_per_round, cri
     An "mc" ring (done = 1, returns as rewards) must not be the ring bootstrapped training samples: the group's own rings are refused.
     Returns dagger_group's per-round records followed by one dict {"critic_loss_first", "critic_loss_last"} ([count] arrays:
     losses[0] after the first and the last critic step) and "transitions" (the rings' shared length)."""
+    _refuse_n_step("warm_start_group", grp)
     if not getattr(grp, "has_evaluate", True):                 # (before dagger_group trains anything: a group without the critic-only update)
         raise NotImplementedError(f"warm_start_group: {type(grp).__name__} has no evaluate() -- the critic-only update of ONE critic -- so "
                                   "its critics cannot be fitted here; nothing was trained")

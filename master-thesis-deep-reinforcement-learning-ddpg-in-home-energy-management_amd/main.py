@@ -24,6 +24,8 @@ Differences that follow from the platform, all explicit:
     defaults 2, 0.2, 0.5) and appends _td3-d<d>-s<sigma>-c<clip> to <case>; unset or `ddpg`: today's bytes and file names;
   * SHEMS_REPLAY=per[:alpha[:beta0]] trains from a replay.PrioritizedRing (proportional prioritized replay, beta annealed from beta0
     to 1 over the run; defaults 0.6, 0.4) and appends _per-a<alpha>-b<beta0> to <case>; unset or `uniform`: today's bytes and names;
+  * SHEMS_NSTEP=<n> (1 .. 16) trains on multi-step returns (Agent(n_step=n): n-step transitions, y = G + gamma^n q') and appends _n<n>
+    to <case>, behind the suffixes above; it combines with SHEMS_ALGO=td3 and SHEMS_REPLAY=per; unset or 1: today's bytes and names;
   * SHEMS_FORESIGHT=1 adds, after the tracking block, the perfect-foresight pass over the tracked data set (foresight.py):
     out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight"; with it,
     SHEMS_FORESIGHT_HORIZON (hours of forecast: one integer or a comma list) and SHEMS_FORESIGHT_CONTROL (hours between plans,
@@ -231,6 +233,26 @@ def replay_case_suffix(alpha, beta0):
     return f"_per-a{float(alpha):g}-b{float(beta0):g}"
 
 
+def parse_nstep(value):
+    """SHEMS_NSTEP -> the steps of a multi-step return: 1 when unset or "1" (today's bytes and file names), else an integer in 2 .. 16
+    (replay.NSTEP_MAX).  Anything else is refused by name."""
+    if value is None:
+        return 1
+    raw = str(value).strip()
+    if not (raw.isascii() and raw.isdigit()) or not 1 <= int(raw) <= 16:
+        raise ValueError(f"SHEMS_NSTEP = {value!r} is not an integer in 1 .. 16")
+    return int(raw)
+
+
+def nstep_case_suffix(n_step):
+    """What the entry script appends to its `case` string for an n-step run, behind the algorithm's and the replay's suffixes."""
+    return "" if int(n_step) == 1 else f"_n{int(n_step)}"
+
+
+def nstep_from_env(environ=os.environ):
+    return parse_nstep(environ.get("SHEMS_NSTEP"))
+
+
 def replay_from_env(environ=os.environ):
     return parse_replay(environ.get("SHEMS_REPLAY"))
 
@@ -408,6 +430,13 @@ def main(environ=os.environ, cwd=".", log=print):
             raise ValueError(f"SHEMS_REPLAY=per: the prioritized update holds networks up to (250, 500), batches up to 128 and no parameter "
                              f"noise, not ({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE} with noise_type = {cfg.noise_type!r}")
         cfg.algo_suffix += replay_case_suffix(**per_hp)
+    n_step = nstep_from_env(environ)
+    cfg.algo_suffix += nstep_case_suffix(n_step)
+    if n_step > 1 and environ.get("SHEMS_FORESIGHT_WARMSTART") is not None:
+        raise NotImplementedError(f"SHEMS_NSTEP = {n_step} with SHEMS_FORESIGHT_WARMSTART: the warm start seeds the ring with one-step "
+                                  "transitions, which an n-step learner would bootstrap with gamma^n")
+    if n_step > EP_LENGTH["train"]:
+        raise ValueError(f"SHEMS_NSTEP = {n_step}: a training episode of {EP_LENGTH['train']} hours holds no full window")
     horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
     forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
     regret = foresight_regret(environ)
@@ -448,10 +477,10 @@ def main(environ=os.environ, cwd=".", log=print):
     D.GAMMA, D.TAU = cfg.gamma, cfg.tau
     if algo == "td3":
         agent = T.TD3Agent(seed=cfg.rng_run, sigma=cfg.noise_act if cfg.noise_type == "gn" else cfg.sigma, noise_type=cfg.noise_type,
-                           theta=cfg.theta, hidden=(cfg.L1, cfg.L2), **td3_hp)
+                           theta=cfg.theta, hidden=(cfg.L1, cfg.L2), n_step=n_step, **td3_hp)
     else:
         agent = D.Agent(seed=cfg.rng_run, sigma=cfg.noise_act if cfg.noise_type == "gn" else cfg.sigma, noise_type=cfg.noise_type,
-                        theta=cfg.theta, hidden=(cfg.L1, cfg.L2))
+                        theta=cfg.theta, hidden=(cfg.L1, cfg.L2), n_step=n_step)
     agent.gamma, agent.tau, agent.batch = float(np.float32(cfg.gamma)), float(np.float32(cfg.tau)), cfg.BATCH_SIZE
     agent.eta_act, agent.eta_crit = float(np.float32(cfg.eta_act)), float(np.float32(cfg.eta_crit))
     ring = D.PrioritizedRing(cfg.MEM_SIZE, alpha=per_hp["alpha"], beta=per_hp["beta0"]) if replay_kind == "per" else D.ReplayRing(cfg.MEM_SIZE)

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
+
 from . import _capi
 
 
@@ -98,3 +100,82 @@ class PrioritizedRing(ReplayRing):
 
     def per_struct(self):
         return PerArgs(self.prio.data_ptr(), self.pmax.data_ptr(), self.ws.data_ptr(), self.alpha, self.beta, self.eps, 0)
+
+
+# ---- multi-step (n-step) returns (include/shems_hip.h) -------------------------------------------------------------------
+NSTEP_MAX = _capi.NSTEP_MAX
+
+
+def check_n_step(n_step, what="n_step"):
+    """1 <= n_step <= NSTEP_MAX, an integer: refused by name.  Host only."""
+    if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or not 1 <= int(n_step) <= NSTEP_MAX:
+        raise ValueError(f"{what} = {n_step!r}: the steps of a multi-step return are an integer in 1 .. {NSTEP_MAX}")
+    return int(n_step)
+
+
+def nstep_gamma(gamma, n):
+    """gamma_n = float32(g64 * g64 * ... * g64), g64 = float64(float32(gamma)), n factors multiplied left to right in float64: the discount
+    every update of an n-step learner bootstraps with.  Computed on the host, once; there is no device pow.  nstep_gamma(g, 1) ==
+    float32(g)."""
+    n = check_n_step(n, "n")
+    g = float(np.float32(gamma))
+    p = g
+    for _ in range(n - 1):
+        p = p * g
+    return float(np.float32(p))
+
+
+class NStepWindow:
+    """What an n-step learner keeps beside its ring: the staging ring the unchanged fused step writes the one-step transitions of the
+    stationary window of households [0, window_count) into (`window`: the step's shems_ring_window), and the history hist_s / hist_a /
+    hist_r [n][window_count][9 | 2 | 1] of the current episode.  fold(ring, hour) runs shems_nstep_fold_dev behind the step of hour
+    `hour` (counted from the episode's reset): from hour n - 1 on it pushes window_count n-step transitions at ring.pos and advances
+    ring.pushed; before that it only records history.  gamma: the one-step discount; gamma_n: what the updates bootstrap with."""
+
+    def __init__(self, n, window_count, gamma, device=None):
+        import torch
+        self.n, self.window_count = check_n_step(n, "n"), int(window_count)
+        if self.window_count < 1:
+            raise ValueError(f"NStepWindow: window_count = {window_count!r} must be >= 1")
+        self.gamma = float(np.float32(gamma))
+        self.gamma_n = nstep_gamma(self.gamma, self.n)
+        self.stage = ReplayRing(self.window_count, device=device)
+        self.device = self.stage.device
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.hist_s, self.hist_a = z(self.n, self.window_count, _capi.NSTATE), z(self.n, self.window_count, _capi.NACTION)
+        self.hist_r = z(self.n, self.window_count)
+        self.window = (0, self.window_count, 0)     # shems_ring_window of the step that fills the staging ring
+        self._L = _capi.declare_nstep()
+
+    def struct(self):
+        return _capi.NStepArgs(self.n, 0, self.window_count, self.gamma, 0, self.hist_s.data_ptr(), self.hist_a.data_ptr(), self.hist_r.data_ptr())
+
+    def fold(self, ring, hour, stream=None):
+        """Returns True when the fold pushed (hour >= n - 1)."""
+        import torch
+        if ring.capacity < self.window_count:
+            raise ValueError(f"NStepWindow.fold: a ring of {ring.capacity} slots cannot take {self.window_count} transitions per step")
+        if ring.s.device != self.device:
+            raise ValueError(f"NStepWindow.fold: the ring lives on {ring.s.device}, the window on {self.device}")
+        ns, ss, rs = self.struct(), self.stage.struct(), ring.struct()
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if stream is None else stream
+        _capi.check(self._L.shems_nstep_fold_dev(C.byref(ns), C.byref(ss), C.byref(rs), ring.pos, int(hour), st))
+        pushed = int(hour) >= self.n - 1
+        if pushed:
+            ring.pushed += self.window_count
+        return pushed
+
+
+def nstep_from_episodes(src, episodes, steps, n, gamma, ring, stream=None):
+    """shems_nstep_from_episodes_dev: `episodes` episodes of `steps` one-step transitions in src (episode e's hour t at slot e * steps + t)
+    become episodes * (steps - n + 1) n-step pushes at ring.pos; ring.pushed advances by that many."""
+    import torch
+    n = check_n_step(n, "n")
+    if int(steps) < n:
+        raise ValueError(f"nstep_from_episodes: episodes of {steps} hours hold no window of n = {n} steps")
+    L = _capi.declare_nstep()
+    ss, rs = src.struct(), ring.struct()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if stream is None else stream
+    _capi.check(L.shems_nstep_from_episodes_dev(C.byref(ss), int(episodes), int(steps), n, float(np.float32(gamma)), C.byref(rs), ring.pos, st))
+    ring.pushed += int(episodes) * (int(steps) - n + 1)
+    return ring
