@@ -1057,6 +1057,63 @@ int shems_nstep_group_fold_dev(const shems_nstep *ns0, const shems_replay *stage
 int shems_nstep_from_episodes_dev(const shems_replay *src, int64_t episodes, int64_t steps, int32_t n, float gamma,
                                   const shems_replay *ring, int64_t ring_pos, void *stream);
 
+/* ------------------------------------------ population-based training of a learner group -- */
+/* Exploit and explore (Jaderberg et al. 2017) on the device, after an evaluation sweep (csrc/shems_pbt_core.h holds the
+ * arithmetic once for host and device).  A POPULATION is the set of learners with the same id in pop[count]; selection never crosses
+ * populations.  One ROUND, per population of size P with quota q = (P * permille) / 1000 in integers (permille 1 .. 500, so 2 q <= P):
+ *   order    a is better than b if a's score is finite and b's is not, or both are finite and score_a > score_b; on equal scores, or
+ *            two non-finite ones, the lower learner index is better.  rank[l] = learners of l's population that are better than l.
+ *   exploit  learners with rank >= P - q are children.  Child l draws ONE Philox4x32-10 block, counter (l, round, 0, kStreamPbt), key =
+ *            the two halves of seed (low word first); its parent is the learner of rank j = (uint64(x) * q) >> 32 of its population
+ *            (always one of the q best).  A parent whose score is not finite: the child keeps itself.  parent[l] = l for every kept
+ *            learner; q = 0 changes nothing.  Parents and children are disjoint sets, so nothing is read and written in one round.
+ *   explore  the child's record becomes the parent's WHOLE record (eta_*, gamma, tau, noise_mu, noise_sigma, batch); then, for every
+ *            field enabled in `fields`, one bit of the block's word y picks the factor f -- set: up, clear: down:
+ *                eta' = (double)(float)(eta * f)      (eta is the Float64 value of a Float32)
+ *                x'   = (float)((double) x * f)       (tau, noise_sigma)
+ *            and the result is clamped to [lo, hi] of that field.  A parent's record is never written in the round.
+ * What the copy moves from parent to child is the caller's list of ranges of a learner's slab; the Python group copies the
+ * parameters, targets, ADAM moments and tiled regions, s_min and s_max -- never the ring, the priorities, the n-step history, the
+ * gradients, the workspaces or the random streams. */
+#define SHEMS_PBT_FIELDS 4
+#define SHEMS_PBT_MAX_RANGES 8
+#define SHEMS_PBT_MAX_COUNT 4096     /* select: the counting loops are O(count^2) per child */
+#define SHEMS_PBT_CHUNK_VECS 2048    /* copy: 16-byte vectors one workgroup moves (32 KB)     */
+enum { SHEMS_PBT_ETA_ACT = 1, SHEMS_PBT_ETA_CRIT = 2, SHEMS_PBT_TAU = 4, SHEMS_PBT_SIGMA = 8 };
+typedef struct shems_pbt_params {
+    uint64_t seed;                       /* Philox key                                              */
+    uint32_t round;                      /* counter word 1: a round never repeats a draw            */
+    int32_t  permille;                   /* truncation in thousandths, 1 .. 500                     */
+    uint32_t fields;                     /* SHEMS_PBT_* bits: the fields explore perturbs           */
+    int32_t  reserved;                   /* 0                                                       */
+    double   down, up;                   /* the two factors, finite and > 0                         */
+    double   lo[SHEMS_PBT_FIELDS];       /* clamp bounds per field, in the order of the bits        */
+    double   hi[SHEMS_PBT_FIELDS];
+} shems_pbt_params;                      /* 104 bytes */
+typedef struct shems_pbt_range {
+    int64_t offset_floats;               /* from the start of a learner's slab; a multiple of 4     */
+    int64_t floats;                      /* a multiple of 4; 0 = nothing                            */
+} shems_pbt_range;
+/* Host only: permille in 1 .. 500, no unknown bit in fields, reserved 0, down and up finite and > 0, and for all four fields lo <= hi,
+ * both finite Float32 values under which a clamped value passes shems_group_hparams_check: eta lo > 0, tau in (0, 1], sigma lo >= 0.
+ * SHEMS_ERR_ARG names the first bad item. */
+int shems_pbt_params_check(const shems_pbt_params *params);
+/* k_pbt_select, one thread per learner: rank, parent and the children's new records IN PLACE in d_hp; d_parent and d_rank [count] int32
+ * receive every learner's parent and rank.  d_pop [count] int32, d_score [count] double, d_hp [count] records, all device memory; params
+ * is host memory.  SHEMS_ERR_ARG, nothing launched: a NULL, count outside 1 .. SHEMS_PBT_MAX_COUNT, whatever shems_pbt_params_check
+ * refuses, d_hp or d_score not 8-byte aligned, d_pop / d_parent / d_rank not 4-byte aligned. */
+int shems_pbt_select_dev(const shems_pbt_params *params, int32_t count, const int32_t *d_pop, const double *d_score,
+                         shems_group_hparams *d_hp, int32_t *d_parent, int32_t *d_rank, void *stream);
+/* k_pbt_copy: for every learner l with d_parent[l] != l, the `n_ranges` ranges (HOST array, passed to the kernel by value) are copied
+ * from slab0 + parent * g->stride_bytes to slab0 + l * g->stride_bytes.  grid = (chunks of SHEMS_PBT_CHUNK_VECS vectors over the
+ * concatenated ranges, learner); a kept learner's workgroups exit at once; the others move 16-byte vectors with non-temporal loads and
+ * stores.  No LDS, no atomics.  A d_parent entry outside 0 .. count - 1, or one that names a learner which is itself a child, leaves that
+ * learner untouched (no slab is read and written in one launch).  SHEMS_ERR_ARG, nothing launched: a NULL, g->count outside 1 .. 65535,
+ * stride_bytes not a positive multiple of 16, slab0 not 16-byte aligned, n_ranges outside 1 .. SHEMS_PBT_MAX_RANGES, a range with a
+ * negative number or one that is no multiple of 4, a range past stride_bytes, all ranges empty. */
+int shems_pbt_copy_dev(float *slab0, const shems_group *g, const shems_pbt_range *ranges, int32_t n_ranges, const int32_t *d_parent,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ UNITS = [
     ("shems_train.hip", []),
     ("shems_dp.hip", []),
     ("shems_nstep.hip", ["-ffp-contract=off"]),
+    ("shems_pbt.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
           "-I" + os.path.join(ROOT, "include")]

@@ -182,6 +182,45 @@ def declare_nstep():
     return L
 
 
+PBT_FIELDS, PBT_MAX_RANGES, PBT_MAX_COUNT, PBT_CHUNK_VECS = 4, 8, 4096, 2048       # SHEMS_PBT_*
+
+
+class PbtParams(C.Structure):          # shems_pbt_params
+    _fields_ = [("seed", C.c_uint64), ("round", C.c_uint32), ("permille", C.c_int32), ("fields", C.c_uint32), ("reserved", C.c_int32),
+                ("down", C.c_double), ("up", C.c_double), ("lo", C.c_double * PBT_FIELDS), ("hi", C.c_double * PBT_FIELDS)]
+
+
+class PbtRange(C.Structure):           # shems_pbt_range
+    _fields_ = [("offset_floats", C.c_int64), ("floats", C.c_int64)]
+
+
+assert C.sizeof(PbtParams) == 104 and C.sizeof(PbtRange) == 16
+
+
+def _pbt_sigs():
+    """Population-based training (shems_group * and the record array go as void pointers: their mirrors live in group.py)."""
+    vp, i32 = C.c_void_p, C.c_int32
+    PP = C.POINTER(PbtParams)
+    return {
+        "shems_pbt_params_check": [PP],
+        "shems_pbt_select_dev": [PP, i32, vp, vp, vp, vp, vp, vp],
+        "shems_pbt_copy_dev": [vp, vp, C.POINTER(PbtRange), i32, vp, vp],
+    }
+
+
+def declare_pbt():
+    """The prototypes of _pbt_sigs (compared with include/shems_hip.h by tests/test_pbt_host.py)."""
+    L = lib()
+    if getattr(L, "_pbt_declared", False):
+        return L
+    for name, args in _pbt_sigs().items():
+        fn = getattr(L, name)
+        fn.argtypes = args
+        fn.restype = C.c_int
+    L._pbt_declared = True
+    return L
+
+
 def exported_symbols():
     """Names include/shems_hip.h declares (used by the CPU-side ABI test)."""
     import re

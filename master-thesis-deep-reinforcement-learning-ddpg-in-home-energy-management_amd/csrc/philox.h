@@ -37,7 +37,8 @@ PHILOX_HD u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3
 enum : uint32_t { kStreamReset = 0x52455345u, kStreamRandAct = 0x52414354u, kStreamNoise = 0x4E4F4953u,
                   kStreamSample = 0x53414D50u, kStreamInit = 0x494E4954u,
                   kStreamTarget = 0x5452474Eu,     // TD3's target-policy noise (shems_td3_core.h): never the act noise's counter
-                  kStreamPer = 0x50455253u };      // the prioritized sampler's stratified draw (shems_per_core.h): never kStreamSample
+                  kStreamPer = 0x50455253u,        // the prioritized sampler's stratified draw (shems_per_core.h): never kStreamSample
+                  kStreamPbt = 0x5042545Fu };      // population-based training's parent and factor draw (shems_pbt_core.h)
 
 PHILOX_HD float u01_24(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }   // [0,1), exact in f32
 

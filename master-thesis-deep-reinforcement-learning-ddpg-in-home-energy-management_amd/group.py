@@ -136,6 +136,86 @@ def nstep_group_refusals(form, noise_type, sized):
                                   "the fold does not keep (the rings advance in lockstep)")
 
 
+PBT_FIELD_BITS = {"eta_act": 1, "eta_crit": 2, "tau": 4, "sigma": 8}       # SHEMS_PBT_*: bit k of the mask and of the draw's word y
+PBT_DEFAULT_BOUNDS = {"eta_act": (1e-6, 1e-1), "eta_crit": (1e-6, 1e-1), "tau": (1e-4, 1.0), "sigma": (0.0, 10.0)}
+
+
+class PBT:
+    """The settings of population-based training of a learner group (Jaderberg et al. 2017; include/shems_hip.h), for
+    LearnerGroup.pbt_round and run_episodes(pbt=...).  Host only: nothing here touches the device.
+    populations: one id per learner; selection never crosses populations (the learners of one charger, say).
+    truncation:  the share of a population that is replaced per round, and the share it draws parents from, in (0, 0.5]; kept as
+                 permille = round(1000 * truncation), the quota of a population of P learners being (P * permille) // 1000.
+    fields:      what explore perturbs, of "eta_act", "eta_crit", "tau", "sigma"; each by the factor `up` or `down`, picked by one
+                 random bit per field, then clamped to bounds[field] = (lo, hi) (Float32 values; defaults PBT_DEFAULT_BOUNDS).
+    seed:        the Philox key of the draws; None = the group's rng_seed.
+    start:       run_episodes runs a round after the sweep of episode i when start <= i < num_ep; None = test_every + 1."""
+
+    def __init__(self, populations, truncation=0.25, fields=("eta_act", "eta_crit", "tau", "sigma"), down=0.8, up=1.2, bounds=None,
+                 seed=None, start=None):
+        pop = np.asarray(list(populations))
+        if pop.ndim != 1 or pop.size < 1 or pop.dtype.kind not in "iu":
+            raise ValueError("population-based training: populations must be one integer id per learner")
+        self.populations = pop.astype(np.int32)
+        if not (isinstance(truncation, (int, float)) and 0.0 < float(truncation) <= 0.5):
+            raise ValueError(f"population-based training: truncation = {truncation!r} outside (0, 0.5]: the parents and the children of a "
+                             "round must be disjoint")
+        self.truncation = float(truncation)
+        self.permille = min(500, max(1, int(round(1000.0 * self.truncation))))
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        for f in fields:
+            if f not in PBT_FIELD_BITS:
+                raise ValueError(f"population-based training: unknown field {f!r} (explore perturbs {', '.join(PBT_FIELD_BITS)})")
+        self.fields = tuple(f for f in PBT_FIELD_BITS if f in fields)
+        self.mask = sum(PBT_FIELD_BITS[f] for f in self.fields)
+        self.down, self.up = float(down), float(up)
+        b = dict(PBT_DEFAULT_BOUNDS)
+        for f, lh in (bounds or {}).items():
+            if f not in PBT_FIELD_BITS:
+                raise ValueError(f"population-based training: bounds: unknown field {f!r} (explore perturbs {', '.join(PBT_FIELD_BITS)})")
+            b[f] = (float(lh[0]), float(lh[1]))
+        self.bounds = {f: (float(np.float32(lo)), float(np.float32(hi))) for f, (lo, hi) in b.items()}
+        self.seed = None if seed is None else int(seed)
+        self.start = None if start is None else int(start)
+        self.params(0, 0)                              # (refuses bad factors and bounds now, by shems_pbt_params_check's message)
+
+    def params(self, round, default_seed):
+        """The shems_pbt_params of round `round`, checked by shems_pbt_params_check."""
+        seed = default_seed if self.seed is None else self.seed
+        lo = (C.c_double * 4)(*[self.bounds[f][0] for f in PBT_FIELD_BITS])
+        hi = (C.c_double * 4)(*[self.bounds[f][1] for f in PBT_FIELD_BITS])
+        p = _capi.PbtParams(int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & 0xFFFFFFFF, self.permille, self.mask, 0, self.down, self.up, lo, hi)
+        L = _capi.declare_pbt()
+        if L.shems_pbt_params_check(C.byref(p)) != _capi.OK:
+            raise ValueError("population-based training: " + L.shems_last_error().decode("utf-8", "replace"))
+        return p
+
+
+def pbt_group_refusals(form, hparams, noise_type, sized, populations, count):
+    """What a group refuses of population-based training before any device work, each by name.  hparams: the group's full per-learner
+    mappings (LearnerGroup.hparams) or None; sized: a record carries its own mem_size."""
+    if form in ("latency", "wide"):
+        raise NotImplementedError(f"population-based training: form={form!r} keeps no per-learner records on the throughput path; the round "
+                                  "runs on a throughput group")
+    if hparams is None:
+        raise ValueError("population-based training: the group has no per-learner records to inherit and perturb: pass "
+                         "hparams=[{}] * count to LearnerGroup")
+    if noise_type == "ou":
+        raise NotImplementedError("population-based training: Ornstein-Uhlenbeck noise ('ou') runs on the *_x entry points, whose second "
+                                  "record array the round does not rewrite")
+    if sized:
+        raise NotImplementedError("population-based training: per-learner mem_size runs on the *_x entry points, whose second record array "
+                                  "the round does not rewrite")
+    pop = np.asarray(populations)
+    if pop.shape != (int(count),):
+        raise ValueError(f"population-based training: populations holds {pop.size} ids for a group of {count} learners")
+    for k in sorted(set(pop.tolist())):
+        hid = sorted({tuple(hparams[l]["hidden"]) for l in np.flatnonzero(pop == k)})
+        if len(hid) > 1:
+            raise ValueError(f"population-based training: population {k} mixes hidden sizes {hid}: a smaller network's zero padding would not "
+                             "survive the copy of a wider parent")
+
+
 def _xparams_records(full, capacity, dt):
     """The XParams array beside the HParams of _hparams_records' full dicts, through shems_group_xparams_check.  Host only."""
     arr = (XParams * len(full))(*[XParams(r["theta"], float(np.float32(dt)), r["mem_size"], 0) for r in full])
@@ -477,6 +557,77 @@ class LearnerGroup:
         """(name, floats) blocks a subclass keeps in every learner's slab, carved after ring_done (td3.TD3LearnerGroup: the second
         critic).  Called once by __init__ after form / tiled are decided."""
         return ()
+
+    # ---- population-based training (include/shems_hip.h, DESIGN.md 4s) ---------------------------------------------------------------
+    def _pbt_blocks(self):
+        """Names of the subclass's slab blocks a child inherits from its parent besides the LearnerGroup's own (td3.TD3LearnerGroup: the
+        second critic's parameters, target, moments and tiles)."""
+        return ()
+
+    def pbt_ranges(self):
+        """The (float offset, floats) ranges of a learner's slab that a child takes over from its parent, adjacent ones merged: the
+        contiguous prefix actor .. w2t_critic (parameters, targets, ADAM moments, both tiled regions), s_min and s_max, and the blocks of
+        _pbt_blocks().  Never the gradients, workspaces, losses, the ring, priorities or the n-step staging and history.  Host only."""
+        lay = self.layout
+        spans = [(0, lay["grad_actor"][0]), (lay["s_min"][0], lay["losses"][0] - lay["s_min"][0])]
+        spans += [(lay[name][0], _pad4(lay[name][1])) for name in self._pbt_blocks()]
+        merged = []
+        for o, n in sorted(s for s in spans if s[1] > 0):
+            if merged and merged[-1][0] + merged[-1][1] == o:
+                merged[-1] = (merged[-1][0], merged[-1][1] + n)
+            else:
+                merged.append((o, n))
+        if len(merged) > _capi.PBT_MAX_RANGES:
+            raise ValueError(f"pbt_ranges: {len(merged)} ranges; one copy launch takes {_capi.PBT_MAX_RANGES}")
+        return merged
+
+    def pbt_round(self, scores, pbt, round):
+        """One round of population-based training on `scores` (float64 [count], a device tensor such as GroupRun._score, or anything
+        torch.as_tensor takes): two launches with no host decision in between -- shems_pbt_select_dev ranks every population, draws each
+        child's parent and writes the child's inherited and perturbed record in place; shems_pbt_copy_dev moves pbt_ranges() from every
+        parent's slab to its children's -- then ONE small copy brings the records and `parent` back and every host mirror follows:
+        hparams[l] (gamma from the parent's mapping: the record holds gamma^n), learners[l].eta_act / eta_crit / tau / sigma / mu /
+        batch / gamma, the host records, an n-step group's one-step discounts; the record variants of clone / evaluate / TD3's hold are
+        dropped and rebuilt from the new values when next asked for.  A child keeps its own ring (and priorities, n-step history,
+        workspaces, random streams: it goes on with seed + l); both layouts of the layer-2 state are copied, so flux_() state is as
+        before.  Returns parent, int32 [count] (parent[l] == l: kept)."""
+        pbt_group_refusals(self.form, self.hparams, self.noise_type, self._x, pbt.populations, self.count)
+        t = self.torch
+        LB = _capi.declare_pbt()
+        st = getattr(self, "_pbt_dev", None)
+        if st is None or st[0] is not pbt:             # the population ids and the two outputs, once per PBT object
+            ranges = self.pbt_ranges()
+            st = (pbt, t.from_numpy(pbt.populations.copy()).to(self.device), t.zeros(self.count, dtype=t.int32, device=self.device),
+                  t.zeros(self.count, dtype=t.int32, device=self.device), (_capi.PbtRange * len(ranges))(*[_capi.PbtRange(o, n) for o, n in ranges]))
+            self._pbt_dev = st
+        _, d_pop, d_parent, d_rank, ranges = st
+        sc = t.as_tensor(scores, dtype=t.float64).to(self.device).contiguous()
+        if sc.shape != (self.count,):
+            raise ValueError(f"pbt_round: scores must hold one float64 per learner ({self.count}), got {tuple(sc.shape)}")
+        params, g = pbt.params(round, self.rng_seed), self.struct()
+        ptr = lambda x: C.c_void_p(x.data_ptr())
+        _capi.check(LB.shems_pbt_select_dev(C.byref(params), self.count, ptr(d_pop), ptr(sc), self._hp_ptr(), ptr(d_parent), ptr(d_rank),
+                                            self._stream()))
+        _capi.check(LB.shems_pbt_copy_dev(ptr(self.slab), C.byref(g), ranges, len(ranges), ptr(d_parent), self._stream()))
+        host = t.cat([self._hp_dev, d_parent.view(t.uint8)]).cpu().numpy()                 # the round's one copy
+        nb = C.sizeof(HParams) * self.count
+        recs = (HParams * self.count).from_buffer_copy(host[:nb].tobytes())
+        parent = host[nb:].view(np.int32).copy()
+        old = [dict(h) for h in self.hparams]
+        for l in np.flatnonzero(parent != np.arange(self.count)):
+            l, r = int(l), recs[int(l)]
+            h = dict(self.hparams[l], gamma=old[int(parent[l])]["gamma"], eta_act=r.eta_act, eta_crit=r.eta_crit, tau=float(r.tau),
+                     sigma=float(r.noise_sigma), mu=float(r.noise_mu), batch=int(r.batch))
+            self.hparams[l] = h
+            ag = self.learners[l]
+            ag.gamma, ag.tau, ag.batch, ag.eta_act, ag.eta_crit = h["gamma"], h["tau"], h["batch"], h["eta_act"], h["eta_crit"]
+            ag.sigma, ag.mu = h["sigma"], h["mu"]
+        self._hp_host = recs
+        if self._gamma1_dev is not None:
+            self._gamma1_dev.copy_(t.tensor([h["gamma"] for h in self.hparams], dtype=t.float32))
+        self._hp_variants = {}
+        self.pbt_rank = d_rank                         # the last round's ranks (device int32 [count]), for a log
+        return parent
 
     def _hp_ptr(self):
         """The entry points' d_hp: the device records, or NULL (the shared values)."""
@@ -850,7 +1001,7 @@ class LearnerGroup:
 
     # ---- run_episodes (DDPG.jl:244-298) for every learner ----------------------------------------------------------------------------
     def run_episodes(self, env_train, env_eval, num_ep, test_every=100, test_runs=100, seed=None, window_count=None, on_eval=None,
-                     on_best=None):
+                     on_best=None, pbt=None):
         """Agent.run_episodes for every learner at once: `num_ep` training episodes (episode_ with rng_ep = seed, episode = i), and when
         i % test_every == 1 an evaluation sweep on env_eval (eval_batch: count blocks of E_eval envs, learner l's block on its charger):
         every block reset with the Agent's fixed key (SEED_INI, episode 0, env indices from 0 inside the block), 72 fused group steps
@@ -859,9 +1010,17 @@ class LearnerGroup:
         Per episode the learners' mean return and mean act() noise stay on the device (no host synchronisation); a sweep copies its
         scores to the host once, for on_eval(l, i, total_reward_l, score_l) (every learner) and on_best(l, i, best_actor_l,
         total_reward_l [i], score_mean_l [sweeps so far]) (the learners that improved; best_actor_l at the learner's own hidden size).
-        On return flux_() has run, so learners[l].export_actor() is the last actor.  Returns a GroupRun."""
+        On return flux_() has run, so learners[l].export_actor() is the last actor.  Returns a GroupRun.
+        pbt: a PBT -- after the sweep of episode i with pbt.start <= i < num_ep (start defaults to test_every + 1, so neither the sweep
+        of episode 1 nor a final sweep triggers one) pbt_round runs on that sweep's scores, round number = the sweep's index; the
+        GroupRun's pbt_parent [count][rounds], pbt_episodes and pbt_hparams (the records after each round) log it.  The best-actor
+        snapshot and best score stay the history of the SLOT: a child does not inherit its parent's."""
         E_eval = run_episodes_check(self.count, self.n_envs, getattr(env_train, "n", None), getattr(env_eval, "n", None), num_ep, test_every,
                                     test_runs)
+        if pbt is not None:
+            pbt_group_refusals(self.form, self.hparams, self.noise_type, self._x, pbt.populations, self.count)
+            pbt_start = int(test_every) + 1 if pbt.start is None else pbt.start
+            parents = []
         t = self.torch
         L, E, num_ep, test_every, test_runs = self.count, self.envs_per_learner, int(num_ep), int(test_every), int(test_runs)
         seed = self.seed if seed is None else int(seed)
@@ -894,6 +1053,10 @@ class LearnerGroup:
             res._score_mean[:, k] = res._score
             e1.record()
             sweeps.append((e0, e1))
+            if pbt is not None and pbt_start <= i < num_ep:
+                parents.append(self.pbt_round(res._score, pbt, k))
+                res.pbt_episodes.append(i)
+                res.pbt_hparams.append([dict(h) for h in self.hparams])
             if on_eval is None and on_best is None:
                 continue
             host = t.stack([res._score, res._improved.to(t.float64), res._total[:, i - 1].to(t.float64)]).cpu().numpy()    # the sweep's one copy
@@ -912,6 +1075,8 @@ class LearnerGroup:
         res.wall_ms = t_start.elapsed_time(t_end)
         res.sweep_ms = sum(a.elapsed_time(b) for a, b in sweeps)
         res.sweeps = len(sweeps)
+        if pbt is not None and parents:
+            res.pbt_parent = np.stack(parents, axis=1)
         self.flux_()
         return res
 
@@ -1109,15 +1274,16 @@ class PrioritizedLearnerGroup(LearnerGroup):
                                 noise_acc=noise_acc)
 
     def run_episodes(self, env_train, env_eval, num_ep, test_every=100, test_runs=100, seed=None, window_count=None, on_eval=None,
-                     on_best=None, anneal_beta_from=None):
+                     on_best=None, anneal_beta_from=None, pbt=None):
         """LearnerGroup.run_episodes on prioritized updates.  anneal_beta_from: beta of episode i is anneal_beta(anneal_beta_from, i - 1,
-        num_ep - 1): linear in the episode, exactly 1.0 in the last one (Agent.run_episodes' rule); None keeps `beta` as it stands."""
+        num_ep - 1): linear in the episode, exactly 1.0 in the last one (Agent.run_episodes' rule); None keeps `beta` as it stands.
+        pbt: as LearnerGroup.run_episodes; a child keeps its own ring, priorities and pmax."""
         if anneal_beta_from is not None:
             anneal_beta(anneal_beta_from, 0, 1)              # (refuses a beta0 outside [0, 1] before anything runs)
             self._anneal = (float(anneal_beta_from), int(num_ep))
         try:
             return super().run_episodes(env_train, env_eval, num_ep, test_every=test_every, test_runs=test_runs, seed=seed,
-                                        window_count=window_count, on_eval=on_eval, on_best=on_best)
+                                        window_count=window_count, on_eval=on_eval, on_best=on_best, pbt=pbt)
         finally:
             self._anneal = None
 
@@ -1160,6 +1326,8 @@ class GroupRun:
         self._improved = t.zeros(L, dtype=t.uint8, device=dev)
         self.wall_ms = self.sweep_ms = 0.0
         self.sweeps = 0
+        self.pbt_parent = np.zeros((L, 0), dtype=np.int32)         # run_episodes(pbt=...): parent[l] of every round (l itself: kept)
+        self.pbt_episodes, self.pbt_hparams = [], []               # the episodes whose sweeps ran a round; the records after each round
 
     total_reward = property(lambda self: self._total.cpu().numpy())          # [L][num_ep] float32
     noise_mean = property(lambda self: self._noise.cpu().numpy())            # [L][num_ep] float32

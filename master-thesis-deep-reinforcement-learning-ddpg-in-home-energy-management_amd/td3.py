@@ -175,6 +175,11 @@ class TD3LearnerGroup(G.LearnerGroup):
         _capi.check(_declare_group().shems_td3_group_workspace_floats(C.byref(nws)))
         return group_extra_blocks(n_critic, self.tiled, nws.value)
 
+    def _pbt_blocks(self):
+        """What a child of a population-based-training round inherits of the second critic: parameters, target, ADAM moments and, on the
+        tiled layout, its tiled region -- not grad_critic2, ws2 or losses2."""
+        return ("critic2", "critic2_t", "m_critic2", "v_critic2", "w2t_critic2")
+
     # ---- views ----
     def _view(self, l, name):
         o, n = self.layout[name]
