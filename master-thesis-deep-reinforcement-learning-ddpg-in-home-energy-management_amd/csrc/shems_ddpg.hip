@@ -2406,11 +2406,6 @@ int shems_ddpg_critic_update(const shems_ddpg *d, const shems_replay *ring, int6
 }
 
 /* ---- prioritized replay (shems_per_core.h) ---- */
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 // everything shems_ddpg_update refuses for (d, ring, ring_len), with nothing launched
 static int check_given(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, double bp1c, double bp2c, double bp1a, double bp2a,
                        const char *fn)
@@ -2421,32 +2416,6 @@ static int check_given(const shems_ddpg *d, const shems_replay *ring, int64_t ri
     if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
         return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
     return set_lds_attrs_per();
-}
-static int check_per(const shems_per *per, const shems_ddpg *d, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count,
-                     int32_t batch, const char *fn)
-{
-    if (!per || !per->prio || !per->pmax || !per->ws) return set_error(SHEMS_ERR_ARG, "%s: shems_per has a NULL buffer", fn);
-    if (capacity < 1 || capacity > kPerMaxSlots)
-        return set_error(SHEMS_ERR_ARG, "%s: a prioritized ring holds 1..%lld slots (got %lld)", fn, (long long)kPerMaxSlots, (long long)capacity);
-    if (ring_len < 1 || ring_len > capacity) return set_error(SHEMS_ERR_ARG, "%s: ring_len must be in 1..capacity", fn);
-    if (batch < 1 || batch > kPerCols) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, batch);
-    if (((uintptr_t)per->prio & 15) != 0 || ((uintptr_t)per->ws & 15) != 0 || ((uintptr_t)per->pmax & 3) != 0)
-        return set_error(SHEMS_ERR_ARG, "%s: prio and the workspace must be 16-byte aligned, pmax 4-byte aligned", fn);
-    const size_t np = (size_t)capacity * 4, nw = (size_t)per_ws_floats(capacity) * 4;
-    if (ranges_overlap(per->prio, np, per->ws, nw) || ranges_overlap(per->prio, np, per->pmax, 4) || ranges_overlap(per->ws, nw, per->pmax, 4))
-        return set_error(SHEMS_ERR_ARG, "%s: prio, pmax and the workspace overlap", fn);
-    if (d && d->ws && (ranges_overlap(per->prio, np, d->ws, (size_t)WS_FLOATS * 4) || ranges_overlap(per->ws, nw, d->ws, (size_t)WS_FLOATS * 4) ||
-                       ranges_overlap(per->pmax, 4, d->ws, (size_t)WS_FLOATS * 4)))
-        return set_error(SHEMS_ERR_ARG, "%s: the prioritized ring's arrays overlap the learner's workspace", fn);
-    for (const float v : {per->alpha, per->beta, per->eps_p})
-        if (!(v >= 0.0f) || !std::isfinite(v)) return set_error(SHEMS_ERR_ARG, "%s: alpha, beta and eps_p must be finite and >= 0", fn);
-    if (per->beta > 1.0f) return set_error(SHEMS_ERR_ARG, "%s: beta must be in [0, 1] (got %g)", fn, (double)per->beta);
-    if (fresh_pos < 0 || fresh_pos >= capacity || fresh_count < 0)
-        return set_error(SHEMS_ERR_ARG, "%s: the fresh range must start inside the ring and have a count >= 0", fn);
-    if (fresh_count > 0 && fresh_count < capacity && ring_len < capacity && fresh_pos + fresh_count > ring_len)
-        return set_error(SHEMS_ERR_ARG, "%s: the fresh range [%lld, +%lld) leaves the %lld filled slots", fn, (long long)fresh_pos,
-                         (long long)fresh_count, (long long)ring_len);
-    return SHEMS_OK;
 }
 static int per_sample_launch(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed,
                              uint32_t tick, int32_t batch, hipStream_t st)
@@ -2466,7 +2435,7 @@ int shems_per_workspace_floats(int64_t capacity, int64_t *out)
 int shems_per_sample_dev(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed,
                          uint32_t tick, int32_t batch, void *stream)
 {
-    if (int rc = check_per(per, nullptr, capacity, ring_len, fresh_pos, fresh_count, batch, "shems_per_sample_dev")) return rc;
+    if (int rc = check_per(per, capacity, ring_len, fresh_pos, fresh_count, &batch, "shems_per_sample_dev")) return rc;
     return per_sample_launch(per, capacity, ring_len, fresh_pos, fresh_count, seed, tick, batch, (hipStream_t)stream);
 }
 
@@ -2495,7 +2464,10 @@ int shems_ddpg_update_per(const shems_ddpg *d, const shems_replay *ring, const s
 {
     const char *fn = "shems_ddpg_update_per";
     if (int rc = check_given(d, ring, ring_len, bp1_crit, bp2_crit, bp1_act, bp2_act, fn)) return rc;
-    if (int rc = check_per(per, d, ring->capacity, ring_len, fresh_pos, fresh_count, d->batch, fn)) return rc;
+    if (int rc = check_per(per, ring->capacity, ring_len, fresh_pos, fresh_count, &d->batch, fn)) return rc;
+    const size_t np = (size_t)ring->capacity * 4, nw = (size_t)per_ws_floats(ring->capacity) * 4, nd = (size_t)WS_FLOATS * 4;
+    if (ranges_overlap(per->prio, np, d->ws, nd) || ranges_overlap(per->ws, nw, d->ws, nd) || ranges_overlap(per->pmax, 4, d->ws, nd))
+        return set_error(SHEMS_ERR_ARG, "%s: the prioritized ring's arrays overlap the learner's workspace", fn);
     if (int rc = per_sample_launch(per, ring->capacity, ring_len, fresh_pos, fresh_count, seed, tick, d->batch, (hipStream_t)stream)) return rc;
     const int32_t *idx = reinterpret_cast<const int32_t *>(per->ws + PW_IDX);
     const GivenLaunch gv{idx, PerHead{per->ws + PW_W, idx, per->prio, per->pmax, ring_len, per->alpha, per->eps_p}};

@@ -36,6 +36,10 @@
 // TD3 for groups (shems_td3_group_update_tp) is a second critic walked by the same kernels: a sampler of its own
 // (k_tp_prep_td3), P1, a forward launch whose target jobs smooth the action (k_tp_fwd_smooth), P3 with the twin head and P4 once per
 // critic (k_tp_d1_twin, k_tp_gw2), and on a policy step P5-P7 -- seven launches, ten on a policy step (the block in front of k_tp_prep_td3).
+// Prioritized replay for groups (shems_ddpg_group_update_per_tp) is a sampler launch S, then P0 .. P7 with a sampler that
+// gathers S's slots (k_tp_prep_per) and the weighted head in P3 (k_tp_d1_per).
+// On the host (the end of this file) all of these are one launch plan: the shared checks, the launch context, the forward jobs, the
+// records and the launch shape of every phase are written once, and an entry point is its own checks plus a sequence of phase calls.
 // Summation orders differ from the latency form (64-wide n-tiles, chunked contractions): per learner the results agree with it to
 // fp32 accumulation accuracy, not bit for bit -- the parity test holds every gradient block of every learner to the float64
 // evaluation with the same bound as the latency form (tests/test_group_gpu.py).
@@ -43,7 +47,7 @@
 
 #include <cmath>
 #include <cstddef>
-#include <cstring>
+#include <initializer_list>
 #include <type_traits>
 
 #include "philox.h"
@@ -1679,99 +1683,215 @@ static int check_group_tp(const shems_group *g, const char *fn)
     return SHEMS_OK;
 }
 
-// t == null: every array in Flux order (round 5's form); else the layer-2 state of both networks lives in the tiled regions.
-// HP: learner l's batch / gamma / tau / eta from hp[l] (device), the *_hp kernels; d->batch / gamma / tau and eta_* are not used.
-// xp / pushed (HP only, shems_ddpg_group_update_tp_x): per-learner ring lengths on the device; ring_len is not used then.
-template <bool TL, bool HP>
-static int group_update_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, const shems_group_hparams *hp,
-                           int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
-                           double bp2_act, int32_t flags, void *stream, const shems_group_xparams *xp = nullptr, const int64_t *pushed = nullptr)
+// ================================================================================================================================
+// Host side of the throughput form: one launch plan behind the entry points
+// ================================================================================================================================
+// Every entry point below reads: its own checks -> check_tp -> tp_ctx, jobs and records -> the phase launchers in the order of the
+// P0 .. P7 list at the top of this file.  A check, a job, a record and a launch shape (grid, LDS, the narrow / wide choice) are each
+// written once, here.
+
+struct TpAdam { double eta, bp1, bp2; };       // one network's ADAM scalars as the entry points take them (eta = 0 with records: the
+                                               // *_hp kernels form k1 from the records; the host context's k1 is never read by them)
+
+// What every throughput entry point refuses, with nothing launched.  crit / act: the scalars of the halves the call updates, null for a
+// half it leaves alone -- the supervised update needs no critic, the critic-only update no actor moments; every call reads the actor and
+// its target.  hp null: d->batch is the batch; t null: Flux order.  The two half updates word their STORE_GRAD and ring refusals in their
+// own way.
+static int check_tp(const char *fn, const shems_ddpg *d, const shems_group *g, const shems_group_w2t *t, const shems_group_hparams *hp,
+                    const shems_replay *ring, int64_t ring_len, int32_t flags, int32_t flags_ok, const TpAdam *crit, const TpAdam *act)
 {
-    const char *fn = xp ? "shems_ddpg_group_update_tp_x" : "shems_ddpg_group_update_tp";
-    if (xp && (((uintptr_t)xp | (uintptr_t)pushed) & 7) != 0)
-        return set_error(SHEMS_ERR_ARG, "%s: d_xp and d_pushed must be 8-byte aligned device arrays of count records", fn);
+    const bool both = crit && act;
     if (int rc = check_group_tp(g, fn)) return rc;
-    if (!d || !d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
-        !d->s_min || !d->s_max || !d->ws || !d->losses)
+    if (!d || !d->actor || !d->actor_t || !d->s_min || !d->s_max || !d->ws || !d->losses || (act && (!d->m_actor || !d->v_actor)) ||
+        (crit && (!d->critic || !d->critic_t || !d->m_critic || !d->v_critic)))
         return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
-    if ((flags & SHEMS_TP_STORE_GRAD) && (!d->grad_actor || !d->grad_critic)) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
-    if (flags & ~SHEMS_TP_STORE_GRAD) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
-    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
-    if (HP && ((uintptr_t)hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
-    if (HP) eta_crit = eta_act = 0.0;        // the *_hp kernels form k1 from the records; the host context's k1 is never read by them
-    for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
+    if ((flags & SHEMS_TP_STORE_GRAD) && ((act && !d->grad_actor) || (crit && !d->grad_critic)))
+        return set_error(SHEMS_ERR_ARG, both ? "%s: STORE_GRAD needs gradient buffers" : "%s: STORE_GRAD needs the gradient buffer", fn);
+    if (flags & ~flags_ok) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
+    if (!hp && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
+    if (((uintptr_t)hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
+    const float *const aligned[] = {d->actor, d->actor_t, d->ws, crit ? d->critic : nullptr, crit ? d->critic_t : nullptr};
+    for (const float *p : aligned)
         if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
     if (int rc = w2t_flux_guard(d->actor, fn)) return rc;       // (a single learner's own tiled mode, shems_ddpg_tiled_enter: not a group's t)
-    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
-        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
-    for (double bp : {bp1_crit, bp2_crit, bp1_act, bp2_act})
-        if (!(bp > 0.0 && bp < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
-    if (TL) if (int rc = check_w2t(t, fn)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned L = (unsigned)g->count;
-    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
-    const int sg = (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0;
-    float *ws = d->ws;
-    float *ta = TL ? t->actor : nullptr, *tc = TL ? t->critic : nullptr;
-    auto arr = [](float *region, int a) -> const float * { return region ? region + a * TL_TILE : nullptr; };
+    const bool arrays = ring && ring->s && ring->a && (!crit || (ring->r && ring->s2 && ring->done));
+    if (!arrays && !both)
+        return set_error(SHEMS_ERR_ARG, crit ? "%s: the ring needs s, a, r, s2 and done" : "%s: the demonstration ring needs s and a", fn);
+    if (!arrays || ring_len < 1 || ring_len > ring->capacity)
+        return set_error(SHEMS_ERR_ARG, both ? "%s: bad replay ring / length" : "%s: bad ring length", fn);
+    for (const TpAdam *a : {crit, act})
+        if (a && !(a->bp1 > 0.0 && a->bp1 < 1.0 && a->bp2 > 0.0 && a->bp2 < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
+    if (t) if (int rc = check_w2t(t, fn)) return rc;
+    return SHEMS_OK;
+}
 
-    auto adam_ctx = [&](bool critic) {
-        const double eta = critic ? eta_crit : eta_act, bp1 = critic ? bp1_crit : bp1_act, bp2 = critic ? bp2_crit : bp2_act;
-        return critic ? AdamCtx{d->critic, d->grad_critic, d->m_critic, d->v_critic, d->critic_t, nullptr, SHEMS_CRITIC_PARAMS, (int)CIN,
-                                eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau}
-                      : AdamCtx{d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
-                                eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau};
-    };
-    struct { PrepArgs pa; FwdArgs f1, f2, f5; NetArgs nc, na; } U;
-    std::memset(&U, 0, sizeof U);
-    U.pa = PrepArgs{*d, *ring, ring_len, gs, seed, tick};
-    for (FwdArgs *f : {&U.f1, &U.f2, &U.f5}) { f->gstride = gs; f->batch = d->batch; }
-    // P1: three independent forward passes
-    U.f1.job[0] = FwdJob{arr(ta, TL_T), d->actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
-    U.f1.job[1] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, NET_CRITIC), nullptr, nullptr, nullptr, ws + TP_H2C, p3_of(ws, NET_CRITIC), nullptr, CIN, 1};
-    U.f1.job[2] = FwdJob{arr(ta, TL_P), d->actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
-    // P2: critic_target on [s'; actor_target(s')]
-    U.f2.job[0] = FwdJob{arr(tc, TL_T), d->critic_t, ws + TP_X2, w1i_of(ws, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, nullptr, nullptr,
-                         p3_of(ws, NET_CRITIC_T), nullptr, CIN, 1};
-    // P5: updated critic on [s; actor(s)], forward + input gradient
-    U.f5.job[0] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, IMG_CRITIC_NEW), p3_of(ws, NET_ACTOR), ws + TP_FB3 + 2, ws + TP_API, nullptr, p3_of(ws, PASS_CRITIC2),
-                         ws + TP_DAP, CIN, 1};
-    U.nc = NetArgs{*d, tc, adam_ctx(true), gs, 1, sg, (int)L};
-    U.na = NetArgs{*d, ta, adam_ctx(false), gs, 2, sg, (int)L};
-    typedef FwdShape<false, 4> SW;           // (typedefs: the launch macro splits its arguments at the commas of a template argument list)
-    typedef FwdShape<false, 2> SN;
-    typedef FwdShape<true, 2> SQ;
-    const bool narrow = L < kNarrowBelow;
-    const unsigned g8 = 8 * ((L + 7) / 8);
-    // the plain kernel, or with HP its *_hp twin with hp appended: the same eight launches, each reading its learner's record
-    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args) {
-        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, hp);
-        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
-    };
-    if (HP && xp) hipLaunchKernelGGL(k_tp_prep_x, dim3(5, L), dim3(256), 0, st, U.pa, hp, xp, pushed);
-    else launch(k_tp_prep, k_tp_prep_hp, dim3(5, L), 0, U.pa);
-    // Few learners: the shapes with twice the workgroups (P1 on 64-wide n-tiles, P3 / P6 on 32-wide k-tiles).  Below kNarrowBelow learners
-    // the wide shapes leave CUs without work (P3 at 32 learners: 128 workgroups); measured per grouped update, wide / narrow: 32 learners
-    // 247 / 226 us, 48 learners 322 / 320, 64 learners 362 / 372, 128 learners 669 / 695 (profiles/NOTES.md, round-5 log).
-    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(3 * SN::TILES, L), SN::LDS, U.f1);
-    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(3 * SW::TILES, L), SW::LDS, U.f1);
-    launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(SN::TILES, L), SN::LDS, U.f2);
-    if (narrow) launch(k_tp_d1<CIN, 1, TL>, k_tp_d1_hp<CIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.nc);
-    else launch(k_tp_d1<CIN, 2, TL>, k_tp_d1_hp<CIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.nc);
-    launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, U.nc);
-    launch(k_tp_fwd<true, 2, TL>, k_tp_fwd_hp<true, 2, TL>, dim3(SQ::TILES, L), SQ::LDS, U.f5);
-    if (narrow) launch(k_tp_d1<SIN, 1, TL>, k_tp_d1_hp<SIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.na);
-    else launch(k_tp_d1<SIN, 2, TL>, k_tp_d1_hp<SIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.na);
-    launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.na);
-    return hip_ok(hipGetLastError(), HP ? "grouped update (throughput form, per-learner hyper-parameters) launches" : "grouped update (throughput form) launches");
+// One call's launch context.  Few learners (narrow): the shapes with twice the workgroups (P1 on 64-wide n-tiles, P3 / P6 on 32-wide
+// k-tiles).  Below kNarrowBelow learners the wide shapes leave CUs without work (P3 at 32 learners: 128 workgroups); measured per grouped
+// update, wide / narrow: 32 learners 247 / 226 us, 48 learners 322 / 320, 64 learners 362 / 372, 128 learners 669 / 695
+// (profiles/NOTES.md, round-5 log).
+struct TpCtx {
+    hipStream_t st;
+    unsigned L;                            // learners: grid y
+    int64_t gs;                            // slab stride in bytes, 0 for one learner
+    int sg, batch;                         // STORE_GRAD; d->batch (the *_hp kernels read the records' instead)
+    bool narrow;
+    unsigned g8;                           // learners rounded up to eight: the D1 grids
+    float *ws, *ta, *tc;                   // learner 0's workspace; the tiled regions of actor and critic, null in Flux order
+    const shems_group_hparams *hp;         // the records the *_hp twins read, null without
+};
+static TpCtx tp_ctx(const shems_ddpg *d, const shems_group *g, const shems_group_w2t *t, const shems_group_hparams *hp, int32_t flags, void *stream)
+{
+    const unsigned L = (unsigned)g->count;
+    return TpCtx{(hipStream_t)stream, L, g->count > 1 ? g->stride_bytes : 0, (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0, d->batch, L < kNarrowBelow,
+                 8 * ((L + 7) / 8), d->ws, t ? t->actor : nullptr, t ? t->critic : nullptr, hp};
+}
+// the plain kernel, or with HP its *_hp twin with the context's records appended: the same launches, each reading its learner's record
+template <bool HP, class K, class KH, class A>
+static void launch(const TpCtx &c, K plain, KH twin, dim3 grid, unsigned lds, const A &args)
+{
+    if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, c.st, args, c.hp);
+    else hipLaunchKernelGGL(plain, grid, dim3(256), lds, c.st, args);
+}
+// f(TL, HP), the two as std::true_type / false_type: the <TL, HP> instantiation of a call's launches -- with (t) or without tiled regions,
+// with (hp) or without per-learner records
+template <class F>
+static int pick(bool tl, bool hp, F f)
+{
+    using Y = std::true_type;
+    using N = std::false_type;
+    return tl ? (hp ? f(Y{}, Y{}) : f(Y{}, N{})) : (hp ? f(N{}, Y{}) : f(N{}, N{}));
+}
+
+// ---- jobs and records -------------------------------------------------------------------------------------------------------------------
+// ws: the learner's workspace (the sampled batch, the actor's passes, the frozen b3).  wn: the workspace that holds the job's own network
+// images and partial sums -- ws again, or ws2 for TD3's second critic.  region: the network's tiled region, null in Flux order.
+static const float *arr(float *region, int a) { return region ? region + a * TL_TILE : nullptr; }
+static FwdJob job_actor_target(float *ws, float *ta, const float *actor_t)         // P1: actor_target(s')
+{
+    return FwdJob{arr(ta, TL_T), actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
+}
+static FwdJob job_critic(float *ws, float *wn, float *tc, const float *critic)     // P1: critic(s, a)
+{
+    return FwdJob{arr(tc, TL_P), critic, ws + TP_X, w1i_of(wn, NET_CRITIC), nullptr, nullptr, nullptr, wn + TP_H2C, p3_of(wn, NET_CRITIC), nullptr, CIN, 1};
+}
+static FwdJob job_actor(float *ws, float *ta, const float *actor)                  // P1: actor(s)
+{
+    return FwdJob{arr(ta, TL_P), actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
+}
+// P2: critic_target on [s'; actor_target(s')]; publish: where n-tile 0 leaves the action it computed (TD3's first target critic), or null
+static FwdJob job_critic_target(float *ws, float *wn, float *tc, const float *critic_t, float *publish)
+{
+    return FwdJob{arr(tc, TL_T), critic_t, ws + TP_X2, w1i_of(wn, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, publish, nullptr,
+                  p3_of(wn, NET_CRITIC_T), nullptr, CIN, 1};
+}
+static FwdJob job_critic_new(float *ws, float *tc, const float *critic)            // P5: updated critic on [s; actor(s)], forward + input gradient
+{
+    return FwdJob{arr(tc, TL_P), critic, ws + TP_X, w1i_of(ws, IMG_CRITIC_NEW), p3_of(ws, NET_ACTOR), ws + TP_FB3 + 2, ws + TP_API, nullptr,
+                  p3_of(ws, PASS_CRITIC2), ws + TP_DAP, CIN, 1};
+}
+static FwdArgs fwd_args(const TpCtx &c, std::initializer_list<FwdJob> jobs)         // up to three jobs; the unused slots stay zero
+{
+    FwdArgs f{};
+    int i = 0;
+    for (const FwdJob &j : jobs) f.job[i++] = j;
+    f.gstride = c.gs;
+    f.batch = c.batch;
+    return f;
+}
+static FwdArgs fwd_p1(const TpCtx &c, const shems_ddpg &d)                          // P1's three jobs; a launch of fewer takes the first ones
+{
+    return fwd_args(c, {job_actor_target(c.ws, c.ta, d.actor_t), job_critic(c.ws, c.ws, c.tc, d.critic), job_actor(c.ws, c.ta, d.actor)});
+}
+static FwdArgs fwd_p2(const TpCtx &c, const shems_ddpg &d) { return fwd_args(c, {job_critic_target(c.ws, c.ws, c.tc, d.critic_t, nullptr)}); }
+static AdamCtx adam_ctx(const shems_ddpg &d, bool critic, const TpAdam &a)
+{
+    AdamCtx c{d.actor, d.grad_actor, d.m_actor, d.v_actor, d.actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
+              a.eta, a.bp1, a.bp2, 1.0, a.eta / (1.0 - a.bp1), 1.0 / (1.0 - a.bp2), d.tau};
+    if (critic) { c.p = d.critic; c.g = d.grad_critic; c.mt = d.m_critic; c.vt = d.v_critic; c.target = d.critic_t; c.n = SHEMS_CRITIC_PARAMS; c.in = CIN; }
+    return c;
+}
+// the record of the launches that differentiate d's critic (P3 / P4: loss head 1) or actor (P6 / P7: head 2); region: its tiled region
+static NetArgs net_args(const TpCtx &c, const shems_ddpg &d, float *region, bool critic, const TpAdam &a)
+{
+    return NetArgs{d, region, adam_ctx(d, critic, a), c.gs, critic ? 1 : 2, c.sg, (int)c.L};
+}
+
+// ---- phase launchers --------------------------------------------------------------------------------------------------------------------
+typedef FwdShape<false, 4> SW;
+typedef FwdShape<false, 2> SN;
+typedef FwdShape<true, 2> SQ;
+template <bool TL, bool HP>
+static void launch_p1(const TpCtx &c, const FwdArgs &f, unsigned jobs)               // P1: `jobs` independent forward passes
+{
+    if (c.narrow) launch<HP>(c, k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(jobs * SN::TILES, c.L), SN::LDS, f);
+    else launch<HP>(c, k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(jobs * SW::TILES, c.L), SW::LDS, f);
+}
+template <bool TL, bool HP>
+static void launch_p2(const TpCtx &c, const FwdArgs &f)                              // P2: one forward pass on the narrow shape
+{
+    launch<HP>(c, k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(SN::TILES, c.L), SN::LDS, f);
+}
+// P3 / P6 for a kernel family (k_tp_d1, _clone, _twin, _per), given at 32-wide (k1*) and at 64-wide (k2*) k-tiles
+template <bool HP, class K, class KH, class A>
+static void launch_d1(const TpCtx &c, K k1, KH k1_hp, K k2, KH k2_hp, const A &args)
+{
+    if (c.narrow) launch<HP>(c, k1, k1_hp, dim3(8 * c.g8), d1_lds(1), args);
+    else launch<HP>(c, k2, k2_hp, dim3(4 * c.g8), d1_lds(2) + SHEMS_D1_PAD, args);
+}
+template <int IN, bool TL, bool HP>
+static void launch_d1_net(const TpCtx &c, const NetArgs &n)                          // ... with the DDPG heads: the critic's P3, the actor's P6
+{
+    launch_d1<HP>(c, k_tp_d1<IN, 1, TL>, k_tp_d1_hp<IN, 1, TL>, k_tp_d1<IN, 2, TL>, k_tp_d1_hp<IN, 2, TL>, n);
+}
+template <int IN, bool TL, bool HP>
+static void launch_gw2(const TpCtx &c, const NetArgs &n)                             // P4 / P7
+{
+    launch<HP>(c, k_tp_gw2<IN, TL>, k_tp_gw2_hp<IN, TL>, dim3(GW_WGS, c.L), GW_LDS, n);
+}
+template <bool TL, bool HP>
+static void launch_actor_half(const TpCtx &c, const shems_ddpg &d, const TpAdam &act)          // P5, P6, P7
+{
+    const FwdArgs f5 = fwd_args(c, {job_critic_new(c.ws, c.tc, d.critic)});
+    const NetArgs na = net_args(c, d, c.ta, false, act);
+    launch<HP>(c, k_tp_fwd<true, 2, TL>, k_tp_fwd_hp<true, 2, TL>, dim3(SQ::TILES, c.L), SQ::LDS, f5);
+    launch_d1_net<SIN, TL, HP>(c, na);
+    launch_gw2<SIN, TL, HP>(c, na);
+}
+
+// ---- the DDPG update: P0 .. P7 ------------------------------------------------------------------------------------------------------------
+// t == null: every array in Flux order (round 5's form); else the layer-2 state of both networks lives in the tiled regions.
+// hp: learner l's batch / gamma / tau / eta from hp[l] (device), the *_hp kernels; d->batch / gamma / tau and eta_* are not used.
+// xp / pushed (shems_ddpg_group_update_tp_x, with hp): per-learner ring lengths on the device; ring_len is not used then.
+static int ddpg_update_tp(const char *fn, const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
+                          const shems_group_hparams *hp, const shems_group_xparams *xp, const int64_t *pushed, int64_t ring_len, uint64_t seed,
+                          uint32_t tick, const TpAdam &crit, const TpAdam &act, int32_t flags, void *stream)
+{
+    if (xp && (((uintptr_t)xp | (uintptr_t)pushed) & 7) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: d_xp and d_pushed must be 8-byte aligned device arrays of count records", fn);
+    if (int rc = check_tp(fn, d, g, t, hp, ring, ring_len, flags, SHEMS_TP_STORE_GRAD, &crit, &act)) return rc;
+    const TpCtx c = tp_ctx(d, g, t, hp, flags, stream);
+    const PrepArgs pa{*d, *ring, ring_len, c.gs, seed, tick};
+    const FwdArgs f1 = fwd_p1(c, *d), f2 = fwd_p2(c, *d);
+    const NetArgs nc = net_args(c, *d, c.tc, true, crit);
+    return pick(t, hp, [&](auto tl, auto rec) {
+        constexpr bool TL = decltype(tl)::value, HP = decltype(rec)::value;
+        if (HP && xp) hipLaunchKernelGGL(k_tp_prep_x, dim3(5, c.L), dim3(256), 0, c.st, pa, hp, xp, pushed);
+        else launch<HP>(c, k_tp_prep, k_tp_prep_hp, dim3(5, c.L), 0, pa);
+        launch_p1<TL, HP>(c, f1, 3);
+        launch_p2<TL, HP>(c, f2);
+        launch_d1_net<CIN, TL, HP>(c, nc);
+        launch_gw2<CIN, TL, HP>(c, nc);
+        launch_actor_half<TL, HP>(c, *d, act);
+        return hip_ok(hipGetLastError(), HP ? "grouped update (throughput form, per-learner hyper-parameters) launches" : "grouped update (throughput form) launches");
+    });
 }
 
 extern "C" int shems_ddpg_group_update_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
                                           const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
                                           double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream)
 {
-    auto *update = t ? (d_hp ? group_update_tp<true, true> : group_update_tp<true, false>) : (d_hp ? group_update_tp<false, true> : group_update_tp<false, false>);
-    return update(d, ring, g, t, d_hp, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags, stream, nullptr, nullptr);
+    return ddpg_update_tp("shems_ddpg_group_update_tp", d, ring, g, t, d_hp, nullptr, nullptr, ring_len, seed, tick,
+                          TpAdam{d_hp ? 0.0 : eta_crit, bp1_crit, bp2_crit}, TpAdam{d_hp ? 0.0 : eta_act, bp1_act, bp2_act}, flags, stream);
 }
 
 extern "C" int shems_ddpg_group_update_tp_x(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
@@ -1780,115 +1900,60 @@ extern "C" int shems_ddpg_group_update_tp_x(const shems_ddpg *d, const shems_rep
                                             double bp2_act, int32_t flags, void *stream)
 {
     if (!d_hp || !d_xp || !d_pushed) return set_error(SHEMS_ERR_ARG, "shems_ddpg_group_update_tp_x: d_hp, d_xp and d_pushed are all required");
-    auto *update = t ? group_update_tp<true, true> : group_update_tp<false, true>;
-    return update(d, ring, g, t, d_hp, 1, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags, stream, d_xp, d_pushed);
+    return ddpg_update_tp("shems_ddpg_group_update_tp_x", d, ring, g, t, d_hp, d_xp, d_pushed, 1, seed, tick, TpAdam{0.0, bp1_crit, bp2_crit},
+                          TpAdam{0.0, bp1_act, bp2_act}, flags, stream);
 }
 
-// ---- the grouped supervised update (CLONE) and the grouped critic-only update: subsets of the launches above ----------------------
-//   CLONE   sampler | forward with the actor(s) job alone (one third of P1's grid) | the actor's D1 with the cloning head | the actor's gW2
+// ---- the grouped supervised update (clone) and the grouped critic-only update: subsets of the launches above ------------------------
+//   clone   sampler | P1 with the actor(s) job alone | the actor's D1 with the cloning head | the actor's gW2
 //   else    sampler | P1 with the actor_target(s') and critic(s, a) jobs | P2 | P3 | P4 -- the update's own kernels on the update's own
-//           inputs: the critic half of group_update_tp, bit for bit
+//           inputs: the critic half of the DDPG update, bit for bit
 // The ring is learner 0's arrays + l * ring_stride bytes (its own stride: the rings need not live in the slabs).
-template <bool TL, bool HP, bool CLONE>
-static int group_half_tp(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride, const shems_group *g, const shems_group_w2t *t,
-                         const shems_group_hparams *hp, int64_t ring_len, uint64_t seed, uint32_t tick, double eta, double bp1, double bp2,
-                         int32_t flags, void *stream)
+static int half_update_tp(bool clone, const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride, const shems_group *g, const shems_group_w2t *t,
+                          const shems_group_hparams *hp, int64_t ring_len, uint64_t seed, uint32_t tick, const TpAdam &adam, int32_t flags, void *stream)
 {
-    const char *fn = CLONE ? "shems_ddpg_group_clone_update_tp" : "shems_ddpg_group_critic_update_tp";
-    if (int rc = check_group_tp(g, fn)) return rc;
+    const char *fn = clone ? "shems_ddpg_group_clone_update_tp" : "shems_ddpg_group_critic_update_tp";
+    if (int rc = check_tp(fn, d, g, t, hp, ring, ring_len, flags, SHEMS_TP_STORE_GRAD, clone ? nullptr : &adam, clone ? &adam : nullptr)) return rc;
     if (ring_stride < 0 || (ring_stride & 3) != 0 || (g->count > 1 && ring_stride == 0))
         return set_error(SHEMS_ERR_ARG, "%s: bad ring stride %lld: a non-negative multiple of 4 bytes, and not 0 for more than one learner", fn,
                          (long long)ring_stride);
-    if (!d || !d->actor || !d->actor_t || !d->s_min || !d->s_max || !d->ws || !d->losses ||
-        (CLONE ? (!d->m_actor || !d->v_actor) : (!d->critic || !d->critic_t || !d->m_critic || !d->v_critic)))
-        return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
-    if ((flags & SHEMS_TP_STORE_GRAD) && !(CLONE ? d->grad_actor : d->grad_critic)) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs the gradient buffer", fn);
-    if (flags & ~SHEMS_TP_STORE_GRAD) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
-    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
-    if (HP && ((uintptr_t)hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
-    if (HP) eta = 0.0;                       // the *_hp kernels form k1 from the records
-    for (const float *p : {(const float *)d->actor, (const float *)d->actor_t, (const float *)d->ws, (const float *)(CLONE ? d->actor : d->critic),
-                           (const float *)(CLONE ? d->actor_t : d->critic_t)})
-        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
-    if (int rc = w2t_flux_guard(d->actor, fn)) return rc;       // (a single learner's own tiled mode, shems_ddpg_tiled_enter: not a group's t)
-    if (!ring || !ring->s || !ring->a || (!CLONE && (!ring->r || !ring->s2 || !ring->done)))
-        return set_error(SHEMS_ERR_ARG, CLONE ? "%s: the demonstration ring needs s and a" : "%s: the ring needs s, a, r, s2 and done", fn);
-    if (ring_len < 1 || ring_len > ring->capacity) return set_error(SHEMS_ERR_ARG, "%s: bad ring length", fn);
-    for (double bp : {bp1, bp2})
-        if (!(bp > 0.0 && bp < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
-    if (TL) if (int rc = check_w2t(t, fn)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned L = (unsigned)g->count;
-    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
-    const int sg = (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0;
-    float *ws = d->ws;
-    float *ta = TL ? t->actor : nullptr, *tc = TL ? t->critic : nullptr;
-    auto arr = [](float *region, int a) -> const float * { return region ? region + a * TL_TILE : nullptr; };
-    struct { PrepRingArgs pa; FwdArgs f1, f2; NetArgs n; } U;
-    std::memset(&U, 0, sizeof U);
-    U.pa = PrepRingArgs{PrepArgs{*d, *ring, ring_len, gs, seed, tick}, g->count > 1 ? ring_stride : 0};
-    for (FwdArgs *f : {&U.f1, &U.f2}) { f->gstride = gs; f->batch = d->batch; }
-    if (CLONE) {
-        U.f1.job[0] = FwdJob{arr(ta, TL_P), d->actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
-        U.n = NetArgs{*d, ta, AdamCtx{d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
-                                      eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau}, gs, 2, sg, (int)L};
-    } else {                                 // the jobs, P2 and the critic's NetArgs exactly as group_update_tp fills them
-        U.f1.job[0] = FwdJob{arr(ta, TL_T), d->actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
-        U.f1.job[1] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, NET_CRITIC), nullptr, nullptr, nullptr, ws + TP_H2C, p3_of(ws, NET_CRITIC), nullptr, CIN, 1};
-        U.f2.job[0] = FwdJob{arr(tc, TL_T), d->critic_t, ws + TP_X2, w1i_of(ws, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, nullptr, nullptr,
-                             p3_of(ws, NET_CRITIC_T), nullptr, CIN, 1};
-        U.n = NetArgs{*d, tc, AdamCtx{d->critic, d->grad_critic, d->m_critic, d->v_critic, d->critic_t, nullptr, SHEMS_CRITIC_PARAMS, (int)CIN,
-                                      eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau}, gs, 1, sg, (int)L};
-    }
-    typedef FwdShape<false, 4> SW;
-    typedef FwdShape<false, 2> SN;
-    const bool narrow = L < kNarrowBelow;
-    const unsigned g8 = 8 * ((L + 7) / 8);
-    constexpr unsigned JOBS = CLONE ? 1 : 2;
-    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args) {
-        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, hp);
-        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
-    };
-    launch(k_tp_prep_ring<CLONE>, k_tp_prep_ring_hp<CLONE>, dim3(CLONE ? 2 : 5, L), 0, U.pa);
-    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(JOBS * SN::TILES, L), SN::LDS, U.f1);
-    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(JOBS * SW::TILES, L), SW::LDS, U.f1);
-    if constexpr (CLONE) {
-        if (narrow) launch(k_tp_d1_clone<1, TL>, k_tp_d1_clone_hp<1, TL>, dim3(8 * g8), d1_lds(1), U.n);
-        else launch(k_tp_d1_clone<2, TL>, k_tp_d1_clone_hp<2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.n);
-        launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.n);
-    } else {
-        launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(SN::TILES, L), SN::LDS, U.f2);
-        if (narrow) launch(k_tp_d1<CIN, 1, TL>, k_tp_d1_hp<CIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.n);
-        else launch(k_tp_d1<CIN, 2, TL>, k_tp_d1_hp<CIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.n);
-        launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, U.n);
-    }
-    return hip_ok(hipGetLastError(), CLONE ? "grouped supervised update (throughput form) launches" : "grouped critic-only update (throughput form) launches");
-}
-template <bool CLONE>
-static int group_half_tp_pick(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride, const shems_group *g, const shems_group_w2t *t,
-                              const shems_group_hparams *hp, int64_t ring_len, uint64_t seed, uint32_t tick, double eta, double bp1, double bp2,
-                              int32_t flags, void *stream)
-{
-    auto *half = t ? (hp ? group_half_tp<true, true, CLONE> : group_half_tp<true, false, CLONE>)
-                   : (hp ? group_half_tp<false, true, CLONE> : group_half_tp<false, false, CLONE>);
-    return half(d, ring, ring_stride, g, t, hp, ring_len, seed, tick, eta, bp1, bp2, flags, stream);
+    const TpCtx c = tp_ctx(d, g, t, hp, flags, stream);
+    const PrepRingArgs pa{PrepArgs{*d, *ring, ring_len, c.gs, seed, tick}, g->count > 1 ? ring_stride : 0};
+    const FwdArgs f1 = clone ? fwd_args(c, {job_actor(c.ws, c.ta, d->actor)}) : fwd_p1(c, *d);
+    const NetArgs n = net_args(c, *d, clone ? c.ta : c.tc, !clone, adam);
+    return pick(t, hp, [&](auto tl, auto rec) {
+        constexpr bool TL = decltype(tl)::value, HP = decltype(rec)::value;
+        if (clone) {
+            launch<HP>(c, k_tp_prep_ring<true>, k_tp_prep_ring_hp<true>, dim3(2, c.L), 0, pa);
+            launch_p1<TL, HP>(c, f1, 1);
+            launch_d1<HP>(c, k_tp_d1_clone<1, TL>, k_tp_d1_clone_hp<1, TL>, k_tp_d1_clone<2, TL>, k_tp_d1_clone_hp<2, TL>, n);
+            launch_gw2<SIN, TL, HP>(c, n);
+            return hip_ok(hipGetLastError(), "grouped supervised update (throughput form) launches");
+        }
+        launch<HP>(c, k_tp_prep_ring<false>, k_tp_prep_ring_hp<false>, dim3(5, c.L), 0, pa);
+        launch_p1<TL, HP>(c, f1, 2);
+        launch_p2<TL, HP>(c, fwd_p2(c, *d));
+        launch_d1_net<CIN, TL, HP>(c, n);
+        launch_gw2<CIN, TL, HP>(c, n);
+        return hip_ok(hipGetLastError(), "grouped critic-only update (throughput form) launches");
+    });
 }
 extern "C" int shems_ddpg_group_clone_update_tp(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride_bytes, const shems_group *g,
                                                 const shems_group_w2t *t, const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed,
                                                 uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream)
 {
-    return group_half_tp_pick<true>(d, ring, ring_stride_bytes, g, t, d_hp, ring_len, seed, tick, eta, bp1, bp2, flags, stream);
+    return half_update_tp(true, d, ring, ring_stride_bytes, g, t, d_hp, ring_len, seed, tick, TpAdam{d_hp ? 0.0 : eta, bp1, bp2}, flags, stream);
 }
 extern "C" int shems_ddpg_group_critic_update_tp(const shems_ddpg *d, const shems_replay *ring, int64_t ring_stride_bytes, const shems_group *g,
                                                  const shems_group_w2t *t, const shems_group_hparams *d_hp, int64_t ring_len, uint64_t seed,
                                                  uint32_t tick, double eta, double bp1, double bp2, int32_t flags, void *stream)
 {
-    return group_half_tp_pick<false>(d, ring, ring_stride_bytes, g, t, d_hp, ring_len, seed, tick, eta, bp1, bp2, flags, stream);
+    return half_update_tp(false, d, ring, ring_stride_bytes, g, t, d_hp, ring_len, seed, tick, TpAdam{d_hp ? 0.0 : eta, bp1, bp2}, flags, stream);
 }
 
 // ---- TD3 for groups: seven launches, ten on a policy step -----------------------------------------------------------------------------
 //   sampler k_tp_prep_td3 | T1 = P1 (actor(s) job on a policy step only) | T2 k_tp_fwd_smooth | T3 k_tp_d1_twin for critic 1, again for
-//   critic 2 | T4 k_tp_gw2<CIN> for critic 1, again for critic 2 | policy step: P5, P6, P7 as group_update_tp launches them.
+//   critic 2 | T4 k_tp_gw2<CIN> for critic 1, again for critic 2 | policy step: P5, P6, P7.
 // Off a policy step the critic launches run with tau = 0 (1 t + 0 p: the targets keep their bytes): d->tau = 0 in their records, or
 // hp_hold (the records with tau = 0) in the place of hp.
 extern "C" int shems_td3_group_workspace_floats(int64_t *out)
@@ -1898,130 +1963,43 @@ extern "C" int shems_td3_group_workspace_floats(int64_t *out)
     return SHEMS_OK;
 }
 
-template <bool TL, bool HP>
-static int td3_group_update_tp(const shems_td3 *t0, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, float *w2t_critic2,
-                               const shems_group_hparams *hp, const shems_group_hparams *hp_hold, int64_t ring_len, uint64_t seed, uint32_t tick,
-                               double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy,
-                               int32_t flags, void *stream)
+// what shems_td3_group_update_tp refuses beyond check_tp: the second critic's blocks, the schedule and the smoothing noise
+static int check_td3_group(const char *fn, const shems_td3 *t0, const shems_group_w2t *t, const float *w2t_critic2, const shems_group_hparams *hp,
+                           const shems_group_hparams *hp_hold, int update_policy, int32_t flags)
 {
-    const char *fn = "shems_td3_group_update_tp";
     const shems_ddpg *d = &t0->d;
-    if (int rc = check_group_tp(g, fn)) return rc;
-    if (!d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
-        !d->s_min || !d->s_max || !d->ws || !d->losses)
-        return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
     if (!t0->critic2 || !t0->critic2_t || !t0->m_critic2 || !t0->v_critic2 || !t0->ws2 || !t0->losses2)
         return set_error(SHEMS_ERR_ARG, "%s: shems_td3 has a NULL critic-2 buffer", fn);
-    if ((flags & SHEMS_TP_STORE_GRAD) && (!d->grad_actor || !d->grad_critic || !t0->grad_critic2))
-        return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
-    if (flags & ~SHEMS_TP_STORE_GRAD) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
+    if ((flags & SHEMS_TP_STORE_GRAD) && !t0->grad_critic2) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
     if (update_policy != 0 && update_policy != 1) return set_error(SHEMS_ERR_ARG, "%s: update_policy must be 0 or 1 (got %d)", fn, update_policy);
     if (!(t0->sigma_trg >= 0.0f) || !(t0->clip_trg >= 0.0f) || t0->sigma_trg > 3.0e38f || t0->clip_trg > 3.0e38f)
         return set_error(SHEMS_ERR_ARG, "%s: sigma_trg and clip_trg must be finite and >= 0", fn);
-    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
-    if (HP && (((uintptr_t)hp | (uintptr_t)hp_hold) & 7) != 0)
-        return set_error(SHEMS_ERR_ARG, "%s: d_hp and d_hp_hold must be 8-byte aligned device arrays of count records", fn);
-    if (HP && !update_policy && !hp_hold)
+    if (hp && !update_policy && !hp_hold)
         return set_error(SHEMS_ERR_ARG, "%s: update_policy = 0 with d_hp needs d_hp_hold (the records with tau = 0)", fn);
-    if (HP) eta_crit = eta_act = 0.0;        // the *_hp kernels form k1 from the records
-    for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
-        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
     for (const float *p : {(const float *)t0->critic2, (const float *)t0->critic2_t, (const float *)t0->m_critic2, (const float *)t0->v_critic2,
                            (const float *)t0->ws2})
         if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: critic-2 blocks and ws2 must be 16-byte aligned", fn);
     if (((uintptr_t)t0->grad_critic2 & 15) != 0 || ((uintptr_t)t0->losses2 & 3) != 0)
         return set_error(SHEMS_ERR_ARG, "%s: grad_critic2 must be 16-byte and losses2 float aligned", fn);
-    {
-        const float *one[5] = {d->critic, d->critic_t, d->m_critic, d->v_critic, d->grad_critic};
-        const float *two[5] = {t0->critic2, t0->critic2_t, t0->m_critic2, t0->v_critic2, t0->grad_critic2};
-        for (int i = 0; i < 5; ++i)
-            for (int j = 0; j < 5; ++j) {
-                if (two[i] && one[j] && two[i] < one[j] + SHEMS_CRITIC_PARAMS && one[j] < two[i] + SHEMS_CRITIC_PARAMS)
-                    return set_error(SHEMS_ERR_ARG, "%s: a critic-2 buffer overlaps one of critic 1's", fn);
-                if (i < j && two[i] && two[j] && two[i] < two[j] + SHEMS_CRITIC_PARAMS && two[j] < two[i] + SHEMS_CRITIC_PARAMS)
-                    return set_error(SHEMS_ERR_ARG, "%s: two critic-2 buffers overlap", fn);
-            }
-        if (t0->ws2 < d->ws + TP_FLOATS && d->ws < t0->ws2 + T2_FLOATS) return set_error(SHEMS_ERR_ARG, "%s: ws2 overlaps ws", fn);
-        if (t0->losses2 < d->losses + 2 && d->losses < t0->losses2 + 1) return set_error(SHEMS_ERR_ARG, "%s: losses2 overlaps losses", fn);
-    }
-    if (int rc = w2t_flux_guard(d->actor, fn)) return rc;       // (a single learner's own tiled mode, shems_ddpg_tiled_enter: not a group's t)
-    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
-        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
-    for (double bp : {bp1_crit, bp2_crit, bp1_act, bp2_act})
-        if (!(bp > 0.0 && bp < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
-    if (TL) {
-        if (int rc = check_w2t(t, fn)) return rc;
+    const float *one[5] = {d->critic, d->critic_t, d->m_critic, d->v_critic, d->grad_critic};
+    const float *two[5] = {t0->critic2, t0->critic2_t, t0->m_critic2, t0->v_critic2, t0->grad_critic2};
+    for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < 5; ++j) {
+            if (two[i] && one[j] && two[i] < one[j] + SHEMS_CRITIC_PARAMS && one[j] < two[i] + SHEMS_CRITIC_PARAMS)
+                return set_error(SHEMS_ERR_ARG, "%s: a critic-2 buffer overlaps one of critic 1's", fn);
+            if (i < j && two[i] && two[j] && two[i] < two[j] + SHEMS_CRITIC_PARAMS && two[j] < two[i] + SHEMS_CRITIC_PARAMS)
+                return set_error(SHEMS_ERR_ARG, "%s: two critic-2 buffers overlap", fn);
+        }
+    if (t0->ws2 < d->ws + TP_FLOATS && d->ws < t0->ws2 + T2_FLOATS) return set_error(SHEMS_ERR_ARG, "%s: ws2 overlaps ws", fn);
+    if (t0->losses2 < d->losses + 2 && d->losses < t0->losses2 + 1) return set_error(SHEMS_ERR_ARG, "%s: losses2 overlaps losses", fn);
+    if (t) {
         if (((uintptr_t)w2t_critic2 & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: the tiled regions must be 16-byte aligned", fn);
         if (w2t_critic2 < t->critic + SHEMS_W2T_FLOATS && t->critic < w2t_critic2 + SHEMS_W2T_FLOATS)
             return set_error(SHEMS_ERR_ARG, "%s: critic 2's tiled region overlaps critic 1's", fn);
         if (w2t_critic2 < t->actor + SHEMS_W2T_FLOATS && t->actor < w2t_critic2 + SHEMS_W2T_FLOATS)
             return set_error(SHEMS_ERR_ARG, "%s: critic 2's tiled region overlaps the actor's", fn);
     }
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned L = (unsigned)g->count;
-    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
-    const int sg = (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0;
-    float *ws = d->ws, *ws2 = t0->ws2;
-    float *ta = TL ? t->actor : nullptr, *tc = TL ? t->critic : nullptr, *tc2 = TL ? w2t_critic2 : nullptr;
-    auto arr = [](float *region, int a) -> const float * { return region ? region + a * TL_TILE : nullptr; };
-    // the records of the critic launches: critic 2's names critic 2's blocks, ws2 and losses2; off a policy step both hold tau = 0
-    shems_ddpg d1 = *d, d2 = *d;
-    d2.critic = t0->critic2; d2.critic_t = t0->critic2_t; d2.m_critic = t0->m_critic2; d2.v_critic = t0->v_critic2;
-    d2.grad_critic = t0->grad_critic2; d2.ws = ws2; d2.losses = t0->losses2;
-    if (!update_policy) d1.tau = d2.tau = 0.0f;
-    auto critic_ctx = [&](const shems_ddpg &x) {
-        return AdamCtx{x.critic, x.grad_critic, x.m_critic, x.v_critic, x.critic_t, nullptr, SHEMS_CRITIC_PARAMS, (int)CIN,
-                       eta_crit, bp1_crit, bp2_crit, 1.0, eta_crit / (1.0 - bp1_crit), 1.0 / (1.0 - bp2_crit), x.tau};
-    };
-    struct { PrepTd3Args pa; FwdArgs f1, f5; FwdSmoothArgs f2; TwinArgs n1, n2; NetArgs na; } U;
-    std::memset(&U, 0, sizeof U);
-    U.pa = PrepTd3Args{PrepArgs{*d, *ring, ring_len, gs, seed, tick}, t0->critic2, t0->critic2_t, ws2};
-    for (FwdArgs *f : {&U.f1, &U.f2.f, &U.f5}) { f->gstride = gs; f->batch = d->batch; }
-    // T1 = P1 of group_update_tp
-    U.f1.job[0] = FwdJob{arr(ta, TL_T), d->actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
-    U.f1.job[1] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, NET_CRITIC), nullptr, nullptr, nullptr, ws + TP_H2C, p3_of(ws, NET_CRITIC), nullptr, CIN, 1};
-    U.f1.job[2] = FwdJob{arr(ta, TL_P), d->actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
-    // T2: both target critics on [s'; a~'] (the first publishes a~'), critic 2 on [s; a]
-    U.f2.f.job[0] = FwdJob{arr(tc, TL_T), d->critic_t, ws + TP_X2, w1i_of(ws, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, ws2 + T2_AT, nullptr,
-                           p3_of(ws, NET_CRITIC_T), nullptr, CIN, 1};
-    U.f2.f.job[1] = FwdJob{arr(tc2, TL_T), t0->critic2_t, ws + TP_X2, w1i_of(ws2, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, nullptr, nullptr,
-                           p3_of(ws2, NET_CRITIC_T), nullptr, CIN, 1};
-    U.f2.f.job[2] = FwdJob{arr(tc2, TL_P), t0->critic2, ws + TP_X, w1i_of(ws2, NET_CRITIC), nullptr, nullptr, nullptr, ws2 + TP_H2C, p3_of(ws2, NET_CRITIC), nullptr, CIN, 1};
-    U.f2.tn = TpNoise{seed, tick, t0->sigma_trg, t0->clip_trg};
-    // P5 of group_update_tp
-    U.f5.job[0] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, IMG_CRITIC_NEW), p3_of(ws, NET_ACTOR), ws + TP_FB3 + 2, ws + TP_API, nullptr, p3_of(ws, PASS_CRITIC2),
-                         ws + TP_DAP, CIN, 1};
-    U.n1 = TwinArgs{NetArgs{d1, tc, critic_ctx(d1), gs, 1, sg, (int)L}, TwinX{ws, ws2, ws2 + T2_PUB}};
-    U.n2 = TwinArgs{NetArgs{d2, tc2, critic_ctx(d2), gs, 1, sg, (int)L}, TwinX{ws, ws2, ws2 + T2_PUB2}};
-    U.na = NetArgs{*d, ta, AdamCtx{d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
-                                   eta_act, bp1_act, bp2_act, 1.0, eta_act / (1.0 - bp1_act), 1.0 / (1.0 - bp2_act), d->tau}, gs, 2, sg, (int)L};
-    typedef FwdShape<false, 4> SW;
-    typedef FwdShape<false, 2> SN;
-    typedef FwdShape<true, 2> SQ;
-    const bool narrow = L < kNarrowBelow;
-    const unsigned g8 = 8 * ((L + 7) / 8);
-    const unsigned JOBS = update_policy ? 3 : 2;
-    const shems_group_hparams *hpc = update_policy ? hp : hp_hold;      // the critic launches' records
-    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args, const shems_group_hparams *rec) {
-        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, rec);
-        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
-    };
-    launch(k_tp_prep_td3, k_tp_prep_td3_hp, dim3(7, L), 0, U.pa, hp);
-    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(JOBS * SN::TILES, L), SN::LDS, U.f1, hp);
-    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(JOBS * SW::TILES, L), SW::LDS, U.f1, hp);
-    launch(k_tp_fwd_smooth<TL>, k_tp_fwd_smooth_hp<TL>, dim3(3 * SN::TILES, L), SN::LDS, U.f2, hp);
-    for (const TwinArgs *n : {&U.n1, &U.n2}) {
-        if (narrow) launch(k_tp_d1_twin<1, TL>, k_tp_d1_twin_hp<1, TL>, dim3(8 * g8), d1_lds(1), *n, hpc);
-        else launch(k_tp_d1_twin<2, TL>, k_tp_d1_twin_hp<2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, *n, hpc);
-    }
-    for (const TwinArgs *n : {&U.n1, &U.n2}) launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, n->n, hpc);
-    if (update_policy) {
-        launch(k_tp_fwd<true, 2, TL>, k_tp_fwd_hp<true, 2, TL>, dim3(SQ::TILES, L), SQ::LDS, U.f5, hp);
-        if (narrow) launch(k_tp_d1<SIN, 1, TL>, k_tp_d1_hp<SIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.na, hp);
-        else launch(k_tp_d1<SIN, 2, TL>, k_tp_d1_hp<SIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.na, hp);
-        launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.na, hp);
-    }
-    return hip_ok(hipGetLastError(), "grouped TD3 update (throughput form) launches");
+    return SHEMS_OK;
 }
 
 extern "C" int shems_td3_group_update_tp(const shems_td3 *t0, const shems_replay *ring0, const shems_group *g, const shems_group_w2t *w,
@@ -2029,46 +2007,45 @@ extern "C" int shems_td3_group_update_tp(const shems_td3 *t0, const shems_replay
                                          uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act,
                                          double bp1_act, double bp2_act, int update_policy, int32_t flags, void *stream)
 {
+    const char *fn = "shems_td3_group_update_tp";
     if (!t0) return set_error(SHEMS_ERR_ARG, "shems_td3_group_update_tp: NULL");
     if ((w != nullptr) != (w2t_critic2 != nullptr))
         return set_error(SHEMS_ERR_ARG, "shems_td3_group_update_tp: the tiled layout needs w AND w2t_critic2 (or neither: Flux order)");
-    auto *update = w ? (d_hp ? td3_group_update_tp<true, true> : td3_group_update_tp<true, false>)
-                     : (d_hp ? td3_group_update_tp<false, true> : td3_group_update_tp<false, false>);
-    return update(t0, ring0, g, w, w2t_critic2, d_hp, d_hp_hold, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act,
-                  update_policy, flags, stream);
+    if (d_hp && (((uintptr_t)d_hp | (uintptr_t)d_hp_hold) & 7) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: d_hp and d_hp_hold must be 8-byte aligned device arrays of count records", fn);
+    const shems_ddpg *d = &t0->d;
+    const TpAdam crit{d_hp ? 0.0 : eta_crit, bp1_crit, bp2_crit}, act{d_hp ? 0.0 : eta_act, bp1_act, bp2_act};
+    if (int rc = check_tp(fn, d, g, w, d_hp, ring0, ring_len, flags, SHEMS_TP_STORE_GRAD, &crit, &act)) return rc;
+    if (int rc = check_td3_group(fn, t0, w, w2t_critic2, d_hp, d_hp_hold, update_policy, flags)) return rc;
+    const TpCtx c = tp_ctx(d, g, w, d_hp, flags, stream);
+    TpCtx cc = c;                            // the critic launches' context: off a policy step their records are the held ones
+    if (!update_policy) cc.hp = d_hp_hold;
+    float *ws = c.ws, *ws2 = t0->ws2, *tc2 = w2t_critic2;
+    // the records of the critic launches: critic 2's names critic 2's blocks, ws2 and losses2; off a policy step both hold tau = 0
+    shems_ddpg d1 = *d, d2 = *d;
+    d2.critic = t0->critic2; d2.critic_t = t0->critic2_t; d2.m_critic = t0->m_critic2; d2.v_critic = t0->v_critic2;
+    d2.grad_critic = t0->grad_critic2; d2.ws = ws2; d2.losses = t0->losses2;
+    if (!update_policy) d1.tau = d2.tau = 0.0f;
+    const PrepTd3Args pa{PrepArgs{*d, *ring0, ring_len, c.gs, seed, tick}, t0->critic2, t0->critic2_t, ws2};
+    const FwdArgs f1 = fwd_p1(c, *d);
+    // T2: both target critics on [s'; a~'] (the first publishes a~'), critic 2 on [s; a]
+    const FwdSmoothArgs f2{fwd_args(c, {job_critic_target(ws, ws, c.tc, d->critic_t, ws2 + T2_AT), job_critic_target(ws, ws2, tc2, t0->critic2_t, nullptr),
+                                        job_critic(ws, ws2, tc2, t0->critic2)}),
+                           TpNoise{seed, tick, t0->sigma_trg, t0->clip_trg}};
+    const TwinArgs n1{net_args(c, d1, c.tc, true, crit), TwinX{ws, ws2, ws2 + T2_PUB}}, n2{net_args(c, d2, tc2, true, crit), TwinX{ws, ws2, ws2 + T2_PUB2}};
+    return pick(w, d_hp, [&](auto tl, auto rec) {
+        constexpr bool TL = decltype(tl)::value, HP = decltype(rec)::value;
+        launch<HP>(c, k_tp_prep_td3, k_tp_prep_td3_hp, dim3(7, c.L), 0, pa);
+        launch_p1<TL, HP>(c, f1, update_policy ? 3 : 2);
+        launch<HP>(c, k_tp_fwd_smooth<TL>, k_tp_fwd_smooth_hp<TL>, dim3(3 * SN::TILES, c.L), SN::LDS, f2);
+        for (const TwinArgs *n : {&n1, &n2}) launch_d1<HP>(cc, k_tp_d1_twin<1, TL>, k_tp_d1_twin_hp<1, TL>, k_tp_d1_twin<2, TL>, k_tp_d1_twin_hp<2, TL>, *n);
+        for (const TwinArgs *n : {&n1, &n2}) launch_gw2<CIN, TL, HP>(cc, n->n);
+        if (update_policy) launch_actor_half<TL, HP>(c, *d, act);
+        return hip_ok(hipGetLastError(), "grouped TD3 update (throughput form) launches");
+    });
 }
 
 // ---- prioritized replay for groups: S, P0 (k_tp_prep_per), P1, P2, P3 (k_tp_d1_per), P4 .. P7 -----------------------------------------
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-// What shems_ddpg_update_per refuses for the prioritized ring's own arguments (check_per of shems_ddpg.hip, repeated here so that
-// that file keeps its text), for learner 0's shems_per.  batch <= 0: the batches are per-learner records on the device (not looked at).
-static int check_per_group(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, int32_t batch,
-                           const char *fn)
-{
-    if (!per || !per->prio || !per->pmax || !per->ws) return set_error(SHEMS_ERR_ARG, "%s: shems_per has a NULL buffer", fn);
-    if (capacity < 1 || capacity > kPerMaxSlots)
-        return set_error(SHEMS_ERR_ARG, "%s: a prioritized ring holds 1..%lld slots (got %lld)", fn, (long long)kPerMaxSlots, (long long)capacity);
-    if (ring_len < 1 || ring_len > capacity) return set_error(SHEMS_ERR_ARG, "%s: ring_len must be in 1..capacity", fn);
-    if (batch > kPerCols || batch == 0) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, batch);
-    if (((uintptr_t)per->prio & 15) != 0 || ((uintptr_t)per->ws & 15) != 0 || ((uintptr_t)per->pmax & 3) != 0)
-        return set_error(SHEMS_ERR_ARG, "%s: prio and the workspace must be 16-byte aligned, pmax 4-byte aligned", fn);
-    const size_t np = (size_t)capacity * 4, nw = (size_t)per_ws_floats(capacity) * 4;
-    if (ranges_overlap(per->prio, np, per->ws, nw) || ranges_overlap(per->prio, np, per->pmax, 4) || ranges_overlap(per->ws, nw, per->pmax, 4))
-        return set_error(SHEMS_ERR_ARG, "%s: prio, pmax and the workspace overlap", fn);
-    for (const float v : {per->alpha, per->beta, per->eps_p})
-        if (!(v >= 0.0f) || !std::isfinite(v)) return set_error(SHEMS_ERR_ARG, "%s: alpha, beta and eps_p must be finite and >= 0", fn);
-    if (per->beta > 1.0f) return set_error(SHEMS_ERR_ARG, "%s: beta must be in [0, 1] (got %g)", fn, (double)per->beta);
-    if (fresh_pos < 0 || fresh_pos >= capacity || fresh_count < 0)
-        return set_error(SHEMS_ERR_ARG, "%s: the fresh range must start inside the ring and have a count >= 0", fn);
-    if (fresh_count > 0 && fresh_count < capacity && ring_len < capacity && fresh_pos + fresh_count > ring_len)
-        return set_error(SHEMS_ERR_ARG, "%s: the fresh range [%lld, +%lld) leaves the %lld filled slots", fn, (long long)fresh_pos,
-                         (long long)fresh_count, (long long)ring_len);
-    return SHEMS_OK;
-}
 // The three blocks of learner 0's shems_per against the slab: with more than one learner they must end inside one stride of the lowest
 // of `blocks` and of themselves (learner l's copy would otherwise reach into learner l + 1's slab), and overlap none of `blocks`.
 struct SlabBlock { const void *p; size_t bytes; };
@@ -2105,100 +2082,10 @@ extern "C" int shems_per_group_sample_dev(const shems_per *per0, const shems_gro
     const char *fn = "shems_per_group_sample_dev";
     if (int rc = check_group_tp(g, fn)) return rc;
     if (d_hp && ((uintptr_t)d_hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
-    if (int rc = check_per_group(per0, capacity, ring_len, fresh_pos, fresh_count, d_hp ? -1 : (batch < 1 ? 0 : batch), fn)) return rc;
+    const int32_t shown = batch < 1 ? 0 : batch;             // (the refusal names every batch below 1 as 0)
+    if (int rc = check_per(per0, capacity, ring_len, fresh_pos, fresh_count, d_hp ? nullptr : &shown, fn)) return rc;
     if (int rc = check_per_slab(per0, capacity, g, nullptr, 0, fn)) return rc;
     return per_group_sample_launch(per0, g, d_hp, capacity, ring_len, fresh_pos, fresh_count, seed, tick, batch, (hipStream_t)stream);
-}
-
-template <bool TL, bool HP>
-static int group_update_per_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t, const shems_group_hparams *hp,
-                               const shems_per *per, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed, uint32_t tick,
-                               double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int32_t flags,
-                               void *stream)
-{
-    const char *fn = "shems_ddpg_group_update_per_tp";
-    // ---- whatever shems_ddpg_group_update_tp refuses ----
-    if (int rc = check_group_tp(g, fn)) return rc;
-    if (!d || !d->actor || !d->critic || !d->actor_t || !d->critic_t || !d->m_actor || !d->v_actor || !d->m_critic || !d->v_critic ||
-        !d->s_min || !d->s_max || !d->ws || !d->losses)
-        return set_error(SHEMS_ERR_ARG, "%s: shems_ddpg has a NULL buffer", fn);
-    if ((flags & SHEMS_TP_STORE_GRAD) && (!d->grad_actor || !d->grad_critic)) return set_error(SHEMS_ERR_ARG, "%s: STORE_GRAD needs gradient buffers", fn);
-    if (flags & ~(SHEMS_TP_STORE_GRAD | SHEMS_TP_PER_GIVEN)) return set_error(SHEMS_ERR_ARG, "%s: unknown flag bits", fn);
-    if (!HP && (d->batch < 1 || d->batch > BP)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
-    if (HP && ((uintptr_t)hp & 7) != 0) return set_error(SHEMS_ERR_ARG, "%s: d_hp must be an 8-byte aligned device array of count records", fn);
-    if (HP) eta_crit = eta_act = 0.0;        // the *_hp kernels form k1 from the records
-    for (const float *p : {(const float *)d->actor, (const float *)d->critic, (const float *)d->actor_t, (const float *)d->critic_t, (const float *)d->ws})
-        if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks and the workspace must be 16-byte aligned", fn);
-    if (int rc = w2t_flux_guard(d->actor, fn)) return rc;
-    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
-        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
-    for (double bp : {bp1_crit, bp2_crit, bp1_act, bp2_act})
-        if (!(bp > 0.0 && bp < 1.0)) return set_error(SHEMS_ERR_ARG, "%s: beta powers must be in (0,1)", fn);
-    if (TL) if (int rc = check_w2t(t, fn)) return rc;
-    // ---- the prioritized ring's own arguments, and its blocks against the slab ----
-    if (int rc = check_per_group(per, ring->capacity, ring_len, fresh_pos, fresh_count, HP ? -1 : d->batch, fn)) return rc;
-    {
-        const size_t na = (size_t)SHEMS_ACTOR_PARAMS * 4, nc = (size_t)SHEMS_CRITIC_PARAMS * 4, cap = (size_t)ring->capacity;
-        const SlabBlock blocks[] = {
-            {d->actor, na}, {d->critic, nc}, {d->actor_t, na}, {d->critic_t, nc}, {d->m_actor, na}, {d->v_actor, na}, {d->m_critic, nc}, {d->v_critic, nc},
-            {d->grad_actor, na}, {d->grad_critic, nc}, {d->s_min, SHEMS_NSTATE * 4}, {d->s_max, SHEMS_NSTATE * 4}, {d->ws, (size_t)kTpWsFloats * 4},
-            {d->losses, 8}, {ring->s, cap * SHEMS_NSTATE * 4}, {ring->a, cap * 2 * 4}, {ring->r, cap * 4}, {ring->s2, cap * SHEMS_NSTATE * 4},
-            {ring->done, cap}, {TL ? t->actor : nullptr, (size_t)SHEMS_W2T_FLOATS * 4}, {TL ? t->critic : nullptr, (size_t)SHEMS_W2T_FLOATS * 4}};
-        if (int rc = check_per_slab(per, ring->capacity, g, blocks, (int)(sizeof blocks / sizeof blocks[0]), fn)) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned L = (unsigned)g->count;
-    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
-    const int sg = (flags & SHEMS_TP_STORE_GRAD) ? 1 : 0;
-    const bool given = (flags & SHEMS_TP_PER_GIVEN) != 0;
-    float *ws = d->ws;
-    float *ta = TL ? t->actor : nullptr, *tc = TL ? t->critic : nullptr;
-    auto arr = [](float *region, int a) -> const float * { return region ? region + a * TL_TILE : nullptr; };
-    auto adam_ctx = [&](bool critic) {
-        const double eta = critic ? eta_crit : eta_act, bp1 = critic ? bp1_crit : bp1_act, bp2 = critic ? bp2_crit : bp2_act;
-        return critic ? AdamCtx{d->critic, d->grad_critic, d->m_critic, d->v_critic, d->critic_t, nullptr, SHEMS_CRITIC_PARAMS, (int)CIN,
-                                eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau}
-                      : AdamCtx{d->actor, d->grad_actor, d->m_actor, d->v_actor, d->actor_t, nullptr, SHEMS_ACTOR_PARAMS, (int)SIN,
-                                eta, bp1, bp2, 1.0, eta / (1.0 - bp1), 1.0 / (1.0 - bp2), d->tau};
-    };
-    // the jobs and records exactly as group_update_tp fills them
-    struct { PrepPerArgs pa; FwdArgs f1, f2, f5; PerD1Args nc; NetArgs ng, na; } U;
-    std::memset(&U, 0, sizeof U);
-    U.pa = PrepPerArgs{PrepArgs{*d, *ring, ring_len, gs, seed, tick}, per->ws};
-    for (FwdArgs *f : {&U.f1, &U.f2, &U.f5}) { f->gstride = gs; f->batch = d->batch; }
-    U.f1.job[0] = FwdJob{arr(ta, TL_T), d->actor_t, ws + TP_X2, w1i_of(ws, NET_ACTOR_T), nullptr, nullptr, nullptr, nullptr, p3_of(ws, NET_ACTOR_T), nullptr, SIN, 2};
-    U.f1.job[1] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, NET_CRITIC), nullptr, nullptr, nullptr, ws + TP_H2C, p3_of(ws, NET_CRITIC), nullptr, CIN, 1};
-    U.f1.job[2] = FwdJob{arr(ta, TL_P), d->actor, ws + TP_X, w1i_of(ws, NET_ACTOR), nullptr, nullptr, nullptr, ws + TP_H2A, p3_of(ws, NET_ACTOR), nullptr, SIN, 2};
-    U.f2.job[0] = FwdJob{arr(tc, TL_T), d->critic_t, ws + TP_X2, w1i_of(ws, NET_CRITIC_T), p3_of(ws, NET_ACTOR_T), ws + TP_FB3 + 4, nullptr, nullptr,
-                         p3_of(ws, NET_CRITIC_T), nullptr, CIN, 1};
-    U.f5.job[0] = FwdJob{arr(tc, TL_P), d->critic, ws + TP_X, w1i_of(ws, IMG_CRITIC_NEW), p3_of(ws, NET_ACTOR), ws + TP_FB3 + 2, ws + TP_API, nullptr, p3_of(ws, PASS_CRITIC2),
-                         ws + TP_DAP, CIN, 1};
-    U.ng = NetArgs{*d, tc, adam_ctx(true), gs, 1, sg, (int)L};
-    U.nc = PerD1Args{U.ng, PerX{per->ws, given ? nullptr : per->prio, given ? nullptr : per->pmax, ring_len, per->alpha, per->eps_p}};
-    U.na = NetArgs{*d, ta, adam_ctx(false), gs, 2, sg, (int)L};
-    typedef FwdShape<false, 4> SW;
-    typedef FwdShape<false, 2> SN;
-    typedef FwdShape<true, 2> SQ;
-    const bool narrow = L < kNarrowBelow;
-    const unsigned g8 = 8 * ((L + 7) / 8);
-    auto launch = [&](auto plain, auto twin, dim3 grid, unsigned lds, const auto &args) {
-        if constexpr (HP) hipLaunchKernelGGL(twin, grid, dim3(256), lds, st, args, hp);
-        else hipLaunchKernelGGL(plain, grid, dim3(256), lds, st, args);
-    };
-    if (!given)
-        if (int rc = per_group_sample_launch(per, g, HP ? hp : nullptr, ring->capacity, ring_len, fresh_pos, fresh_count, seed, tick, d->batch, st)) return rc;
-    launch(k_tp_prep_per, k_tp_prep_per_hp, dim3(5, L), 0, U.pa);
-    if (narrow) launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(3 * SN::TILES, L), SN::LDS, U.f1);
-    else launch(k_tp_fwd<false, 4, TL>, k_tp_fwd_hp<false, 4, TL>, dim3(3 * SW::TILES, L), SW::LDS, U.f1);
-    launch(k_tp_fwd<false, 2, TL>, k_tp_fwd_hp<false, 2, TL>, dim3(SN::TILES, L), SN::LDS, U.f2);
-    if (narrow) launch(k_tp_d1_per<1, TL>, k_tp_d1_per_hp<1, TL>, dim3(8 * g8), d1_lds(1), U.nc);
-    else launch(k_tp_d1_per<2, TL>, k_tp_d1_per_hp<2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.nc);
-    launch(k_tp_gw2<CIN, TL>, k_tp_gw2_hp<CIN, TL>, dim3(GW_WGS, L), GW_LDS, U.ng);
-    launch(k_tp_fwd<true, 2, TL>, k_tp_fwd_hp<true, 2, TL>, dim3(SQ::TILES, L), SQ::LDS, U.f5);
-    if (narrow) launch(k_tp_d1<SIN, 1, TL>, k_tp_d1_hp<SIN, 1, TL>, dim3(8 * g8), d1_lds(1), U.na);
-    else launch(k_tp_d1<SIN, 2, TL>, k_tp_d1_hp<SIN, 2, TL>, dim3(4 * g8), d1_lds(2) + SHEMS_D1_PAD, U.na);
-    launch(k_tp_gw2<SIN, TL>, k_tp_gw2_hp<SIN, TL>, dim3(GW_WGS, L), GW_LDS, U.na);
-    return hip_ok(hipGetLastError(), "grouped prioritized update (throughput form) launches");
 }
 
 extern "C" int shems_ddpg_group_update_per_tp(const shems_ddpg *d, const shems_replay *ring, const shems_group *g, const shems_group_w2t *t,
@@ -2206,10 +2093,38 @@ extern "C" int shems_ddpg_group_update_per_tp(const shems_ddpg *d, const shems_r
                                               int64_t fresh_count, uint64_t seed, uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit,
                                               double eta_act, double bp1_act, double bp2_act, int32_t flags, void *stream)
 {
-    auto *update = t ? (d_hp ? group_update_per_tp<true, true> : group_update_per_tp<true, false>)
-                     : (d_hp ? group_update_per_tp<false, true> : group_update_per_tp<false, false>);
-    return update(d, ring, g, t, d_hp, per, ring_len, fresh_pos, fresh_count, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, flags,
-                  stream);
+    const char *fn = "shems_ddpg_group_update_per_tp";
+    const TpAdam crit{d_hp ? 0.0 : eta_crit, bp1_crit, bp2_crit}, act{d_hp ? 0.0 : eta_act, bp1_act, bp2_act};
+    if (int rc = check_tp(fn, d, g, t, d_hp, ring, ring_len, flags, SHEMS_TP_STORE_GRAD | SHEMS_TP_PER_GIVEN, &crit, &act)) return rc;
+    // the prioritized ring's own arguments, and its blocks against the slab
+    if (int rc = check_per(per, ring->capacity, ring_len, fresh_pos, fresh_count, d_hp ? nullptr : &d->batch, fn)) return rc;
+    {
+        const size_t na = (size_t)SHEMS_ACTOR_PARAMS * 4, nc = (size_t)SHEMS_CRITIC_PARAMS * 4, cap = (size_t)ring->capacity;
+        const SlabBlock blocks[] = {
+            {d->actor, na}, {d->critic, nc}, {d->actor_t, na}, {d->critic_t, nc}, {d->m_actor, na}, {d->v_actor, na}, {d->m_critic, nc}, {d->v_critic, nc},
+            {d->grad_actor, na}, {d->grad_critic, nc}, {d->s_min, SHEMS_NSTATE * 4}, {d->s_max, SHEMS_NSTATE * 4}, {d->ws, (size_t)kTpWsFloats * 4},
+            {d->losses, 8}, {ring->s, cap * SHEMS_NSTATE * 4}, {ring->a, cap * 2 * 4}, {ring->r, cap * 4}, {ring->s2, cap * SHEMS_NSTATE * 4},
+            {ring->done, cap}, {t ? t->actor : nullptr, (size_t)SHEMS_W2T_FLOATS * 4}, {t ? t->critic : nullptr, (size_t)SHEMS_W2T_FLOATS * 4}};
+        if (int rc = check_per_slab(per, ring->capacity, g, blocks, (int)(sizeof blocks / sizeof blocks[0]), fn)) return rc;
+    }
+    const TpCtx c = tp_ctx(d, g, t, d_hp, flags, stream);
+    const bool given = (flags & SHEMS_TP_PER_GIVEN) != 0;
+    const PrepPerArgs pa{PrepArgs{*d, *ring, ring_len, c.gs, seed, tick}, per->ws};
+    const FwdArgs f1 = fwd_p1(c, *d), f2 = fwd_p2(c, *d);
+    const NetArgs nc = net_args(c, *d, c.tc, true, crit);
+    const PerD1Args np{nc, PerX{per->ws, given ? nullptr : per->prio, given ? nullptr : per->pmax, ring_len, per->alpha, per->eps_p}};
+    if (!given)
+        if (int rc = per_group_sample_launch(per, g, d_hp, ring->capacity, ring_len, fresh_pos, fresh_count, seed, tick, d->batch, c.st)) return rc;
+    return pick(t, d_hp, [&](auto tl, auto rec) {
+        constexpr bool TL = decltype(tl)::value, HP = decltype(rec)::value;
+        launch<HP>(c, k_tp_prep_per, k_tp_prep_per_hp, dim3(5, c.L), 0, pa);
+        launch_p1<TL, HP>(c, f1, 3);
+        launch_p2<TL, HP>(c, f2);
+        launch_d1<HP>(c, k_tp_d1_per<1, TL>, k_tp_d1_per_hp<1, TL>, k_tp_d1_per<2, TL>, k_tp_d1_per_hp<2, TL>, np);
+        launch_gw2<CIN, TL, HP>(c, nc);
+        launch_actor_half<TL, HP>(c, *d, act);
+        return hip_ok(hipGetLastError(), "grouped prioritized update (throughput form) launches");
+    });
 }
 
 static_assert(sizeof(shems_group_xparams) == 16 && offsetof(shems_group_xparams, ou_dt) == 4 && offsetof(shems_group_xparams, mem_size) == 8 &&

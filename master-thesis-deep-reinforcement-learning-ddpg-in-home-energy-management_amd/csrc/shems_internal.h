@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include "../../include/shems_hip.h"
+#include "shems_per_core.h"
 
 namespace shems {
 int set_error(int code, const char *fmt, ...);          // records the thread-local message, returns code
@@ -30,6 +32,36 @@ int check_view(const shems_view *v, const char *fn);    // every entry point tha
 // so -- what every entry point that reads or writes such a block in Flux order calls before it launches anything.
 bool w2t_lookup(const float *block, shems_group_w2t *out);
 int w2t_flux_guard(const float *block, const char *fn);
+inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+// What every entry point that takes a prioritized ring (shems_per_core.h) refuses for the ring's own arguments: a single learner's
+// (shems_ddpg.hip) or learner 0's of a group (shems_gupd.hip).  batch null: the batches are per-learner records on the device.
+inline int check_per(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, const int32_t *batch,
+                     const char *fn)
+{
+    if (!per || !per->prio || !per->pmax || !per->ws) return set_error(SHEMS_ERR_ARG, "%s: shems_per has a NULL buffer", fn);
+    if (capacity < 1 || capacity > kPerMaxSlots)
+        return set_error(SHEMS_ERR_ARG, "%s: a prioritized ring holds 1..%lld slots (got %lld)", fn, (long long)kPerMaxSlots, (long long)capacity);
+    if (ring_len < 1 || ring_len > capacity) return set_error(SHEMS_ERR_ARG, "%s: ring_len must be in 1..capacity", fn);
+    if (batch && (*batch < 1 || *batch > kPerCols)) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, *batch);
+    if (((uintptr_t)per->prio & 15) != 0 || ((uintptr_t)per->ws & 15) != 0 || ((uintptr_t)per->pmax & 3) != 0)
+        return set_error(SHEMS_ERR_ARG, "%s: prio and the workspace must be 16-byte aligned, pmax 4-byte aligned", fn);
+    const size_t np = (size_t)capacity * 4, nw = (size_t)per_ws_floats(capacity) * 4;
+    if (ranges_overlap(per->prio, np, per->ws, nw) || ranges_overlap(per->prio, np, per->pmax, 4) || ranges_overlap(per->ws, nw, per->pmax, 4))
+        return set_error(SHEMS_ERR_ARG, "%s: prio, pmax and the workspace overlap", fn);
+    for (const float v : {per->alpha, per->beta, per->eps_p})
+        if (!(v >= 0.0f) || !std::isfinite(v)) return set_error(SHEMS_ERR_ARG, "%s: alpha, beta and eps_p must be finite and >= 0", fn);
+    if (per->beta > 1.0f) return set_error(SHEMS_ERR_ARG, "%s: beta must be in [0, 1] (got %g)", fn, (double)per->beta);
+    if (fresh_pos < 0 || fresh_pos >= capacity || fresh_count < 0)
+        return set_error(SHEMS_ERR_ARG, "%s: the fresh range must start inside the ring and have a count >= 0", fn);
+    if (fresh_count > 0 && fresh_count < capacity && ring_len < capacity && fresh_pos + fresh_count > ring_len)
+        return set_error(SHEMS_ERR_ARG, "%s: the fresh range [%lld, +%lld) leaves the %lld filled slots", fn, (long long)fresh_pos,
+                         (long long)fresh_count, (long long)ring_len);
+    return SHEMS_OK;
+}
 // ADAM (Flux 0.12.1) + soft target update over n consecutive parameters, the data-parallel path's sweep (shems_ddpg.hip: k_adam_soft)
 // on any parameter count: the wide-network path (shems_wide.hip) applies its gradients with it.
 int adam_soft_sweep(float *p, const float *g, float *m, float *v, float *target, float *publish, int n, double eta, double bp1, double bp2,

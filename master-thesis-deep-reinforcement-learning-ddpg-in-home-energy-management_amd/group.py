@@ -863,11 +863,18 @@ class LearnerGroup:
             _capi.check(self.L.shems_ddpg_group_critic_apply(C.byref(d), C.byref(g), *adam_c, st))
             _capi.check(self.L.shems_ddpg_group_actor_grad(C.byref(d), C.byref(g), st))
             _capi.check(self.L.shems_ddpg_group_actor_apply(C.byref(d), C.byref(g), *adam_a, st))
-        for ag in self.learners:                   # the learners advance in lockstep: shared beta powers / update count
-            ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
-            ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
-            ag.updates += 1
+        self._advance_learners(critic=True, actor=True, counter="updates")
         self.updates += 1
+
+    def _advance_learners(self, critic, actor, counter):
+        """The learners advance in lockstep after a grouped update: the beta powers of the networks it stepped (shared by the group's
+        launches) and every learner's `counter` ("updates", "clones" or "evaluations")."""
+        for ag in self.learners:
+            if critic:
+                ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
+            if actor:
+                ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
+            setattr(ag, counter, getattr(ag, counter) + 1)
 
     # ---- grouped imitation: the supervised and the critic-only update for every learner ------------------------------------------------
     def _hp_variant(self, tau, check=True):
@@ -923,13 +930,7 @@ class LearnerGroup:
                            1 if self.store_grad else 0, self._stream()))
             if tl:
                 self._flux_valid = False
-            for ag in self.learners:               # the learners advance in lockstep, as in replay()
-                if critic:
-                    ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
-                    ag.evaluations += 1
-                else:
-                    ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
-                    ag.clones += 1
+            self._advance_learners(critic=critic, actor=not critic, counter="evaluations" if critic else "clones")
         else:                                      # latency form: the single-learner call on every learner's views, the same bits
             self._use_tiled()
             for ag, ring in zip(self.learners, objs):
@@ -1237,10 +1238,7 @@ class PrioritizedLearnerGroup(LearnerGroup):
                                                            flags | (_capi.TP_STORE_GRAD if self.store_grad else 0), self._stream()))
         if tl:
             self._flux_valid = False
-        for ag in self.learners:                   # the learners advance in lockstep, as in LearnerGroup.replay()
-            ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
-            ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
-            ag.updates += 1
+        self._advance_learners(critic=True, actor=True, counter="updates")
         self.updates += 1
 
     def replay(self, tick=None):

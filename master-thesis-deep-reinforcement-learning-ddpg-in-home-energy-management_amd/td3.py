@@ -292,11 +292,7 @@ class TD3LearnerGroup(G.LearnerGroup):
                                                      1 if self.store_grad else 0, self._stream()))
         if tl:
             self._flux_valid = False
-        for ag in self.learners:
-            ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
-            if policy:
-                ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
-            ag.updates += 1
+        self._advance_learners(critic=True, actor=policy, counter="updates")
         self.updates += 1
 
 
