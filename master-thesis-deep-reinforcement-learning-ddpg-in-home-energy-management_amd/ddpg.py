@@ -384,7 +384,12 @@ class Agent:
         self.eta_act, self.eta_crit = float(f32(ETA_ACT)), float(f32(ETA_CRIT))
         self.batch = BATCH_SIZE
         self.bp_actor = [0.9, 0.999]               # Flux ADAM state beta^t (Float64), advanced after every step
-        self.bp_critic = [0.9, 0.999]
+        self.bp_critic = [0.9, 0.999]              # by plain multiplication, no clamp.  The powers never leave (0, 1), which every entry
+                                                   # point insists on: 0.9^t is subnormal from update 6 724 on and sticks at 5 units of the
+                                                   # smallest subnormal (2.5e-323: 5 x 0.9 rounds back to 5) from update 7 050 on; 0.999^t is
+                                                   # 4.8e-32 after a thesis run (72 072 updates) and sticks at 499 units (2.5e-321) past
+                                                   # 700 000.  1 - bp1 == 1.0 from update 356, 1 - bp2 == 1.0 from update 37 412
+                                                   # (tests/test_adam_horizon_host.py holds all of it)
         self.updates = 0
         self.clones = 0                            # supervised updates on demonstrations (clone); they advance bp_actor, not `updates`
         self.evaluations = 0                       # critic-only updates (evaluate); they advance bp_critic, not `updates`
