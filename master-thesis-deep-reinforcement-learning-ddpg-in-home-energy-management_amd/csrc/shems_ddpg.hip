@@ -2011,47 +2011,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 constexpr int FWD_LDS = FwdShape<false>::LDS, QG_LDS = FWD_LDS > QG16_LDS ? FWD_LDS : QG16_LDS;
 constexpr int MID_LDS = FWD_LDS > E_LDS ? FWD_LDS : E_LDS;
 static_assert(QG_LDS <= 160 * 1024, "one workgroup's LDS");
-static int set_lds_attrs()
-{
-    static std::atomic<uint64_t> m_fwd{0}, m_mid{0}, m_grad{0};          // per device: see lds_optin
-    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd), QG_LDS, "attr k_fwd")) return rc;
-    if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid), MID_LDS, "attr k_mid")) return rc;
-    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad), GR_LDS, "attr k_grad")) return rc;
-    return SHEMS_OK;
-}
-// The supervised update's two kernels: asked by shems_ddpg_clone_update alone, so that the calls replay() makes stay as they are.
-static int set_lds_attrs_clone()
-{
-    static std::atomic<uint64_t> m_fwd{0}, m_grad{0};
-    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_clone), FWD_LDS, "attr k_fwd_clone")) return rc;
-    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_clone), GR_LDS, "attr k_grad_clone")) return rc;
-    return SHEMS_OK;
-}
-static int set_lds_attrs_tiled()
-{
-    static std::atomic<uint64_t> m_fwd{0}, m_mid{0}, m_grad{0};
-    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_t), QG_LDS, "attr k_fwd_t")) return rc;
-    if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid_t), MID_LDS, "attr k_mid_t")) return rc;
-    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_t), GR_LDS, "attr k_grad_t")) return rc;
-    return SHEMS_OK;
-}
+// ---- the host side: one launch plan.  Grids, each written once (the kernels' wrappers divide blockIdx.x by the same counts):
+constexpr unsigned FWD_TILES = NT * (BP / 32);             // one forward pass: 32-wide n-tiles x 32 columns
+constexpr unsigned FWD_WGS = FWD_TILES + 6;                // ... of K1, with the job's six publishing workgroups (see fwd_body)
+constexpr unsigned QG_TILES = NT16 * (BP / 32);            // K4's pass on 16-wide n-tiles
+constexpr unsigned E_WGS = KT * NQ;                        // one E product
+constexpr unsigned GRAD_WGS = GR_NW + GR_NG + GR_NR;       // one network's gradient launch
 
-static int set_lds_attrs_per()
-{
-    static std::atomic<uint64_t> m_fwd{0}, m_grad{0};
-    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_per), FWD_LDS, "attr k_fwd_per")) return rc;
-    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_per), GR_LDS, "attr k_grad_per")) return rc;
-    return SHEMS_OK;
-}
-
-static int set_lds_attrs_td3()
-{
-    static std::atomic<uint64_t> m_fwd{0}, m_mid{0}, m_grad{0};
-    if (int rc = lds_optin(m_fwd, reinterpret_cast<const void *>(&k_fwd_td3), FWD_LDS, "attr k_fwd_td3")) return rc;
-    if (int rc = lds_optin(m_mid, reinterpret_cast<const void *>(&k_mid_td3), MID_LDS, "attr k_mid_td3")) return rc;
-    if (int rc = lds_optin(m_grad, reinterpret_cast<const void *>(&k_grad_td3), GR_LDS, "attr k_grad_td3")) return rc;
-    return SHEMS_OK;
-}
+// A kernel with more than 64 KB of dynamic LDS: its largest launch and its own per-device opt-in mask (lds_optin).  launch() asks for
+// the opt-in, so a path opts in exactly the kernels it launches and no check makes a HIP call.
+template <class A> struct Kern { void (*fn)(A); int lds; const char *what; std::atomic<uint64_t> mask{0}; };
+static Kern<FwdArgs> K_FWD{k_fwd, QG_LDS, "attr k_fwd"}, K_FWD_T{k_fwd_t, QG_LDS, "attr k_fwd_t"}, K_FWD_CLONE{k_fwd_clone, FWD_LDS, "attr k_fwd_clone"};
+static Kern<MidArgs> K_MID{k_mid, MID_LDS, "attr k_mid"}, K_MID_T{k_mid_t, MID_LDS, "attr k_mid_t"};
+static Kern<GradArgs> K_GRAD{k_grad, GR_LDS, "attr k_grad"}, K_GRAD_T{k_grad_t, GR_LDS, "attr k_grad_t"}, K_GRAD_CLONE{k_grad_clone, GR_LDS, "attr k_grad_clone"};
+static Kern<PerFwdArgs> K_FWD_PER{k_fwd_per, FWD_LDS, "attr k_fwd_per"};
+static Kern<PerGradArgs> K_GRAD_PER{k_grad_per, GR_LDS, "attr k_grad_per"};
+static Kern<Td3FwdArgs> K_FWD_TD3{k_fwd_td3, FWD_LDS, "attr k_fwd_td3"};
+static Kern<Td3MidArgs> K_MID_TD3{k_mid_td3, MID_LDS, "attr k_mid_td3"};
+static Kern<Td3GradArgs> K_GRAD_TD3{k_grad_td3, GR_LDS, "attr k_grad_td3"};
+// The families: who runs a path's forward (K1, K4), middle (K2) and gradient launches (K3, K5).  kClone and kPer borrow k_mid; the actor
+// side of the given-slots and of the TD3 update is kPlain's.
+template <class F, class M, class G> struct Family { Kern<F> &fwd; Kern<M> &mid; Kern<G> &grad; };
+typedef Family<FwdArgs, MidArgs, GradArgs> Kernels;
+static const Kernels kPlain{K_FWD, K_MID, K_GRAD}, kTiled{K_FWD_T, K_MID_T, K_GRAD_T}, kClone{K_FWD_CLONE, K_MID, K_GRAD_CLONE};
+static const Family<PerFwdArgs, MidArgs, PerGradArgs> kPer{K_FWD_PER, K_MID, K_GRAD_PER};
+static const Family<Td3FwdArgs, Td3MidArgs, Td3GradArgs> kTd3{K_FWD_TD3, K_MID_TD3, K_GRAD_TD3};
 
 // ---- single learners on the tiled working layout: who they are ------------------------------------------------------------------
 // shems_ddpg_tiled_enter records a learner's eight Flux-order blocks (parameters, targets, moments) with its regions; until
@@ -2094,6 +2078,7 @@ int w2t_flux_guard(const float *block, const char *fn)
 
 using namespace shems;
 
+// ---- checks: arguments and host state, never a HIP call ---------------------------------------------------------------------------------
 // t: where the caller reads the layer-2 state from the tiled regions (shems_ddpg_update); every other caller speaks Flux order and is
 // refused while the regions are current.
 static int check_ddpg(const shems_ddpg *d, const char *fn, const shems_group_w2t *t = nullptr)
@@ -2104,10 +2089,10 @@ static int check_ddpg(const shems_ddpg *d, const char *fn, const shems_group_w2t
     if (d->batch < 1 || d->batch > BP) return set_error(SHEMS_ERR_ARG, "%s: batch must be in 1..128 (got %d)", fn, d->batch);
     for (const float *p : {d->actor, d->critic, d->actor_t, d->critic_t})
         if (((uintptr_t)p & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: parameter blocks must be 16-byte aligned", fn);
-    if (t) return set_lds_attrs_tiled();
+    if (t) return SHEMS_OK;
     for (const float *p : {d->actor, d->critic, d->actor_t, d->critic_t, d->m_actor, d->v_actor, d->m_critic, d->v_critic})
         if (int rc = w2t_flux_guard(p, fn)) return rc;
-    return set_lds_attrs();
+    return SHEMS_OK;
 }
 
 static int check_group(const shems_group *g, const char *fn)
@@ -2123,8 +2108,28 @@ static int check_adam(double bp1, double bp2, const char *fn)
     return SHEMS_OK;
 }
 
-struct AdamScalars { double eta, bp1, bp2, gscale; float *publish; };
+static int check_ring(const shems_replay *ring, int64_t ring_len, const char *fn)
+{
+    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
+        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    return SHEMS_OK;
+}
 
+// What K1..K3 refuse.  The messages name shems_ddpg_critic_grad (and _ex) whichever entry point was called, as the actor side's name
+// shems_ddpg_actor_grad: callers match on them.
+static int check_critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, int64_t excl_pos, int64_t excl_count,
+                             const shems_group_w2t *t = nullptr)
+{
+    if (int rc = check_ddpg(d, "shems_ddpg_critic_grad", t)) return rc;
+    if (int rc = check_ring(ring, ring_len, "shems_ddpg_critic_grad")) return rc;
+    if (excl_count < 0 || excl_pos < 0 || (excl_count > 0 && (ring_len != ring->capacity || excl_count >= ring_len)))
+        return set_error(SHEMS_ERR_ARG, "shems_ddpg_critic_grad_ex: an exclusion window needs a full ring and 0 <= count < capacity");
+    return SHEMS_OK;
+}
+
+// ---- one call's launch context ------------------------------------------------------------------------------------------------------------
+struct AdamScalars { double eta, bp1, bp2, gscale; float *publish; };
+static const AdamScalars kNoAdam{0, 0.5, 0.5, 1.0, nullptr};       // a gradient launch that applies nothing (split form): never read
 static AdamCtx adam_ctx(const shems_ddpg *d, bool critic, const AdamScalars &s)
 {
     const double k1 = s.eta / (1.0 - s.bp1), ic2 = 1.0 / (1.0 - s.bp2);
@@ -2135,122 +2140,139 @@ static AdamCtx adam_ctx(const shems_ddpg *d, bool critic, const AdamScalars &s)
 }
 
 struct GivenLaunch { const int32_t *idx; PerHead h; };
-
-// K1 + K2 + K3: the critic side of replay() (DDPG.jl:123-135).  fuse: K3 applies ADAM + the soft target update itself.
-// Data-parallel form only: the actor's two E products, when shems_ddpg.flags asked critic_grad to leave them out of K2 so that they
-// can run under the critic's gradient all-reduce (they need nothing the critic update produces).
-static int actor_e_launch(const shems_ddpg *d, unsigned L, int64_t gs, hipStream_t st)
+struct Ctx {
+    hipStream_t st;
+    unsigned L;                        // learners: grid z
+    int64_t gs;                        // slab stride in bytes, 0 for one learner
+    const shems_group_w2t *t;          // a single learner on the tiled working layout (L == 1, fused): its regions; else null
+    const GivenLaunch *gv;             // slots and weights are given (update_given / update_per): K1 and K3 are kPer's; else null
+    bool critic_only;                  // K1 without the actor's job, K2 without the actor's E products
+};
+static const shems_group kOne{1, 0, 0, 0};                            // a single learner
+static int64_t group_stride(const shems_group *g) { return g->count > 1 ? g->stride_bytes : 0; }
+static Ctx ctx(void *stream, const shems_group *g = &kOne, const shems_group_w2t *t = nullptr, const GivenLaunch *gv = nullptr, bool critic_only = false)
 {
-    float *ws = d->ws, *SA = slot(ws, SLOT_ACTOR);
-    MidArgs m;
-    std::memset(&m, 0, sizeof m);
-    m.gstride = gs; m.nfwd = 0;
-    m.e[0] = EJob{d->actor, SIN, 2, 0, SA + SL_H2, SA + SL_EP};
-    m.e[1] = EJob{d->actor, SIN, 2, 1, SA + SL_H2, ws + WS_EA1};
-    m.e[2] = m.e[1];
-    hipLaunchKernelGGL(k_mid, dim3(2 * KT * NQ, 1, L), dim3(256), E_LDS, st, m);
-    return hip_ok(hipGetLastError(), "k_mid (actor E) launch");
+    return Ctx{(hipStream_t)stream, (unsigned)g->count, group_stride(g), t, gv, critic_only};
+}
+static const Kernels &kernels(const Ctx &c) { return c.t ? kTiled : kPlain; }
+// the LDS opt-in of the kernel on this device (first launch only), then the launch
+template <class A>
+static int launch(const Ctx &c, Kern<A> &k, unsigned wgs, int lds, const A &args)
+{
+    if (int rc = lds_optin(k.mask, reinterpret_cast<const void *>(k.fn), k.lds, k.what)) return rc;
+    hipLaunchKernelGGL(k.fn, dim3(wgs, 1, c.L), dim3(256), lds, c.st, args);
+    return SHEMS_OK;
+}
+// K1 / K3 of the critic side: the context's family, or with given slots kPer's twin with the record appended
+static int launch_k1(const Ctx &c, unsigned wgs, const FwdArgs &f)
+{
+    return c.gv ? launch(c, kPer.fwd, wgs, FWD_LDS, PerFwdArgs{f, c.gv->idx}) : launch(c, kernels(c).fwd, wgs, FWD_LDS, f);
+}
+static int launch_k3(const Ctx &c, const GradArgs &g)
+{
+    return c.gv ? launch(c, kPer.grad, GRAD_WGS, GR_LDS, PerGradArgs{g, c.gv->h}) : launch(c, kernels(c).grad, GRAD_WGS, GR_LDS, g);
 }
 
-static int critic_side(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
-                       int64_t excl_pos, int64_t excl_count, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream,
-                       bool critic_only = false, const shems_group_w2t *t = nullptr, const GivenLaunch *gv = nullptr)
+// ---- jobs and records ---------------------------------------------------------------------------------------------------------------------
+// array 2 / 3 of a network's tiled region: its p / target (see w2t_idx); null in Flux order
+static const float *w2t(const Ctx &c, bool critic, int array) { return c.t ? (critic ? c.t->critic : c.t->actor) + array * W2T_TILE : nullptr; }
+// Where K1 leaves what the later launches read of a network they differentiate: its layer-1 image, its slot (SL_H2, SL_P3, SL_EP) and
+// its frozen W3 -- in ws, or for TD3's second critic in ws2.
+struct NetWs { const float *w1t; float *S; const float *w3f; };
+static NetWs critic_ws(float *ws) { return NetWs{w1t_of(ws, SLOT_CRITIC), slot(ws, SLOT_CRITIC), ws + WS_FW3C}; }
+static NetWs actor_ws(float *ws) { return NetWs{w1t_of(ws, SLOT_ACTOR), slot(ws, SLOT_ACTOR), ws + WS_FW3A}; }
+static NetWs critic2_ws(float *ws2) { return NetWs{ws2 + W2_W1T + 12 * 256, ws2 + W2_SLOT, ws2 + W2_FW3C}; }
+static const XSrc X_NONE{nullptr, nullptr, nullptr, nullptr, nullptr};       // K1: prep_column gathers the input
+static FwdJob job_actor_target(const Ctx &c, const shems_ddpg &d)           // K1: actor_target(s')
 {
-    // gv: slots and weights are given (shems_ddpg_update_given): K1 and K3 are k_fwd_per / k_grad_per, K2 is the same launch
-    // t: a single learner on the tiled working layout (L == 1, fused): W2 / moments / targets from the regions, the *_t kernels
-    if (int rc = check_ddpg(d, "shems_ddpg_critic_grad", t)) return rc;
-    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
-        return set_error(SHEMS_ERR_ARG, "shems_ddpg_critic_grad: bad replay ring / length");
-    if (excl_count < 0 || excl_pos < 0 || (excl_count > 0 && (ring_len != ring->capacity || excl_count >= ring_len)))
-        return set_error(SHEMS_ERR_ARG, "shems_ddpg_critic_grad_ex: an exclusion window needs a full ring and 0 <= count < capacity");
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = d->ws;
-    const XSrc none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    const XSrc x_s2a{ws + WS_X2T, nullptr, slot(ws, SLOT_ACTOR_T) + SL_P3, d->actor_t + off_b3(SIN, 2), nullptr};
-    const XSrc x_sa{ws + WS_XT, ws + WS_AT, nullptr, nullptr, nullptr};
-    float *SC = slot(ws, SLOT_CRITIC), *SA = slot(ws, SLOT_ACTOR);
-    FwdArgs f;
-    std::memset(&f, 0, sizeof f);
-    f.gstride = gs;
-    const unsigned fgx = NT * (BP / 32);
-    const int flds = FWD_LDS;
-    // K1: three independent forward passes; sample + gather + normalise + image packing + head freezing ride in this launch
-    f.job[0] = FwdJob{nullptr, d->actor_t, SIN, 2, 0, none, nullptr, slot(ws, SLOT_ACTOR_T) + SL_P3, nullptr, nullptr};
-    f.job[1] = FwdJob{nullptr, d->critic, CIN, 1, 1, none, SC + SL_H2, SC + SL_P3, nullptr, nullptr};
-    f.job[2] = FwdJob{nullptr, d->actor, SIN, 2, 2, none, SA + SL_H2, SA + SL_P3, nullptr, nullptr};
-    f.prep = 1;
-    f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count};
-    if (t) { f.job[0].W2t = t->actor + 3 * W2T_TILE; f.job[1].W2t = t->critic + 2 * W2T_TILE; f.job[2].W2t = t->actor + 2 * W2T_TILE; }
-    // + 6 publishing workgroups per job (see fwd_body); they do their work in job 0, so the critic-only update drops job 2 whole
-    if (gv) hipLaunchKernelGGL(k_fwd_per, dim3(3 * (fgx + 6), 1, 1), dim3(256), flds, st, PerFwdArgs{f, gv->idx});
-    else if (t) hipLaunchKernelGGL(k_fwd_t, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
-    else hipLaunchKernelGGL(k_fwd, dim3((critic_only ? 2 : 3) * (fgx + 6), 1, L), dim3(256), flds, st, f);
+    return FwdJob{nullptr, d.actor_t, SIN, 2, 0, X_NONE, nullptr, slot(d.ws, SLOT_ACTOR_T) + SL_P3, nullptr, nullptr, w2t(c, false, 3)};
+}
+static FwdJob job_critic(const Ctx &c, const float *critic, float *S)       // K1: critic(s, a), into slot S
+{
+    return FwdJob{nullptr, critic, CIN, 1, 1, X_NONE, S + SL_H2, S + SL_P3, nullptr, nullptr, w2t(c, true, 2)};
+}
+static FwdJob job_actor(const Ctx &c, const shems_ddpg &d)                  // K1: actor(s)
+{
+    float *SA = slot(d.ws, SLOT_ACTOR);
+    return FwdJob{nullptr, d.actor, SIN, 2, 2, X_NONE, SA + SL_H2, SA + SL_P3, nullptr, nullptr, w2t(c, false, 2)};
+}
+// K2: a target critic on [s'; actor_target(s')]; publish: where n-tile 0 leaves the action it computed (TD3's first target critic), or null
+static FwdJob job_critic_target(const Ctx &c, const shems_ddpg &d, const float *w1t, const float *critic_t, float *P3, float *publish)
+{
+    const XSrc x{d.ws + WS_X2T, nullptr, slot(d.ws, SLOT_ACTOR_T) + SL_P3, d.actor_t + off_b3(SIN, 2), publish};
+    return FwdJob{w1t, critic_t, CIN, 1, 0, x, nullptr, P3, nullptr, nullptr, w2t(c, true, 3)};
+}
+// K4: the critic as it stands now on [s; a_pi], a_pi = tanh(b3 + partials of the actor pass), forward + input gradient; workgroup 0
+// publishes a_pi for K5's head
+static FwdJob job_critic_through_actor(const Ctx &c, const shems_ddpg &d)
+{
+    float *ws = d.ws;
+    const XSrc x{ws + WS_XT, nullptr, slot(ws, SLOT_ACTOR) + SL_P3, d.actor + off_b3(SIN, 2), ws + WS_API};
+    return FwdJob{nullptr, d.critic, CIN, 1, 0, x, nullptr, slot(ws, SLOT_CRITIC2) + SL_P3, ws + WS_D3Q, ws + WS_DAP, w2t(c, true, 2)};
+}
+// K2's E products: a critic's (slot S), the actor's two outputs (e[0], e[1])
+static EJob e_critic(const Ctx &c, const float *critic, float *S) { return EJob{critic, CIN, 1, 0, S + SL_H2, S + SL_EP, w2t(c, true, 2)}; }
+static void e_actor(const Ctx &c, const shems_ddpg &d, EJob *e)
+{
+    float *SA = slot(d.ws, SLOT_ACTOR);
+    e[0] = EJob{d.actor, SIN, 2, 0, SA + SL_H2, SA + SL_EP, w2t(c, false, 2)};
+    e[1] = EJob{d.actor, SIN, 2, 1, SA + SL_H2, d.ws + WS_EA1, w2t(c, false, 2)};
+}
+// The gradient launch of d's critic (K3) or actor (K5) with loss head `head`; fuse: the launch applies ADAM + the soft update itself
+static GradArgs grad_args(const Ctx &c, const shems_ddpg &d, bool critic, const NetWs &w, int head, const AdamScalars *fuse)
+{
+    GradArgs g{};
+    g.w1t = w.w1t; g.P = critic ? d.critic : d.actor; g.in = critic ? CIN : SIN; g.out = critic ? 1 : 2;
+    g.x = XSrc{d.ws + WS_XT, critic ? d.ws + WS_AT : nullptr, nullptr, nullptr, nullptr};
+    g.H2 = w.S + SL_H2; g.w3f = w.w3f; g.grad = critic ? d.grad_critic : d.grad_actor;
+    g.E0 = w.S + SL_EP; g.E1 = critic ? nullptr : d.ws + WS_EA1; g.head = head; g.fuse = fuse ? 1 : 0; g.dd = d; g.gstride = c.gs;
+    g.c = adam_ctx(&d, critic, fuse ? *fuse : kNoAdam);
+    g.w2t = c.t ? (critic ? c.t->critic : c.t->actor) : nullptr;
+    return g;
+}
+
+// ---- phases ---------------------------------------------------------------------------------------------------------------------------------
+// K1 + K2 + K3: the critic side of replay() (DDPG.jl:123-135).  fuse: K3 applies ADAM + the soft target update itself.
+static int critic_phases(const Ctx &c, const shems_ddpg *d, const PrepArgs &pa, const AdamScalars *fuse)
+{
+    // K1: three independent forward passes; sample + gather + normalise + image packing + head freezing ride in this launch.  The
+    // publishing workgroups do their work in job 0, so the critic-only update drops job 2 whole
+    const NetWs wc = critic_ws(d->ws);
+    FwdArgs f{};
+    f.gstride = c.gs; f.prep = 1; f.pa = pa;
+    f.job[0] = job_actor_target(c, *d); f.job[1] = job_critic(c, d->critic, wc.S); f.job[2] = job_actor(c, *d);
+    if (int rc = launch_k1(c, (c.critic_only ? 2 : 3) * FWD_WGS, f)) return rc;
     // K2: critic_target on [s'; actor_target(s')] | E of the critic | E of the actor's two outputs
-    MidArgs m;
-    std::memset(&m, 0, sizeof m);
-    m.gstride = gs; m.nfwd = (int)fgx;
-    m.fwd = FwdJob{w1t_of(ws, SLOT_CRITIC_T), d->critic_t, CIN, 1, 0, x_s2a, nullptr, slot(ws, SLOT_CRITIC_T) + SL_P3, nullptr, nullptr};
-    m.e[0] = EJob{d->critic, CIN, 1, 0, SC + SL_H2, SC + SL_EP};
-    m.e[1] = EJob{d->actor, SIN, 2, 0, SA + SL_H2, SA + SL_EP};
-    m.e[2] = EJob{d->actor, SIN, 2, 1, SA + SL_H2, ws + WS_EA1};
-    if (t) {
-        m.fwd.W2t = t->critic + 3 * W2T_TILE; m.e[0].W2t = t->critic + 2 * W2T_TILE;
-        m.e[1].W2t = m.e[2].W2t = t->actor + 2 * W2T_TILE;
-    }
-    const bool defer_ea = critic_only || (!fuse && (d->flags & SHEMS_DDPG_DEFER_ACTOR_E) != 0);   // the caller runs shems_ddpg_actor_prepare later, or never
-    if (t) hipLaunchKernelGGL(k_mid_t, dim3(fgx + (defer_ea ? 1 : 3) * KT * NQ, 1, L), dim3(256), MID_LDS, st, m);
-    else hipLaunchKernelGGL(k_mid, dim3(fgx + (defer_ea ? 1 : 3) * KT * NQ, 1, L), dim3(256), MID_LDS, st, m);
+    MidArgs m{};
+    m.gstride = c.gs; m.nfwd = (int)FWD_TILES;
+    m.fwd = job_critic_target(c, *d, w1t_of(d->ws, SLOT_CRITIC_T), d->critic_t, slot(d->ws, SLOT_CRITIC_T) + SL_P3, nullptr);
+    m.e[0] = e_critic(c, d->critic, wc.S); e_actor(c, *d, m.e + 1);
+    const bool defer_ea = c.critic_only || (!fuse && (d->flags & SHEMS_DDPG_DEFER_ACTOR_E) != 0);   // the caller runs shems_ddpg_actor_prepare later, or never
+    if (int rc = launch(c, kernels(c).mid, FWD_TILES + (defer_ea ? 1 : 3) * E_WGS, MID_LDS, m)) return rc;
     // K3: critic gradient (+ ADAM + soft update)
-    GradArgs g;
-    std::memset(&g, 0, sizeof g);
-    g.w1t = w1t_of(ws, SLOT_CRITIC); g.P = d->critic; g.in = CIN; g.out = 1; g.x = x_sa; g.H2 = SC + SL_H2; g.w3f = ws + WS_FW3C;
-    g.grad = d->grad_critic; g.E0 = SC + SL_EP; g.E1 = nullptr; g.head = 1; g.fuse = fuse ? 1 : 0; g.dd = *d; g.gstride = gs;
-    g.c = adam_ctx(d, true, fuse ? *fuse : AdamScalars{0, 0.5, 0.5, 1.0, nullptr});
-    g.w2t = t ? t->critic : nullptr;
-    if (gv) hipLaunchKernelGGL(k_grad_per, dim3(GR_NW + GR_NG + GR_NR, 1, 1), dim3(256), GR_LDS, st, PerGradArgs{g, gv->h});
-    else if (t) hipLaunchKernelGGL(k_grad_t, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
-    else hipLaunchKernelGGL(k_grad, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
+    if (int rc = launch_k3(c, grad_args(c, *d, true, wc, 1, fuse))) return rc;
     return hip_ok(hipGetLastError(), "ddpg critic-side launches");
 }
 
 // K4 + K5: the actor side (DDPG.jl:137-140), through the critic as it stands now (already updated)
-static int actor_side(const shems_ddpg *d, unsigned L, int64_t gs, const AdamScalars *fuse, void *stream, const shems_group_w2t *t = nullptr)
+static int actor_phases(const Ctx &c, const shems_ddpg *d, const AdamScalars *fuse)
 {
-    if (int rc = check_ddpg(d, "shems_ddpg_actor_grad", t)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = d->ws;
-    // critic on [s; a_pi], a_pi = tanh(b3 + partials of the actor pass); workgroup 0 publishes a_pi for K5's head
-    const XSrc x_spi{ws + WS_XT, nullptr, slot(ws, SLOT_ACTOR) + SL_P3, d->actor + off_b3(SIN, 2), ws + WS_API};
-    const XSrc x_s{ws + WS_XT, nullptr, nullptr, nullptr, nullptr};
-    float *C2 = slot(ws, SLOT_CRITIC2), *SA = slot(ws, SLOT_ACTOR);
-    FwdArgs f;
-    std::memset(&f, 0, sizeof f);
-    f.gstride = gs;
-    const unsigned fgx = NT16 * (BP / 32);
-    f.prep = 2;
-    f.job[0] = FwdJob{nullptr, d->critic, CIN, 1, 0, x_spi, nullptr, C2 + SL_P3, ws + WS_D3Q, ws + WS_DAP};
-    GradArgs g;
-    std::memset(&g, 0, sizeof g);
-    g.w1t = w1t_of(ws, SLOT_ACTOR); g.P = d->actor; g.in = SIN; g.out = 2; g.x = x_s; g.H2 = SA + SL_H2; g.w3f = ws + WS_FW3A;
-    g.grad = d->grad_actor; g.E0 = SA + SL_EP; g.E1 = ws + WS_EA1; g.head = 2; g.fuse = fuse ? 1 : 0; g.dd = *d; g.gstride = gs;
-    g.c = adam_ctx(d, false, fuse ? *fuse : AdamScalars{0, 0.5, 0.5, 1.0, nullptr});
-    if (t) {
-        f.job[0].W2t = t->critic + 2 * W2T_TILE; g.w2t = t->actor;
-        hipLaunchKernelGGL(k_fwd_t, dim3(fgx, 1, L), dim3(256), QG16_LDS, st, f);
-        hipLaunchKernelGGL(k_grad_t, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
-        return hip_ok(hipGetLastError(), "ddpg actor-side launches");
-    }
-    hipLaunchKernelGGL(k_fwd, dim3(fgx, 1, L), dim3(256), QG16_LDS, st, f);
-    hipLaunchKernelGGL(k_grad, dim3(GR_NW + GR_NG + GR_NR, 1, L), dim3(256), GR_LDS, st, g);
+    FwdArgs f{};
+    f.gstride = c.gs; f.prep = 2; f.job[0] = job_critic_through_actor(c, *d);
+    if (int rc = launch(c, kernels(c).fwd, QG_TILES, QG16_LDS, f)) return rc;
+    if (int rc = launch(c, kernels(c).grad, GRAD_WGS, GR_LDS, grad_args(c, *d, false, actor_ws(d->ws), 2, fuse))) return rc;
     return hip_ok(hipGetLastError(), "ddpg actor-side launches");
 }
 
-static int adam_launch(const shems_ddpg *d, bool critic, const AdamScalars &s, hipStream_t st, unsigned L, int64_t gs)
+// The actor's two E products alone: the supervised update, and the data-parallel form when shems_ddpg.flags asked critic_grad to leave
+// them out of K2 so that they can run under the critic's gradient all-reduce (they need nothing the critic update produces).
+static int actor_e_phase(const Ctx &c, const shems_ddpg *d)
 {
-    if (int rc = check_adam(s.bp1, s.bp2, "adam")) return rc;
-    const AdamCtx c = adam_ctx(d, critic, s);
-    hipLaunchKernelGGL(k_adam_soft, dim3((c.n + 1023) / 1024, 1, L), dim3(256), 0, st, c, gs);
-    return hip_ok(hipGetLastError(), "k_adam_soft launch");
+    MidArgs m{};
+    m.gstride = c.gs; m.nfwd = 0;
+    e_actor(c, *d, m.e); m.e[2] = m.e[1];
+    if (int rc = launch(c, kPlain.mid, 2 * E_WGS, E_LDS, m)) return rc;
+    return hip_ok(hipGetLastError(), "k_mid (actor E) launch");
 }
 
 namespace shems {
@@ -2281,7 +2303,7 @@ int adam_soft_sweep_group(float *p, const float *g, float *m, float *v, float *t
 }
 }  // namespace shems
 
-extern "C" {
+extern "C" {           // ---- entry points: their own checks, the context, the phases
 
 #ifdef SHEMS_STAMP
 /* diagnostic build only: d_buf = device buffer of 5 * 1024 * 16 * 2 uint64 (or NULL to switch the stamps off) */
@@ -2310,23 +2332,23 @@ int shems_ddpg_sample_indices(uint64_t seed, uint32_t tick, int32_t batch, int64
     return SHEMS_OK;
 }
 
-/* replay() in one call, single replica: K1..K5 with ADAM + soft updates inside the gradient launches. */
+/* replay() in one call, single replica: K1..K5 with ADAM + soft updates inside the gradient launches.  A learner on the tiled working
+ * layout takes W2, its moments and its targets from its regions (kTiled). */
 int shems_ddpg_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                       int64_t excl_pos, int64_t excl_count, double eta_crit, double bp1_crit, double bp2_crit,
                       double eta_act, double bp1_act, double bp2_act, float *d_publish, void *stream)
 {
     if (int rc = check_adam(bp1_crit, bp2_crit, "shems_ddpg_update")) return rc;
     if (int rc = check_adam(bp1_act, bp2_act, "shems_ddpg_update")) return rc;
+    shems_group_w2t regions;
+    const shems_group_w2t *t = d && w2t_lookup(d->actor, &regions) ? &regions : nullptr;
+    // the second copy of the updated actor (the pipelined modes) is a Flux-order block: its W2 range would need the scattered stores back
+    if (t && d_publish) return set_error(SHEMS_ERR_STATE, "shems_ddpg_update: d_publish is not written from the tiled working layout");
+    if (int rc = check_critic_side(d, ring, ring_len, excl_pos, excl_count, t)) return rc;
     const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr}, sa{eta_act, bp1_act, bp2_act, 1.0, d_publish};
-    shems_group_w2t t;
-    if (d && w2t_lookup(d->actor, &t)) {
-        // the second copy of the updated actor (the pipelined modes) is a Flux-order block: its W2 range would need the scattered stores back
-        if (d_publish) return set_error(SHEMS_ERR_STATE, "shems_ddpg_update: d_publish is not written from the tiled working layout");
-        if (int rc = critic_side(d, ring, ring_len, seed, tick, excl_pos, excl_count, 1, 0, &sc, stream, false, &t)) return rc;
-        return actor_side(d, 1, 0, &sa, stream, &t);
-    }
-    if (int rc = critic_side(d, ring, ring_len, seed, tick, excl_pos, excl_count, 1, 0, &sc, stream)) return rc;
-    return actor_side(d, 1, 0, &sa, stream);
+    const Ctx c = ctx(stream, &kOne, t);
+    if (int rc = critic_phases(c, d, PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count}, &sc)) return rc;
+    return actor_phases(c, d, &sa);
 }
 
 /* A single learner on the tiled working layout: see shems_hip.h. */
@@ -2336,8 +2358,7 @@ int shems_ddpg_tiled_enter(const shems_ddpg *d, const shems_group_w2t *t, void *
     if (int rc = check_ddpg(d, fn)) return rc;                 // (a learner that has entered already: SHEMS_ERR_STATE)
     if (!t || !t->actor || !t->critic || ((uintptr_t)t->actor & 127) != 0 || ((uintptr_t)t->critic & 127) != 0)
         return set_error(SHEMS_ERR_ARG, "%s: shems_group_w2t needs two 128-byte aligned device regions", fn);
-    const shems_group one{1, 0, 0, 0};
-    if (int rc = shems_group_w2_to_tiled(d, &one, t, stream)) return rc;
+    if (int rc = shems_group_w2_to_tiled(d, &kOne, t, stream)) return rc;
     TiledGuard lock;
     if (g_ntiled == (int)(sizeof g_tiled / sizeof g_tiled[0])) return set_error(SHEMS_ERR_STATE, "%s: too many learners on the tiled layout", fn);
     g_tiled[g_ntiled++] = TiledLearner{{d->actor, d->critic, d->actor_t, d->critic_t, d->m_actor, d->v_actor, d->m_critic, d->v_critic}, *t};
@@ -2349,8 +2370,7 @@ int shems_ddpg_tiled_leave(const shems_ddpg *d, void *stream)
     const char *fn = "shems_ddpg_tiled_leave";
     shems_group_w2t t;
     if (!d || !w2t_lookup(d->actor, &t)) return set_error(SHEMS_ERR_STATE, "%s: this learner is not on the tiled layout", fn);
-    const shems_group one{1, 0, 0, 0};
-    if (int rc = shems_group_w2_to_flux(d, &one, &t, stream)) return rc;
+    if (int rc = shems_group_w2_to_flux(d, &kOne, &t, stream)) return rc;
     TiledGuard lock;
     const int i = tiled_find(d->actor);
     if (i >= 0) g_tiled[i] = g_tiled[--g_ntiled];
@@ -2365,57 +2385,44 @@ int shems_ddpg_tiled_current(const shems_ddpg *d, int32_t *out)
 }
 
 /* One supervised update of the actor on demonstrations: K1's actor job alone, the actor's two E products, the actor's gradient
- * launch with the cloning head (ADAM + soft update inside).  Nothing of the critic is written. */
+ * launch with the cloning head (ADAM + soft update inside) -- kClone, instantiations of their own, so that the kernels replay() runs
+ * stay as they are.  Nothing of the critic is written. */
 int shems_ddpg_clone_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                             double eta, double bp1, double bp2, float *d_publish, void *stream)
 {
     const char *fn = "shems_ddpg_clone_update";
     if (int rc = check_adam(bp1, bp2, fn)) return rc;
     if (int rc = check_ddpg(d, fn)) return rc;
-    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
-        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
-    if (int rc = set_lds_attrs_clone()) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = d->ws, *SA = slot(ws, SLOT_ACTOR);
-    const XSrc none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    const XSrc x_s{ws + WS_XT, nullptr, nullptr, nullptr, nullptr};
+    if (int rc = check_ring(ring, ring_len, fn)) return rc;
     const AdamScalars sa{eta, bp1, bp2, 1.0, d_publish};
-    FwdArgs f;
-    std::memset(&f, 0, sizeof f);
-    f.job[0] = FwdJob{nullptr, d->actor, SIN, 2, 2, none, SA + SL_H2, SA + SL_P3, nullptr, nullptr};
-    f.prep = 1;
-    f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, 0, 0};
-    hipLaunchKernelGGL(k_fwd_clone, dim3(NT * (BP / 32) + 6), dim3(256), FWD_LDS, st, f);
-    if (int rc = actor_e_launch(d, 1, 0, st)) return rc;
-    GradArgs g;
-    std::memset(&g, 0, sizeof g);
-    g.w1t = w1t_of(ws, SLOT_ACTOR); g.P = d->actor; g.in = SIN; g.out = 2; g.x = x_s; g.H2 = SA + SL_H2; g.w3f = ws + WS_FW3A;
-    g.grad = d->grad_actor; g.E0 = SA + SL_EP; g.E1 = ws + WS_EA1; g.head = 3; g.fuse = 1; g.dd = *d; g.gstride = 0;
-    g.c = adam_ctx(d, false, sa);
-    hipLaunchKernelGGL(k_grad_clone, dim3(GR_NW + GR_NG + GR_NR), dim3(256), GR_LDS, st, g);
+    const Ctx c = ctx(stream);
+    FwdArgs f{};
+    f.prep = 1; f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, 0, 0}; f.job[0] = job_actor(c, *d);
+    if (int rc = launch(c, kClone.fwd, FWD_WGS, FWD_LDS, f)) return rc;
+    if (int rc = actor_e_phase(c, d)) return rc;
+    if (int rc = launch(c, kClone.grad, GRAD_WGS, GR_LDS, grad_args(c, *d, false, actor_ws(d->ws), 3, &sa))) return rc;
     return hip_ok(hipGetLastError(), "ddpg clone-update launches");
 }
 
-/* Policy evaluation: the critic side of replay() alone, with K1 and K2 cut down to what the critic reads (critic_side). */
+/* Policy evaluation: the critic side of replay() alone, with K1 and K2 cut down to what the critic reads (Ctx.critic_only). */
 int shems_ddpg_critic_update(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                              double eta, double bp1, double bp2, void *stream)
 {
     if (int rc = check_adam(bp1, bp2, "shems_ddpg_critic_update")) return rc;
+    if (int rc = check_critic_side(d, ring, ring_len, 0, 0)) return rc;
     const AdamScalars sc{eta, bp1, bp2, 1.0, nullptr};
-    return critic_side(d, ring, ring_len, seed, tick, 0, 0, 1, 0, &sc, stream, true);
+    return critic_phases(ctx(stream, &kOne, nullptr, nullptr, true), d, PrepArgs{*d, *ring, ring_len, seed, tick, 0, 0}, &sc);
 }
 
 /* ---- prioritized replay (shems_per_core.h) ---- */
-// everything shems_ddpg_update refuses for (d, ring, ring_len), with nothing launched
+// everything shems_ddpg_update refuses for (d, ring, ring_len)
 static int check_given(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, double bp1c, double bp2c, double bp1a, double bp2a,
                        const char *fn)
 {
     if (int rc = check_adam(bp1c, bp2c, fn)) return rc;
     if (int rc = check_adam(bp1a, bp2a, fn)) return rc;
     if (int rc = check_ddpg(d, fn)) return rc;
-    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
-        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
-    return set_lds_attrs_per();
+    return check_ring(ring, ring_len, fn);
 }
 static int per_sample_launch(const shems_per *per, int64_t capacity, int64_t ring_len, int64_t fresh_pos, int64_t fresh_count, uint64_t seed,
                              uint32_t tick, int32_t batch, hipStream_t st)
@@ -2439,11 +2446,13 @@ int shems_per_sample_dev(const shems_per *per, int64_t capacity, int64_t ring_le
     return per_sample_launch(per, capacity, ring_len, fresh_pos, fresh_count, seed, tick, batch, (hipStream_t)stream);
 }
 
+// K1..K5 on the slots and weights of gv (checked by the caller): K1 and K3 are kPer's, the rest replay()'s own
 static int update_given_launch(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, const GivenLaunch &gv, const AdamScalars &sc,
                                const AdamScalars &sa, void *stream)
 {
-    if (int rc = critic_side(d, ring, ring_len, 0, 0, 0, 0, 1, 0, &sc, stream, false, nullptr, &gv)) return rc;
-    return actor_side(d, 1, 0, &sa, stream);
+    const Ctx c = ctx(stream, &kOne, nullptr, &gv);
+    if (int rc = critic_phases(c, d, PrepArgs{*d, *ring, ring_len, 0, 0, 0, 0}, &sc)) return rc;
+    return actor_phases(c, d, &sa);
 }
 
 int shems_ddpg_update_given(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, const int32_t *d_idx, const float *d_w,
@@ -2482,8 +2491,9 @@ int shems_td3_workspace_floats(int64_t *out)
     return SHEMS_OK;
 }
 
-/* One TD3 update: see shems_hip.h.  Three launches with both critics in each (k_fwd_td3, k_mid_td3, k_grad_td3); a policy step adds
- * replay()'s own K4 + K5 through the updated critic 1. */
+/* One TD3 update: see shems_hip.h.  Three launches with both critics in each (kTd3); the second critic's jobs and records are the first
+ * one's builders on ws2 and a copy of d that names critic 2's blocks.  A policy step adds replay()'s own K4 + K5 through the updated
+ * critic 1. */
 int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
                      double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy, void *stream)
 {
@@ -2492,8 +2502,7 @@ int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_
     const shems_ddpg *d = &t->d;
     if (int rc = check_adam(bp1_crit, bp2_crit, fn)) return rc;
     if (int rc = check_adam(bp1_act, bp2_act, fn)) return rc;
-    if (!ring || !ring->s || !ring->a || !ring->r || !ring->s2 || !ring->done || ring_len < 1 || ring_len > ring->capacity)
-        return set_error(SHEMS_ERR_ARG, "%s: bad replay ring / length", fn);
+    if (int rc = check_ring(ring, ring_len, fn)) return rc;
     if (update_policy != 0 && update_policy != 1) return set_error(SHEMS_ERR_ARG, "%s: update_policy must be 0 or 1 (got %d)", fn, update_policy);
     if (!(t->sigma_trg >= 0.0f) || !(t->clip_trg >= 0.0f) || t->sigma_trg > 3.0e38f || t->clip_trg > 3.0e38f)
         return set_error(SHEMS_ERR_ARG, "%s: sigma_trg and clip_trg must be finite and >= 0", fn);
@@ -2506,78 +2515,53 @@ int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_
     if (d->critic && d->critic_t && d->m_critic && d->v_critic && d->grad_critic) {
         const float *one[5] = {d->critic, d->critic_t, d->m_critic, d->v_critic, d->grad_critic};
         const float *two[5] = {t->critic2, t->critic2_t, t->m_critic2, t->v_critic2, t->grad_critic2};
+        const size_t nb = (size_t)SHEMS_CRITIC_PARAMS * 4;
         for (int i = 0; i < 5; ++i)
             for (int j = 0; j < 5; ++j) {
-                if (two[i] < one[j] + SHEMS_CRITIC_PARAMS && one[j] < two[i] + SHEMS_CRITIC_PARAMS)
-                    return set_error(SHEMS_ERR_ARG, "%s: a critic-2 buffer overlaps one of critic 1's", fn);
-                if (i < j && two[i] < two[j] + SHEMS_CRITIC_PARAMS && two[j] < two[i] + SHEMS_CRITIC_PARAMS)
-                    return set_error(SHEMS_ERR_ARG, "%s: two critic-2 buffers overlap", fn);
+                if (ranges_overlap(two[i], nb, one[j], nb)) return set_error(SHEMS_ERR_ARG, "%s: a critic-2 buffer overlaps one of critic 1's", fn);
+                if (i < j && ranges_overlap(two[i], nb, two[j], nb)) return set_error(SHEMS_ERR_ARG, "%s: two critic-2 buffers overlap", fn);
             }
-        if (d->ws && t->ws2 < d->ws + WS_FLOATS && d->ws < t->ws2 + W2_FLOATS) return set_error(SHEMS_ERR_ARG, "%s: ws2 overlaps ws", fn);
-        if (d->losses && t->losses2 < d->losses + 2 && d->losses < t->losses2 + 1) return set_error(SHEMS_ERR_ARG, "%s: losses2 overlaps losses", fn);
+        if (d->ws && ranges_overlap(t->ws2, (size_t)W2_FLOATS * 4, d->ws, (size_t)WS_FLOATS * 4)) return set_error(SHEMS_ERR_ARG, "%s: ws2 overlaps ws", fn);
+        if (d->losses && ranges_overlap(t->losses2, 4, d->losses, 8)) return set_error(SHEMS_ERR_ARG, "%s: losses2 overlaps losses", fn);
     }
     if (int rc = check_ddpg(d, fn)) return rc;                 // NULLs, batch, alignment; a learner on the tiled layout: SHEMS_ERR_STATE
-    if (int rc = set_lds_attrs_td3()) return rc;
-    hipStream_t st = (hipStream_t)stream;
+    const Ctx c = ctx(stream);
     float *ws = d->ws, *ws2 = t->ws2;
-    const XSrc none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    const XSrc x_sa{ws + WS_XT, ws + WS_AT, nullptr, nullptr, nullptr};
-    float *SC = slot(ws, SLOT_CRITIC), *SA = slot(ws, SLOT_ACTOR), *S2 = ws2 + W2_SLOT;
-    float *PT1 = slot(ws, SLOT_CRITIC_T) + SL_P3, *PT2 = ws2 + W2_PT, *PAT = slot(ws, SLOT_ACTOR_T) + SL_P3;
-    const unsigned tiles = NT * (BP / 32);
+    const NetWs w1 = critic_ws(ws), w2 = critic2_ws(ws2);
+    float *PT1 = slot(ws, SLOT_CRITIC_T) + SL_P3, *PT2 = ws2 + W2_PT;
     // T1
-    Td3FwdArgs f;
-    std::memset(&f, 0, sizeof f);
-    f.job[0] = FwdJob{nullptr, d->actor_t, SIN, 2, 0, none, nullptr, PAT, nullptr, nullptr};
-    f.job[1] = FwdJob{nullptr, d->critic, CIN, 1, 1, none, SC + SL_H2, SC + SL_P3, nullptr, nullptr};
-    f.job[2] = FwdJob{nullptr, t->critic2, CIN, 1, 1, none, S2 + SL_H2, S2 + SL_P3, nullptr, nullptr};
-    f.job[3] = FwdJob{nullptr, d->actor, SIN, 2, 2, none, SA + SL_H2, SA + SL_P3, nullptr, nullptr};
-    f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, 0, 0};
-    f.c2 = t->critic2; f.c2t = t->critic2_t; f.ws2 = ws2;
-    hipLaunchKernelGGL(k_fwd_td3, dim3((update_policy ? 4 : 3) * (tiles + 6)), dim3(256), FWD_LDS, st, f);
+    Td3FwdArgs f{};
+    f.job[0] = job_actor_target(c, *d); f.job[1] = job_critic(c, d->critic, w1.S); f.job[2] = job_critic(c, t->critic2, w2.S); f.job[3] = job_actor(c, *d);
+    f.pa = PrepArgs{*d, *ring, ring_len, seed, tick, 0, 0}; f.c2 = t->critic2; f.c2t = t->critic2_t; f.ws2 = ws2;
+    if (int rc = launch(c, kTd3.fwd, (update_policy ? 4 : 3) * FWD_WGS, FWD_LDS, f)) return rc;
     // T2
-    Td3MidArgs m;
-    std::memset(&m, 0, sizeof m);
-    const XSrc x_s2a{ws + WS_X2T, nullptr, PAT, d->actor_t + off_b3(SIN, 2), ws2 + W2_AT};
-    XSrc x_s2b = x_s2a;
-    x_s2b.publish = nullptr;
-    m.fwd[0] = FwdJob{w1t_of(ws, SLOT_CRITIC_T), d->critic_t, CIN, 1, 0, x_s2a, nullptr, PT1, nullptr, nullptr};
-    m.fwd[1] = FwdJob{ws2 + W2_W1T, t->critic2_t, CIN, 1, 0, x_s2b, nullptr, PT2, nullptr, nullptr};
-    m.e[0] = EJob{d->critic, CIN, 1, 0, SC + SL_H2, SC + SL_EP};
-    m.e[1] = EJob{t->critic2, CIN, 1, 0, S2 + SL_H2, S2 + SL_EP};
-    m.e[2] = EJob{d->actor, SIN, 2, 0, SA + SL_H2, SA + SL_EP};
-    m.e[3] = EJob{d->actor, SIN, 2, 1, SA + SL_H2, ws + WS_EA1};
+    Td3MidArgs m{};
+    m.fwd[0] = job_critic_target(c, *d, w1t_of(ws, SLOT_CRITIC_T), d->critic_t, PT1, ws2 + W2_AT);
+    m.fwd[1] = job_critic_target(c, *d, ws2 + W2_W1T, t->critic2_t, PT2, nullptr);
+    m.e[0] = e_critic(c, d->critic, w1.S); m.e[1] = e_critic(c, t->critic2, w2.S); e_actor(c, *d, m.e + 2);
     m.tn = Td3Noise{seed, tick, t->sigma_trg, t->clip_trg};
-    hipLaunchKernelGGL(k_mid_td3, dim3(2 * tiles + (update_policy ? 4 : 2) * KT * NQ), dim3(256), MID_LDS, st, m);
+    if (int rc = launch(c, kTd3.mid, 2 * FWD_TILES + (update_policy ? 4 : 2) * E_WGS, MID_LDS, m)) return rc;
     // T3: off a policy step the critics' targets stay (tau = 0: 1 t + 0 p)
     const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr};
     shems_ddpg d2 = *d;
     d2.critic = t->critic2; d2.critic_t = t->critic2_t; d2.m_critic = t->m_critic2; d2.v_critic = t->v_critic2;
     d2.grad_critic = t->grad_critic2; d2.losses = t->losses2;
-    Td3GradArgs g;
-    std::memset(&g, 0, sizeof g);
-    for (int i = 0; i < 2; ++i) {
-        const shems_ddpg *di = i == 0 ? d : &d2;
-        float *Si = i == 0 ? SC : S2;
-        GradArgs &G = g.g[i];
-        G.w1t = i == 0 ? w1t_of(ws, SLOT_CRITIC) : ws2 + W2_W1T + 12 * 256;
-        G.P = di->critic; G.in = CIN; G.out = 1; G.x = x_sa; G.H2 = Si + SL_H2; G.w3f = i == 0 ? ws + WS_FW3C : ws2 + W2_FW3C;
-        G.grad = di->grad_critic; G.E0 = Si + SL_EP; G.E1 = nullptr; G.head = 1; G.fuse = 1; G.dd = *di; G.gstride = 0;
-        G.c = adam_ctx(di, true, sc);
-        if (!update_policy) G.c.tau = 0.0f;
-        g.h[i] = i == 0 ? TwinHead{PT1, PT2, SC + SL_P3, ws + WS_FB3 + 1, ws2 + W2_FB3 + 1, ws + WS_FB3 + 0, ws + WS_Y, ws + WS_Q, ws + WS_D3C,
-                                   ws2 + W2_QT1, ws2 + W2_QT2}
-                        : TwinHead{PT1, PT2, S2 + SL_P3, ws + WS_FB3 + 1, ws2 + W2_FB3 + 1, ws2 + W2_FB3 + 0, ws2 + W2_Y, ws2 + W2_Q, ws2 + W2_D3C,
-                                   nullptr, nullptr};
-    }
-    hipLaunchKernelGGL(k_grad_td3, dim3(2 * (GR_NW + GR_NG + GR_NR)), dim3(256), GR_LDS, st, g);
+    Td3GradArgs g{};
+    g.g[0] = grad_args(c, *d, true, w1, 1, &sc); g.g[1] = grad_args(c, d2, true, w2, 1, &sc);
+    if (!update_policy) g.g[0].c.tau = g.g[1].c.tau = 0.0f;
+    g.h[0] = TwinHead{PT1, PT2, w1.S + SL_P3, ws + WS_FB3 + 1, ws2 + W2_FB3 + 1, ws + WS_FB3 + 0, ws + WS_Y, ws + WS_Q, ws + WS_D3C,
+                      ws2 + W2_QT1, ws2 + W2_QT2};
+    g.h[1] = TwinHead{PT1, PT2, w2.S + SL_P3, ws + WS_FB3 + 1, ws2 + W2_FB3 + 1, ws2 + W2_FB3 + 0, ws2 + W2_Y, ws2 + W2_Q, ws2 + W2_D3C,
+                      nullptr, nullptr};
+    if (int rc = launch(c, kTd3.grad, 2 * GRAD_WGS, GR_LDS, g)) return rc;
     if (int rc = hip_ok(hipGetLastError(), "td3 critic-side launches")) return rc;
     if (!update_policy) return SHEMS_OK;
     // the actor through the updated critic 1, ADAM, the actor's soft update: replay()'s K4 + K5 as they are (DDPG.jl:137-140)
     const AdamScalars sa{eta_act, bp1_act, bp2_act, 1.0, nullptr};
-    return actor_side(d, 1, 0, &sa, stream);
+    return actor_phases(c, d, &sa);
 }
 
+/* The latency form of learner groups: the same phases with grid z = learner. */
 int shems_ddpg_group_update(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int64_t ring_len, uint64_t seed,
                             uint32_t tick, double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act,
                             double bp2_act, void *stream)
@@ -2585,72 +2569,85 @@ int shems_ddpg_group_update(const shems_ddpg *d0, const shems_replay *ring0, con
     if (int rc = check_group(g, "shems_ddpg_group_update")) return rc;
     if (int rc = check_adam(bp1_crit, bp2_crit, "shems_ddpg_group_update")) return rc;
     if (int rc = check_adam(bp1_act, bp2_act, "shems_ddpg_group_update")) return rc;
+    if (int rc = check_critic_side(d0, ring0, ring_len, 0, 0)) return rc;
     const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr}, sa{eta_act, bp1_act, bp2_act, 1.0, nullptr};
-    const int64_t gs = g->count > 1 ? g->stride_bytes : 0;
-    if (int rc = critic_side(d0, ring0, ring_len, seed, tick, 0, 0, (unsigned)g->count, gs, &sc, stream)) return rc;
-    return actor_side(d0, (unsigned)g->count, gs, &sa, stream);
+    const Ctx c = ctx(stream, g);
+    if (int rc = critic_phases(c, d0, PrepArgs{*d0, *ring0, ring_len, seed, tick, 0, 0}, &sc)) return rc;
+    return actor_phases(c, d0, &sa);
+}
+
+/* The split form (data-parallel replicas, parameter noise, sub-batches): the two gradient halves, the E products on their own, the sweeps. */
+int shems_ddpg_critic_grad_ex(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                              int64_t excl_pos, int64_t excl_count, void *stream)
+{
+    if (int rc = check_critic_side(d, ring, ring_len, excl_pos, excl_count)) return rc;
+    return critic_phases(ctx(stream), d, PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count}, nullptr);
 }
 
 int shems_ddpg_critic_grad(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                            void *stream)
 {
-    return critic_side(d, ring, ring_len, seed, tick, 0, 0, 1, 0, nullptr, stream);
-}
-
-int shems_ddpg_critic_grad_ex(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
-                              int64_t excl_pos, int64_t excl_count, void *stream)
-{
-    return critic_side(d, ring, ring_len, seed, tick, excl_pos, excl_count, 1, 0, nullptr, stream);
+    return shems_ddpg_critic_grad_ex(d, ring, ring_len, seed, tick, 0, 0, stream);
 }
 
 int shems_ddpg_group_critic_grad(const shems_ddpg *d0, const shems_replay *ring0, const shems_group *g, int64_t ring_len,
                                  uint64_t seed, uint32_t tick, void *stream)
 {
     if (int rc = check_group(g, "shems_ddpg_group_critic_grad")) return rc;
-    return critic_side(d0, ring0, ring_len, seed, tick, 0, 0, (unsigned)g->count, g->count > 1 ? g->stride_bytes : 0, nullptr, stream);
+    if (int rc = check_critic_side(d0, ring0, ring_len, 0, 0)) return rc;
+    return critic_phases(ctx(stream, g), d0, PrepArgs{*d0, *ring0, ring_len, seed, tick, 0, 0}, nullptr);
 }
 
 int shems_ddpg_actor_prepare(const shems_ddpg *d, void *stream)
 {
     if (int rc = check_ddpg(d, "shems_ddpg_actor_prepare")) return rc;
-    return actor_e_launch(d, 1, 0, (hipStream_t)stream);
+    return actor_e_phase(ctx(stream), d);
 }
 
-int shems_ddpg_critic_apply(const shems_ddpg *d, double eta, double bp1, double bp2, double grad_scale, void *stream)
+int shems_ddpg_actor_grad(const shems_ddpg *d, void *stream)
 {
-    if (int rc = check_ddpg(d, "shems_ddpg_critic_apply")) return rc;
-    return adam_launch(d, true, AdamScalars{eta, bp1, bp2, grad_scale, nullptr}, (hipStream_t)stream, 1, 0);
+    if (int rc = check_ddpg(d, "shems_ddpg_actor_grad")) return rc;
+    return actor_phases(ctx(stream), d, nullptr);
 }
-
-int shems_ddpg_group_critic_apply(const shems_ddpg *d, const shems_group *g, double eta, double bp1, double bp2, void *stream)
-{
-    if (int rc = check_ddpg(d, "shems_ddpg_group_critic_apply")) return rc;
-    if (int rc = check_group(g, "shems_ddpg_group_critic_apply")) return rc;
-    return adam_launch(d, true, AdamScalars{eta, bp1, bp2, 1.0, nullptr}, (hipStream_t)stream, (unsigned)g->count,
-                       g->count > 1 ? g->stride_bytes : 0);
-}
-
-int shems_ddpg_actor_grad(const shems_ddpg *d, void *stream) { return actor_side(d, 1, 0, nullptr, stream); }
 
 int shems_ddpg_group_actor_grad(const shems_ddpg *d0, const shems_group *g, void *stream)
 {
     if (int rc = check_group(g, "shems_ddpg_group_actor_grad")) return rc;
-    return actor_side(d0, (unsigned)g->count, g->count > 1 ? g->stride_bytes : 0, nullptr, stream);
+    if (int rc = check_ddpg(d0, "shems_ddpg_actor_grad")) return rc;
+    return actor_phases(ctx(stream, g), d0, nullptr);
+}
+
+// the five sweeps of the split form: fn's checks of d and g (kOne: a single learner), the beta powers, one k_adam_soft launch (no LDS)
+static int apply(const char *fn, const shems_ddpg *d, const shems_group *g, bool critic, const AdamScalars &s, void *stream)
+{
+    if (int rc = check_ddpg(d, fn)) return rc;
+    if (int rc = check_group(g, fn)) return rc;
+    if (int rc = check_adam(s.bp1, s.bp2, "adam")) return rc;
+    const Ctx c = ctx(stream, g);
+    const AdamCtx a = adam_ctx(d, critic, s);
+    hipLaunchKernelGGL(k_adam_soft, dim3((a.n + 1023) / 1024, 1, c.L), dim3(256), 0, c.st, a, c.gs);
+    return hip_ok(hipGetLastError(), "k_adam_soft launch");
+}
+
+int shems_ddpg_critic_apply(const shems_ddpg *d, double eta, double bp1, double bp2, double grad_scale, void *stream)
+{
+    return apply("shems_ddpg_critic_apply", d, &kOne, true, AdamScalars{eta, bp1, bp2, grad_scale, nullptr}, stream);
+}
+
+int shems_ddpg_group_critic_apply(const shems_ddpg *d, const shems_group *g, double eta, double bp1, double bp2, void *stream)
+{
+    return apply("shems_ddpg_group_critic_apply", d, g, true, AdamScalars{eta, bp1, bp2, 1.0, nullptr}, stream);
 }
 
 int shems_ddpg_group_actor_apply(const shems_ddpg *d, const shems_group *g, double eta, double bp1, double bp2, void *stream)
 {
-    if (int rc = check_ddpg(d, "shems_ddpg_group_actor_apply")) return rc;
-    if (int rc = check_group(g, "shems_ddpg_group_actor_apply")) return rc;
-    return adam_launch(d, false, AdamScalars{eta, bp1, bp2, 1.0, nullptr}, (hipStream_t)stream, (unsigned)g->count,
-                       g->count > 1 ? g->stride_bytes : 0);
+    return apply("shems_ddpg_group_actor_apply", d, g, false, AdamScalars{eta, bp1, bp2, 1.0, nullptr}, stream);
 }
 
 int shems_ddpg_actor_apply_pub(const shems_ddpg *d, double eta, double bp1, double bp2, double grad_scale, float *d_publish,
                                void *stream)
 {
-    if (int rc = check_ddpg(d, "shems_ddpg_actor_apply")) return rc;
-    return adam_launch(d, false, AdamScalars{eta, bp1, bp2, grad_scale, d_publish}, (hipStream_t)stream, 1, 0);
+    return apply("shems_ddpg_actor_apply", d, &kOne, false, AdamScalars{eta, bp1, bp2, grad_scale, d_publish}, stream);
 }
 
 int shems_ddpg_actor_apply(const shems_ddpg *d, double eta, double bp1, double bp2, double grad_scale, void *stream)
@@ -2703,7 +2700,7 @@ int shems_minmax_group_dev(const shems_replay *ring, const shems_group *g, int64
     if (!ring || !ring->s || ring_len < 1 || ring_len > ring->capacity || count < 1 || !d_s_min || !d_s_max)
         return set_error(SHEMS_ERR_ARG, "shems_minmax_group_dev: bad arguments");
     hipLaunchKernelGGL(k_minmax, dim3((unsigned)g->count), dim3(1024), 0, (hipStream_t)stream, *ring, ring_len, count, seed, d_s_min,
-                       d_s_max, g->count > 1 ? g->stride_bytes : (int64_t)0);
+                       d_s_max, group_stride(g));
     return hip_ok(hipGetLastError(), "k_minmax launch");
 }
 

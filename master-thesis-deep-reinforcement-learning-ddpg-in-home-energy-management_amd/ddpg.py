@@ -58,6 +58,11 @@ def anneal_beta(beta0, update, total):
     return min(1.0, beta0 + (1.0 - beta0) * (float(update) / float(total)))
 
 
+def _pub(publish):
+    """The d_publish argument: the tensor that also receives the updated actor, or NULL."""
+    return C.c_void_p(publish.data_ptr()) if publish is not None else None
+
+
 class DdpgArgs(C.Structure):           # shems_ddpg
     _fields_ = [(n, C.c_void_p) for n in ("actor", "critic", "actor_t", "critic_t", "m_actor", "v_actor", "m_critic",
                                           "v_critic", "grad_actor", "grad_critic", "s_min", "s_max", "ws", "losses")] + \
@@ -707,8 +712,18 @@ class Agent:
             return _capi.check(self.L.shems_wide_actor_grad(C.byref(d), *self.whidden, st))
         _capi.check(self.L.shems_ddpg_actor_grad(C.byref(d), st))
 
+    def _advance(self, critic, actor, counter):
+        """After an update: the beta powers of the networks it stepped advance -- a plain product, a new list -- and `counter`
+        ("updates", "clones" or "evaluations") counts it; None where the update's second half is still to come."""
+        for name, stepped in (("bp_critic", critic), ("bp_actor", actor)):
+            if stepped:
+                bp = getattr(self, name)
+                setattr(self, name, [bp[0] * 0.9, bp[1] * 0.999])
+        if counter is not None:
+            setattr(self, counter, getattr(self, counter) + 1)
+
     def _actor_apply_pub(self, d, gs, publish, st):
-        pub = C.c_void_p(publish.data_ptr()) if publish is not None else None
+        pub = _pub(publish)
         if self.wide:
             return _capi.check(self.L.shems_wide_actor_apply_pub(C.byref(d), *self.whidden, self.eta_act, self.bp_actor[0], self.bp_actor[1], gs, pub, st))
         _capi.check(self.L.shems_ddpg_actor_apply_pub(C.byref(d), self.eta_act, self.bp_actor[0], self.bp_actor[1], gs, pub, st))
@@ -732,7 +747,7 @@ class Agent:
         # the ADAM / soft-update sweeps work on the learner's own (combined) gradient buffers; they do not look at `batch`
         dm = self._ddpg_args(dict(ga=self.grad_actor, gc=self.grad_critic, ws=self.ws, losses=self.losses, batch=subs[0]["batch"]))
         self._critic_apply(dm, gs, st)
-        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
+        self._advance(critic=True, actor=False, counter=None)
         for i, sb in enumerate(subs):
             d = self._ddpg_args(sb)
             self._actor_grad(d, st)
@@ -741,8 +756,7 @@ class Agent:
             _capi.check(self.L.shems_ddpg_combine_dev(vp(self.losses[1:]), vp(sb["losses"][1:]), 1, 0.0 if i == 0 else 1.0, w, st))
         self._allreduce(self.grad_actor)
         self._actor_apply_pub(dm, gs, publish, st)
-        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-        self.updates += 1
+        self._advance(critic=False, actor=True, counter="updates")
 
     def enable_data_parallel(self, dist, native=None):
         """Replicas (one per GPU, each with its own env shard and ring) all-reduce gradients over RCCL.  native: a shems_dp communicator
@@ -779,21 +793,16 @@ class Agent:
             # replay() is one call (K1..K5, csrc/shems_ddpg.hip)
             _capi.check(self.L.shems_ddpg_update(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt,
                                                  self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
-                                                 self.bp_actor[1], C.c_void_p(publish.data_ptr()) if publish is not None else None, st))
-            self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
-            self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-            self.updates += 1
+                                                 self.bp_actor[1], _pub(publish), st))
+            self._advance(critic=True, actor=True, counter="updates")
             return
         if self.sync.native is not None and self.sync.world > 1 and self.noise_type != "pn" and not self.wide:
             # replicas with a native communicator: the split form and both all-reduces in ONE call, everything in this stream
             d.flags = 0                             # (no deferred E products: nothing runs beside an in-stream exchange)
             _capi.check(self.L.shems_ddpg_update_dp(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt,
                                                     self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
-                                                    self.bp_actor[1], C.c_void_p(publish.data_ptr()) if publish is not None else None,
-                                                    self.sync.native, st))
-            self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
-            self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-            self.updates += 1
+                                                    self.bp_actor[1], _pub(publish), self.sync.native, st))
+            self._advance(critic=True, actor=True, counter="updates")
             return
         self._critic_grad_ex(d, rs, len(ring), tick, ex_pos, ex_cnt, st)
         if self.noise_type == "pn":                # DDPG.jl:126-128 (the actor is still the pre-update one here)
@@ -810,12 +819,11 @@ class Agent:
             self._allreduce(self.grad_critic)
         gs = self.sync.grad_scale
         self._critic_apply(d, gs, st)
-        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
+        self._advance(critic=True, actor=False, counter=None)
         self._actor_grad(d, st)
         self._allreduce(self.grad_actor)
         self._actor_apply_pub(d, gs, publish, st)
-        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-        self.updates += 1
+        self._advance(critic=False, actor=True, counter="updates")
 
     def _replay_per(self, ring, tick=None, exclude=None, publish=None):
         """replay() on a prioritized ring (shems_ddpg_update_per: the sampler launch, then K1..K5 with the weighted critic head and
@@ -847,9 +855,7 @@ class Agent:
                                             int(tick) & 0xFFFFFFFF, self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act,
                                             self.bp_actor[0], self.bp_actor[1], self._stream()))
         ring.covered = ring.pushed
-        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
-        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-        self.updates += 1
+        self._advance(critic=True, actor=True, counter="updates")
 
     def replay_given(self, ring, idx, weights):
         """replay() on slots and weights the caller supplies (shems_ddpg_update_given): idx int32 [128] (-1 in the pad columns) and
@@ -867,9 +873,7 @@ class Agent:
         _capi.check(_declare_per().shems_ddpg_update_given(C.byref(d), C.byref(rs), len(ring), idx.data_ptr(), weights.data_ptr(), self.eta_crit,
                                                            self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
                                                            self.bp_actor[1], self._stream()))
-        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
-        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-        self.updates += 1
+        self._advance(critic=True, actor=True, counter="updates")
 
     def clone(self, demos, tick=None, tau=1.0, publish=None):
         """One SUPERVISED update of the actor on demonstrations (imitation.Demos, or any ring whose s and a hold (observation,
@@ -895,10 +899,8 @@ class Agent:
         rs = demos.struct()
         tick = self.clones if tick is None else tick
         _capi.check(self.L.shems_ddpg_clone_update(C.byref(d), C.byref(rs), len(demos), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_act,
-                                                   self.bp_actor[0], self.bp_actor[1],
-                                                   C.c_void_p(publish.data_ptr()) if publish is not None else None, self._stream()))
-        self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-        self.clones += 1
+                                                   self.bp_actor[0], self.bp_actor[1], _pub(publish), self._stream()))
+        self._advance(critic=False, actor=True, counter="clones")
 
     def evaluate(self, ring, tick=None, tau=None):
         """One CRITIC-ONLY update (policy evaluation) from `ring`: update_model!(critic, ...) and soft_update!(critic_target, critic) of
@@ -926,8 +928,7 @@ class Agent:
         tick = self.evaluations if tick is None else tick
         _capi.check(self.L.shems_ddpg_critic_update(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_crit,
                                                     self.bp_critic[0], self.bp_critic[1], self._stream()))
-        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
-        self.evaluations += 1
+        self._advance(critic=True, actor=False, counter="evaluations")
 
     def sample_indices(self, tick, ring_len, batch=None):
         batch = self.batch if batch is None else int(batch)

@@ -870,11 +870,7 @@ class LearnerGroup:
         """The learners advance in lockstep after a grouped update: the beta powers of the networks it stepped (shared by the group's
         launches) and every learner's `counter` ("updates", "clones" or "evaluations")."""
         for ag in self.learners:
-            if critic:
-                ag.bp_critic = [ag.bp_critic[0] * 0.9, ag.bp_critic[1] * 0.999]
-            if actor:
-                ag.bp_actor = [ag.bp_actor[0] * 0.9, ag.bp_actor[1] * 0.999]
-            setattr(ag, counter, getattr(ag, counter) + 1)
+            Agent._advance(ag, critic, actor, counter)
 
     # ---- grouped imitation: the supervised and the critic-only update for every learner ------------------------------------------------
     def _hp_variant(self, tau, check=True):

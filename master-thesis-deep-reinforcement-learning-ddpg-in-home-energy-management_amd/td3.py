@@ -412,7 +412,4 @@ class TD3Agent(D.Agent):
         _capi.check(self.L.shems_td3_update(C.byref(a), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_crit,
                                             self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0], self.bp_actor[1],
                                             1 if policy else 0, self._stream()))
-        self.bp_critic = [self.bp_critic[0] * 0.9, self.bp_critic[1] * 0.999]
-        if policy:
-            self.bp_actor = [self.bp_actor[0] * 0.9, self.bp_actor[1] * 0.999]
-        self.updates += 1
+        self._advance(critic=True, actor=policy, counter="updates")
