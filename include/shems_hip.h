@@ -381,6 +381,42 @@ int shems_td3_workspace_floats(int64_t *out);
 int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
                      double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act,
                      int update_policy, void *stream);
+/* --------------------------- behaviour-regularised actor update (TD3+BC) -- */
+/* One update of replay() (shems_ddpg_update) or of TD3 (shems_td3_update) with only the ACTOR's loss changed to the TD3+BC objective
+ * (Fujimoto, Gu 2021): the normalised critic value plus a mean-squared pull towards the ring's stored action.  The reference has no
+ * such loss; the definition is this one (csrc/shems_bc_core.h holds the scalar arithmetic).  With B = batch, the live
+ * columns m < B, a_pi = actor(s_n) as K4 forms it, a = the ring's stored, unscaled action of the minibatch, and
+ * q_m = critic([s_n; a_pi])_m through the critic AS UPDATED BY THIS SAME UPDATE (critic 1 for TD3):
+ *   1. Qbar = (1/B) sum_{m<B} |q_m|;
+ *   2. lambda = normalise ? alpha / max(Qbar, 1e-8f) : alpha -- a constant of the update: no gradient flows through it;
+ *   3. loss_act = -lambda mean_m(q_m) + weight Flux.mse(a_pi, a), the mse over the 2 B elements (as shems_ddpg_clone_update has it);
+ *   4. at the actor's output, for m < B: d loss / d a_pi[o][m] = lambda da[o][m] + weight (a_pi - a)[o][m] / B, where da is the sum of
+ *      K4's 32 partials of d(-mean q) / d a_pi, in the order shems_ddpg_update sums them; pad columns m >= B contribute 0 to both terms
+ *      and to Qbar; then through tanh, d3 = (...) (1 - a_pi^2);
+ *   5. everything downstream is the actor's gradient launch as it is: every gradient block, ADAM and the soft update of actor_t in the
+ *      workgroup that made the gradient, the d_publish copy.  The critic side is untouched.
+ * The paper's values are alpha = 2.5, weight = 1, normalise = 1.  With normalise = 0, alpha = 1, weight = 0 the update leaves
+ * shems_ddpg_update's (shems_td3_update's) bits; with alpha = 0 it is the cloning gradient on the update's minibatch.
+ * The same launches as the plain entry points, the last one replaced by k_grad_bc (csrc/shems_ddpg.hip).
+ * out: a 16-byte aligned device buffer of the caller's, SHEMS_BC_OUT_FLOATS = 4 + 128 floats, written by the actor's gradient launch:
+ * out[0] = lambda, out[1] = Qbar, out[2] = -mean q, out[3] = mse(a_pi, a), out[4 + m] = q_m (columns >= batch are padding).  losses[1]
+ * receives loss_act.  shems_td3_update_bc with update_policy = 0 checks bc and neither reads nor writes out.
+ * SHEMS_ERR_ARG, nothing launched: whatever the plain entry point refuses; NULL bc or out; misaligned out; out overlapping ws, ws2,
+ * losses, losses2 or a parameter, moment or gradient block; alpha or weight negative or not finite; normalise outside {0, 1};
+ * reserved != 0.  SHEMS_ERR_STATE: a learner between shems_ddpg_tiled_enter and shems_ddpg_tiled_leave (the tiled layout has no
+ * behaviour-regularised gradient launch). */
+#define SHEMS_BC_OUT_FLOATS (4 + 128)
+typedef struct shems_bc {
+    float alpha, weight;         /* 2.5, 1 (the paper's)                                             */
+    int32_t normalise, reserved; /* 1 = lambda = alpha / Qbar; reserved = 0                          */
+    float *out;                  /* [SHEMS_BC_OUT_FLOATS] device, 16-byte aligned                    */
+} shems_bc;
+int shems_ddpg_update_bc(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                         int64_t excl_pos, int64_t excl_count, double eta_crit, double bp1_crit, double bp2_crit,
+                         double eta_act, double bp1_act, double bp2_act, float *d_publish, const shems_bc *bc, void *stream);
+int shems_td3_update_bc(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                        double eta_crit, double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act,
+                        int update_policy, const shems_bc *bc, void *stream);
 /* ------------------------------------------- prioritized replay update -- */
 /* Prioritized experience replay (Schaul et al. 2016, proportional variant) for the single learner, in replay()'s conventions.  The
  * reference has no such sampler; the definition is this one (csrc/shems_per_core.h states it again with every summation order;

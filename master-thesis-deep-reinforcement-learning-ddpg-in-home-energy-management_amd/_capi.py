@@ -221,6 +221,37 @@ def declare_pbt():
     return L
 
 
+class BcArgs(C.Structure):             # shems_bc
+    _fields_ = [("alpha", C.c_float), ("weight", C.c_float), ("normalise", C.c_int32), ("reserved", C.c_int32), ("out", C.c_void_p)]
+
+
+BC_OUT_FLOATS = 4 + 128                # SHEMS_BC_OUT_FLOATS: lambda, Qbar, -mean q, mse, q [128]
+assert C.sizeof(BcArgs) == 24
+
+
+def _bc_sigs():
+    """The behaviour-regularised updates (shems_ddpg * and shems_td3 * go as void pointers: their mirrors live in ddpg.py / td3.py)."""
+    vp, i64, u64, u32, dbl = C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.c_double
+    PB, PR_ = C.POINTER(BcArgs), C.POINTER(Replay)
+    return {
+        "shems_ddpg_update_bc": [vp, PR_, i64, u64, u32, i64, i64, dbl, dbl, dbl, dbl, dbl, dbl, vp, PB, vp],
+        "shems_td3_update_bc": [vp, PR_, i64, u64, u32, dbl, dbl, dbl, dbl, dbl, dbl, C.c_int, PB, vp],
+    }
+
+
+def declare_bc():
+    """The prototypes of _bc_sigs (compared with include/shems_hip.h by tests/test_bc_host.py)."""
+    L = lib()
+    if getattr(L, "_bc_declared", False):
+        return L
+    for name, args in _bc_sigs().items():
+        fn = getattr(L, name)
+        fn.argtypes = args
+        fn.restype = C.c_int
+    L._bc_declared = True
+    return L
+
+
 def exported_symbols():
     """Names include/shems_hip.h declares (used by the CPU-side ABI test)."""
     import re

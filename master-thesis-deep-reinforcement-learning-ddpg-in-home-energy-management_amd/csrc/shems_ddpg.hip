@@ -46,6 +46,7 @@
 #include "shems_adam.h"
 #include "shems_td3_core.h"
 #include "shems_per_core.h"
+#include "shems_bc_core.h"
 
 namespace shems {
 
@@ -1255,6 +1256,70 @@ __device__ __forceinline__ void head_clone(const shems_ddpg &d, const HeadRegs &
     }
 }
 
+// ---- behaviour-regularised actor head (shems_ddpg_update_bc / shems_td3_update_bc; shems_bc_core.h), head_actor's compile-time sibling
+// in the prologue of every workgroup of k_grad_bc.  Every workgroup needs lambda before it can form d3, so each forms q_m for all 128
+// columns -- critic b3 + K4's NT16 partials of SLOT_CRITIC2 + SL_P3, in the publisher's order -- and reduces |q_m| over m < batch in a
+// fixed order (wave sums of waves 0 and 1, then (w0 + w1) through LDS; no atomics).  d3[o][m] = (lambda da + weight (a_pi - a) / B)
+// (1 - a_pi^2) for m < batch, 0 in the pad columns (the workspace holds non-zero a_pi there: the mask keeps them out).  da is summed as
+// head_actor sums it; with lambda = 1 and weight = 0 the head leaves head_actor's bits.  Workgroup 0 publishes d3, gb3, losses[1] and the
+// caller's record out = {lambda, Qbar, -mean q, mse, q[128]}.  All loads join the workgroup's first batch.
+struct BcHead { float alpha, weight; int32_t normalise; float *out; };
+struct BcRegs { float dap[NT16]; float qp[NT16]; float api, at, b3; };
+__device__ __forceinline__ void head_actor_bc_load(const shems_ddpg &d, BcRegs &R)
+{
+    const float *ws = d.ws;
+    const int t = threadIdx.x, o = t >> 7, m = t & 127;
+    const float *Pq = slot(d.ws, SLOT_CRITIC2) + SL_P3;
+#pragma unroll
+    for (int p = 0; p < NT16; ++p) R.dap[p] = ws[WS_DAP + (int64_t)(p * 2 + o) * BP + m];
+#pragma unroll
+    for (int i = 0; i < NT16; ++i) R.qp[i] = Pq[i * BP + m];           // K4's 32 tiles of 16 hidden units (both halves load: no predicate)
+    R.api = ws[WS_API + t];
+    R.at = ws[WS_AT + t];
+    R.b3 = d.critic[off_b3(CIN, 1)];                                   // the critic as updated by this update; nobody writes it in this launch
+}
+__device__ __forceinline__ void head_actor_bc(const shems_ddpg &d, const BcHead &h, const BcRegs &R, float *d3 /*LDS [2][BP]*/, float *red /*LDS [8]*/,
+                                              float *scr /*LDS, >= 8 words*/, bool publisher, const AdamCtx *fuse)
+{
+    float *ws = d.ws;
+    const int t = threadIdx.x, o = t >> 7, m = t & 127;
+    const bool live = m < d.batch;
+    float qm = R.b3;
+#pragma unroll
+    for (int i = 0; i < NT16; ++i) qm += R.qp[i];
+    const float sa = wave_sum((o == 0 && live) ? fabsf(qm) : 0.0f);
+    if ((t & 63) == 0) scr[t >> 6] = sa;
+    __syncthreads();
+    const float qbar = (scr[0] + scr[1]) / (float)d.batch;
+    const float lam = bc_lambda(h.alpha, qbar, h.normalise);
+    const float a = R.api;
+    float da = 0.0f;
+#pragma unroll
+    for (int p = 0; p < NT16; ++p) da += R.dap[p];
+    const float diff = live ? a - R.at : 0.0f;
+    const float dl = live ? bc_dloss(lam, da, h.weight, diff, (float)d.batch) : 0.0f;
+    const float g = dl * (1.0f - a * a);                       // through tanh
+    d3[t] = g;
+    if (publisher) {
+        ws[WS_D3A + t] = g;
+        if (o == 0) h.out[4 + m] = qm;
+        const float q = (o == 0 && live) ? qm : 0.0f;
+        const float sg = wave_sum(g), sq = wave_sum(q), sl = wave_sum(diff * diff);
+        if ((t & 63) == 0) { red[t >> 6] = sg; red[4 + (t >> 6)] = sq; scr[4 + (t >> 6)] = sl; }
+        __syncthreads();
+        if (t == 0) {
+            const float g0 = red[0] + red[1], g1 = red[2] + red[3];
+            d.grad_actor[off_b3(SIN, 2) + 0] = g0;
+            d.grad_actor[off_b3(SIN, 2) + 1] = g1;
+            const float nmq = -(red[4] + red[5]) / (float)d.batch;                                   // head_actor's losses[1]
+            const float mse = ((scr[4] + scr[5]) + (scr[6] + scr[7])) / (2.0f * (float)d.batch);     // head_clone's
+            d.losses[1] = bc_loss(lam, nmq, h.weight, mse);
+            h.out[0] = lam; h.out[1] = qbar; h.out[2] = nmq; h.out[3] = mse;
+            if (fuse) { adam_elem(*fuse, off_b3(SIN, 2), g0); adam_elem(*fuse, off_b3(SIN, 2) + 1, g1); }
+        }
+    }
+}
+
 // ---- TD3: the second workspace block and the twin head (shems_td3_update) --------------------------------------------------
 // ws2 carve (floats).  The first four arrays are what shems_hip.h promises a caller can read after an update.
 constexpr int64_t W2_AT = 0;                          // [2][BP]  a~' = clamp(actor_t(s') + eps, -1, 1)
@@ -1492,8 +1557,10 @@ __device__ __forceinline__ void l1row_wave(const L1Row<IN, OUT> &R, const float 
 
 // CLONE: the supervised update's instantiation (k_grad_clone) takes the cloning head at compile time; otherwise GradArgs.head decides.
 // PER: the weighted critic head of the prioritized update (k_grad_per), head_loss's compile-time sibling.
-template <int IN, int OUT, bool CLONE = false, bool TILED = false, bool TWIN = false, bool PER = false>
-__device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx, const TwinHead *th = nullptr, const PerHead *ph = nullptr)
+// BC: the behaviour-regularised actor head (k_grad_bc), head_actor's compile-time sibling.
+template <int IN, int OUT, bool CLONE = false, bool TILED = false, bool TWIN = false, bool PER = false, bool BC = false>
+__device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const int bx, const TwinHead *th = nullptr, const PerHead *ph = nullptr,
+                                          const BcHead *bh = nullptr)
 {
     // bx: this workgroup's index within the gradient grid
     float *Bt = smem;                          // W: [32 n][GR_PS] D2 panel
@@ -1522,12 +1589,15 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
         l1row_load<IN, OUT>(A, min(k, H1N - 1), lane, R);
         [[maybe_unused]] TwinRegs tr;
         [[maybe_unused]] PerRegs pg;
-        if constexpr (PER) { head_loss_load(A.dd, hr); head_per_load(*ph, pg, false); }
+        [[maybe_unused]] BcRegs br;
+        if constexpr (BC) head_actor_bc_load(A.dd, br);
+        else if constexpr (PER) { head_loss_load(A.dd, hr); head_per_load(*ph, pg, false); }
         else if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
         else if constexpr (CLONE) head_clone_load(A.dd, hr);
         else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
         STAMP(kRegion, 1);
-        if constexpr (PER) head_per(A.dd, *ph, hr, pg, d3, red, smem, false, nullptr);
+        if constexpr (BC) head_actor_bc(A.dd, *bh, br, d3, red, smem, false, nullptr);
+        else if constexpr (PER) head_per(A.dd, *ph, hr, pg, d3, red, smem, false, nullptr);
         else if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, false, nullptr);
         else if constexpr (CLONE) head_clone(A.dd, hr, d3, red, false, nullptr);
         else if (A.head == 1) head_loss(A.dd, hr, d3, red, false, nullptr); else head_actor(A.dd, hr, d3, red, false, nullptr);
@@ -1597,7 +1667,9 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
     HeadRegs hr;
     [[maybe_unused]] TwinRegs tr;
     [[maybe_unused]] PerRegs pg;
-    if constexpr (PER) { head_loss_load(A.dd, hr); head_per_load(*ph, pg, publisher); }
+    [[maybe_unused]] BcRegs br;
+    if constexpr (BC) head_actor_bc_load(A.dd, br);
+    else if constexpr (PER) { head_loss_load(A.dd, hr); head_per_load(*ph, pg, publisher); }
     else if constexpr (TWIN) head_twin_load(A.dd, *th, tr);
     else if constexpr (CLONE) head_clone_load(A.dd, hr);
     else if (A.head == 1) head_loss_load(A.dd, hr); else head_actor_load(A.dd, hr);
@@ -1605,7 +1677,8 @@ __device__ __forceinline__ void grad_body(const GradArgs &A, float *smem, const 
         build_x_store<IN>(A.x, xr, xs, false);
         if (tid < 96) *reinterpret_cast<f32x4 *>(w1 + (tid >> 3) * 32 + 4 * (tid & 7)) = wq;
     }
-    if constexpr (PER) head_per(A.dd, *ph, hr, pg, d3, red, Bt, publisher, fz);      // (Bt: free until the barrier behind the heads)
+    if constexpr (BC) head_actor_bc(A.dd, *bh, br, d3, red, Bt, publisher, fz);      // (Bt: free until the barrier behind the heads)
+    else if constexpr (PER) head_per(A.dd, *ph, hr, pg, d3, red, Bt, publisher, fz);
     else if constexpr (TWIN) head_twin(A.dd, *th, tr, d3, red, publisher, fz);
     else if constexpr (CLONE) head_clone(A.dd, hr, d3, red, publisher, fz);
     else if (A.head == 1) head_loss(A.dd, hr, d3, red, publisher, fz); else head_actor(A.dd, hr, d3, red, publisher, fz);
@@ -2008,6 +2081,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     grad_body<CIN, 1, false, false, false, true>(A.g, smem, (int)blockIdx.x, nullptr, &A.h);
 }
 
+// The actor's gradient launch with the behaviour-regularised head (shems_ddpg_update_bc / shems_td3_update_bc): an instantiation of its
+// own behind every other kernel (see k_fwd_clone), so that k_grad, which replay() runs, keeps its code and registers.
+struct BcGradArgs { GradArgs g; BcHead h; };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_grad_bc(BcGradArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    grad_body<SIN, 2, false, false, false, false, true>(A.g, smem, (int)blockIdx.x, nullptr, nullptr, &A.h);
+}
+
 constexpr int FWD_LDS = FwdShape<false>::LDS, QG_LDS = FWD_LDS > QG16_LDS ? FWD_LDS : QG16_LDS;
 constexpr int MID_LDS = FWD_LDS > E_LDS ? FWD_LDS : E_LDS;
 static_assert(QG_LDS <= 160 * 1024, "one workgroup's LDS");
@@ -2026,6 +2108,7 @@ static Kern<MidArgs> K_MID{k_mid, MID_LDS, "attr k_mid"}, K_MID_T{k_mid_t, MID_L
 static Kern<GradArgs> K_GRAD{k_grad, GR_LDS, "attr k_grad"}, K_GRAD_T{k_grad_t, GR_LDS, "attr k_grad_t"}, K_GRAD_CLONE{k_grad_clone, GR_LDS, "attr k_grad_clone"};
 static Kern<PerFwdArgs> K_FWD_PER{k_fwd_per, FWD_LDS, "attr k_fwd_per"};
 static Kern<PerGradArgs> K_GRAD_PER{k_grad_per, GR_LDS, "attr k_grad_per"};
+static Kern<BcGradArgs> K_GRAD_BC{k_grad_bc, GR_LDS, "attr k_grad_bc"};
 static Kern<Td3FwdArgs> K_FWD_TD3{k_fwd_td3, FWD_LDS, "attr k_fwd_td3"};
 static Kern<Td3MidArgs> K_MID_TD3{k_mid_td3, MID_LDS, "attr k_mid_td3"};
 static Kern<Td3GradArgs> K_GRAD_TD3{k_grad_td3, GR_LDS, "attr k_grad_td3"};
@@ -2254,13 +2337,16 @@ static int critic_phases(const Ctx &c, const shems_ddpg *d, const PrepArgs &pa, 
     return hip_ok(hipGetLastError(), "ddpg critic-side launches");
 }
 
-// K4 + K5: the actor side (DDPG.jl:137-140), through the critic as it stands now (already updated)
-static int actor_phases(const Ctx &c, const shems_ddpg *d, const AdamScalars *fuse)
+// K4 + K5: the actor side (DDPG.jl:137-140), through the critic as it stands now (already updated).  bc (checked by the caller: a
+// single learner in Flux order): K5 is k_grad_bc, the behaviour-regularised head in front of the same gradient launch.
+static int actor_phases(const Ctx &c, const shems_ddpg *d, const AdamScalars *fuse, const shems_bc *bc = nullptr)
 {
     FwdArgs f{};
     f.gstride = c.gs; f.prep = 2; f.job[0] = job_critic_through_actor(c, *d);
     if (int rc = launch(c, kernels(c).fwd, QG_TILES, QG16_LDS, f)) return rc;
-    if (int rc = launch(c, kernels(c).grad, GRAD_WGS, GR_LDS, grad_args(c, *d, false, actor_ws(d->ws), 2, fuse))) return rc;
+    const GradArgs g = grad_args(c, *d, false, actor_ws(d->ws), 2, fuse);
+    if (int rc = bc ? launch(c, K_GRAD_BC, GRAD_WGS, GR_LDS, BcGradArgs{g, BcHead{bc->alpha, bc->weight, bc->normalise, bc->out}})
+                    : launch(c, kernels(c).grad, GRAD_WGS, GR_LDS, g)) return rc;
     return hip_ok(hipGetLastError(), "ddpg actor-side launches");
 }
 
@@ -2349,6 +2435,45 @@ int shems_ddpg_update(const shems_ddpg *d, const shems_replay *ring, int64_t rin
     const Ctx c = ctx(stream, &kOne, t);
     if (int rc = critic_phases(c, d, PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count}, &sc)) return rc;
     return actor_phases(c, d, &sa);
+}
+
+/* ---- behaviour-regularised actor update (shems_bc_core.h) ---- */
+// What the *_bc entry points refuse of the record, behind the plain entry point's own checks of d (so d's buffers are there).  t: the
+// TD3 learner, whose critic-2 blocks, ws2 and losses2 out must not overlap either, or null.
+static int check_bc(const shems_bc *bc, const shems_ddpg *d, const shems_td3 *t, const char *fn)
+{
+    if (!bc || !bc->out) return set_error(SHEMS_ERR_ARG, "%s: NULL shems_bc or out", fn);
+    if (((uintptr_t)bc->out & 15) != 0) return set_error(SHEMS_ERR_ARG, "%s: shems_bc.out must be 16-byte aligned", fn);
+    if (!(bc->alpha >= 0.0f) || !(bc->weight >= 0.0f) || bc->alpha > 3.0e38f || bc->weight > 3.0e38f)
+        return set_error(SHEMS_ERR_ARG, "%s: alpha and weight must be finite and >= 0", fn);
+    if (bc->normalise != 0 && bc->normalise != 1) return set_error(SHEMS_ERR_ARG, "%s: normalise must be 0 or 1 (got %d)", fn, bc->normalise);
+    if (bc->reserved != 0) return set_error(SHEMS_ERR_ARG, "%s: shems_bc.reserved must be 0", fn);
+    const size_t no = (size_t)SHEMS_BC_OUT_FLOATS * 4, na = (size_t)SHEMS_ACTOR_PARAMS * 4, nc = (size_t)SHEMS_CRITIC_PARAMS * 4;
+    bool hit = ranges_overlap(bc->out, no, d->ws, (size_t)WS_FLOATS * 4) || ranges_overlap(bc->out, no, d->losses, 8);
+    for (const float *p : {d->actor, d->actor_t, d->m_actor, d->v_actor, d->grad_actor}) hit = hit || ranges_overlap(bc->out, no, p, na);
+    for (const float *p : {d->critic, d->critic_t, d->m_critic, d->v_critic, d->grad_critic}) hit = hit || ranges_overlap(bc->out, no, p, nc);
+    if (t) {
+        for (const float *p : {t->critic2, t->critic2_t, t->m_critic2, t->v_critic2, t->grad_critic2}) hit = hit || ranges_overlap(bc->out, no, p, nc);
+        hit = hit || ranges_overlap(bc->out, no, t->ws2, (size_t)W2_FLOATS * 4) || ranges_overlap(bc->out, no, t->losses2, 4);
+    }
+    if (hit) return set_error(SHEMS_ERR_ARG, "%s: shems_bc.out overlaps the workspace, the losses or a parameter block", fn);
+    return SHEMS_OK;
+}
+
+/* replay() with the behaviour-regularised actor loss: K1..K4 as they are, K5 = k_grad_bc.  Flux order only (there is no k_grad_bc_t). */
+int shems_ddpg_update_bc(const shems_ddpg *d, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick,
+                         int64_t excl_pos, int64_t excl_count, double eta_crit, double bp1_crit, double bp2_crit,
+                         double eta_act, double bp1_act, double bp2_act, float *d_publish, const shems_bc *bc, void *stream)
+{
+    const char *fn = "shems_ddpg_update_bc";
+    if (int rc = check_adam(bp1_crit, bp2_crit, fn)) return rc;
+    if (int rc = check_adam(bp1_act, bp2_act, fn)) return rc;
+    if (int rc = check_critic_side(d, ring, ring_len, excl_pos, excl_count)) return rc;      // (the tiled layout: SHEMS_ERR_STATE)
+    if (int rc = check_bc(bc, d, nullptr, fn)) return rc;
+    const AdamScalars sc{eta_crit, bp1_crit, bp2_crit, 1.0, nullptr}, sa{eta_act, bp1_act, bp2_act, 1.0, d_publish};
+    const Ctx c = ctx(stream);
+    if (int rc = critic_phases(c, d, PrepArgs{*d, *ring, ring_len, seed, tick, excl_pos, excl_count}, &sc)) return rc;
+    return actor_phases(c, d, &sa, bc);
 }
 
 /* A single learner on the tiled working layout: see shems_hip.h. */
@@ -2494,10 +2619,10 @@ int shems_td3_workspace_floats(int64_t *out)
 /* One TD3 update: see shems_hip.h.  Three launches with both critics in each (kTd3); the second critic's jobs and records are the first
  * one's builders on ws2 and a copy of d that names critic 2's blocks.  A policy step adds replay()'s own K4 + K5 through the updated
  * critic 1. */
-int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
-                     double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy, void *stream)
+static int td3_update(const char *fn, const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
+                      double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy, bool with_bc,
+                      const shems_bc *bc, void *stream)
 {
-    const char *fn = "shems_td3_update";
     if (!t) return set_error(SHEMS_ERR_ARG, "%s: NULL", fn);
     const shems_ddpg *d = &t->d;
     if (int rc = check_adam(bp1_crit, bp2_crit, fn)) return rc;
@@ -2525,6 +2650,8 @@ int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_
         if (d->losses && ranges_overlap(t->losses2, 4, d->losses, 8)) return set_error(SHEMS_ERR_ARG, "%s: losses2 overlaps losses", fn);
     }
     if (int rc = check_ddpg(d, fn)) return rc;                 // NULLs, batch, alignment; a learner on the tiled layout: SHEMS_ERR_STATE
+    if (with_bc)
+        if (int rc = check_bc(bc, d, t, fn)) return rc;
     const Ctx c = ctx(stream);
     float *ws = d->ws, *ws2 = t->ws2;
     const NetWs w1 = critic_ws(ws), w2 = critic2_ws(ws2);
@@ -2558,7 +2685,21 @@ int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_
     if (!update_policy) return SHEMS_OK;
     // the actor through the updated critic 1, ADAM, the actor's soft update: replay()'s K4 + K5 as they are (DDPG.jl:137-140)
     const AdamScalars sa{eta_act, bp1_act, bp2_act, 1.0, nullptr};
-    return actor_phases(c, d, &sa);
+    return actor_phases(c, d, &sa, bc);
+}
+int shems_td3_update(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
+                     double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy, void *stream)
+{
+    return td3_update("shems_td3_update", t, ring, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, update_policy,
+                      false, nullptr, stream);
+}
+/* The same with the behaviour-regularised actor loss on the policy step (k_grad_bc); off a policy step bc is checked and not read. */
+int shems_td3_update_bc(const shems_td3 *t, const shems_replay *ring, int64_t ring_len, uint64_t seed, uint32_t tick, double eta_crit,
+                        double bp1_crit, double bp2_crit, double eta_act, double bp1_act, double bp2_act, int update_policy,
+                        const shems_bc *bc, void *stream)
+{
+    return td3_update("shems_td3_update_bc", t, ring, ring_len, seed, tick, eta_crit, bp1_crit, bp2_crit, eta_act, bp1_act, bp2_act, update_policy,
+                      true, bc, stream);
 }
 
 /* The latency form of learner groups: the same phases with grid z = learner. */

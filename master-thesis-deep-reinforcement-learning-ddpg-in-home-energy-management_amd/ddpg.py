@@ -58,6 +58,85 @@ def anneal_beta(beta0, update, total):
     return min(1.0, beta0 + (1.0 - beta0) * (float(update) / float(total)))
 
 
+BC_ALPHA, BC_WEIGHT = 2.5, 1.0                   # Fujimoto, Gu 2021
+
+
+class BC:
+    """The behaviour-regularised actor loss of TD3+BC (include/shems_hip.h, shems_ddpg_update_bc): loss_act = -lambda mean(q) + weight
+    mse(a_pi, a) with lambda = alpha / mean|q| (normalise) or alpha.  A small immutable value: Agent(bc=BC(...)) trains with it,
+    agent.bc = BC(2.5, w) between updates decays the pull.  alpha, weight: finite and >= 0 in float32."""
+
+    __slots__ = ("alpha", "weight", "normalise")
+
+    def __init__(self, alpha=BC_ALPHA, weight=BC_WEIGHT, normalise=True):
+        import math
+        for name, v in (("alpha", alpha), ("weight", weight)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise ValueError(f"BC: {name} = {v!r} is not a number")
+            if not (math.isfinite(float(v)) and 0.0 <= float(v) <= float(np.finfo(f32).max)):
+                raise ValueError(f"BC: {name} = {v!r} must be finite and >= 0")
+        if not isinstance(normalise, (bool, np.bool_)) and normalise not in (0, 1):
+            raise ValueError(f"BC: normalise = {normalise!r} must be True or False")
+        object.__setattr__(self, "alpha", float(alpha))
+        object.__setattr__(self, "weight", float(weight))
+        object.__setattr__(self, "normalise", bool(normalise))
+
+    def __setattr__(self, k, v):
+        raise AttributeError("BC is immutable: assign a new BC to agent.bc")
+
+    def __eq__(self, other):
+        return isinstance(other, BC) and (self.alpha, self.weight, self.normalise) == (other.alpha, other.weight, other.normalise)
+
+    def __hash__(self):
+        return hash((self.alpha, self.weight, self.normalise))
+
+    def __repr__(self):
+        return f"BC(alpha={self.alpha:g}, weight={self.weight:g}, normalise={self.normalise})"
+
+    def struct(self, out_ptr):
+        return _capi.BcArgs(self.alpha, self.weight, 1 if self.normalise else 0, 0, out_ptr)
+
+
+def parse_bc(value):
+    """SHEMS_BC of the entry script: None when unset, BC(alpha[, weight]) for <alpha>[:<weight>].  Anything else is refused by name."""
+    if value is None:
+        return None
+    parts = str(value).split(":")
+    try:
+        if not 1 <= len(parts) <= 2:
+            raise ValueError
+        nums = [float(x) for x in parts]
+        return BC(*nums)
+    except ValueError:
+        raise ValueError(f"SHEMS_BC = {value!r} is not <alpha>[:<weight>] with finite numbers >= 0") from None
+
+
+def bc_case_suffix(bc):
+    """What the entry script appends to its `case` string for a run with the term."""
+    return f"_bc-a{bc.alpha:g}-w{bc.weight:g}"
+
+
+def bc_refusals(what, *, prioritized=False, batch=BATCH_SIZE, wide=False, noise_type="gn", world=1, tiled=False, grouped=False, fused=True):
+    """What the behaviour-regularised update does not cover, by name, before any device work: never run without the term."""
+    if prioritized:
+        raise NotImplementedError(f"{what}: bc with a PrioritizedRing: the weighted update has no behaviour-regularised head")
+    if batch > 128:
+        raise NotImplementedError(f"{what}: bc with BATCH_SIZE = {batch}; the behaviour-regularised update holds at most 128 columns")
+    if wide:
+        raise NotImplementedError(f"{what}: bc with a wide network: hidden sizes beyond ({L1}, {L2}) run layer by layer (shems_wide_*), which has no "
+                                  "behaviour-regularised head")
+    if noise_type == "pn":
+        raise NotImplementedError(f"{what}: bc with parameter noise (noise_type = 'pn'), which adapts between getData and the updates of replay()")
+    if world > 1:
+        raise NotImplementedError(f"{what}: bc with data-parallel replicas (sync.world = {world}): the split form has no behaviour-regularised head")
+    if tiled:
+        raise NotImplementedError(f"{what}: bc with the tiled working layout (use_tiled): there is no tiled behaviour-regularised gradient launch")
+    if grouped:
+        raise NotImplementedError(f"{what}: bc for a learner of a learner group: learner groups have no behaviour-regularised update")
+    if not fused:
+        raise NotImplementedError(f"{what}: bc with the split form of replay() (fused = False)")
+
+
 def _pub(publish):
     """The d_publish argument: the tensor that also receives the updated actor, or NULL."""
     return C.c_void_p(publish.data_ptr()) if publish is not None else None
@@ -316,7 +395,7 @@ class Agent:
     """The DDPG learner state on one GPU (one replica under data parallelism)."""
 
     def __init__(self, seed=1231, device=None, sigma=NOISE_SIGMA, mu=0.0, rng_seed=None, noise_type="gn", theta=0.15,
-                 dt=1e-2, eps=0.5, tensors=None, hidden=(L1, L2), wide=None, layout=None, n_step=1):
+                 dt=1e-2, eps=0.5, tensors=None, hidden=(L1, L2), wide=None, layout=None, n_step=1, bc=None):
         """tensors: dict of float32 device views (actor, critic, actor_t, critic_t, m_actor, v_actor, m_critic, v_critic,
         grad_actor, grad_critic, s_min, s_max, ws, losses) in memory the caller owns -- a learner group's slab -- instead
         of buffers allocated here.  wide: None = by size (is_wide); True = the layer-by-layer path whatever the size (tests hold the two
@@ -324,9 +403,12 @@ class Agent:
         and the wide kernels run at (a wide learner group's width, group.LearnerGroup(form="wide")); None = `hidden`.  export_* and
         set_params speak `hidden`.  n_step: the steps of a multi-step return (1 .. 16, include/shems_hip.h): with n_step > 1 the
         training episodes push (s_t, a_t, G_t, s_{t+n}) through a replay.NStepWindow, populate_memory converts whole episodes, and
-        every update of this agent bootstraps with gamma_n; `gamma` stays the one-step discount."""
+        every update of this agent bootstraps with gamma_n; `gamma` stays the one-step discount.  bc: a BC, or None: replay() then takes
+        the behaviour-regularised actor loss (shems_ddpg_update_bc); it may be reassigned between updates."""
         import torch
         self.n_step = check_n_step(n_step)             # (an argument error before any device work)
+        self._slab_learner = tensors is not None   # a learner of a learner group (its state lives in the group's slab)
+        self.bc = bc
         self._nstep = None                         # the NStepWindow of the training episodes, made on first use
         self.torch = torch
         self.L = _declare()
@@ -476,11 +558,59 @@ class Agent:
     _LEARNER_TENSORS = ("actor", "critic", "actor_t", "critic_t", "m_actor", "v_actor", "m_critic", "v_critic", "grad_actor",
                         "grad_critic", "losses")
 
+    # ---- the behaviour-regularised actor loss (BC): the value, and what the last such update published ----
+    _bc = None
+    _bc_rec = None                                 # [SHEMS_BC_OUT_FLOATS]: lambda, Qbar, -mean q, mse, q [128]; allocated on first use
+
+    @property
+    def bc(self):
+        return self._bc
+
+    @bc.setter
+    def bc(self, v):
+        if v is not None and not isinstance(v, BC):
+            raise ValueError(f"bc = {v!r} is not a ddpg.BC or None")
+        if v is not None and getattr(self, "_slab_learner", False):
+            raise NotImplementedError("bc for a learner of a learner group: learner groups have no behaviour-regularised update")
+        self._bc = v
+
+    @property
+    def bc_out(self):
+        """The record of the last behaviour-regularised update (zeros before the first)."""
+        if self._bc_rec is None:
+            self._bc_rec = self.torch.zeros(_capi.BC_OUT_FLOATS, dtype=self.torch.float32, device=self.device)
+        return self._bc_rec
+
+    @property
+    def bc_lambda(self):
+        """lambda of the last behaviour-regularised update, a [1] device view."""
+        return self.bc_out[0:1]
+
+    @property
+    def bc_q_abs_mean(self):
+        """Qbar = mean |q_m| over the live columns."""
+        return self.bc_out[1:2]
+
+    @property
+    def bc_mse(self):
+        """mse(a_pi, a) over the 2 * batch elements."""
+        return self.bc_out[3:4]
+
+    @property
+    def bc_q(self):
+        """q_m = critic([s_n; a_pi])_m through the updated critic, [128] (columns >= batch are padding)."""
+        return self.bc_out[4:4 + 128]
+
+    def _bc_refusals(self, what, ring):
+        bc_refusals(what, prioritized=isinstance(ring, PrioritizedRing), batch=self.batch, wide=self.wide or is_wide(self.hidden),
+                    noise_type=self.noise_type, world=self.sync.world, tiled=self.tiled_mode or self._tiled_current,
+                    grouped=getattr(self, "_before_param_write", None) is not None, fused=self.fused)
+
     def snapshot(self):
         """Everything replay() mutates (device clones + the host-side ADAM powers / counters)."""
         return ({k: getattr(self, k).clone() for k in self._LEARNER_TENSORS},
                 dict(bp_actor=list(self.bp_actor), bp_critic=list(self.bp_critic), updates=self.updates, tick=self.tick,
-                     pn_sigma=self.pn_sigma, fused=self.fused))
+                     pn_sigma=self.pn_sigma, fused=self.fused, bc=self.bc))
 
     def restore(self, snap):
         hook = getattr(self, "_before_param_write", None)
@@ -774,8 +904,11 @@ class Agent:
     def replay(self, ring, tick=None, exclude=None, publish=None):
         """replay(; rng_rpl) (DDPG.jl:121-145): one DDPG update from `ring`.  exclude = (pos, count): ring slots another
         stream is writing right now (pipelined mode); publish = tensor that also receives the updated actor.  A
-        replay.PrioritizedRing takes the prioritized update (_replay_per)."""
+        replay.PrioritizedRing takes the prioritized update (_replay_per).  With `bc` set (a BC) the actor's loss is the
+        behaviour-regularised one (_replay_bc); whatever that update does not cover is refused by name, never run without the term."""
         self._same_device(None, ring)
+        if self.bc is not None:
+            return self._replay_bc(ring, tick, exclude, publish)
         if isinstance(ring, PrioritizedRing):
             return self._replay_per(ring, tick, exclude, publish)
         # the one-call form works on the tiled regions where the mode is on (the second copy `publish` is a Flux-order block: not from tiles)
@@ -825,6 +958,21 @@ class Agent:
         self._actor_apply_pub(d, gs, publish, st)
         self._advance(critic=False, actor=True, counter="updates")
 
+    def _replay_bc(self, ring, tick=None, exclude=None, publish=None):
+        """replay() with the behaviour-regularised actor loss (shems_ddpg_update_bc: K1..K4 as they are, K5 = k_grad_bc), on the
+        one-call route.  State advances as in replay(); bc_lambda, bc_q_abs_mean, bc_mse and bc_q view what the update published."""
+        self._bc_refusals("replay", ring)
+        L = _capi.declare_bc()
+        d = self._ddpg_args()
+        rs = ring.struct()
+        tick = self.updates if tick is None else tick
+        ex_pos, ex_cnt = (0, 0) if exclude is None else (int(exclude[0]) % ring.capacity, int(exclude[1]))
+        b = self.bc.struct(self.bc_out.data_ptr())
+        _capi.check(L.shems_ddpg_update_bc(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt,
+                                           self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
+                                           self.bp_actor[1], _pub(publish), C.byref(b), self._stream()))
+        self._advance(critic=True, actor=True, counter="updates")
+
     def _replay_per(self, ring, tick=None, exclude=None, publish=None):
         """replay() on a prioritized ring (shems_ddpg_update_per: the sampler launch, then K1..K5 with the weighted critic head and
         the priority write-back in K3; include/shems_hip.h states the definition).  The pushes since the ring's last update are its
@@ -861,6 +1009,8 @@ class Agent:
         """replay() on slots and weights the caller supplies (shems_ddpg_update_given): idx int32 [128] (-1 in the pad columns) and
         weights float32 [128], device tensors.  No sampler launch, no write-back; with idx = sample_indices(tick, len(ring)) and
         weights of 1.0 it leaves replay()'s bits.  State advances as in replay()."""
+        if self.bc is not None:
+            raise NotImplementedError("replay_given: bc with given slots and weights: the weighted update has no behaviour-regularised head")
         if self.batch > self.MAX_PASS_BATCH or self.wide or is_wide(self.hidden) or self.noise_type == "pn" or self.sync.world > 1 or \
                 self.tiled_mode or getattr(self, "_before_param_write", None) is not None or not self.fused:
             raise NotImplementedError("replay_given: one replica on the tuned kernels in Flux order, the one-call form, batch <= 128, no parameter noise")

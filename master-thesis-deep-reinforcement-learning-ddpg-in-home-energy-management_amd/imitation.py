@@ -324,6 +324,58 @@ def warm_start(agent, env, values, demos, ring, rounds, steps_per_round, critic_
     return out + [{"critic_loss_first": first, "critic_loss_last": last, "transitions": len(ring)}]
 
 
+OFFLINE_HEADER = ["update", "critic_loss", "actor_loss", "lambda", "mse"]
+
+
+def offline(agent, ring, updates, record_every=1):
+    """OFFLINE training: `updates` calls of agent.replay(ring) with no environment step, on transitions a tracked pass left in `ring`
+    (transitions(..., mode="td")), with the behaviour-regularised actor loss holding the actor to the data (agent.bc, ddpg.BC).  The
+    normalisation is the caller's (agent.min_max_buffer(ring) or set_norm).  Everything goes on PyTorch's current stream; after update
+    u with u % record_every == 0, and after the last, (losses[0], losses[1], lambda, mse) are copied into a device table, which is
+    read back in ONE copy at the end.  For a TD3Agent the last three columns are those of the latest policy step.
+    Refused by name before anything is trained: agent.bc is None (without the term this is not offline training but replay() on a ring
+    nobody refreshes); a ring that holds done = 1 slots -- an "mc" ring, by the rule warm_start documents: its rewards are returns and
+    every bootstrapped target would be cut short; an empty ring.
+    Returns the rows (update, losses[0], losses[1], lambda, mse) as a list of tuples."""
+    if getattr(agent, "bc", None) is None:
+        raise ValueError("offline: agent.bc is None: offline training needs the behaviour-regularised actor loss (ddpg.BC)")
+    updates, record_every = int(updates), int(record_every)
+    if updates < 1 or record_every < 1:
+        raise ValueError(f"offline: updates = {updates}, record_every = {record_every}; both at least 1")
+    n = len(ring)
+    if n < 1:
+        raise ValueError("offline: the ring is empty")
+    if bool((ring.done[:n] != 0).any()):
+        raise ValueError("offline: the ring holds done = 1 slots (an 'mc' ring of returns): bootstrapped training must never sample them; "
+                         "seed a 'td' ring (transitions(..., mode='td'))")
+    torch = agent.torch
+    at = [u for u in range(updates) if u % record_every == 0 or u == updates - 1]
+    table = torch.zeros((len(at), 4), dtype=torch.float32, device=agent.device)
+    k = 0
+    for u in range(updates):
+        agent.replay(ring)
+        if u == at[k]:
+            table[k, 0:2].copy_(agent.losses)
+            table[k, 2:3].copy_(agent.bc_lambda)
+            table[k, 3:4].copy_(agent.bc_mse)
+            k += 1
+    rows = table.cpu().numpy()                               # the call's one copy back
+    return [(int(u),) + tuple(float(x) for x in r) for u, r in zip(at, rows)]
+
+
+def write_to_offline_file(rows, path):
+    """offline's recorded rows as a CSV beside the imitation file."""
+    import csv
+    import os
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(OFFLINE_HEADER)
+        for r in rows:
+            w.writerow([int(r[0])] + [repr(float(x)) for x in r[1:]])
+    return path
+
+
 def _group_check(grp, env, demos, what):
     if env.n != grp.count:
         raise ValueError(f"{what}: the env batch holds {env.n} envs for a group of {grp.count} learners (one env per learner, env l on "

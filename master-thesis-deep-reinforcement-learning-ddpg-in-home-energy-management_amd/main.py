@@ -26,6 +26,10 @@ Differences that follow from the platform, all explicit:
     to 1 over the run; defaults 0.6, 0.4) and appends _per-a<alpha>-b<beta0> to <case>; unset or `uniform`: today's bytes and names;
   * SHEMS_NSTEP=<n> (1 .. 16) trains on multi-step returns (Agent(n_step=n): n-step transitions, y = G + gamma^n q') and appends _n<n>
     to <case>, behind the suffixes above; it combines with SHEMS_ALGO=td3 and SHEMS_REPLAY=per; unset or 1: today's bytes and names;
+  * SHEMS_BC=<alpha>[:<weight>] trains with the behaviour-regularised actor loss of TD3+BC (ddpg.BC; weight default 1) and appends
+    _bc-a<alpha>-w<weight> to <case>, behind the suffixes above; it combines with SHEMS_ALGO=td3 and SHEMS_NSTEP, not with
+    SHEMS_REPLAY=per; unset: today's bytes and names; SHEMS_FORESIGHT_OFFLINE=<updates> (needs SHEMS_FORESIGHT=1 and SHEMS_BC) first
+    trains offline on the foresight pass of the training series (imitation.offline) and writes ..._results_<case>_offline.csv;
   * SHEMS_FORESIGHT=1 adds, after the tracking block, the perfect-foresight pass over the tracked data set (foresight.py):
     out/tracker/<Job_ID>_<run>_results_<case>_foresight.csv and a tracker row with seed = "foresight"; with it,
     SHEMS_FORESIGHT_HORIZON (hours of forecast: one integer or a comma list) and SHEMS_FORESIGHT_CONTROL (hours between plans,
@@ -342,6 +346,40 @@ def foresight_warmstart(environ=os.environ):
     return steps, parts[1] if len(parts) == 2 else "mc"
 
 
+def bc_from_env(environ=os.environ):
+    """SHEMS_BC=<alpha>[:<weight>] -> a ddpg.BC (the behaviour-regularised actor loss, normalised as the paper has it): the run trains with
+    the term and `case` gains "_bc-a<alpha>-w<weight>" behind the other suffixes.  None when unset: today's bytes and names.  A malformed
+    value is refused by name."""
+    from .ddpg import parse_bc
+    return parse_bc(environ.get("SHEMS_BC"))
+
+
+def foresight_offline(environ=os.environ):
+    """SHEMS_FORESIGHT_OFFLINE=<updates> -> updates >= 1: before the first episode the foresight pass of the TRAINING series goes into a
+    "td" ring (imitation.transitions), the normalisation is set from that ring, and imitation.offline runs <updates> updates on it; the
+    recorded rows go to ..._results_<case>_offline.csv beside the imitation file.  None when unset.  It needs SHEMS_FORESIGHT=1 and
+    SHEMS_BC; a malformed value is refused by name."""
+    raw = environ.get("SHEMS_FORESIGHT_OFFLINE")
+    if raw is None:
+        return None
+    if environ.get("SHEMS_FORESIGHT") != "1":
+        raise ValueError("SHEMS_FORESIGHT_OFFLINE is set without SHEMS_FORESIGHT=1")
+    if environ.get("SHEMS_BC") is None:
+        raise ValueError("SHEMS_FORESIGHT_OFFLINE is set without SHEMS_BC: offline training needs the behaviour-regularised actor loss")
+    try:
+        updates = int(raw)
+    except ValueError:
+        raise ValueError(f"SHEMS_FORESIGHT_OFFLINE = {raw!r} is not an integer number of updates") from None
+    if updates < 1:
+        raise ValueError(f"SHEMS_FORESIGHT_OFFLINE = {raw!r}: at least one update")
+    return updates
+
+
+def offline_file_name(job_id, run, case, out_dir="out/tracker"):
+    """The recorded rows of SHEMS_FORESIGHT_OFFLINE, beside imitation_file_name's file."""
+    return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_offline.csv")
+
+
 def warmstart_file_name(job_id, run, case, out_dir="out/tracker"):
     """The critic figures of SHEMS_FORESIGHT_WARMSTART, beside imitation_file_name's file."""
     return os.path.join(out_dir, f"{job_id}_{run}_results_{case}_warmstart.csv")
@@ -437,6 +475,15 @@ def main(environ=os.environ, cwd=".", log=print):
                                   "transitions, which an n-step learner would bootstrap with gamma^n")
     if n_step > EP_LENGTH["train"]:
         raise ValueError(f"SHEMS_NSTEP = {n_step}: a training episode of {EP_LENGTH['train']} hours holds no full window")
+    bc = bc_from_env(environ)
+    if bc is not None:
+        if replay_kind == "per":
+            raise NotImplementedError("SHEMS_BC with SHEMS_REPLAY=per: the weighted update has no behaviour-regularised head")
+        if cfg.L1 > 250 or cfg.L2 > 500 or cfg.BATCH_SIZE > 128 or cfg.noise_type == "pn":
+            raise ValueError(f"SHEMS_BC: the behaviour-regularised update holds networks up to (250, 500), batches up to 128 and no parameter "
+                             f"noise, not ({cfg.L1}, {cfg.L2}) at {cfg.BATCH_SIZE} with noise_type = {cfg.noise_type!r}")
+        cfg.algo_suffix += D.bc_case_suffix(bc)
+    offline = foresight_offline(environ)
     horizons, control = foresight_horizons(environ) if environ.get("SHEMS_FORESIGHT") == "1" else ([], 1)
     forecast = foresight_forecast(environ) if environ.get("SHEMS_FORESIGHT") == "1" else None
     regret = foresight_regret(environ)
@@ -477,10 +524,10 @@ def main(environ=os.environ, cwd=".", log=print):
     D.GAMMA, D.TAU = cfg.gamma, cfg.tau
     if algo == "td3":
         agent = T.TD3Agent(seed=cfg.rng_run, sigma=cfg.noise_act if cfg.noise_type == "gn" else cfg.sigma, noise_type=cfg.noise_type,
-                           theta=cfg.theta, hidden=(cfg.L1, cfg.L2), n_step=n_step, **td3_hp)
+                           theta=cfg.theta, hidden=(cfg.L1, cfg.L2), n_step=n_step, bc=bc, **td3_hp)
     else:
         agent = D.Agent(seed=cfg.rng_run, sigma=cfg.noise_act if cfg.noise_type == "gn" else cfg.sigma, noise_type=cfg.noise_type,
-                        theta=cfg.theta, hidden=(cfg.L1, cfg.L2), n_step=n_step)
+                        theta=cfg.theta, hidden=(cfg.L1, cfg.L2), n_step=n_step, bc=bc)
     agent.gamma, agent.tau, agent.batch = float(np.float32(cfg.gamma)), float(np.float32(cfg.tau)), cfg.BATCH_SIZE
     agent.eta_act, agent.eta_crit = float(np.float32(cfg.eta_act)), float(np.float32(cfg.eta_crit))
     ring = D.PrioritizedRing(cfg.MEM_SIZE, alpha=per_hp["alpha"], beta=per_hp["beta0"]) if replay_kind == "per" else D.ReplayRing(cfg.MEM_SIZE)
@@ -488,7 +535,22 @@ def main(environ=os.environ, cwd=".", log=print):
 
     # ---- Memory Buffer (MAIN:27-30) ----
     agent.populate_memory(env_train, ring, seed=cfg.rng_run)
-    agent.min_max_buffer(ring, cfg.MEM_SIZE, seed=cfg.rng_run)
+    offline_written = []
+    if offline is None:
+        agent.min_max_buffer(ring, cfg.MEM_SIZE, seed=cfg.rng_run)
+    else:                                                                # offline training on the foresight pass of the training series
+        from . import imitation
+        steps = tabs["train"].shape[0] - 1                               # (a pass of n steps reads row n + 1)
+        env_off = mk(1, steps, tabs["train"])
+        values = harness.foresight_values(env_off)
+        _, res_off = harness.inference_foresight(env_off, values=values)
+        seeded = D.ReplayRing(steps)
+        imitation.transitions(values, res_off[0], seeded, mode="td", gamma=agent.gamma)
+        agent.min_max_buffer(seeded, len(seeded), seed=cfg.rng_run)      # the normalisation of the run: the training below keeps it
+        rows = imitation.offline(agent, seeded, offline, record_every=max(1, offline // 100))
+        offline_written.append(imitation.write_to_offline_file(rows, offline_file_name(cfg.job_id, cfg.run, cfg.case)))
+        env_off.close()
+        log(f"offline: {offline} updates on {len(seeded)} transitions of the foresight pass; mse(a_pi, a) {rows[0][4]:.4g} -> {rows[-1][4]:.4g}")
 
     noise_mean = np.zeros(cfg.NUM_EP, np.float32)
     best_eval = 0
@@ -507,7 +569,7 @@ def main(environ=os.environ, cwd=".", log=print):
         log(f"trained {cfg.NUM_EP} episodes in {time.time() - t0:.1f} s; best evaluation at episode {best_eval}")
 
     # ---- track evaluation (MAIN:87-110) ----
-    written, audited = [], []                                            # audited: (results path, rows) of every pass stepped on the true table
+    written, audited = list(offline_written), []                         # audited: (results path, rows) of every pass stepped on the true table
     tk = dict(num_ep=cfg.NUM_EP, l1=cfg.L1, l2=cfg.L2, batch_size=cfg.BATCH_SIZE, mem_size=cfg.MEM_SIZE, min_exp_size=cfg.MEM_SIZE,
               season=cfg.season, run=cfg.run, job_id=cfg.job_id, case=cfg.case)
     if cfg.track == 1 and cfg.seed_run == cfg.num_seeds:

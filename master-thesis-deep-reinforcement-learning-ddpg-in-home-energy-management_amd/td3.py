@@ -389,7 +389,8 @@ class TD3Agent(D.Agent):
 
     def replay(self, ring, tick=None, exclude=None, publish=None, update_policy=None):
         """One TD3 update from `ring` (shems_td3_update).  update_policy: None = the schedule, is_policy_step(self.updates,
-        self.policy_delay).  bp_critic advances on every update, bp_actor on policy steps; `updates` counts updates."""
+        self.policy_delay).  bp_critic advances on every update, bp_actor on policy steps; `updates` counts updates.  With `bc` set
+        (ddpg.BC) the policy step's actor loss is the behaviour-regularised one (shems_td3_update_bc)."""
         if isinstance(ring, D.PrioritizedRing):
             raise NotImplementedError("TD3: the twin-critic update has no weighted head; a PrioritizedRing belongs to ddpg.Agent")
         if exclude is not None or publish is not None:
@@ -409,6 +410,15 @@ class TD3Agent(D.Agent):
         a = self._td3_args()
         rs = ring.struct()
         tick = self.updates if tick is None else tick
+        if self.bc is not None:
+            # the policy step's actor loss is the behaviour-regularised one (shems_td3_update_bc); off a policy step nothing of it runs
+            b = self.bc.struct(self.bc_out.data_ptr())
+            _capi.check(_capi.declare_bc().shems_td3_update_bc(C.byref(a), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF,
+                                                               self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act,
+                                                               self.bp_actor[0], self.bp_actor[1], 1 if policy else 0, C.byref(b),
+                                                               self._stream()))
+            self._advance(critic=True, actor=policy, counter="updates")
+            return
         _capi.check(self.L.shems_td3_update(C.byref(a), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_crit,
                                             self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0], self.bp_actor[1],
                                             1 if policy else 0, self._stream()))
