@@ -116,25 +116,109 @@ def bc_case_suffix(bc):
     return f"_bc-a{bc.alpha:g}-w{bc.weight:g}"
 
 
+# ---- what every update form of the single learner refuses ------------------------------------------------------------------------------
+# REFUSALS[form]: the facts (FACTS' keys) the form refuses, in the order it asks them, each with its words -- by name, before any device
+# work, never run as another algorithm.  With two faults the earlier row speaks.  Where a form omits or narrows a fact the others ask, a
+# comment says so: the forms grew one by one, which of these differences were meant is not on record, and they are kept as found.
+_GIVEN = "replay_given: one replica on the tuned kernels in Flux order, the one-call form, batch <= 128, no parameter noise"
+_TD3_TILED = "TD3: the tiled working layout (use_tiled)"
+_BC_TILED = "{what}: bc with the tiled working layout (use_tiled): there is no tiled behaviour-regularised gradient launch"
+REFUSALS = {
+    "replay": (("pn", "parameter-noise adaptation with BATCH_SIZE > 128"),),       # Agent.replay itself, asked on the sub-batch route only
+    "per": (                                       # Agent.replay on a PrioritizedRing
+        ("piped", "prioritized replay: the pipelined forms of replay() (exclude / publish) belong to shems_ddpg_update"),
+        ("batch_over", "prioritized replay: BATCH_SIZE = {batch}; the sampler draws at most 128 columns"),
+        ("wide", "prioritized replay: hidden sizes {hidden} run layer by layer (shems_wide_*), which has no weighted head"),
+        ("pn", "prioritized replay: parameter noise (noise_type = 'pn') adapts between getData and the updates of replay()"),
+        ("replicas", "prioritized replay: data-parallel replicas do not exchange priorities"),
+        ("tiled_asked", "prioritized replay: the tiled working layout (use_tiled)"),        # narrowed: not tiled_current (_ddpg_args leaves the tiles)
+        ("grouped", "prioritized replay: a learner of a learner group keeps its own working layout"),
+        ("split", "prioritized replay: the split form of replay() (fused = False)")),
+    "given": (                                     # Agent.replay_given; takes a PrioritizedRing; tiled narrowed to tiled_asked, as "per"
+        ("bc", "replay_given: bc with given slots and weights: the weighted update has no behaviour-regularised head"),
+        ("batch_over", _GIVEN), ("wide", _GIVEN), ("pn", _GIVEN), ("replicas", _GIVEN), ("tiled_asked", _GIVEN), ("grouped", _GIVEN), ("split", _GIVEN)),
+    # Agent.clone and Agent.evaluate: the same rows in their own nouns.  Both omit pn, tiled_asked, tiled_current, split and bc: the
+    # half updates run beside all of them
+    **{what: (("prioritized", f"{what}: the {kind} update draws uniformly; a PrioritizedRing has no {noun} form"),
+              ("wide", f"{what}: hidden sizes {{hidden}} run layer by layer (shems_wide_*), which has no {kind} update"),
+              ("batch_over", f"{what}: BATCH_SIZE = {{batch}}; the {kind} update holds at most 128 columns"),
+              ("replicas", f"{what}: data-parallel replicas do not exchange the {kind} gradient"),
+              ("grouped", f"{what}: a learner of a learner group keeps its own working layout"))
+       for what, kind, noun in (("clone", "supervised", "cloning"), ("evaluate", "critic-only", "critic-only"))},
+    "bc": (                                        # Agent.replay with bc set, and bc_refusals; exclude / publish are taken
+        ("prioritized", "{what}: bc with a PrioritizedRing: the weighted update has no behaviour-regularised head"),
+        ("batch_over", "{what}: bc with BATCH_SIZE = {batch}; the behaviour-regularised update holds at most 128 columns"),
+        ("wide", "{what}: bc with a wide network: hidden sizes beyond (250, 500) run layer by layer (shems_wide_*), which has no "
+                 "behaviour-regularised head"),
+        ("pn", "{what}: bc with parameter noise (noise_type = 'pn'), which adapts between getData and the updates of replay()"),
+        ("replicas", "{what}: bc with data-parallel replicas (sync.world = {world}): the split form has no behaviour-regularised head"),
+        ("tiled_asked", _BC_TILED), ("tiled_current", _BC_TILED),
+        ("grouped", "{what}: bc for a learner of a learner group: learner groups have no behaviour-regularised update"),
+        ("split", "{what}: bc with the split form of replay() (fused = False)")),
+    "td3": (       # TD3Agent.replay, with bc set too (the "bc" rows are NOT asked there).  Omits wide (left to "td3.init") and split
+        ("prioritized", "TD3: the twin-critic update has no weighted head; a PrioritizedRing belongs to ddpg.Agent"),
+        ("piped", "TD3: the pipelined forms of replay() (exclude / publish) belong to shems_ddpg_update"),
+        ("batch_over", "TD3: BATCH_SIZE = {batch}; the twin-critic update holds at most 128 columns"),
+        ("pn", "TD3: parameter noise (noise_type = 'pn')"),
+        ("replicas", "TD3: data-parallel replicas do not exchange the second critic's gradient"),
+        ("tiled_asked", _TD3_TILED), ("tiled_current", _TD3_TILED),
+        ("grouped", "TD3: a learner of a learner group keeps its own working layout")),
+    "td3.init": (                                  # TD3Agent(...), of its keywords (slab: tensors= given)
+        ("wide", "TD3: hidden sizes {hidden} run layer by layer (shems_wide_*), which has no twin-critic update"),
+        ("pn", "TD3: parameter noise (noise_type = 'pn') adapts between getData and the updates of replay(); the TD3 update is one call"),
+        ("slab", "TD3: a learner of a learner group keeps its state in the group's slab; twin critics for a group are td3.TD3LearnerGroup")),
+}
+TD3_NEVER = {                                      # what a TD3Agent refuses whatever its state: the method raises these words itself
+    "use_tiled": "TD3: the tiled working layout (use_tiled) holds the actor's and critic 1's layer-2 state only",
+    "evaluate": "TD3: evaluate() is the critic-only update of ONE critic; the twin critics have none",
+    "enable_data_parallel": "TD3: data-parallel replicas do not exchange the second critic's gradient",
+    "replay_given": "TD3: replay_given is the single-critic update (shems_ddpg_update_given); the twin critics have none"}
+
+# The facts a row may ask of the learner; "prioritized", "piped" (exclude or publish given) and {what} come with the call (_CallFacts).
+FACTS = {
+    "batch_over": lambda ag: ag.batch > ag.MAX_PASS_BATCH,
+    "wide": lambda ag: ag.wide or is_wide(ag.hidden),
+    "pn": lambda ag: ag.noise_type == "pn",
+    "replicas": lambda ag: ag.sync.world > 1,
+    "tiled_asked": lambda ag: ag.tiled_mode,
+    "tiled_current": lambda ag: ag._tiled_current,
+    "grouped": lambda ag: param_write_hook(ag) is not None,                    # a learner of a tiled learner group
+    "split": lambda ag: not ag.fused,
+    "bc": lambda ag: ag.bc is not None,
+    "batch": lambda ag: ag.batch, "hidden": lambda ag: ag.hidden, "world": lambda ag: ag.sync.world,      # what the words quote
+}
+
+
+def param_write_hook(ag):
+    """What a learner of a group on the tiled working layout calls before it writes a parameter block (group.py sets it); else None."""
+    return getattr(ag, "_before_param_write", None)
+
+
+class _CallFacts(dict):
+    """The facts of one call: what came with the call (ag, prioritized, piped, what), and FACTS of the learner.  Nothing of the learner is
+    read before a row asks: a form never touches the attribute of a fact it omits (the host tests drive the forms on bare objects that
+    carry only what their form reads)."""
+
+    def __missing__(self, fact):
+        return FACTS[fact](self["ag"])
+
+
+def refuse(form, facts):
+    """Raise REFUSALS[form]'s first row that the mapping `facts` meets.  Host only."""
+    for fact, words in REFUSALS[form]:
+        if facts[fact]:
+            raise NotImplementedError(words.format_map(facts))
+
+
 def bc_refusals(what, *, prioritized=False, batch=BATCH_SIZE, wide=False, noise_type="gn", world=1, tiled=False, grouped=False, fused=True):
-    """What the behaviour-regularised update does not cover, by name, before any device work: never run without the term."""
-    if prioritized:
-        raise NotImplementedError(f"{what}: bc with a PrioritizedRing: the weighted update has no behaviour-regularised head")
-    if batch > 128:
-        raise NotImplementedError(f"{what}: bc with BATCH_SIZE = {batch}; the behaviour-regularised update holds at most 128 columns")
-    if wide:
-        raise NotImplementedError(f"{what}: bc with a wide network: hidden sizes beyond ({L1}, {L2}) run layer by layer (shems_wide_*), which has no "
-                                  "behaviour-regularised head")
-    if noise_type == "pn":
-        raise NotImplementedError(f"{what}: bc with parameter noise (noise_type = 'pn'), which adapts between getData and the updates of replay()")
-    if world > 1:
-        raise NotImplementedError(f"{what}: bc with data-parallel replicas (sync.world = {world}): the split form has no behaviour-regularised head")
-    if tiled:
-        raise NotImplementedError(f"{what}: bc with the tiled working layout (use_tiled): there is no tiled behaviour-regularised gradient launch")
-    if grouped:
-        raise NotImplementedError(f"{what}: bc for a learner of a learner group: learner groups have no behaviour-regularised update")
-    if not fused:
-        raise NotImplementedError(f"{what}: bc with the split form of replay() (fused = False)")
+    """What the behaviour-regularised update does not cover: REFUSALS["bc"] for a caller that has the facts but no learner."""
+    refuse("bc", dict(what=what, prioritized=prioritized, batch_over=batch > 128, batch=batch, wide=wide, pn=noise_type == "pn", replicas=world > 1,
+                      world=world, tiled_asked=tiled, tiled_current=False, grouped=grouped, split=not fused))
+
+
+def tick32(tick, default=None):
+    """The sampler tick as the kernels take it: its low 32 bits.  default: the form's own counter, for a caller that may pass tick=None."""
+    return int(default if tick is None else tick) & 0xFFFFFFFF
 
 
 def _pub(publish):
@@ -601,10 +685,10 @@ class Agent:
         """q_m = critic([s_n; a_pi])_m through the updated critic, [128] (columns >= batch are padding)."""
         return self.bc_out[4:4 + 128]
 
-    def _bc_refusals(self, what, ring):
-        bc_refusals(what, prioritized=isinstance(ring, PrioritizedRing), batch=self.batch, wide=self.wide or is_wide(self.hidden),
-                    noise_type=self.noise_type, world=self.sync.world, tiled=self.tiled_mode or self._tiled_current,
-                    grouped=getattr(self, "_before_param_write", None) is not None, fused=self.fused)
+    _param_write_hook = property(param_write_hook)
+
+    def _facts(self, ring=None, exclude=None, publish=None, what=None):      # the facts of one update call, for refuse()
+        return _CallFacts(ag=self, prioritized=isinstance(ring, PrioritizedRing), piped=exclude is not None or publish is not None, what=what)
 
     def snapshot(self):
         """Everything replay() mutates (device clones + the host-side ADAM powers / counters)."""
@@ -613,7 +697,7 @@ class Agent:
                      pn_sigma=self.pn_sigma, fused=self.fused, bc=self.bc))
 
     def restore(self, snap):
-        hook = getattr(self, "_before_param_write", None)
+        hook = self._param_write_hook
         if hook is not None:
             hook()
         tensors, host = snap
@@ -639,7 +723,7 @@ class Agent:
         """actor / critic: flat Flux-layout vectors, either of this learner's network size (padded here) or already in the (250, 500)
         layout."""
         t = self.torch
-        hook = getattr(self, "_before_param_write", None)      # a learner of a group on the tiled working layout (group.py)
+        hook = self._param_write_hook
         if hook is not None:
             hook()
         for name, vec, n_lay, n_own in (("actor", actor, self.n_actor, net_size(STATE, ACTION, self.hidden)),
@@ -825,17 +909,28 @@ class Agent:
             self._subs = [dict(batch=b, ws=z(self.ws.numel()), gc=z(self.n_critic), ga=z(self.n_actor), losses=z(2)) for b in sizes]
         return self._subs
 
+    # ---- what every update call is built from: a form is its refusals, one native call, one _advance ----
+    def _sample(self, ring, tick, counter="updates"):      # (ring length, seed, tick) of the update's draw; default tick: the form's counter
+        return len(ring), self.rng_seed, tick32(tick, getattr(self, counter))
+
+    _adam_c = property(lambda self: (self.eta_crit, self.bp_critic[0], self.bp_critic[1]))    # (eta, beta1^t, beta2^t) of the critic's ADAM step
+    _adam_a = property(lambda self: (self.eta_act, self.bp_actor[0], self.bp_actor[1]))       # ... and of the actor's
+
+    @staticmethod
+    def _excluded(ring, exclude):                          # (pos, count) of the ring slots another stream is writing, the position wrapped
+        return (0, 0) if exclude is None else (int(exclude[0]) % ring.capacity, int(exclude[1]))
+
     # the four split-form calls of replay(), on the tuned kernels or -- a network wider than (250, 500) -- layer by layer (shems_wide_*)
     def _critic_grad_ex(self, d, rs, ring_len, tick, ex_pos, ex_cnt, st):
+        sample = (ring_len, self.rng_seed, tick32(tick))
         if self.wide:
-            return _capi.check(self.L.shems_wide_critic_grad_ex(C.byref(d), *self.whidden, C.byref(rs), ring_len, self.rng_seed,
-                                                                int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt, st))
-        _capi.check(self.L.shems_ddpg_critic_grad_ex(C.byref(d), C.byref(rs), ring_len, self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt, st))
+            return _capi.check(self.L.shems_wide_critic_grad_ex(C.byref(d), *self.whidden, C.byref(rs), *sample, ex_pos, ex_cnt, st))
+        _capi.check(self.L.shems_ddpg_critic_grad_ex(C.byref(d), C.byref(rs), *sample, ex_pos, ex_cnt, st))
 
     def _critic_apply(self, d, gs, st):
         if self.wide:
-            return _capi.check(self.L.shems_wide_critic_apply(C.byref(d), *self.whidden, self.eta_crit, self.bp_critic[0], self.bp_critic[1], gs, st))
-        _capi.check(self.L.shems_ddpg_critic_apply(C.byref(d), self.eta_crit, self.bp_critic[0], self.bp_critic[1], gs, st))
+            return _capi.check(self.L.shems_wide_critic_apply(C.byref(d), *self.whidden, *self._adam_c, gs, st))
+        _capi.check(self.L.shems_ddpg_critic_apply(C.byref(d), *self._adam_c, gs, st))
 
     def _actor_grad(self, d, st):
         if self.wide:
@@ -855,10 +950,10 @@ class Agent:
     def _actor_apply_pub(self, d, gs, publish, st):
         pub = _pub(publish)
         if self.wide:
-            return _capi.check(self.L.shems_wide_actor_apply_pub(C.byref(d), *self.whidden, self.eta_act, self.bp_actor[0], self.bp_actor[1], gs, pub, st))
-        _capi.check(self.L.shems_ddpg_actor_apply_pub(C.byref(d), self.eta_act, self.bp_actor[0], self.bp_actor[1], gs, pub, st))
+            return _capi.check(self.L.shems_wide_actor_apply_pub(C.byref(d), *self.whidden, *self._adam_a, gs, pub, st))
+        _capi.check(self.L.shems_ddpg_actor_apply_pub(C.byref(d), *self._adam_a, gs, pub, st))
 
-    def _replay_wide(self, ring, tick, ex_pos, ex_cnt, publish):
+    def _replay_wide(self, ring, tick, ex, publish):
         """replay() for BATCH_SIZE > 128: the loss is a mean over the minibatch, so its gradient is the size-weighted mean of the
         sub-batches' gradients (shems_ddpg_combine_dev); ONE ADAM step per network, in the reference's order (critic first, the actor
         through the updated critic, DDPG.jl:134-140).  Sub-batch i draws its indices with sampler tick `tick * 8 + i`."""
@@ -868,7 +963,7 @@ class Agent:
         vp = lambda x: C.c_void_p(x.data_ptr())
         for i, sb in enumerate(subs):
             d = self._ddpg_args(sb)
-            self._critic_grad_ex(d, rs, len(ring), int(tick) * MAX_SUB_BATCHES + i, ex_pos, ex_cnt, st)
+            self._critic_grad_ex(d, rs, len(ring), int(tick) * MAX_SUB_BATCHES + i, *ex, st)
             w = sb["batch"] / self.batch
             _capi.check(self.L.shems_ddpg_combine_dev(vp(self.grad_critic), vp(sb["gc"]), self.n_critic, 0.0 if i == 0 else 1.0, w, st))
             _capi.check(self.L.shems_ddpg_combine_dev(vp(self.losses), vp(sb["losses"]), 1, 0.0 if i == 0 else 1.0, w, st))
@@ -915,29 +1010,25 @@ class Agent:
         d = self._ddpg_args(raw=True) if publish is None and self._enter_tiled() else self._ddpg_args()
         st = self._stream()
         rs = ring.struct()
-        tick = self.updates if tick is None else tick
-        ex_pos, ex_cnt = (0, 0) if exclude is None else (int(exclude[0]) % ring.capacity, int(exclude[1]))
+        sample = n, _, tick = self._sample(ring, tick)
+        ex = self._excluded(ring, exclude)
         if self.batch > self.MAX_PASS_BATCH:
-            if self.noise_type == "pn":
-                raise NotImplementedError("parameter-noise adaptation with BATCH_SIZE > 128")
-            return self._replay_wide(ring, tick, ex_pos, ex_cnt, publish)
+            refuse("replay", self._facts(ring))
+            return self._replay_wide(ring, tick, ex, publish)
         if self.fused and self.sync.world == 1 and self.noise_type != "pn" and not self.wide:
             # one replica, nothing to exchange and no parameter-noise adaptation between getData and the updates: the whole
             # replay() is one call (K1..K5, csrc/shems_ddpg.hip)
-            _capi.check(self.L.shems_ddpg_update(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt,
-                                                 self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
-                                                 self.bp_actor[1], _pub(publish), st))
+            _capi.check(self.L.shems_ddpg_update(C.byref(d), C.byref(rs), *sample, *ex, *self._adam_c, *self._adam_a, _pub(publish), st))
             self._advance(critic=True, actor=True, counter="updates")
             return
         if self.sync.native is not None and self.sync.world > 1 and self.noise_type != "pn" and not self.wide:
             # replicas with a native communicator: the split form and both all-reduces in ONE call, everything in this stream
             d.flags = 0                             # (no deferred E products: nothing runs beside an in-stream exchange)
-            _capi.check(self.L.shems_ddpg_update_dp(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt,
-                                                    self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
-                                                    self.bp_actor[1], _pub(publish), self.sync.native, st))
+            _capi.check(self.L.shems_ddpg_update_dp(C.byref(d), C.byref(rs), *sample, *ex, *self._adam_c, *self._adam_a,
+                                                    _pub(publish), self.sync.native, st))
             self._advance(critic=True, actor=True, counter="updates")
             return
-        self._critic_grad_ex(d, rs, len(ring), tick, ex_pos, ex_cnt, st)
+        self._critic_grad_ex(d, rs, n, tick, *ex, st)
         if self.noise_type == "pn":                # DDPG.jl:126-128 (the actor is still the pre-update one here)
             self.adapt_param_noise_(ring, tick)
         if d.flags & 1:
@@ -961,47 +1052,24 @@ class Agent:
     def _replay_bc(self, ring, tick=None, exclude=None, publish=None):
         """replay() with the behaviour-regularised actor loss (shems_ddpg_update_bc: K1..K4 as they are, K5 = k_grad_bc), on the
         one-call route.  State advances as in replay(); bc_lambda, bc_q_abs_mean, bc_mse and bc_q view what the update published."""
-        self._bc_refusals("replay", ring)
+        refuse("bc", self._facts(ring, what="replay"))
         L = _capi.declare_bc()
-        d = self._ddpg_args()
-        rs = ring.struct()
-        tick = self.updates if tick is None else tick
-        ex_pos, ex_cnt = (0, 0) if exclude is None else (int(exclude[0]) % ring.capacity, int(exclude[1]))
+        d, rs = self._ddpg_args(), ring.struct()
         b = self.bc.struct(self.bc_out.data_ptr())
-        _capi.check(L.shems_ddpg_update_bc(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, ex_pos, ex_cnt,
-                                           self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
-                                           self.bp_actor[1], _pub(publish), C.byref(b), self._stream()))
+        _capi.check(L.shems_ddpg_update_bc(C.byref(d), C.byref(rs), *self._sample(ring, tick), *self._excluded(ring, exclude), *self._adam_c,
+                                           *self._adam_a, _pub(publish), C.byref(b), self._stream()))
         self._advance(critic=True, actor=True, counter="updates")
 
     def _replay_per(self, ring, tick=None, exclude=None, publish=None):
         """replay() on a prioritized ring (shems_ddpg_update_per: the sampler launch, then K1..K5 with the weighted critic head and
         the priority write-back in K3; include/shems_hip.h states the definition).  The pushes since the ring's last update are its
-        fresh range; bp_critic, bp_actor and `updates` advance as in replay().  Everything the six launches do not cover is refused
-        by name, never run as the uniform update."""
-        if exclude is not None or publish is not None:
-            raise NotImplementedError("prioritized replay: the pipelined forms of replay() (exclude / publish) belong to shems_ddpg_update")
-        if self.batch > self.MAX_PASS_BATCH:
-            raise NotImplementedError(f"prioritized replay: BATCH_SIZE = {self.batch}; the sampler draws at most {self.MAX_PASS_BATCH} columns")
-        if self.wide or is_wide(self.hidden):
-            raise NotImplementedError(f"prioritized replay: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no weighted head")
-        if self.noise_type == "pn":
-            raise NotImplementedError("prioritized replay: parameter noise (noise_type = 'pn') adapts between getData and the updates of replay()")
-        if self.sync.world > 1:
-            raise NotImplementedError("prioritized replay: data-parallel replicas do not exchange priorities")
-        if self.tiled_mode:
-            raise NotImplementedError("prioritized replay: the tiled working layout (use_tiled)")
-        if getattr(self, "_before_param_write", None) is not None:
-            raise NotImplementedError("prioritized replay: a learner of a learner group keeps its own working layout")
-        if not self.fused:
-            raise NotImplementedError("prioritized replay: the split form of replay() (fused = False)")
+        fresh range; bp_critic, bp_actor and `updates` advance as in replay().  What the six launches do not cover: REFUSALS["per"]."""
+        refuse("per", self._facts(ring, exclude, publish))
         L = _declare_per()
-        d = self._ddpg_args()
-        rs, ps = ring.struct(), ring.per_struct()
-        tick = self.updates if tick is None else tick
-        fresh_pos, fresh_count = ring.fresh_range()
-        _capi.check(L.shems_ddpg_update_per(C.byref(d), C.byref(rs), C.byref(ps), len(ring), fresh_pos, fresh_count, self.rng_seed,
-                                            int(tick) & 0xFFFFFFFF, self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act,
-                                            self.bp_actor[0], self.bp_actor[1], self._stream()))
+        d, rs, ps = self._ddpg_args(), ring.struct(), ring.per_struct()
+        n, seed, tick = self._sample(ring, tick)
+        _capi.check(L.shems_ddpg_update_per(C.byref(d), C.byref(rs), C.byref(ps), n, *ring.fresh_range(), seed, tick, *self._adam_c, *self._adam_a,
+                                            self._stream()))
         ring.covered = ring.pushed
         self._advance(critic=True, actor=True, counter="updates")
 
@@ -1009,20 +1077,14 @@ class Agent:
         """replay() on slots and weights the caller supplies (shems_ddpg_update_given): idx int32 [128] (-1 in the pad columns) and
         weights float32 [128], device tensors.  No sampler launch, no write-back; with idx = sample_indices(tick, len(ring)) and
         weights of 1.0 it leaves replay()'s bits.  State advances as in replay()."""
-        if self.bc is not None:
-            raise NotImplementedError("replay_given: bc with given slots and weights: the weighted update has no behaviour-regularised head")
-        if self.batch > self.MAX_PASS_BATCH or self.wide or is_wide(self.hidden) or self.noise_type == "pn" or self.sync.world > 1 or \
-                self.tiled_mode or getattr(self, "_before_param_write", None) is not None or not self.fused:
-            raise NotImplementedError("replay_given: one replica on the tuned kernels in Flux order, the one-call form, batch <= 128, no parameter noise")
+        refuse("given", self._facts(ring))
         t = self.torch
         if idx.dtype != t.int32 or weights.dtype != t.float32 or idx.numel() != 128 or weights.numel() != 128:
             raise ValueError("replay_given: idx int32 [128], weights float32 [128]")
         self._same_device(None, ring)
-        d = self._ddpg_args()
-        rs = ring.struct()
-        _capi.check(_declare_per().shems_ddpg_update_given(C.byref(d), C.byref(rs), len(ring), idx.data_ptr(), weights.data_ptr(), self.eta_crit,
-                                                           self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0],
-                                                           self.bp_actor[1], self._stream()))
+        d, rs = self._ddpg_args(), ring.struct()
+        _capi.check(_declare_per().shems_ddpg_update_given(C.byref(d), C.byref(rs), len(ring), idx.data_ptr(), weights.data_ptr(), *self._adam_c,
+                                                           *self._adam_a, self._stream()))
         self._advance(critic=True, actor=True, counter="updates")
 
     def clone(self, demos, tick=None, tau=1.0, publish=None):
@@ -1033,23 +1095,12 @@ class Agent:
         for bit (1 p + 0 t): a pre-trained actor starts DDPG with its target on itself.  The loss lands in losses[1].  bp_actor
         advances as in replay(); the step counts in `clones` (the default tick), `updates` does not move.  publish: a tensor that
         also receives the updated actor.  Networks up to (250, 500) (smaller ones through pad_net), batch <= 128, one replica."""
-        if isinstance(demos, PrioritizedRing):
-            raise NotImplementedError("clone: the supervised update draws uniformly; a PrioritizedRing has no cloning form")
-        if self.wide or is_wide(self.hidden):
-            raise NotImplementedError(f"clone: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no supervised update")
-        if self.batch > self.MAX_PASS_BATCH:
-            raise NotImplementedError(f"clone: BATCH_SIZE = {self.batch}; the supervised update holds at most {self.MAX_PASS_BATCH} columns")
-        if self.sync.world > 1:
-            raise NotImplementedError("clone: data-parallel replicas do not exchange the supervised gradient")
-        if getattr(self, "_before_param_write", None) is not None:
-            raise NotImplementedError("clone: a learner of a learner group keeps its own working layout")
+        refuse("clone", self._facts(demos))
         self._same_device(None, demos)
-        d = self._ddpg_args()
+        d, rs = self._ddpg_args(), demos.struct()
         d.tau = float(tau)
-        rs = demos.struct()
-        tick = self.clones if tick is None else tick
-        _capi.check(self.L.shems_ddpg_clone_update(C.byref(d), C.byref(rs), len(demos), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_act,
-                                                   self.bp_actor[0], self.bp_actor[1], _pub(publish), self._stream()))
+        _capi.check(self.L.shems_ddpg_clone_update(C.byref(d), C.byref(rs), *self._sample(demos, tick, "clones"), *self._adam_a, _pub(publish),
+                                                   self._stream()))
         self._advance(critic=False, actor=True, counter="clones")
 
     def evaluate(self, ring, tick=None, tau=None):
@@ -1060,30 +1111,18 @@ class Agent:
         targets, and losses[0] is the calibration error of the critic on the minibatch.  bp_critic advances as in replay(); the step
         counts in `evaluations` (the default tick), `updates` and `clones` do not move.  tau: the soft update's, None = the agent's.
         It leaves the bits of _critic_grad_ex + _critic_apply.  Networks up to (250, 500), batch <= 128, one replica."""
-        if isinstance(ring, PrioritizedRing):
-            raise NotImplementedError("evaluate: the critic-only update draws uniformly; a PrioritizedRing has no critic-only form")
-        if self.wide or is_wide(self.hidden):
-            raise NotImplementedError(f"evaluate: hidden sizes {self.hidden} run layer by layer (shems_wide_*), which has no critic-only update")
-        if self.batch > self.MAX_PASS_BATCH:
-            raise NotImplementedError(f"evaluate: BATCH_SIZE = {self.batch}; the critic-only update holds at most {self.MAX_PASS_BATCH} columns")
-        if self.sync.world > 1:
-            raise NotImplementedError("evaluate: data-parallel replicas do not exchange the critic-only gradient")
-        if getattr(self, "_before_param_write", None) is not None:
-            raise NotImplementedError("evaluate: a learner of a learner group keeps its own working layout")
+        refuse("evaluate", Agent._facts(self, ring))       # (unbound: tests/test_warmstart_host.py drives this form on a plain namespace)
         self._same_device(None, ring)
-        d = self._ddpg_args()
+        d, rs = self._ddpg_args(), ring.struct()
         if tau is not None:
             d.tau = float(tau)
-        rs = ring.struct()
-        tick = self.evaluations if tick is None else tick
-        _capi.check(self.L.shems_ddpg_critic_update(C.byref(d), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_crit,
-                                                    self.bp_critic[0], self.bp_critic[1], self._stream()))
+        _capi.check(self.L.shems_ddpg_critic_update(C.byref(d), C.byref(rs), *self._sample(ring, tick, "evaluations"), *self._adam_c, self._stream()))
         self._advance(critic=True, actor=False, counter="evaluations")
 
     def sample_indices(self, tick, ring_len, batch=None):
         batch = self.batch if batch is None else int(batch)
         out = np.empty(batch, np.int64)
-        _capi.check(self.L.shems_ddpg_sample_indices(self.rng_seed, int(tick) & 0xFFFFFFFF, batch, int(ring_len),
+        _capi.check(self.L.shems_ddpg_sample_indices(self.rng_seed, tick32(tick), batch, int(ring_len),
                                                      out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -1103,7 +1142,6 @@ class Agent:
         out = C.c_int64(0)
         _capi.check(self.L.shems_act_step_grid(int(n), C.byref(out)))
         return out.value
-
 
     # ------------------------------------------------------------- training loop
     def populate_memory(self, env, ring, seed=None):
@@ -1242,6 +1280,7 @@ def _w2_block_property(k):
     return property(get, put)
 
 
+assert (Agent.MAX_PASS_BATCH, L1, L2) == (128, 250, 500)      # REFUSALS' words quote these figures
 for _k in Agent._W2_BLOCKS:
     setattr(Agent, _k, _w2_block_property(_k))
 del _k

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _capi
 from .ddpg import (ACTION, BATCH_SIZE, EP_LENGTH_TRAIN, ETA_ACT, ETA_CRIT, GAMMA, L1, L2, MEM_SIZE, N_ACTOR, N_CRITIC, NOISE_SIGMA, SEED_INI,
-                   STATE, TAU, Agent, RingWindow, _declare, act_kernel_name, anneal_beta, unpad_net, unpad_net_from)
+                   STATE, TAU, Agent, RingWindow, _declare, act_kernel_name, anneal_beta, is_wide, tick32, unpad_net, unpad_net_from)
 from .replay import PER_COLS, PER_MAX_SLOTS, PW_IDX, PW_W, PerArgs, ReplayRing, per_workspace_floats, check_n_step, nstep_gamma
 
 
@@ -835,9 +835,8 @@ class LearnerGroup:
         a0, g, r0 = self.learners[0], self.struct(), self._ring0()
         d = a0._ddpg_args()
         st = self._stream()
-        tick = self.updates if tick is None else tick
-        sample = (len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF)
-        adam_c, adam_a = (a0.eta_crit, a0.bp_critic[0], a0.bp_critic[1]), (a0.eta_act, a0.bp_actor[0], a0.bp_actor[1])
+        sample = (len(self.rings[0]), self.rng_seed, tick32(tick, self.updates))
+        adam_c, adam_a = a0._adam_c, a0._adam_a
         tl = self.form != "wide" and self._use_tiled()      # (a tiled group switched to the latency form: its Flux blocks are brought up to date)
         if self.form == "wide":                    # 24 launches for the whole group (csrc/shems_wide.hip)
             if self._x:
@@ -911,8 +910,7 @@ class LearnerGroup:
         if tau is not None and not 0.0 < float(tau) <= 1.0:
             raise ValueError(f"{what}: tau {tau} outside (0, 1]")
         a0 = self.learners[0]
-        count = self.evaluations if critic else self.clones
-        tick = count if tick is None else tick
+        tick = tick32(tick, self.evaluations if critic else self.clones)
         if self.form == "throughput" or self._hp_dev is not None:
             tl = self._use_tiled()
             d, g = a0._ddpg_args(), self.struct()
@@ -921,8 +919,8 @@ class LearnerGroup:
             hp = None if self._hp_dev is None else (self._hp_ptr() if tau is None else self._hp_variant(tau))
             t = C.byref(self.w2t_struct()) if tl else None
             fn = self.L.shems_ddpg_group_critic_update_tp if critic else self.L.shems_ddpg_group_clone_update_tp
-            adam = (a0.eta_crit, *a0.bp_critic) if critic else (a0.eta_act, *a0.bp_actor)
-            _capi.check(fn(C.byref(d), C.byref(r0), stride, C.byref(g), t, hp, n, self.rng_seed, int(tick) & 0xFFFFFFFF, *adam,
+            adam = a0._adam_c if critic else a0._adam_a
+            _capi.check(fn(C.byref(d), C.byref(r0), stride, C.byref(g), t, hp, n, self.rng_seed, tick, *adam,
                            1 if self.store_grad else 0, self._stream()))
             if tl:
                 self._flux_valid = False
@@ -1105,28 +1103,35 @@ def per_extra_blocks(capacity):
     return (("per_prio", int(capacity)), ("per_pmax", 4), ("per_ws", per_workspace_floats(int(capacity))))
 
 
-def per_group_refusals(form=None, noise_type="gn", hparams=None, hidden=None, capacity=MEM_SIZE, alpha=0.6, beta=0.4, eps=1e-6):
-    """What PrioritizedLearnerGroup refuses before any device work, each by name."""
-    import math
+def variant_group_refusals(w, form, noise_type, hparams, hidden):
+    """The walk the variants of the throughput group share (per_group_refusals, td3.group_refusals): form, then "ou", then hidden=, then
+    the records' mem_size / batch / hidden, in the variant's words `w`.  Host only."""
+    no = lambda words: NotImplementedError(f"{w['name']}: {words}")
     if form in ("latency", "wide"):
-        raise NotImplementedError(f"prioritized learner group: form={form!r} has no weighted head; the group runs the throughput form "
-                                  "(shems_ddpg_group_update_per_tp) whatever its count")
+        raise no(f"form={form!r} has no {w['head']}; the group runs the throughput form ({w['entry']}) whatever its count")
     if form not in (None, "throughput"):
         raise ValueError("form must be 'throughput'")
     if noise_type == "ou":
-        raise NotImplementedError("prioritized learner group: Ornstein-Uhlenbeck noise runs on the *_x entry points, which have no prioritized update")
+        raise no(f"Ornstein-Uhlenbeck noise runs on the *_x entry points, which have no {w['update']}")
     if hidden is not None:
-        raise NotImplementedError("prioritized learner group: hidden= belongs to form='wide', which has no prioritized update")
+        raise no(f"hidden= belongs to form='wide', which has no {w['update']}")
     for l, h in enumerate(hparams or ()):
         if hasattr(h, "keys") and "mem_size" in h:
-            raise NotImplementedError(f"prioritized learner group: hparams[{l}]: per-learner mem_size runs on the *_x entry points, which have no "
-                                      "prioritized update (the rings advance in lockstep)")
+            raise no(f"hparams[{l}]: per-learner mem_size runs on the *_x entry points, which have no {w['update']}{w['mem_size']}")
         if hasattr(h, "keys") and int(h.get("batch", 0)) > MAX_GROUP_BATCH:
-            raise NotImplementedError(f"prioritized learner group: hparams[{l}]: batch {h['batch']} > {MAX_GROUP_BATCH}: the sampler draws at most "
-                                      f"{MAX_GROUP_BATCH} columns")
-        if hasattr(h, "keys") and "hidden" in h and (int(h["hidden"][0]) > L1 or int(h["hidden"][1]) > L2):
-            raise NotImplementedError(f"prioritized learner group: hparams[{l}]: hidden {tuple(h['hidden'])} is wider than ({L1}, {L2}): the wide "
-                                      "form has no prioritized update")
+            raise no(f"hparams[{l}]: batch {h['batch']} > {MAX_GROUP_BATCH}: {w['batch']}")
+        if hasattr(h, "keys") and "hidden" in h and is_wide(h["hidden"]):
+            raise no(f"hparams[{l}]: hidden {tuple(h['hidden'])} is wider than ({L1}, {L2}): the wide form has no {w['update']}")
+
+
+_PER_WORDS = dict(name="prioritized learner group", head="weighted head", update="prioritized update", entry="shems_ddpg_group_update_per_tp",
+                  mem_size=" (the rings advance in lockstep)", batch=f"the sampler draws at most {MAX_GROUP_BATCH} columns")
+
+
+def per_group_refusals(form=None, noise_type="gn", hparams=None, hidden=None, capacity=MEM_SIZE, alpha=0.6, beta=0.4, eps=1e-6):
+    """What PrioritizedLearnerGroup refuses before any device work, each by name."""
+    import math
+    variant_group_refusals(_PER_WORDS, form, noise_type, hparams, hidden)
     if int(capacity) > PER_MAX_SLOTS:
         raise NotImplementedError(f"prioritized learner group: capacity {int(capacity)} > {PER_MAX_SLOTS}: a learner's sampler workgroup keeps "
                                   "every block sum in LDS")
@@ -1206,9 +1211,8 @@ class PrioritizedLearnerGroup(LearnerGroup):
         replay() would draw them.  fresh: (pos, count) in place of fresh_range(); `covered` does not move."""
         a0, g, per = self.learners[0], self.struct(), self.per_struct()
         pos, cnt = self.fresh_range() if fresh is None else fresh
-        tick = self.updates if tick is None else tick
         _capi.check(self.LP.shems_per_group_sample_dev(C.byref(per), C.byref(g), self._hp_ptr(), self.capacity, len(self.rings[0]), int(pos),
-                                                       int(cnt), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.batch if batch is None else int(batch),
+                                                       int(cnt), self.rng_seed, tick32(tick, self.updates), a0.batch if batch is None else int(batch),
                                                        self._stream()))
 
     # ---- refused paths ----
@@ -1225,12 +1229,9 @@ class PrioritizedLearnerGroup(LearnerGroup):
                                       f"{MAX_GROUP_BATCH} columns")
         tl = self._use_tiled()
         d, per = a0._ddpg_args(), self.per_struct()
-        tick = self.updates if tick is None else tick
         t = C.byref(self.w2t_struct()) if tl else None
-        fresh_pos, fresh_count = self.fresh_range()
         _capi.check(self.LP.shems_ddpg_group_update_per_tp(C.byref(d), C.byref(r0), C.byref(g), t, self._hp_ptr(), C.byref(per), len(self.rings[0]),
-                                                           fresh_pos, fresh_count, self.rng_seed, int(tick) & 0xFFFFFFFF, a0.eta_crit,
-                                                           a0.bp_critic[0], a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1],
+                                                           *self.fresh_range(), self.rng_seed, tick32(tick, self.updates), *a0._adam_c, *a0._adam_a,
                                                            flags | (_capi.TP_STORE_GRAD if self.store_grad else 0), self._stream()))
         if tl:
             self._flux_valid = False

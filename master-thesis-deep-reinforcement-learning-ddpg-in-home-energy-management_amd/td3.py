@@ -12,9 +12,7 @@ replay() (DDPG.jl:121-145): Float32 arithmetic, Flux 0.12.1 ADAM, the minibatch 
     parse_algo(value)      SHEMS_ALGO of the entry script
 
 act, act_step, episode_, run_episodes, populate_memory, min_max_buffer and clone are the Agent's.  What TD3 does not cover is refused by
-name (NotImplementedError), never run as DDPG: networks wider than (250, 500), batches above 128, parameter noise, data-parallel
-replicas, the tiled working layout, evaluate(), a TD3Agent on a group's slab (a group of TD3 learners is a TD3LearnerGroup), the pipelined forms
-of replay() (exclude / publish); for a TD3LearnerGroup see its docstring.
+name (NotImplementedError), never run as DDPG: the "td3" rows of ddpg.REFUSALS; for a TD3LearnerGroup see its docstring.
 """
 from __future__ import annotations
 
@@ -29,7 +27,7 @@ from . import group as G
 
 SIGMA_TRG, CLIP_TRG, POLICY_DELAY = 0.2, 0.5, 2        # input.jl:231; the paper's clip and delay
 CRITIC2_SEED_OFFSET = 1000
-BP = 128                                               # columns of one update pass (csrc/shems_ddpg.hip)
+BP = G.MAX_GROUP_BATCH                                 # 128 columns of one update pass (csrc/shems_ddpg.hip); the groups' walk tests it
 
 
 class Td3Args(C.Structure):            # shems_td3
@@ -100,27 +98,13 @@ def group_extra_blocks(n_critic, tiled, ws2_floats):
                                                                  ("losses2", 1))
 
 
+_GROUP_WORDS = dict(name="TD3 learner group", head="twin-critic update", update="twin-critic update", entry="shems_td3_group_update_tp",
+                    mem_size="", batch=f"the twin-critic update holds one {BP}-column pass")
+
+
 def group_refusals(form=None, noise_type="gn", hparams=None, hidden=None, sigma_trg=SIGMA_TRG, clip_trg=CLIP_TRG, policy_delay=POLICY_DELAY):
     """What TD3LearnerGroup refuses before any device work, each by name."""
-    if form in ("latency", "wide"):
-        raise NotImplementedError(f"TD3 learner group: form={form!r} has no twin-critic update; the group runs the throughput form "
-                                  "(shems_td3_group_update_tp) whatever its count")
-    if form not in (None, "throughput"):
-        raise ValueError("form must be 'throughput'")
-    if noise_type == "ou":
-        raise NotImplementedError("TD3 learner group: Ornstein-Uhlenbeck noise runs on the *_x entry points, which have no twin-critic update")
-    if hidden is not None:
-        raise NotImplementedError("TD3 learner group: hidden= belongs to form='wide', which has no twin-critic update")
-    for l, h in enumerate(hparams or ()):
-        if hasattr(h, "keys") and "mem_size" in h:
-            raise NotImplementedError(f"TD3 learner group: hparams[{l}]: per-learner mem_size runs on the *_x entry points, which have no "
-                                      "twin-critic update")
-        if hasattr(h, "keys") and int(h.get("batch", 0)) > BP:
-            raise NotImplementedError(f"TD3 learner group: hparams[{l}]: batch {h['batch']} > {BP}: the twin-critic update holds one "
-                                      f"{BP}-column pass")
-        if hasattr(h, "keys") and "hidden" in h and D.is_wide(tuple(int(x) for x in h["hidden"])):
-            raise NotImplementedError(f"TD3 learner group: hparams[{l}]: hidden {tuple(h['hidden'])} is wider than ({D.L1}, {D.L2}): the "
-                                      "wide form has no twin-critic update")
+    G.variant_group_refusals(_GROUP_WORDS, form, noise_type, hparams, hidden)
     if not (math.isfinite(float(sigma_trg)) and float(sigma_trg) >= 0.0 and math.isfinite(float(clip_trg)) and float(clip_trg) >= 0.0):
         raise ValueError(f"TD3 learner group: sigma_trg = {sigma_trg}, clip_trg = {clip_trg} must be finite and >= 0")
     is_policy_step(0, policy_delay)                          # (refuses d < 1)
@@ -283,13 +267,11 @@ class TD3LearnerGroup(G.LearnerGroup):
             raise NotImplementedError(f"TD3 learner group: batch {a0.batch} > {BP}: the twin-critic update holds one {BP}-column pass")
         tl = self._use_tiled()
         t3 = self._td3_args()
-        tick = self.updates if tick is None else tick
         w = C.byref(self.w2t_struct()) if tl else None
         w2 = C.c_void_p(self.slab.data_ptr() + 4 * self.layout["w2t_critic2"][0]) if tl else None
         _capi.check(self.L.shems_td3_group_update_tp(C.byref(t3), C.byref(r0), C.byref(g), w, w2, self._hp_ptr(), self._hold_ptr(),
-                                                     len(self.rings[0]), self.rng_seed, int(tick) & 0xFFFFFFFF, a0.eta_crit, a0.bp_critic[0],
-                                                     a0.bp_critic[1], a0.eta_act, a0.bp_actor[0], a0.bp_actor[1], 1 if policy else 0,
-                                                     1 if self.store_grad else 0, self._stream()))
+                                                     len(self.rings[0]), self.rng_seed, D.tick32(tick, self.updates), *a0._adam_c, *a0._adam_a,
+                                                     1 if policy else 0, 1 if self.store_grad else 0, self._stream()))
         if tl:
             self._flux_valid = False
         self._advance_learners(critic=True, actor=policy, counter="updates")
@@ -304,14 +286,8 @@ class TD3Agent(D.Agent):
 
     def __init__(self, seed=1231, sigma_trg=SIGMA_TRG, clip_trg=CLIP_TRG, policy_delay=POLICY_DELAY, critic2_seed=None, **kw):
         hidden = tuple(int(h) for h in kw.get("hidden", (D.L1, D.L2)))
-        if kw.get("wide") or D.is_wide(hidden):
-            raise NotImplementedError(f"TD3: hidden sizes {hidden} run layer by layer (shems_wide_*), which has no twin-critic update")
-        if kw.get("noise_type", "gn") == "pn":
-            raise NotImplementedError("TD3: parameter noise (noise_type = 'pn') adapts between getData and the updates of replay(); "
-                                      "the TD3 update is one call")
-        if kw.get("tensors") is not None:
-            raise NotImplementedError("TD3: a learner of a learner group keeps its state in the group's slab; twin critics for a group are "
-                                      "td3.TD3LearnerGroup")
+        D.refuse("td3.init", dict(wide=kw.get("wide") or D.is_wide(hidden), hidden=hidden, pn=kw.get("noise_type", "gn") == "pn",
+                                  slab=kw.get("tensors") is not None))
         if not (math.isfinite(float(sigma_trg)) and float(sigma_trg) >= 0.0 and math.isfinite(float(clip_trg)) and float(clip_trg) >= 0.0):
             raise ValueError(f"TD3: sigma_trg = {sigma_trg}, clip_trg = {clip_trg} must be finite and >= 0")
         is_policy_step(0, policy_delay)                      # (refuses d < 1)
@@ -355,14 +331,14 @@ class TD3Agent(D.Agent):
     # ---- refused paths ----
     def use_tiled(self, on=True):
         if on:
-            raise NotImplementedError("TD3: the tiled working layout (use_tiled) holds the actor's and critic 1's layer-2 state only")
+            raise NotImplementedError(D.TD3_NEVER["use_tiled"])
         return super().use_tiled(False)
 
     def evaluate(self, ring, tick=None, tau=None):
-        raise NotImplementedError("TD3: evaluate() is the critic-only update of ONE critic; the twin critics have none")
+        raise NotImplementedError(D.TD3_NEVER["evaluate"])
 
     def enable_data_parallel(self, dist, native=None):
-        raise NotImplementedError("TD3: data-parallel replicas do not exchange the second critic's gradient")
+        raise NotImplementedError(D.TD3_NEVER["enable_data_parallel"])
 
     def set_params(self, actor=None, critic=None, sync_targets=True, critic2=None):
         """As Agent.set_params, and critic2: a flat Flux-layout vector of this learner's critic size (padded here) or of the (250, 500)
@@ -385,41 +361,22 @@ class TD3Agent(D.Agent):
                        p(self.ws2), p(self.losses2), self.sigma_trg, self.clip_trg)
 
     def replay_given(self, ring, idx, weights):
-        raise NotImplementedError("TD3: replay_given is the single-critic update (shems_ddpg_update_given); the twin critics have none")
+        raise NotImplementedError(D.TD3_NEVER["replay_given"])
 
     def replay(self, ring, tick=None, exclude=None, publish=None, update_policy=None):
         """One TD3 update from `ring` (shems_td3_update).  update_policy: None = the schedule, is_policy_step(self.updates,
         self.policy_delay).  bp_critic advances on every update, bp_actor on policy steps; `updates` counts updates.  With `bc` set
         (ddpg.BC) the policy step's actor loss is the behaviour-regularised one (shems_td3_update_bc)."""
-        if isinstance(ring, D.PrioritizedRing):
-            raise NotImplementedError("TD3: the twin-critic update has no weighted head; a PrioritizedRing belongs to ddpg.Agent")
-        if exclude is not None or publish is not None:
-            raise NotImplementedError("TD3: the pipelined forms of replay() (exclude / publish) belong to shems_ddpg_update")
-        if self.batch > self.MAX_PASS_BATCH:
-            raise NotImplementedError(f"TD3: BATCH_SIZE = {self.batch}; the twin-critic update holds at most {self.MAX_PASS_BATCH} columns")
-        if self.noise_type == "pn":
-            raise NotImplementedError("TD3: parameter noise (noise_type = 'pn')")
-        if self.sync.world > 1:
-            raise NotImplementedError("TD3: data-parallel replicas do not exchange the second critic's gradient")
-        if self.tiled_mode or self._tiled_current:
-            raise NotImplementedError("TD3: the tiled working layout (use_tiled)")
-        if getattr(self, "_before_param_write", None) is not None:
-            raise NotImplementedError("TD3: a learner of a learner group keeps its own working layout")
+        D.refuse("td3", self._facts(ring, exclude, publish))
         self._same_device(None, ring)
         policy = is_policy_step(self.updates, self.policy_delay) if update_policy is None else bool(update_policy)
-        a = self._td3_args()
-        rs = ring.struct()
-        tick = self.updates if tick is None else tick
+        a, rs = self._td3_args(), ring.struct()
         if self.bc is not None:
             # the policy step's actor loss is the behaviour-regularised one (shems_td3_update_bc); off a policy step nothing of it runs
             b = self.bc.struct(self.bc_out.data_ptr())
-            _capi.check(_capi.declare_bc().shems_td3_update_bc(C.byref(a), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF,
-                                                               self.eta_crit, self.bp_critic[0], self.bp_critic[1], self.eta_act,
-                                                               self.bp_actor[0], self.bp_actor[1], 1 if policy else 0, C.byref(b),
-                                                               self._stream()))
-            self._advance(critic=True, actor=policy, counter="updates")
-            return
-        _capi.check(self.L.shems_td3_update(C.byref(a), C.byref(rs), len(ring), self.rng_seed, int(tick) & 0xFFFFFFFF, self.eta_crit,
-                                            self.bp_critic[0], self.bp_critic[1], self.eta_act, self.bp_actor[0], self.bp_actor[1],
-                                            1 if policy else 0, self._stream()))
+            _capi.check(_capi.declare_bc().shems_td3_update_bc(C.byref(a), C.byref(rs), *self._sample(ring, tick), *self._adam_c, *self._adam_a,
+                                                               1 if policy else 0, C.byref(b), self._stream()))
+        else:
+            _capi.check(self.L.shems_td3_update(C.byref(a), C.byref(rs), *self._sample(ring, tick), *self._adam_c, *self._adam_a,
+                                                1 if policy else 0, self._stream()))
         self._advance(critic=True, actor=policy, counter="updates")

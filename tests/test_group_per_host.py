@@ -222,3 +222,21 @@ def test_the_twin_is_per_ref_with_the_groups_key():
     # the sampler edge cases of per_cases that fit the group's slabs are all there
     names = [n for n, _ in K.sampler_edge_cases()]
     assert len(names) == 31 and "beta0" in names and "fresh-wrap" in names and "zeros-1000" in names and all("24000" not in n for n in names)
+
+
+def test_group_refusals_word_for_word_and_in_order():
+    """The walk a prioritized group shares with a TD3 group (tests/util.py holds the rows), then its own numbers."""
+    G = _feature()
+    rows = U.group_variant_refusal_rows("prioritized learner group", "prioritized update", "weighted head", "shems_ddpg_group_update_per_tp",
+                         " (the rings advance in lockstep)", "the sampler draws at most 128 columns")
+    cap = "prioritized learner group: capacity 262145 > 262144: a learner's sampler workgroup keeps every block sum in LDS"
+    own = [(dict(capacity=262145), NotImplementedError, cap), (dict(alpha=-0.1), ValueError, "prioritized learner group: alpha = -0.1 must be finite and >= 0"),
+           (dict(beta=1.5), ValueError, "prioritized learner group: beta = 1.5 must be in [0, 1]"),
+           (dict(hparams=[{"hidden": (300, 600)}], capacity=262145), NotImplementedError, rows[7][2]),           # the walk before the own numbers
+           (dict(capacity=262145, alpha=-0.1), NotImplementedError, cap),
+           (dict(alpha=-0.1, beta=1.5), ValueError, "prioritized learner group: alpha = -0.1 must be finite and >= 0")]
+    for kw, exc, message in rows + own:
+        with pytest.raises(exc) as ei:
+            G.per_group_refusals(**kw)
+        assert str(ei.value) == message, kw
+    assert G.per_group_refusals() is None and G.per_group_refusals(form="throughput", hparams=[{"batch": 128, "hidden": (250, 500)}]) is None

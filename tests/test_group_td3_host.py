@@ -166,3 +166,18 @@ def test_the_record_case_meets_its_conditions_on_the_twin():
         for tick in K.TICKS:
             K.assert_coverage(l, tick, rec["batch"])
             assert K.initial_ties(l, tick, rec["batch"]) == []
+
+
+def test_group_refusals_word_for_word_and_in_order():
+    T = _feature()
+    rows = U.group_variant_refusal_rows("TD3 learner group", "twin-critic update", "twin-critic update", "shems_td3_group_update_tp", "",
+                      "the twin-critic update holds one 128-column pass")
+    own = [(dict(sigma_trg=-0.5), ValueError, "TD3 learner group: sigma_trg = -0.5, clip_trg = 0.5 must be finite and >= 0"),
+           (dict(policy_delay=0), ValueError, "policy_delay = 0: the actor moves every 1 or more updates"),
+           (dict(hparams=[{"hidden": (300, 600)}], sigma_trg=-0.5), NotImplementedError, rows[7][2]),            # the walk before the own numbers
+           (dict(sigma_trg=-0.5, policy_delay=0), ValueError, "TD3 learner group: sigma_trg = -0.5, clip_trg = 0.5 must be finite and >= 0")]
+    for kw, exc, message in rows + own:
+        with pytest.raises(exc) as ei:
+            T.group_refusals(**kw)
+        assert str(ei.value) == message, kw
+    assert T.group_refusals() is None and T.group_refusals(form="throughput", hparams=[{"batch": 128, "hidden": (250, 500)}]) is None

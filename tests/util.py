@@ -215,3 +215,25 @@ def obs_of_rows(tab, idx, soc_b):
     h_cos, h_sin, season)."""
     rows = tab[np.asarray(idx) - 1]
     return np.concatenate([np.asarray(soc_b, np.float32)[:, None], rows[:, [1, 0]], rows[:, 2:]], 1).astype(np.float32)
+
+
+# ------------------------------------------ the throughput group's variants --
+def group_variant_refusal_rows(name, update, head, entry, mem_tail, batch_words):
+    """The rows the two variants of the throughput group share (td3.group_refusals, group.per_group_refusals), every message in full: one
+    per fault, then pairs of faults adjacent in the walk's order, the earlier one reported."""
+    form = f"{name}: form={{!r}} has no {head}; the group runs the throughput form ({entry}) whatever its count"
+    ou = f"{name}: Ornstein-Uhlenbeck noise runs on the *_x entry points, which have no {update}"
+    hid = f"{name}: hidden= belongs to form='wide', which has no {update}"
+    mem = f"{name}: hparams[{{}}]: per-learner mem_size runs on the *_x entry points, which have no {update}{mem_tail}"
+    bat = f"{name}: hparams[{{}}]: batch 129 > 128: {batch_words}"
+    wid = f"{name}: hparams[{{}}]: hidden (300, 600) is wider than (250, 500): the wide form has no {update}"
+    NI = NotImplementedError
+    return [(dict(form="latency"), NI, form.format("latency")), (dict(form="wide"), NI, form.format("wide")),
+            (dict(form="fast"), ValueError, "form must be 'throughput'"), (dict(noise_type="ou"), NI, ou), (dict(hidden=(300, 600)), NI, hid),
+            (dict(hparams=[{"mem_size": 64}, {}]), NI, mem.format(0)), (dict(hparams=[{}, {"batch": 129}]), NI, bat.format(1)),
+            (dict(hparams=[{"hidden": (300, 600)}, {}]), NI, wid.format(0)),
+            (dict(form="wide", noise_type="ou"), NI, form.format("wide")), (dict(form="fast", noise_type="ou"), ValueError, "form must be 'throughput'"),
+            (dict(noise_type="ou", hidden=(300, 600)), NI, ou), (dict(hidden=(300, 600), hparams=[{"mem_size": 64}]), NI, hid),
+            (dict(hparams=[{"mem_size": 64, "batch": 129}]), NI, mem.format(0)), (dict(hparams=[{"batch": 129, "hidden": (300, 600)}]), NI, bat.format(0)),
+            (dict(hparams=[{"hidden": (300, 600)}, {"mem_size": 64}]), NI, wid.format(0)),       # (record by record: learner 0's last check first)
+            (dict(hparams=[(), {"batch": 129}]), NI, bat.format(1))]                                # (a record that is no mapping is passed over)

@@ -2,7 +2,7 @@
 replay() -- fused (one C call), split (the data-parallel call sequence without collectives) and split with real RCCL all-reduce calls on a
 one-rank group (identity, but the full host path of torch.distributed).  If the enqueue time exceeds the GPU time of a step, the host is the bound."""
 import os, sys, time, importlib
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.distributed as dist
 PKG = "master-thesis-deep-reinforcement-learning-ddpg-in-home-energy-management_amd"
 S = importlib.import_module(PKG); D = importlib.import_module(PKG + ".ddpg"); P = importlib.import_module(PKG + ".parallel")
